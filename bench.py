@@ -70,7 +70,30 @@ def parse():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="rank launch + process group + barrier / max-over-ranks + the rank-0 JSON line, NO compute and value = null "
                          "(lets the CPU test suite exercise `--gpus N` without a GPU; never a bench result)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the top-k lists of the last timed step as DIR/scores.npy (float32), DIR/rows.npy and "
+                         "DIR/query_index.npy (float64), so that two builds can be compared output for output on the same seeded inputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(folder, scores, rows):
+    """--dump-outputs: what a caller of the timed step receives, scores [nq, k] and global corpus rows [nq, k] (float64: exact below 2^53), plus the
+    query numbers they belong to.  A result larger than DUMP_MAX_BYTES is cut to a fixed, seeded sample of query rows (query_index says which)."""
+    s = np.asarray(scores, dtype=np.float32)
+    r = np.asarray(rows).astype(np.float64)
+    q = np.arange(s.shape[0])
+    per_query = s.shape[1] * (4 + 8) + 8
+    if s.shape[0] * per_query > DUMP_MAX_BYTES - 4096:               # 4 KiB: the three .npy headers
+        q = np.sort(np.random.default_rng(0).choice(s.shape[0], (DUMP_MAX_BYTES - 4096) // per_query, replace=False))
+    os.makedirs(folder, exist_ok=True)
+    for name, a in (("scores", s[q]), ("rows", r[q]), ("query_index", q.astype(np.float64))):
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def launch_ranks(args) -> int:
@@ -561,20 +584,22 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     coarse_log.clear()
+    last = None                                                      # (scores, rows) of the last timed step
     if use_blocks:
         for b0 in range(0, args.steps, world):
-            block_of_steps(b0, min(world, args.steps - b0))
+            last = block_of_steps(b0, min(world, args.steps - b0))[-1]
             coarse_ms.append(index.stats()["last_coarse_ms"])
     for i in range(0 if use_blocks else args.steps):
         if use_async:
             step_async(i)
         else:
-            step()
+            last = step()
             coarse_ms.append(index.stats()["last_coarse_ms"])
     if use_async:
         drain()
         coarse_ms = list(coarse_log)
         assert len(coarse_ms) == args.steps
+        last = (pin_s[(args.steps - 1) & 1], pin_i[(args.steps - 1) & 1])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -583,6 +608,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
 
     enc_info = None
     if encoder is not None:

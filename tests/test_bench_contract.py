@@ -48,11 +48,16 @@ def test_committed_bench_line_has_the_contract_fields():
         assert r.get("traffic_range_over_boxes") is None or r["traffic_range_over_boxes"][0] <= r["traffic"] <= r["traffic_range_over_boxes"][1]
 
 
-def test_bench_defaults_are_the_metric_configuration():
+def _bench_module():
     import importlib.util
-    import sys
     spec = importlib.util.spec_from_file_location("kr_bench", os.path.join(REPO, "bench.py"))
     m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+    return m
+
+
+def test_bench_defaults_are_the_metric_configuration():
+    import sys
+    m = _bench_module()
     argv, sys.argv = sys.argv, ["bench.py"]
     try:
         a = m.parse()
@@ -92,15 +97,75 @@ import pytest
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("split,steps", [("batch", "3"), ("queries", "2")])
-def test_bench_gpus_2_real_step_on_one_box(split, steps):
+def test_bench_gpus_2_real_step_on_one_box(split, steps, tmp_path):
     """The real N = 2 step (row shards, all-gather of query vectors and of per-shard top-k, device merge) started by `python bench.py --gpus 2` itself, under
     both encode schedules: "batch" (rank r encodes the whole batch of every 2nd step; 3 steps = one full and one partial block) and "queries" (every rank
-    encodes half of every batch).  The two ranks share the box's one GPU, so the collective backend is gloo (RCCL wants one device per rank)."""
+    encodes half of every batch).  The two ranks share the box's one GPU, so the collective backend is gloo (RCCL wants one device per rank).
+    --dump-outputs writes rank 0's merged lists of the last step: rows from both shards, scores in descending order."""
+    import numpy as np
     p, lines = _run_bench(["--gpus", "2", "--total-rows", "300000", "--queries", "256", "--steps", steps, "--warmup", "1", "--passages", "64",
-                           "--no-cpu-baseline", "--encode-split", split], {"KIRAG_BENCH_BACKEND": "gloo"}, timeout=900)
+                           "--no-cpu-baseline", "--encode-split", split, "--dump-outputs", str(tmp_path)], {"KIRAG_BENCH_BACKEND": "gloo"}, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["rows_per_gpu"] == 150000
     st = d["search_stats"]
     assert st["certified"] + st["fallback"] == st["queries"]
+    s, r = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "rows.npy")
+    assert s.dtype == np.float32 and s.shape == r.shape == (256, 100) and np.all(np.diff(s, axis=1) <= 0)
+    assert np.all((r >= 0) & (r < 300000)) and (r < 150000).any() and (r >= 150000).any()
+
+
+def test_steps_below_one_are_refused():
+    p, lines = _run_bench(["--steps", "0", "--plumbing-only"])
+    assert p.returncode != 0 and not lines and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_the_lists_and_samples_above_the_cap(tmp_path):
+    """bench.dump_outputs: scores float32 and rows / query numbers float64, every query while the files fit in 64 MB, above that the same seeded
+    sample of queries on every call."""
+    import numpy as np
+    import torch
+    m = _bench_module()
+    rng = np.random.default_rng(1)
+    s = -np.sort(-rng.standard_normal((7, 5)).astype(np.float32), axis=1)
+    r = rng.integers(0, 5_000_000, (7, 5))
+    m.dump_outputs(str(tmp_path / "small"), torch.from_numpy(s), torch.from_numpy(r))
+    got = {f: np.load(tmp_path / "small" / (f + ".npy")) for f in ("scores", "rows", "query_index")}
+    assert got["scores"].dtype == np.float32 and got["rows"].dtype == np.float64 and got["query_index"].dtype == np.float64
+    assert np.array_equal(got["scores"], s) and np.array_equal(got["rows"], r) and np.array_equal(got["query_index"], np.arange(7))
+
+    nq, k = 60_000, 100                                            # 72 MB of lists: over the cap
+    s = np.broadcast_to(np.arange(nq, dtype=np.float32)[:, None], (nq, k))
+    r = np.broadcast_to(np.arange(nq, dtype=np.int64)[:, None] * 3, (nq, k))
+    for name in ("a", "b"):
+        m.dump_outputs(str(tmp_path / name), s, r)
+    files = [tmp_path / n / (f + ".npy") for n in ("a", "b") for f in ("scores", "rows", "query_index")]
+    assert sum(os.path.getsize(f) for f in files[:3]) <= m.DUMP_MAX_BYTES
+    sa, ra, qa = (np.load(f) for f in files[:3])
+    sb, rb, qb = (np.load(f) for f in files[3:])
+    assert np.array_equal(qa, qb) and np.array_equal(sa, sb) and np.array_equal(ra, rb)
+    assert 50_000 < len(qa) < nq and np.all(np.diff(qa) > 0)
+    assert np.array_equal(sa[:, 0], qa) and np.array_equal(ra[:, 0], qa * 3)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_lists(tmp_path):
+    """--dump-outputs at N = 1 writes the top-k lists of the last timed step: the enqueue-only step and the blocking one (--sync-search) write the same
+    lists bit for bit (the search is exact), a second run with the same arguments writes them again, and search-only queries (near-duplicates of corpus
+    rows 0 .. nq - 1) find their own row first."""
+    import numpy as np
+    small = ["--total-rows", "300000", "--queries", "256", "--passages", "64", "--warmup", "1",
+             "--no-cpu-baseline", "--no-latency", "--no-entry-point", "--no-surface"]
+    runs = {"async": ["--steps", "3"], "again": ["--steps", "2"], "sync": ["--steps", "2", "--sync-search"], "search_only": ["--steps", "2", "--no-encoder"]}
+    out = {}
+    for name, extra in runs.items():
+        p, lines = _run_bench(small + extra + ["--dump-outputs", str(tmp_path / name)], timeout=600)
+        assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
+        out[name] = [np.load(tmp_path / name / (f + ".npy")) for f in ("scores", "rows", "query_index")]
+    s, r, q = out["async"]
+    assert s.dtype == np.float32 and r.dtype == np.float64 and s.shape == r.shape == (256, 100) and np.array_equal(q, np.arange(256))
+    assert np.all(np.diff(s, axis=1) <= 0) and np.all((r >= 0) & (r < 300000))
+    for name in ("again", "sync"):
+        assert np.array_equal(out[name][0].view(np.uint32), s.view(np.uint32)) and np.array_equal(out[name][1], r), name
+    assert np.array_equal(out["search_only"][1][:, 0], np.arange(256))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # k_rerank average duration under rocprofv3 for two builds of the library (bash tools/rerank_ab.sh libA libB)
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 for dist in gaussian e5like; do
 for lib in "$@"; do
   export KIRAG_AMD_LIB=$R/$lib

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel-trace stats of REPS forwards of one batch shape (bash tools/shape_trace.sh B S [reps]) -> gpurun_out/shape_B_S/
+R=$(cd "$(dirname "$0")/.." && pwd); B=$1; S=$2; N=${3:-10}
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT; B=$1; S=$2; N=${3:-10}
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/shape_${B}_${S} -- python3 $R/tools/one_shape.py $B $S $N > /dev/null 2>&1
 python3 - <<PY
 import csv, glob

@@ -3,7 +3,7 @@
 an address range that is unmapped, freed with hipMemAddressFree, reserved again (same addresses) and mapped to new physical chunks is read by kernels
 through stale translations.  `KIRAG_AMD_DEBUG_FREE_VA=1 python tools/vmm_va_reuse_repro.py plain` shows it (self-matches of rows 0..4 are not found: the scan kernels
 do not see the rows a copy engine reads back correctly); without the variable the library retires the range instead and the search is right."""
-import os, sys, time; sys.path.insert(0, "/root/repo")
+import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from kirag_amd.retriever.index import FlatIPIndex
 def unit(n, d): return torch.nn.functional.normalize(torch.randn(n, d, device="cuda"), dim=1)
