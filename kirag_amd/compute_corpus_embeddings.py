@@ -23,6 +23,7 @@ import torch
 
 from . import feed, tensor_pickle
 from .collators import COLLATOR_MAP
+from .retriever.formats import shard_range
 from .retriever.retrievers import InBatchRetriever
 from .utils import prefetch_map, to_device
 
@@ -52,11 +53,6 @@ def setup_parser(argv=None):
     parser.add_argument("--no_embedding_files", action="store_true",
                         help="do not write corpus_embeddings_*.pkl / passage_id_list_*.pkl (streamed encode straight into a resident index shard)")
     return parser.parse_args(argv)
-
-
-def shard_range(n: int, rank: int, world: int):
-    per = (n + world - 1) // world
-    return min(rank * per, n), min((rank + 1) * per, n)
 
 
 def effective_cpus() -> int:

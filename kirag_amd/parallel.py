@@ -58,7 +58,8 @@ class ShardedSearcher:
         self.collective = collective
         self.exchange_first = bool(exchange_first)
         self._comm = None
-        self._outstanding = []
+        self._dev_key = self._tk_key = None
+        self._outstanding = []       # ring slots of the deferred searches not finished yet, oldest first
         self.redone = 0              # deferred batches whose exchange was repeated because some rank re-answered queries (finish_deferred)
 
     def _kr_comm(self, dev):
@@ -128,9 +129,7 @@ class ShardedSearcher:
         j = len(self._outstanding)
         if j >= len(self._slots):
             raise RuntimeError("too many deferred searches outstanding: call finish_deferred()")
-        mine, loc = self._slots[j]
-        ids = mine[:nq * k * 8].view(torch.int64).view(nq, k)
-        sc = mine[nq * k * 8:nq * k * 12].view(torch.float32).view(nq, k)
+        _, loc, _, sc = self._slots[j]
         if self.exchange_first and self.world > 1 and self.EXCHANGE_FIRST_MIN_NQ <= nq <= 1024:     # the split search takes one block of at most 1024 queries
             # coarse scan -> all-gather of the shards' k best coarse scores (+ error bound) per query -> the global bound -> re-rank above it: enqueue only
             tk, tk_all, theta = self._topk_bufs(nq, k, dev)
@@ -140,12 +139,9 @@ class ShardedSearcher:
             self.index.search_rerank_async(theta, sc, loc)       # may return fewer than k rows of this shard: (-inf, -1) at the tail
         else:
             self.index.search_async(q, k, sc, loc)               # local rows; finish() may re-write rows of loc / sc for uncertified queries
-        self._global_rows(loc, ids)
-        self._exchange(mine, sc, ids, nq, k, dev)
-        ps, pi = self._ring[j]
-        ps.copy_(self._out_s, non_blocking=True); pi.copy_(self._out_i, non_blocking=True)
-        self._outstanding.append((q, k, nq, dev, j))
-        return ps, pi
+        self._exchange_slot(j)
+        self._outstanding.append(j)
+        return self._ring[j]
 
     def finish_deferred(self):
         """Finishes every search enqueued by ``search_deferred`` since the last call (a collective: every rank calls it with the same number of
@@ -155,10 +151,10 @@ class ShardedSearcher:
         after the all-reduce (nobody is left blocking in it) and the searcher is usable again."""
         import torch
         import torch.distributed as dist
-        out = [self._ring[j] for (_, _, _, _, j) in self._outstanding]
+        out = [self._ring[j] for j in self._outstanding]
         if not self._outstanding:
             return out
-        dev = self._outstanding[0][3]
+        dev = self._dev_key[3]
         n_out = len(self._outstanding)
         # A rank whose local finish fails (a HIP error in passes 2 / 3, or fewer certificate records than searches) must still take part in the collective
         # below, or the other ranks block in it forever (ADVICE r04): the failure travels as code 2 in the all-reduced tensor and every rank raises after it.
@@ -182,16 +178,9 @@ class ShardedSearcher:
             if any(r >= 2 for r in redo):
                 raise RuntimeError("finish_deferred: another rank failed to finish its local searches; this block's results are not usable")
             self.redone += sum(1 for r in redo if r)
-            for (q, k, nq, dev, j), r in zip(self._outstanding, redo):
-                if not r:
-                    continue
-                mine, loc = self._slots[j]
-                ids = mine[:nq * k * 8].view(torch.int64).view(nq, k)
-                sc = mine[nq * k * 8:nq * k * 12].view(torch.float32).view(nq, k)
-                self._global_rows(loc, ids)
-                self._exchange(mine, sc, ids, nq, k, dev)
-                ps, pi = self._ring[j]
-                ps.copy_(self._out_s, non_blocking=True); pi.copy_(self._out_i, non_blocking=True)
+            for j, r in zip(self._outstanding, redo):
+                if r:
+                    self._exchange_slot(j)
             if any(redo):
                 torch.cuda.current_stream(dev).synchronize()
         finally:
@@ -245,22 +234,29 @@ class ShardedSearcher:
     def _topk_bufs(self, nq: int, k: int, dev):
         import torch
         key = (nq, k, self.world, dev)
-        if getattr(self, "_tk_key", None) != key:
+        if self._tk_key != key:
             self._tk = torch.empty((nq, k + 1), dtype=torch.float32, device=dev)
             self._tk_all = torch.empty((self.world * nq, k + 1), dtype=torch.float32, device=dev)
             self._theta = torch.empty((nq,), dtype=torch.float32, device=dev)
             self._tk_key = key
         return self._tk, self._tk_all, self._theta
 
+    @staticmethod
+    def _block_views(buf, nq: int, k: int):
+        """(ids int64 [..., nq, k], scores fp32 [..., nq, k]) of exchange blocks [..., bytes] laid out [ids | scores]: one all-gather moves both"""
+        import torch
+        lead = tuple(buf.shape[:-1])
+        return (buf[..., :nq * k * 8].view(torch.int64).view(*lead, nq, k), buf[..., nq * k * 8:nq * k * 12].view(torch.float32).view(*lead, nq, k))
+
     def _buffers(self, nq: int, k: int, dev):
         """persistent device / pinned buffers for (nq, k): this rank's block of the gather buffer, the gathered blocks, the merged result, and one
-        (block, local rows) pair + one pinned result pair per deferred search that may be outstanding"""
+        (block, local rows, ids view, scores view) slot + one pinned result pair per deferred search that may be outstanding"""
         import torch
         W = self.world
         block = (nq * k * 12 + 15) // 16 * 16                    # bytes per rank: multiple of 16 so both strides are whole elements
         key = (nq, k, W, dev)
-        if getattr(self, "_dev_key", None) != key:
-            if getattr(self, "_outstanding", None):
+        if self._dev_key != key:
+            if self._outstanding:
                 raise RuntimeError("finish_deferred() before searching with another shape")
             self._mine = torch.empty(block, dtype=torch.uint8, device=dev)
             self._all = torch.empty(W * block, dtype=torch.uint8, device=dev)
@@ -269,12 +265,20 @@ class ShardedSearcher:
             self._pin_s = torch.empty((nq, k), dtype=torch.float32, pin_memory=True)
             self._pin_i = torch.empty((nq, k), dtype=torch.int64, pin_memory=True)
             ring = min(max(self.RING, W), self.PEND_MAX)          # never more than the index keeps outstanding (a 17th kr_index_search_async finishes the oldest itself)
-            self._slots = [(torch.empty(block, dtype=torch.uint8, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev)) for _ in range(ring)]
+            mines = [torch.empty(block, dtype=torch.uint8, device=dev) for _ in range(ring)]
+            self._slots = [(m, torch.empty((nq, k), dtype=torch.int64, device=dev)) + self._block_views(m, nq, k) for m in mines]
             self._ring = [(torch.empty((nq, k), dtype=torch.float32, pin_memory=True), torch.empty((nq, k), dtype=torch.int64, pin_memory=True))
                           for _ in range(ring)]
-            self._outstanding = []
             self._dev_key = key
-        return block
+
+    def _exchange_slot(self, j: int):
+        """deferred search j (its local list in slot j): global rows, exchange, D2H of the result into pinned ring slot j — enqueue only"""
+        nq, k, _, dev = self._dev_key
+        mine, loc, ids, sc = self._slots[j]
+        self._global_rows(loc, ids)
+        self._exchange(mine, sc, ids, nq, k, dev)
+        ps, pi = self._ring[j]
+        ps.copy_(self._out_s, non_blocking=True); pi.copy_(self._out_i, non_blocking=True)
 
     def _exchange(self, mine, sc, ids, nq: int, k: int, dev):
         """all-gather of this rank's (ids | scores) block + device merge of the W lists into _out_s / _out_i: enqueue only"""
@@ -299,11 +303,10 @@ class ShardedSearcher:
         import torch
         import torch.distributed as dist
         W = self.world
-        if getattr(self, "_outstanding", None):
+        if self._outstanding:
             raise RuntimeError("finish_deferred() before a blocking search")
-        block = self._buffers(nq, k, dev)
-        ids = self._mine[:nq * k * 8].view(torch.int64).view(nq, k)
-        sc = self._mine[nq * k * 8:nq * k * 12].view(torch.float32).view(nq, k)
+        self._buffers(nq, k, dev)
+        ids, sc = self._block_views(self._mine, nq, k)
         if kl == k and hasattr(self.index, "search_into"):
             self.index.search_into(q, k, sc, ids)
         else:                                                    # a shard with fewer than k rows (or a CPU stand-in index): pad with (-inf, -1)
@@ -316,10 +319,8 @@ class ShardedSearcher:
         if W * k > self.DEVICE_MERGE_MAX:
             # beyond the device merge's LDS capacity (kr_topk_merge_device: nshards * k <= 8192, e.g. 16 shards x k = 1024): merge on the host
             dist.all_gather_into_tensor(self._all, self._mine, group=self.group)
-            host = self._all.cpu().numpy().reshape(W, block)
-            ids_h = np.ascontiguousarray(host[:, :nq * k * 8]).view(np.int64).reshape(W, nq, k)
-            sc_h = np.ascontiguousarray(host[:, nq * k * 8:nq * k * 12]).view(np.float32).reshape(W, nq, k)
-            return merge_topk(sc_h, ids_h, k)
+            ids_h, sc_h = self._block_views(self._all.cpu().view(W, -1), nq, k)
+            return merge_topk(sc_h.numpy(), ids_h.numpy(), k)
         self._exchange(self._mine, sc, ids, nq, k, dev)
         self._pin_s.copy_(self._out_s, non_blocking=True); self._pin_i.copy_(self._out_i, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()

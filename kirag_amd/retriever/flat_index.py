@@ -29,6 +29,7 @@ class FlatIPIndex:
         _lib.check(lib.kr_index_create(self.d, 0, {"bf16": 0, "f16": 1}[coarse_dtype], self.device, C.byref(h)))
         self._h = h
         self._lib = lib
+        self._pending = []      # keep-alive of the tensors of outstanding asynchronous calls, oldest first (one entry per C-side call)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -63,10 +64,7 @@ class FlatIPIndex:
         return None
 
     def add(self, x) -> None:
-        if isinstance(x, np.ndarray):
-            x = np.ascontiguousarray(x, dtype=np.float32)
-        else:
-            x = x.detach().float().contiguous()
+        x = self._contiguous(x)
         if x.ndim != 2 or x.shape[1] != self.d:
             raise ValueError(f"expected [n,{self.d}] embeddings, got {tuple(x.shape)}")
         p, keep = self._ptr(x)
@@ -86,18 +84,27 @@ class FlatIPIndex:
         _lib.check(self._lib.kr_index_prepare(self._h, int(nq), k, stream))
         self._small_out(1, 1)          # the pinned result / query scratch of small calls (three pinned allocations: 0.25 ms of a first 0.2-ms search otherwise)
 
-    def search(self, q, k: int, mode: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        """(scores float32 [nq,k] descending, internal rows int64 [nq,k]) — faiss's (D, I)."""
-        if isinstance(q, np.ndarray):
-            q = np.ascontiguousarray(q, dtype=np.float32)
-        else:
-            q = q.detach().float().contiguous()
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [nq,{self.d}] queries, got {tuple(q.shape)}")
+    def _check_queries(self, q, async_call: Optional[str] = None, max_nq: Optional[int] = None) -> int:
+        """nq of a [nq, d] block of queries (at least one and at most ``max_nq`` when given); ValueError otherwise.  The enqueue-only calls
+        (``async_call``: the caller's name) take a contiguous float32 CUDA tensor only."""
+        if async_call is not None:
+            import torch
+            if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()):
+                raise ValueError(f"{async_call} needs a contiguous float32 CUDA tensor of queries")
+        if q.ndim != 2 or q.shape[1] != self.d or (max_nq is not None and not 0 < q.shape[0] <= max_nq):
+            raise ValueError(f"expected [{'nq' if max_nq is None else f'1..{max_nq}'},{self.d}] queries, got {tuple(q.shape)}")
+        return int(q.shape[0])
+
+    def _check_k(self, k) -> int:
         k = int(k)
         if not 0 < k <= self.ntotal:
             raise ValueError(f"top_docs={k} must satisfy 0 < k <= ntotal={self.ntotal}")
-        nq = int(q.shape[0])
+        return k
+
+    def search(self, q, k: int, mode: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(scores float32 [nq,k] descending, internal rows int64 [nq,k]) — faiss's (D, I)."""
+        q = self._contiguous(q)
+        nq, k = self._check_queries(q), self._check_k(k)
         q = self._local(q)
         p, keep = self._ptr(q)
         self._pending = []          # kr_index_search drains the handle's outstanding calls (finish_search): their keep-alives go with them
@@ -116,8 +123,15 @@ class FlatIPIndex:
         _lib.check(self._lib.kr_index_search(self._h, p, nq, k, scores.ctypes.data, rows.ctypes.data, int(mode), self._stream(q)))
         return scores, rows
 
+    @staticmethod
+    def _contiguous(q):
+        """a numpy array or torch tensor as contiguous float32 (copied only when it is not already)"""
+        return np.ascontiguousarray(q, dtype=np.float32) if isinstance(q, np.ndarray) else q.detach().float().contiguous()
+
     def _local(self, q):
-        """queries as this index's device can read them in stream order: a CUDA tensor on another GPU is moved by torch (which orders the copy on both devices)"""
+        """Queries as this index's device can read them in stream order.  A CUDA tensor on ANOTHER GPU (the encoder on cuda:1, the index on LOCAL_RANK / 0) is
+        moved with ``.to()``: torch orders that copy behind the encoder's kernels on the source GPU's stream and before the search on this one's (ADVICE r05:
+        the C side would otherwise stage the foreign pointer with a hipMemcpyAsync on the index GPU's stream, which nothing orders after the encoder)."""
         if not isinstance(q, np.ndarray) and getattr(q, "is_cuda", False) and q.device.index != self.device:
             import torch
             return q.to(torch.device("cuda", self.device))
@@ -143,10 +157,8 @@ class FlatIPIndex:
     def search_into(self, q, k: int, scores_out, rows_out, mode: int = 0) -> None:
         """Same as ``search`` but writes into caller-provided torch tensors (host or device):
         ``scores_out`` float32 [nq,k], ``rows_out`` int64 [nq,k], both contiguous."""
-        q = q.detach().float().contiguous() if not isinstance(q, np.ndarray) else np.ascontiguousarray(q, dtype=np.float32)
-        nq, k = int(q.shape[0]), int(k)
-        if not 0 < k <= self.ntotal:
-            raise ValueError(f"top_docs={k} must satisfy 0 < k <= ntotal={self.ntotal}")
+        q = self._contiguous(q)
+        nq, k = self._check_queries(q), self._check_k(k)
         assert tuple(scores_out.shape) == (nq, k) and tuple(rows_out.shape) == (nq, k)
         assert scores_out.is_contiguous() and rows_out.is_contiguous()
         q = self._local(q)
@@ -160,19 +172,11 @@ class FlatIPIndex:
         call returns without waiting for the device; ``q`` (a contiguous float32 CUDA tensor), ``scores_out`` and ``rows_out`` must stay alive and
         untouched until ``finish()`` — which waits, re-answers the queries whose exactness certificate did not hold, and makes the results final."""
         import torch
-        if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()):
-            raise ValueError("search_async needs a contiguous float32 CUDA tensor of queries")
-        nq, k = int(q.shape[0]), int(k)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [nq,{self.d}] queries, got {tuple(q.shape)}")
-        if not 0 < k <= self.ntotal:
-            raise ValueError(f"top_docs={k} must satisfy 0 < k <= ntotal={self.ntotal}")
+        nq, k = self._check_queries(q, "search_async"), self._check_k(k)
         assert tuple(scores_out.shape) == (nq, k) and tuple(rows_out.shape) == (nq, k)
         assert scores_out.is_contiguous() and rows_out.is_contiguous() and scores_out.dtype == torch.float32 and rows_out.dtype == torch.int64
         if nq == 0:
             raise ValueError("search_async needs at least one query")              # (kr_index_search_async would return without an outstanding call)
-        if not isinstance(getattr(self, "_pending", None), list):
-            self._pending = []
         self._pending.append((q, scores_out, rows_out))                            # keep-alive until finish()
         _lib.check(self._lib.kr_index_search_async(self._h, int(q.data_ptr()), nq, k, int(scores_out.data_ptr()), int(rows_out.data_ptr()),
                                                    self._stream(q, scores_out, rows_out)))
@@ -182,16 +186,8 @@ class FlatIPIndex:
         ``topk_out`` (float32 CUDA tensor [nq, k + 1]) receives this shard's k best coarse scores per query and the query's error bound — what the shards
         exchange BEFORE anybody re-ranks (``ShardedSearcher``)."""
         import torch
-        if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()):
-            raise ValueError("search_coarse_async needs a contiguous float32 CUDA tensor of queries")
-        nq, k = int(q.shape[0]), int(k)
-        if q.ndim != 2 or q.shape[1] != self.d or not 0 < nq <= 1024:
-            raise ValueError(f"expected [1..1024,{self.d}] queries, got {tuple(q.shape)}")
-        if not 0 < k <= self.ntotal:
-            raise ValueError(f"top_docs={k} must satisfy 0 < k <= ntotal={self.ntotal}")
+        nq, k = self._check_queries(q, "search_coarse_async", max_nq=1024), self._check_k(k)
         assert tuple(topk_out.shape) == (nq, k + 1) and topk_out.is_cuda and topk_out.is_contiguous() and topk_out.dtype == torch.float32
-        if not isinstance(getattr(self, "_pending", None), list):
-            self._pending = []
         self._pending.append((q, topk_out))
         _lib.check(self._lib.kr_index_search_coarse_async(self._h, int(q.data_ptr()), nq, k, int(topk_out.data_ptr()), self._stream(q)))
 

@@ -13,6 +13,13 @@ from .flat_index import FlatIPIndex
 _IO_CHUNK_ROWS = 1 << 18
 
 
+def shard_range(n: int, rank: int, world: int):
+    """Rows [a, b) of rank ``rank``'s contiguous share of ``n`` rows split over ``world`` ranks: ``ceil(n / world)`` rows each, the last shares
+    shorter or empty.  The one split of the package: the embedding writers, both index readers and ``ShardedIndexer``."""
+    per = (n + world - 1) // world
+    return min(rank * per, n), min((rank + 1) * per, n)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # faiss flat-index file layout.  faiss is a third-party dependency of the reference (requirements.txt:10) and
 # its source is not on disk here: the layout below restates faiss 1.8 `write_index` for IndexFlat from its
@@ -51,12 +58,8 @@ def read_faiss_flat_ip(path: str, device: Optional[int] = None, coarse_dtype: st
         (nfloat,) = struct.unpack("<Q", f.read(8))
         if nfloat != n * d:
             raise ValueError(f"{path}: payload {nfloat} floats != ntotal*d = {n * d}")
-        a, b = 0, n
-        if row_range is not None:
-            rank, world = row_range
-            per = (n + world - 1) // world
-            a, b = min(rank * per, n), min((rank + 1) * per, n)
-            f.seek(a * d * 4, os.SEEK_CUR)
+        a, b = (0, n) if row_range is None else shard_range(n, *row_range)
+        f.seek(a * d * 4, os.SEEK_CUR)
         index = FlatIPIndex(d, device=device, coarse_dtype=coarse_dtype)
         index.reserve(b - a)
         for s in range(a, b, _IO_CHUNK_ROWS):
@@ -125,11 +128,7 @@ def read_native_shards(dir_path: str, device: Optional[int] = None, coarse_dtype
     if man.get("format") != "krshard-1":
         raise ValueError(f"{dir_path}: unknown shard format {man.get('format')!r}")
     n, d = int(man["ntotal"]), int(man["d"])
-    a, b = 0, n
-    if row_range is not None:
-        rank, world = row_range
-        per = (n + world - 1) // world
-        a, b = min(rank * per, n), min((rank + 1) * per, n)
+    a, b = (0, n) if row_range is None else shard_range(n, *row_range)
     index = FlatIPIndex(d, device=device, coarse_dtype=coarse_dtype)
     index.reserve(b - a)
     raw = man["coarse_dtype"] == coarse_dtype

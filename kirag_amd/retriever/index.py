@@ -32,16 +32,17 @@ logger = logging.getLogger()
 
 class Indexer(object):
 
-    def __init__(self, vector_sz, metric="inner_product", n_subquantizers=0, n_bits=8, device=None, coarse_dtype="bf16", faiss_padding=False):
+    def __init__(self, vector_sz, metric="inner_product", n_subquantizers=0, n_bits=8, device=None, coarse_dtype="bf16", faiss_padding=False, *,
+                 local_index=None):
         """``faiss_padding=True`` reproduces what the reference does when ``top_docs > ntotal`` instead of raising: faiss pads the result with
         label -1 and score -FLT_MAX, and ``index.py:49`` maps label -1 through ``index_id_to_db_id[-1]`` to the LAST id — recalled from faiss's
-        documented behaviour (not verifiable here: faiss is absent), so it stays opt-in."""
+        documented behaviour (not verifiable here: faiss is absent), so it stays opt-in.  ``local_index``: wrapped instead of a new ``FlatIPIndex``."""
         self.faiss_padding = bool(faiss_padding)
         if n_subquantizers > 0:
             raise NotImplementedError("IndexPQ (n_subquantizers > 0) is not part of the MI355X path; no reference caller uses it")
         if metric != "inner_product":
             raise NotImplementedError(f"metric={metric!r}: only 'inner_product' (IndexFlatIP) is implemented")
-        self.index = FlatIPIndex(vector_sz, device=device, coarse_dtype=coarse_dtype)
+        self.index = FlatIPIndex(vector_sz, device=device, coarse_dtype=coarse_dtype) if local_index is None else local_index
         self.index_id_to_db_id = np.empty((0), dtype=np.int64)
 
     PREPARE_FROM_ROWS = 1 << 19     # index size from which small query blocks stream the int8 copy (kr_set_option "debug_byte_min_rows" default)
@@ -75,29 +76,45 @@ class Indexer(object):
         top_docs = int(top_docs)
         nq_all = len(query_vectors)
         blocks = [(s, min(s + index_batch_size, nq_all)) for s in range(0, nq_all, index_batch_size)]
-        result = []
         if self.faiss_padding and top_docs > self.index.ntotal:
-            for s0, e0 in blocks:
-                q = query_vectors[s0:e0]
-                n = self.index.ntotal
-                scores = np.full((len(q), top_docs), -np.finfo(np.float32).max, np.float32)
-                indexes = np.full((len(q), top_docs), -1, np.int64)
-                if n > 0:
-                    s_, i_ = self.index.search(q, n)
-                    scores[:, :n] = s_; indexes[:, :n] = i_
-                db_ids = ids_to_str_rows(self.index_id_to_db_id[indexes])
-                result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
-            return result
-        query_vectors = self._on_index_device(query_vectors)
+            return self._search_knn_padded(query_vectors, top_docs, blocks)
         if len(blocks) <= 1:
-            for s0, e0 in blocks:
-                scores, indexes = self.index.search(query_vectors[s0:e0], top_docs)
-                db_ids = ids_to_str_rows(self.index_id_to_db_id[indexes])   # external ids (vectorised form of index.py:49)
-                result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
-            return result
+            return self._search_knn_single(query_vectors, top_docs, blocks)
+        return self._search_knn_pipelined(query_vectors, top_docs, blocks)
+
+    def _append_hits(self, result, scores, rows):
+        """index.py:49-50 for a block: internal rows -> external id strings (vectorised), one (ids, scores) tuple per query appended to ``result``"""
+        db_ids = ids_to_str_rows(self.index_id_to_db_id[rows])
+        result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
+
+    def _search_knn_padded(self, query_vectors, top_docs, blocks):
+        """``faiss_padding`` with ``top_docs > ntotal``: every row, then label -1 / score -FLT_MAX (see ``__init__``)"""
+        result = []
+        for s0, e0 in blocks:
+            q = query_vectors[s0:e0]
+            n = self.index.ntotal
+            scores = np.full((len(q), top_docs), -np.finfo(np.float32).max, np.float32)
+            indexes = np.full((len(q), top_docs), -1, np.int64)
+            if n > 0:
+                s_, i_ = self.index.search(q, n)
+                scores[:, :n] = s_; indexes[:, :n] = i_
+            self._append_hits(result, scores, indexes)
+        return result
+
+    def _search_knn_single(self, query_vectors, top_docs, blocks):
+        """no block or one: one blocking search, nothing to overlap"""
+        result = []
+        for s0, e0 in blocks:
+            self._append_hits(result, *self.index.search(query_vectors[s0:e0], top_docs))
+        return result
+
+    def _search_knn_pipelined(self, query_vectors, top_docs, blocks):
+        """two or more blocks: two searches in flight while the host builds the id strings of the oldest (``search_knn``)"""
         import torch
         if not 0 < top_docs <= self.index.ntotal:
             raise ValueError(f"top_docs={top_docs} must satisfy 0 < k <= ntotal={self.index.ntotal}")
+        nq_all = len(query_vectors)
+        result = []
         # the conversion of the LAST block's ids has no search left to hide under: that block is searched as two pieces (3/4 + 1/4, whole 128-query tiles), so
         # only a quarter block's strings (~2 ms instead of ~8) are built after the device has finished; same lists, same order
         s_last, e_last = blocks[-1]
@@ -161,8 +178,7 @@ class Indexer(object):
                     scores = ps[:e0 - s0].numpy().copy(); indexes = pi[:e0 - s0].numpy().copy()
                     if j + 2 < len(blocks):
                         enqueue(j + 2)                                  # slot (j + 2) % 3 was read out one iteration ago
-                    db_ids = ids_to_str_rows(self.index_id_to_db_id[indexes])
-                    result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
+                    self._append_hits(result, scores, indexes)
             except BaseException:
                 try:
                     self.index.finish()                                 # nothing of this call stays outstanding on the handle
@@ -179,15 +195,6 @@ class Indexer(object):
                         gc.freeze(); gc.unfreeze()
                     gc.enable()
         return result
-
-    def _on_index_device(self, q):
-        """A CUDA tensor of queries on ANOTHER GPU than the index's (the encoder on cuda:1, ``Indexer(device=None)`` on LOCAL_RANK / 0) is moved with ``.to()``:
-        torch orders that cross-device copy behind the encoder's kernels on the source GPU's stream and before the search on this one's (the C
-        side would otherwise stage the foreign pointer with a hipMemcpyAsync on the index GPU's stream, which nothing orders after the encoder)."""
-        if not isinstance(q, np.ndarray) and getattr(q, "is_cuda", False) and q.device.index != self.index.device:
-            import torch
-            return q.to(torch.device("cuda", self.index.device))
-        return q
 
     # ---- on-disk formats (index.py:55-79) --------------------------------------------------------------
     def serialize(self, dir_path):
@@ -218,4 +225,9 @@ class Indexer(object):
         self.index_id_to_db_id = np.concatenate((self.index_id_to_db_id, new_ids), axis=0)
 
 
-from .sharded import ShardedIndexer   # noqa: E402,F401  (lives in sharded.py; imported here so that `from kirag_amd.retriever.index import ShardedIndexer` keeps working)
+def __getattr__(name):
+    """``ShardedIndexer`` lives in sharded.py (which imports this module); ``from kirag_amd.retriever.index import ShardedIndexer`` keeps working (PEP 562)."""
+    if name == "ShardedIndexer":
+        from .sharded import ShardedIndexer
+        return ShardedIndexer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -8,8 +8,9 @@ import pickle
 
 import numpy as np
 
-from .flat_index import ids_to_str_rows
-from .formats import (SHARD_MANIFEST, _ids_crc32, _manifest_matches, read_faiss_flat_ip, read_native_shards, shard_file_name, write_native_shard)
+from ..parallel import ShardedSearcher
+from .formats import (SHARD_MANIFEST, _ids_crc32, _manifest_matches, read_faiss_flat_ip, read_native_shards, shard_file_name, shard_range,
+                      write_native_shard)
 from .index import Indexer
 
 logger = logging.getLogger()
@@ -24,12 +25,15 @@ class ShardedIndexer(Indexer):
     ONE all-gather of ``nq * k * 12`` bytes per rank, host-side merge by (score desc, global row asc) — identical to the unsharded
     ``Indexer`` (tested).  ``index.ntotal`` is the LOCAL row count; ``ntotal_global`` the corpus size."""
 
-    def __init__(self, vector_sz, metric="inner_product", n_subquantizers=0, n_bits=8, device=None, coarse_dtype="bf16", group=None):
+    _searcher = None                     # the ShardedSearcher of the current shard and row offset, made by the first search that needs it
+
+    def __init__(self, vector_sz, metric="inner_product", n_subquantizers=0, n_bits=8, device=None, coarse_dtype="bf16", group=None, *, local_index=None):
         import torch.distributed as dist
+        super().__init__(vector_sz, metric=metric, n_subquantizers=n_subquantizers, n_bits=n_bits, device=device, coarse_dtype=coarse_dtype,
+                         local_index=local_index)
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        super().__init__(vector_sz, metric=metric, n_subquantizers=n_subquantizers, n_bits=n_bits, device=device, coarse_dtype=coarse_dtype)
         self.row_offset = 0
         self.ntotal_global = 0
         self._local_ids = []
@@ -60,21 +64,29 @@ class ShardedIndexer(Indexer):
         work = dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.group, async_op=async_op)
         return flag, work
 
-    def _assemble(self):
-        """Collective: ``index_id_to_db_id`` (all ranks' ids in rank order), ``row_offset`` and ``ntotal_global`` from every rank's local ids."""
+    def _gather(self, obj):
+        """Collective: every rank's ``obj``, in rank order"""
+        if self.world == 1:
+            return [obj]
         import torch.distributed as dist
-        local = np.concatenate(self._local_ids, axis=0) if self._local_ids else np.empty((0), dtype=np.int64)
         parts = [None] * self.world
-        if self.world > 1:
-            dist.all_gather_object(parts, local, group=self.group)
-        else:
-            parts = [local]
+        dist.all_gather_object(parts, obj, group=self.group)
+        return parts
+
+    def _set_shards(self, local):
+        """Collective: this rank's ids ``local`` (int64) become its whole id list; ``index_id_to_db_id`` (all ranks' ids in rank order), ``row_offset``,
+        ``ntotal_global`` and the smallest shard's row count follow from every rank's list."""
+        parts = self._gather(local)
         self.row_offset = int(sum(len(p) for p in parts[: self.rank]))
         self.index_id_to_db_id = np.concatenate(parts, axis=0)
         self.ntotal_global = len(self.index_id_to_db_id)
         self._local_ids = [local]
         self._dirty = False
         self._min_shard_rows = min(len(p) for p in parts)
+
+    def _assemble(self):
+        """Collective: ``_set_shards`` with every id this rank has appended."""
+        self._set_shards(np.concatenate(self._local_ids, axis=0) if self._local_ids else np.empty((0), dtype=np.int64))
 
     def sync_shards(self):
         """Collective: assemble ``index_id_to_db_id``, ``row_offset`` and ``ntotal_global`` after ``index_data`` calls (no-op when no rank appended rows)."""
@@ -88,21 +100,10 @@ class ShardedIndexer(Indexer):
     def set_local_shard(self, local_ids, embeddings):
         """Resident-shard build path (``compute_corpus_embeddings.cal_doc_embeddings(..., indexer=...)`` on every rank): this rank contributes
         its contiguous rows; the global id map and the row offsets are assembled with one ``all_gather_object``.  Collective."""
-        import torch.distributed as dist
         if isinstance(embeddings, np.ndarray):
             embeddings = embeddings.astype('float32')
         self.index.add(embeddings)
-        local = np.array(local_ids, dtype=np.int64)
-        parts = [None] * self.world
-        if self.world > 1:
-            dist.all_gather_object(parts, local, group=self.group)
-        else:
-            parts = [local]
-        self.row_offset = int(sum(len(p) for p in parts[: self.rank]))
-        self.index_id_to_db_id = np.concatenate(parts, axis=0)
-        self.ntotal_global = len(self.index_id_to_db_id)
-        self._local_ids, self._dirty = [local], False
-        self._min_shard_rows = min(len(p) for p in parts)
+        self._set_shards(np.array(local_ids, dtype=np.int64))
         self._prepare_small_searches()
 
     def deserialize_from(self, dir_path):
@@ -129,8 +130,7 @@ class ShardedIndexer(Indexer):
         # later index_data() calls append to this rank's shard: its ids so far are its slice of the loaded map
         self._local_ids = [np.asarray(self.index_id_to_db_id[self.row_offset: self.row_offset + self.index.ntotal], dtype=np.int64)]
         self._dirty = False
-        per = (self.ntotal_global + self.world - 1) // self.world          # the contiguous split both readers use (row_range = (rank, world))
-        self._min_shard_rows = min(max(0, min((r + 1) * per, self.ntotal_global) - min(r * per, self.ntotal_global)) for r in range(self.world))
+        self._min_shard_rows = min(b - a for a, b in (shard_range(self.ntotal_global, r, self.world) for r in range(self.world)))   # the readers' split
         self._prepare_small_searches()
 
     def serialize(self, dir_path):
@@ -143,12 +143,7 @@ class ShardedIndexer(Indexer):
         os.makedirs(dir_path, exist_ok=True)
         n_local = self.index.ntotal
         write_native_shard(self.index, os.path.join(dir_path, shard_file_name(self.rank, self.world)), self.row_offset, self.ntotal_global)
-        info = [None] * self.world
-        mine = {"rank": self.rank, "row0": int(self.row_offset), "rows": int(n_local), "file": shard_file_name(self.rank, self.world)}
-        if self.world > 1:
-            dist.all_gather_object(info, mine, group=self.group)
-        else:
-            info = [mine]
+        info = self._gather({"rank": self.rank, "row0": int(self.row_offset), "rows": int(n_local), "file": shard_file_name(self.rank, self.world)})
         if self.rank == 0:
             import json
             with open(os.path.join(dir_path, SHARD_MANIFEST), "w") as f:
@@ -163,7 +158,6 @@ class ShardedIndexer(Indexer):
         """Collective-safe: depends only on values every rank holds (world, k, the smallest shard's row count, the backend)."""
         import torch
         import torch.distributed as dist
-        from ..parallel import ShardedSearcher
         return (self.world > 1 and dist.is_initialized() and torch.cuda.is_available() and self._min_shard_rows is not None
                 and 0 < k <= self._min_shard_rows and self.world * k <= ShardedSearcher.DEVICE_MERGE_MAX)
 
@@ -182,13 +176,11 @@ class ShardedIndexer(Indexer):
                 if j + 1 < len(starts):
                     a = starts[j + 1] - lo
                     sr.search_deferred(qd[a: a + bs], k)
-                db_ids = ids_to_str_rows(self.index_id_to_db_id[rows])
-                result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
+                self._append_hits(result, scores, rows)
                 self.deferred_blocks += 1
 
     def _get_searcher(self):
-        from ..parallel import ShardedSearcher
-        sr = getattr(self, "_searcher", None)
+        sr = self._searcher
         if sr is None or sr.row_offset != self.row_offset or sr.index is not self.index:
             sr = self._searcher = ShardedSearcher(self.index, row_offset=self.row_offset, world=self.world, group=self.group)
         return sr
@@ -223,9 +215,7 @@ class ShardedIndexer(Indexer):
                 flag = None
             if not 0 < top_docs <= self.ntotal_global:
                 raise ValueError(f"top_docs={top_docs} must satisfy 0 < k <= ntotal={self.ntotal_global}")
-            scores, rows = res if res is not None else self._get_searcher().search(q, top_docs)
-            db_ids = ids_to_str_rows(self.index_id_to_db_id[rows])
-            result.extend([(db_ids[i], scores[i]) for i in range(len(db_ids))])
+            self._append_hits(result, *(res if res is not None else self._get_searcher().search(q, top_docs)))
             done += 1
             if done < len(starts) and self._deferred_ok(top_docs):
                 # the remaining blocks, pipelined like Indexer.search_knn: block j + 1 (local search + all-gather + device merge + D2H, enqueue only) runs

@@ -406,3 +406,26 @@ def test_bulk_id_strings_equal_str_per_id():
     buf = C.create_string_buffer(8); n = C.c_int64(0)
     v = np.array([123456789012], np.int64)
     assert lib.kr_format_ids(v.ctypes.data, 1, b" ", C.addressof(buf), 8, C.byref(n)) == -22         # KR_EINVAL: fewer than 21 bytes left for an id
+
+
+
+def test_each_index_module_imports_first_in_a_fresh_interpreter():
+    """No import cycle among the index modules: each one can be the first thing a process imports, and the names other modules import from
+    ``retriever.index`` (``ShardedIndexer`` included), ``parallel`` and ``compute_corpus_embeddings`` are there."""
+    import subprocess
+    import sys
+    names = ("from kirag_amd.retriever.index import (FlatIPIndex, Indexer, ShardedIndexer, ids_to_str_rows, read_faiss_flat_ip, read_native_shards,\n"
+             "                                       write_faiss_flat_ip, write_native_shard, SHARD_MANIFEST)\n"
+             "from kirag_amd.parallel import ShardedSearcher, merge_topk\n"
+             "from kirag_amd.compute_corpus_embeddings import shard_range\n"
+             "from kirag_amd.retriever import sharded\n"
+             "assert ShardedIndexer is sharded.ShardedIndexer and issubclass(ShardedIndexer, Indexer)\n")
+    mods = [f"kirag_amd.retriever.{m}" for m in ("sharded", "index", "flat_index", "formats", "retrievers")] + ["kirag_amd.parallel"]
+    procs = {m: subprocess.Popen([sys.executable, "-c", f"import {m}\n" + names], cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             for m in mods}
+    failed = {}
+    for m, p in procs.items():
+        out, _ = p.communicate(timeout=300)
+        if p.returncode != 0:
+            failed[m] = out[-2000:]
+    assert not failed, failed

@@ -52,10 +52,8 @@ def _worker(rank, world, port, ret):
             def ntotal(self): return len(self.x)
             def add(self, e): self.x = np.concatenate([self.x, np.asarray(e, np.float32)])
             def search(self, qq, k): return S.search_canonical(np.asarray(qq), self.x, k)
-        sx = ShardedIndexer.__new__(ShardedIndexer)
-        sx.group, sx.rank, sx.world, sx.faiss_padding = None, rank, world, False
-        sx.index, sx.index_id_to_db_id = Rows(), np.empty((0), dtype=np.int64)
-        sx.row_offset, sx.ntotal_global, sx._local_ids, sx._dirty = 0, 0, [], False
+        sx = ShardedIndexer(32, local_index=Rows())
+        assert (sx.rank, sx.world, sx.row_offset, sx.ntotal_global) == (rank, world, 0, 0)
         if rank == 1:                                            # rank 0's share of the streamed build is empty
             sx.index_data([str(7 * j + 1) for j in range(len(x))], x)
         calls = []
@@ -132,10 +130,8 @@ def _worker4(rank, world, port, ret):
             def add(self, e): self.x = np.concatenate([self.x, np.asarray(e, np.float32)])
             def search(self, qq, kk): return S.search_canonical(np.asarray(qq), self.x, kk)
             def prepare(self, *a_, **k_): pass
-        sx = ShardedIndexer.__new__(ShardedIndexer)
-        sx.group, sx.rank, sx.world, sx.faiss_padding = None, rank, world, False
-        sx.index, sx.index_id_to_db_id = Rows(), np.empty((0), dtype=np.int64)
-        sx.row_offset, sx.ntotal_global, sx._local_ids, sx._dirty, sx._min_shard_rows, sx.deferred_blocks = 0, 0, [], False, None, 0
+        sx = ShardedIndexer(d, local_index=Rows())
+        assert (sx.rank, sx.world, sx._min_shard_rows, sx.deferred_blocks) == (rank, world, None, 0)
         sx.index_data([str(5 * j + 3) for j in range(a, b)], x[a:b])
         res = sx.search_knn(q, k, index_batch_size=4)
         assert sx._min_shard_rows == 9 and sx.row_offset == a and sx.ntotal_global == n and not sx._deferred_ok(k) and sx.deferred_blocks == 0
