@@ -1,6 +1,8 @@
 """MI355X counterpart of the reference's ``faiss_index_corpus.py`` (``build_faiss_index`` :27-52): read the pickled shards
 ``corpus_embeddings_*.pkl`` / ``passage_id_list_*.pkl`` in ``end``-index order, append them to an ``Indexer`` (resident in
-HBM), serialise ``index.faiss`` + ``index_meta.faiss`` and delete the shard files — same flags, same side effects."""
+HBM), serialise ``index.faiss`` + ``index_meta.faiss`` and delete the shard files — same flags, same side effects.  ``--index_devices 0,1,...``
+(or ``KIRAG_AMD_INDEX_DEVICES``) builds the index over several GPUs in this one process (``MultiDeviceIndexer``): the way to build a corpus that does not
+fit one GPU; the files written are the same."""
 from __future__ import annotations
 
 import argparse
@@ -10,6 +12,7 @@ import os
 import pickle
 
 from .retriever.index import Indexer
+from .retriever.multi_device import make_indexer
 
 logger = logging.getLogger(__file__)
 
@@ -19,6 +22,7 @@ def setup_parser(argv=None):
     parser.add_argument("--index_name", type=str, default="ip_indexer")
     parser.add_argument("--index_folder", type=str, default=None)
     parser.add_argument("--embedding_size", type=int, default=1024)
+    parser.add_argument("--index_devices", type=str, default=None, help="e.g. 0,1,2,3: rows sharded over these GPUs (one process)")
     return parser.parse_args(argv)
 
 
@@ -32,7 +36,7 @@ def sort_embedding_files(files):
 
 
 def build_faiss_index(args, serialize: bool = True, remove_shards: bool = True) -> Indexer:
-    indexer = Indexer(args.embedding_size, metric="inner_product")
+    indexer = make_indexer(args, args.embedding_size)
     embedding_files = sort_embedding_files(glob.glob(os.path.join(args.index_folder, "corpus_embeddings_*.pkl")))
     id_files = {_end_index(p): p for p in glob.glob(os.path.join(args.index_folder, "passage_id_list_*.pkl"))}
     assert len(embedding_files) == len(id_files)

@@ -8,7 +8,9 @@ Extras over the reference (all optional, none changes results):
   * ``corpus_dataset=`` lets a caller pass its own corpus object instead of ``utils.const.CORPUS_MAP`` (which lives in the reference);
   * the ``retriever/e5.py`` singleton is pointed at the already resident e5 encoder when the retriever is an E5 one, so the
     exemplar ranking of ``knowledge_graph/models.py:1309-1317`` does not load a third copy of e5-large;
-  * ``device=`` / ``args.local_rank`` select the GPU that holds the index shard and the encoder.
+  * ``device=`` / ``args.local_rank`` select the GPU that holds the index shard and the encoder;
+  * ``args.index_devices`` (or ``KIRAG_AMD_INDEX_DEVICES`` when the attribute is absent or None: ``[0, 1]`` or ``"0,1"``) spreads the index rows over
+    those GPUs in this one process (``MultiDeviceIndexer``, same results); the encoder stays on ``local_rank`` / 0.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import logging
 
 from .collators import COLLATOR_MAP
 from .retriever import e5 as e5_module
-from .retriever.index import Indexer
+from .retriever.multi_device import make_indexer
 from .retriever.retrievers import DenseRetriever, InBatchRetriever
 
 logger = logging.getLogger(__file__)
@@ -45,7 +47,7 @@ def setup_retriever_model(args, corpus_dataset=None, tokenizer=None):
             raise ImportError("args.corpus needs the KiRAG repository on PYTHONPATH (utils/const.py CORPUS_MAP), or pass corpus_dataset=") from e
         corpus_dataset = CORPUS_MAP[args.corpus](title_prefix="title: ", passage_prefix="text: ")
     logger.info(f"Loading index from {args.index_folder} ...")
-    indexer = Indexer(args.embedding_size, metric="inner_product", device=device)
+    indexer = make_indexer(args, args.embedding_size, device=device)
     indexer.deserialize_from(args.index_folder)
     dense_retriever = DenseRetriever(retriever=retriever, collator=collator, indexer=indexer, corpus=corpus_dataset,
                                      batch_size=args.per_gpu_batch_size)

@@ -226,8 +226,12 @@ class Indexer(object):
 
 
 def __getattr__(name):
-    """``ShardedIndexer`` lives in sharded.py (which imports this module); ``from kirag_amd.retriever.index import ShardedIndexer`` keeps working (PEP 562)."""
+    """``ShardedIndexer`` lives in sharded.py and ``MultiDeviceIndexer`` in multi_device.py (both import this module); ``from kirag_amd.retriever.index
+    import ShardedIndexer`` / ``MultiDeviceIndexer`` keeps working (PEP 562)."""
     if name == "ShardedIndexer":
         from .sharded import ShardedIndexer
         return ShardedIndexer
+    if name == "MultiDeviceIndexer":
+        from .multi_device import MultiDeviceIndexer
+        return MultiDeviceIndexer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
