@@ -75,21 +75,14 @@ struct LayerW {
 struct Knobs {
     int pw = 8;            // KIRAG_AMD_PATCH_W: feature tiles per XCD patch of the tile walk (profiles/r03)
     int epi_prio = 0;      // KIRAG_AMD_EPI_PRIO (proj_epilogue)
-    int store_nt = -1;     // KIRAG_AMD_STORE_NT = 0 / 1 forces the epilogue store policy, -1 = by output size (ProjArgs::nt)
-    bool nt_h = true;      // KIRAG_AMD_NT_H=0: FF2's activation operand with plain loads
     int force_tile = 0;    // KIRAG_AMD_PROJ_TILE: 32 / 128 / 130 / 256 force a projection path (tests run every parity case through all of them)
-    int ratio8 = 5;        // KIRAG_AMD_SMALL_RATIO: eighths of the CU count below which the 128x128 tiling is used (tools/ab_encoder.py)
-    bool attn_lds = false, attn_dma = false;   // KIRAG_AMD_ATTN_LDS / KIRAG_AMD_ATTN_DMA: force one attention kernel (A/B)
+    bool attn_lds = false; // KIRAG_AMD_ATTN_LDS: the register-staged attention kernel for long sequences too
     void read() {
         auto geti = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
         pw = geti("KIRAG_AMD_PATCH_W", 8); if (pw < 1) pw = 8;
         epi_prio = geti("KIRAG_AMD_EPI_PRIO", 0);
-        store_nt = geti("KIRAG_AMD_STORE_NT", -1);
-        nt_h = geti("KIRAG_AMD_NT_H", 1) != 0;
         force_tile = geti("KIRAG_AMD_PROJ_TILE", 0);
-        ratio8 = geti("KIRAG_AMD_SMALL_RATIO", 5);
         attn_lds = getenv("KIRAG_AMD_ATTN_LDS") != nullptr;
-        attn_dma = geti("KIRAG_AMD_ATTN_DMA", 0) != 0;
     }
 };
 
@@ -112,7 +105,6 @@ struct Encoder {
     bool use_lo = false;       // KIRAG_AMD_RESIDUAL_LO=1 at kr_encoder_create
     uint16_t *y = nullptr, *xb = nullptr, *q = nullptr, *k = nullptr, *vT = nullptr, *ctx = nullptr, *h = nullptr;
     int lastB = 0, lastS = 0;
-    int h_pad = 0;                   // extra elements per row of h (row pitch not a power of two: see ensure_ws)
     int* h_err = nullptr;            // pinned: copy of d_err taken at the end of the last asynchronous forward
     hipEvent_t ev_done = nullptr;    // recorded after that copy
     bool pending = false;            // an asynchronous forward's error word has not been looked at yet
@@ -681,9 +673,6 @@ __device__ __forceinline__ void store_rows_bf16(AccTile<Shape>& acc, char* stage
     uint4 d[2][4];
 #pragma unroll
     for (int mi = 0; mi <= Shape::TM; ++mi) {
-#ifdef KR_STAMP
-        acc.stamp(mi);                      // [0] = everything before the first block (bias loads ...), [mi] = block mi-1
-#endif
         if (mi < Shape::TM) {
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
@@ -706,9 +695,6 @@ __device__ __forceinline__ void store_rows_bf16(AccTile<Shape>& acc, char* stage
             }
         }
     }
-#ifdef KR_STAMP
-    acc.stamp(Shape::TM + 1);
-#endif
 }
 
 // V^T[feature, token]: each 32x32 tile is staged as [32 features][32 tokens] (80-B rows), lanes = consecutive tokens of a feature row,
@@ -917,18 +903,12 @@ __device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint
         const char* krow = Kst + key * 128;
         const int swz = (key >> 1) & 7;
         uint4 kf[two ? 8 : 4];
-#if defined(ATTN_ABL) && ATTN_ABL == 7      // ablation: no LDS fragment reads (fragments = registers)
-#pragma unroll
-        for (int sk = 0; sk < (two ? 8 : 4); ++sk) kf[sk] = qf[sk & 3];
-        (void)krow; (void)swz;
-#else
 #pragma unroll
         for (int sk = 0; sk < 4; ++sk) kf[sk] = *reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4));
         if constexpr (two) {
 #pragma unroll
             for (int sk = 0; sk < 4; ++sk) kf[4 + sk] = *reinterpret_cast<const uint4*>(krow + 32 * 128 + (((2 * sk + hf) ^ swz) << 4));
         }
-#endif
         st0 = ET::mfma(kf[0], qf[0], zero);
 #pragma unroll
         for (int sk = 1; sk < 4; ++sk) st0 = ET::mfma(kf[sk], qf[sk], st0);
@@ -976,15 +956,8 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
     uint4 vpre[PF ? (two ? 8 : 4) : 1];
     if constexpr (PF) {                                  // the V^T fragments land under the maximum / rescale arithmetic
 #pragma unroll
-#if defined(ATTN_ABL) && ATTN_ABL == 7
-        for (int ks = 0; ks < (two ? 4 : 2); ++ks) { vpre[2 * ks] = make_uint4(__builtin_bit_cast(unsigned, st0[ks]), 0x3c003c00u, 0x3c003c00u, 0x3c003c00u); vpre[2 * ks + 1] = vpre[2 * ks]; }
-#else
         for (int ks = 0; ks < (two ? 4 : 2); ++ks) { vpre[2 * ks] = vfrag(0, ks); vpre[2 * ks + 1] = vfrag(1, ks); }
-#endif
     }
-#if defined(ATTN_ABL) && (ATTN_ABL == 2 || ATTN_ABL == 6 || ATTN_ABL == 7)     // tools/attn_bench.hip ablation: no maximum
-    float tmax = st0[0];
-#else
     float tmax = fmaxf(fmaxf(st0[0], st0[1]), st0[2]);
 #pragma unroll
     for (int r = 3; r < 15; r += 2) tmax = fmaxf(fmaxf(tmax, st0[r]), st0[r + 1]);   // v_max3_f32
@@ -994,7 +967,6 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
         for (int r = 0; r < 16; r += 2) tmax = fmaxf(fmaxf(tmax, st1[r]), st1[r + 1]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-#endif
     const bool fresh = s.mref == -INFINITY;               // nothing accumulated for this query yet
     if (__builtin_amdgcn_ballot_w64(fresh || tmax > s.mref + ATTN_RESCALE_THR) != 0ull) {
         // raise the reference (never lower it)
@@ -1013,26 +985,9 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
         for (int a = 0; a < 2; ++a) {
             float e[8];
 #pragma unroll
-#if defined(ATTN_ABL) && (ATTN_ABL == 6 || ATTN_ABL == 7)     // ablation: no softmax arithmetic at all (P = S)
-            for (int i = 0; i < 8; ++i) { e[i] = stx[8 * a + i]; }
-            psum = e[0];
-#elif defined(ATTN_ABL) && ATTN_ABL == 1     // ablation: no exponential
-            for (int i = 0; i < 8; ++i) { e[i] = stx[8 * a + i] - mshift; psum += e[i]; }
-#elif defined(ATTN_ABL) && ATTN_ABL == 3   // ablation: no row sum
-            for (int i = 0; i < 8; ++i) { e[i] = __builtin_amdgcn_exp2f(stx[8 * a + i] - mshift); }
-            psum = e[0];
-#else
             for (int i = 0; i < 8; ++i) { e[i] = __builtin_amdgcn_exp2f(stx[8 * a + i] - mshift); psum += e[i]; }
-#endif
             uint4 pf;
             pf.x = pack_bf16x2(e[0], e[1]); pf.y = pack_bf16x2(e[2], e[3]); pf.z = pack_bf16x2(e[4], e[5]); pf.w = pack_bf16x2(e[6], e[7]);
-#if defined(ATTN_ABL) && ATTN_ABL == 4     // ablation: no P.V MFMAs (P and the V^T fragments stay live)
-            if constexpr (PF) {
-                const uint4 va = vpre[2 * (ks0 + a)], vb = vpre[2 * (ks0 + a) + 1];
-                const unsigned keep = pf.x ^ pf.y ^ pf.z ^ pf.w ^ va.x ^ va.y ^ va.z ^ va.w ^ vb.x ^ vb.y ^ vb.z ^ vb.w;
-                asm volatile("" :: "v"(keep));
-            } else
-#endif
             if constexpr (PF) {
                 s.o0 = ET::mfma(vpre[2 * (ks0 + a)], pf, s.o0);
                 s.o1 = ET::mfma(vpre[2 * (ks0 + a) + 1], pf, s.o1);
@@ -1044,9 +999,7 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
     };
     pv(st0, 0);
     if (two) pv(st1, 2);
-#if !(defined(ATTN_ABL) && (ATTN_ABL == 3 || ATTN_ABL == 6 || ATTN_ABL == 7))
     psum += __shfl_xor(psum, 32, 64);
-#endif
     s.l += psum;
 }
 
@@ -1089,14 +1042,10 @@ __device__ __forceinline__ void attn_store_tile(const AttnState& s, char* Os, ui
     }
 }
 
-#ifndef ALDS_PF_N
-#define ALDS_PF_N 0
-#endif
-constexpr bool ALDS_PF = ALDS_PF_N != 0;                   // fragment prefetch in k_attn_lds (tools: A/B builds)
 // HPB = heads per block: 1 when a sequence has >= 3 q-tiles, 2 / 4 for short sequences so that all four waves have work.
 // __launch_bounds__(256, 3): at most 168 registers per lane, which makes hipcc keep the MFMA accumulators in VGPRs; with the default bound it put
 // them in AGPRs and spent 112 of the 276 VALU instructions of a key tile on v_accvgpr_read / _write around the softmax rescale
-template <int HPB, bool NTL = false>   // NTL (experiment builds only): q / k / v loaded non-temporally
+template <int HPB>
 __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
                                                   int H, int heads, int kchunk, uint16_t* __restrict__ ctx) {
@@ -1126,8 +1075,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
         const int qi = (q0 + c < nq) ? (q0 + c) : (nq - 1);
         const uint16_t* qrow = q + (off + qi) * H + head * 64;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = NTL ? __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(qrow + 16 * s + 8 * hf)))
-                                                : *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
+        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
     }
     AttnState st;
     attn_init(st);
@@ -1158,7 +1106,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
                         kv[h2][j] = make_uint4(0u, 0u, 0u, 0u);
                         if (head2 < heads && i < nkcs && key < nkc) {
                             const uint16_t* kp = k + (off + kc0 + key) * H + head2 * 64 + ch * 8;
-                            kv[h2][j] = NTL ? __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(kp))) : *reinterpret_cast<const uint4*>(kp);
+                            kv[h2][j] = *reinterpret_cast<const uint4*>(kp);
                         }
                     }
                 }
@@ -1175,8 +1123,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
                         vv[h2][j] = make_uint2(0u, 0u);
                         if (head2 < heads && i < nvc && vk * 4 < nkc) {
                             const uint16_t* vp = vT + (int64_t)(head2 * 64 + vd) * ldv + off + kc0 + vk * 4;   // off, kc0 % 4 == 0: 8-B aligned
-                            typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-                            vv[h2][j] = NTL ? __builtin_bit_cast(uint2, __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(vp))) : *reinterpret_cast<const uint2*>(vp);
+                            vv[h2][j] = uint2(*reinterpret_cast<const uint2*>(vp));
                         }
                     }
                 }
@@ -1221,7 +1168,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
                 const uint2 a0 = *reinterpret_cast<const uint2*>(v), a1 = *reinterpret_cast<const uint2*>(v + 8);
                 return make_uint4(a0.x, a0.y, a1.x, a1.y);
             };
-            attn_step64<false, ALDS_PF>(st, qf, Kh, k0, 64, c, hf, vfrag);
+            attn_step64<false>(st, qf, Kh, k0, 64, c, hf, vfrag);
         }
         if (kfull < nkc) {
             auto vfrag = [&](int dh, int ks) {
@@ -1237,16 +1184,11 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
 }
 
 // ---- long sequences: LDS-DMA ring ------------------------------------------------------------------------------------------------------------
-#ifdef KR_STAMP_ATTN
-__device__ unsigned long long kr_attn_stamps[8];          // diagnostic build only (tools/attn_bench.hip)
-#endif
 constexpr int ADMA_STAGE = 16384;                          // per 64-key chunk: K [64 keys][128 B] + V^T [64 d][128 B]
 constexpr int ADMA_RING = 3;
 constexpr int ADMA_LDS = ADMA_RING * ADMA_STAGE;           // 48 KiB; the O staging (4 waves x 4 KiB) re-uses the ring after the last chunk
-#ifndef ADMA_WAVES_N
-#define ADMA_WAVES_N 4                                     // tools/attn_bench.hip builds the 8-wave variant too (one block per (sequence, head) up to 512 tokens:
-#endif                                                     // 5 % faster at 128 x 512, 10-35 % slower at 64 x 512, 256 x 256 and 341 x 192)
-constexpr int ADMA_WAVES = ADMA_WAVES_N;
+constexpr int ADMA_WAVES = 4;                              // eight (one block per (sequence, head) up to 512 tokens) measured 5 % faster at 128 x 512,
+                                                           // 10-35 % slower at 64 x 512, 256 x 256 and 341 x 192
 constexpr int ADMA_THREADS = ADMA_WAVES * 64;
 constexpr int ADMA_QT = 2 * ADMA_WAVES;                    // q-tiles per block: TWO per wave (w and w + ADMA_WAVES), so every staged chunk serves 256 queries
 constexpr int ADMA_PIECES = 8 / ADMA_WAVES;                // K pieces (and V^T pieces) of 1 KiB a wave issues per chunk
@@ -1314,37 +1256,23 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         attn_init(st[j]);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): Q fragments (and chunks 0, 1) have landed
-#ifdef KR_STAMP_ATTN
-    unsigned long long sa_turn = 0, sa_t0 = 0, sa_t1 = 0, sa_prev = __builtin_amdgcn_s_memtime();
-    const unsigned long long sa_begin = sa_prev;
-#define KR_SA(acc) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - sa_prev; sa_prev = now_; } while (0)
-#else
-#define KR_SA(acc) do { } while (0)
-#endif
     auto turn = [&](int ci) {
         if (ci + 1 < nchunks) wait_vmcnt<2 * ADMA_PIECES>(); else wait_vmcnt<0>();   // this wave's pieces of chunk ci have landed; chunk ci + 1 may be in flight
         __builtin_amdgcn_s_barrier();                      // everybody's pieces of chunk ci landed, everybody is done reading chunk ci - 1
-#if defined(ATTN_ABL) && ATTN_ABL == 5      // tools/attn_bench.hip ablation: no K / V^T traffic after the first two chunks (stale stages are multiplied)
-        (void)ci;
-#else
         if (ci + 2 < nchunks) issue(ci + 2);               // into the stage of chunk ci - 1
-#endif
     };
     // The chunks with 64 valid keys run in loops of their own (one per number of active q-tiles) that hold nothing but the unmasked step: with the masked
     // variants and the act[] tests inside one loop the accumulators of both tiles went through copies at every join (32 v_mov_b64 per step)
     const int nfull = nk >> 6;
     auto full_chunk = [&](int ci, auto two_tiles) {
         turn(ci);
-        KR_SA(sa_turn);
         char* stg = smem + (ci % ADMA_RING) * ADMA_STAGE;
         auto vfrag = [&](int dh, int ks) {
             const int d = c + 32 * dh;
             return *reinterpret_cast<const uint4*>(stg + 8192 + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
         };
         attn_step64<false, true>(st[0], qf[0], stg, 0, 64, c, hf, vfrag);
-        KR_SA(sa_t0);
         if constexpr (decltype(two_tiles)::value) attn_step64<false, true>(st[1], qf[1], stg, 0, 64, c, hf, vfrag);
-        KR_SA(sa_t1);
     };
     if (act[1]) {
         for (int ci = 0; ci < nfull; ++ci) full_chunk(ci, std::true_type{});
@@ -1389,13 +1317,6 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
 #pragma unroll
     for (int j = 0; j < 2; ++j)
         if (act[j]) attn_store_tile(st[j], Os, ctx, off, q0[j], nq, H, head, lane);
-#ifdef KR_STAMP_ATTN
-    if (lane == 0) {       // [0] barrier / wait / DMA issue, [1] first tile's step, [2] second tile's step, [3] whole lifetime, [4] waves
-        const unsigned long long end = __builtin_amdgcn_s_memtime();
-        atomicAdd(&kr_attn_stamps[0], sa_turn); atomicAdd(&kr_attn_stamps[1], sa_t0); atomicAdd(&kr_attn_stamps[2], sa_t1);
-        atomicAdd(&kr_attn_stamps[3], end - sa_begin); atomicAdd(&kr_attn_stamps[4], 1ull);
-    }
-#endif
 }
 
 __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* __restrict__ seq_off,
@@ -1549,11 +1470,11 @@ static int ensure_ws(Encoder* e, int B, int S) {
     e->ldv = capT + 64;   // slack: the last key tile of the last sequence may read up to 43 columns past T
     KR_TRY(dmalloc(&e->vT, (size_t)H * e->ldv * 2));
     KR_HIP(hipMemset(e->vT, 0, (size_t)H * e->ldv * 2));
-    KR_TRY(dmalloc(&e->ctx, capT * H * 2)); KR_TRY(dmalloc(&e->h, capT * (FF + e->h_pad) * 2));
+    KR_TRY(dmalloc(&e->ctx, capT * H * 2)); KR_TRY(dmalloc(&e->h, capT * FF * 2));
     if (e->cls_shortcut) {
         const int64_t capC = round_up(capB, 256);                 // token-indexed buffers come in multiples of the 256-row tile (see k_proj)
         KR_TRY(dmalloc(&e->c_ctx, capC * H * 2)); KR_TRY(dmalloc(&e->c_xb, capC * H * 2)); KR_TRY(dmalloc(&e->c_y, capC * H * 2)); KR_TRY(dmalloc(&e->c_xlo, capC * H));
-        KR_TRY(dmalloc(&e->c_h, capC * (FF + e->h_pad) * 2));
+        KR_TRY(dmalloc(&e->c_h, capC * FF * 2));
         KR_HIP(hipMemset(e->c_ctx, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xb, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xlo, 0x80, (size_t)capC * H));
         KR_TRY(dmalloc(&e->c_off, capB * 4)); KR_TRY(dmalloc(&e->c_nk, capB * 4)); KR_TRY(dmalloc(&e->c_cls, capB * 4)); KR_TRY(dmalloc(&e->d_B, sizeof(int)));
     }
@@ -1639,21 +1560,16 @@ template <class Shape, int STAGES, bool NT>
 static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int device, hipStream_t st) {
     constexpr int lds = STAGES * Shape::STAGE_BYTES + Shape::NWAVE * EPI_STAGE_BYTES;   // 160 KiB for the 256x256 tile: the whole LDS of a CU
     // function attributes belong to the device's code-object instance: once per (kernel, device)
-    auto go = [&](auto kern, int) -> int {
+    auto go = [&](auto kern) -> int {
         KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
-        int repeat = 1;
-#ifdef KR_STAMP
-        { const int sl = (epi % 3) + (a.K > 1024 ? 2 : 0); (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(kr_stamp_slot), &sl, sizeof(int), 0, hipMemcpyHostToDevice, st); }
-        { const char* r = getenv("KIRAG_AMD_DEBUG_REPEAT"); if (r) repeat = atoi(r); }   // diagnostic: the same launch again (warm instruction cache?)
-#endif
-        for (int rep = 0; rep < repeat; ++rep) hipLaunchKernelGGL(kern, dim3(blocks), dim3(Shape::NTHREADS), lds, st, a);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(Shape::NTHREADS), lds, st, a);
         return 0;
     };
     const bool ant = a.ant && Shape::BM == 256;   // the non-temporal activation operand exists for the ping-pong loop only
     switch (epi) {
-        case EPI_QKV: return go(&k_proj<EPI_QKV, Shape, STAGES, NT>, 0);
-        case EPI_DENSE: return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>, 1) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>, 2);
-        case EPI_GELU: return go(&k_proj<EPI_GELU, Shape, STAGES, NT>, 3);
+        case EPI_QKV: return go(&k_proj<EPI_QKV, Shape, STAGES, NT>);
+        case EPI_DENSE: return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>);
+        case EPI_GELU: return go(&k_proj<EPI_GELU, Shape, STAGES, NT>);
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }
@@ -1688,15 +1604,15 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     a.pw = kn.pw;
     a.epi_prio = kn.epi_prio;
     // store policy by output size (see ProjArgs::nt)
-    a.nt = kn.store_nt >= 0 ? kn.store_nt : (max_tokens * (int64_t)a.F * 2 > ((int64_t)96 << 20) ? 1 : 0);
+    a.nt = max_tokens * (int64_t)a.F * 2 > ((int64_t)96 << 20) ? 1 : 0;
     // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
     // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
-    // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).  KIRAG_AMD_NT_H=0 switches it off (A/B).
-    a.ant = (a.K > a.H && kn.nt_h) ? 1 : 0;
+    // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
+    a.ant = a.K > a.H ? 1 : 0;
     const int64_t big_tiles = ((max_tokens + 255) / 256) * ((a.F + 255) / 256);
     const int64_t small_tiles = ((max_tokens + 127) / 128) * ((a.F + 127) / 128);
-    const int force = kn.force_tile, ratio8 = kn.ratio8;
-    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * ratio8);   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
+    const int force = kn.force_tile;
+    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * 5);   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
     // a handful of token rows: the skinny loop, one tile per block (latency chain: the operand stream of the launch spread over as many CUs as it has
     // tiles).  32 x 32 tiles while there is at most one per CU, 64 x 64 (four multiplying waves share every staged K-tile: half the L2 -> LDS bytes per
     // output element) up to four 32 x 32 tiles' worth per CU — the crossover against the 128x128 producer / consumer loop measured in round 1.
@@ -1762,7 +1678,6 @@ int enc_create(const kr_bert_cfg* cfg, int device, int residual_lo, void** out) 
     e->use_lo = residual_lo != 0;
     { const char* v = getenv("KIRAG_AMD_CLS_FULL"); e->cls_shortcut = !(v && atoi(v) != 0); }
     { const char* v = getenv("KIRAG_AMD_GRAPH"); e->graphs_off = !(v && atoi(v) != 0); }   // opt-in: measured SLOWER than eager launches on ROCm 7.2 (see run_forward)
-    { const char* v = getenv("KIRAG_AMD_HPAD"); e->h_pad = v ? (atoi(v) / 8) * 8 : 0; }
     { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) e->num_cu = (p.multiProcessorCount / 8) * 8; }
     e->num_cu_all = e->num_cu;
     e->L.resize(cfg->layers);
@@ -1893,8 +1808,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
     const float eps = e->cfg.ln_eps;
     e->kn.read();
     const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
-    const bool long_seq = (nqt_max > 4 && !e->kn.attn_lds) || e->kn.attn_dma;   // KIRAG_AMD_ATTN_DMA=1: the ring kernel for short sequences too (A/B)
-            // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: A/B against the register-staged one)
+    const bool long_seq = nqt_max > 4 && !e->kn.attn_lds;                          // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
     const int align = long_seq ? 8 : 4;                                            // sequence offsets: multiple of 8 tokens so that V^T chunks start 16-B aligned
     if (ragged_total >= 0) {
         // kr_encoder_forward_packed: e->d_ids holds the int32 token list, e->d_mask the int32 lengths, e->d_tt is scratch for the input offsets
@@ -1960,9 +1874,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
             a.W = l.wo; a.X = e->c_ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = e->c_y; a.ldx = 0; a.ldo = 0;
             KR_TRY(launch_proj(EPI_DENSE, a, B, e, st));
             hipLaunchKernelGGL(ln_kernel, dim3(c_ln_grid), dim3(256), 0, st, e->c_y, l.bo_eff, e->d_B, l.ln1g, l.ln1b, eps, H, c_lo, c_lo, e->c_xb);
-            a.W = l.w1; a.X = e->c_xb; a.F = FF; a.K = H; a.bias = l.b1; a.out0 = e->c_h; a.ldx = 0; a.ldo = FF + e->h_pad;
+            a.W = l.w1; a.X = e->c_xb; a.F = FF; a.K = H; a.bias = l.b1; a.out0 = e->c_h; a.ldx = 0; a.ldo = FF;
             KR_TRY(launch_proj(EPI_GELU, a, B, e, st));
-            a.W = l.w2; a.X = e->c_h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = e->c_y; a.ldx = FF + e->h_pad; a.ldo = 0;
+            a.W = l.w2; a.X = e->c_h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = e->c_y; a.ldx = FF; a.ldo = 0;
             KR_TRY(launch_proj(EPI_DENSE, a, B, e, st));
             hipLaunchKernelGGL(ln_kernel, dim3(c_ln_grid), dim3(256), 0, st, e->c_y, l.b2, e->d_B, l.ln2g, l.ln2b, eps, H, c_lo, e->c_xlo, e->c_xb);
             KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
@@ -1975,10 +1889,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
         KR_TRY(launch_proj(EPI_DENSE, a, maxT, e, st));
         hipLaunchKernelGGL(ln_kernel, dim3(ln_grid), dim3(256), 0, st, e->y, l.bo_eff, e->d_T, l.ln1g, l.ln1b, eps, H, lo_rw, lo_rw, e->xb);
         // intermediate.dense + GELU
-        a.W = l.w1; a.X = e->xb; a.F = FF; a.K = H; a.bias = l.b1; a.out0 = e->h; a.ldx = 0; a.ldo = FF + e->h_pad;
+        a.W = l.w1; a.X = e->xb; a.F = FF; a.K = H; a.bias = l.b1; a.out0 = e->h; a.ldx = 0; a.ldo = FF;
         KR_TRY(launch_proj(EPI_GELU, a, maxT, e, st));
         // output.dense + residual -> LayerNorm
-        a.W = l.w2; a.X = e->h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = e->y; a.ldx = FF + e->h_pad; a.ldo = 0;
+        a.W = l.w2; a.X = e->h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = e->y; a.ldx = FF; a.ldo = 0;
         KR_TRY(launch_proj(EPI_DENSE, a, maxT, e, st));
         // the LAST LayerNorm always writes the low half: pooling and kr_encoder_last_hidden read the final hidden state with 16 mantissa bits
         hipLaunchKernelGGL(ln_kernel, dim3(ln_grid), dim3(256), 0, st, e->y, l.b2, e->d_T, l.ln2g, l.ln2b, eps, H, lo_rw, last ? e->xlo : lo_rw, e->xb);
@@ -2136,27 +2050,6 @@ int enc_check(void* h) {
     e->pending = false;
     return report_token_error(e, e->last_stream);
 }
-
-#if defined(KR_STAMP) && !defined(KR_ENC_BUILD_F16)
-}  // namespace KR_ENC_NS
-}  // namespace kr
-extern "C" {
-using namespace kr;
-int kr_debug_read_fine_enc(unsigned long long* out128) {
-    if (hipMemcpyFromSymbol(out128, HIP_SYMBOL(kr_stamp_fine), 128 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long z[128] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(kr_stamp_fine), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-// diagnostic build only: the projection kernels' copy of the stamp sums
-int kr_debug_read_stamps_enc(unsigned long long* out256) {
-    if (hipMemcpyFromSymbol(out256, HIP_SYMBOL(kr_stamp_buf), 256 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long z[256] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(kr_stamp_buf), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-}  // extern "C"
-namespace kr {
-namespace KR_ENC_NS {
-#endif
 
 // last_hidden_state of the previous forward, un-packed to [B,S,H]; rows of non-attended positions are zero
 int enc_last_hidden(void* h, float* out, int B, int S) {

@@ -44,10 +44,6 @@ template <class Shape>
 struct AccTile {
     f32x16 v[Shape::TM][Shape::TN];
     int m_wave, n_wave, lane;
-#ifdef KR_STAMP
-    unsigned long long fine[6] = {0, 0, 0, 0, 0, 0}, fine_prev = 0;
-    __device__ __forceinline__ void stamp(int step) { const unsigned long long now = __builtin_amdgcn_s_memtime(); fine[step] += now - fine_prev; fine_prev = now; }
-#endif
     __device__ __forceinline__ int row(int mi, int r) const { return m_wave + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
     __device__ __forceinline__ int col(int ni) const { return n_wave + ni * 32 + (lane & 31); }
 };
@@ -103,16 +99,6 @@ __device__ __forceinline__ void patch_coord(int64_t n, int64_t tm_count, int64_t
 }
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// Diagnostic build only (-DKR_STAMP, tools/stamp_build.sh): per-wave cycle sums of the three parts of an output tile in gemm_nt_pingpong — [0] tile
-// set-up (coordinates, cursor), [1] the K loop (all intervals), [2] the epilogue, [3] tiles — accumulated into kr_stamp_buf[wave 0..7][4].  The
-// product build contains none of this.
-#ifdef KR_STAMP
-__device__ unsigned long long kr_stamp_buf[8 * 8 * 4];   // [slot][wave][part]
-__device__ int kr_stamp_slot;                              // set by the host (stream-ordered) before a launch
-__device__ unsigned long long kr_stamp_fine[8 * 2 * 8];    // [slot][group][step]: cycle sums at finer points inside an epilogue (kept in SGPRs per tile)
-#define KR_STAMP_NOW() __builtin_amdgcn_s_memtime()
-#endif
 
 template <class T, class Shape, int STAGES = 3, bool SWAP = false, class Coord, class Epilogue>
 __device__ __forceinline__ void gemm_nt_stream(const uint16_t* __restrict__ A, int64_t lda, int64_t M, const uint16_t* __restrict__ B, int64_t ldb,
@@ -384,9 +370,8 @@ __device__ __forceinline__ void gemm_nt_split(const uint16_t* __restrict__ A, in
 // =====================================================================================================================
 using ShapeSkinny = GemmShape<32, 32, 1, 1>;
 constexpr int SKINNY_STAGE = 8192;                         // bytes per K-tile of the 1 x 1 shape
-#ifndef SKINNY_GROUP
-#define SKINNY_GROUP 2                                     // K-tiles per barrier at most (4 needs a ring of 16 and measured the same as 2: profiles/r05/tried_skinny_prologue.txt); 1 = rounds 1-4
-#endif
+constexpr int SKINNY_GROUP = 2;                            // K-tiles per barrier when their count is even (4 needs a ring of 16 and measured the same as 2:
+                                                           // profiles/r05/tried_skinny_prologue.txt; 1 = rounds 1-4)
 template <int WM, int WN> struct SkinnyGeom {
     static constexpr int NC = WM * WN;                     // multiplying waves
     static constexpr int THREADS = (NC + 4) * 64;
@@ -454,8 +439,8 @@ __device__ __forceinline__ bool gemm_nt_skinny(const uint16_t* __restrict__ A, i
         // GRP K-tiles per barrier (round 5): the multiplying waves' four MFMAs per K-tile are 128 cycles, a barrier round trip with five to eight waves is
         // half of that again.  At barrier j tiles GRP j .. GRP j + GRP - 1 (multiplied in full) and GRP j + GRP (its first fragments are prefetched) are
         // resident; behind it the slots of the previous GRP tiles are free and GRP new tiles are issued.  Same MFMAs in the same order.
-        auto grouped = [&](auto grp_tag) {
-            constexpr int GRP = decltype(grp_tag)::value;
+        auto grouped = [&]() {
+            constexpr int GRP = SKINNY_GROUP;
             for (int p = 0; p < RING - GRP; ++p)
                 if (pf < nk) stage_next();
             constexpr int FULLG = G::PPW * (RING - 2 * GRP - 1);   // tiles GRP j .. GRP j + GRP landed, the younger ones in flight
@@ -469,8 +454,7 @@ __device__ __forceinline__ bool gemm_nt_skinny(const uint16_t* __restrict__ A, i
                     if (pf < nk) stage_next();                               // -> the slots of tiles g - GRP .. g - 1
             }
         };
-        if (SKINNY_GROUP >= 4 && RING >= 16 && (nk & 3) == 0) { grouped(std::integral_constant<int, 4>{}); return true; }
-        if (SKINNY_GROUP >= 2 && (nk & 1) == 0) { grouped(std::integral_constant<int, 2>{}); return true; }
+        if ((nk & 1) == 0) { grouped(); return true; }
         for (int p = 0; p < RING - 1; ++p)
             if (pf < nk) stage_next();                 // tile by tile (A, B): a tile is complete as soon as its own pieces have landed (vmcnt retires in order)
         constexpr int FULL = G::PPW * (RING - 3);      // tiles g, g+1 landed, RING - 3 younger ones in flight
@@ -502,8 +486,8 @@ __device__ __forceinline__ bool gemm_nt_skinny(const uint16_t* __restrict__ A, i
     for (int r = 0; r < 16; ++r) acc.v[0][0][r] = 0.f;
     __builtin_amdgcn_s_barrier();                          // start barrier
     load_frags(0, 0, 0); load_frags(0, 1, 1);
-    auto grouped = [&](auto grp_tag) {
-        constexpr int GRP = decltype(grp_tag)::value;
+    auto grouped = [&]() {
+        constexpr int GRP = SKINNY_GROUP;
         for (int g = 0; g < nk; g += GRP) {
             __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -516,8 +500,7 @@ __device__ __forceinline__ bool gemm_nt_skinny(const uint16_t* __restrict__ A, i
         }
         epi(acc, m0 + wm * 32, n0 + wn * 32);
     };
-    if (SKINNY_GROUP >= 4 && RING >= 16 && (nk & 3) == 0) { grouped(std::integral_constant<int, 4>{}); return true; }
-    if (SKINNY_GROUP >= 2 && (nk & 1) == 0) { grouped(std::integral_constant<int, 2>{}); return true; }
+    if ((nk & 1) == 0) { grouped(); return true; }
     for (int g = 0; g < nk; ++g) {
         __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -562,11 +545,7 @@ __device__ __forceinline__ bool gemm_nt_skinny(const uint16_t* __restrict__ A, i
 // =====================================================================================================================
 using ShapePP = GemmShape<256, 256, 2, 4>;
 
-// M16 (experiment, tools/gemm_bench.hip only): the same loop on v_mfma_f32_16x16x32 — one 32-deep k-step per interval, 8 x 4 blocks of 16 x 16 per wave,
-// the same 12 ds_read_b128 and the same matrix-pipe cycles per interval (MI355X_MICROARCH.md, DVFS give-back item 7: the chip may hold a higher clock on
-// this shape).  The accumulators are handed to the epilogue in AccTile's storage with block (mi16, ni16) in v[mi16 >> 1][ni16 >> 1] registers
-// 8 (mi16 & 1) + 4 (ni16 & 1) .. + 3 — a layout no product epilogue understands.
-template <class T, bool SWAP = false, bool A_NT = false, bool M16 = false, class Coord, class Epilogue>
+template <class T, bool SWAP = false, bool A_NT = false, class Coord, class Epilogue>
 __device__ __forceinline__ void gemm_nt_pingpong(const uint16_t* __restrict__ A, int64_t lda, int64_t M, const uint16_t* __restrict__ B, int64_t ldb,
                                                  int64_t N, int K, int64_t total_tiles, char* smem, Coord&& coord, Epilogue&& epi) {
     using Shape = ShapePP;
@@ -660,57 +639,19 @@ __device__ __forceinline__ void gemm_nt_pingpong(const uint16_t* __restrict__ A,
     const int b_row_byte = (wq * 64 + frow) * 128;
 
     int cur = 0;   // ring slot of the K-tile being multiplied
-#ifdef KR_STAMP
-    unsigned long long st_gap = 0, st_loop = 0, st_epi = 0, st_t0 = KR_STAMP_NOW();
-    unsigned long long st_fine[6] = {0, 0, 0, 0, 0, 0};
-#endif
     for (int64_t i = 0; i < my; ++i) {
         int64_t m0, n0;
         const int64_t nat = xcd_chunk_map((int64_t)blockIdx.x + i * G, total_tiles);
         coord(nat, m0, n0);
-#ifdef KR_STAMP
-        const unsigned long long st_t1 = KR_STAMP_NOW();
-        st_gap += st_t1 - st_t0;
-#endif
         AccTile<Shape> acc;
         acc.m_wave = grp * 128;
         acc.n_wave = wq * 64;
         acc.lane = lane;
-        f32x4 c16[M16 ? 8 : 1][M16 ? 4 : 1];
         // One interval = L(t,h) (fragments of k-half h, 4 DMA pieces, counted waits) + barrier + M(t,h) (16 MFMAs, nothing else).  The first interval of
         // an output tile is a separate instantiation (FIRST): its first k-step takes the inline constant 0 as the C operand, so the accumulators are never
         // zero-initialised (128 v_mov per wave and tile at the boundary, where nothing overlaps them).
         auto interval = [&](auto first_tag, const char* sa, const char* sb, int h, bool last) {
             constexpr bool FIRST = decltype(first_tag)::value;
-            if constexpr (M16) {
-                uint4 af16[8], bf16v[4];
-                const int r16 = lane & 15;
-                const int coff16 = ((4 * h + (lane >> 4)) ^ ((r16 >> 1) & 7)) << 4;
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) bf16v[ni] = *reinterpret_cast<const uint4*>(sb + (wq * 64 + ni * 16 + r16) * 128 + coff16);
-#pragma unroll
-                for (int mi = 0; mi < 8; ++mi) af16[mi] = *reinterpret_cast<const uint4*>(sa + (grp * 128 + mi * 16 + r16) * 128 + coff16);
-                if (h == 0) issue4(cx, false, xpiece, offx); else issue4(cy, true, ypiece, offy);
-                wait_vmcnt<4>();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 4; ++ni) {
-                        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-                        if (FIRST) c16[mi][ni] = SWAP ? T::mfma16(bf16v[ni], af16[mi], zero4) : T::mfma16(af16[mi], bf16v[ni], zero4);
-                        else c16[mi][ni] = SWAP ? T::mfma16(bf16v[ni], af16[mi], c16[mi][ni]) : T::mfma16(af16[mi], bf16v[ni], c16[mi][ni]);
-                    }
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (!(last && grp)) __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                return;
-            }
             uint4 af[2][4], bf[2][2];
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2) {
@@ -762,157 +703,12 @@ __device__ __forceinline__ void gemm_nt_pingpong(const uint16_t* __restrict__ A,
             interval(std::false_type{}, sa, sa + ABYTES, 0, false);
             interval(std::false_type{}, sa, sa + ABYTES, 1, kt == nk - 1);
         }
-#ifdef KR_STAMP
-        const unsigned long long st_t2 = KR_STAMP_NOW();
-        st_loop += st_t2 - st_t1;
-        acc.fine_prev = st_t2;
-#endif
-        if constexpr (M16) {
-#pragma unroll
-            for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc.v[mi >> 1][ni >> 1][8 * (mi & 1) + 4 * (ni & 1) + e] = c16[mi][ni][e];
-        }
         epi(acc, m0, n0, nat);
-#ifdef KR_STAMP
-        st_t0 = KR_STAMP_NOW();
-        st_epi += st_t0 - st_t2;
-        for (int z = 0; z < 6; ++z) st_fine[z] += acc.fine[z];
-#endif
         if (grp) __builtin_amdgcn_s_barrier();
     }
-#ifdef KR_STAMP
-    if (lane == 0) {
-        unsigned long long* sb = kr_stamp_buf + (kr_stamp_slot & 7) * 32 + wave * 4;
-        atomicAdd(&sb[0], st_gap); atomicAdd(&sb[1], st_loop); atomicAdd(&sb[2], st_epi); atomicAdd(&sb[3], (unsigned long long)my);
-        for (int z = 0; z < 6; ++z) atomicAdd(&kr_stamp_fine[((kr_stamp_slot & 7) * 2 + grp) * 8 + z], st_fine[z]);
-    }
-#endif
     if (!grp) __builtin_amdgcn_s_barrier();   // group 0 started one interval early: same number of barriers for every wave
     wait_vmcnt<0>();                            // dummy tail DMAs must not land after the caller re-uses the ring
     __builtin_amdgcn_s_barrier();
-}
-
-
-// =====================================================================================================================
-// EXPERIMENT (tools/gemm_bench.hip only; not used by the product): ONE wave per SIMD.  256x256x64 tiles, 4 waves of 128x128 (256 accumulator registers
-// of the 512 a lone wave may use), ring of two 64-KiB K-tiles, ONE s_barrier per K-tile: K-tile g+1 is staged (16 LDS-DMA pieces per wave: waves 0, 1
-// the A rows, waves 2, 3 the B rows) while K-tile g is multiplied; the pieces are issued between the MFMAs of the first k-steps.  Purpose: measure what
-// the main loop alone sustains in this structure before building the deferred-store epilogue that is its reason to exist.
-// =====================================================================================================================
-using ShapeSolo = GemmShape<256, 256, 2, 2>;
-
-template <class T, bool SWAP = false, class Coord, class Epilogue>
-__device__ __forceinline__ void gemm_nt_solo(const uint16_t* __restrict__ A, int64_t lda, int64_t M, const uint16_t* __restrict__ B, int64_t ldb,
-                                             int64_t N, int K, int64_t total_tiles, char* smem, Coord&& coord, Epilogue&& epi) {
-    using Shape = ShapeSolo;
-    constexpr int BK = Shape::BK, STAGE = Shape::STAGE_BYTES, ABYTES = Shape::A_BYTES;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t G = gridDim.x;
-    const int64_t my = (total_tiles > (int64_t)blockIdx.x) ? (total_tiles - blockIdx.x + G - 1) / G : 0;
-    if (my == 0) return;
-    const int nk = K / BK;
-    const int64_t total_g = my * nk;
-    // ---- DMA cursor: this wave stages 16 pieces (128 rows) of ONE operand per K-tile: waves 0, 1 -> A rows 128 * wave .., waves 2, 3 -> B rows 128 * (wave - 2) ..
-    const bool isA = wave < 2;
-    const int row0 = (wave & 1) * 128;
-    int64_t c_tile = 0; int c_kt = 0;
-    const char* c_base = nullptr;
-    uint32_t c_off[16];
-    auto set_base = [&]() {
-        int64_t m0, n0;
-        coord(xcd_chunk_map((int64_t)blockIdx.x + c_tile * G, total_tiles), m0, n0);
-        const int64_t r0 = isA ? m0 : n0, ld = isA ? lda : ldb, left = (isA ? M : N) - r0;
-        c_base = reinterpret_cast<const char*>((isA ? A : B) + r0 * ld);
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-            int row = row0 + p * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-            if (row >= left) row = (int)left - 1;
-            c_off[p] = (uint32_t)(row * ld * 2 + chunk * 16);
-        }
-    };
-    set_base();
-    auto issue_pieces = [&](int slot, int p_begin, int p_end) {     // pieces [p_begin, p_end) of the cursor's K-tile into ring slot `slot`
-        char* dst = smem + slot * STAGE + (isA ? 0 : ABYTES) + row0 * 128;
-        const char* src = c_base + (int64_t)c_kt * (BK * 2);
-#pragma unroll
-        for (int p = p_begin; p < p_end; ++p)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(src + c_off[p]), (lds_void*)(dst + p * 1024), 16, 0, 0);
-    };
-    auto advance = [&]() {
-        if (c_kt + 1 < nk) ++c_kt;
-        else if (c_tile + 1 < my) { c_kt = 0; ++c_tile; set_base(); }
-    };
-    issue_pieces(0, 0, 16); advance();
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    if (total_g > 1) { issue_pieces(1, 0, 16); advance(); }            // K-tile 1 in flight while K-tile 0 is multiplied
-
-    const int frow = lane & 31, fh = lane >> 5;
-    const int fswz = (frow >> 1) & 7;
-    const int a_row_byte = (wm * 128 + frow) * 128;
-    const int b_row_byte = ABYTES + (wn * 128 + frow) * 128;
-    int64_t g = 0;
-    uint4 af[2][4], bf[2][4];
-    auto load_frags = [&](int64_t gg, int ks, int buf) {
-        const char* st = smem + (int)(gg & 1) * STAGE;
-        const int coff = ((2 * ks + fh) ^ fswz) << 4;
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) af[buf][mi] = *reinterpret_cast<const uint4*>(st + a_row_byte + mi * 32 * 128 + coff);
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) bf[buf][ni] = *reinterpret_cast<const uint4*>(st + b_row_byte + ni * 32 * 128 + coff);
-    };
-    load_frags(0, 0, 0);
-    for (int64_t i = 0; i < my; ++i) {
-        int64_t m0, n0;
-        const int64_t nat = xcd_chunk_map((int64_t)blockIdx.x + i * G, total_tiles);
-        coord(nat, m0, n0);
-        AccTile<Shape> acc;
-        acc.m_wave = wm * 128; acc.n_wave = wn * 128; acc.lane = lane;
-        // Software pipeline per K-tile g (fragments of its k-step 0 are already in buffer 0):
-        //   k-steps 0, 1, 2   MFMAs + the fragment reads of the next k-step
-        //   wait (own DMA pieces of K-tile g + 1 landed, own LDS reads done) + s_barrier: K-tile g + 1 is resident, nobody reads K-tile g any more
-        //   issue the 16 DMA pieces of K-tile g + 2 into K-tile g's slot and read the fragments of (g + 1, k-step 0)  -- under the MFMAs of k-step 3
-        // The first K-tile of an output tile is a separate instantiation (C operand 0 in its first k-step; a run-time branch there costs > 100 spills).
-        auto mfmas = [&](auto first_tag, int ks) {
-            constexpr bool FIRST = decltype(first_tag)::value;
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) {
-                    if constexpr (FIRST) {
-                        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        acc.v[mi][ni] = SWAP ? T::mfma(bf[ks & 1][ni], af[ks & 1][mi], zero) : T::mfma(af[ks & 1][mi], bf[ks & 1][ni], zero);
-                    } else {
-                        acc.v[mi][ni] = SWAP ? T::mfma(bf[ks & 1][ni], af[ks & 1][mi], acc.v[mi][ni]) : T::mfma(af[ks & 1][mi], bf[ks & 1][ni], acc.v[mi][ni]);
-                    }
-                }
-        };
-        auto ktile = [&](auto first_tag) {
-            load_frags(g, 1, 1);
-            mfmas(first_tag, 0);
-            load_frags(g, 2, 0);
-            mfmas(std::false_type{}, 1);
-            load_frags(g, 3, 1);
-            mfmas(std::false_type{}, 2);
-            wait_vmcnt<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (g + 2 < total_g) { issue_pieces((int)(g & 1), 0, 16); advance(); }
-            if (g + 1 < total_g) load_frags(g + 1, 0, 0);
-            mfmas(std::false_type{}, 3);
-            ++g;
-        };
-        ktile(std::true_type{});
-        for (int kt = 1; kt < nk; ++kt) ktile(std::false_type{});
-        epi(acc, m0, n0, nat);
-    }
 }
 
 }  // namespace kr

@@ -100,13 +100,10 @@ struct VBuf {
         handles.clear(); mapped = 0;
         // The address range is deliberately NOT handed back (hipMemAddressFree): on ROCm 7.2 / gfx950 a range that is freed, reserved again (the runtime
         // returns the same addresses) and mapped to new physical chunks is read by kernels through stale translations — the fp32 rows a copy engine
-        // reads back are correct while the scan kernels see other memory (found by tests/soak_gpu.py; tools/vmm_va_reuse_repro.py, fixed when the range
+        // reads back are correct while the scan kernels see other memory (found by tests/soak_gpu.py; fixed when the range
         // is never reused).  Physical memory IS returned (unmap + release above); only virtual addresses are retired, counted in g_va_retired, and
         // grow() stops using this path before the 47-bit address space could run short.
-        if (base) {
-            if (getenv("KIRAG_AMD_DEBUG_FREE_VA")) (void)hipMemAddressFree(base, reserved);   // the broken behaviour, for the repro tool only
-            else g_va_retired.fetch_add(reserved);
-        }
+        if (base) g_va_retired.fetch_add(reserved);
         base = nullptr; reserved = 0;
     }
 };
@@ -2723,15 +2720,6 @@ int kr_score_topk(const float* q, int nq, const float* x, int64_t n, int d, int 
     KR_HIP(hipStreamSynchronize(st));
     return 0;
 }
-
-#ifdef KR_STAMP
-// diagnostic build only: read and clear the per-wave stamp sums of gemm_nt_pingpong (this translation unit's copy: the coarse scan)
-int kr_debug_read_stamps(unsigned long long* out256) {
-    if (hipMemcpyFromSymbol(out256, HIP_SYMBOL(kr_stamp_buf), 256 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long z[256] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(kr_stamp_buf), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 void kr_release_scratch(void) {
     std::lock_guard<std::mutex> lock(g_scratch_mu);

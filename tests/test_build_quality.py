@@ -3,7 +3,9 @@
 A spilled vector register is a scratch store / reload — a VMEM operation in the same in-order queue as the LDS-DMA rings, which hipcc follows with
 `s_waitcnt vmcnt(0)`: in round 3's library that drained the ring in the V^T tiles of the QKV projection and in front of the DMA of k_attn_dma's
 partial chunk.  The library must carry none."""
+import glob
 import os
+import re
 import sys
 
 import pytest
@@ -56,3 +58,21 @@ def test_no_kernel_uses_v_ashr_pk_u8_i32():
     if not os.path.exists(kernel_notes.OBJDUMP):
         pytest.skip("llvm-objdump not installed")
     assert kernel_notes.count_instruction(LIB, "v_ashr_pk_u8_i32") == 0
+
+
+def test_preprocessor_conditionals_name_only_the_build_switches():
+    """Experiment variants do not live in the HIP sources (kirag_amd/csrc/Makefile): every #if / #ifdef / #ifndef / #elif there names only the f16
+    build of encoder.hip (KR_ENC_BUILD_F16) or the device pass of the compiler (__HIP_DEVICE_COMPILE__), so the product build is the only build."""
+    allowed = {"defined", "KR_ENC_BUILD_F16", "__HIP_DEVICE_COMPILE__"}
+    srcs = sorted(glob.glob(os.path.join(REPO, "kirag_amd", "csrc", "*.hip")) + glob.glob(os.path.join(REPO, "kirag_amd", "csrc", "*.hpp")))
+    assert srcs
+    bad = []
+    for path in srcs:
+        text = re.sub(r"/\*.*?\*/", " ", open(path).read().replace("\\\n", " "), flags=re.S)
+        for line in text.splitlines():
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line.split("//")[0])
+            if m:
+                names = set(re.findall(r"[A-Za-z_]\w*", m.group(2))) - allowed
+                if names:
+                    bad.append("%s: #%s %s" % (os.path.basename(path), m.group(1), " ".join(sorted(names))))
+    assert not bad, bad

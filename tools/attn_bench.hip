@@ -1,6 +1,6 @@
 // Micro-benchmark of the long-sequence attention kernel (kirag_amd/csrc/encoder.hip: k_attn_dma) on synthetic f16 Q / K / V^T of B sequences x S tokens,
-// 16 heads x 64:   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DKR_STAMP_ATTN] tools/attn_bench.hip -o gpurun_out/attn_bench && ./gpurun_out/attn_bench [B S]
-// Prints us per launch (HIP events), TFLOP/s of the two MFMA products, a checksum of ctx, and with -DKR_STAMP_ATTN the per-wave cycle split of the chunk loop.
+// 16 heads x 64:   mkdir -p tools/bin && hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/attn_bench.hip -o tools/bin/attn_bench && tools/bin/attn_bench [B S]
+// Prints us per launch (HIP events), TFLOP/s of the two MFMA products and a checksum of ctx.
 #define KR_ENC_BUILD_F16 1
 #include "../kirag_amd/csrc/encoder.hip"
 
@@ -44,9 +44,6 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int i = 0; i < 3; ++i) launch();
     CK(hipDeviceSynchronize());
-#ifdef KR_STAMP_ATTN
-    unsigned long long zero[8] = {}; CK(hipMemcpyToSymbol(HIP_SYMBOL(kr_attn_stamps), zero, sizeof zero));
-#endif
     const int reps = 20;
     CK(hipEventRecord(e0));
     for (int i = 0; i < reps; ++i) launch();
@@ -57,11 +54,5 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(hc.data(), ctx, hc.size() * 2, hipMemcpyDeviceToHost));
     double sum = 0; for (size_t i = 0; i < hc.size(); i += 97) { _Float16 h; __builtin_memcpy(&h, &hc[i], 2); sum += (double)(float)h; }
     printf("k_attn_dma %d x %d (+%d B LDS): %.1f us per launch, %.0f TFLOP/s (QK^T + PV), ctx checksum %.6f\n", B, S, extra_lds, us, fl / us / 1e6, sum);
-#ifdef KR_STAMP_ATTN
-    unsigned long long st[8]; CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(kr_attn_stamps), sizeof st));
-    const double w = (double)st[4], chunks = (double)(S / 64);
-    printf("  per wave: lifetime %.0f cycles; per chunk: barrier/wait/issue %.0f, tile 0 step %.0f, tile 1 step %.0f; outside the chunk loop %.0f\n", st[3] / w,
-           st[0] / w / chunks, st[1] / w / chunks, st[2] / w / chunks, (st[3] - st[0] - st[1] - st[2]) / w);
-#endif
     return 0;
 }
