@@ -10,10 +10,15 @@ With --gpus N the SAME job is split over the ranks (strong scaling, SURVEY.md 8e
 (5M / N rows per GPU), every rank encodes its 1/N slice of the query batch, the query embeddings are all-gathered (RCCL, nq*4 KiB),
 every rank searches all queries on its shard, and the per-shard top-100 are all-gathered and merged on the host.
 
-Prints ONE JSON line on rank 0 (see the round brief for the contract) including
-    "roofline"      for the dominant kernel (the MFMA coarse scan k_coarse), timed live with HIP events
+Prints ONE JSON line on rank 0 including
+    "roofline"      for the dominant kernel (the MFMA coarse scan k_coarse), timed live with HIP events during the timed steps
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  With --full it then also measures
+    "encode"        passages-encoded/s at the passage shape (fixed and ragged lengths) and, at N = 1, from passage text (entry_point)
+    "latency"       small-batch forwards and one KiRAG hop, at the C ABI and at the reference's surface (N = 1)
+    "surface"       Indexer.search_knn next to the C-ABI search (N = 1)
     "cpu_baseline"  the reference's CPU path timed on the host cores on a bounded sample of the same step: HF BertModel fp32 query
-                    encoding (oracle/encoder_torch.py) + the oracle's fp32 sgemm + top-k stand-in for faiss.IndexFlatIP
+                    encoding (oracle/encoder_torch.py) + the oracle's fp32 sgemm + top-k stand-in for faiss.IndexFlatIP (N = 1)
+In a --full run --no-latency, --no-surface, --no-cpu-baseline and --no-entry-point skip their block.
 """
 import argparse
 import json
@@ -54,15 +59,18 @@ def parse():
                          "with one host synchronisation per block; 'queries' = every rank encodes 1/W of every batch, step by step (round-2 schedule)")
     ap.add_argument("--search-stream", action="store_true", help="one GPU experiment: enqueue the search of step i on a second stream (overlaps the encode of step i + 1)")
     ap.add_argument("--sync-search", action="store_true", help="one GPU: use the blocking kr_index_search per step instead of search_async + finish")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the small-batch latency block (forwards of the reference's real batch shapes + one KiRAG hop)")
-    ap.add_argument("--no-entry-point", action="store_true", help="skip the cal_doc_embeddings-from-text measurement (encode.entry_point)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the passage-encode legs, and at N = 1 the latency, entry-point "
+                         "and surface blocks and the CPU baseline (off by default: a plain run stops after the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the small-batch latency block (forwards of the reference's real batch shapes + one KiRAG hop)")
+    ap.add_argument("--no-entry-point", action="store_true", help="--full: skip the cal_doc_embeddings-from-text measurement (encode.entry_point)")
     ap.add_argument("--entry-passages", type=int, default=65536, help="synthetic text passages of the encode.entry_point block")
-    ap.add_argument("--no-surface", action="store_true", help="skip the reference-surface search measurement (Indexer.search_knn on --surface-queries queries)")
-    ap.add_argument("--surface", action="store_true", help="(default on at N = 1) report queries/s of Indexer.search_knn next to the C-ABI search on the same queries")
+    ap.add_argument("--no-surface", action="store_true", help="--full: skip the reference-surface search measurement (Indexer.search_knn on --surface-queries queries)")
+    ap.add_argument("--surface", action="store_true", help="(default on with --full at N = 1) report queries/s of Indexer.search_knn next to the C-ABI search on the same queries")
     ap.add_argument("--surface-queries", type=int, default=4096)
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000, help="corpus rows of the CPU search baseline (BASELINE.md: the 1M point)")
-    ap.add_argument("--cpu-full-corpus", action="store_true", help="CPU search baseline over ALL corpus rows (the 5M point: ~20 GB of host memory, minutes)")
+    ap.add_argument("--cpu-full-corpus", action="store_true", help="--full: CPU search baseline over ALL corpus rows (the 5M point: ~20 GB of host memory, minutes)")
     ap.add_argument("--cpu-sample-queries", type=int, default=32)
     ap.add_argument("--corpus-dist", default="gaussian", choices=["gaussian", "e5like", "mixed", "neardup"],
                     help="synthetic corpus: iid Gaussian directions (SURVEY 8d) or e5like (shared mean direction + anisotropic remainder: scores in a "
@@ -480,7 +488,6 @@ def main():
         from kirag_amd import bench_support as BS
         encoder = BS.make_hip_encoder(dev, operand_dtype=args.encoder_dtype, residual_lo=None if args.residual_lo is None else bool(args.residual_lo))
         tok_ids, tok_mask = BS.synthetic_tokens(dev, nq, args.query_tokens, seed=2)
-        pas_ids, pas_mask = BS.synthetic_tokens(dev, args.passages, args.passage_tokens, seed=1)
     searcher = ShardedSearcher(index, row_offset=row0, world=world, collective=args.collective)
     q_all = torch.empty((nq, d), dtype=torch.float32, device=dev)
     counts = [((r + 1) * nq) // world - (r * nq) // world for r in range(world)]
@@ -612,8 +619,9 @@ def main():
         dump_outputs(args.dump_outputs, *last)
 
     enc_info = None
-    if encoder is not None:
+    if encoder is not None and args.full:
         # passages-encoded/s leg of the metric (BASELINE config 1/2 passage shape: 128 tokens), same protocol
+        pas_ids, pas_mask = BS.synthetic_tokens(dev, args.passages, args.passage_tokens, seed=1)
         for _ in range(max(1, args.warmup)):
             encoder.forward(pas_ids, pas_mask, 0)
         if world > 1:
@@ -710,17 +718,18 @@ def main():
                                  "around each launch on its stream; algorithmic FLOPs = 2*nq*rows*dim; the bf16 MFMA-only loop measured on this "
                                  "device sustains ~1.6-1.7 PFLOP/s on random data (tools/gemm_bench.hip); peak = the 2.4-GHz nameplate, the kernel's counter-measured "
                                  "sustained clock is in sustained_clock_ghz: frac_of_clock_adjusted_peak = frac * 2.4 / clock = what the chip offers at the clock it holds"},
-            "encode": enc_info,
             "search_stats": {kk: st[kk] for kk in ("queries", "certified", "fallback", "fine", "exact", "overflow", "reranked_rows", "coarse_rounds", "fine_rounds", "marked_passes", "marked_rows")},
         }
-        if world == 1 and encoder is not None and not args.no_latency:
-            out["latency"] = latency_block(args, encoder, index, dev)
-        if world == 1 and encoder is not None and not args.no_entry_point:
-            out["encode"]["entry_point"] = entry_point_block(args, encoder, dev)
-        if world == 1 and not args.no_surface:
-            out["surface"] = surface_block(args, index, q_vec, dev)
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
-            out["cpu_baseline"] = cpu_baseline(args, q_vec.cpu().numpy(), encoder is not None, args.corpus_dist, index)
+        if args.full:
+            out["encode"] = enc_info
+            if world == 1 and encoder is not None and not args.no_latency:
+                out["latency"] = latency_block(args, encoder, index, dev)
+            if world == 1 and encoder is not None and not args.no_entry_point:
+                out["encode"]["entry_point"] = entry_point_block(args, encoder, dev)
+            if world == 1 and not args.no_surface:
+                out["surface"] = surface_block(args, index, q_vec, dev)
+            if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
+                out["cpu_baseline"] = cpu_baseline(args, q_vec.cpu().numpy(), encoder is not None, args.corpus_dist, index)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -1,4 +1,4 @@
-"""The committed bench line (profiles/rNN/bench_plain.json of the NEWEST round that has one, produced by `python bench.py` on an MI355X) carries every
+"""The committed bench line (profiles/rNN/bench_plain.json of the NEWEST round that has one, produced by `python bench.py --full` on an MI355X) carries every
 field of the driver's contract, with consistent arithmetic.  bench.py itself needs a GPU; this checks the artefact the round ships."""
 import glob
 import json
@@ -65,6 +65,7 @@ def test_bench_defaults_are_the_metric_configuration():
         sys.argv = argv
     assert (a.gpus, a.total_rows, a.queries, a.topk, a.dim, a.query_tokens, a.passage_tokens) == (1, 5_000_000, 1000, 100, 1024, 32, 128)
     assert a.steps * 35e-3 < 60 and a.coarse_dtype == "bf16"        # the default run finishes within minutes
+    assert a.full is False                                          # a plain run measures the headline only; --full adds the other blocks
 
 
 def _run_bench(extra, env_extra=None, timeout=600):
@@ -114,6 +115,31 @@ def test_bench_gpus_2_real_step_on_one_box(split, steps, tmp_path):
     s, r = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "rows.npy")
     assert s.dtype == np.float32 and s.shape == r.shape == (256, 100) and np.all(np.diff(s, axis=1) <= 0)
     assert np.all((r >= 0) & (r < 300000)) and (r < 150000).any() and (r >= 150000).any()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_full_adds_the_other_blocks(tmp_path):
+    """A plain run prints the headline line (roofline and search statistics of the timed steps included) and measures nothing else; --full adds the
+    passage-encode legs and the latency, entry-point and surface blocks (the CPU baseline is skipped here: minutes of host time).  Both runs dump the
+    same lists: what follows the timed steps does not touch them."""
+    import numpy as np
+    small = ["--total-rows", "300000", "--queries", "256", "--passages", "64", "--steps", "2", "--warmup", "1", "--entry-passages", "1024",
+             "--surface-queries", "1100"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        p, out = _run_bench(small + extra + ["--dump-outputs", str(tmp_path / name)], timeout=600)
+        assert p.returncode == 0 and len(out) == 1, p.stderr[-3000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["value"] > 0 and abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6 and d["roofline"]["launch_ms"] > 0
+        assert d["search_stats"]["queries"] == 2 * 256
+    assert not {"encode", "latency", "surface", "cpu_baseline"} & set(plain)
+    assert full["encode"]["passages_per_s"] > 0 and full["encode"]["ragged"]["passages_per_s_per_gpu"] > 0 and full["encode"]["entry_point"]["passages"] == 1024
+    assert set(full["latency"]["forwards"]) == {"1x32", "1x256", "8x128", "125x32"} and full["surface"]["lists_match_c_abi"] is True
+    assert "cpu_baseline" not in full
+    for f in ("scores", "rows", "query_index"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (f + ".npy")), np.load(tmp_path / "full" / (f + ".npy"))), f
 
 
 def test_steps_below_one_are_refused():
