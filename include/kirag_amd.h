@@ -215,9 +215,9 @@ int kr_shard_allgather_topk(kr_comm* c, const float* scores_local, const int64_t
 typedef struct kr_encoder kr_encoder;
 
 typedef struct {
-    int hidden;        /* H   (1024 for e5-large-v2 / bge-large-en) */
-    int layers;        /* L   (24) */
-    int heads;         /* 16; hidden / heads must be 64 */
+    int hidden;        /* H   (1024 for e5-large-v2 / bge-large-en, 384 for e5-small-v2 / bge-small-en / MiniLM); multiple of 128, <= 2048 */
+    int layers;        /* L   (24; 12 / 6 for the small models) */
+    int heads;         /* 16 (12 for the small models); hidden / heads (the head width) must be 32 or 64, anything else is KR_EINVAL */
     int intermediate;  /* FF  (4096) */
     int vocab;         /* 30522 */
     int max_pos;       /* 512 */

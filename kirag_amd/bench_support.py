@@ -10,6 +10,10 @@ from .retriever.encoders import HipBertForward
 
 E5_LARGE = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096, vocab_size=30522,
                 max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12, hidden_act="gelu")
+# the small siblings (e5-small-v2, bge-small-en-v1.5, gte-small: 12 layers; all-MiniLM-L6-v2: 6): 12 heads of 32
+E5_SMALL = dict(E5_LARGE, hidden_size=384, num_hidden_layers=12, num_attention_heads=12, intermediate_size=1536)
+MINILM_L6 = dict(E5_SMALL, num_hidden_layers=6)
+ENCODER_SHAPES = {"e5-large": E5_LARGE, "e5-small": E5_SMALL, "minilm-l6": MINILM_L6}
 
 
 def synthetic_state(cfg: SimpleNamespace, device, seed: int = 0):

@@ -729,7 +729,7 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
 // one value per lane and ni.  Token-indexed buffers are allocated in multiples of 256 rows, so a partial last token tile needs no bounds
 // test (rows >= T are written with values computed from clamped loads and never read).
 // Tiles are walked in patches of (token tiles x 8 feature tiles) per XCD so operand slices are reused from that XCD's L2.
-//   EPI_QKV:   F = 3H: features [0,H) -> q (bias, 1/8 folded into the weights), [H,2H) -> k, [2H,3H) -> V^T (its bias lives in bo_eff)
+//   EPI_QKV:   F = 3H: features [0,H) -> q (bias, log2(e) / sqrt(d_h) folded into the weights), [H,2H) -> k, [2H,3H) -> V^T (its bias lives in bo_eff)
 //   EPI_DENSE: out0[T,F] = acc as bf16 (k_ln adds the bias and the residual in fp32)
 //   EPI_GELU:  out0[T,F] = gelu(acc + bias)
 template <int EPI, class ShapeE, bool NT>
@@ -861,24 +861,36 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
 // perm(i) = i with bits 2 and 3 exchanged: a lane's registers 8a .. 8a+7 then hold 8 CONSECUTIVE keys (16 a + 8 hf .. + 7), i.e. the P^T fragment of a
 // k-step matches one contiguous 16-byte run of a V^T row (without the permutation a lane owns keys {0..3, 8..11} + 4 hf: two 8-byte reads per fragment).
 // The permutation maps each ds_read_b128 lane group onto itself, so the K reads stay bank-conflict free.
-//   K image   128-B rows, 16-B chunk index XOR ((key >> 1) & 7) (same image as the GEMM ring)
-//   V^T image k_attn_lds: row pitch 2 * cap + 8 bytes (pitch / 8 odd: conflict-free ds_read_b64), keys >= nk stored as zero;
-//             k_attn_dma: [64 d][128 B] per chunk, chunk index XOR ((d >> 1) & 7) like the K image (one ds_read_b128 per fragment), columns >= nk of
-//             the last chunk zeroed in LDS after they landed (no 0 * NaN from rows of other sequences).
-// The O tile is staged through a wave-private 4-KiB LDS block and stored as whole 128-B rows of ctx.
+// Everything is a template on the head width DH (32 or 64): S^T takes DH / 16 k-steps of the 32x32x16 MFMA, O^T is DH / 32 accumulators of 32 d rows.
+//   K image   rows of 2 DH bytes (DH / 8 16-B chunks), chunk index XOR attn_kswz<DH>(key): DH = 64 128-B rows, XOR ((key >> 1) & 7) (same image as the
+//             GEMM ring); DH = 32 64-B rows, XOR ((key >> 2) & 3).  Either way the 16 lanes of a ds_read_b128 group (keys {0..3, 12..15, 20..27} or
+//             {4..11, 16..19, 28..31} of a 32-key tile) land on 16 different 16-B slots of a 256-B bank window
+//   V^T image k_attn_lds: DH rows, row pitch 2 * cap + 8 bytes (pitch / 8 odd: conflict-free ds_read_b64), keys >= nk stored as zero;
+//             k_attn_dma: [DH d][128 B] per chunk, chunk index XOR ((d >> 1) & 7) like the 64-wide K image (one ds_read_b128 per fragment), columns >= nk
+//             of the last chunk zeroed in LDS after they landed (no 0 * NaN from rows of other sequences).
+// The O tile is staged through a wave-private LDS block of 32 x 2 DH bytes and stored as whole 2 DH-byte rows of ctx at column head * DH.
 // ---------------------------------------------------------------------------------------------------------
+template <int DH>
 struct AttnState {
-    f32x16 o0, o1;
+    static_assert(DH == 32 || DH == 64, "head width 32 or 64");
+    f32x16 o[DH / 32];  // O^T of the tile: d rows 32 j .. 32 j + 31 in o[j]
     float mref, l;      // reference maximum (log2 units) the accumulated o / l are scaled by; running denominator
 };
 
-__device__ __forceinline__ void attn_init(AttnState& s) {
+template <int DH>
+__device__ __forceinline__ void attn_init(AttnState<DH>& s) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { s.o0[r] = 0.f; s.o1[r] = 0.f; }
+    for (int j = 0; j < DH / 32; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s.o[j][r] = 0.f;
     s.mref = -INFINITY; s.l = 0.f;
 }
 
 __device__ __forceinline__ int attn_perm(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
+
+// 16-B chunk swizzle of row `key` of a K image with 2 DH-byte rows (128 / DH rows per 256-B bank window)
+template <int DH>
+__device__ __forceinline__ int attn_kswz(int key) { return (key >> (DH == 64 ? 1 : 2)) & (DH / 8 - 1); }
 
 // One 64-key step of a wave's 32-query tile.  Kst: K image (128-B rows, swizzled), k0 = row of the step's first key in it; nvalid = keys of the
 // step that exist (MASKED instantiation: < 64; <= 32: the second 32-key tile is skipped — it would only add exact zeros); vfrag(dh, ks) returns the
@@ -894,44 +906,45 @@ constexpr float ATTN_RESCALE_THR = 8.0f;
 // 2 = exactly 32 (one full tile: a 32-token sequence), 3 = 33 .. 63 (second tile masked)
 // PF (k_attn_dma): all K fragments of the step are requested before the first MFMA (counted lgkmcnt waits instead of one exposed LDS round trip per
 // MFMA); same MFMAs in the same order, so the result does not depend on it
-template <int MODE, bool PF = false>
-__device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint4 (&qf)[4], const char* Kst, int k0, int nvalid, int c, int hf) {
+template <int DH, int MODE, bool PF = false>
+__device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf) {
     constexpr bool two = MODE == 0 || MODE == 3;
+    constexpr int NK = DH / 16, KR = 2 * DH;              // k-steps of S^T; bytes per K row
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if constexpr (PF) {
         const int key = k0 + attn_perm(c);
-        const char* krow = Kst + key * 128;
-        const int swz = (key >> 1) & 7;
-        uint4 kf[two ? 8 : 4];
+        const char* krow = Kst + key * KR;
+        const int swz = attn_kswz<DH>(key);
+        uint4 kf[two ? 2 * NK : NK];
 #pragma unroll
-        for (int sk = 0; sk < 4; ++sk) kf[sk] = *reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4));
+        for (int sk = 0; sk < NK; ++sk) kf[sk] = *reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4));
         if constexpr (two) {
 #pragma unroll
-            for (int sk = 0; sk < 4; ++sk) kf[4 + sk] = *reinterpret_cast<const uint4*>(krow + 32 * 128 + (((2 * sk + hf) ^ swz) << 4));
+            for (int sk = 0; sk < NK; ++sk) kf[NK + sk] = *reinterpret_cast<const uint4*>(krow + 32 * KR + (((2 * sk + hf) ^ swz) << 4));
         }
         st0 = ET::mfma(kf[0], qf[0], zero);
 #pragma unroll
-        for (int sk = 1; sk < 4; ++sk) st0 = ET::mfma(kf[sk], qf[sk], st0);
+        for (int sk = 1; sk < NK; ++sk) st0 = ET::mfma(kf[sk], qf[sk], st0);
         if constexpr (two) {
-            st1 = ET::mfma(kf[4], qf[0], zero);
+            st1 = ET::mfma(kf[NK], qf[0], zero);
 #pragma unroll
-            for (int sk = 1; sk < 4; ++sk) st1 = ET::mfma(kf[4 + sk], qf[sk], st1);
+            for (int sk = 1; sk < NK; ++sk) st1 = ET::mfma(kf[NK + sk], qf[sk], st1);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) st1[r] = -INFINITY;
         }
     } else {
         const int key = k0 + attn_perm(c);
-        const char* krow = Kst + key * 128;
-        const int swz = (key >> 1) & 7;
+        const char* krow = Kst + key * KR;
+        const int swz = attn_kswz<DH>(key);
         st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((0 + hf) ^ swz) << 4)), qf[0], zero);
 #pragma unroll
-        for (int sk = 1; sk < 4; ++sk) st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st0);
+        for (int sk = 1; sk < NK; ++sk) st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st0);
         if (two) {
-            const char* krow1 = krow + 32 * 128;          // (key + 32) >> 1 & 7 == swz
+            const char* krow1 = krow + 32 * KR;           // attn_kswz(key + 32) == swz
             st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((0 + hf) ^ swz) << 4)), qf[0], zero);
 #pragma unroll
-            for (int sk = 1; sk < 4; ++sk) st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st1);
+            for (int sk = 1; sk < NK; ++sk) st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st1);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) st1[r] = -INFINITY;      // never read (two == false below)
@@ -950,13 +963,16 @@ __device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint
 }
 
 // second half: online softmax and O^T += V^T . P^T
-template <int MODE, bool PF = false, class VFrag>
-__device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0, const f32x16& st1, VFrag&& vfrag) {
+template <int MODE, bool PF = false, int DH, class VFrag>
+__device__ __forceinline__ void attn_softmax_pv(AttnState<DH>& s, const f32x16& st0, const f32x16& st1, VFrag&& vfrag) {
     constexpr bool two = MODE == 0 || MODE == 3;
-    uint4 vpre[PF ? (two ? 8 : 4) : 1];
+    constexpr int ND = DH / 32;                          // accumulators of O^T
+    uint4 vpre[PF ? (two ? 4 : 2) * ND : 1];
     if constexpr (PF) {                                  // the V^T fragments land under the maximum / rescale arithmetic
 #pragma unroll
-        for (int ks = 0; ks < (two ? 4 : 2); ++ks) { vpre[2 * ks] = vfrag(0, ks); vpre[2 * ks + 1] = vfrag(1, ks); }
+        for (int ks = 0; ks < (two ? 4 : 2); ++ks)
+#pragma unroll
+            for (int j = 0; j < ND; ++j) vpre[ND * ks + j] = vfrag(j, ks);
     }
     float tmax = fmaxf(fmaxf(st0[0], st0[1]), st0[2]);
 #pragma unroll
@@ -973,7 +989,8 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
         const float mnew = fmaxf(s.mref, tmax);
         const float alpha = fresh ? 1.f : __builtin_amdgcn_exp2f(s.mref - mnew);   // fresh: o = l = 0 (and mref - mnew is -inf - x)
         s.l *= alpha;
-        s.o0 *= alpha; s.o1 *= alpha;
+#pragma unroll
+        for (int j = 0; j < ND; ++j) s.o[j] *= alpha;
         s.mref = mnew;
     }
     const float mshift = (s.mref == -INFINITY) ? 0.f : s.mref;   // still -inf: no valid key so far, every score is -inf and stays so
@@ -989,11 +1006,11 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
             uint4 pf;
             pf.x = pack_bf16x2(e[0], e[1]); pf.y = pack_bf16x2(e[2], e[3]); pf.z = pack_bf16x2(e[4], e[5]); pf.w = pack_bf16x2(e[6], e[7]);
             if constexpr (PF) {
-                s.o0 = ET::mfma(vpre[2 * (ks0 + a)], pf, s.o0);
-                s.o1 = ET::mfma(vpre[2 * (ks0 + a) + 1], pf, s.o1);
+#pragma unroll
+                for (int j = 0; j < ND; ++j) s.o[j] = ET::mfma(vpre[ND * (ks0 + a) + j], pf, s.o[j]);
             } else {
-                s.o0 = ET::mfma(vfrag(0, ks0 + a), pf, s.o0);
-                s.o1 = ET::mfma(vfrag(1, ks0 + a), pf, s.o1);
+#pragma unroll
+                for (int j = 0; j < ND; ++j) s.o[j] = ET::mfma(vfrag(j, ks0 + a), pf, s.o[j]);
             }
         }
     };
@@ -1003,50 +1020,61 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState& s, const f32x16& st0,
     s.l += psum;
 }
 
-template <int MODE, bool PF = false, class VFrag>
-__device__ __forceinline__ void attn_step64m(AttnState& s, const uint4 (&qf)[4], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
+template <int MODE, bool PF = false, int DH, class VFrag>
+__device__ __forceinline__ void attn_step64m(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
     f32x16 st0, st1;
-    attn_scores<MODE, PF>(st0, st1, qf, Kst, k0, nvalid, c, hf);
+    attn_scores<DH, MODE, PF>(st0, st1, qf, Kst, k0, nvalid, c, hf);
     attn_softmax_pv<MODE, PF>(s, st0, st1, vfrag);
 }
 // MASKED = false: 64 valid keys; true: fewer (nvalid says how many)
-template <bool MASKED, bool PF = false, class VFrag>
-__device__ __forceinline__ void attn_step64(AttnState& s, const uint4 (&qf)[4], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
+template <bool MASKED, bool PF = false, int DH, class VFrag>
+__device__ __forceinline__ void attn_step64(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
     if constexpr (!MASKED) attn_step64m<0, PF>(s, qf, Kst, k0, 64, c, hf, vfrag);
     else if (nvalid == 32) attn_step64m<2>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
     else if (nvalid < 32) attn_step64m<1>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
     else attn_step64m<3>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
 }
 
-// normalise a finished 32-query tile and store it as whole 128-B rows of ctx through the wave-private 4-KiB LDS block Os
-__device__ __forceinline__ void attn_store_tile(const AttnState& s, char* Os, uint16_t* __restrict__ ctx, int64_t off, int q0, int nq, int H, int head, int lane) {
+// normalise a finished 32-query tile and store it as whole 2 DH-byte rows of ctx (columns head * DH ..) through the wave-private LDS block Os of
+// 32 x 2 DH bytes (8-byte chunk index XOR the row)
+template <int DH>
+__device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os, uint16_t* __restrict__ ctx, int64_t off, int q0, int nq, int H, int head, int lane) {
+    constexpr int RB = 2 * DH, C8 = DH / 4, LR = DH / 8;  // row bytes, 8-byte chunks per row, lanes per row in the store
     asm volatile("" : "+v"(lane));   // opaque: the store addresses are computed here, after the key loop, instead of living in registers (or scratch) across it
     const int c = lane & 31, hf = lane >> 5;
     // a query with no attendable key (all-masked sequence) is 0/0 = NaN, as under HF's -inf masking
     const float inv = 1.0f / s.l;
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
-        uint2 w0, w1;
-        w0.x = pack_bf16x2(s.o0[4 * gq + 0] * inv, s.o0[4 * gq + 1] * inv); w0.y = pack_bf16x2(s.o0[4 * gq + 2] * inv, s.o0[4 * gq + 3] * inv);
-        w1.x = pack_bf16x2(s.o1[4 * gq + 0] * inv, s.o1[4 * gq + 1] * inv); w1.y = pack_bf16x2(s.o1[4 * gq + 2] * inv, s.o1[4 * gq + 3] * inv);
-        const int j8 = 2 * gq + hf;     // 8-byte chunk (4 features) of the 128-B row of query c
-        *reinterpret_cast<uint2*>(Os + c * 128 + ((j8 ^ (c & 15)) << 3)) = w0;
-        *reinterpret_cast<uint2*>(Os + c * 128 + (((8 + j8) ^ (c & 15)) << 3)) = w1;
+        uint2 w[DH / 32];
+#pragma unroll
+        for (int j = 0; j < DH / 32; ++j) {
+            w[j].x = pack_bf16x2(s.o[j][4 * gq + 0] * inv, s.o[j][4 * gq + 1] * inv); w[j].y = pack_bf16x2(s.o[j][4 * gq + 2] * inv, s.o[j][4 * gq + 3] * inv);
+        }
+#pragma unroll
+        for (int j = 0; j < DH / 32; ++j) {
+            const int j8 = 8 * j + 2 * gq + hf;     // 8-byte chunk (4 features) of the row of query c
+            *reinterpret_cast<uint2*>(Os + c * RB + ((j8 ^ (c & (C8 - 1))) << 3)) = w[j];
+        }
     }
 #pragma unroll
-    for (int p4 = 0; p4 < 4; ++p4) {
-        const int rq = p4 * 8 + (lane >> 3), ch = lane & 7;
-        const uint2 lo = *reinterpret_cast<const uint2*>(Os + rq * 128 + (((2 * ch) ^ (rq & 15)) << 3));
-        const uint2 hi = *reinterpret_cast<const uint2*>(Os + rq * 128 + (((2 * ch + 1) ^ (rq & 15)) << 3));
-        if (q0 + rq < nq) *reinterpret_cast<uint4*>(ctx + (off + q0 + rq) * H + head * 64 + ch * 8) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+    for (int p4 = 0; p4 < 32 * LR / 64; ++p4) {
+        const int rq = p4 * (64 / LR) + (lane >> (DH == 64 ? 3 : 2)), ch = lane & (LR - 1);
+        const uint2 lo = *reinterpret_cast<const uint2*>(Os + rq * RB + (((2 * ch) ^ (rq & (C8 - 1))) << 3));
+        const uint2 hi = *reinterpret_cast<const uint2*>(Os + rq * RB + (((2 * ch + 1) ^ (rq & (C8 - 1))) << 3));
+        if (q0 + rq < nq) *reinterpret_cast<uint4*>(ctx + (off + q0 + rq) * H + head * DH + ch * 8) = make_uint4(lo.x, lo.y, hi.x, hi.y);
     }
 }
 
-// HPB = heads per block: 1 when a sequence has >= 3 q-tiles, 2 / 4 for short sequences so that all four waves have work.
-// __launch_bounds__(256, 3): at most 168 registers per lane, which makes hipcc keep the MFMA accumulators in VGPRs; with the default bound it put
-// them in AGPRs and spent 112 of the 276 VALU instructions of a key tile on v_accvgpr_read / _write around the softmax rescale
-template <int HPB>
-__global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
+// HPB = heads per block: 1 when a sequence has >= 3 q-tiles, 2 / 4 for short sequences so that all four waves have work (the choice follows the q-tiles,
+// not the head width).
+// __launch_bounds__(256, 3) at DH = 64: at most 168 registers per lane, which makes hipcc keep the MFMA accumulators in VGPRs; with the default bound it
+// put them in AGPRs and spent 112 of the 276 VALU instructions of a key tile on v_accvgpr_read / _write around the softmax rescale.  A 32-wide head
+// stages half the bytes (<= 25 KiB per block for any HPB, see launch_attn) and keeps half the Q fragments and accumulators: four blocks per CU (<= 128
+// registers).
+template <int DH> constexpr int attn_lds_blocks() { return DH == 64 ? 3 : 4; }
+template <int DH, int HPB>
+__global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
                                                   int H, int heads, int kchunk, uint16_t* __restrict__ ctx) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1059,25 +1087,26 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
     if ((int)blockIdx.z * QT * 32 >= nq) return;          // block-uniform: no q-tile of this block exists (nq == 0 included)
     const int nk = seq_nk[b];
     const int64_t off = seq_off[b];
+    constexpr int KR = 2 * DH, NC = DH / 8, NCS = DH == 64 ? 3 : 2;   // K row bytes, 16-B chunks per K row (1 << NCS)
     const int vpitch = kchunk * 2 + 8;
-    char* Ks = smem;                                      // [HPB][kchunk][128 B]
-    char* Vs = smem + (size_t)HPB * kchunk * 128;         // [HPB][64][vpitch]
-    char* Os = Vs + (size_t)HPB * 64 * vpitch + wave * 4096;
+    char* Ks = smem;                                      // [HPB][kchunk][KR]
+    char* Vs = smem + (size_t)HPB * kchunk * KR;          // [HPB][DH][vpitch]
+    char* Os = Vs + (size_t)HPB * DH * vpitch + wave * (32 * KR);
     const int hs = wave % HPB;
     const int head = hb * HPB + hs;
     const bool active = head < heads && q0 < nq;          // inactive waves still stage and meet every barrier
-    const char* Kh = Ks + (size_t)hs * kchunk * 128;
-    const char* Vh = Vs + (size_t)hs * 64 * vpitch;
+    const char* Kh = Ks + (size_t)hs * kchunk * KR;
+    const char* Vh = Vs + (size_t)hs * DH * vpitch;
     const int c = lane & 31, hf = lane >> 5;
-    // Q^T as the B operand: lane (c, hf) holds Q[q0 + c][16 s + 8 hf .. +7], s = 0..3
-    uint4 qf[4] = {};
+    // Q^T as the B operand: lane (c, hf) holds Q[q0 + c][16 s + 8 hf .. +7], s = 0 .. DH / 16 - 1
+    uint4 qf[DH / 16] = {};
     if (active) {
         const int qi = (q0 + c < nq) ? (q0 + c) : (nq - 1);
-        const uint16_t* qrow = q + (off + qi) * H + head * 64;
+        const uint16_t* qrow = q + (off + qi) * H + head * DH;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
+        for (int s = 0; s < DH / 16; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
     }
-    AttnState st;
+    AttnState<DH> st;
     attn_init(st);
     constexpr int NB = HPB == 1 ? 4 : 2;                  // loads in flight per thread, head and batch (register budget: 3 blocks per CU = 168 VGPRs; HPB = 4 means <= 32 keys: 2 cover a head)
     for (int kc0 = 0; kc0 < nk; kc0 += kchunk) {
@@ -1091,7 +1120,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
         {
             // all heads of the block in ONE batch: every global load (K and V^T of up to HPB heads) is issued before the first LDS store, so a block with
             // 2 / 4 heads pays one memory round trip per batch, not one per head (a 32-token sequence is a single batch)
-            const int nkcs = nkp * 8, nvc = 64 * cpr;
+            const int nkcs = nkp * NC, nvc = DH * cpr;
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));      // opaque: the staging indices are derived per chunk and die with it (the key loop below runs at the register limit)
             for (int base = 0; base < nkcs || base < nvc; base += 256 * NB) {
@@ -1102,10 +1131,10 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
                         const int i = base + j * 256 + tid;
-                        const int key = i >> 3, ch = i & 7;
+                        const int key = i >> NCS, ch = i & (NC - 1);
                         kv[h2][j] = make_uint4(0u, 0u, 0u, 0u);
                         if (head2 < heads && i < nkcs && key < nkc) {
-                            const uint16_t* kp = k + (off + kc0 + key) * H + head2 * 64 + ch * 8;
+                            const uint16_t* kp = k + (off + kc0 + key) * H + head2 * DH + ch * 8;
                             kv[h2][j] = *reinterpret_cast<const uint4*>(kp);
                         }
                     }
@@ -1122,7 +1151,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
                         int vd, vk; vsplit(i, vd, vk);
                         vv[h2][j] = make_uint2(0u, 0u);
                         if (head2 < heads && i < nvc && vk * 4 < nkc) {
-                            const uint16_t* vp = vT + (int64_t)(head2 * 64 + vd) * ldv + off + kc0 + vk * 4;   // off, kc0 % 4 == 0: 8-B aligned
+                            const uint16_t* vp = vT + (int64_t)(head2 * DH + vd) * ldv + off + kc0 + vk * 4;   // off, kc0 % 4 == 0: 8-B aligned
                             vv[h2][j] = uint2(*reinterpret_cast<const uint2*>(vp));
                         }
                     }
@@ -1130,18 +1159,18 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
 #pragma unroll
                 for (int h2 = 0; h2 < HPB; ++h2) {
                     if (hb * HPB + h2 >= heads) continue;
-                    char* Kw = Ks + (size_t)h2 * kchunk * 128;
+                    char* Kw = Ks + (size_t)h2 * kchunk * KR;
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
                         const int i = base + j * 256 + tid;
-                        const int key = i >> 3, ch = i & 7;
-                        if (i < nkcs) *reinterpret_cast<uint4*>(Kw + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kv[h2][j];
+                        const int key = i >> NCS, ch = i & (NC - 1);
+                        if (i < nkcs) *reinterpret_cast<uint4*>(Kw + key * KR + ((ch ^ attn_kswz<DH>(key)) << 4)) = kv[h2][j];
                     }
                 }
 #pragma unroll
                 for (int h2 = 0; h2 < HPB; ++h2) {
                     if (hb * HPB + h2 >= heads) continue;
-                    char* Vw = Vs + (size_t)h2 * 64 * vpitch;
+                    char* Vw = Vs + (size_t)h2 * DH * vpitch;
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
                         const int i = base + j * 256 + tid;
@@ -1184,14 +1213,20 @@ __global__ __launch_bounds__(256, 3) void k_attn_lds(const uint16_t* __restrict_
 }
 
 // ---- long sequences: LDS-DMA ring ------------------------------------------------------------------------------------------------------------
-constexpr int ADMA_STAGE = 16384;                          // per 64-key chunk: K [64 keys][128 B] + V^T [64 d][128 B]
 constexpr int ADMA_RING = 3;
-constexpr int ADMA_LDS = ADMA_RING * ADMA_STAGE;           // 48 KiB; the O staging (4 waves x 4 KiB) re-uses the ring after the last chunk
 constexpr int ADMA_WAVES = 4;                              // eight (one block per (sequence, head) up to 512 tokens) measured 5 % faster at 128 x 512,
                                                            // 10-35 % slower at 64 x 512, 256 x 256 and 341 x 192
 constexpr int ADMA_THREADS = ADMA_WAVES * 64;
 constexpr int ADMA_QT = 2 * ADMA_WAVES;                    // q-tiles per block: TWO per wave (w and w + ADMA_WAVES), so every staged chunk serves 256 queries
-constexpr int ADMA_PIECES = 8 / ADMA_WAVES;                // K pieces (and V^T pieces) of 1 KiB a wave issues per chunk
+// per 64-key chunk: K [64 keys][2 DH B] + V^T [DH d][128 B]; DH = 64: 16 KiB per stage, 48 KiB per block, DH = 32: 8 / 24 KiB.  The O staging
+// (4 waves x 32 x 2 DH B) re-uses the ring after the last chunk
+template <int DH>
+struct AdmaGeom {
+    static constexpr int KB = 64 * 2 * DH;                 // K bytes of a chunk (= V^T bytes)
+    static constexpr int STAGE = 2 * KB;
+    static constexpr int LDS = ADMA_RING * STAGE;
+    static constexpr int PIECES = KB / 1024 / ADMA_WAVES;  // K pieces (and V^T pieces) of 1 KiB a wave issues per chunk
+};
 
 // Measured at 128 x 512 tokens (us per layer; the register-staged kernel: 344): two q-tiles per wave one after the other 253; one q-tile per wave with
 // four waves per block and three waves per SIMD 285 (every chunk then serves 128 queries and the block meets a barrier per step: its waves run in
@@ -1200,30 +1235,34 @@ constexpr int ADMA_PIECES = 8 / ADMA_WAVES;                // K pieces (and V^T 
 // needs both score tiles live: 42 spilled registers at the 256-register limit, two of them reloaded per chunk (VMEM: the DMA ring drains) — not kept.
 // (the body is a function with __restrict__ K / V^T pointers on purpose: after inlining the LDS-DMA carries their alias scope and the ring's ds_reads are
 // marked as not aliasing it, which lets the compiler's waitcnt pass leave the COUNTED vmcnt waits alone; see coarse_q32_body in search.hip)
+template <int DH>
 __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hf = lane >> 5;
+    using G = AdmaGeom<DH>;
+    constexpr int ADMA_PIECES = G::PIECES, KB = G::KB, ADMA_STAGE = G::STAGE;
+    constexpr int NC = DH / 8, NCS = DH == 64 ? 3 : 2, KROWS = 1024 / (2 * DH);  // 16-B chunks per K row (1 << NCS), keys per 1-KiB K piece
     const int nchunks = (nk + 63) >> 6;
-    // DMA of one chunk: 16 pieces of 1 KiB (8 K pieces = 8 keys x 128 B each, 8 V^T pieces = 8 d rows x 128 B each); wave w issues pieces
-    // w * ADMA_PIECES .. + ADMA_PIECES - 1 of both.  lane -> row 8 p + (lane >> 3), 16-B chunk (lane & 7) ^ swizzle(row) of that row (the LDS destination is
-    // lane-linear: the swizzle sits on the source)
+    // DMA of one chunk: 2 DH / 8 pieces of 1 KiB (DH / 8 K pieces of 1024 / (2 DH) keys each, DH / 8 V^T pieces = 8 d rows x 128 B each); wave w issues
+    // pieces w * ADMA_PIECES .. + ADMA_PIECES - 1 of both.  K: lane -> key KROWS p + lane / NC, 16-B chunk (lane % NC) ^ attn_kswz(key); V^T: lane -> d row
+    // 8 p + (lane >> 3), 16-B chunk (lane & 7) ^ ((d >> 1) & 7) (the LDS destination is lane-linear: the swizzle sits on the source)
     // addresses = a buffer resource per operand whose base is this (sequence, head)'s first byte (scalar registers) + a wave-uniform chunk offset (the
     // instruction's scalar offset) + a 32-bit per-lane offset that never changes: buffer_load_dwordx4 ... lds.  (With global_load_lds the compiler kept four
     // zero-extended 64-bit lane offsets, spilled them at the 256-register limit and reloaded them — s_waitcnt vmcnt(0) each — in front of the DMA of the
     // partial last chunk.)  Rows past the sequence (last chunk) are read and masked; the K buffer has 64 rows and V^T 64 columns of slack behind the last
     // token (ensure_ws), so nothing is out of range.
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(k)) + (int64_t)head * 128 + off * H * 2, 0, 0xffffffff, 0x00020000);
+        const_cast<char*>(reinterpret_cast<const char*>(k)) + (int64_t)head * 2 * DH + off * H * 2, 0, 0xffffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(vT)) + ((int64_t)head * 64) * ldv * 2 + off * 2, 0, 0xffffffff, 0x00020000);
+        const_cast<char*>(reinterpret_cast<const char*>(vT)) + ((int64_t)head * DH) * ldv * 2 + off * 2, 0, 0xffffffff, 0x00020000);
     uint32_t klane[ADMA_PIECES], vlane[ADMA_PIECES];
 #pragma unroll
     for (int pp = 0; pp < ADMA_PIECES; ++pp) {
-        const int row = 8 * (wave * ADMA_PIECES + pp) + (lane >> 3);   // key inside the chunk / d row
-        const int sw = ((lane & 7) ^ ((row >> 1) & 7)) << 4;
-        klane[pp] = (uint32_t)(row * H * 2 + sw);
-        vlane[pp] = (uint32_t)((int64_t)row * ldv * 2 + sw);          // < 2^32: 64 rows x (tokens + 64) x 2 B, tokens <= 2^24 (ensure_ws)
+        const int p = wave * ADMA_PIECES + pp;
+        const int key = KROWS * p + (lane >> NCS), row = 8 * p + (lane >> 3);   // key inside the chunk / d row
+        klane[pp] = (uint32_t)(key * H * 2 + (((lane & (NC - 1)) ^ attn_kswz<DH>(key)) << 4));
+        vlane[pp] = (uint32_t)((int64_t)row * ldv * 2 + (((lane & 7) ^ ((row >> 1) & 7)) << 4));   // < 2^32: DH rows x (tokens + 64) x 2 B, tokens <= 2^24 (ensure_ws)
     }
     auto issue = [&](int cidx) {
         char* stg = smem + (cidx % ADMA_RING) * ADMA_STAGE;
@@ -1232,7 +1271,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         for (int pp = 0; pp < ADMA_PIECES; ++pp) {
             const int p = wave * ADMA_PIECES + pp;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_void*)(stg + p * 1024), 16, klane[pp], kc, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void*)(stg + 8192 + p * 1024), 16, vlane[pp], vc, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void*)(stg + KB + p * 1024), 16, vlane[pp], vc, 0, 0);
         }
     };
     issue(0);
@@ -1241,17 +1280,17 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     // otherwise its waitcnt pass keeps them "possibly pending" around the loop's back edge and puts s_waitcnt vmcnt(0) in front of the first MFMA of
     // every chunk, which drains the DMA ring (one memory round trip per chunk, as without a ring)
     int q0[2]; bool act[2];
-    uint4 qf[2][4] = {};
-    AttnState st[2];
+    uint4 qf[2][DH / 16] = {};
+    AttnState<DH> st[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         q0[j] = (qg * ADMA_QT + wave + ADMA_WAVES * j) * 32;
         act[j] = q0[j] < nq;                               // wave-uniform; act[1] implies act[0]
         if (act[j]) {
             const int qi = (q0[j] + c < nq) ? (q0[j] + c) : (nq - 1);
-            const uint16_t* qrow = q + (off + qi) * H + head * 64;
+            const uint16_t* qrow = q + (off + qi) * H + head * DH;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) qf[j][s] = *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
+            for (int s = 0; s < DH / 16; ++s) qf[j][s] = *reinterpret_cast<const uint4*>(qrow + 16 * s + 8 * hf);
         }
         attn_init(st[j]);
     }
@@ -1269,7 +1308,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         char* stg = smem + (ci % ADMA_RING) * ADMA_STAGE;
         auto vfrag = [&](int dh, int ks) {
             const int d = c + 32 * dh;
-            return *reinterpret_cast<const uint4*>(stg + 8192 + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
+            return *reinterpret_cast<const uint4*>(stg + KB + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
         };
         attn_step64<false, true>(st[0], qf[0], stg, 0, 64, c, hf, vfrag);
         if constexpr (decltype(two_tiles)::value) attn_step64<false, true>(st[1], qf[1], stg, 0, 64, c, hf, vfrag);
@@ -1285,14 +1324,14 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         const int nkc = min(nk - ci * 64, 64);
         auto vfrag = [&](int dh, int ks) {
             const int d = c + 32 * dh;
-            return *reinterpret_cast<const uint4*>(stg + 8192 + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
+            return *reinterpret_cast<const uint4*>(stg + KB + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
         };
         if (nkc < 64) {
             // V^T columns >= nkc of the last chunk hold other sequences' values (or padding): zero them, so that P = 0 meets 0 and not a possible NaN / Inf
-            for (int i = tid; i < 64 * 8; i += ADMA_THREADS) {
+            for (int i = tid; i < DH * 8; i += ADMA_THREADS) {
                 const int d = i >> 3, chk = i & 7;         // (d row, 16-B chunk)
                 if (chk * 8 + 8 > nkc) {
-                    uint4* w = reinterpret_cast<uint4*>(stg + 8192 + d * 128 + ((chk ^ ((d >> 1) & 7)) << 4));
+                    uint4* w = reinterpret_cast<uint4*>(stg + KB + d * 128 + ((chk ^ ((d >> 1) & 7)) << 4));
                     uint4 v = *w;
                     unsigned int* u = reinterpret_cast<unsigned int*>(&v);
 #pragma unroll
@@ -1313,12 +1352,13 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         }
     }
     __syncthreads();                                       // the ring is free: re-use it for the O staging
-    char* Os = smem + wave * 4096;
+    char* Os = smem + wave * (32 * 2 * DH);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
         if (act[j]) attn_store_tile(st[j], Os, ctx, off, q0[j], nq, H, head, lane);
 }
 
+template <int DH>
 __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* __restrict__ seq_off,
                                                              const int* __restrict__ seq_nk, const int* __restrict__ seq_nq, int H, int64_t capT, uint16_t* ctx, int heads, int nseq, int qgroups) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1334,7 +1374,7 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
     if (b >= nseq) return;                                 // the grid is padded to whole groups of 8 pairs
     const int nq = seq_nq[b];
     if (qg * ADMA_QT * 32 >= nq) return;                   // block-uniform (nq == 0 included)
-    attn_dma_body(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem);
+    attn_dma_body<DH>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem);
 }
 
 // pooling + L2 normalisation: one block per sequence.  Mean pooling: wave w sums the tokens t = w, w+4, ... (8-byte loads of the (hi, lo)
@@ -1529,30 +1569,42 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     return fail(KR_EINVAL, "unknown tensor name '%s'", name);
 }
 
-template <int HPB>
+template <int DH, int HPB>
 static int launch_attn(const Encoder* e, int B, int cap, int nqt, hipStream_t st) {
     const int H = e->cfg.hidden, heads = e->cfg.heads;
-    const int kchunk = cap < 128 ? cap : 128;            // keys staged at a time: K 16 KiB + V^T 16.5 KiB per head -> 49 KiB per block, 3 blocks per CU for any S
-    const int lds = HPB * (kchunk * 128 + 64 * (kchunk * 2 + 8)) + 4 * 4096;
+    // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
+    // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
+    const int kchunk = cap < 128 ? cap : 128;
+    const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
     static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance
     int& attr_lds = attr_lds_dev[e->device & 63];
     if (lds > attr_lds) {
-        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<HPB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_lds = lds;
     }
     const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
-    hipLaunchKernelGGL((k_attn_lds<HPB>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
+    hipLaunchKernelGGL((k_attn_lds<DH, HPB>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
                        e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx);
     return 0;
 }
 
+template <int DH>
 static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
     const int64_t pairs = (int64_t)B * e->cfg.heads;
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
-    hipLaunchKernelGGL(k_attn_dma, dim3((unsigned)blocks), dim3(ADMA_THREADS), ADMA_LDS, st, e->q, e->k, e->vT, e->ldv,
+    hipLaunchKernelGGL(k_attn_dma<DH>, dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
                        e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups);
     return 0;
+}
+
+// the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
+template <int DH>
+static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, hipStream_t st) {
+    if (long_seq) return launch_attn_dma<DH>(e, B, nqt, st);
+    if (nqt >= 3) return launch_attn<DH, 1>(e, B, cap, nqt, st);
+    if (nqt == 2) return launch_attn<DH, 2>(e, B, cap, nqt, st);
+    return launch_attn<DH, 4>(e, B, cap, nqt, st);
 }
 
 static int set_lds_once(const void* kern, int lds, int device);
@@ -1669,7 +1721,8 @@ int enc_create(const kr_bert_cfg* cfg, int device, int residual_lo, void** out) 
     if (!out || !cfg) return fail(KR_EINVAL, "NULL argument");
     *out = nullptr;
     if (cfg->hidden <= 0 || cfg->hidden % 128 != 0 || cfg->hidden > 2048) return fail(KR_EINVAL, "hidden=%d unsupported (multiple of 128, <= 2048)", cfg->hidden);
-    if (cfg->heads <= 0 || cfg->hidden != cfg->heads * 64) return fail(KR_EINVAL, "hidden/heads must be 64 (got %d/%d)", cfg->hidden, cfg->heads);
+    if (cfg->heads <= 0 || (cfg->hidden != cfg->heads * 64 && cfg->hidden != cfg->heads * 32))
+        return fail(KR_EINVAL, "hidden/heads must be 32 or 64 (got %d/%d)", cfg->hidden, cfg->heads);
     if (cfg->intermediate <= 0 || cfg->intermediate % 128 != 0) return fail(KR_EINVAL, "intermediate=%d must be a multiple of 128", cfg->intermediate);
     if (cfg->layers <= 0 || cfg->vocab <= 0 || cfg->max_pos <= 0 || cfg->type_vocab <= 0) return fail(KR_EINVAL, "bad BERT config");
     KR_TRY(select_device(device));
@@ -1732,6 +1785,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     }
     KR_HIP(hipMemcpy(e->stage, data, (size_t)numel * 4, hipMemcpyDefault));
     const int64_t H = e->cfg.hidden;
+    const float qscale = (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
     const unsigned grid = (unsigned)((numel + 255) / 256);
     auto to_bf16 = [&](uint16_t* dst, float scale) { hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
     auto to_f32 = [&](float* dst, float scale) { hipLaunchKernelGGL(k_scale_copy, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
@@ -1741,9 +1795,10 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     } else {
         LayerW& l = e->L[(slot - T_LAYER0) / L_COUNT];
         switch ((slot - T_LAYER0) % L_COUNT) {
-            // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2
-            case L_QW: to_bf16(l.wqkv, 0.125f * 1.4426950408889634f); break;
-            case L_QB: to_f32(l.bqkv, 0.125f * 1.4426950408889634f); break;
+            // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2.  The
+            // multiply is fp32, before the 16-bit conversion (d_h = 32: the factor is not a power of two; d_h = 64: the same bits as log2(e) / 8)
+            case L_QW: to_bf16(l.wqkv, qscale); break;
+            case L_QB: to_f32(l.bqkv, qscale); break;
             case L_KW: to_bf16(l.wqkv + H * H, 1.f); break;
             case L_KB: to_f32(l.bqkv + H, 1.f); break;
             case L_VW: to_bf16(l.wqkv + 2 * H * H, 1.f); break;
@@ -1857,11 +1912,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
         KR_TRY(launch_proj(EPI_QKV, a, maxT, e, st));
         {
             const int cap = (int)round_up(S, 32);
-            const int nqt = nqt_max;
-            if (long_seq) KR_TRY(launch_attn_dma(e, B, nqt, st));
-            else if (nqt >= 3) KR_TRY(launch_attn<1>(e, B, cap, nqt, st));
-            else if (nqt == 2) KR_TRY(launch_attn<2>(e, B, cap, nqt, st));
-            else KR_TRY(launch_attn<4>(e, B, cap, nqt, st));
+            if (H == 32 * e->cfg.heads) KR_TRY(launch_attention<32>(e, B, cap, nqt_max, long_seq, st));
+            else KR_TRY(launch_attention<64>(e, B, cap, nqt_max, long_seq, st));
         }
         if (last && shortcut) {
             // only the CLS row of every sequence is read after this layer: gather those rows and finish the layer on B rows (same kernels, same arithmetic per
