@@ -219,10 +219,10 @@ typedef struct {
     int layers;        /* L   (24; 12 / 6 for the small models) */
     int heads;         /* 16 (12 for the small models); hidden / heads (the head width) must be 32 or 64, anything else is KR_EINVAL */
     int intermediate;  /* FF  (4096) */
-    int vocab;         /* 30522 */
-    int max_pos;       /* 512 */
-    int type_vocab;    /* 2 */
-    float ln_eps;      /* 1e-12 */
+    int vocab;         /* 30522 (250002 for XLM-R: multilingual-e5, bge-m3) */
+    int max_pos;       /* 512 (XLM-R: 514 position rows = 512 tokens; bge-m3: 8194 = 8192 tokens) */
+    int type_vocab;    /* 2 (XLM-R: 1) */
+    float ln_eps;      /* 1e-12 (XLM-R: 1e-5) */
 } kr_bert_cfg;
 
 #define KR_POOL_MEAN 0 /* E5: average_pool (encoders.py:56-58) then F.normalize */
@@ -244,7 +244,14 @@ int kr_encoder_operand_dtype(const kr_encoder* enc);   /* what the handle was cr
 int kr_encoder_residual_lo(const kr_encoder* enc);
 void kr_encoder_destroy(kr_encoder* enc);
 /* one call per HF state_dict tensor of BertModel ("embeddings.word_embeddings.weight",
- * "encoder.layer.3.attention.self.query.bias", ...), fp32, numel checked; "pooler.*" / "*position_ids" ignored. */
+ * "encoder.layer.3.attention.self.query.bias", ...), fp32, numel checked; "pooler.*" / "*position_ids" ignored.  XLMRobertaModel / RobertaModel have the
+ * same names.
+ * Names that start with "config." are reserved for settings of the handle (no state-dict tensor starts so); an unknown one is KR_EINVAL.
+ *   "config.position_padding_idx": data = ONE float holding an integer P, 0 <= P <= max_pos - 2 (anything else is KR_EINVAL).  The handle then follows
+ *   fairseq's position rule (RoBERTa / XLM-R, pad_token_id = P = 1): the position embedding of column i of a row is P + (number of ids != P in columns
+ *   0..i, attended or not) where ids[i] != P, and P where ids[i] == P; the forwards then take S <= max_pos - P - 1.  Without it the handle follows BERT's
+ *   rule (position = column), bit for bit as before.  Accepted before the handle's first finalize and kept for the handle's life: later the same value is
+ *   a no-op, another value KR_EINVAL.  kr_encoder_last_hidden keeps placing rows at their columns under both rules. */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);

@@ -100,6 +100,12 @@ struct Encoder {
     int64_t *d_ids = nullptr, *d_mask = nullptr, *d_tt = nullptr;   // d_tt: token_type_ids of the batch (only written when the caller passes them)
     int *seq_off = nullptr, *seq_nk = nullptr, *seq_nq = nullptr, *seq_cls = nullptr, *seq_has0 = nullptr, *d_T = nullptr, *d_err = nullptr;
     int *tok_id = nullptr, *tok_pos = nullptr, *tok_type = nullptr;
+    // position rule of the handle.  pad_idx < 0: BERT's (embedding position = column, tok_pos serves k_embed_ln and the un-packer).  pad_idx = P >= 0: fairseq's
+    // (RoBERTa / XLM-R: P + number of ids != P up to and including the column, P itself where the id is P): the packers write that into tok_epos for k_embed_ln
+    // and tok_pos keeps the column for the un-packer.  Set through the reserved name "config.position_padding_idx" before the first finalize.
+    int pad_idx = -1;
+    bool finalized_once = false;
+    int *tok_epos = nullptr;
     float *out = nullptr;
     uint8_t *xlo = nullptr;    // low half of the residual stream, one byte per element (lo_encode): written by every LayerNorm with use_lo, else by the last one only
     bool use_lo = false;       // KIRAG_AMD_RESIDUAL_LO=1 at kr_encoder_create
@@ -182,38 +188,56 @@ __global__ __launch_bounds__(64) void k_seq_scan(const int* __restrict__ nk, con
     if (lane == 0) { *T = carry; }   // *err is sticky: set by k_fill_tokens, cleared by the host once it has been reported
 }
 
-// one wave per sequence: packed token list (attended positions in order; the optional query-only row for position 0 last)
-// tt: token_type_ids of the batch or nullptr (= all zero, what every KiRAG caller passes); a value outside [0, type_vocab) sets error bit 2 and is read as 0
-__global__ __launch_bounds__(64) void k_fill_tokens(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int64_t* __restrict__ tt, int S, int vocab,
-                                                    int type_vocab, int align, const int* __restrict__ off, const int* __restrict__ nk, const int* __restrict__ nq,
-                                                    int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int o = off[b];
-    int run = 0;
+// The packed token list of ONE sequence of a padded batch, by one wave (attended positions in order; the optional query-only row for position 0 last).
+// tok_epos == nullptr: BERT's position rule, tok_pos (the column) is all there is.  Otherwise fairseq's rule with padding index P: a second ballot counts the
+// ids != P over ALL columns of the row, attended or not (the count the attended-only `run` cannot give), and tok_epos gets P + that count (P where the id is P).
+__device__ __forceinline__ void fill_one(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int64_t* __restrict__ tt, int S, int vocab, int type_vocab,
+                                         int align, int o, int n_att, int n, int lane, int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type,
+                                         int* __restrict__ err, int P, int* __restrict__ tok_epos) {
+    int run = 0, erun = 0;
     for (int base = 0; base < S; base += 64) {
         const int p = base + lane;
-        const bool v = (p < S) && (mask[(int64_t)b * S + p] != 0);
+        const bool v = (p < S) && (mask[p] != 0);
         const unsigned long long bal = __ballot(v);
+        int64_t id = 0;
+        if (v || (tok_epos && p < S)) id = ids[p];
+        const bool m = tok_epos && p < S && id != P;
+        const unsigned long long mbal = __ballot(m);
         if (v) {
             const int r = run + __popcll(bal & ((1ull << lane) - 1ull));
-            int64_t id = ids[(int64_t)b * S + p];
+            if (tok_epos) tok_epos[o + r] = P + (m ? erun + __popcll(mbal & ((2ull << lane) - 1ull)) : 0);
             if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
-            int64_t ty = tt ? tt[(int64_t)b * S + p] : 0;
+            int64_t ty = tt ? tt[p] : 0;
             if (ty < 0 || ty >= type_vocab) { atomicOr(err, 4); ty = 0; }
             tok_id[o + r] = (int)id; tok_pos[o + r] = p; tok_type[o + r] = (int)ty;
         }
         run += __popcll(bal);
+        erun += __popcll(mbal);
     }
-    const int n = nq[b];
-    if (lane == 0 && n > nk[b]) {
-        int64_t id = ids[(int64_t)b * S];
+    if (lane == 0 && n > n_att) {
+        int64_t id = ids[0];
+        if (tok_epos) tok_epos[o + n_att] = P + (id != P ? 1 : 0);
         if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
-        int64_t ty = tt ? tt[(int64_t)b * S] : 0;
+        int64_t ty = tt ? tt[0] : 0;
         if (ty < 0 || ty >= type_vocab) { atomicOr(err, 4); ty = 0; }
-        tok_id[o + nk[b]] = (int)id; tok_pos[o + nk[b]] = 0; tok_type[o + nk[b]] = (int)ty;
+        tok_id[o + n_att] = (int)id; tok_pos[o + n_att] = 0; tok_type[o + n_att] = (int)ty;
     }
     const int padded = (n + align - 1) & ~(align - 1);
-    if (lane < padded - n) { tok_id[o + n + lane] = 0; tok_pos[o + n + lane] = 0; tok_type[o + n + lane] = 0; }
+    if (lane < padded - n) {
+        tok_id[o + n + lane] = 0; tok_pos[o + n + lane] = 0; tok_type[o + n + lane] = 0;
+        if (tok_epos) tok_epos[o + n + lane] = 0;
+    }
+}
+
+// one wave per sequence: fill_one
+// tt: token_type_ids of the batch or nullptr (= all zero, what every KiRAG caller passes); a value outside [0, type_vocab) sets error bit 2 and is read as 0
+__global__ __launch_bounds__(64) void k_fill_tokens(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int64_t* __restrict__ tt, int S, int vocab,
+                                                    int type_vocab, int align, const int* __restrict__ off, const int* __restrict__ nk, const int* __restrict__ nq,
+                                                    int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err, int P,
+                                                    int* __restrict__ tok_epos) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    fill_one(ids + (int64_t)b * S, mask + (int64_t)b * S, tt ? tt + (int64_t)b * S : nullptr, S, vocab, type_vocab, align, off[b], nk[b], nq[b], lane, tok_id, tok_pos,
+             tok_type, err, P, tok_epos);
 }
 
 // the three kernels above as ONE single-block launch for small batches (B <= PACK_SMALL_B; a 32-token forward is launch-bound, round 5): wave w counts,
@@ -222,7 +246,7 @@ constexpr int PACK_SMALL_B = 64;
 __global__ __launch_bounds__(1024) void k_pack_small(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int64_t* __restrict__ tt, int B, int S, int vocab,
                                                      int type_vocab, int pool, int align, int* __restrict__ nk, int* __restrict__ has0, int* __restrict__ nq, int* __restrict__ off,
                                                      int* __restrict__ cls, int* __restrict__ T, int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type,
-                                                     int* __restrict__ err) {
+                                                     int* __restrict__ err, int P, int* __restrict__ tok_epos) {
     __shared__ int s_nk[PACK_SMALL_B], s_h0[PACK_SMALL_B], s_nq[PACK_SMALL_B], s_off[PACK_SMALL_B];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int b = wave; b < B; b += 16) {                       // k_seq_len
@@ -245,34 +269,9 @@ __global__ __launch_bounds__(1024) void k_pack_small(const int64_t* __restrict__
         if (lane == 63) *T = incl;
     }
     __syncthreads();
-    for (int b = wave; b < B; b += 16) {                       // k_fill_tokens
-        const int o = s_off[b];
-        int run = 0;
-        for (int base = 0; base < S; base += 64) {
-            const int p = base + lane;
-            const bool v = (p < S) && (mask[(int64_t)b * S + p] != 0);
-            const unsigned long long bal = __ballot(v);
-            if (v) {
-                const int r = run + __popcll(bal & ((1ull << lane) - 1ull));
-                int64_t id = ids[(int64_t)b * S + p];
-                if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
-                int64_t ty = tt ? tt[(int64_t)b * S + p] : 0;
-                if (ty < 0 || ty >= type_vocab) { atomicOr(err, 4); ty = 0; }
-                tok_id[o + r] = (int)id; tok_pos[o + r] = p; tok_type[o + r] = (int)ty;
-            }
-            run += __popcll(bal);
-        }
-        const int n = s_nq[b];
-        if (lane == 0 && n > s_nk[b]) {
-            int64_t id = ids[(int64_t)b * S];
-            if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
-            int64_t ty = tt ? tt[(int64_t)b * S] : 0;
-            if (ty < 0 || ty >= type_vocab) { atomicOr(err, 4); ty = 0; }
-            tok_id[o + s_nk[b]] = (int)id; tok_pos[o + s_nk[b]] = 0; tok_type[o + s_nk[b]] = (int)ty;
-        }
-        const int padded = (n + align - 1) & ~(align - 1);
-        if (lane < padded - n) { tok_id[o + n + lane] = 0; tok_pos[o + n + lane] = 0; tok_type[o + n + lane] = 0; }
-    }
+    for (int b = wave; b < B; b += 16)                         // k_fill_tokens
+        fill_one(ids + (int64_t)b * S, mask + (int64_t)b * S, tt ? tt + (int64_t)b * S : nullptr, S, vocab, type_vocab, align, s_off[b], s_nk[b], s_nq[b], lane, tok_id,
+                 tok_pos, tok_type, err, P, tok_epos);
 }
 
 // ---- ragged input (kr_encoder_forward_packed): ids32 = the attended tokens of every sequence back to back, lens[b] = how many belong to sequence b, at
@@ -280,16 +279,34 @@ __global__ __launch_bounds__(1024) void k_pack_small(const int64_t* __restrict__
 // padded-input kernels above fill for the equivalent [B,S] batch (mask[b,p] = p < lens[b]), so everything behind them is the same code on the same data.
 // A length outside [0, S], or lengths that do not add up to `total`, set error bit 8 and the sequence is read as empty (nothing is read out of bounds).
 __device__ __forceinline__ void rag_fill_one(const int* __restrict__ src, int n_in, int n, int o, int vocab, int align, int lane, int* __restrict__ tok_id,
-                                             int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err) {
-    for (int p = lane; p < n_in; p += 64) {
-        int id = src[p];
-        if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
-        tok_id[o + p] = id; tok_pos[o + p] = p; tok_type[o + p] = 0;
+                                             int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err, int P, int* __restrict__ tok_epos) {
+    int erun = 0;                                                    // fairseq rule: ids != P in front of this step (the padded twin's tail holds P and never counts)
+    for (int base = 0; base < n_in; base += 64) {
+        const int p = base + lane;
+        const bool v = p < n_in;
+        int id = v ? src[p] : 0;
+        const bool m = tok_epos && v && id != P;
+        const unsigned long long mbal = __ballot(m);
+        if (v) {
+            if (tok_epos) tok_epos[o + p] = P + (m ? erun + __popcll(mbal & ((2ull << lane) - 1ull)) : 0);
+            if (id < 0 || id >= vocab) { atomicOr(err, 1); id = 0; }
+            tok_id[o + p] = id; tok_pos[o + p] = p; tok_type[o + p] = 0;
+        }
+        erun += __popcll(mbal);
     }
-    // CLS pooling of an empty sequence: the query-only row for position 0 reads token id 0 (the padded call with input_ids padded by [PAD] = 0)
-    if (lane == 0 && n > n_in) { tok_id[o + n_in] = 0; tok_pos[o + n_in] = 0; tok_type[o + n_in] = 0; }
+    // CLS pooling of an empty sequence: the query-only row for position 0 reads what the padded call holds there: [PAD] = 0 at position 0 under BERT's rule,
+    // id P at position P under fairseq's
+    if (lane == 0 && n > n_in) {
+        int id = tok_epos ? P : 0;
+        if (id >= vocab) { atomicOr(err, 1); id = 0; }
+        tok_id[o + n_in] = id; tok_pos[o + n_in] = 0; tok_type[o + n_in] = 0;
+        if (tok_epos) tok_epos[o + n_in] = P;
+    }
     const int padded = (n + align - 1) & ~(align - 1);
-    if (lane < padded - n) { tok_id[o + n + lane] = 0; tok_pos[o + n + lane] = 0; tok_type[o + n + lane] = 0; }
+    if (lane < padded - n) {
+        tok_id[o + n + lane] = 0; tok_pos[o + n + lane] = 0; tok_type[o + n + lane] = 0;
+        if (tok_epos) tok_epos[o + n + lane] = 0;
+    }
 }
 
 // one wave: k_seq_len + k_seq_scan of the ragged form, plus the exclusive scan of the raw lengths (where each sequence starts in ids32)
@@ -327,15 +344,16 @@ __global__ __launch_bounds__(64) void k_rag_scan(const int* __restrict__ lens, i
 
 __global__ __launch_bounds__(64) void k_rag_fill(const int* __restrict__ ids32, int vocab, int align, const int* __restrict__ in_off, const int* __restrict__ off,
                                                  const int* __restrict__ nk, const int* __restrict__ nq, int* __restrict__ tok_id, int* __restrict__ tok_pos,
-                                                 int* __restrict__ tok_type, int* __restrict__ err) {
+                                                 int* __restrict__ tok_type, int* __restrict__ err, int P, int* __restrict__ tok_epos) {
     const int b = blockIdx.x;
-    rag_fill_one(ids32 + in_off[b], nk[b], nq[b], off[b], vocab, align, threadIdx.x, tok_id, tok_pos, tok_type, err);
+    rag_fill_one(ids32 + in_off[b], nk[b], nq[b], off[b], vocab, align, threadIdx.x, tok_id, tok_pos, tok_type, err, P, tok_epos);
 }
 
 // both as ONE single-block launch for B <= PACK_SMALL_B (the ragged twin of k_pack_small)
 __global__ __launch_bounds__(1024) void k_rag_small(const int* __restrict__ ids32, const int* __restrict__ lens, int B, int S, int total, int vocab, int pool, int align,
                                                     int* __restrict__ nk, int* __restrict__ has0, int* __restrict__ nq, int* __restrict__ off, int* __restrict__ cls,
-                                                    int* __restrict__ T, int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err) {
+                                                    int* __restrict__ T, int* __restrict__ tok_id, int* __restrict__ tok_pos, int* __restrict__ tok_type, int* __restrict__ err,
+                                                    int P, int* __restrict__ tok_epos) {
     __shared__ int s_nk[PACK_SMALL_B], s_nq[PACK_SMALL_B], s_off[PACK_SMALL_B], s_in[PACK_SMALL_B];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave == 0) {
@@ -363,7 +381,7 @@ __global__ __launch_bounds__(1024) void k_rag_small(const int* __restrict__ ids3
         if (lane == 63) *T = incl;
     }
     __syncthreads();
-    for (int b = wave; b < B; b += 16) rag_fill_one(ids32 + s_in[b], s_nk[b], s_nq[b], s_off[b], vocab, align, lane, tok_id, tok_pos, tok_type, err);
+    for (int b = wave; b < B; b += 16) rag_fill_one(ids32 + s_in[b], s_nk[b], s_nq[b], s_off[b], vocab, align, lane, tok_id, tok_pos, tok_type, err, P, tok_epos);
 }
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -466,7 +484,8 @@ __device__ __forceinline__ void ln_row_store(float4 (&v)[8], int H, int lane, co
     }
 }
 
-// embeddings: word[id] + position[pos] + token_type[0] -> LayerNorm       (one wave per token)
+// embeddings: word[id] + position[pos] + token_type[0] -> LayerNorm       (one wave per token; tok_pos = the handle's embedding-position table: the column
+// under BERT's rule, tok_epos under fairseq's)
 __global__ __launch_bounds__(256) void k_embed_ln(const int* __restrict__ tok_id, const int* __restrict__ tok_pos, const int* __restrict__ tok_type, const int* __restrict__ Tp,
                                                   const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type,
                                                   const float* __restrict__ g, const float* __restrict__ bta, float eps, int H,
@@ -1266,7 +1285,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     }
     auto issue = [&](int cidx) {
         char* stg = smem + (cidx % ADMA_RING) * ADMA_STAGE;
-        const int kc = cidx * 64 * H * 2, vc = cidx * 128;             // chunk offsets (bytes): <= 512 tokens per sequence
+        const int kc = cidx * 64 * H * 2, vc = cidx * 128;             // chunk offsets (bytes): 32 MiB / 16 KiB at 8192 tokens and H = 2048
 #pragma unroll
         for (int pp = 0; pp < ADMA_PIECES; ++pp) {
             const int p = wave * ADMA_PIECES + pp;
@@ -1477,11 +1496,11 @@ static int dmalloc(P** p, size_t bytes) {
 
 static void free_ws(Encoder* e) {
     if (!e->graphs.empty()) { (void)hipDeviceSynchronize(); drop_graphs(e); }   // captured kernels hold workspace pointers
-    void* ptrs[] = {e->d_ids, e->d_mask, e->d_tt, e->tok_type, e->seq_off, e->seq_nk, e->seq_nq, e->seq_cls, e->seq_has0, e->tok_id, e->tok_pos, e->xlo, e->y, e->out,
+    void* ptrs[] = {e->d_ids, e->d_mask, e->d_tt, e->tok_type, e->seq_off, e->seq_nk, e->seq_nq, e->seq_cls, e->seq_has0, e->tok_id, e->tok_pos, e->tok_epos, e->xlo, e->y, e->out,
                     e->xb, e->q, e->k, e->vT, e->ctx, e->h, e->c_ctx, e->c_xb, e->c_y, e->c_h, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     e->c_ctx = e->c_xb = e->c_y = e->c_h = nullptr; e->c_xlo = nullptr; e->c_off = e->c_nk = e->c_cls = e->d_B = nullptr;
-    e->d_ids = e->d_mask = e->d_tt = nullptr; e->tok_type = nullptr; e->seq_off = e->seq_nk = e->seq_nq = e->seq_cls = e->seq_has0 = nullptr; e->tok_id = e->tok_pos = nullptr;
+    e->d_ids = e->d_mask = e->d_tt = nullptr; e->tok_type = nullptr; e->seq_off = e->seq_nk = e->seq_nq = e->seq_cls = e->seq_has0 = nullptr; e->tok_id = e->tok_pos = e->tok_epos = nullptr;
     e->out = nullptr; e->xlo = nullptr; e->y = e->xb = e->q = e->k = e->vT = e->ctx = e->h = nullptr;
     e->capT = 0; e->capB = 0; e->capBS = 0;
 }
@@ -1503,6 +1522,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
     KR_TRY(dmalloc(&e->d_ids, capBS * 8)); KR_TRY(dmalloc(&e->d_mask, capBS * 8)); KR_TRY(dmalloc(&e->d_tt, capBS * 8));
     KR_TRY(dmalloc(&e->seq_off, capB * 4)); KR_TRY(dmalloc(&e->seq_nk, capB * 4)); KR_TRY(dmalloc(&e->seq_nq, capB * 4)); KR_TRY(dmalloc(&e->seq_cls, capB * 4)); KR_TRY(dmalloc(&e->seq_has0, capB * 4));
     KR_TRY(dmalloc(&e->tok_id, capT * 4)); KR_TRY(dmalloc(&e->tok_pos, capT * 4)); KR_TRY(dmalloc(&e->tok_type, capT * 4));
+    if (e->pad_idx >= 0) KR_TRY(dmalloc(&e->tok_epos, capT * 4));
     KR_TRY(dmalloc(&e->xlo, capT * H)); KR_TRY(dmalloc(&e->y, capT * H * 2)); KR_TRY(dmalloc(&e->out, (size_t)capB * H * 4));
     KR_TRY(dmalloc(&e->xb, capT * H * 2)); KR_TRY(dmalloc(&e->q, capT * H * 2));
     KR_TRY(dmalloc(&e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
@@ -1769,10 +1789,29 @@ void enc_destroy(void* h) {
     delete e;
 }
 
+// Settings of the handle travel through the name-addressed loader under the reserved prefix "config." (no tensor of an HF state dict starts with it).
+// config.position_padding_idx = P (one float holding an integer, 0 <= P <= max_pos - 2): fairseq's position rule.  Accepted before the first finalize; later
+// the same value is a no-op and any other is refused (the workspace and the meaning of every embedding depend on it).
+static int set_config(Encoder* e, const char* name, const float* data, int64_t numel) {
+    if (std::strcmp(name, "config.position_padding_idx") != 0) return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx)", name);
+    if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
+    float v = 0.f;
+    KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
+    if (!(v >= 0.f && v <= (float)(e->cfg.max_pos - 2)) || v != (float)(int)v)
+        return fail(KR_EINVAL, "config.position_padding_idx = %g: expected an integer in [0, max_position_embeddings - 2 = %d]", (double)v, e->cfg.max_pos - 2);
+    if (e->finalized_once) {
+        if ((int)v == e->pad_idx) return 0;
+        return fail(KR_EINVAL, "config.position_padding_idx = %d after kr_encoder_finalize: the handle's position rule is fixed (it has %d; -1 = BERT's rule)", (int)v, e->pad_idx);
+    }
+    e->pad_idx = (int)v;
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(select_device(e->device));
+    if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
     int slot = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want));
     if (slot < 0) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
@@ -1835,6 +1874,7 @@ int enc_finalize(void* h) {
     KR_HIP(hipGetLastError());
     KR_HIP(hipDeviceSynchronize());
     e->ready = true;
+    e->finalized_once = true;
     return 0;
 }
 
@@ -1872,21 +1912,21 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
         int* in_off = reinterpret_cast<int*>(e->d_tt);
         if (B <= PACK_SMALL_B) {
             hipLaunchKernelGGL(k_rag_small, dim3(1), dim3(1024), 0, st, ids32, lens, B, S, ragged_total, e->cfg.vocab, pool, align, e->seq_nk, e->seq_has0, e->seq_nq,
-                               e->seq_off, e->seq_cls, e->d_T, e->tok_id, e->tok_pos, e->tok_type, e->d_err);
+                               e->seq_off, e->seq_cls, e->d_T, e->tok_id, e->tok_pos, e->tok_type, e->d_err, e->pad_idx, e->tok_epos);
         } else {
             hipLaunchKernelGGL(k_rag_scan, dim3(1), dim3(64), 0, st, lens, B, S, ragged_total, pool, align, e->seq_nk, e->seq_has0, e->seq_nq, e->seq_off, e->seq_cls,
                                in_off, e->d_T, e->d_err);
             hipLaunchKernelGGL(k_rag_fill, dim3(B), dim3(64), 0, st, ids32, e->cfg.vocab, align, in_off, e->seq_off, e->seq_nk, e->seq_nq, e->tok_id, e->tok_pos,
-                               e->tok_type, e->d_err);
+                               e->tok_type, e->d_err, e->pad_idx, e->tok_epos);
         }
     } else if (B <= PACK_SMALL_B) {
         hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(1024), 0, st, e->d_ids, e->d_mask, has_tt ? e->d_tt : nullptr, B, S, e->cfg.vocab, e->cfg.type_vocab, pool, align,
-                           e->seq_nk, e->seq_has0, e->seq_nq, e->seq_off, e->seq_cls, e->d_T, e->tok_id, e->tok_pos, e->tok_type, e->d_err);
+                           e->seq_nk, e->seq_has0, e->seq_nq, e->seq_off, e->seq_cls, e->d_T, e->tok_id, e->tok_pos, e->tok_type, e->d_err, e->pad_idx, e->tok_epos);
     } else {
         hipLaunchKernelGGL(k_seq_len, dim3(B), dim3(64), 0, st, e->d_mask, B, S, e->seq_nk, e->seq_has0);
         hipLaunchKernelGGL(k_seq_scan, dim3(1), dim3(64), 0, st, e->seq_nk, e->seq_has0, B, pool, align, e->seq_nq, e->seq_off, e->seq_cls, e->d_T, e->d_err);
         hipLaunchKernelGGL(k_fill_tokens, dim3(B), dim3(64), 0, st, e->d_ids, e->d_mask, has_tt ? e->d_tt : nullptr, S, e->cfg.vocab, e->cfg.type_vocab, align, e->seq_off,
-                           e->seq_nk, e->seq_nq, e->tok_id, e->tok_pos, e->tok_type, e->d_err);
+                           e->seq_nk, e->seq_nq, e->tok_id, e->tok_pos, e->tok_type, e->d_err, e->pad_idx, e->tok_epos);
     }
     const int64_t maxT = (int64_t)B * (((S + (pool == KR_POOL_CLS ? 1 : 0)) + align - 1) & ~(align - 1));   // upper bound of the packed token count (each sequence is padded to `align`)
     const unsigned row_grid = (unsigned)((maxT + 3) / 4);
@@ -1898,7 +1938,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
     const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
     unsigned ln_mult = 8u;
     const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
-    hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->tok_pos, e->tok_type, e->d_T, e->word, e->pos, e->type, e->elng, e->elnb, eps, H,
+    hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->pad_idx >= 0 ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word, e->pos, e->type, e->elng, e->elnb, eps, H,
                        e->use_lo ? e->xlo : nullptr, e->xb);
     uint8_t* const lo_rw = e->use_lo ? e->xlo : nullptr;       // low half read / written by the inner LayerNorms
     const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr;
@@ -2022,6 +2062,9 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     if (!e->ready) return fail(KR_ESTATE, "encoder weights incomplete: call kr_encoder_finalize after loading every tensor");
     if (B < 0 || S <= 0 || (B > 0 && (!input_ids || !attention_mask || !out))) return fail(KR_EINVAL, "bad input pointers / shape");
     if (S > e->cfg.max_pos) return fail(KR_EINVAL, "sequence length %d exceeds max_position_embeddings %d", S, e->cfg.max_pos);
+    if (e->pad_idx >= 0 && S + e->pad_idx + 1 > e->cfg.max_pos)
+        return fail(KR_EINVAL, "sequence length %d + padding index %d + 1 exceeds max_position_embeddings %d (fairseq position rule: at most %d tokens)", S, e->pad_idx,
+                    e->cfg.max_pos, e->cfg.max_pos - e->pad_idx - 1);
     if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS) return fail(KR_EINVAL, "pool must be 0 (mean) or 1 (cls)");
     if (B == 0) return 0;
     if (B > 65535) return fail(KR_EINVAL, "at most 65535 sequences per call");
@@ -2062,6 +2105,9 @@ int enc_forward_packed(void* h, const int32_t* token_ids, const int32_t* seq_len
     if (!e->ready) return fail(KR_ESTATE, "encoder weights incomplete: call kr_encoder_finalize after loading every tensor");
     if (B < 0 || S <= 0 || total_tokens < 0 || (B > 0 && (!seq_lens || !out)) || (total_tokens > 0 && !token_ids)) return fail(KR_EINVAL, "bad input pointers / shape");
     if (S > e->cfg.max_pos) return fail(KR_EINVAL, "sequence length %d exceeds max_position_embeddings %d", S, e->cfg.max_pos);
+    if (e->pad_idx >= 0 && S + e->pad_idx + 1 > e->cfg.max_pos)
+        return fail(KR_EINVAL, "sequence length %d + padding index %d + 1 exceeds max_position_embeddings %d (fairseq position rule: at most %d tokens)", S, e->pad_idx,
+                    e->cfg.max_pos, e->cfg.max_pos - e->pad_idx - 1);
     if (total_tokens > (int64_t)B * S) return fail(KR_EINVAL, "total_tokens %lld exceeds B * S = %lld", (long long)total_tokens, (long long)B * S);
     if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS) return fail(KR_EINVAL, "pool must be 0 (mean) or 1 (cls)");
     if (B == 0) return 0;

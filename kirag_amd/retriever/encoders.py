@@ -13,6 +13,12 @@ Which path runs:
     on a GPU; there is NO CPU fallback — a CPU model in eval mode raises.
   * ``model.train()`` (Aligner fine-tuning, ``trainer/aligner_trainer.py:25-30``): the inherited PyTorch
     autograd forward, unchanged — backward is outside the hot path.
+
+RoBERTa-family checkpoints (``model_type`` roberta / xlm-roberta / camembert: multilingual-e5, bge-m3's dense head): the layer stack is BERT's and the
+state-dict names are identical, but the embedding position follows fairseq's rule (``padding_idx + cumsum(ids != padding_idx)``, ``padding_idx`` itself where
+the id is the padding id).  ``XLMRobertaE5Encoder`` / ``XLMRobertaBGEEncoder`` are the twins of the two classes above over ``transformers.XLMRobertaModel``;
+``E5Encoder.from_pretrained`` / ``BGEEncoder.from_pretrained`` read the checkpoint's ``config.json`` first and return the twin for such a checkpoint, so the
+registry names ``E5Retriever`` / ``BGERetriever`` serve both families.
 """
 from __future__ import annotations
 
@@ -22,11 +28,13 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel
+from transformers import BertModel, PretrainedConfig, XLMRobertaModel
 
 from .. import _lib
 
 POOL_MEAN, POOL_CLS = 0, 1
+# model_type values whose position ids follow fairseq's rule on BERT's post-LN layer stack ("xlm-roberta-xl" is pre-LN: not one of them)
+ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
 
 
 def average_pool(last_hidden_states: Tensor, attention_mask: Tensor) -> Tensor:
@@ -57,6 +65,16 @@ class HipBertForward:
         self.residual_lo = bool(lib.kr_encoder_residual_lo(h))
         self.hidden = config.hidden_size
         self.fingerprint = None
+        # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P.  It travels through the
+        # name-addressed loader under the reserved name "config.position_padding_idx", before the first finalize, and holds for the handle's life
+        self.position_padding_idx = None
+        if getattr(config, "model_type", "bert") in ROBERTA_TYPES:
+            P = getattr(config, "pad_token_id", None)
+            if P is None:
+                raise ValueError(f"model_type={config.model_type!r} needs config.pad_token_id (the padding index of fairseq's position rule)")
+            v = C.c_float(float(P))
+            _lib.check(lib.kr_encoder_load_weight(h, b"config.position_padding_idx", C.addressof(v), 1))
+            self.position_padding_idx = int(P)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -215,8 +233,11 @@ class HipBertForward:
         return out
 
 
-class _HipSentenceEncoder(BertModel):
+class _HipSentenceMixin:
+    """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel`` or ``XLMRobertaModel``, the next class in the MRO): the HIP
+    eval forward, weight sync, ``forward_packed``, the train / eval switch and the pooled autograd forward of ``train()`` mode."""
     _pool = POOL_MEAN
+    _hf_base = None
     accepts_host_inputs = True       # eval forward takes the collator's CPU tensors and uploads them itself (DenseRetriever skips its to_device)
 
     def __init__(self, config, add_pooling_layer=True, **kwargs):
@@ -281,33 +302,71 @@ class _HipSentenceEncoder(BertModel):
         return out
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        out = BertModel.forward(self, input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, return_dict=True)
+        out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, return_dict=True)
         return out.last_hidden_state
+
+    def forward(self, input_ids, attention_mask, token_type_ids=None, **kwargs):
+        if not self.training:
+            return self._hip_forward(input_ids, attention_mask, token_type_ids)
+        last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
+        embeddings = average_pool(last_hidden_states, attention_mask) if self._pool == POOL_MEAN else last_hidden_states[:, 0]
+        embeddings = F.normalize(embeddings, p=2, dim=1)
+        return embeddings
 
     def hip_last_hidden_state(self, B: int, S: int) -> Tensor:
         """last_hidden_state [B,S,H] (CPU, fp32) of the previous HIP forward; rows of masked positions are zero."""
         return self._hip.last_hidden(B, S)
 
 
-class E5Encoder(_HipSentenceEncoder):
-    _pool = POOL_MEAN
+# keyword arguments of from_pretrained that say WHERE the checkpoint is: all that reading its config.json needs
+_CONFIG_KWARGS = ("cache_dir", "force_download", "local_files_only", "token", "revision", "subfolder", "proxies", "trust_remote_code")
 
-    def forward(self, input_ids, attention_mask, token_type_ids=None, **kwargs):
-        if not self.training:
-            return self._hip_forward(input_ids, attention_mask, token_type_ids)
-        last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
-        embeddings = average_pool(last_hidden_states, attention_mask)
-        embeddings = F.normalize(embeddings, p=2, dim=1)
-        return embeddings
+
+class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
+    _hf_base = BertModel
+    _roberta_twin = None             # the same encoder over XLMRobertaModel (set below)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        """A BERT checkpoint loads exactly as ``BertModel.from_pretrained`` always did.  A RoBERTa-family checkpoint (``ROBERTA_TYPES``) has the same state-dict
+        names and would load into this class without an error and then compute with BERT's position ids: it goes to the XLM-R twin instead."""
+        if cls._roberta_twin is None:
+            return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        config = kwargs.get("config")
+        if isinstance(config, PretrainedConfig):
+            model_type = config.model_type
+        else:
+            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
+            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
+            model_type = cfg_dict.get("model_type", "bert")
+        if model_type in ROBERTA_TYPES:
+            return cls._roberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+
+
+class _HipXLMRSentenceEncoder(_HipSentenceMixin, XLMRobertaModel):
+    _hf_base = XLMRobertaModel
+
+
+class E5Encoder(_HipSentenceEncoder):
+    """BertModel -> masked mean -> L2 normalise"""
+    _pool = POOL_MEAN
 
 
 class BGEEncoder(_HipSentenceEncoder):
+    """BertModel -> [:, 0] -> L2 normalise"""
     _pool = POOL_CLS
 
-    def forward(self, input_ids, attention_mask, token_type_ids=None, **kwargs):
-        if not self.training:
-            return self._hip_forward(input_ids, attention_mask, token_type_ids)
-        last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
-        embeddings = last_hidden_states[:, 0]
-        embeddings = F.normalize(embeddings, p=2, dim=1)
-        return embeddings
+
+class XLMRobertaE5Encoder(_HipXLMRSentenceEncoder):
+    """XLMRobertaModel -> masked mean -> L2 normalise (intfloat/multilingual-e5-*)"""
+    _pool = POOL_MEAN
+
+
+class XLMRobertaBGEEncoder(_HipXLMRSentenceEncoder):
+    """XLMRobertaModel -> [:, 0] -> L2 normalise (the dense head of BAAI/bge-m3)"""
+    _pool = POOL_CLS
+
+
+E5Encoder._roberta_twin = XLMRobertaE5Encoder
+BGEEncoder._roberta_twin = XLMRobertaBGEEncoder

@@ -4,7 +4,9 @@ tolerance on YOUR weights, and could a cheaper mode be used?
 
     python tools/checkpoint_check.py <hf_dir> [--texts file.txt] [--n 16] [--max-length 128] [--pool mean|cls] [--emulate] [--json out.json]
 
-<hf_dir> is any HF BERT-family checkpoint directory (config.json + weights; e5-large-v2 / bge-large-en: retriever/e5.py:18-19 of the reference).  No
+<hf_dir> is any HF BERT-family checkpoint directory (config.json + weights; e5-large-v2 / bge-large-en: retriever/e5.py:18-19 of the reference) or a
+RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
+HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
 SYNTHETIC outlier recipes (golden set G10: "out3" models the two orders of magnitude between outlier and median channels that real
 BERT-family checkpoints show).  This tool replaces that assertion by a measurement the day weights exist.  It reports
@@ -35,7 +37,7 @@ MODES = [("f16", True), ("f16", False), ("bf16", True), ("bf16", False)]      # 
 MODE_COST = {("f16", True): "default: 29.5 ms per 1000-query step", ("f16", False): "-3 %", ("bf16", True): "-3.5 %", ("bf16", False): "-7 %"}
 
 
-def load_inputs(args, hf_dir, vocab):
+def load_inputs(args, hf_dir, vocab, pad_id=None):
     """-> list of (input_ids, attention_mask) int64 numpy batches: [queries, passages]"""
     tok = None
     if not args.random_tokens and os.path.isdir(hf_dir):
@@ -65,8 +67,12 @@ def load_inputs(args, hf_dir, vocab):
         lens = np.clip(rng.normal(0.8 * S, 0.2 * S, size=args.n).astype(np.int64), 3, S)
         ids = rng.integers(1000 if vocab > 2000 else 5, vocab, size=(args.n, S), dtype=np.int64)
         mask = (np.arange(S)[None, :] < lens[:, None]).astype(np.int64)
-        ids[:, 0] = 101 if vocab > 2000 else 1
-        ids = ids * mask
+        if pad_id is None:
+            ids[:, 0] = 101 if vocab > 2000 else 1
+            ids = ids * mask
+        else:                                          # RoBERTa family: <s> = 0 first, the pad id in every masked column (fairseq's rule counts what is not the pad id)
+            ids[:, 0] = 0
+            ids = np.where(mask != 0, ids, pad_id)
         out.append((ids, mask))
     return out
 
@@ -134,19 +140,25 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
-    if getattr(cfg, "model_type", "bert") != "bert":
-        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge)")
+    from kirag_amd.retriever.encoders import ROBERTA_TYPES
+    if getattr(cfg, "model_type", "bert") not in ("bert",) + ROBERTA_TYPES:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge) and the RoBERTa family "
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3)")
     model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
     return check_model(model, args, hf_dir)
 
 
 def check_model(model, args, hf_dir="(in-memory model)"):
-    """the same check on an already constructed HF BertModel (tests build one from the synthetic outlier recipes)"""
+    """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
+    from kirag_amd.retriever.encoders import ROBERTA_TYPES
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
+    roberta = getattr(cfg, "model_type", "bert") in ROBERTA_TYPES
+    if roberta and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} follows fairseq's position rule, which the torch emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
-    batches = load_inputs(args, hf_dir, cfg.vocab_size)
+    batches = load_inputs(args, hf_dir, cfg.vocab_size, cfg.pad_token_id if roberta else None)
     ref, table = reference_and_stats(model, batches, args.pool, dev)
     print(f"# {hf_dir}: {cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}; {sum(len(b[0]) for b in batches)} sequences, pooling {args.pool}; "
           f"tested path: {'HIP encoder (libkirag_amd)' if use_hip else 'torch emulation of the rounding points'}")

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6 ...] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3 ...] [--pool mean|cls] [--hf-fp16]
+                              [--first-forward]
 
-Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel in fp16 under torch on the
-same batch: a yardstick, not a product path."""
+Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
+torch on the same batch: a yardstick, not a product path.  --first-forward times, instead, the first eval forward of the MODULE (E5Encoder or its XLM-R
+twin on the GPU: the weight sync, the word table included) and the first one after a train() / eval() round trip."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,13 +14,22 @@ from kirag_amd import bench_support as BS
 
 PEAK_MFMA_DENSE_16BIT = 2.5e15   # MI355X_MICROARCH.md: bf16/f16 dense MFMA peak
 
+# the RoBERTa-family shapes (fairseq position rule, padding index 1): xlm-roberta-base / -large (multilingual-e5-base / -large) and bge-m3 (xlmr-large with
+# 8194 position rows = 8192 tokens)
+XLMR_LARGE = dict(BS.E5_LARGE, vocab_size=250002, max_position_embeddings=514, type_vocab_size=1, layer_norm_eps=1e-5, model_type="xlm-roberta", pad_token_id=1)
+XLMR_BASE = dict(XLMR_LARGE, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072)
+BGE_M3 = dict(XLMR_LARGE, max_position_embeddings=8194)
+SHAPES = dict(BS.ENCODER_SHAPES, **{"xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3})
+
 ap = argparse.ArgumentParser()
 ap.add_argument("n", type=int, nargs="?", default=1024)
 ap.add_argument("S", type=int, nargs="?", default=128)
 ap.add_argument("ragged", nargs="?", default="")
-ap.add_argument("--shape", action="append", choices=sorted(BS.ENCODER_SHAPES))
+ap.add_argument("--shape", action="append", choices=sorted(SHAPES))
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--hf-fp16", action="store_true")
+ap.add_argument("--pool", default="mean", choices=["mean", "cls"])
+ap.add_argument("--first-forward", action="store_true")
 args = ap.parse_args()
 n, S, ragged = args.n, args.S, args.ragged == "ragged"
 dev = torch.device("cuda:0")
@@ -35,21 +46,54 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def hf_classes(cfg):
+    """(config class, model class, sentence-encoder module) of a shape: the RoBERTa family by its model_type"""
+    import transformers as T
+    from kirag_amd.retriever import encoders as ENC
+    if cfg.get("model_type") in ENC.ROBERTA_TYPES:
+        return T.XLMRobertaConfig, T.XLMRobertaModel, (ENC.XLMRobertaE5Encoder if args.pool == "mean" else ENC.XLMRobertaBGEEncoder)
+    return T.BertConfig, T.BertModel, (ENC.E5Encoder if args.pool == "mean" else ENC.BGEEncoder)
+
+
+def first_forward(shape, cfg, ids, mask):
+    conf_cls, _, mod_cls = hf_classes(cfg)
+    m = mod_cls(conf_cls(**{k: v for k, v in cfg.items() if k not in ("hidden_act", "model_type")}), add_pooling_layer=False).to(dev).eval()
+
+    def once():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m(ids, mask)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    a, b = once(), once()
+    m.train(); m.eval()
+    c, d = once(), once()
+    print(f"{shape} module {mod_cls.__name__} n={n} S={S}: first eval forward {a:.0f} ms (weight sync), next {b:.2f} ms; after train() / eval(): {c:.0f} ms, next {d:.2f} ms",
+          flush=True)
+
+
+pool = 0 if args.pool == "mean" else 1
 for shape in args.shape or ["e5-large"]:
-    cfg = BS.ENCODER_SHAPES[shape]
-    enc = BS.make_hip_encoder(dev, cfg)
+    cfg = SHAPES[shape]
     ids, mask = BS.synthetic_tokens(dev, n, S, seed=1, ragged=ragged)
+    if "pad_token_id" in cfg:
+        ids = torch.where(mask != 0, ids, torch.full_like(ids, cfg["pad_token_id"]))      # fairseq's rule counts every column that does not hold the pad id
+    if args.first_forward:
+        first_forward(shape, cfg, ids, mask)
+        torch.cuda.empty_cache()
+        continue
+    enc = BS.make_hip_encoder(dev, cfg)
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
-    dt = timed(lambda: enc.forward(ids, mask, 0), args.reps)
+    dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
-          f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
+          f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
           f"{fl/dt/PEAK_MFMA_DENSE_16BIT:.3f} of MFMA peak  ({fl/n/1e9:.2f} GFLOP per sequence)", flush=True)
     del enc
     if args.hf_fp16:
-        from transformers import BertConfig, BertModel
-        m = BertModel(BertConfig(**{k: v for k, v in cfg.items() if k != "hidden_act"}), add_pooling_layer=False).to(dev).half().eval()
+        conf_cls, model_cls, _ = hf_classes(cfg)
+        m = model_cls(conf_cls(**{k: v for k, v in cfg.items() if k not in ("hidden_act", "model_type")}), add_pooling_layer=False).to(dev).half().eval()
         with torch.no_grad():
             dt = timed(lambda: m(input_ids=ids, attention_mask=mask).last_hidden_state, args.reps)
-        print(f"{shape} HF BertModel fp16 (yardstick) n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s", flush=True)
+        print(f"{shape} HF {model_cls.__name__} fp16 (yardstick) n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s", flush=True)
         del m
     torch.cuda.empty_cache()
