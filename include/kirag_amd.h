@@ -251,7 +251,19 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   fairseq's position rule (RoBERTa / XLM-R, pad_token_id = P = 1): the position embedding of column i of a row is P + (number of ids != P in columns
  *   0..i, attended or not) where ids[i] != P, and P where ids[i] == P; the forwards then take S <= max_pos - P - 1.  Without it the handle follows BERT's
  *   rule (position = column), bit for bit as before.  Accepted before the handle's first finalize and kept for the handle's life: later the same value is
- *   a no-op, another value KR_EINVAL.  kr_encoder_last_hidden keeps placing rows at their columns under both rules. */
+ *   a no-op, another value KR_EINVAL.  kr_encoder_last_hidden keeps placing rows at their columns under both rules.
+ * MPNetModel (all-mpnet-base-v2, multi-qa-mpnet-*): its state dict loads unchanged.  The layer names "encoder.layer.N.attention.attn.{q,k,v,o}.{weight,bias}"
+ * and "encoder.layer.N.attention.LayerNorm.{weight,bias}" fill the slots of BERT's attention.self.{query,key,value} / attention.output.{dense,LayerNorm}
+ * (last write wins when a caller uses both spellings for one slot).  MPNet has no token types: create the handle with type_vocab = 1 and load ONE row of
+ * zeros as "embeddings.token_type_embeddings.weight"; its embedding positions follow fairseq's rule with P = 1 ("config.position_padding_idx" above).
+ *   "encoder.relative_attention_bias.weight": 32 x heads floats ([bucket][head]; any other count is KR_EINVAL — MPNet always uses 32 buckets and
+ *   max_distance 128, whatever its config says).  Loading it makes the handle an MPNet handle: every attention score becomes
+ *       q.k / sqrt(d_h) + W[bucket(d)][head],   d = column of the key - column of the query,
+ *   where a token's column is its index in the padded [B, S] batch (not its position id and not its rank among the attended tokens; in
+ *   kr_encoder_forward_packed, the index inside its sequence), and with n = |d|:  bucket = n for n < 8, else min(15, 8 + max{ j >= 0 : 64 * 2^j <= n * n });
+ *   plus 16 when d > 0 (key after query).  Buckets 8 .. 15 begin at n = 8, 12, 16, 23, 32, 46, 64, 91.  Like the position rule this is fixed at the first
+ *   finalize: a handle finalized with the tensor takes new values for it later (followed by kr_encoder_finalize, as for every tensor), a handle finalized
+ *   without it refuses it with KR_EINVAL.  Handles without it run the same kernels, bit for bit, as before the tensor was known. */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);

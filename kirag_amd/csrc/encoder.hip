@@ -106,6 +106,11 @@ struct Encoder {
     int pad_idx = -1;
     bool finalized_once = false;
     int *tok_epos = nullptr;
+    // relative attention bias (MPNet): loading "encoder.relative_attention_bias.weight" [32 buckets, heads] makes the handle an MPNet handle; like the position
+    // rule that is fixed at the first finalize.  rel_w: the tensor as loaded (host); bias_tab: what the attention kernels read (AttnBiasArgs), built by finalize
+    std::vector<float> rel_w;
+    float* bias_tab = nullptr; int bias_width = 0;
+    bool bias_gather = false;  // KIRAG_AMD_ATTN_BIAS_GATHER=1 at kr_encoder_create: key columns always from tok_pos (the path of masks with holes), for tests
     float *out = nullptr;
     uint8_t *xlo = nullptr;    // low half of the residual stream, one byte per element (lo_encode): written by every LayerNorm with use_lo, else by the last one only
     bool use_lo = false;       // KIRAG_AMD_RESIDUAL_LO=1 at kr_encoder_create
@@ -920,16 +925,92 @@ __device__ __forceinline__ int attn_kswz(int key) { return (key >> (DH == 64 ? 1
 // cancels in o / l.  The slow path is taken by the whole wave (wave-uniform branch), so a tile's P.V is never split.  (Feeding -mref to the S^T MFMAs
 // as their C operand would save the subtraction too, but costs 16 more live registers per tile: measured as spills at three blocks per CU.)
 constexpr float ATTN_RESCALE_THR = 8.0f;
+
+// Relative attention bias (MPNet): score(head, query, key) += W[bucket(col_key - col_query)][head], col = the token's column in the padded batch (tok_pos).
+// The kernels read a per-handle fp32 table built at finalize: `width` floats per head, entry width / 2 + d = log2(e) * W[bucket(d)][head] for every column
+// difference d the position table allows (plus 64 entries of slack on both sides for the keys a masked tile reads past the sequence).  The bias TILE of a step
+// is loaded into the (dead) score registers and handed to the first S^T MFMA as its C operand in place of the zero tile: no add instruction, no extra live
+// registers, and a zero table starts the chain from the same zeros as the instantiation without a bias.  Both kernels and both ways of finding the column
+// difference load the same table entries into the same operand, so a sequence's rows do not depend on which of them ran.
+//   consecutive columns (right / left padding, ragged input): key column = col0 + packed key index: a lane's 8 consecutive keys are 8 consecutive entries
+//   holes in the mask (or KIRAG_AMD_ATTN_BIAS_GATHER=1): the column of every key is read from tok_pos
+// The query's column is always read from tok_pos (the extra CLS query row sits behind the keys in the packed order and has column 0).
+struct AttnBiasArgs {
+    const float* tab;     // [heads][width]
+    const int* col;       // tok_pos: column of every packed row
+    int width;            // floats per head (even); the entry of difference 0 is width / 2
+    int gather;           // != 0: take every key's column from `col` even when they are consecutive
+};
+struct AttnNoBiasArgs {};
+template <bool BIAS> using AttnBiasArg = std::conditional_t<BIAS, AttnBiasArgs, AttnNoBiasArgs>;
+
+// BM (bias mode of a kernel body, block-uniform): 0 no bias, 1 consecutive key columns, 2 gathered key columns.  The choice between 1 and 2 is made once per
+// block, outside the key loops (a branch inside them costs the accumulators register copies at every join)
+struct AttnNoBias { static constexpr bool on = false; };
+template <bool GATHER>
+struct AttnBiasLane {
+    static constexpr bool on = true;
+    const float* tab;     // table of the head (wave-uniform)
+    const int* col;       // columns of the sequence's packed rows (GATHER)
+    int lane0;            // width / 2 - column of this lane's query + 8 hf (+ the column of key 0 when the columns are consecutive)
+    int nk;
+};
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load at a 4-byte aligned address (one global_load_dwordx4)
+
+// does sequence (off, nk) need the gathered key columns?  (the packers write the attended columns in increasing order: consecutive <=> last - first = nk - 1)
+__device__ __forceinline__ bool attn_bias_gathers(const AttnBiasArgs& ba, int64_t off, int nk) {
+    return ba.gather != 0 || (nk >= 2 && ba.col[off + nk - 1] - ba.col[off] != nk - 1);
+}
+
+template <int BM>
+__device__ __forceinline__ auto attn_bias_lane(const AttnBiasArg<BM != 0>& ba, int64_t off, int nk, int head, int qi, int hf) {
+    if constexpr (BM != 0) {
+        const int* col = ba.col + off;
+        AttnBiasLane<BM == 2> bl;
+        bl.tab = ba.tab + (int64_t)head * ba.width;
+        bl.col = col;
+        bl.lane0 = (ba.width >> 1) - col[qi] + 8 * hf + (BM == 1 && nk > 0 ? col[0] : 0);
+        bl.nk = nk;
+        return bl;
+    } else {
+        return AttnNoBias{};
+    }
+}
+
+// the bias of one 32-key tile in the layout of the score registers: register r = key kb + 16 (r >> 3) + 8 hf + (r & 7) of the sequence, this lane's query
+template <bool GATHER>
+__device__ __forceinline__ void attn_bias_tile(f32x16& st, const AttnBiasLane<GATHER>& bl, int kb, int hf) {
+    __builtin_amdgcn_sched_barrier(0);      // the loads stay behind the previous step: hoisted into it they would need registers next to its live score tiles
+    if constexpr (!GATHER) {
+        const float* p = bl.tab + (unsigned)(bl.lane0 + kb);     // unsigned 32-bit lane offset on a wave-uniform base: one address register per lane
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const f32x4u x = *reinterpret_cast<const f32x4u*>(p + 16 * a), y = *reinterpret_cast<const f32x4u*>(p + 16 * a + 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { st[8 * a + i] = x[i]; st[8 * a + 4 + i] = y[i]; }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = kb + 16 * (r >> 3) + 8 * hf + (r & 7);
+            st[r] = bl.tab[(unsigned)(bl.lane0 - 8 * hf + bl.col[(unsigned)min(key, bl.nk - 1)])];     // keys >= nk are masked below: any entry will do
+        }
+    }
+}
 // first half of a step: the shifted-score tiles S^T = K . Q^T (st1 = -inf when the second 32-key tile does not exist)
 // MODE (wave-uniform, picked from the number of valid keys of the step): 0 = 64, 1 = fewer than 32 (first tile masked, no second tile),
 // 2 = exactly 32 (one full tile: a 32-token sequence), 3 = 33 .. 63 (second tile masked)
 // PF (k_attn_dma): all K fragments of the step are requested before the first MFMA (counted lgkmcnt waits instead of one exposed LDS round trip per
 // MFMA); same MFMAs in the same order, so the result does not depend on it
-template <int DH, int MODE, bool PF = false>
-__device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf) {
+// BL: AttnNoBias, or AttnBiasLane with kb = index of the step's first key in its sequence: the chains start from the bias tiles instead of zero
+template <int DH, int MODE, bool PF = false, class BL>
+__device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, const BL& bl, int kb) {
     constexpr bool two = MODE == 0 || MODE == 3;
     constexpr int NK = DH / 16, KR = 2 * DH;              // k-steps of S^T; bytes per K row
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (BL::on) attn_bias_tile(st0, bl, kb, hf);
+    auto c0 = [&]() -> const f32x16& { if constexpr (BL::on) return st0; else return zero; };
+    auto c1 = [&]() -> const f32x16& { if constexpr (BL::on) return st1; else return zero; };
     if constexpr (PF) {
         const int key = k0 + attn_perm(c);
         const char* krow = Kst + key * KR;
@@ -941,11 +1022,12 @@ __device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint
 #pragma unroll
             for (int sk = 0; sk < NK; ++sk) kf[NK + sk] = *reinterpret_cast<const uint4*>(krow + 32 * KR + (((2 * sk + hf) ^ swz) << 4));
         }
-        st0 = ET::mfma(kf[0], qf[0], zero);
+        st0 = ET::mfma(kf[0], qf[0], c0());
 #pragma unroll
         for (int sk = 1; sk < NK; ++sk) st0 = ET::mfma(kf[sk], qf[sk], st0);
         if constexpr (two) {
-            st1 = ET::mfma(kf[NK], qf[0], zero);
+            if constexpr (BL::on) attn_bias_tile(st1, bl, kb + 32, hf);     // after the first chain: its K fragments are dead by now
+            st1 = ET::mfma(kf[NK], qf[0], c1());
 #pragma unroll
             for (int sk = 1; sk < NK; ++sk) st1 = ET::mfma(kf[NK + sk], qf[sk], st1);
         } else {
@@ -956,12 +1038,13 @@ __device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint
         const int key = k0 + attn_perm(c);
         const char* krow = Kst + key * KR;
         const int swz = attn_kswz<DH>(key);
-        st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((0 + hf) ^ swz) << 4)), qf[0], zero);
+        st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((0 + hf) ^ swz) << 4)), qf[0], c0());
 #pragma unroll
         for (int sk = 1; sk < NK; ++sk) st0 = ET::mfma(*reinterpret_cast<const uint4*>(krow + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st0);
         if (two) {
             const char* krow1 = krow + 32 * KR;           // attn_kswz(key + 32) == swz
-            st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((0 + hf) ^ swz) << 4)), qf[0], zero);
+            if constexpr (BL::on) attn_bias_tile(st1, bl, kb + 32, hf);
+            st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((0 + hf) ^ swz) << 4)), qf[0], c1());
 #pragma unroll
             for (int sk = 1; sk < NK; ++sk) st1 = ET::mfma(*reinterpret_cast<const uint4*>(krow1 + (((2 * sk + hf) ^ swz) << 4)), qf[sk], st1);
         } else {
@@ -1039,19 +1122,19 @@ __device__ __forceinline__ void attn_softmax_pv(AttnState<DH>& s, const f32x16& 
     s.l += psum;
 }
 
-template <int MODE, bool PF = false, int DH, class VFrag>
-__device__ __forceinline__ void attn_step64m(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
+template <int MODE, bool PF = false, int DH, class VFrag, class BL>
+__device__ __forceinline__ void attn_step64m(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag, const BL& bl, int kb) {
     f32x16 st0, st1;
-    attn_scores<DH, MODE, PF>(st0, st1, qf, Kst, k0, nvalid, c, hf);
+    attn_scores<DH, MODE, PF>(st0, st1, qf, Kst, k0, nvalid, c, hf, bl, kb);
     attn_softmax_pv<MODE, PF>(s, st0, st1, vfrag);
 }
-// MASKED = false: 64 valid keys; true: fewer (nvalid says how many)
-template <bool MASKED, bool PF = false, int DH, class VFrag>
-__device__ __forceinline__ void attn_step64(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag) {
-    if constexpr (!MASKED) attn_step64m<0, PF>(s, qf, Kst, k0, 64, c, hf, vfrag);
-    else if (nvalid == 32) attn_step64m<2>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
-    else if (nvalid < 32) attn_step64m<1>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
-    else attn_step64m<3>(s, qf, Kst, k0, nvalid, c, hf, vfrag);
+// MASKED = false: 64 valid keys; true: fewer (nvalid says how many).  bl / kb: the relative attention bias of the lane and the step's first key (attn_scores)
+template <bool MASKED, bool PF = false, int DH, class VFrag, class BL>
+__device__ __forceinline__ void attn_step64(AttnState<DH>& s, const uint4 (&qf)[DH / 16], const char* Kst, int k0, int nvalid, int c, int hf, VFrag&& vfrag, const BL& bl, int kb) {
+    if constexpr (!MASKED) attn_step64m<0, PF>(s, qf, Kst, k0, 64, c, hf, vfrag, bl, kb);
+    else if (nvalid == 32) attn_step64m<2>(s, qf, Kst, k0, nvalid, c, hf, vfrag, bl, kb);
+    else if (nvalid < 32) attn_step64m<1>(s, qf, Kst, k0, nvalid, c, hf, vfrag, bl, kb);
+    else attn_step64m<3>(s, qf, Kst, k0, nvalid, c, hf, vfrag, bl, kb);
 }
 
 // normalise a finished 32-query tile and store it as whole 2 DH-byte rows of ctx (columns head * DH ..) through the wave-private LDS block Os of
@@ -1092,11 +1175,10 @@ __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os
 // stages half the bytes (<= 25 KiB per block for any HPB, see launch_attn) and keeps half the Q fragments and accumulators: four blocks per CU (<= 128
 // registers).
 template <int DH> constexpr int attn_lds_blocks() { return DH == 64 ? 3 : 4; }
-template <int DH, int HPB>
-__global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
-                                                  const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int DH, int HPB, int BM>
+__device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
+                                              const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
+                                              int H, int heads, int kchunk, uint16_t* __restrict__ ctx, const AttnBiasArg<BM != 0>& ba, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; as a scalar, the head / q-tile / LDS bases derived from it cost no VGPRs
     const int hb = blockIdx.x, b = blockIdx.y;            // heads fastest: the heads of one sequence (same 2-KiB q/k rows) run together
@@ -1119,6 +1201,7 @@ __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const u
     const int c = lane & 31, hf = lane >> 5;
     // Q^T as the B operand: lane (c, hf) holds Q[q0 + c][16 s + 8 hf .. +7], s = 0 .. DH / 16 - 1
     uint4 qf[DH / 16] = {};
+    const auto bl = attn_bias_lane<BM>(ba, off, nk, head, min(q0 + c, nq - 1), hf);    // nq >= 1 here; an inactive wave never reads through it
     if (active) {
         const int qi = (q0 + c < nq) ? (q0 + c) : (nq - 1);
         const uint16_t* qrow = q + (off + qi) * H + head * DH;
@@ -1216,7 +1299,7 @@ __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const u
                 const uint2 a0 = *reinterpret_cast<const uint2*>(v), a1 = *reinterpret_cast<const uint2*>(v + 8);
                 return make_uint4(a0.x, a0.y, a1.x, a1.y);
             };
-            attn_step64<false>(st, qf, Kh, k0, 64, c, hf, vfrag);
+            attn_step64<false>(st, qf, Kh, k0, 64, c, hf, vfrag, bl, kc0 + k0);
         }
         if (kfull < nkc) {
             auto vfrag = [&](int dh, int ks) {
@@ -1224,11 +1307,25 @@ __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const u
                 const uint2 a0 = *reinterpret_cast<const uint2*>(v), a1 = *reinterpret_cast<const uint2*>(v + 8);
                 return make_uint4(a0.x, a0.y, a1.x, a1.y);
             };
-            attn_step64<true>(st, qf, Kh, kfull, nkc - kfull, c, hf, vfrag);
+            attn_step64<true>(st, qf, Kh, kfull, nkc - kfull, c, hf, vfrag, bl, kc0 + kfull);
         }
     }
     if (!active) return;
     attn_store_tile(st, Os, ctx, off, q0, nq, H, head, lane);
+}
+
+template <int DH, int HPB, bool BIAS = false>
+__global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
+                                                  const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
+                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS> ba) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (BIAS) {
+        const int b = blockIdx.y;
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 2>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        else attn_lds_body<DH, HPB, 1>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+    } else {
+        attn_lds_body<DH, HPB, 0>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+    }
 }
 
 // ---- long sequences: LDS-DMA ring ------------------------------------------------------------------------------------------------------------
@@ -1254,9 +1351,9 @@ struct AdmaGeom {
 // needs both score tiles live: 42 spilled registers at the 256-register limit, two of them reloaded per chunk (VMEM: the DMA ring drains) — not kept.
 // (the body is a function with __restrict__ K / V^T pointers on purpose: after inlining the LDS-DMA carries their alias scope and the ring's ds_reads are
 // marked as not aliasing it, which lets the compiler's waitcnt pass leave the COUNTED vmcnt waits alone; see coarse_q32_body in search.hip)
-template <int DH>
+template <int DH, int BM>
 __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
-                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem) {
+                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, const AttnBiasArg<BM != 0>& ba) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hf = lane >> 5;
     using G = AdmaGeom<DH>;
@@ -1301,10 +1398,12 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     int q0[2]; bool act[2];
     uint4 qf[2][DH / 16] = {};
     AttnState<DH> st[2];
+    decltype(attn_bias_lane<BM>(ba, off, nk, head, 0, hf)) bl[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         q0[j] = (qg * ADMA_QT + wave + ADMA_WAVES * j) * 32;
         act[j] = q0[j] < nq;                               // wave-uniform; act[1] implies act[0]
+        bl[j] = attn_bias_lane<BM>(ba, off, nk, head, min(q0[j] + c, nq - 1), hf);      // nq >= 1 (k_attn_dma)
         if (act[j]) {
             const int qi = (q0[j] + c < nq) ? (q0[j] + c) : (nq - 1);
             const uint16_t* qrow = q + (off + qi) * H + head * DH;
@@ -1329,8 +1428,9 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
             const int d = c + 32 * dh;
             return *reinterpret_cast<const uint4*>(stg + KB + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
         };
-        attn_step64<false, true>(st[0], qf[0], stg, 0, 64, c, hf, vfrag);
-        if constexpr (decltype(two_tiles)::value) attn_step64<false, true>(st[1], qf[1], stg, 0, 64, c, hf, vfrag);
+        // (gathered key columns: without the fragment prefetch — the gather's indices and the prefetched fragments together do not fit the register file)
+        attn_step64<false, BM != 2>(st[0], qf[0], stg, 0, 64, c, hf, vfrag, bl[0], ci * 64);
+        if constexpr (decltype(two_tiles)::value) attn_step64<false, BM != 2>(st[1], qf[1], stg, 0, 64, c, hf, vfrag, bl[1], ci * 64);
     };
     if (act[1]) {
         for (int ci = 0; ci < nfull; ++ci) full_chunk(ci, std::true_type{});
@@ -1366,8 +1466,8 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (!act[j]) continue;
-            if (nkc < 64) attn_step64<true>(st[j], qf[j], stg, 0, nkc, c, hf, vfrag);
-            else attn_step64<false>(st[j], qf[j], stg, 0, 64, c, hf, vfrag);
+            if (nkc < 64) attn_step64<true>(st[j], qf[j], stg, 0, nkc, c, hf, vfrag, bl[j], ci * 64);
+            else attn_step64<false>(st[j], qf[j], stg, 0, 64, c, hf, vfrag, bl[j], ci * 64);
         }
     }
     __syncthreads();                                       // the ring is free: re-use it for the O staging
@@ -1377,9 +1477,10 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         if (act[j]) attn_store_tile(st[j], Os, ctx, off, q0[j], nq, H, head, lane);
 }
 
-template <int DH>
+template <int DH, bool BIAS = false>
 __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* __restrict__ seq_off,
-                                                             const int* __restrict__ seq_nk, const int* __restrict__ seq_nq, int H, int64_t capT, uint16_t* ctx, int heads, int nseq, int qgroups) {
+                                                             const int* __restrict__ seq_nk, const int* __restrict__ seq_nq, int H, int64_t capT, uint16_t* ctx, int heads, int nseq, int qgroups,
+                                                             AttnBiasArg<BIAS> ba) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // linear block id -> (pair p = b * heads + head, q-group qg).  Consecutive workgroups go to consecutive XCDs (id mod 8), and each XCD has its own L2:
     // the q-groups of one (sequence, head) read the same K / V^T stream, so they are placed 8 ids apart — same XCD, dispatched together — and the second
@@ -1393,7 +1494,12 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
     if (b >= nseq) return;                                 // the grid is padded to whole groups of 8 pairs
     const int nq = seq_nq[b];
     if (qg * ADMA_QT * 32 >= nq) return;                   // block-uniform (nq == 0 included)
-    attn_dma_body<DH>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem);
+    if constexpr (BIAS) {
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 2>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+        else attn_dma_body<DH, 1>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+    } else {
+        attn_dma_body<DH, 0>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+    }
 }
 
 // pooling + L2 normalisation: one block per sequence.  Mean pooling: wave w sums the tokens t = w, w+4, ... (8-byte loads of the (hi, lo)
@@ -1544,6 +1650,8 @@ static int ensure_ws(Encoder* e, int B, int S) {
 
 // tensor slot ids: 0..4 embeddings, then 16 per layer
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
+constexpr int T_RELBIAS = -2;          // not a slot of `got`: an optional tensor (parse_name)
+constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says
 enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_COUNT };
 
 static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& numel) {
@@ -1552,13 +1660,21 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     size_t pl = s.find("encoder.layer.");
     const int64_t H = e->cfg.hidden, FF = e->cfg.intermediate;
     if (s.find("position_ids") != std::string::npos || s.find("pooler.") != std::string::npos) { slot = -1; return 0; }
+    {
+        static const char rel[] = "encoder.relative_attention_bias.weight";
+        if (s.size() >= sizeof(rel) - 1 && s.compare(s.size() - (sizeof(rel) - 1), sizeof(rel) - 1, rel) == 0) { slot = T_RELBIAS; numel = (int64_t)REL_BUCKETS * e->cfg.heads; return 0; }
+    }
     if (pl != std::string::npos) {
         const char* c = s.c_str() + pl + strlen("encoder.layer.");
         char* end = nullptr;
         const long l = strtol(c, &end, 10);
         if (end == c || *end != '.' || l < 0 || l >= e->cfg.layers) return fail(KR_EINVAL, "bad layer index in '%s'", name);
         const std::string r(end + 1);
+        // BERT's names (BertModel, RobertaModel, XLMRobertaModel) and MPNet's (MPNetModel: attention.attn.{q,k,v,o}, attention.LayerNorm) for the same slots
         static const struct { const char* n; int id; } tbl[] = {
+            {"attention.attn.q.weight", L_QW}, {"attention.attn.q.bias", L_QB}, {"attention.attn.k.weight", L_KW}, {"attention.attn.k.bias", L_KB},
+            {"attention.attn.v.weight", L_VW}, {"attention.attn.v.bias", L_VB}, {"attention.attn.o.weight", L_OW}, {"attention.attn.o.bias", L_OB},
+            {"attention.LayerNorm.weight", L_LN1G}, {"attention.LayerNorm.bias", L_LN1B},
             {"attention.self.query.weight", L_QW}, {"attention.self.query.bias", L_QB}, {"attention.self.key.weight", L_KW},
             {"attention.self.key.bias", L_KB}, {"attention.self.value.weight", L_VW}, {"attention.self.value.bias", L_VB},
             {"attention.output.dense.weight", L_OW}, {"attention.output.dense.bias", L_OB},
@@ -1589,7 +1705,9 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     return fail(KR_EINVAL, "unknown tensor name '%s'", name);
 }
 
-template <int DH, int HPB>
+static AttnBiasArgs bias_args(const Encoder* e) { return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0}; }
+
+template <int DH, int HPB, bool BIAS>
 static int launch_attn(const Encoder* e, int B, int cap, int nqt, hipStream_t st) {
     const int H = e->cfg.hidden, heads = e->cfg.heads;
     // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
@@ -1599,32 +1717,36 @@ static int launch_attn(const Encoder* e, int B, int cap, int nqt, hipStream_t st
     static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance
     int& attr_lds = attr_lds_dev[e->device & 63];
     if (lds > attr_lds) {
-        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_lds = lds;
     }
     const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
-    hipLaunchKernelGGL((k_attn_lds<DH, HPB>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
-                       e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx);
+    AttnBiasArg<BIAS> ba{};
+    if constexpr (BIAS) ba = bias_args(e);
+    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
+                       e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, ba);
     return 0;
 }
 
-template <int DH>
+template <int DH, bool BIAS>
 static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
     const int64_t pairs = (int64_t)B * e->cfg.heads;
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
-    hipLaunchKernelGGL(k_attn_dma<DH>, dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
-                       e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups);
+    AttnBiasArg<BIAS> ba{};
+    if constexpr (BIAS) ba = bias_args(e);
+    hipLaunchKernelGGL((k_attn_dma<DH, BIAS>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
+                       e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, ba);
     return 0;
 }
 
 // the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
-template <int DH>
+template <int DH, bool BIAS>
 static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, hipStream_t st) {
-    if (long_seq) return launch_attn_dma<DH>(e, B, nqt, st);
-    if (nqt >= 3) return launch_attn<DH, 1>(e, B, cap, nqt, st);
-    if (nqt == 2) return launch_attn<DH, 2>(e, B, cap, nqt, st);
-    return launch_attn<DH, 4>(e, B, cap, nqt, st);
+    if (long_seq) return launch_attn_dma<DH, BIAS>(e, B, nqt, st);
+    if (nqt >= 3) return launch_attn<DH, 1, BIAS>(e, B, cap, nqt, st);
+    if (nqt == 2) return launch_attn<DH, 2, BIAS>(e, B, cap, nqt, st);
+    return launch_attn<DH, 4, BIAS>(e, B, cap, nqt, st);
 }
 
 static int set_lds_once(const void* kern, int lds, int device);
@@ -1750,6 +1872,7 @@ int enc_create(const kr_bert_cfg* cfg, int device, int residual_lo, void** out) 
     e->cfg = *cfg; e->device = device;
     e->use_lo = residual_lo != 0;
     { const char* v = getenv("KIRAG_AMD_CLS_FULL"); e->cls_shortcut = !(v && atoi(v) != 0); }
+    { const char* v = getenv("KIRAG_AMD_ATTN_BIAS_GATHER"); e->bias_gather = v && atoi(v) != 0; }
     { const char* v = getenv("KIRAG_AMD_GRAPH"); e->graphs_off = !(v && atoi(v) != 0); }   // opt-in: measured SLOWER than eager launches on ROCm 7.2 (see run_forward)
     { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) e->num_cu = (p.multiProcessorCount / 8) * 8; }
     e->num_cu_all = e->num_cu;
@@ -1780,7 +1903,7 @@ void enc_destroy(void* h) {
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     if (e->gstream) (void)hipStreamDestroy(e->gstream);
-    void* ptrs[] = {e->word, e->pos, e->type, e->elng, e->elnb, e->stage, e->d_T, e->d_err};
+    void* ptrs[] = {e->word, e->pos, e->type, e->elng, e->elnb, e->stage, e->d_T, e->d_err, e->bias_tab};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& l : e->L) {
         void* lp[] = {l.wqkv, l.wo, l.w1, l.w2, l.bqkv, l.bo, l.bo_eff, l.b1, l.b2, l.ln1g, l.ln1b, l.ln2g, l.ln2b};
@@ -1807,6 +1930,48 @@ static int set_config(Encoder* e, const char* name, const float* data, int64_t n
     return 0;
 }
 
+// MPNet's bucket of a column difference d = col_key - col_query (MPNetEncoder.relative_position_bucket with its fixed 32 buckets / max_distance 128, whose
+// float32 log this integer rule reproduces for every |d| <= 8200): n = |d|; n < 8: n, else min(15, 8 + max{j >= 0 : 64 * 2^j <= n^2}); + 16 when d > 0
+static int rel_bucket(int d) {
+    const int64_t n = d < 0 ? -(int64_t)d : d;
+    int b = (int)n;
+    if (n >= 8) {
+        b = 8;
+        while (b < 15 && (int64_t)128 << (b - 8) <= n * n) ++b;
+    }
+    return b + (d > 0 ? 16 : 0);
+}
+
+// encoder.relative_attention_bias.weight [32, heads].  Before the first finalize it makes the handle an MPNet handle; afterwards a handle that has it takes
+// new values (the weight sync reloads every parameter) and a handle finalized without it refuses it.
+static int load_rel_bias(Encoder* e, const char* name, const float* data, int64_t numel, int64_t want) {
+    if (numel != want)
+        return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets)", name, (long long)numel, (long long)want,
+                    REL_BUCKETS, e->cfg.heads, REL_BUCKETS);
+    if (e->finalized_once && e->rel_w.empty())
+        return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a relative attention bias and stays a BERT / RoBERTa handle", name);
+    std::vector<float> w((size_t)numel);
+    KR_HIP(hipMemcpy(w.data(), data, (size_t)numel * 4, hipMemcpyDefault));
+    e->rel_w.swap(w);
+    e->ready = false;
+    return 0;
+}
+
+// the table the attention kernels read (AttnBiasArgs): per head, log2(e) * W[bucket(d)][head] at entry width / 2 + d, |d| < max_pos + 64 (every column
+// difference the position table allows; the slack covers the keys a masked tile reads past the end of its sequence).  The scores are in log2 units
+// (enc_load_weight folds log2(e) / sqrt(d_h) into W_q): the same fp32 multiply here.
+static int build_bias_table(Encoder* e) {
+    const int heads = e->cfg.heads, half = e->cfg.max_pos + 64, width = 2 * half;
+    std::vector<float> tab((size_t)heads * width);
+    const float log2e = (float)1.4426950408889634;
+    for (int h = 0; h < heads; ++h)
+        for (int i = 0; i < width; ++i) tab[(size_t)h * width + i] = e->rel_w[(size_t)rel_bucket(i - half) * heads + h] * log2e;
+    if (!e->bias_tab) KR_TRY(dmalloc(&e->bias_tab, tab.size() * 4));
+    KR_HIP(hipMemcpy(e->bias_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    e->bias_width = width;
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
@@ -1814,6 +1979,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
     int slot = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want));
+    if (slot == T_RELBIAS) return load_rel_bias(e, hf_name, data, numel, want);
     if (slot < 0) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
     if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", hf_name, (long long)numel, (long long)want);
     if ((size_t)numel > e->stage_elems) {
@@ -1871,6 +2037,7 @@ int enc_finalize(void* h) {
     KR_TRY(select_device(e->device));
     const int H = e->cfg.hidden;
     for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * H, l.bo_eff, H);
+    if (!e->rel_w.empty()) KR_TRY(build_bias_table(e));
     KR_HIP(hipGetLastError());
     KR_HIP(hipDeviceSynchronize());
     e->ready = true;
@@ -1952,8 +2119,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, b
         KR_TRY(launch_proj(EPI_QKV, a, maxT, e, st));
         {
             const int cap = (int)round_up(S, 32);
-            if (H == 32 * e->cfg.heads) KR_TRY(launch_attention<32>(e, B, cap, nqt_max, long_seq, st));
-            else KR_TRY(launch_attention<64>(e, B, cap, nqt_max, long_seq, st));
+            const bool bias = e->bias_tab != nullptr;      // an MPNet handle: the instantiations with the relative attention bias
+            if (H == 32 * e->cfg.heads) KR_TRY((bias ? launch_attention<32, true>(e, B, cap, nqt_max, long_seq, st) : launch_attention<32, false>(e, B, cap, nqt_max, long_seq, st)));
+            else KR_TRY((bias ? launch_attention<64, true>(e, B, cap, nqt_max, long_seq, st) : launch_attention<64, false>(e, B, cap, nqt_max, long_seq, st)));
         }
         if (last && shortcut) {
             // only the CLS row of every sequence is read after this layer: gather those rows and finish the layer on B rows (same kernels, same arithmetic per

@@ -19,6 +19,11 @@ state-dict names are identical, but the embedding position follows fairseq's rul
 the id is the padding id).  ``XLMRobertaE5Encoder`` / ``XLMRobertaBGEEncoder`` are the twins of the two classes above over ``transformers.XLMRobertaModel``;
 ``E5Encoder.from_pretrained`` / ``BGEEncoder.from_pretrained`` read the checkpoint's ``config.json`` first and return the twin for such a checkpoint, so the
 registry names ``E5Retriever`` / ``BGERetriever`` serve both families.
+
+MPNet checkpoints (``model_type`` mpnet: all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1, paraphrase-mpnet-base-v2): BERT's post-LN stack under other state-dict
+names, no token types, fairseq's position rule with padding index 1, and one learned bias per (head, bucket of the column distance) added to every attention
+score — a table the attention kernels read (``encoder.relative_attention_bias.weight``).  ``MPNetE5Encoder`` / ``MPNetBGEEncoder`` are the twins over
+``transformers.MPNetModel``; ``from_pretrained`` of the two registry classes dispatches to them as well.
 """
 from __future__ import annotations
 
@@ -28,13 +33,16 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, PretrainedConfig, XLMRobertaModel
+from transformers import BertModel, MPNetModel, PretrainedConfig, XLMRobertaModel
 
 from .. import _lib
 
 POOL_MEAN, POOL_CLS = 0, 1
 # model_type values whose position ids follow fairseq's rule on BERT's post-LN layer stack ("xlm-roberta-xl" is pre-LN: not one of them)
 ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
+MPNET_TYPE = "mpnet"
+MPNET_PADDING_IDX = 1    # MPNetEmbeddings.padding_idx: a class constant of HF's implementation, not config.pad_token_id
+MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
 
 
 def average_pool(last_hidden_states: Tensor, attention_mask: Tensor) -> Tensor:
@@ -54,8 +62,14 @@ class HipBertForward:
             raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only")
         if getattr(config, "position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only absolute position embeddings are implemented")
+        self.is_mpnet = getattr(config, "model_type", "bert") == MPNET_TYPE
+        if self.is_mpnet and getattr(config, "relative_attention_num_buckets", MPNET_BUCKETS) != MPNET_BUCKETS:
+            raise ValueError(f"relative_attention_num_buckets={config.relative_attention_num_buckets}: MPNet's bias table has {MPNET_BUCKETS} buckets "
+                             "(the only size HF's MPNetEncoder computes with)")
+        # MPNet has no token types: one row of zeros stands in for the table (sync supplies it)
+        type_vocab = 1 if self.is_mpnet else config.type_vocab_size
         cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, config.intermediate_size,
-                           config.vocab_size, config.max_position_embeddings, config.type_vocab_size, float(config.layer_norm_eps))
+                           config.vocab_size, config.max_position_embeddings, type_vocab, float(config.layer_norm_eps))
         h = C.c_void_p()
         dt = -1 if operand_dtype is None else {"bf16": 0, "f16": 1}[operand_dtype]
         lo = -1 if residual_lo is None else int(bool(residual_lo))
@@ -68,8 +82,8 @@ class HipBertForward:
         # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P.  It travels through the
         # name-addressed loader under the reserved name "config.position_padding_idx", before the first finalize, and holds for the handle's life
         self.position_padding_idx = None
-        if getattr(config, "model_type", "bert") in ROBERTA_TYPES:
-            P = getattr(config, "pad_token_id", None)
+        if self.is_mpnet or getattr(config, "model_type", "bert") in ROBERTA_TYPES:
+            P = MPNET_PADDING_IDX if self.is_mpnet else getattr(config, "pad_token_id", None)
             if P is None:
                 raise ValueError(f"model_type={config.model_type!r} needs config.pad_token_id (the padding index of fairseq's position rule)")
             v = C.c_float(float(P))
@@ -122,8 +136,14 @@ class HipBertForward:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
+        self._load_zero_token_types()
         _lib.check(self._lib.kr_encoder_finalize(self._h))
         self.fingerprint = fp
+
+    def _load_zero_token_types(self) -> None:
+        if self.is_mpnet:
+            z = torch.zeros(self.hidden, dtype=torch.float32)
+            _lib.check(self._lib.kr_encoder_load_weight(self._h, b"embeddings.token_type_embeddings.weight", z.data_ptr(), z.numel()))
 
     def load_state(self, state: dict) -> None:
         """Load weights from a mapping HF-state-dict-name -> numpy array / tensor (host or device)."""
@@ -136,6 +156,8 @@ class HipBertForward:
                 w = w.detach().float().contiguous()
                 ptr, n = w.data_ptr(), w.numel()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), ptr, n))
+        if not any(name.endswith("token_type_embeddings.weight") for name in state):
+            self._load_zero_token_types()
         _lib.check(self._lib.kr_encoder_finalize(self._h))
         self.fingerprint = None
 
@@ -234,7 +256,7 @@ class HipBertForward:
 
 
 class _HipSentenceMixin:
-    """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel`` or ``XLMRobertaModel``, the next class in the MRO): the HIP
+    """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel``, ``XLMRobertaModel`` or ``MPNetModel``, the next class in the MRO): the HIP
     eval forward, weight sync, ``forward_packed``, the train / eval switch and the pooled autograd forward of ``train()`` mode."""
     _pool = POOL_MEAN
     _hf_base = None
@@ -302,7 +324,8 @@ class _HipSentenceMixin:
         return out
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, return_dict=True)
+        kw = {} if self._hf_base is MPNetModel else {"token_type_ids": token_type_ids}     # MPNet has no token types
+        out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
     def forward(self, input_ids, attention_mask, token_type_ids=None, **kwargs):
@@ -325,6 +348,7 @@ _CONFIG_KWARGS = ("cache_dir", "force_download", "local_files_only", "token", "r
 class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _hf_base = BertModel
     _roberta_twin = None             # the same encoder over XLMRobertaModel (set below)
+    _mpnet_twin = None               # ... and over MPNetModel
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -341,11 +365,18 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
             model_type = cfg_dict.get("model_type", "bert")
         if model_type in ROBERTA_TYPES:
             return cls._roberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type == MPNET_TYPE:
+            # MPNet's layer names differ: loaded into this class every layer would stay randomly initialised, with warnings only
+            return cls._mpnet_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
 class _HipXLMRSentenceEncoder(_HipSentenceMixin, XLMRobertaModel):
     _hf_base = XLMRobertaModel
+
+
+class _HipMPNetSentenceEncoder(_HipSentenceMixin, MPNetModel):
+    _hf_base = MPNetModel
 
 
 class E5Encoder(_HipSentenceEncoder):
@@ -368,5 +399,17 @@ class XLMRobertaBGEEncoder(_HipXLMRSentenceEncoder):
     _pool = POOL_CLS
 
 
+class MPNetE5Encoder(_HipMPNetSentenceEncoder):
+    """MPNetModel -> masked mean -> L2 normalise (sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1)"""
+    _pool = POOL_MEAN
+
+
+class MPNetBGEEncoder(_HipMPNetSentenceEncoder):
+    """MPNetModel -> [:, 0] -> L2 normalise"""
+    _pool = POOL_CLS
+
+
 E5Encoder._roberta_twin = XLMRobertaE5Encoder
 BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
+E5Encoder._mpnet_twin = MPNetE5Encoder
+BGEEncoder._mpnet_twin = MPNetBGEEncoder

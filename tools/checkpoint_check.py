@@ -5,6 +5,7 @@ tolerance on YOUR weights, and could a cheaper mode be used?
     python tools/checkpoint_check.py <hf_dir> [--texts file.txt] [--n 16] [--max-length 128] [--pool mean|cls] [--emulate] [--json out.json]
 
 <hf_dir> is any HF BERT-family checkpoint directory (config.json + weights; e5-large-v2 / bge-large-en: retriever/e5.py:18-19 of the reference) or a
+MPNet one (model_type mpnet: all-mpnet-base-v2, multi-qa-mpnet-*; reference MPNetModel in fp32, GPU only) or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -93,8 +94,11 @@ def reference_and_stats(model, batches, pool, dev):
         return fn
     for li, layer in enumerate(model.encoder.layer):
         att = layer.attention
-        for key, mod in (("q", att.self.query), ("k", att.self.key), ("v", att.self.value), ("ctx", att.self), ("y1", att.output.dense), ("ln1", att.output.LayerNorm),
-                         ("h", layer.intermediate), ("y2", layer.output.dense), ("ln2", layer.output.LayerNorm)):
+        if hasattr(att, "attn"):                       # MPNetModel: q / k / v / o live in attention.attn (whose output is already o's), the LayerNorm in attention
+            mods = (("q", att.attn.q), ("k", att.attn.k), ("v", att.attn.v), ("y1", att.attn.o), ("ln1", att.LayerNorm))
+        else:
+            mods = (("q", att.self.query), ("k", att.self.key), ("v", att.self.value), ("ctx", att.self), ("y1", att.output.dense), ("ln1", att.output.LayerNorm))
+        for key, mod in mods + (("h", layer.intermediate), ("y2", layer.output.dense), ("ln2", layer.output.LayerNorm)):
             hooks.append(mod.register_forward_hook(grab(li, key)))
     embs = []
     with torch.no_grad():
@@ -140,25 +144,27 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
-    from kirag_amd.retriever.encoders import ROBERTA_TYPES
-    if getattr(cfg, "model_type", "bert") not in ("bert",) + ROBERTA_TYPES:
-        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge) and the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3)")
+    from kirag_amd.retriever.encoders import MPNET_TYPE, ROBERTA_TYPES
+    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE) + ROBERTA_TYPES:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3) and MPNet (all-mpnet-base-v2)")
     model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
     return check_model(model, args, hf_dir)
 
 
 def check_model(model, args, hf_dir="(in-memory model)"):
     """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
-    from kirag_amd.retriever.encoders import ROBERTA_TYPES
+    from kirag_amd.retriever.encoders import MPNET_PADDING_IDX, MPNET_TYPE, ROBERTA_TYPES
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
-    roberta = getattr(cfg, "model_type", "bert") in ROBERTA_TYPES
+    mpnet = getattr(cfg, "model_type", "bert") == MPNET_TYPE
+    roberta = mpnet or getattr(cfg, "model_type", "bert") in ROBERTA_TYPES
     if roberta and not use_hip:
-        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} follows fairseq's position rule, which the torch emulation does not implement: run on the GPU")
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} follows fairseq's position rule" + (" and adds a relative attention bias" if mpnet else "") +
+                         ", which the torch emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
-    batches = load_inputs(args, hf_dir, cfg.vocab_size, cfg.pad_token_id if roberta else None)
+    batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)
     ref, table = reference_and_stats(model, batches, args.pool, dev)
     print(f"# {hf_dir}: {cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}; {sum(len(b[0]) for b in batches)} sequences, pooling {args.pool}; "
           f"tested path: {'HIP encoder (libkirag_amd)' if use_hip else 'torch emulation of the rounding points'}")

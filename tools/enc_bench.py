@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3 ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|mpnet-base|mpnet-base-nobias ...] [--pool mean|cls] [--hf-fp16]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -19,7 +19,12 @@ PEAK_MFMA_DENSE_16BIT = 2.5e15   # MI355X_MICROARCH.md: bf16/f16 dense MFMA peak
 XLMR_LARGE = dict(BS.E5_LARGE, vocab_size=250002, max_position_embeddings=514, type_vocab_size=1, layer_norm_eps=1e-5, model_type="xlm-roberta", pad_token_id=1)
 XLMR_BASE = dict(XLMR_LARGE, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072)
 BGE_M3 = dict(XLMR_LARGE, max_position_embeddings=8194)
-SHAPES = dict(BS.ENCODER_SHAPES, **{"xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3})
+# MPNet (all-mpnet-base-v2): the xlmr-base stack at vocab 30527 + the relative attention bias inside the attention kernels; mpnet-base-nobias is the same
+# shape as a RoBERTa handle (identical GEMMs, attention without the bias): what the bias costs is the difference of the two
+MPNET_BASE = dict(XLMR_BASE, vocab_size=30527, model_type="mpnet", relative_attention_num_buckets=32)
+MPNET_BASE_NOBIAS = dict(XLMR_BASE, vocab_size=30527)
+SHAPES = dict(BS.ENCODER_SHAPES, **{"xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+                                    "mpnet-base-nobias": MPNET_BASE_NOBIAS})
 
 ap = argparse.ArgumentParser()
 ap.add_argument("n", type=int, nargs="?", default=1024)
@@ -50,9 +55,27 @@ def hf_classes(cfg):
     """(config class, model class, sentence-encoder module) of a shape: the RoBERTa family by its model_type"""
     import transformers as T
     from kirag_amd.retriever import encoders as ENC
+    if cfg.get("model_type") == ENC.MPNET_TYPE:
+        return T.MPNetConfig, T.MPNetModel, (ENC.MPNetE5Encoder if args.pool == "mean" else ENC.MPNetBGEEncoder)
     if cfg.get("model_type") in ENC.ROBERTA_TYPES:
         return T.XLMRobertaConfig, T.XLMRobertaModel, (ENC.XLMRobertaE5Encoder if args.pool == "mean" else ENC.XLMRobertaBGEEncoder)
     return T.BertConfig, T.BertModel, (ENC.E5Encoder if args.pool == "mean" else ENC.BGEEncoder)
+
+
+def make_encoder(cfg):
+    """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize)"""
+    if cfg.get("model_type") != "mpnet":
+        return BS.make_hip_encoder(dev, cfg)
+    from types import SimpleNamespace
+    from kirag_amd.retriever.encoders import HipBertForward
+    ns = SimpleNamespace(**cfg)
+    enc = HipBertForward(ns, 0)
+    state = dict(BS.synthetic_state(ns, dev, 0))
+    g = torch.Generator(device=dev); g.manual_seed(977)
+    state["encoder.relative_attention_bias.weight"] = torch.randn(32, cfg["num_attention_heads"], generator=g, device=dev)
+    enc.load_state(state)
+    enc.cfg = ns
+    return enc
 
 
 def first_forward(shape, cfg, ids, mask):
@@ -82,7 +105,7 @@ for shape in args.shape or ["e5-large"]:
         first_forward(shape, cfg, ids, mask)
         torch.cuda.empty_cache()
         continue
-    enc = BS.make_hip_encoder(dev, cfg)
+    enc = make_encoder(cfg)
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
