@@ -1,0 +1,267 @@
+// Sentence encoder, device code of the projections (ProjArgs, the epilogues, k_proj*).  Part of encoder.hip (see its header).
+#pragma once
+#include "encoder_rows.hpp"
+
+namespace kr {
+namespace KR_ENC_NS {
+
+using ShapeBig = GemmShape<256, 256, 2, 4>;     // 8 waves of 128x64, 128 KiB LDS, one block per CU: best main loop (long-K GEMMs)
+// Four main loops, one per launch size (launch_proj picks; all give bit-identical rows):
+//   256x256 ping-pong (gemm_nt_pingpong)          launches with >= 5/8 of the CUs' worth of 256x256 tiles
+//   128x128 producer / consumer (gemm_nt_split)   fewer: at most one tile per CU, or more than two
+//   128x128 streaming, 2 slots, 2 blocks per CU   in between (k_proj<.., ShapeSmall, 2>)
+//   32x32 / 64x64 skinny (gemm_nt_skinny)         a handful of token rows (<= 4 tiles of 32x32 per CU)
+
+using ShapeSmall = GemmShape<128, 128, 2, 2>;   // 4 waves of 64x64, 64 KiB ring, two blocks per CU: for launches with too few 256x256 tiles to fill the chip
+
+// all main loops run with exchanged MFMA operands (accumulators hold 4 consecutive features per lane)
+template <class ShapeE, int STAGES, bool ANT = false, class Coord, class Epilogue>
+__device__ __forceinline__ void gemm_main(const uint16_t* __restrict__ A, int64_t lda, int64_t M, const uint16_t* __restrict__ B, int64_t ldb, int64_t N,
+                                          int K, int64_t total_tiles, char* smem, Coord&& coord, Epilogue&& epi) {
+    if constexpr (ShapeE::BM == 256 && ShapeE::BN == 256) gemm_nt_pingpong<ET, true, ANT>(A, lda, M, B, ldb, N, K, total_tiles, smem, coord, epi);
+    else gemm_nt_stream<ET, ShapeE, STAGES, true>(A, lda, M, B, ldb, N, K, total_tiles, smem, coord, epi);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// projections: C[token, feature] = X[token, :] . W[feature, :]   (rows = tokens, cols = output features)
+// ---------------------------------------------------------------------------------------------------------
+struct ProjArgs {
+    const uint16_t* W; const uint16_t* X; const int* Tp; int F; int K; int H;
+    const float* bias;
+    uint16_t* out0; uint16_t* out1; uint16_t* outT; int64_t ldT;   // QKV: q, k row-major [T,H]; vT [H, ldT].  Others: out0 [T, F]
+    int64_t ldx, ldo;   // row pitch (elements) of X and of out0 (EPI_DENSE / EPI_GELU); 0 = K / F
+    int pw;   // feature tiles per XCD patch of the tile walk (patch_coord)
+    int epi_prio;   // A/B knob, see proj_epilogue
+    int ant;  // activation loads non-temporal (FF2's h: launch_proj)
+    int nt;   // epilogue stores non-temporal (large launches: the output is consumed from HBM by the next kernel, keep it out of L2) or plain
+              // (small launches: the whole output fits in L2 / Infinity Cache, the next kernel reads it from there)
+};
+
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2 };
+
+// erf-GELU x Phi(x) = max(x, 0) - 0.5 |x| erfc(|x| / sqrt 2), with erfc(a / sqrt 2) = 2^-Q(a), Q(a) = a (c1 + c2 a + c3 a^2 + c4 a^3 + c5 a^4) a weighted
+// minimax fit of -log2 erfc on [0, 8] (weight a erfc(a / sqrt 2) = the sensitivity of the result; fitted offline, c5 > 0 so Q keeps growing and the
+// tail underflows to the exact limit max(x, 0)).  |error| <= 9.4e-7 absolute on the whole line in fp32 arithmetic (the result is rounded to bf16:
+// 2^-9 relative), no sign handling, and ONE quarter-rate transcendental (v_exp_f32) per element instead of two: 13 VALU instructions per element
+// pair (76 issue cycles) against 22 (136) for the Abramowitz-Stegun 7.1.26 form used before, in an epilogue that nothing overlaps with (the GELU
+// was 1557 VALU instructions per wave and 256x256 tile, with both waves of a SIMD in it at the same time).
+// two elements at once: the polynomial / products run as packed fp32 (v_pk_fma_f32 / v_pk_mul_f32), only exp2 / abs / max stay scalar
+__device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
+    const f32x2 ax = {fabsf(x.x), fabsf(x.y)};
+    f32x2 q = __builtin_elementwise_fma(ax, f32x2{4.881049150e-04f, 4.881049150e-04f}, f32x2{-7.198719129e-03f, -7.198719129e-03f});
+    q = __builtin_elementwise_fma(q, ax, f32x2{5.214659068e-02f, 5.214659068e-02f});
+    q = __builtin_elementwise_fma(q, ax, f32x2{4.595959239e-01f, 4.595959239e-01f});
+    q = __builtin_elementwise_fma(q, ax, f32x2{1.151000505e+00f, 1.151000505e+00f});
+    q = q * ax;
+    const f32x2 e = {__builtin_amdgcn_exp2f(-q.x), __builtin_amdgcn_exp2f(-q.y)};
+    const f32x2 r = {fmaxf(x.x, 0.f), fmaxf(x.y, 0.f)};
+    return __builtin_elementwise_fma(ax * e, f32x2{-0.5f, -0.5f}, r);
+}
+
+// A 32x32 MFMA accumulator has its COLUMN on the lane, so a direct store writes 2-byte elements (128 store instructions per lane per
+// 256x256 tile, the epilogue then costs as much as a third of the main loop).  Instead every wave owns a private 4-KiB LDS stage
+// behind the ring (no barrier: only this wave touches it, LDS operations of one wave complete in order):
+//   rows:  the wave's 32 x 64 block (one mi, both ni) is written as bf16 [32 rows][128 B] and read back 16 B per lane, so each global
+//          store instruction writes eight whole 128-B lines of the output;
+//   V^T:   each 32x32 tile is written TRANSPOSED ([feature][token], 4 consecutive tokens of a lane packed into 8 B, 80-B rows) and
+//          read back 16 B per lane: a store instruction writes 64-B runs of sixteen V^T rows.
+constexpr int EPI_STAGE_BYTES = 4096;
+
+// Both helpers take the SWAPPED accumulator layout of gemm_nt_pingpong / gemm_nt_split / gemm_nt_stream / gemm_nt_skinny with SWAP = true: tile (mi, ni), register r,
+// lane (c = l & 31, h = l >> 5) is token mi*32 + c, feature ni*32 + (r & 3) + 8 (r >> 2) + 4 h of the wave's (TM*32 tokens) x (TN*32 features).
+//
+// rows: for one mi the wave's 32 tokens x 64 features are staged as bf16 [32 tokens][128 B]; registers 4g .. 4g+3 of a lane are 4
+// consecutive features -> one packed ds_write_b64 (16-B chunk index XOR (token & 7): 2-way instead of 16-way conflicts), read back 16 B
+// per lane: every global store instruction writes eight whole 128-B rows.  f(v, mi, ni, g) maps 4 features (bias / GELU / row scale) before packing.
+template <class Shape, bool NT, class F>
+__device__ __forceinline__ void store_rows_bf16(AccTile<Shape>& acc, char* stage, uint16_t* __restrict__ out, int64_t ld, int64_t row0, int col0, F&& f) {
+    static_assert(Shape::TN == 2, "stage geometry assumes 64 features per wave");
+    const int c = acc.lane & 31, h = acc.lane >> 5;
+    const int r8 = acc.lane >> 3, ch = acc.lane & 7;
+    const char* st_rd = stage + r8 * 128 + ((ch ^ r8) << 4);
+    uint16_t* g_base = out + (row0 + r8) * ld + col0 + ch * 8;
+    // software pipeline over the mi blocks: write(mi), read(mi), THEN the global stores of mi-1 — LDS operations of one wave complete in order, so
+    // the single 4-KiB stage is safe to overwrite right after the reads were issued, and the stores of block mi-1 only wait for their own reads
+    // (counted lgkmcnt) while the LDS round trip of block mi is in flight (one exposed round trip per tile instead of one per block)
+    uint4 d[2][4];
+#pragma unroll
+    for (int mi = 0; mi <= Shape::TM; ++mi) {
+        if (mi < Shape::TM) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 v = f(f32x4{acc.v[mi][ni][4 * g], acc.v[mi][ni][4 * g + 1], acc.v[mi][ni][4 * g + 2], acc.v[mi][ni][4 * g + 3]}, mi, ni, g);
+                    uint2 w;
+                    w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
+                    *reinterpret_cast<uint2*>(stage + c * 128 + (((ni * 4 + g) ^ (c & 7)) << 4) + h * 8) = w;
+                }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) d[mi & 1][p] = *reinterpret_cast<const uint4*>(st_rd + p * 8 * 128);
+        }
+        if (mi > 0) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {  // rl & 7 == lane >> 3 for every p: one lane-dependent LDS / global base, the rest are wave-uniform steps (8 rows per store)
+                u32x4_t* dst = reinterpret_cast<u32x4_t*>(g_base + (int64_t)((mi - 1) * 32 + p * 8) * ld);
+                if constexpr (NT) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, d[(mi - 1) & 1][p]), dst);
+                else *dst = __builtin_bit_cast(u32x4_t, d[(mi - 1) & 1][p]);
+            }
+        }
+    }
+}
+
+// V^T[feature, token]: each 32x32 tile is staged as [32 features][32 tokens] (80-B rows), lanes = consecutive tokens of a feature row,
+// read back 16 B per lane: a store instruction writes 64-B runs of sixteen V^T rows.
+template <class Shape, bool NT>
+__device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char* stage, uint16_t* __restrict__ outT, int64_t ldT, int64_t t0, int f0) {
+    // the lane id is made opaque HERE: everything below that depends on it (LDS offsets, the 64-bit V^T addresses) is then recomputed per tile (a few VALU
+    // instructions) instead of being hoisted out of the persistent tile loop into registers the main loop has no room for — hipcc spilled them, and the
+    // scratch reloads (VMEM, followed by s_waitcnt vmcnt(0)) drained the LDS-DMA ring in every V^T tile (tests/test_capi_and_host.py: no spills allowed)
+    int ln = acc.lane;
+    asm volatile("" : "+v"(ln));
+    const int c = ln & 31, h = ln >> 5;
+#pragma unroll
+    for (int mi = 0; mi < Shape::TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < Shape::TN; ++ni) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                *reinterpret_cast<uint16_t*>(stage + ((r & 3) + 8 * (r >> 2) + 4 * h) * 80 + c * 2) = ET::from_f32(acc.v[mi][ni][r]);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int fl = p * 16 + (ln >> 2), ch = ln & 3;
+                const uint4 d = *reinterpret_cast<const uint4*>(stage + fl * 80 + ch * 16);
+                u32x4_t* dst = reinterpret_cast<u32x4_t*>(outT + (int64_t)(f0 + ni * 32 + fl) * ldT + t0 + mi * 32 + ch * 8);
+                if constexpr (NT) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, d), dst);
+                else *dst = __builtin_bit_cast(u32x4_t, d);
+            }
+        }
+}
+
+// persistent streaming projections (256x256 ping-pong or 128x128 streaming main loop).  rows = tokens, cols = output features; bias is
+// one value per lane and ni.  Token-indexed buffers are allocated in multiples of 256 rows, so a partial last token tile needs no bounds
+// test (rows >= T are written with values computed from clamped loads and never read).
+// Tiles are walked in patches of (token tiles x 8 feature tiles) per XCD so operand slices are reused from that XCD's L2.
+//   EPI_QKV:   F = 3H: features [0,H) -> q (bias, log2(e) / sqrt(d_h) folded into the weights), [H,2H) -> k, [2H,3H) -> V^T (its bias lives in bo_eff)
+//   EPI_DENSE: out0[T,F] = acc as bf16 (k_ln adds the bias and the residual in fp32)
+//   EPI_GELU:  out0[T,F] = gelu(acc + bias)
+template <int EPI, class ShapeE, bool NT>
+__device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>& acc, int64_t m0, int64_t n0, char* stage) {
+    const int64_t t0 = m0 + acc.m_wave;
+    const int f0 = (int)n0 + acc.n_wave;          // first feature of this wave's 64 columns; F % 64 == 0, so a wave is never partial
+    if (f0 >= a.F) return;
+    // A/B knob (KIRAG_AMD_EPI_PRIO, profiles/r03/tried_ab_epi_prio.txt): the two wave groups of the ping-pong loop run their epilogues side by side and the
+    // younger group (tile rows 128 ..) loses the issue arbitration (its epilogue takes ~2x as long): 1 = that group at priority 1, 2 = the older group
+    if (a.epi_prio && ((a.epi_prio == 1) == (acc.m_wave >= 128))) __builtin_amdgcn_s_setprio(1);
+    const int h = acc.lane >> 5;
+    f32x4 b[2][4];                                // bias of the lane's 32 features: (ni, g) -> features ni*32 + 8g + 4h .. +3
+    if constexpr (EPI != EPI_DENSE) {
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) b[ni][g] = *reinterpret_cast<const f32x4*>(a.bias + f0 + ni * 32 + 8 * g + 4 * h);
+    }
+    if constexpr (EPI == EPI_QKV) {
+        const int region = f0 / a.H;              // H % 64 == 0: a wave's columns never straddle q | k | v
+        if (region == 2) {
+            store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - 2 * a.H);   // value bias lives in bo_eff
+        } else {
+            store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H,
+                                    [&](f32x4 v, int mi, int ni, int g) { return v + b[ni][g]; });
+        }
+    } else if constexpr (EPI == EPI_DENSE) {
+        store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int, int, int) { return v; });   // the bias is added in k_ln (fp32)
+    } else {
+        store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int mi, int ni, int g) {
+            const f32x4 x = v + b[ni][g];
+            const f32x2 lo = gelu_erf_fast2(f32x2{x.x, x.y}), hi = gelu_erf_fast2(f32x2{x.z, x.w});
+            return f32x4{lo.x, lo.y, hi.x, hi.y};
+        });
+    }
+    if (a.epi_prio) __builtin_amdgcn_s_setprio(0);
+}
+
+// ANT: the activation operand is loaded non-temporally (FF2's h: launch_proj)
+template <int EPI, class ShapeE, int STAGES, bool NT, bool ANT = false>
+__global__ __launch_bounds__(ShapeE::NTHREADS, 2) void k_proj(ProjArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int T = *a.Tp;
+    const int64_t tm_count = (T + ShapeE::BM - 1) / ShapeE::BM, tn_count = (a.F + ShapeE::BN - 1) / ShapeE::BN;
+    char* stage = smem + STAGES * ShapeE::STAGE_BYTES + (threadIdx.x >> 6) * EPI_STAGE_BYTES;
+    auto coord = [&](int64_t nat, int64_t& m0, int64_t& n0) {
+        int64_t tm, tn;
+        patch_coord(nat, tm_count, tn_count, tm, tn, (uint32_t)a.pw);
+        m0 = tm * ShapeE::BM; n0 = tn * ShapeE::BN;
+    };
+    gemm_main<ShapeE, STAGES, ANT>(a.X, a.ldx, T, a.W, a.K, a.F, a.K, tm_count * tn_count, smem, coord,
+                                   [&](AccTile<ShapeE>& acc, int64_t m0, int64_t n0, int64_t) { proj_epilogue<EPI, ShapeE, NT>(a, acc, m0, n0, stage); });
+}
+
+// the same projections on the producer / consumer 128x128 loop (gemm_nt_split): 4 multiplying + 4 staging waves, 4-slot ring + one 4-KiB epilogue
+// stage per multiplying wave = 144 KiB, one persistent block per CU
+template <int EPI>
+__global__ __launch_bounds__(SPLIT_THREADS) void k_proj_split(ProjArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int T = *a.Tp;
+    const int64_t tm_count = (T + 127) / 128, tn_count = (a.F + 127) / 128;
+    char* stage = smem + SPLIT_RING * ShapeSplit::STAGE_BYTES + ((threadIdx.x >> 6) & 3) * EPI_STAGE_BYTES;
+    gemm_nt_split<ET, true>(
+        a.X, a.ldx, T, a.W, a.K, a.F, a.K, tm_count * tn_count, smem,
+        [&](int64_t nat, int64_t& m0, int64_t& n0) {
+            int64_t tm, tn;
+            patch_coord(nat, tm_count, tn_count, tm, tn, (uint32_t)a.pw);
+            m0 = tm * 128; n0 = tn * 128;
+        },
+        [&](AccTile<ShapeSplit>& acc, int64_t m0, int64_t n0, int64_t) { proj_epilogue<EPI, ShapeSplit, false>(a, acc, m0, n0, stage); });
+}
+
+// the same projections for a handful of token rows on the skinny loop (gemm_nt_skinny): one (32 WM)-token x (32 WN)-feature tile per block,
+// grid = (F / (32 WN), T / (32 WM)).  Epilogue straight from the accumulator (swapped layout: a lane holds 4 consecutive features of one token per register
+// quad): 8-byte row stores, 2-byte stores for V^T — at these sizes the stores are noise next to the operand stream.
+// (Round 5 built the LayerNorm behind a dense projection as the TAIL of this launch — write-through y, an arrival counter per token tile, the last
+// arriver normalises the tile's rows — bit-identical and SLOWER: the one block that finds itself last works through 32 rows alone, 26.8 us per launch
+// against 9.2 + 5.3 for the two launches; profiles/r05/tried_ln_tail.txt.)
+template <int EPI, int RING, int WM = 1, int WN = 1>
+__global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t m0 = (int64_t)blockIdx.y * (32 * WM), n0 = (int64_t)blockIdx.x * (32 * WN);
+    f32x4 bias4[4];                                       // multiplying waves: the bias of the lane's 16 features, requested before the main loop
+    gemm_nt_skinny<ET, RING, WM, WN, true>(a.X, a.ldx, a.Tp, m0, a.W, a.K, a.F, n0, a.K, smem,
+        [&](int64_t, int64_t f0) {
+            if constexpr (EPI != EPI_DENSE) {
+                const int h = (threadIdx.x & 63) >> 5;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) bias4[g] = *reinterpret_cast<const f32x4*>(a.bias + f0 + 8 * g + 4 * h);   // QKV: the V third's slots are never used
+            }
+        },
+        [&](AccTile<ShapeSkinny>& acc, int64_t t0, int64_t f0) {
+        const int c = acc.lane & 31, h = acc.lane >> 5;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 v = {acc.v[0][0][4 * g], acc.v[0][0][4 * g + 1], acc.v[0][0][4 * g + 2], acc.v[0][0][4 * g + 3]};
+            const int f = (int)f0 + 8 * g + 4 * h;        // first of the lane's 4 consecutive features
+            if constexpr (EPI == EPI_QKV) {
+                const int region = (int)f0 / a.H;
+                if (region == 2) {                        // V^T [feature, token]; its bias lives in bo_eff
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) a.outT[(int64_t)(f - 2 * a.H + j) * a.ldT + t0 + c] = ET::from_f32(v[j]);
+                    continue;
+                }
+                v = v + bias4[g];
+                uint2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
+                *reinterpret_cast<uint2*>((region ? a.out1 : a.out0) + (t0 + c) * a.H + (f - region * a.H)) = w;
+            } else {
+                if constexpr (EPI == EPI_GELU) {
+                    v = v + bias4[g];
+                    const f32x2 lo = gelu_erf_fast2(f32x2{v.x, v.y}), hi = gelu_erf_fast2(f32x2{v.z, v.w});
+                    v = f32x4{lo.x, lo.y, hi.x, hi.y};
+                }
+                uint2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
+                *reinterpret_cast<uint2*>(a.out0 + (t0 + c) * a.ldo + f) = w;
+            }
+        }
+    });
+}
+
+}  // namespace KR_ENC_NS
+}  // namespace kr

@@ -1,0 +1,399 @@
+// Sentence encoder, device code over token rows: weight conversion, the residual stream's byte codec, embedding + LayerNorm, LayerNorm, pooling and the
+// CLS gather.  Part of encoder.hip (see its header); defines the namespace of the build's operand type and ET for the other encoder_*.hpp.
+#pragma once
+#include "gemm_nt.hpp"
+
+// This file is compiled TWICE (kirag_amd/csrc/Makefile): once per 16-bit operand type of the MFMAs and of every stored activation —
+//   bf16 (8 significand bits, fp32 range)  and  f16 (11 significand bits, |x| <= 65504; -DKR_ENC_F16)
+// — into the namespaces kr::enc_bf16 / kr::enc_f16; encoder_api.hip holds the C entry points and picks one per handle (kr_encoder_create_ex).
+// Why both exist: DESIGN.md section 4.2 "operand precision" (weights with outlier channels need the 11 bits to stay within the 1e-3 score tolerance).
+#ifdef KR_ENC_BUILD_F16
+#define KR_ENC_NS enc_f16
+#else
+#define KR_ENC_NS enc_bf16
+#endif
+
+namespace kr {
+namespace KR_ENC_NS {
+
+#ifdef KR_ENC_BUILD_F16
+using ET = F16;
+#else
+using ET = BF16;
+#endif
+
+// ---------------------------------------------------------------------------------------------------------
+// small kernels
+// ---------------------------------------------------------------------------------------------------------
+__global__ void k_f32_to_bf16(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n, float scale) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = ET::from_f32(src[i] * scale);
+}
+__global__ void k_scale_copy(const float* __restrict__ src, float* __restrict__ dst, int64_t n, float scale) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i] * scale;
+}
+
+// b_o' = b_o + W_o . b_v : softmax rows sum to 1, so P (X W_v^T + b_v) = P X W_v^T + b_v and the value bias moves into the output projection
+__global__ void k_fold_vbias(const uint16_t* __restrict__ wo, const float* __restrict__ bo, const float* __restrict__ bv, float* __restrict__ out, int H) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H) return;
+    float s = 0.f;
+    for (int j = 0; j < H; ++j) s += ET::to_f32(wo[(int64_t)i * H + j]) * bv[j];
+    out[i] = bo[i] + s;
+}
+
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+// two floats -> packed 16-bit pair (lo in bits 0..15), round-to-nearest-even, NaN stays NaN: ONE v_cvt_pk_bf16_f32 / the f16 conversions of the target
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+#ifdef KR_ENC_BUILD_F16
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, f16x2_t));
+#else
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2_t));
+#endif
+}
+// the two halves of a packed pair as fp32
+__device__ __forceinline__ float unpack_lo16(unsigned int w) {
+#ifdef KR_ENC_BUILD_F16
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
+#else
+    return __builtin_bit_cast(float, w << 16);
+#endif
+}
+__device__ __forceinline__ float unpack_hi16(unsigned int w) {
+#ifdef KR_ENC_BUILD_F16
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+#else
+    return __builtin_bit_cast(float, w & 0xffff0000u);
+#endif
+}
+
+// Low half of the residual stream: x = hi + lo with hi = the 16-bit operand the GEMMs read (round-to-nearest of x) and lo = ONE byte: the distance from hi to
+// x in units of ulp(hi) / 256, biased by 128 (19 significand bits with f16 operands, 16 with bf16).  Round 2 kept lo as a second 16-bit word (10 B per
+// element through a LayerNorm instead of 6); the byte makes it 8 B — on the emulation of the rounding points (tools/precision_probe.py, G10 out3 / out16) the
+// worst score error is unchanged (9.1e-5 vs 8.6e-5 / 1.2e-3 vs 9.5e-4).
+// The byte is computed ON THE BIT PATTERNS (round 4): x and hi have the same sign and neighbouring magnitudes, so bits(x) - bits(hi) (both as fp32) is their
+// distance in fp32 ulps, signed towards larger magnitude, and 2^LO_SH of those are ulp(hi) / 256 (a unit half as large when hi rounded up into the next
+// binade: still within +-128).  Encode = subtract, add the rounding constant, shift, clamp (4 integer instructions); decode = shift-add + constant (3, the
+// byte extraction included) — a third of the floating-point form (exponent extraction, two constructed powers of two, rint, min, max, conversions) that made
+// round 4's fused residual epilogue VALU-bound (profiles/r04/tried_fused_layernorm.txt).  |x| < 2^-25 (hi = +-0) clamps to a denormal: an absolute error below 2^-25.
+#ifdef KR_ENC_BUILD_F16
+constexpr int LO_SH = 5;        // 23 - 10 stored mantissa bits - 8
+#else
+constexpr int LO_SH = 8;        // 23 - 7 - 8
+#endif
+__device__ __forceinline__ unsigned int lo_encode(float o, float hf) {
+    const int d = (int)(__builtin_bit_cast(unsigned int, o) - __builtin_bit_cast(unsigned int, hf));
+    // round to nearest, biased by 128; clamped BEFORE the shift.  (Shift-then-clamp of two neighbours is selected to v_ashr_pk_u8_i32, which on gfx950 writes only
+    // bits 15:0 of its destination — the compiler assumes the upper half is zero and ORs the stale bits into the neighbouring bytes: tools/ashr_pk_check.hip)
+    const int t = min(max(d + ((1 << (LO_SH - 1)) + (128 << LO_SH)), 0), (256 << LO_SH) - 1);
+    return (unsigned int)t >> LO_SH;
+}
+__device__ __forceinline__ float lo_decode(unsigned int byte, float hf) {
+    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned int, hf) + (byte << LO_SH) - (128u << LO_SH));
+}
+// lo_decode for readers of the FINAL hidden state (pooling, kr_encoder_last_hidden): a non-finite hi (a LayerNorm output beyond the f16 range, or NaN) decodes
+// to ITSELF — on the bit patterns inf - 4096 would be a finite 3.4e38.  Inside the stack the overflow travels with the 16-bit stream itself (the next GEMM reads
+// hi = inf and every LayerNorm behind it sees NaN through y), so the LayerNorm's residual decode keeps the 3-instruction form (its two extra VALU instructions per
+// element cost 0.3 % of the 1000-query step); behind the LAST LayerNorm there is no GEMM, only this decode (tests/test_lo_codec_spec.py,
+// tests/test_gpu_lifecycle.py: an overflow in the last LayerNorm must raise KR_ERANGE).
+__device__ __forceinline__ float lo_decode_final(unsigned int byte, float hf) {
+    const unsigned int hb = __builtin_bit_cast(unsigned int, hf);
+    return (hb & 0x7f800000u) == 0x7f800000u ? hf : lo_decode(byte, hf);
+}
+
+// LayerNorm of one row held as up to 8 float4 per lane (H <= 2048); writes fp32 and bf16 copies
+__device__ __forceinline__ void ln_row_store(float4 (&v)[8], int H, int lane, const float* __restrict__ g, const float* __restrict__ bta, float eps,
+                                             uint8_t* __restrict__ xlo_row, uint16_t* __restrict__ xb_row) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) if (lane * 4 + j * 256 < H) s += v[j].x + v[j].y + v[j].z + v[j].w;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    const float mu = s / (float)H;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (lane * 4 + j * 256 < H) {
+            const float a = v[j].x - mu, b = v[j].y - mu, c = v[j].z - mu, d = v[j].w - mu;
+            q += a * a + b * b + c * c + d * d;
+        }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
+    const float rstd = 1.0f / sqrtf(q / (float)H + eps);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = lane * 4 + j * 256;
+        if (i < H) {
+            const float4 gg = *reinterpret_cast<const float4*>(g + i);
+            const float4 bb = *reinterpret_cast<const float4*>(bta + i);
+            float4 o;
+            o.x = (v[j].x - mu) * rstd * gg.x + bb.x; o.y = (v[j].y - mu) * rstd * gg.y + bb.y;
+            o.z = (v[j].z - mu) * rstd * gg.z + bb.z; o.w = (v[j].w - mu) * rstd * gg.w + bb.w;
+            ushort4 ob;
+            ob.x = ET::from_f32(o.x); ob.y = ET::from_f32(o.y); ob.z = ET::from_f32(o.z); ob.w = ET::from_f32(o.w);
+            *reinterpret_cast<ushort4*>(xb_row + i) = ob;
+            if (xlo_row)                                                      // optional low half (kernel-uniform branch): one byte per element
+                *reinterpret_cast<unsigned int*>(xlo_row + i) = lo_encode(o.x, ET::to_f32(ob.x)) | (lo_encode(o.y, ET::to_f32(ob.y)) << 8) |
+                                                                (lo_encode(o.z, ET::to_f32(ob.z)) << 16) | (lo_encode(o.w, ET::to_f32(ob.w)) << 24);
+        }
+    }
+}
+
+// embeddings: word[id] + position[pos] + token_type[0] -> LayerNorm       (one wave per token; tok_pos = the handle's embedding-position table: the column
+// under BERT's rule, tok_epos under fairseq's)
+__global__ __launch_bounds__(256) void k_embed_ln(const int* __restrict__ tok_id, const int* __restrict__ tok_pos, const int* __restrict__ tok_type, const int* __restrict__ Tp,
+                                                  const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type,
+                                                  const float* __restrict__ g, const float* __restrict__ bta, float eps, int H,
+                                                  uint8_t* __restrict__ xlo, uint16_t* __restrict__ xb) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= *Tp) return;
+    const float* w = word + (int64_t)tok_id[t] * H;
+    const float* p = pos + (int64_t)tok_pos[t] * H;
+    const float* ty = type + (int64_t)tok_type[t] * H;       // token_type_embeddings row (0 for every KiRAG caller)
+    float4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = lane * 4 + j * 256;
+        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < H) {
+            const float4 a = *reinterpret_cast<const float4*>(w + i);
+            const float4 b = *reinterpret_cast<const float4*>(p + i);
+            const float4 c = *reinterpret_cast<const float4*>(ty + i);
+            v[j] = make_float4((a.x + b.x) + c.x, (a.y + b.y) + c.y, (a.z + b.z) + c.z, (a.w + b.w) + c.w);
+        }
+    }
+    ln_row_store(v, H, lane, g, bta, eps, xlo ? xlo + t * H : nullptr, xb + t * H);
+}
+
+// LayerNorm(y + bias + residual) with 16-byte accesses: a lane owns 8 consecutive elements per 512-element step (one global_load_dwordx4 per tensor and step:
+// 8-byte accesses reach 0.54-0.70 of the 16-byte rate, MI355X_MICROARCH.md).  NS 512-element steps cover a row (H <= 512 NS, H % 8 == 0).
+// The row arithmetic lives in Ln16<NS> (one definition for every kernel that normalises a row).
+template <int NS>
+struct Ln16 {
+    float gg[NS][8], bb[NS][8], yb[NS][8];     // gamma, beta, the projection's bias (added in fp32) of the lane's elements
+    __device__ __forceinline__ void load_params(const float* __restrict__ g, const float* __restrict__ bta, const float* __restrict__ ybias, int H, int lane) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) { gg[j][c] = 0.f; bb[j][c] = 0.f; yb[j][c] = 0.f; }
+            if (i < H) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float4 a = *reinterpret_cast<const float4*>(g + i + 4 * h), b = *reinterpret_cast<const float4*>(bta + i + 4 * h), c = *reinterpret_cast<const float4*>(ybias + i + 4 * h);
+                    gg[j][4 * h] = a.x; gg[j][4 * h + 1] = a.y; gg[j][4 * h + 2] = a.z; gg[j][4 * h + 3] = a.w;
+                    bb[j][4 * h] = b.x; bb[j][4 * h + 1] = b.y; bb[j][4 * h + 2] = b.z; bb[j][4 * h + 3] = b.w;
+                    yb[j][4 * h] = c.x; yb[j][4 * h + 1] = c.y; yb[j][4 * h + 2] = c.z; yb[j][4 * h + 3] = c.w;
+                }
+            }
+        }
+    }
+    // v = (y + bias) + residual, the residual decoded from its 16-bit half and its low-half byte
+    __device__ __forceinline__ void combine(const uint4 (&a)[NS], const uint4 (&rh)[NS], const uint2 (&rl)[NS], float (&v)[NS][8]) const {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const unsigned int aw[4] = {a[j].x, a[j].y, a[j].z, a[j].w}, hw[4] = {rh[j].x, rh[j].y, rh[j].z, rh[j].w}, lw[2] = {rl[j].x, rl[j].y};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {   // elements 2c, 2c + 1: low-half bytes 2c, 2c + 1 of the 8
+                v[j][2 * c] = (unpack_lo16(aw[c]) + yb[j][2 * c]) + lo_decode((lw[c >> 1] >> (16 * (c & 1))) & 0xffu, unpack_lo16(hw[c]));
+                v[j][2 * c + 1] = (unpack_hi16(aw[c]) + yb[j][2 * c + 1]) + lo_decode((lw[c >> 1] >> (16 * (c & 1) + 8)) & 0xffu, unpack_hi16(hw[c]));
+            }
+        }
+    }
+    // mean / variance over the wave, normalise, store the 16-bit row and (xlo_row != nullptr) its low-half bytes.  NTS: the low half stored non-temporally
+    template <bool NTS>
+    __device__ __forceinline__ void normalize_store(const float (&v)[NS][8], int H, float eps, int lane, uint16_t* xb_row, uint8_t* xlo_row) const {
+        typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            if (lane * 8 + j * 512 < H)
+#pragma unroll
+                for (int c = 0; c < 8; ++c) s += v[j][c];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+        const float mu = s / (float)H;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            if (lane * 8 + j * 512 < H)
+#pragma unroll
+                for (int c = 0; c < 8; ++c) { const float dlt = v[j][c] - mu; q += dlt * dlt; }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
+        const float rstd = 1.0f / sqrtf(q / (float)H + eps);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+            if (i < H) {
+                float o[8];
+                unsigned int ob[4], ol[4];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) o[c] = (v[j][c] - mu) * rstd * gg[j][c] + bb[j][c];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) ob[c] = pack_bf16x2(o[2 * c], o[2 * c + 1]);
+                *reinterpret_cast<uint4*>(xb_row + i) = make_uint4(ob[0], ob[1], ob[2], ob[3]);
+                if (xlo_row) {   // optional low half: one byte per element (lo_encode)
+                    ol[0] = ol[1] = 0u;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        ol[c >> 1] |= (lo_encode(o[2 * c], unpack_lo16(ob[c])) | (lo_encode(o[2 * c + 1], unpack_hi16(ob[c])) << 8)) << (16 * (c & 1));
+                    if constexpr (NTS) __builtin_nontemporal_store(u32x2_t{ol[0], ol[1]}, reinterpret_cast<u32x2_t*>(xlo_row + i));
+                    else *reinterpret_cast<uint2*>(xlo_row + i) = make_uint2(ol[0], ol[1]);
+                }
+            }
+        }
+    }
+};
+
+// one wave per token row, grid-stride.  Same arithmetic per element as round 1's 8-byte k_ln; the row sums add the elements in the lane order of Ln16
+// (rows stay independent of the batch).
+// POL (cache policy of the streams; profiles/r04/tried_ln_policies.txt): bit 0 = y loaded non-temporally (dead after this kernel), bit 1 = the low half loaded
+// non-temporally, bit 2 = the low half stored non-temporally (its next reader is the next LayerNorm, ~600 MiB of traffic later)
+template <int NS, int POL = 0>
+__global__ __launch_bounds__(256) void k_ln16(const uint16_t* __restrict__ y, const float* __restrict__ ybias, const int* __restrict__ Tp, const float* __restrict__ g,
+                                              const float* __restrict__ bta, float eps, int H, const uint8_t* xlo_in, uint8_t* xlo, uint16_t* xb) {
+    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+    const int lane = threadIdx.x & 63;
+    const int T = *Tp;
+    Ln16<NS> ln;
+    ln.load_params(g, bta, ybias, H, lane);
+    const int64_t step = (int64_t)gridDim.x * 4;
+    int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    uint4 a[NS], rh[NS]; uint2 rl[NS];
+    auto load_row = [&](int64_t row) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+            a[j] = rh[j] = make_uint4(0u, 0u, 0u, 0u); rl[j] = make_uint2(0x80808080u, 0x80808080u);      // byte 128 = a zero low half
+            if (i < H && row < T) {
+                a[j] = (POL & 1) ? __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(y + row * H + i))) : *reinterpret_cast<const uint4*>(y + row * H + i);
+                rh[j] = *reinterpret_cast<const uint4*>(xb + row * H + i);
+                if (xlo_in) rl[j] = (POL & 2) ? __builtin_bit_cast(uint2, __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(xlo_in + row * H + i))) : *reinterpret_cast<const uint2*>(xlo_in + row * H + i);
+            }
+        }
+    };
+    load_row(t);
+    for (; t < T; t += step) {
+        float v[NS][8];
+        ln.combine(a, rh, rl, v);
+        load_row(t + step);                                   // next row's loads in flight while this one is reduced and stored
+        ln.template normalize_store<(POL & 4) != 0>(v, H, eps, lane, xb + t * H, xlo ? xlo + t * H : nullptr);
+    }
+}
+
+// pooling + L2 normalisation: one block per sequence.  Mean pooling: wave w sums the tokens t = w, w+4, ... (8-byte loads of the (hi, lo)
+// stream, 4 columns per lane and step), the four partial sums are combined in a fixed order (w = 0..3), so the result is deterministic.
+// pooling + L2 normalisation: one block of 16 waves per sequence.  Masked mean: wave w sums tokens w, w + 16, ... (in that order), the 16 partial rows are added
+// in wave order — a fixed order per sequence, whatever the batch.  (Rounds 1-4 used 4 waves: the kernel is bound by the VALU work of decoding and adding
+// 262 k elements for a 256-token sequence on ONE block, 37 us — 2.7 % of a one-sequence forward; 16 waves: see profiles/r05.)
+constexpr int POOL_WAVES = 16;
+template <int NJ>     // 256-element steps that cover a row: H <= 256 NJ
+__global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo, const int* __restrict__ seq_off,
+                                                         const int* __restrict__ seq_nk, const int* __restrict__ seq_cls, int H, int pool, float* __restrict__ out,
+                                                         int* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* part = reinterpret_cast<float*>(smem);                     // [POOL_WAVES][NJ * 256]
+    float* red = part + POOL_WAVES * NJ * 256;                        // [POOL_WAVES]
+    constexpr int HP = NJ * 256;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t off = seq_off[b];
+    const int nk = seq_nk[b];
+    float4 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int t_begin = pool == KR_POOL_CLS ? (wave == 0 ? seq_cls[b] : 1 << 30) : wave;
+    const int t_end = pool == KR_POOL_CLS ? (wave == 0 ? seq_cls[b] + 1 : 0) : nk;
+    // PU of the wave's tokens per step: all their loads are issued before the first add; the adds keep the order t, t + 16, t + 32, ... so the result does
+    // not depend on the unrolling
+    constexpr int PU = NJ <= 4 ? 4 : 2;       // 16 waves per block: 128 registers per lane
+    for (int t = t_begin; t < t_end; t += POOL_WAVES * PU) {
+        ushort4 hi[PU][NJ]; unsigned int lo[PU][NJ];
+#pragma unroll
+        for (int u = 0; u < PU; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int i = lane * 4 + j * 256;
+                if (i < H && t + POOL_WAVES * u < t_end) {
+                    hi[u][j] = *reinterpret_cast<const ushort4*>(xb + (off + t + POOL_WAVES * u) * H + i);
+                    lo[u][j] = xlo ? *reinterpret_cast<const unsigned int*>(xlo + (off + t + POOL_WAVES * u) * H + i) : 0x80808080u;
+                }
+            }
+#pragma unroll
+        for (int u = 0; u < PU; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int i = lane * 4 + j * 256;
+                if (i < H && t + POOL_WAVES * u < t_end) {
+                    acc[j].x += lo_decode_final(lo[u][j] & 0xffu, ET::to_f32(hi[u][j].x)); acc[j].y += lo_decode_final((lo[u][j] >> 8) & 0xffu, ET::to_f32(hi[u][j].y));
+                    acc[j].z += lo_decode_final((lo[u][j] >> 16) & 0xffu, ET::to_f32(hi[u][j].z)); acc[j].w += lo_decode_final(lo[u][j] >> 24, ET::to_f32(hi[u][j].w));
+                }
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int i = lane * 4 + j * 256;
+        if (i < H) *reinterpret_cast<float4*>(&part[wave * HP + i]) = acc[j];
+    }
+    __syncthreads();
+    constexpr int VJ = (NJ * 256 + POOL_WAVES * 64 - 1) / (POOL_WAVES * 64);      // elements per thread of the pooled row
+    float v[VJ];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) {
+        const int i = tid + j * POOL_WAVES * 64;
+        v[j] = 0.f;
+        if (i < H) {
+            float s = part[i];
+#pragma unroll
+            for (int w = 1; w < POOL_WAVES; ++w) s += part[w * HP + i];
+            v[j] = pool == KR_POOL_CLS ? s : s / (float)nk;   // nk == 0 -> 0/0 = NaN like average_pool (encoders.py:56-58)
+            ss += v[j] * v[j];
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    float n2 = red[0];
+#pragma unroll
+    for (int w = 1; w < POOL_WAVES; ++w) n2 += red[w];
+    const float nrm = sqrtf(n2);
+    // A sequence WITH attended tokens whose pooled vector is not finite: an activation left the 16-bit operand range upstream (f16: |x| > 65504 becomes
+    // inf, the next LayerNorm row NaN) or the weights hold NaN / Inf.  Recorded in the sticky error word (bit 1) and reported like an out-of-vocabulary
+    // token id (kr_encoder_check: KR_ERANGE) instead of being returned as an embedding.  nk == 0 is the reference's own NaN (average_pool of nothing).
+    if (tid == 0 && nk > 0 && !(nrm < INFINITY)) atomicOr(err, 2);
+    const float den = fmaxf(nrm, 1e-12f);   // F.normalize eps; NaN norm stays NaN (fmaxf would drop it)
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) {
+        const int i = tid + j * POOL_WAVES * 64;
+        if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] / den : NAN;
+    }
+}
+
+// CLS shortcut: row seq_off[b] + seq_cls[b] of ctx / the residual stream (hi, lo) -> row b of the compact buffers; also the compact "sequence" tables
+// (one token per sequence) and the row count for the B-row kernels that follow
+__global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__ ctx, const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,
+                                                    const int* __restrict__ seq_off, const int* __restrict__ seq_cls, const int* __restrict__ seq_nk, int H, uint16_t* __restrict__ c_ctx,
+                                                    uint16_t* __restrict__ c_xb, uint8_t* __restrict__ c_xlo, int* __restrict__ c_off, int* __restrict__ c_nk,
+                                                    int* __restrict__ c_cls, int* __restrict__ d_B) {
+    const int b = blockIdx.x;
+    const int64_t src = (int64_t)seq_off[b] + seq_cls[b];
+    for (int i = threadIdx.x * 8; i < H; i += 256 * 8) {
+        *reinterpret_cast<uint4*>(c_ctx + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(ctx + src * H + i);
+        *reinterpret_cast<uint4*>(c_xb + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(xb + src * H + i);
+        if (xlo) *reinterpret_cast<uint2*>(c_xlo + (int64_t)b * H + i) = *reinterpret_cast<const uint2*>(xlo + src * H + i);
+    }
+    if (threadIdx.x == 0) {
+        c_off[b] = b; c_nk[b] = seq_nk[b] > 0 ? 1 : 0; c_cls[b] = 0;   // c_nk == 0: an all-masked sequence (its NaN is the reference's own, not an overflow: k_pool)
+        if (b == 0) *d_B = (int)gridDim.x;
+    }
+}
+
+}  // namespace KR_ENC_NS
+}  // namespace kr

@@ -2,7 +2,7 @@
 in front of ``compute_corpus_embeddings.py:77-81``): batches of passage TEXT become token frames sitting in pinned host memory, in corpus order, ahead of the GPU.
 
 What travels is RAGGED: the int32 ids of the attended positions of every sequence back to back + one int32 length per sequence - exactly the token list
-``kr_encoder_forward_packed`` packs on the device (``k_rag_fill``), 4-16x fewer bytes than the padded int64 ``input_ids`` + ``attention_mask`` the collator
+``kr_encoder_forward_packed`` packs on the device (``k_rag_fill``, ``csrc/encoder_pack.hip``), 4-16x fewer bytes than the padded int64 ``input_ids`` + ``attention_mask`` the collator
 returns, as raw buffers (a 32-byte header + two arrays), never a pickle.  A batch whose mask is not "1^len 0^(S-len)" (a tokenizer that pads on the left)
 travels padded instead and takes the ``model.doc({"input_ids", "attention_mask"})`` route; results are the same rows either way.
 

@@ -267,23 +267,29 @@ class _HipSentenceMixin:
         self.kwargs = kwargs
         self._hip: Optional[HipBertForward] = None
 
-    def _hip_forward(self, input_ids, attention_mask, token_type_ids):
+    def _synced_hip(self) -> HipBertForward:
+        """The ``HipBertForward`` of the device the parameters are on, holding their current values."""
         p = next(self.parameters())
         if not p.is_cuda:
             raise RuntimeError(
                 f"{type(self).__name__} in eval mode runs on the MI355X HIP path only; its parameters are on {p.device}. "
                 "Move the model to a GPU (kirag_amd has no CPU fallback).")
-        if input_ids.dim() != 2:
-            raise ValueError(f"input_ids must be [B,S], got {tuple(input_ids.shape)}")
         idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
         if self._hip is None or self._hip.device_index != idx:
             self._hip = HipBertForward(self.config, idx)
         self._hip.sync(self)
-        if (input_ids.is_cuda and input_ids.device != p.device) or (not input_ids.is_cuda and token_type_ids is not None):
-            input_ids = input_ids.to(p.device)
-        with torch.cuda.device(idx):
+        return self._hip
+
+    def _hip_forward(self, input_ids, attention_mask, token_type_ids):
+        hip = self._synced_hip()
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B,S], got {tuple(input_ids.shape)}")
+        device = next(self.parameters()).device
+        if (input_ids.is_cuda and input_ids.device != device) or (not input_ids.is_cuda and token_type_ids is not None):
+            input_ids = input_ids.to(device)
+        with torch.cuda.device(hip.device_index):
             # CPU inputs (the collator's tensors as they are) are uploaded by the library from pinned staging; token types go to the kernels (kr_encoder_forward_tt)
-            return self._hip.forward(input_ids, attention_mask, self._pool, token_type_ids)
+            return hip.forward(input_ids, attention_mask, self._pool, token_type_ids)
 
     def forward_packed(self, token_ids: Tensor, seq_lens: Tensor, max_len: int, total_tokens: Optional[int] = None) -> Tensor:
         """Sentence embeddings [B, hidden] from the ragged token list of a right-padded batch (int32 attended ids back to back + int32 lengths; see
@@ -291,14 +297,7 @@ class _HipSentenceMixin:
         ``attention_mask``.  Bit-identical to ``forward(input_ids, attention_mask)`` on the padded batch; eval mode only (the HIP path)."""
         if self.training:
             raise RuntimeError("forward_packed is the inference (HIP) path: call model.eval() first")
-        p = next(self.parameters())
-        if not p.is_cuda:
-            raise RuntimeError(f"{type(self).__name__} in eval mode runs on the MI355X HIP path only; its parameters are on {p.device}.")
-        idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
-        if self._hip is None or self._hip.device_index != idx:
-            self._hip = HipBertForward(self.config, idx)
-        self._hip.sync(self)
-        return self._hip.forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
+        return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def invalidate_hip_weights(self) -> None:
         if self._hip is not None:

@@ -1,4 +1,4 @@
-"""The residual stream's low byte (kirag_amd/csrc/encoder.hip: lo_encode / lo_decode) as a numpy specification: x is kept as hi = the 16-bit operand
+"""The residual stream's low byte (kirag_amd/csrc/encoder_rows.hpp: lo_encode / lo_decode) as a numpy specification: x is kept as hi = the 16-bit operand
 (round to nearest) plus ONE byte = the distance bits(x) - bits(hi) on the fp32 bit patterns in units of 2^LO_SH fp32 ulps (= ulp(hi) / 256), biased by 128
 and clamped BEFORE the shift (the shift-then-clamp form is selected to v_ashr_pk_u8_i32, which writes only 16 bits on gfx950: tests/test_build_quality.py).
 The properties below are what the kernels rely on; the device functions are exercised by tools/lo_codec_check.hip and, end to end, by the encoder goldens."""

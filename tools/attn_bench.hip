@@ -1,8 +1,8 @@
-// Micro-benchmark of the long-sequence attention kernel (kirag_amd/csrc/encoder.hip: k_attn_dma) on synthetic f16 Q / K / V^T of B sequences x S tokens,
+// Micro-benchmark of the long-sequence attention kernel (kirag_amd/csrc/encoder_attn.hpp: k_attn_dma) on synthetic f16 Q / K / V^T of B sequences x S tokens,
 // 16 heads x 64:   mkdir -p tools/bin && hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/attn_bench.hip -o tools/bin/attn_bench && tools/bin/attn_bench [B S]
 // Prints us per launch (HIP events), TFLOP/s of the two MFMA products and a checksum of ctx.
 #define KR_ENC_BUILD_F16 1
-#include "../kirag_amd/csrc/encoder.hip"
+#include "../kirag_amd/csrc/encoder_attn.hpp"
 
 #include <cstdio>
 #include <random>
@@ -15,6 +15,7 @@ bool is_device_pointer(const void*) { return true; }
 std::atomic<int> g_force_exact{0};
 }
 using namespace kr::enc_f16;
+constexpr int ADMA_LDS = AdmaGeom<64>::LDS;     // 64-wide heads, no relative attention bias: k_attn_dma<64>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
 int main(int argc, char** argv) {
@@ -36,10 +37,10 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(d_off, off.data(), B * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(d_nk, nk.data(), B * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(d_nq, nq.data(), B * 4, hipMemcpyHostToDevice));
     const int nqt = (S + 31) / 32, qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;
     const int extra_lds = argc > 3 ? atoi(argv[3]) : 0;      // > 32 KiB: only one block fits a CU (one wave per SIMD): how much do two co-resident blocks overlap?
-    if (extra_lds) CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dma), hipFuncAttributeMaxDynamicSharedMemorySize, ADMA_LDS + extra_lds));
+    if (extra_lds) CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_dma<64>), hipFuncAttributeMaxDynamicSharedMemorySize, ADMA_LDS + extra_lds));
     auto launch = [&] {
-        hipLaunchKernelGGL(k_attn_dma, dim3(((B * heads + 7) / 8) * 8 * qgroups), dim3(ADMA_THREADS), ADMA_LDS + extra_lds, 0, q, k, vT, ldv, d_off, d_nk, d_nq, H, T, ctx,
-                           heads, B, qgroups);
+        hipLaunchKernelGGL(k_attn_dma<64>, dim3(((B * heads + 7) / 8) * 8 * qgroups), dim3(ADMA_THREADS), ADMA_LDS + extra_lds, 0, q, k, vT, ldv, d_off, d_nk, d_nq, H, T, ctx,
+                           heads, B, qgroups, AttnNoBiasArgs{});
     };
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int i = 0; i < 3; ++i) launch();

@@ -2,6 +2,7 @@
 """Per-kernel resource notes of the gfx950 code objects embedded in a built object / shared library.
 
     python tools/kernel_notes.py kirag_amd/libkirag_amd.so [--spills]
+    python tools/kernel_notes.py --isa-diff old.so new.so       # symbols whose gfx950 disassembly differs between two builds
 
 Reads the clang offload bundles out of the file (no GPU needed), runs `llvm-readelf --notes` on every gfx950 code object and prints
 VGPR / AGPR / SGPR counts, spill counts, scratch and static LDS bytes per kernel.  `tests/test_build_quality.py` uses `kernels()` to
@@ -57,6 +58,34 @@ def count_instruction(path, mnemonic, arch="gfx950"):
     return n
 
 
+def disassembly(path, arch="gfx950"):
+    """{symbol: disassembly text} over the `arch` code objects of `path`, without addresses and encodings."""
+    syms = {}
+    for co in code_objects(path, arch):
+        with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
+            f.write(co)
+        try:
+            txt = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", "--no-leading-addr", "--mcpu=" + arch, f.name], capture_output=True, text=True, check=True).stdout
+        finally:
+            os.unlink(f.name)
+        name = None
+        for line in txt.splitlines():
+            m = re.match(r"<(.+)>:$", line)
+            if m:
+                name = m.group(1)
+                syms[name] = []
+            elif name:
+                syms[name].append(line.split("//")[0].rstrip())     # the AMDGPU printer keeps address + encoding in a trailing comment
+    return {k: "\n".join(v) for k, v in syms.items()}
+
+
+def isa_diff(path_a, path_b, arch="gfx950"):
+    """Symbols whose disassembly differs between two builds: (only in a, only in b, in both but different), each sorted.  A refactor that claims to leave
+    the kernels alone shows it here: every symbol it did not mean to touch is absent from all three lists."""
+    a, b = disassembly(path_a, arch), disassembly(path_b, arch)
+    return sorted(set(a) - set(b)), sorted(set(b) - set(a)), sorted(k for k in set(a) & set(b) if a[k] != b[k])
+
+
 def kernels(path, arch="gfx950"):
     """List of dicts (one per kernel): name, vgpr_count, agpr_count, sgpr_count, vgpr_spill_count, sgpr_spill_count,
     private_segment_fixed_size, group_segment_fixed_size (all ints except name)."""
@@ -85,6 +114,15 @@ def kernels(path, arch="gfx950"):
 
 
 if __name__ == "__main__":
+    if "--isa-diff" in sys.argv:       # kernel_notes.py --isa-diff old.so new.so
+        old, new = [a for a in sys.argv[1:] if not a.startswith("--")]
+        gone, added, changed = isa_diff(old, new)
+        print("%d symbols in %s, %d in %s" % (len(disassembly(old)), old, len(disassembly(new)), new))
+        for title, names in (("only in " + old, gone), ("only in " + new, added), ("different", changed)):
+            print("%s: %d" % (title, len(names)))
+            for n in names:
+                print("    " + n)
+        sys.exit(0)
     only_spills = "--spills" in sys.argv
     for r in kernels([a for a in sys.argv[1:] if not a.startswith("--")][0]):
         if only_spills and not (r.get("vgpr_spill_count") or r.get("private_segment_fixed_size")):

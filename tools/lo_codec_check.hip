@@ -1,4 +1,4 @@
-// Stand-alone check of the residual stream's byte codec (kirag_amd/csrc/encoder.hip: lo_encode / lo_decode, f16 build): random values through the
+// Stand-alone check of the residual stream's byte codec (kirag_amd/csrc/encoder_rows.hpp: lo_encode / lo_decode, f16 build): random values through the
 // device functions, compared with hi alone.  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/lo_codec_check.hip -o tools/bin/lo_codec_check
 #include <hip/hip_runtime.h>
 #include <cstdio>
