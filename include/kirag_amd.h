@@ -252,6 +252,26 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   0..i, attended or not) where ids[i] != P, and P where ids[i] == P; the forwards then take S <= max_pos - P - 1.  Without it the handle follows BERT's
  *   rule (position = column), bit for bit as before.  Accepted before the handle's first finalize and kept for the handle's life: later the same value is
  *   a no-op, another value KR_EINVAL.  kr_encoder_last_hidden keeps placing rows at their columns under both rules.
+ *   "config.rotary_inv_freq": data = d_h / 2 floats (d_h = hidden / heads; any other count is KR_EINVAL), HF's rotary_emb.inv_freq.  Loading it before the
+ *   handle's first finalize makes the handle a NomicBert handle for life (nomic-embed-text-v1 / -v1.5, transformers.NomicBertModel); afterwards the same
+ *   values are a no-op and other values, or loading it onto a handle that was finalized without it, are KR_EINVAL.  kr_encoder_finalize then builds cos / sin
+ *   tables [max_pos][d_h / 2] (max_pos <= 8192): the angle is the fp32 product float(pos) * inv_freq[j], the entries its cosine / sine.  On such a handle
+ *     - there is no position table ("embeddings.position_embeddings.weight" is not required; the embedding LayerNorm sums word + token type), and the
+ *       forwards take S <= max_pos;
+ *     - q and k of every head are rotated after the projection and before they are rounded to 16 bits, NeoX pairing over the whole head width:
+ *           x'[j] = x[j] cos - x[j + d_h/2] sin,   x'[j + d_h/2] = x[j + d_h/2] cos + x[j] sin,   cos / sin = table[pos][j],  j < d_h / 2,
+ *       where pos is the token's column in the padded [B, S] batch (in kr_encoder_forward_packed, its index inside its sequence) minus the smallest column
+ *       among its sequence's rows (the first attended column; 0 when CLS pooling adds the query row of a masked column 0).  Scores depend on column
+ *       differences only, so the shift changes no exact score, left padding and masks with holes need no further rule, and a sequence gives the same
+ *       bits wherever it stands in the padded batch;
+ *     - the MLP is gated: down_proj(silu(gate_proj(x)) * up_proj(x)), gate | up as one projection of 2 * intermediate columns;
+ *     - NomicBertModel's state dict loads unchanged: "layers.N.self_attn.{q,k,v,o}_proj.weight" fill the slots of BERT's attention.self.{query,key,value} /
+ *       attention.output.dense, "layers.N.post_attention_layernorm.*" / "layers.N.post_mlp_layernorm.*" those of attention.output.LayerNorm / output.LayerNorm,
+ *       "layers.N.mlp.down_proj.weight" that of output.dense, and "layers.N.mlp.gate_proj.weight" + "layers.N.mlp.up_proj.weight" together that of the
+ *       intermediate projection (a missing one fails finalize as "never loaded"); "embeddings.{word_embeddings,token_type_embeddings,LayerNorm}.*" as in BERT.
+ *       q_proj / k_proj / gate_proj / up_proj must come under these names (their packed copies have another row order) and have no bias; the biases of
+ *       v / o / down (BERT's names) are zero unless loaded.  A handle without the setting refuses these names at finalize.  It combines with neither
+ *       "config.position_padding_idx" nor MPNet's bias tensor.
  * MPNetModel (all-mpnet-base-v2, multi-qa-mpnet-*): its state dict loads unchanged.  The layer names "encoder.layer.N.attention.attn.{q,k,v,o}.{weight,bias}"
  * and "encoder.layer.N.attention.LayerNorm.{weight,bias}" fill the slots of BERT's attention.self.{query,key,value} / attention.output.{dense,LayerNorm}
  * (last write wins when a caller uses both spellings for one slot).  MPNet has no token types: create the handle with type_vocab = 1 and load ONE row of

@@ -17,6 +17,9 @@
 // residual -> LayerNorm;  W1 x + b -> erf-GELU;  W2 h + b + residual -> LayerNorm.  Pooling (masked mean or CLS)
 // + L2 normalisation produce out[B,H] fp32.
 //
+// NomicBert handles (config.rotary_inv_freq, see Encoder::inv_freq): no position table, q and k rotated by the token's column in the QKV epilogue (EPI_QKV_ROT),
+// [gate | up] x as one GEMM whose epilogue writes silu(gate) * up (EPI_SWIGLU) in place of W1 x + b -> erf-GELU; everything else as above.
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -39,6 +42,8 @@ struct LayerW {
     uint16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;   // bf16 [out, in]
     float *bqkv = nullptr, *bo = nullptr, *bo_eff = nullptr, *b1 = nullptr, *b2 = nullptr;   // bo_eff = bo + Wo.bv
     float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
+    // w1 is allocated by its first tensor: [FF, H] (intermediate.dense) or, gated, [2 FF, H] (NomicBert's gate_proj | up_proj, interleaved per 32-row tile)
+    bool gated = false;
 };
 
 // A/B switches of the projection / attention launches, read from the environment ONCE per forward (enqueue_forward), not per launch: a forward is 96
@@ -67,7 +72,7 @@ struct Encoder {
     // every hipMalloc of the handle is recorded where it is made (dmalloc) and freed by walking its list: ws_bufs = the workspace (free_ws), own_bufs = what
     // lives as long as the handle (enc_destroy)
     std::vector<void**> ws_bufs, own_bufs;
-    std::vector<uint8_t> got;     // 5 + 16*layers flags
+    std::vector<uint8_t> got;     // 5 + L_COUNT * layers flags: 0 = never loaded, 1 = loaded, 2 = loaded under a NomicBert name (enc_finalize: rows in tile-pair order)
     bool ready = false;
     float* stage = nullptr; size_t stage_elems = 0;   // fp32 upload staging for load_weight
     // workspace
@@ -90,6 +95,13 @@ struct Encoder {
     std::vector<float> rel_w;
     float* bias_tab = nullptr; int bias_width = 0;
     bool bias_gather = false;  // KIRAG_AMD_ATTN_BIAS_GATHER=1 at kr_encoder_create: key columns always from tok_pos (the path of masks with holes), for tests
+    // rotary positions (NomicBert): loading "config.rotary_inv_freq" (d_h / 2 values, HF's rotary_emb.inv_freq) before the first finalize makes the handle a
+    // NomicBert handle for life: no position table (the embedding adds pos_zero through tok_zero), q and k rotated in the QKV epilogue by rot_cos / rot_sin
+    // [max_pos][d_h / 2] (built by finalize), gate | up as ONE projection with the SwiGLU epilogue, linear biases zero unless loaded
+    std::vector<float> inv_freq;
+    float *rot_cos = nullptr, *rot_sin = nullptr, *pos_zero = nullptr;
+    int *tok_zero = nullptr, *tok_rpos = nullptr;   // tok_rpos: the position each token is rotated by (k_rot_pos)
+    bool rotary() const { return !inv_freq.empty(); }
     float *out = nullptr;
     uint8_t *xlo = nullptr;    // low half of the residual stream, one byte per element (lo_encode): written by every LayerNorm with use_lo, else by the last one only
     bool use_lo = false;       // KIRAG_AMD_RESIDUAL_LO=1 at kr_encoder_create
@@ -157,6 +169,10 @@ static int ensure_ws(Encoder* e, int B, int S) {
     KR_TRY(dmalloc(e->ws_bufs, &e->seq_off, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_nk, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_nq, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_cls, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_has0, capB * 4));
     KR_TRY(dmalloc(e->ws_bufs, &e->tok_id, capT * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->tok_pos, capT * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->tok_type, capT * 4));
     if (e->pad_idx >= 0) KR_TRY(dmalloc(e->ws_bufs, &e->tok_epos, capT * 4));
+    if (e->rotary()) {
+        KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
+        KR_TRY(dmalloc(e->ws_bufs, &e->tok_rpos, capT * 4)); KR_HIP(hipMemset(e->tok_rpos, 0, (size_t)capT * 4));
+    }
     KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * H * 4));
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
@@ -176,16 +192,24 @@ static int ensure_ws(Encoder* e, int B, int S) {
     return 0;
 }
 
-// tensor slot ids: 0..4 embeddings, then 16 per layer
+// tensor slot ids: 0..4 embeddings, then L_COUNT per layer (L_UW: NomicBert's up_proj, the second half of a gated intermediate projection)
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
 constexpr int T_RELBIAS = -2;          // not a slot of `got`: an optional tensor (parse_name)
 constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says
-enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_COUNT };
+enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
 
-static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& numel) {
+// nomic: the name is NomicBertModel's ("layers.N.self_attn.q_proj.weight", ...)
+static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& numel, bool& nomic) {
     std::string s(name);
+    nomic = false;
     size_t p = s.find("embeddings.");
     size_t pl = s.find("encoder.layer.");
+    size_t skip = strlen("encoder.layer.");
+    if (pl == std::string::npos && (s.compare(0, 7, "layers.") == 0 || s.find(".layers.") != std::string::npos)) {
+        pl = s.compare(0, 7, "layers.") == 0 ? 0 : s.find(".layers.") + 1;
+        skip = strlen("layers.");
+        nomic = true;
+    }
     const int64_t H = e->cfg.hidden, FF = e->cfg.intermediate;
     if (s.find("position_ids") != std::string::npos || s.find("pooler.") != std::string::npos) { slot = -1; return 0; }
     {
@@ -193,13 +217,18 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
         if (s.size() >= sizeof(rel) - 1 && s.compare(s.size() - (sizeof(rel) - 1), sizeof(rel) - 1, rel) == 0) { slot = T_RELBIAS; numel = (int64_t)REL_BUCKETS * e->cfg.heads; return 0; }
     }
     if (pl != std::string::npos) {
-        const char* c = s.c_str() + pl + strlen("encoder.layer.");
+        const char* c = s.c_str() + pl + skip;
         char* end = nullptr;
         const long l = strtol(c, &end, 10);
         if (end == c || *end != '.' || l < 0 || l >= e->cfg.layers) return fail(KR_EINVAL, "bad layer index in '%s'", name);
         const std::string r(end + 1);
         // BERT's names (BertModel, RobertaModel, XLMRobertaModel) and MPNet's (MPNetModel: attention.attn.{q,k,v,o}, attention.LayerNorm) for the same slots
-        static const struct { const char* n; int id; } tbl[] = {
+        struct NameId { const char* n; int id; };
+        static const NameId nomic_tbl[] = {
+            {"self_attn.q_proj.weight", L_QW}, {"self_attn.k_proj.weight", L_KW}, {"self_attn.v_proj.weight", L_VW}, {"self_attn.o_proj.weight", L_OW},
+            {"post_attention_layernorm.weight", L_LN1G}, {"post_attention_layernorm.bias", L_LN1B}, {"mlp.gate_proj.weight", L_IW}, {"mlp.up_proj.weight", L_UW},
+            {"mlp.down_proj.weight", L_FW}, {"post_mlp_layernorm.weight", L_LN2G}, {"post_mlp_layernorm.bias", L_LN2B}};
+        static const NameId bert_tbl[] = {
             {"attention.attn.q.weight", L_QW}, {"attention.attn.q.bias", L_QB}, {"attention.attn.k.weight", L_KW}, {"attention.attn.k.bias", L_KB},
             {"attention.attn.v.weight", L_VW}, {"attention.attn.v.bias", L_VB}, {"attention.attn.o.weight", L_OW}, {"attention.attn.o.bias", L_OB},
             {"attention.LayerNorm.weight", L_LN1G}, {"attention.LayerNorm.bias", L_LN1B},
@@ -209,12 +238,14 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
             {"attention.output.LayerNorm.weight", L_LN1G}, {"attention.output.LayerNorm.bias", L_LN1B},
             {"intermediate.dense.weight", L_IW}, {"intermediate.dense.bias", L_IB}, {"output.dense.weight", L_FW}, {"output.dense.bias", L_FB},
             {"output.LayerNorm.weight", L_LN2G}, {"output.LayerNorm.bias", L_LN2B}};
-        for (const auto& t : tbl)
-            if (r == t.n) {
+        const NameId* tbl = nomic ? nomic_tbl : bert_tbl;
+        const size_t tbl_n = nomic ? sizeof(nomic_tbl) / sizeof(nomic_tbl[0]) : sizeof(bert_tbl) / sizeof(bert_tbl[0]);
+        for (size_t ti = 0; ti < tbl_n; ++ti)
+            if (const NameId& t = tbl[ti]; r == t.n) {
                 slot = T_LAYER0 + (int)l * L_COUNT + t.id;
                 switch (t.id) {
                     case L_QW: case L_KW: case L_VW: case L_OW: numel = H * H; break;
-                    case L_IW: case L_FW: numel = H * FF; break;
+                    case L_IW: case L_FW: case L_UW: numel = H * FF; break;
                     case L_IB: numel = FF; break;
                     default: numel = H;
                 }
@@ -292,6 +323,8 @@ static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int devi
         case EPI_QKV: return go(&k_proj<EPI_QKV, Shape, STAGES, NT>);
         case EPI_DENSE: return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>);
         case EPI_GELU: return go(&k_proj<EPI_GELU, Shape, STAGES, NT>);
+        case EPI_QKV_ROT: return go(&k_proj<EPI_QKV_ROT, Shape, STAGES, NT>);
+        case EPI_SWIGLU: return go(&k_proj<EPI_SWIGLU, Shape, STAGES, NT>);
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }
@@ -326,7 +359,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     a.pw = kn.pw;
     a.epi_prio = kn.epi_prio;
     // store policy by output size (see ProjArgs::nt)
-    a.nt = max_tokens * (int64_t)a.F * 2 > ((int64_t)96 << 20) ? 1 : 0;
+    a.nt = max_tokens * (int64_t)(epi == EPI_SWIGLU ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
     // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
     // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
     // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
@@ -357,6 +390,8 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
                 case EPI_QKV: return launch(shape_tag, &k_proj_skinny<EPI_QKV, RING, WM, WM>);
                 case EPI_DENSE: return launch(shape_tag, &k_proj_skinny<EPI_DENSE, RING, WM, WM>);
                 case EPI_GELU: return launch(shape_tag, &k_proj_skinny<EPI_GELU, RING, WM, WM>);
+                case EPI_QKV_ROT: return launch(shape_tag, &k_proj_skinny<EPI_QKV_ROT, RING, WM, WM>);
+                case EPI_SWIGLU: return launch(shape_tag, &k_proj_skinny<EPI_SWIGLU, RING, WM, WM>);
                 default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
             }
         };
@@ -376,6 +411,8 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
             case EPI_QKV: return go(&k_proj_split<EPI_QKV>);
             case EPI_DENSE: return go(&k_proj_split<EPI_DENSE>);
             case EPI_GELU: return go(&k_proj_split<EPI_GELU>);
+            case EPI_QKV_ROT: return go(&k_proj_split<EPI_QKV_ROT>);
+            case EPI_SWIGLU: return go(&k_proj_split<EPI_SWIGLU>);
             default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
         }
     }
@@ -409,10 +446,11 @@ int enc_create(const kr_bert_cfg* cfg, int device, int residual_lo, void** out) 
     const size_t H = cfg->hidden, FF = cfg->intermediate;
     int rc = 0;
     auto A = [&](auto** p, size_t bytes) { if (!rc) rc = dmalloc(e->own_bufs, p, bytes); };
-    A(&e->word, (size_t)cfg->vocab * H * 4); A(&e->pos, (size_t)cfg->max_pos * H * 4); A(&e->type, (size_t)cfg->type_vocab * H * 4);
+    A(&e->word, (size_t)cfg->vocab * H * 4); A(&e->type, (size_t)cfg->type_vocab * H * 4);
     A(&e->elng, H * 4); A(&e->elnb, H * 4);
+    // the position table and every layer's w1 are allocated by their first tensor (enc_load_weight): a NomicBert handle has no table, and its w1 is [2 FF, H]
     for (auto& l : e->L) {
-        A(&l.wqkv, 3 * H * H * 2); A(&l.wo, H * H * 2); A(&l.w1, FF * H * 2); A(&l.w2, H * FF * 2);
+        A(&l.wqkv, 3 * H * H * 2); A(&l.wo, H * H * 2); A(&l.w2, H * FF * 2);
         A(&l.bqkv, 3 * H * 4); A(&l.bo, H * 4); A(&l.bo_eff, H * 4); A(&l.b1, FF * 4); A(&l.b2, H * 4);
         A(&l.ln1g, H * 4); A(&l.ln1b, H * 4); A(&l.ln2g, H * 4); A(&l.ln2b, H * 4);
     }
@@ -439,8 +477,31 @@ void enc_destroy(void* h) {
 // Settings of the handle travel through the name-addressed loader under the reserved prefix "config." (no tensor of an HF state dict starts with it).
 // config.position_padding_idx = P (one float holding an integer, 0 <= P <= max_pos - 2): fairseq's position rule.  Accepted before the first finalize; later
 // the same value is a no-op and any other is refused (the workspace and the meaning of every embedding depend on it).
+// config.rotary_inv_freq = d_h / 2 values (HF's rotary_emb.inv_freq): rotary positions, a NomicBert handle (Encoder::inv_freq).  The same rule: before the first
+// finalize; later the same values are a no-op, anything else is refused.
+static int set_rotary(Encoder* e, const float* data, int64_t numel) {
+    const int half = e->cfg.hidden / e->cfg.heads / 2;
+    if (numel != half) return fail(KR_EINVAL, "config.rotary_inv_freq takes d_h / 2 = %d values, got %lld", half, (long long)numel);
+    if (e->cfg.max_pos > 8192) return fail(KR_EINVAL, "config.rotary_inv_freq: max_position_embeddings = %d, rotary tables are built for at most 8192", e->cfg.max_pos);
+    std::vector<float> v((size_t)half);
+    KR_HIP(hipMemcpy(v.data(), data, (size_t)half * 4, hipMemcpyDefault));
+    for (float x : v) if (!std::isfinite(x)) return fail(KR_EINVAL, "config.rotary_inv_freq holds a non-finite value");
+    if (e->finalized_once) {
+        if (!e->rotary())
+            return fail(KR_EINVAL, "config.rotary_inv_freq after kr_encoder_finalize: the handle was finalized without rotary positions and stays a BERT / RoBERTa / MPNet handle");
+        if (std::memcmp(v.data(), e->inv_freq.data(), (size_t)half * 4) != 0)
+            return fail(KR_EINVAL, "config.rotary_inv_freq with other values after kr_encoder_finalize: the handle's rotary frequencies are fixed");
+        return 0;
+    }
+    e->inv_freq.swap(v);
+    e->ready = false;
+    return 0;
+}
+
 static int set_config(Encoder* e, const char* name, const float* data, int64_t numel) {
-    if (std::strcmp(name, "config.position_padding_idx") != 0) return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx)", name);
+    if (std::strcmp(name, "config.rotary_inv_freq") == 0) return set_rotary(e, data, numel);
+    if (std::strcmp(name, "config.position_padding_idx") != 0)
+        return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx, config.rotary_inv_freq)", name);
     if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
     float v = 0.f;
     KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
@@ -496,13 +557,34 @@ static int build_bias_table(Encoder* e) {
     return 0;
 }
 
+// cos / sin [max_pos][d_h / 2] with HF's arithmetic (NomicBertRotaryEmbedding.forward): the angle is the fp32 product float(pos) * inv_freq[j], the entry the
+// cosine / sine of that fp32 angle (evaluated in double and rounded once).  Also the zero row the embedding adds in place of a position row.
+static int build_rotary_tables(Encoder* e) {
+    const int half = (int)e->inv_freq.size(), P = e->cfg.max_pos, H = e->cfg.hidden;
+    std::vector<float> cs((size_t)P * half), sn((size_t)P * half);
+    for (int p = 0; p < P; ++p)
+        for (int j = 0; j < half; ++j) {
+            const float ang = (float)p * e->inv_freq[j];
+            cs[(size_t)p * half + j] = (float)std::cos((double)ang);
+            sn[(size_t)p * half + j] = (float)std::sin((double)ang);
+        }
+    if (!e->rot_cos) {
+        KR_TRY(dmalloc(e->own_bufs, &e->rot_cos, cs.size() * 4)); KR_TRY(dmalloc(e->own_bufs, &e->rot_sin, sn.size() * 4));
+        KR_TRY(dmalloc(e->own_bufs, &e->pos_zero, (size_t)H * 4));
+        KR_HIP(hipMemset(e->pos_zero, 0, (size_t)H * 4));
+    }
+    KR_HIP(hipMemcpy(e->rot_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(e->rot_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(select_device(e->device));
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
-    int slot = -1; int64_t want = 0;
-    KR_TRY(parse_name(e, hf_name, slot, want));
+    int slot = -1; int64_t want = 0; bool nomic = false;
+    KR_TRY(parse_name(e, hf_name, slot, want, nomic));
     if (slot == T_RELBIAS) return load_rel_bias(e, hf_name, data, numel, want);
     if (slot < 0) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
     if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", hf_name, (long long)numel, (long long)want);
@@ -518,17 +600,30 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     const unsigned grid = (unsigned)((numel + 255) / 256);
     auto to_bf16 = [&](uint16_t* dst, float scale) { hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
     auto to_f32 = [&](float* dst, float scale) { hipLaunchKernelGGL(k_scale_copy, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
+    // NomicBert's matrices whose rows go into tile-pair order (k_f32_to_bf16_rows)
+    auto to_bf16_rows = [&](uint16_t* dst, float scale, int mode) {
+        hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, (int)H, scale, mode);
+    };
+    const bool head64 = nomic && H == 64 * e->cfg.heads;
     if (slot < T_LAYER0) {
+        if (slot == T_POS && !e->pos) KR_TRY(dmalloc(e->own_bufs, &e->pos, (size_t)numel * 4));
         float* dst[] = {e->word, e->pos, e->type, e->elng, e->elnb};
         to_f32(dst[slot], 1.f);
     } else {
         LayerW& l = e->L[(slot - T_LAYER0) / L_COUNT];
-        switch ((slot - T_LAYER0) % L_COUNT) {
+        const int id = (slot - T_LAYER0) % L_COUNT;
+        if (id == L_IW || id == L_UW) {
+            if (l.w1 && l.gated != nomic)
+                return fail(KR_EINVAL, "'%s': layer %d already holds %s", hf_name, (slot - T_LAYER0) / L_COUNT, nomic ? "intermediate.dense" : "a gated projection (gate_proj / up_proj)");
+            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * (nomic ? 4 : 2)));
+            l.gated = nomic;
+        }
+        switch (id) {
             // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2.  The
             // multiply is fp32, before the 16-bit conversion (d_h = 32: the factor is not a power of two; d_h = 64: the same bits as log2(e) / 8)
-            case L_QW: to_bf16(l.wqkv, qscale); break;
+            case L_QW: if (head64) to_bf16_rows(l.wqkv, qscale, ROWS_HEAD64); else to_bf16(l.wqkv, qscale); break;
             case L_QB: to_f32(l.bqkv, qscale); break;
-            case L_KW: to_bf16(l.wqkv + H * H, 1.f); break;
+            case L_KW: if (head64) to_bf16_rows(l.wqkv + H * H, 1.f, ROWS_HEAD64); else to_bf16(l.wqkv + H * H, 1.f); break;
             case L_KB: to_f32(l.bqkv + H, 1.f); break;
             case L_VW: to_bf16(l.wqkv + 2 * H * H, 1.f); break;
             case L_VB: to_f32(l.bqkv + 2 * H, 1.f); break;
@@ -536,7 +631,8 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             case L_OB: to_f32(l.bo, 1.f); break;
             case L_LN1G: to_f32(l.ln1g, 1.f); break;
             case L_LN1B: to_f32(l.ln1b, 1.f); break;
-            case L_IW: to_bf16(l.w1, 1.f); break;
+            case L_IW: if (nomic) to_bf16_rows(l.w1, 1.f, ROWS_GATE); else to_bf16(l.w1, 1.f); break;
+            case L_UW: to_bf16_rows(l.w1, 1.f, ROWS_UP); break;
             case L_IB: to_f32(l.b1, 1.f); break;
             case L_FW: to_bf16(l.w2, 1.f); break;
             case L_FB: to_f32(l.b2, 1.f); break;
@@ -546,7 +642,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     }
     KR_HIP(hipGetLastError());
     KR_HIP(hipDeviceSynchronize());
-    e->got[slot] = 1;
+    e->got[slot] = nomic ? 2 : 1;
     e->ready = false;
     return 0;
 }
@@ -554,12 +650,43 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
 int enc_finalize(void* h) {
     if (!h) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
+    const bool rot = e->rotary();
+    if (rot && (e->pad_idx >= 0 || !e->rel_w.empty()))
+        return fail(KR_EINVAL, "config.rotary_inv_freq next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
+    // q / k and the intermediate projection are packed in another row order under NomicBert's names (enc_load_weight): names and handle kind must agree
+    for (int li = 0; li < e->cfg.layers; ++li) {
+        const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
+        if (rot && (g[L_QW] == 1 || g[L_KW] == 1 || g[L_IW] == 1))
+            return fail(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj and mlp.{gate,up}_proj under NomicBert's names", li);
+        if (rot && (g[L_QB] || g[L_KB] || g[L_IB]))
+            return fail(KR_EINVAL, "layer %d: the q / k / gate / up projections of a NomicBert handle have no bias", li);
+        if (!rot && (g[L_QW] == 2 || g[L_KW] == 2 || g[L_IW] == 2 || g[L_UW]))
+            return fail(KR_EINVAL, "layer %d holds tensors under NomicBert's names but config.rotary_inv_freq was never loaded: load it before kr_encoder_finalize", li);
+    }
+    // a NomicBert handle has no position table and needs up_proj; its linear biases are zero unless loaded
+    auto optional = [&](size_t i) {
+        if (i < T_LAYER0) return rot && i == T_POS;
+        const int id = (int)((i - T_LAYER0) % L_COUNT);
+        if (id == L_UW) return !rot;
+        return rot && (id == L_QB || id == L_KB || id == L_VB || id == L_OB || id == L_IB || id == L_FB);
+    };
     for (size_t i = 0; i < e->got.size(); ++i)
-        if (!e->got[i]) return fail(KR_ESTATE, "weight slot %zu (layer %d, tensor %d) was never loaded", i,
+        if (!e->got[i] && !optional(i)) return fail(KR_ESTATE, "weight slot %zu (layer %d, tensor %d) was never loaded", i,
                                     i < T_LAYER0 ? -1 : (int)((i - T_LAYER0) / L_COUNT), i < T_LAYER0 ? (int)i : (int)((i - T_LAYER0) % L_COUNT));
     if (e->stage) { (void)hipFree(e->stage); e->stage = nullptr; e->stage_elems = 0; }
     KR_TRY(select_device(e->device));
     const int H = e->cfg.hidden;
+    if (rot) {
+        for (int li = 0; li < e->cfg.layers; ++li) {
+            const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
+            LayerW& l = e->L[li];
+            KR_HIP(hipMemset(l.bqkv, 0, (size_t)2 * H * 4));
+            if (!g[L_VB]) KR_HIP(hipMemset(l.bqkv + 2 * H, 0, (size_t)H * 4));
+            if (!g[L_OB]) KR_HIP(hipMemset(l.bo, 0, (size_t)H * 4));
+            if (!g[L_FB]) KR_HIP(hipMemset(l.b2, 0, (size_t)H * 4));
+        }
+        KR_TRY(build_rotary_tables(e));
+    }
     for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * H, l.bo_eff, H);
     if (!e->rel_w.empty()) KR_TRY(build_bias_table(e));
     KR_HIP(hipGetLastError());
@@ -607,7 +734,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
     unsigned ln_mult = 8u;
     const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
-    hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->pad_idx >= 0 ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word, e->pos, e->type, e->elng, e->elnb, eps, H,
+    const bool rot = e->rotary();       // a NomicBert handle: no position row in the embedding (a zero row through tok_zero), rotary QKV and SwiGLU epilogues
+    if (rot) hipLaunchKernelGGL(k_rot_pos, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nq, align, e->tok_pos, e->tok_rpos);
+    hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, rot ? e->tok_zero : e->pad_idx >= 0 ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word,
+                       rot ? e->pos_zero : e->pos, e->type, e->elng, e->elnb, eps, H,
                        e->use_lo ? e->xlo : nullptr, e->xb);
     const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr;
     e->last_shortcut = shortcut;
@@ -620,9 +750,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         a.W = l.wo; a.X = r.ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = r.y; a.ldx = 0; a.ldo = 0;
         KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
         hipLaunchKernelGGL(ln_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, r.lo, r.lo, r.xb);
-        // intermediate.dense + GELU
-        a.W = l.w1; a.X = r.xb; a.F = FF; a.K = H; a.bias = l.b1; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
-        KR_TRY(launch_proj(EPI_GELU, a, r.max_rows, e, st));
+        // intermediate.dense + GELU, or gate_proj | up_proj (one GEMM of 2 FF columns) + SwiGLU: h [rows, FF] either way
+        a.W = l.w1; a.X = r.xb; a.F = rot ? 2 * FF : FF; a.K = H; a.bias = l.b1; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
+        KR_TRY(launch_proj(rot ? EPI_SWIGLU : EPI_GELU, a, r.max_rows, e, st));
         // output.dense + residual -> LayerNorm
         a.W = l.w2; a.X = r.h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = r.y; a.ldx = FF; a.ldo = 0;
         KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
@@ -634,9 +764,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         const bool last = (&l == &e->L.back());
         ProjArgs a{};
         a.Tp = e->d_T; a.H = H;
+        a.rot_cos = e->rot_cos; a.rot_sin = e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
         // q | k | v^T in one GEMM (F = 3H)
         a.W = l.wqkv; a.X = e->xb; a.F = 3 * H; a.K = H; a.bias = l.bqkv; a.out0 = e->q; a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv; a.ldx = 0; a.ldo = 0;
-        KR_TRY(launch_proj(EPI_QKV, a, maxT, e, st));
+        KR_TRY(launch_proj(rot ? EPI_QKV_ROT : EPI_QKV, a, maxT, e, st));
         {
             const int cap = (int)round_up(S, 32);
             const bool bias = e->bias_tab != nullptr;      // an MPNet handle: the instantiations with the relative attention bias

@@ -35,9 +35,44 @@ struct ProjArgs {
     int ant;  // activation loads non-temporal (FF2's h: launch_proj)
     int nt;   // epilogue stores non-temporal (large launches: the output is consumed from HBM by the next kernel, keep it out of L2) or plain
               // (small launches: the whole output fits in L2 / Infinity Cache, the next kernel reads it from there)
+    // EPI_QKV_ROT (NomicBert handles): cos / sin tables [max_pos][dh / 2] fp32, the position every token row is rotated by (k_rot_pos), the head width (32 or 64)
+    const float* rot_cos; const float* rot_sin; const int* tpos; int max_pos; int dh;
 };
 
-enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2 };
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4 };
+
+// The two epilogues of NomicBert handles combine feature pairs: a rotary pair (j, j + d_h / 2) of q or k, or gate and up of one intermediate feature.  The
+// packed weights are laid out (tile_pair_row, encoder_rows.hpp) so that on EVERY main loop both partners sit in one 32x32 accumulator tile, column cc < 16 with
+// cc + 16: in the swapped layout that is register r with register r + 8 of the same lane.  No cross-lane traffic, and the skinny loop's one-tile waves work too.
+//   EPI_QKV_ROT: tile columns 0..15 are the head's features jb .. jb + 15 and columns 16..31 their partners jb + d_h / 2 ..; jb = 0 for 32-wide heads (a tile is
+//   a head) and 0 / 16 for the even / odd tile of a 64-wide head.  q and k are STORED in that order (a 64-wide head as 0..15, 32..47, 16..31, 48..63): the
+//   attention kernels only ever dot q with k over a head, and both carry the same order.
+__device__ __forceinline__ int rot_jbase(int dh, int f) { return dh == 64 ? ((f >> 5) & 1) << 4 : 0; }
+
+// x'[j] = x[j] cos - x[j + d_h/2] sin,  x'[j + d_h/2] = x[j + d_h/2] cos + x[j] sin  (HF apply_rotary_pos_emb, NeoX pairing), fp32, on one tile of one lane:
+// cs / sn point at the lane's token row of the tables, at jb + 4 h
+__device__ __forceinline__ void rotate_tile(f32x16& v, const float* __restrict__ cs, const float* __restrict__ sn) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const f32x4 c = *reinterpret_cast<const f32x4*>(cs + 8 * g), s = *reinterpret_cast<const f32x4*>(sn + 8 * g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a = v[4 * g + i], b = v[4 * g + 8 + i];
+            v[4 * g + i] = a * c[i] - b * s[i];
+            v[4 * g + 8 + i] = b * c[i] + a * s[i];
+        }
+    }
+}
+// the table row of token t: its column relative to its sequence's first row (k_rot_pos).  Rows past the packed total hold none (partial last tile): row 0
+__device__ __forceinline__ int64_t rot_row(const ProjArgs& a, int64_t t) {
+    const int p = a.tpos[t];
+    return (int64_t)((unsigned)p < (unsigned)a.max_pos ? p : 0) * (a.dh >> 1);
+}
+
+// silu(g) u = g u / (1 + exp(-g)) in fp32: one v_exp_f32 and one v_rcp_f32 per element (exp overflows to +inf for g < -88: the quotient is then -0)
+__device__ __forceinline__ float silu_mul(float g, float u) {
+    return g * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f)) * u;
+}
 
 // erf-GELU x Phi(x) = max(x, 0) - 0.5 |x| erfc(|x| / sqrt 2), with erfc(a / sqrt 2) = 2^-Q(a), Q(a) = a (c1 + c2 a + c3 a^2 + c4 a^3 + c5 a^4) a weighted
 // minimax fit of -log2 erfc on [0, 8] (weight a erfc(a / sqrt 2) = the sensitivity of the result; fitted offline, c5 > 0 so Q keeps growing and the
@@ -110,6 +145,44 @@ __device__ __forceinline__ void store_rows_bf16(AccTile<Shape>& acc, char* stage
     }
 }
 
+// EPI_SWIGLU: the wave's 64 GEMM columns are 2 tiles of (16 gate | 16 up) = 32 consecutive intermediate features: out[token, col0 + ni*16 + 8g + 4h ..] =
+// silu(gate) * up from registers 4g.. and 4g + 8.. (g < 2).  Staged like store_rows_bf16, as bf16 [32 tokens][64 B] (16-B chunk index XOR (token >> 2) & 3: 2-way
+// conflicts), read back 16 B per lane: every global store instruction writes sixteen whole aligned 64-B runs.  Same software pipeline over the mi blocks.
+template <class Shape, bool NT>
+__device__ __forceinline__ void store_rows_gated(AccTile<Shape>& acc, char* stage, uint16_t* __restrict__ out, int64_t ld, int64_t row0, int col0) {
+    static_assert(Shape::TN == 2, "stage geometry assumes 64 GEMM columns per wave");
+    const int c = acc.lane & 31, h = acc.lane >> 5;
+    const int r4 = acc.lane >> 2, ch = acc.lane & 3;
+    const char* st_rd = stage + r4 * 64 + ((ch ^ ((r4 >> 2) & 3)) << 4);
+    uint16_t* g_base = out + (row0 + r4) * ld + col0 + ch * 8;
+    uint4 d[2][2];
+#pragma unroll
+    for (int mi = 0; mi <= Shape::TM; ++mi) {
+        if (mi < Shape::TM) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const f32x16& v = acc.v[mi][ni];
+                    uint2 w;
+                    w.x = pack_bf16x2(silu_mul(v[4 * g], v[4 * g + 8]), silu_mul(v[4 * g + 1], v[4 * g + 9]));
+                    w.y = pack_bf16x2(silu_mul(v[4 * g + 2], v[4 * g + 10]), silu_mul(v[4 * g + 3], v[4 * g + 11]));
+                    *reinterpret_cast<uint2*>(stage + c * 64 + (((ni * 2 + g) ^ ((c >> 2) & 3)) << 4) + h * 8) = w;
+                }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) d[mi & 1][p] = *reinterpret_cast<const uint4*>(st_rd + p * 16 * 64);
+        }
+        if (mi > 0) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {  // (row >> 2) & 3 == (lane >> 4) & 3 for both p: one lane-dependent LDS / global base (16 rows per store)
+                u32x4_t* dst = reinterpret_cast<u32x4_t*>(g_base + (int64_t)((mi - 1) * 32 + p * 16) * ld);
+                if constexpr (NT) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, d[(mi - 1) & 1][p]), dst);
+                else *dst = __builtin_bit_cast(u32x4_t, d[(mi - 1) & 1][p]);
+            }
+        }
+    }
+}
+
 // V^T[feature, token]: each 32x32 tile is staged as [32 features][32 tokens] (80-B rows), lanes = consecutive tokens of a feature row,
 // read back 16 B per lane: a store instruction writes 64-B runs of sixteen V^T rows.
 template <class Shape, bool NT>
@@ -145,6 +218,8 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
 //   EPI_QKV:   F = 3H: features [0,H) -> q (bias, log2(e) / sqrt(d_h) folded into the weights), [H,2H) -> k, [2H,3H) -> V^T (its bias lives in bo_eff)
 //   EPI_DENSE: out0[T,F] = acc as bf16 (k_ln adds the bias and the residual in fp32)
 //   EPI_GELU:  out0[T,F] = gelu(acc + bias)
+//   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV)
+//   EPI_SWIGLU:  F = 2 FF, gate | up interleaved per tile: out0[T, F / 2] = silu(gate) * up, no bias (NomicBert handles)
 template <int EPI, class ShapeE, bool NT>
 __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>& acc, int64_t m0, int64_t n0, char* stage) {
     const int64_t t0 = m0 + acc.m_wave;
@@ -155,7 +230,7 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
     if (a.epi_prio && ((a.epi_prio == 1) == (acc.m_wave >= 128))) __builtin_amdgcn_s_setprio(1);
     const int h = acc.lane >> 5;
     f32x4 b[2][4];                                // bias of the lane's 32 features: (ni, g) -> features ni*32 + 8g + 4h .. +3
-    if constexpr (EPI != EPI_DENSE) {
+    if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -169,6 +244,37 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H,
                                     [&](f32x4 v, int mi, int ni, int g) { return v + b[ni][g]; });
         }
+    } else if constexpr (EPI == EPI_QKV_ROT) {
+        const int region = f0 / a.H;
+        if (region == 2) {
+            store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - 2 * a.H);
+        } else {
+            // the rotation rides in store_rows_bf16's map: the table rows of ONE mi block are live at a time (requested at its first call; all of them up front
+            // left the 256x256 tile's 128 accumulator registers no room), the token columns of all blocks are fetched before the first
+            int64_t row[ShapeE::TM];
+#pragma unroll
+            for (int mi = 0; mi < ShapeE::TM; ++mi) row[mi] = rot_row(a, t0 + mi * 32 + (acc.lane & 31)) + 4 * h;
+            const int jb1 = rot_jbase(a.dh, f0 + 32);     // f0 % 64 == 0: tile ni = 0 starts at 0
+            f32x4 cs[2][2], sn[2][2];
+            store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H, [&](f32x4 v, int mi, int ni, int g) {
+                if (ni == 0 && g == 0) {
+#pragma unroll
+                    for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                        for (int g2 = 0; g2 < 2; ++g2) {
+                            const int64_t o = row[mi] + (n2 ? jb1 : 0) + 8 * g2;
+                            cs[n2][g2] = *reinterpret_cast<const f32x4*>(a.rot_cos + o);
+                            sn[n2][g2] = *reinterpret_cast<const f32x4*>(a.rot_sin + o);
+                        }
+                }
+                // v = registers 4g ..: the first halves (g < 2) take - partner * sin, the second halves + partner * sin (see rotate_tile)
+                const int gp = g ^ 2;
+                const f32x4 o = {acc.v[mi][ni][4 * gp], acc.v[mi][ni][4 * gp + 1], acc.v[mi][ni][4 * gp + 2], acc.v[mi][ni][4 * gp + 3]};
+                return g < 2 ? v * cs[ni][g & 1] - o * sn[ni][g & 1] : v * cs[ni][g & 1] + o * sn[ni][g & 1];
+            });
+        }
+    } else if constexpr (EPI == EPI_SWIGLU) {
+        store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1);
     } else if constexpr (EPI == EPI_DENSE) {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int, int, int) { return v; });   // the bias is added in k_ln (fp32)
     } else {
@@ -228,7 +334,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
     f32x4 bias4[4];                                       // multiplying waves: the bias of the lane's 16 features, requested before the main loop
     gemm_nt_skinny<ET, RING, WM, WN, true>(a.X, a.ldx, a.Tp, m0, a.W, a.K, a.F, n0, a.K, smem,
         [&](int64_t, int64_t f0) {
-            if constexpr (EPI != EPI_DENSE) {
+            if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {
                 const int h = (threadIdx.x & 63) >> 5;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) bias4[g] = *reinterpret_cast<const f32x4*>(a.bias + f0 + 8 * g + 4 * h);   // QKV: the V third's slots are never used
@@ -236,18 +342,35 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         },
         [&](AccTile<ShapeSkinny>& acc, int64_t t0, int64_t f0) {
         const int c = acc.lane & 31, h = acc.lane >> 5;
+        if constexpr (EPI == EPI_SWIGLU) {                // the tile's 16 features: 8-byte row stores of silu(gate) * up
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                const f32x16& v = acc.v[0][0];
+                uint2 w;
+                w.x = pack_bf16x2(silu_mul(v[4 * g], v[4 * g + 8]), silu_mul(v[4 * g + 1], v[4 * g + 9]));
+                w.y = pack_bf16x2(silu_mul(v[4 * g + 2], v[4 * g + 10]), silu_mul(v[4 * g + 3], v[4 * g + 11]));
+                *reinterpret_cast<uint2*>(a.out0 + (t0 + c) * a.ldo + ((int)f0 >> 1) + 8 * g + 4 * h) = w;
+            }
+            return;
+        }
+        if constexpr (EPI == EPI_QKV_ROT) {
+            if ((int)f0 < 2 * a.H) {                      // q and k: rotated in place, then stored like EPI_QKV's
+                const int64_t o = rot_row(a, t0 + c) + 4 * h + rot_jbase(a.dh, (int)f0);
+                rotate_tile(acc.v[0][0], a.rot_cos + o, a.rot_sin + o);
+            }
+        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             f32x4 v = {acc.v[0][0][4 * g], acc.v[0][0][4 * g + 1], acc.v[0][0][4 * g + 2], acc.v[0][0][4 * g + 3]};
             const int f = (int)f0 + 8 * g + 4 * h;        // first of the lane's 4 consecutive features
-            if constexpr (EPI == EPI_QKV) {
+            if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_ROT) {
                 const int region = (int)f0 / a.H;
                 if (region == 2) {                        // V^T [feature, token]; its bias lives in bo_eff
 #pragma unroll
                     for (int j = 0; j < 4; ++j) a.outT[(int64_t)(f - 2 * a.H + j) * a.ldT + t0 + c] = ET::from_f32(v[j]);
                     continue;
                 }
-                v = v + bias4[g];
+                if constexpr (EPI == EPI_QKV) v = v + bias4[g];
                 uint2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
                 *reinterpret_cast<uint2*>((region ? a.out1 : a.out0) + (t0 + c) * a.H + (f - region * a.H)) = w;
             } else {

@@ -29,6 +29,22 @@ __global__ void k_f32_to_bf16(const float* __restrict__ src, uint16_t* __restric
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = ET::from_f32(src[i] * scale);
 }
+// the same conversion of a [rows, cols] matrix whose rows change place (NomicBert handles: every 32-column MFMA tile of a projection holds 16 features and
+// their 16 partners, so that the rotary / gated epilogues combine register r with r + 8 of ONE tile on every main loop, see encoder_proj.hpp):
+//   ROWS_HEAD64:  q / k with 64-wide heads: the four 16-row blocks of a head in the order 0, 2, 1, 3 (feature j next to its rotary partner j + 32)
+//   ROWS_GATE / ROWS_UP:  gate_proj / up_proj into one [2 FF, H] matrix: tile t = gate rows 16 t .. 16 t + 15, then the up rows of the same features
+enum { ROWS_HEAD64 = 0, ROWS_GATE = 1, ROWS_UP = 2 };
+__host__ __device__ inline int64_t tile_pair_row(int64_t r, int mode) {
+    if (mode == ROWS_HEAD64) {
+        const int64_t b = (r >> 4) & 3;
+        return (r & ~(int64_t)63) + ((((b & 1) << 1) | (b >> 1)) << 4) + (r & 15);
+    }
+    return ((r >> 4) << 5) + (mode == ROWS_UP ? 16 : 0) + (r & 15);
+}
+__global__ void k_f32_to_bf16_rows(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n, int cols, float scale, int mode) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[tile_pair_row(i / cols, mode) * cols + i % cols] = ET::from_f32(src[i] * scale);
+}
 __global__ void k_scale_copy(const float* __restrict__ src, float* __restrict__ dst, int64_t n, float scale) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i] * scale;
@@ -168,6 +184,19 @@ __global__ __launch_bounds__(256) void k_embed_ln(const int* __restrict__ tok_id
         }
     }
     ln_row_store(v, H, lane, g, bta, eps, xlo ? xlo + t * H : nullptr, xb + t * H);
+}
+
+// Rotary handles: the position a token is rotated by = its column minus the smallest column among its sequence's rows (attended rows are packed in column
+// order; the query-only CLS row of a masked column 0 has column 0 and sits last).  Scores depend on column differences only, so the shift changes nothing in
+// exact arithmetic; in 16-bit storage it makes a sequence's rows the same bits wherever it stands in the padded batch, and keeps the angles small.  One wave per
+// sequence; the alignment rows behind a sequence get 0.
+__global__ __launch_bounds__(64) void k_rot_pos(const int* __restrict__ seq_off, const int* __restrict__ seq_nq, int align, const int* __restrict__ tok_pos,
+                                                 int* __restrict__ rpos) {
+    const int o = seq_off[blockIdx.x], n = seq_nq[blockIdx.x];
+    if (n <= 0) return;
+    const int first = min(tok_pos[o], tok_pos[o + n - 1]);
+    const int padded = (n + align - 1) & ~(align - 1);
+    for (int i = threadIdx.x; i < padded; i += 64) rpos[o + i] = i < n ? tok_pos[o + i] - first : 0;
 }
 
 // LayerNorm(y + bias + residual) with 16-byte accesses: a lane owns 8 consecutive elements per 512-element step (one global_load_dwordx4 per tensor and step:

@@ -24,6 +24,12 @@ MPNet checkpoints (``model_type`` mpnet: all-mpnet-base-v2, multi-qa-mpnet-base-
 names, no token types, fairseq's position rule with padding index 1, and one learned bias per (head, bucket of the column distance) added to every attention
 score — a table the attention kernels read (``encoder.relative_attention_bias.weight``).  ``MPNetE5Encoder`` / ``MPNetBGEEncoder`` are the twins over
 ``transformers.MPNetModel``; ``from_pretrained`` of the two registry classes dispatches to them as well.
+
+NomicBert checkpoints (``model_type`` nomic_bert: nomic-embed-text-v1 / -v1.5 and their fine-tunes): BERT's post-LN stack without a position table — q and k
+of every head are rotated by the token's column (rotary embeddings, NeoX pairing), inside the QKV projection's epilogue — with a gated MLP
+``down(silu(gate(x)) * up(x))`` (gate | up run as one projection whose epilogue writes the product), no linear biases, and state-dict names of its own.  The
+handle learns the frequencies through ``config.rotary_inv_freq`` (HF's ``rotary_emb.inv_freq``, so every static rope variant of HF is covered).
+``NomicBertE5Encoder`` / ``NomicBertBGEEncoder`` are the twins over ``transformers.NomicBertModel``, reached through the same dispatch.
 """
 from __future__ import annotations
 
@@ -33,7 +39,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, MPNetModel, PretrainedConfig, XLMRobertaModel
+from transformers import BertModel, MPNetModel, NomicBertModel, PretrainedConfig, XLMRobertaModel
 
 from .. import _lib
 
@@ -42,6 +48,7 @@ POOL_MEAN, POOL_CLS = 0, 1
 ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
 MPNET_TYPE = "mpnet"
 MPNET_PADDING_IDX = 1    # MPNetEmbeddings.padding_idx: a class constant of HF's implementation, not config.pad_token_id
+NOMIC_TYPE = "nomic_bert"
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
 
 
@@ -58,8 +65,10 @@ class HipBertForward:
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
         low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it)."""
         lib = _lib.load()
-        if getattr(config, "hidden_act", "gelu") != "gelu":
-            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only")
+        self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
+        inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
+        if not self.is_nomic and getattr(config, "hidden_act", "gelu") != "gelu":
+            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
         if getattr(config, "position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only absolute position embeddings are implemented")
         self.is_mpnet = getattr(config, "model_type", "bert") == MPNET_TYPE
@@ -89,6 +98,25 @@ class HipBertForward:
             v = C.c_float(float(P))
             _lib.check(lib.kr_encoder_load_weight(h, b"config.position_padding_idx", C.addressof(v), 1))
             self.position_padding_idx = int(P)
+        # rotary positions travel the same way ("config.rotary_inv_freq", d_h / 2 values) and make the handle a NomicBert handle for life
+        if inv_freq is not None:
+            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", inv_freq.data_ptr(), inv_freq.numel()))
+
+    @staticmethod
+    def _nomic_inv_freq(config) -> Tensor:
+        """``rotary_emb.inv_freq`` of a NomicBert config, from HF's own ``NomicBertRotaryEmbedding`` built on the CPU (whatever static rope type the config
+        names); ``NotImplementedError`` naming the field for what the kernels do not compute."""
+        from transformers.models.nomic_bert.modeling_nomic_bert import NomicBertRotaryEmbedding
+        if getattr(config, "hidden_act", "silu") != "silu":
+            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the gated MLP of a {NOMIC_TYPE} handle implements silu only")
+        d_h = config.hidden_size // config.num_attention_heads
+        if (getattr(config, "head_dim", None) or d_h) != d_h:
+            raise NotImplementedError(f"head_dim={config.head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+        rope = NomicBertRotaryEmbedding(config)
+        if float(rope.attention_scaling) != 1.0:
+            raise NotImplementedError(f"attention_scaling={float(rope.attention_scaling)} (rope_type {rope.rope_type!r}): only rope variants with attention_scaling 1.0 "
+                                      "are implemented")
+        return rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -348,6 +376,7 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _hf_base = BertModel
     _roberta_twin = None             # the same encoder over XLMRobertaModel (set below)
     _mpnet_twin = None               # ... and over MPNetModel
+    _nomic_twin = None               # ... and over NomicBertModel
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -367,6 +396,9 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
         if model_type == MPNET_TYPE:
             # MPNet's layer names differ: loaded into this class every layer would stay randomly initialised, with warnings only
             return cls._mpnet_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type == NOMIC_TYPE:
+            # other layer names, no position table, a gated MLP: nothing of it fits BertModel
+            return cls._nomic_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -376,6 +408,10 @@ class _HipXLMRSentenceEncoder(_HipSentenceMixin, XLMRobertaModel):
 
 class _HipMPNetSentenceEncoder(_HipSentenceMixin, MPNetModel):
     _hf_base = MPNetModel
+
+
+class _HipNomicSentenceEncoder(_HipSentenceMixin, NomicBertModel):
+    _hf_base = NomicBertModel
 
 
 class E5Encoder(_HipSentenceEncoder):
@@ -408,7 +444,31 @@ class MPNetBGEEncoder(_HipMPNetSentenceEncoder):
     _pool = POOL_CLS
 
 
+class NomicBertE5Encoder(_HipNomicSentenceEncoder):
+    """NomicBertModel -> masked mean -> L2 normalise (nomic-ai/nomic-embed-text-v1, -v1.5)"""
+    _pool = POOL_MEAN
+
+
+class NomicBertBGEEncoder(_HipNomicSentenceEncoder):
+    """NomicBertModel -> [:, 0] -> L2 normalise"""
+    _pool = POOL_CLS
+
+
 E5Encoder._roberta_twin = XLMRobertaE5Encoder
 BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
 E5Encoder._mpnet_twin = MPNetE5Encoder
 BGEEncoder._mpnet_twin = MPNetBGEEncoder
+E5Encoder._nomic_twin = NomicBertE5Encoder
+BGEEncoder._nomic_twin = NomicBertBGEEncoder
+
+
+def _register_nomic_checkpoint_format() -> None:
+    """nomic-embed checkpoints are stored in their original layout (``encoder.layers.N.attn.Wqkv``, ``mlp.fc11`` / ``fc12`` / ``fc2``, ``norm1`` / ``norm2``,
+    ``emb_ln``); transformers converts it on load and back on save through a mapping it looks up by class name or ``model_type`` — but not for classes
+    defined outside the library, unless the mapping is registered for them.  Without this the twins would load every layer as missing."""
+    from transformers.conversion_mapping import get_checkpoint_conversion_mapping, register_checkpoint_conversion_mapping
+    for cls in (NomicBertE5Encoder, NomicBertBGEEncoder):
+        register_checkpoint_conversion_mapping(cls.__name__, get_checkpoint_conversion_mapping(NOMIC_TYPE), overwrite=True)
+
+
+_register_nomic_checkpoint_format()

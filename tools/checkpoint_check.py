@@ -5,7 +5,8 @@ tolerance on YOUR weights, and could a cheaper mode be used?
     python tools/checkpoint_check.py <hf_dir> [--texts file.txt] [--n 16] [--max-length 128] [--pool mean|cls] [--emulate] [--json out.json]
 
 <hf_dir> is any HF BERT-family checkpoint directory (config.json + weights; e5-large-v2 / bge-large-en: retriever/e5.py:18-19 of the reference) or a
-MPNet one (model_type mpnet: all-mpnet-base-v2, multi-qa-mpnet-*; reference MPNetModel in fp32, GPU only) or a
+MPNet one (model_type mpnet: all-mpnet-base-v2, multi-qa-mpnet-*; reference MPNetModel in fp32, GPU only), a NomicBert one (model_type nomic_bert:
+nomic-embed-text-v1 / -v1.5; reference NomicBertModel in fp32, GPU only: rotary positions and the gated MLP are not in the torch emulation) or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -92,7 +93,15 @@ def reference_and_stats(model, batches, pool, dev):
                 stats[li][key].append(t.detach()[cur["mask"]].abs().float().flatten().cpu())
             stats[li]["max16"] = max(stats[li]["max16"], float(t.detach()[cur["mask"]].abs().max()))
         return fn
-    for li, layer in enumerate(model.encoder.layer):
+    nomic = hasattr(model, "layers")                   # NomicBertModel: layers.N.{self_attn, mlp, post_attention_layernorm, post_mlp_layernorm}
+    for li, layer in enumerate(model.layers if nomic else model.encoder.layer):
+        if nomic:
+            att, mlp = layer.self_attn, layer.mlp      # q / k before the rotation (a rotation keeps their size); "h" = what the gated projection stores
+            for key, mod in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("y1", att.o_proj), ("ln1", layer.post_attention_layernorm),
+                             ("h", mlp.down_proj), ("y2", mlp.down_proj), ("ln2", layer.post_mlp_layernorm)):
+                hooks.append((mod.register_forward_pre_hook(lambda _m, inp, f=grab(li, key): f(_m, inp, inp[0])) if key == "h" else
+                              mod.register_forward_hook(grab(li, key))))
+            continue
         att = layer.attention
         if hasattr(att, "attn"):                       # MPNetModel: q / k / v / o live in attention.attn (whose output is already o's), the LayerNorm in attention
             mods = (("q", att.attn.q), ("k", att.attn.k), ("v", att.attn.v), ("y1", att.attn.o), ("ln1", att.LayerNorm))
@@ -144,17 +153,17 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
-    from kirag_amd.retriever.encoders import MPNET_TYPE, ROBERTA_TYPES
-    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE) + ROBERTA_TYPES:
+    from kirag_amd.retriever.encoders import MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
+    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3) and MPNet (all-mpnet-base-v2)")
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2) and NomicBert (nomic-embed-text-v1 / -v1.5)")
     model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
     return check_model(model, args, hf_dir)
 
 
 def check_model(model, args, hf_dir="(in-memory model)"):
     """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
-    from kirag_amd.retriever.encoders import MPNET_PADDING_IDX, MPNET_TYPE, ROBERTA_TYPES
+    from kirag_amd.retriever.encoders import MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
     mpnet = getattr(cfg, "model_type", "bert") == MPNET_TYPE
@@ -162,6 +171,8 @@ def check_model(model, args, hf_dir="(in-memory model)"):
     if roberta and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} follows fairseq's position rule" + (" and adds a relative attention bias" if mpnet else "") +
                          ", which the torch emulation does not implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") == NOMIC_TYPE and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has rotary positions and a gated MLP, which the torch emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
     batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|mpnet-base|mpnet-base-nobias ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base ...] [--pool mean|cls] [--hf-fp16]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -19,12 +19,18 @@ PEAK_MFMA_DENSE_16BIT = 2.5e15   # MI355X_MICROARCH.md: bf16/f16 dense MFMA peak
 XLMR_LARGE = dict(BS.E5_LARGE, vocab_size=250002, max_position_embeddings=514, type_vocab_size=1, layer_norm_eps=1e-5, model_type="xlm-roberta", pad_token_id=1)
 XLMR_BASE = dict(XLMR_LARGE, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072)
 BGE_M3 = dict(XLMR_LARGE, max_position_embeddings=8194)
+XLMR_BASE_8K = dict(XLMR_BASE, max_position_embeddings=8194)     # xlmr-base with bge-m3's position rows: the yardstick of nomic-base beyond 512 tokens
 # MPNet (all-mpnet-base-v2): the xlmr-base stack at vocab 30527 + the relative attention bias inside the attention kernels; mpnet-base-nobias is the same
 # shape as a RoBERTa handle (identical GEMMs, attention without the bias): what the bias costs is the difference of the two
 MPNET_BASE = dict(XLMR_BASE, vocab_size=30527, model_type="mpnet", relative_attention_num_buckets=32)
 MPNET_BASE_NOBIAS = dict(XLMR_BASE, vocab_size=30527)
+# NomicBert (nomic-embed-text-v1 / -v1.5): H and heads of xlmr-base, no position table (rotary q / k in the QKV epilogue), a gated MLP (gate | up as one
+# projection of 2 FF columns + the SwiGLU epilogue): 32 H^2 projection FLOPs per token and layer against 24 H^2
+NOMIC_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, vocab_size=30528, max_position_embeddings=8192,
+                  type_vocab_size=2, layer_norm_eps=1e-12, hidden_act="silu", model_type="nomic_bert", head_dim=64,
+                  rope_parameters={"rope_theta": 1000.0, "rope_type": "default"})
 SHAPES = dict(BS.ENCODER_SHAPES, **{"xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
-                                    "mpnet-base-nobias": MPNET_BASE_NOBIAS})
+                                    "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
 ap.add_argument("n", type=int, nargs="?", default=1024)
@@ -55,6 +61,8 @@ def hf_classes(cfg):
     """(config class, model class, sentence-encoder module) of a shape: the RoBERTa family by its model_type"""
     import transformers as T
     from kirag_amd.retriever import encoders as ENC
+    if cfg.get("model_type") == ENC.NOMIC_TYPE:
+        return T.NomicBertConfig, T.NomicBertModel, (ENC.NomicBertE5Encoder if args.pool == "mean" else ENC.NomicBertBGEEncoder)
     if cfg.get("model_type") == ENC.MPNET_TYPE:
         return T.MPNetConfig, T.MPNetModel, (ENC.MPNetE5Encoder if args.pool == "mean" else ENC.MPNetBGEEncoder)
     if cfg.get("model_type") in ENC.ROBERTA_TYPES:
@@ -63,8 +71,9 @@ def hf_classes(cfg):
 
 
 def make_encoder(cfg):
-    """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize)"""
-    if cfg.get("model_type") != "mpnet":
+    """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
+    shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw)"""
+    if cfg.get("model_type") not in ("mpnet", "nomic_bert"):
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
     from kirag_amd.retriever.encoders import HipBertForward
@@ -72,7 +81,23 @@ def make_encoder(cfg):
     enc = HipBertForward(ns, 0)
     state = dict(BS.synthetic_state(ns, dev, 0))
     g = torch.Generator(device=dev); g.manual_seed(977)
-    state["encoder.relative_attention_bias.weight"] = torch.randn(32, cfg["num_attention_heads"], generator=g, device=dev)
+    if cfg["model_type"] == "nomic_bert":
+        names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),
+                 ("attention.output.dense.", "self_attn.o_proj."), ("attention.output.LayerNorm.", "post_attention_layernorm."),
+                 ("intermediate.dense.", "mlp.gate_proj."), ("output.dense.", "mlp.down_proj."), ("output.LayerNorm.", "post_mlp_layernorm."))
+        renamed = {}
+        for k, v in state.items():
+            if "position_embeddings" in k or (k.endswith(".bias") and "LayerNorm" not in k):
+                continue
+            k = k.replace("encoder.layer.", "layers.")
+            for a, b in names:
+                k = k.replace(a, b)
+            renamed[k] = v
+            if "gate_proj" in k:
+                renamed[k.replace("gate_proj", "up_proj")] = 0.02 * torch.randn(v.shape, generator=g, device=dev)
+        state = renamed
+    else:
+        state["encoder.relative_attention_bias.weight"] = torch.randn(32, cfg["num_attention_heads"], generator=g, device=dev)
     enc.load_state(state)
     enc.cfg = ns
     return enc
@@ -80,7 +105,7 @@ def make_encoder(cfg):
 
 def first_forward(shape, cfg, ids, mask):
     conf_cls, _, mod_cls = hf_classes(cfg)
-    m = mod_cls(conf_cls(**{k: v for k, v in cfg.items() if k not in ("hidden_act", "model_type")}), add_pooling_layer=False).to(dev).eval()
+    m = mod_cls(conf_cls(**{k: v for k, v in cfg.items() if k != "model_type" and (k != "hidden_act" or v != "gelu")}), add_pooling_layer=False).to(dev).eval()
 
     def once():
         torch.cuda.synchronize()
@@ -107,6 +132,8 @@ for shape in args.shape or ["e5-large"]:
         continue
     enc = make_encoder(cfg)
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
+    if cfg.get("model_type") == "nomic_bert":      # the third intermediate matrix: + 8 H^2 per token and layer (FF = 4 H)
+        fl += float(mask.sum()) * cfg["num_hidden_layers"] * 8.0 * cfg["hidden_size"] ** 2
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
           f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
@@ -114,7 +141,7 @@ for shape in args.shape or ["e5-large"]:
     del enc
     if args.hf_fp16:
         conf_cls, model_cls, _ = hf_classes(cfg)
-        m = model_cls(conf_cls(**{k: v for k, v in cfg.items() if k not in ("hidden_act", "model_type")}), add_pooling_layer=False).to(dev).half().eval()
+        m = model_cls(conf_cls(**{k: v for k, v in cfg.items() if k != "model_type" and (k != "hidden_act" or v != "gelu")}), add_pooling_layer=False).to(dev).half().eval()
         with torch.no_grad():
             dt = timed(lambda: m(input_ids=ids, attention_mask=mask).last_hidden_state, args.reps)
         print(f"{shape} HF {model_cls.__name__} fp16 (yardstick) n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s", flush=True)
