@@ -272,6 +272,26 @@ void kr_encoder_destroy(kr_encoder* enc);
  *       q_proj / k_proj / gate_proj / up_proj must come under these names (their packed copies have another row order) and have no bias; the biases of
  *       v / o / down (BERT's names) are zero unless loaded.  A handle without the setting refuses these names at finalize.  It combines with neither
  *       "config.position_padding_idx" nor MPNet's bias tensor.
+ *   "config.local_attention_layers": data = one float per layer, 0 or 1 (1 = sliding-window attention).  Loading it before the handle's first finalize makes
+ *   the handle a ModernBert handle for life (transformers.ModernBertModel: gte-modernbert-base, modernbert-embed, granite-embedding-english-r2); it needs
+ *   "config.rotary_inv_freq" (the frequencies of the global layers; all layers when none is local) and, when any flag is 1,
+ *   "config.rotary_inv_freq_local": data = d_h / 2 floats, the frequencies of the local layers (a second pair of cos / sin tables), and
+ *   "config.attention_half_window": data = ONE float holding an integer w >= 1: a local layer admits key column j for query column i iff |i - j| <= w
+ *   (HF: config.sliding_window = local_attention / 2, inclusive), on top of the padding mask; columns are those of the padded [B, S] batch, so with holes in
+ *   the mask the distance counts columns, not attended tokens.
+ *   All three follow the rule of the other settings: before the first finalize; later the same values are a no-op, anything else KR_EINVAL.
+ *   kr_encoder_finalize refuses (KR_EINVAL, naming the setting) a flag count other than cfg.layers, local layers without frequencies or half-window, the
+ *   flags without "config.rotary_inv_freq", the two local settings without the flags, any of them next to "config.position_padding_idx" or MPNet's bias
+ *   tensor, ModernBert's tensor names on a handle of another kind and other names on this one.  On such a handle
+ *     - the stack is PRE-LN: x += attn.Wo . attention(rot(attn.Wqkv . attn_norm_l(x))), x += mlp.Wo . (erf_gelu(input) * gate) with
+ *       input | gate = mlp.Wi . mlp_norm_l(x), attn_norm_0 = identity, output = final_norm(x); the embedding is LayerNorm(tok_embeddings[id]) (the token-type
+ *       table is one row: load zeros under BERT's name "embeddings.token_type_embeddings.weight");
+ *     - ModernBertModel's state dict loads unchanged: "embeddings.tok_embeddings.weight", "embeddings.norm.*", "layers.N.attn_norm.*" (N >= 1),
+ *       "layers.N.attn.Wqkv.weight" [3H, H], "layers.N.attn.Wo.*", "layers.N.mlp_norm.*", "layers.N.mlp.Wi.*" [2 FF, H], "layers.N.mlp.Wo.*" [H, FF],
+ *       "final_norm.*".  LayerNorm biases and the biases of attn.Wqkv [3H] / attn.Wo / mlp.Wi / mlp.Wo are zero unless loaded (the q and k thirds of
+ *       attn.Wqkv.bias are added before the rotation, as HF rotates Wqkv x + b).  cfg.intermediate must be a multiple of 128 like everywhere (the Python layer zero-pads ModernBERT-large's 2624);
+ *     - a query whose window holds no attended column (the CLS row of a MASKED column 0 whose sequence starts beyond column w) gets a zero attention
+ *       output in the local layers.
  * MPNetModel (all-mpnet-base-v2, multi-qa-mpnet-*): its state dict loads unchanged.  The layer names "encoder.layer.N.attention.attn.{q,k,v,o}.{weight,bias}"
  * and "encoder.layer.N.attention.LayerNorm.{weight,bias}" fill the slots of BERT's attention.self.{query,key,value} / attention.output.{dense,LayerNorm}
  * (last write wins when a caller uses both spellings for one slot).  MPNet has no token types: create the handle with type_vocab = 1 and load ONE row of

@@ -20,6 +20,11 @@
 // NomicBert handles (config.rotary_inv_freq, see Encoder::inv_freq): no position table, q and k rotated by the token's column in the QKV epilogue (EPI_QKV_ROT),
 // [gate | up] x as one GEMM whose epilogue writes silu(gate) * up (EPI_SWIGLU) in place of W1 x + b -> erf-GELU; everything else as above.
 //
+// ModernBert handles (config.local_attention_layers, see Encoder::local_layers): a PRE-LN stack on the same launches.  The residual stream r (rb + rlo) is kept
+// apart from the normalised operand xb; each of the two LayerNorm launches of a layer is k_ln16_pre: r += y + bias, store r, xb = LN_next(r), LN_next = this
+// layer's mlp_norm, then the next layer's attn_norm (final_norm behind the last layer).  Rotary q / k as above with one table per layer type, the MLP
+// Wo (erf_gelu(input) * gate) as one [2 FF, H] projection (EPI_GEGLU), and in the layers flagged local a sliding window over the key columns (k_attn_*<.., WIN>).
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -42,8 +47,10 @@ struct LayerW {
     uint16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;   // bf16 [out, in]
     float *bqkv = nullptr, *bo = nullptr, *bo_eff = nullptr, *b1 = nullptr, *b2 = nullptr;   // bo_eff = bo + Wo.bv
     float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-    // w1 is allocated by its first tensor: [FF, H] (intermediate.dense) or, gated, [2 FF, H] (NomicBert's gate_proj | up_proj, interleaved per 32-row tile)
+    // w1 is allocated by its first tensor: [FF, H] (intermediate.dense) or, gated, [2 FF, H] (NomicBert's gate_proj | up_proj, ModernBert's mlp.Wi: interleaved
+    // per 32-row tile)
     bool gated = false;
+    float* b1p = nullptr;   // ModernBert handles: the bias of the [2 FF, H] projection in its rows' order (zero unless mlp.Wi.bias was loaded)
 };
 
 // A/B switches of the projection / attention launches, read from the environment ONCE per forward (enqueue_forward), not per launch: a forward is 96
@@ -72,7 +79,7 @@ struct Encoder {
     // every hipMalloc of the handle is recorded where it is made (dmalloc) and freed by walking its list: ws_bufs = the workspace (free_ws), own_bufs = what
     // lives as long as the handle (enc_destroy)
     std::vector<void**> ws_bufs, own_bufs;
-    std::vector<uint8_t> got;     // 5 + L_COUNT * layers flags: 0 = never loaded, 1 = loaded, 2 = loaded under a NomicBert name (enc_finalize: rows in tile-pair order)
+    std::vector<uint8_t> got;     // 5 + L_COUNT * layers flags: 0 = never loaded, else the family of the name it was loaded under (FAM_*; enc_finalize: names and handle kind agree)
     bool ready = false;
     float* stage = nullptr; size_t stage_elems = 0;   // fp32 upload staging for load_weight
     // workspace
@@ -102,6 +109,16 @@ struct Encoder {
     float *rot_cos = nullptr, *rot_sin = nullptr, *pos_zero = nullptr;
     int *tok_zero = nullptr, *tok_rpos = nullptr;   // tok_rpos: the position each token is rotated by (k_rot_pos)
     bool rotary() const { return !inv_freq.empty(); }
+    // ModernBert: loading "config.local_attention_layers" (one 0 / 1 flag per layer: 1 = sliding-window attention) before the first finalize makes the handle a
+    // ModernBert handle for life (needs config.rotary_inv_freq too): pre-LN stack, ModernBert's state-dict names, GEGLU.  Local layers rotate by
+    // "config.rotary_inv_freq_local" (rot_cos_l / rot_sin_l) and admit key columns within "config.attention_half_window" of the query's.
+    std::vector<float> local_layers, inv_freq_local;
+    int half_window = 0;
+    float *rot_cos_l = nullptr, *rot_sin_l = nullptr;
+    bool modern() const { return !local_layers.empty(); }
+    bool local_layer(int li) const { return (size_t)li < local_layers.size() && local_layers[li] != 0.f; }
+    uint16_t *rb = nullptr, *c_rb = nullptr;   // the pre-LN residual stream (and its CLS-row copy): 16-bit high half
+    uint8_t *rlo = nullptr, *c_rlo = nullptr;  // ... and the low-half bytes (use_lo)
     float *out = nullptr;
     uint8_t *xlo = nullptr;    // low half of the residual stream, one byte per element (lo_encode): written by every LayerNorm with use_lo, else by the last one only
     bool use_lo = false;       // KIRAG_AMD_RESIDUAL_LO=1 at kr_encoder_create
@@ -167,7 +184,10 @@ static int ensure_ws(Encoder* e, int B, int S) {
     const int64_t capT = round_up(maxT, 256), capB = B, capBS = (int64_t)B * S;   // multiple of the 256-token tile: see k_proj
     KR_TRY(dmalloc(e->ws_bufs, &e->d_ids, capBS * 8)); KR_TRY(dmalloc(e->ws_bufs, &e->d_mask, capBS * 8)); KR_TRY(dmalloc(e->ws_bufs, &e->d_tt, capBS * 8));
     KR_TRY(dmalloc(e->ws_bufs, &e->seq_off, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_nk, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_nq, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_cls, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->seq_has0, capB * 4));
-    KR_TRY(dmalloc(e->ws_bufs, &e->tok_id, capT * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->tok_pos, capT * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->tok_type, capT * 4));
+    KR_TRY(dmalloc(e->ws_bufs, &e->tok_id, capT * 4));
+    KR_TRY(dmalloc(e->ws_bufs, &e->tok_pos, (capT + 64) * 4));    // 64 entries of slack: the window's gathered key columns are read in whole 64-key steps (attn_window_tile)
+    KR_HIP(hipMemset(e->tok_pos, 0, (size_t)(capT + 64) * 4));
+    KR_TRY(dmalloc(e->ws_bufs, &e->tok_type, capT * 4));
     if (e->pad_idx >= 0) KR_TRY(dmalloc(e->ws_bufs, &e->tok_epos, capT * 4));
     if (e->rotary()) {
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
@@ -181,10 +201,18 @@ static int ensure_ws(Encoder* e, int B, int S) {
     KR_TRY(dmalloc(e->ws_bufs, &e->vT, (size_t)H * e->ldv * 2));
     KR_HIP(hipMemset(e->vT, 0, (size_t)H * e->ldv * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->ctx, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->h, capT * FF * 2));
+    if (e->modern()) {
+        KR_TRY(dmalloc(e->ws_bufs, &e->rb, capT * H * 2));
+        if (e->use_lo) KR_TRY(dmalloc(e->ws_bufs, &e->rlo, capT * H));
+    }
     if (e->cls_shortcut) {
         const int64_t capC = round_up(capB, 256);                 // token-indexed buffers come in multiples of the 256-row tile (see k_proj)
         KR_TRY(dmalloc(e->ws_bufs, &e->c_ctx, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xb, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_y, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xlo, capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_h, capC * FF * 2));
+        if (e->modern()) {
+            KR_TRY(dmalloc(e->ws_bufs, &e->c_rb, capC * H * 2)); KR_HIP(hipMemset(e->c_rb, 0, (size_t)capC * H * 2));
+            if (e->use_lo) { KR_TRY(dmalloc(e->ws_bufs, &e->c_rlo, capC * H)); KR_HIP(hipMemset(e->c_rlo, 0x80, (size_t)capC * H)); }
+        }
         KR_HIP(hipMemset(e->c_ctx, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xb, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xlo, 0x80, (size_t)capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_off, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_nk, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_cls, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->d_B, sizeof(int)));
     }
@@ -195,13 +223,17 @@ static int ensure_ws(Encoder* e, int B, int S) {
 // tensor slot ids: 0..4 embeddings, then L_COUNT per layer (L_UW: NomicBert's up_proj, the second half of a gated intermediate projection)
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
 constexpr int T_RELBIAS = -2;          // not a slot of `got`: an optional tensor (parse_name)
+constexpr int T_WQKV = -3, T_WI = -4, T_WIB = -5, T_WQKVB = -6;   // ModernBert's fused tensors of layer `layer` (parse_name): attn.Wqkv.weight, mlp.Wi.weight, mlp.Wi.bias, attn.Wqkv.bias
+enum { FAM_BERT = 1, FAM_NOMIC = 2, FAM_MODERN = 3 };   // whose state-dict name a tensor came under
 constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says
 enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
 
-// nomic: the name is NomicBertModel's ("layers.N.self_attn.q_proj.weight", ...)
-static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& numel, bool& nomic) {
+// fam: FAM_NOMIC = the name is NomicBertModel's ("layers.N.self_attn.q_proj.weight", ...), FAM_MODERN = ModernBertModel's ("layers.N.attn.Wqkv.weight", ...);
+// layer: the layer of a fused ModernBert tensor (slot T_WQKV / T_WI / T_WIB)
+static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& numel, int& fam, int& layer) {
     std::string s(name);
-    nomic = false;
+    bool nomic = false;
+    fam = FAM_BERT; layer = -1;
     size_t p = s.find("embeddings.");
     size_t pl = s.find("encoder.layer.");
     size_t skip = strlen("encoder.layer.");
@@ -212,6 +244,13 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     }
     const int64_t H = e->cfg.hidden, FF = e->cfg.intermediate;
     if (s.find("position_ids") != std::string::npos || s.find("pooler.") != std::string::npos) { slot = -1; return 0; }
+    auto ends_with = [&](const char* t) { const size_t n = strlen(t); return s.size() >= n && s.compare(s.size() - n, n, t) == 0 && (s.size() == n || s[s.size() - n - 1] == '.'); };
+    // ModernBert: final_norm is the LayerNorm behind the last layer's MLP
+    if (ends_with("final_norm.weight") || ends_with("final_norm.bias")) {
+        fam = FAM_MODERN; numel = H;
+        slot = T_LAYER0 + (e->cfg.layers - 1) * L_COUNT + (ends_with("final_norm.weight") ? L_LN2G : L_LN2B);
+        return 0;
+    }
     {
         static const char rel[] = "encoder.relative_attention_bias.weight";
         if (s.size() >= sizeof(rel) - 1 && s.compare(s.size() - (sizeof(rel) - 1), sizeof(rel) - 1, rel) == 0) { slot = T_RELBIAS; numel = (int64_t)REL_BUCKETS * e->cfg.heads; return 0; }
@@ -238,6 +277,24 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
             {"attention.output.LayerNorm.weight", L_LN1G}, {"attention.output.LayerNorm.bias", L_LN1B},
             {"intermediate.dense.weight", L_IW}, {"intermediate.dense.bias", L_IB}, {"output.dense.weight", L_FW}, {"output.dense.bias", L_FB},
             {"output.LayerNorm.weight", L_LN2G}, {"output.LayerNorm.bias", L_LN2B}};
+        if (nomic) {
+            // ModernBert's names first.  The fused tensors have slots of their own; attn_norm of layer N is the LayerNorm behind the MLP of layer N - 1 (the
+            // launch that applies it), mlp_norm the one behind the attention output
+            static const NameId modern_tbl[] = {{"attn.Wqkv.weight", T_WQKV}, {"attn.Wqkv.bias", T_WQKVB}, {"mlp.Wi.weight", T_WI}, {"mlp.Wi.bias", T_WIB},
+                                                {"attn.Wo.weight", L_OW}, {"attn.Wo.bias", L_OB}, {"mlp_norm.weight", L_LN1G}, {"mlp_norm.bias", L_LN1B},
+                                                {"mlp.Wo.weight", L_FW}, {"mlp.Wo.bias", L_FB}, {"attn_norm.weight", L_LN2G}, {"attn_norm.bias", L_LN2B}};
+            for (const NameId& t : modern_tbl)
+                if (r == t.n) {
+                    fam = FAM_MODERN; layer = (int)l;
+                    const bool attn_norm = t.id == L_LN2G || t.id == L_LN2B;
+                    if (attn_norm && l == 0) return fail(KR_EINVAL, "'%s': attn_norm of layer 0 is the identity in ModernBert", name);
+                    slot = t.id < 0 ? t.id : T_LAYER0 + (int)(attn_norm ? l - 1 : l) * L_COUNT + t.id;
+                    numel = t.id == T_WQKV ? 3 * H * H : t.id == T_WQKVB ? 3 * H : t.id == T_WI ? 2 * H * FF : t.id == T_WIB ? 2 * FF : t.id == L_OW ? H * H
+                          : t.id == L_FW ? H * FF : H;
+                    return 0;
+                }
+            fam = FAM_NOMIC;
+        }
         const NameId* tbl = nomic ? nomic_tbl : bert_tbl;
         const size_t tbl_n = nomic ? sizeof(nomic_tbl) / sizeof(nomic_tbl[0]) : sizeof(bert_tbl) / sizeof(bert_tbl[0]);
         for (size_t ti = 0; ti < tbl_n; ++ti)
@@ -255,6 +312,9 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     }
     if (p != std::string::npos) {
         const std::string r = s.substr(p + strlen("embeddings."));
+        if (r == "tok_embeddings.weight") { fam = FAM_MODERN; slot = T_WORD; numel = (int64_t)e->cfg.vocab * H; return 0; }
+        if (r == "norm.weight") { fam = FAM_MODERN; slot = T_ELNG; numel = H; return 0; }
+        if (r == "norm.bias") { fam = FAM_MODERN; slot = T_ELNB; numel = H; return 0; }
         if (r == "word_embeddings.weight") { slot = T_WORD; numel = (int64_t)e->cfg.vocab * H; return 0; }
         if (r == "position_embeddings.weight") { slot = T_POS; numel = (int64_t)e->cfg.max_pos * H; return 0; }
         if (r == "token_type_embeddings.weight") { slot = T_TYPE; numel = (int64_t)e->cfg.type_vocab * H; return 0; }
@@ -265,47 +325,55 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
 }
 
 static AttnBiasArgs bias_args(const Encoder* e) { return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0}; }
+static AttnWinArgs win_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->half_window, e->bias_gather ? 1 : 0}; }
+// AM, the attention of a layer: 0 plain, 1 with the relative attention bias (MPNet handles), 2 under the sliding window (local layers of ModernBert handles)
+enum { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2 };
+template <int AM>
+static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN> attn_mode_args(const Encoder* e) {
+    if constexpr (AM == AM_BIAS) return bias_args(e);
+    else if constexpr (AM == AM_WIN) return win_args(e);
+    else return AttnNoBiasArgs{};
+}
 
-template <int DH, int HPB, bool BIAS>
+template <int DH, int HPB, int AM>
 static int launch_attn(const Encoder* e, int B, int cap, int nqt, hipStream_t st) {
     const int H = e->cfg.hidden, heads = e->cfg.heads;
     // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
     // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
     const int kchunk = cap < 128 ? cap : 128;
     const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
-    static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance
+    constexpr bool BIAS = AM == AM_BIAS, WIN = AM == AM_WIN;
+    static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance (one per instantiation of this function)
     int& attr_lds = attr_lds_dev[e->device & 63];
     if (lds > attr_lds) {
-        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_lds = lds;
     }
     const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
-    AttnBiasArg<BIAS> ba{};
-    if constexpr (BIAS) ba = bias_args(e);
-    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
+    const auto ba = attn_mode_args<AM>(e);
+    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
                        e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, ba);
     return 0;
 }
 
-template <int DH, bool BIAS>
+template <int DH, int AM>
 static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
     const int64_t pairs = (int64_t)B * e->cfg.heads;
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
-    AttnBiasArg<BIAS> ba{};
-    if constexpr (BIAS) ba = bias_args(e);
-    hipLaunchKernelGGL((k_attn_dma<DH, BIAS>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
+    const auto ba = attn_mode_args<AM>(e);
+    hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, AM == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
                        e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, ba);
     return 0;
 }
 
 // the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
-template <int DH, bool BIAS>
+template <int DH, int AM>
 static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, hipStream_t st) {
-    if (long_seq) return launch_attn_dma<DH, BIAS>(e, B, nqt, st);
-    if (nqt >= 3) return launch_attn<DH, 1, BIAS>(e, B, cap, nqt, st);
-    if (nqt == 2) return launch_attn<DH, 2, BIAS>(e, B, cap, nqt, st);
-    return launch_attn<DH, 4, BIAS>(e, B, cap, nqt, st);
+    if (long_seq) return launch_attn_dma<DH, AM>(e, B, nqt, st);
+    if (nqt >= 3) return launch_attn<DH, 1, AM>(e, B, cap, nqt, st);
+    if (nqt == 2) return launch_attn<DH, 2, AM>(e, B, cap, nqt, st);
+    return launch_attn<DH, 4, AM>(e, B, cap, nqt, st);
 }
 
 static int set_lds_once(const void* kern, int lds, int device);
@@ -324,7 +392,11 @@ static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int devi
         case EPI_DENSE: return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>);
         case EPI_GELU: return go(&k_proj<EPI_GELU, Shape, STAGES, NT>);
         case EPI_QKV_ROT: return go(&k_proj<EPI_QKV_ROT, Shape, STAGES, NT>);
+        case EPI_QKV_ROTB:      // not on the 256 x 256 tile (launch_proj): the bias quads next to its 128 accumulators spill
+            if constexpr (Shape::BM == 256) return fail(KR_EINVAL, "projection epilogue %d is not built for the 256 x 256 tile", epi);
+            else return go(&k_proj<EPI_QKV_ROTB, Shape, STAGES, NT>);
         case EPI_SWIGLU: return go(&k_proj<EPI_SWIGLU, Shape, STAGES, NT>);
+        case EPI_GEGLU: return go(&k_proj<EPI_GEGLU, Shape, STAGES, NT>);
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }
@@ -359,7 +431,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     a.pw = kn.pw;
     a.epi_prio = kn.epi_prio;
     // store policy by output size (see ProjArgs::nt)
-    a.nt = max_tokens * (int64_t)(epi == EPI_SWIGLU ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
+    a.nt = max_tokens * (int64_t)(epi == EPI_SWIGLU || epi == EPI_GEGLU ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
     // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
     // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
     // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
@@ -367,7 +439,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     const int64_t big_tiles = ((max_tokens + 255) / 256) * ((a.F + 255) / 256);
     const int64_t small_tiles = ((max_tokens + 127) / 128) * ((a.F + 127) / 128);
     const int force = kn.force_tile;
-    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * 5);   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
+    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * 5) || epi == EPI_QKV_ROTB;   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
     // a handful of token rows: the skinny loop, one tile per block (latency chain: the operand stream of the launch spread over as many CUs as it has
     // tiles).  32 x 32 tiles while there is at most one per CU, 64 x 64 (four multiplying waves share every staged K-tile: half the L2 -> LDS bytes per
     // output element) up to four 32 x 32 tiles' worth per CU — the crossover against the 128x128 producer / consumer loop measured in round 1.
@@ -391,7 +463,9 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
                 case EPI_DENSE: return launch(shape_tag, &k_proj_skinny<EPI_DENSE, RING, WM, WM>);
                 case EPI_GELU: return launch(shape_tag, &k_proj_skinny<EPI_GELU, RING, WM, WM>);
                 case EPI_QKV_ROT: return launch(shape_tag, &k_proj_skinny<EPI_QKV_ROT, RING, WM, WM>);
+                case EPI_QKV_ROTB: return launch(shape_tag, &k_proj_skinny<EPI_QKV_ROTB, RING, WM, WM>);
                 case EPI_SWIGLU: return launch(shape_tag, &k_proj_skinny<EPI_SWIGLU, RING, WM, WM>);
+                case EPI_GEGLU: return launch(shape_tag, &k_proj_skinny<EPI_GEGLU, RING, WM, WM>);
                 default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
             }
         };
@@ -412,7 +486,9 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
             case EPI_DENSE: return go(&k_proj_split<EPI_DENSE>);
             case EPI_GELU: return go(&k_proj_split<EPI_GELU>);
             case EPI_QKV_ROT: return go(&k_proj_split<EPI_QKV_ROT>);
+            case EPI_QKV_ROTB: return go(&k_proj_split<EPI_QKV_ROTB>);
             case EPI_SWIGLU: return go(&k_proj_split<EPI_SWIGLU>);
+            case EPI_GEGLU: return go(&k_proj_split<EPI_GEGLU>);
             default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
         }
     }
@@ -498,10 +574,48 @@ static int set_rotary(Encoder* e, const float* data, int64_t numel) {
     return 0;
 }
 
+// The settings of a ModernBert handle (kirag_amd.h).  They are only stored here — what they must add up to is enc_finalize's business — under the rule of the
+// other two: before the first finalize; later the same values are a no-op and anything else is refused.
+static int set_modern(Encoder* e, const char* name, std::vector<float>& dst, const float* data, int64_t numel) {
+    if (numel < 1 || numel > 4096) return fail(KR_EINVAL, "'%s': %lld values", name, (long long)numel);
+    std::vector<float> v((size_t)numel);
+    KR_HIP(hipMemcpy(v.data(), data, (size_t)numel * 4, hipMemcpyDefault));
+    for (float x : v) if (!std::isfinite(x)) return fail(KR_EINVAL, "'%s' holds a non-finite value", name);
+    if (e->finalized_once) {
+        if (v.size() == dst.size() && std::memcmp(v.data(), dst.data(), v.size() * 4) == 0) return 0;
+        return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle's kind and its attention settings are fixed at the first finalize", name);
+    }
+    dst.swap(v);
+    e->ready = false;
+    return 0;
+}
+
 static int set_config(Encoder* e, const char* name, const float* data, int64_t numel) {
     if (std::strcmp(name, "config.rotary_inv_freq") == 0) return set_rotary(e, data, numel);
+    if (std::strcmp(name, "config.local_attention_layers") == 0) {
+        std::vector<float> v = e->local_layers;
+        KR_TRY(set_modern(e, name, v, data, numel));
+        for (float x : v) if (x != 0.f && x != 1.f) return fail(KR_EINVAL, "'%s' takes one 0 / 1 flag per layer, got %g", name, (double)x);
+        e->local_layers.swap(v);
+        return 0;
+    }
+    if (std::strcmp(name, "config.rotary_inv_freq_local") == 0) {
+        const int half = e->cfg.hidden / e->cfg.heads / 2;
+        if (numel != half) return fail(KR_EINVAL, "%s takes d_h / 2 = %d values, got %lld", name, half, (long long)numel);
+        return set_modern(e, name, e->inv_freq_local, data, numel);
+    }
+    if (std::strcmp(name, "config.attention_half_window") == 0) {
+        if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
+        std::vector<float> v;
+        if (e->half_window > 0) v.push_back((float)e->half_window);
+        KR_TRY(set_modern(e, name, v, data, numel));
+        if (!(v[0] >= 1.f && v[0] <= 65536.f) || v[0] != (float)(int)v[0]) return fail(KR_EINVAL, "%s = %g: expected an integer >= 1", name, (double)v[0]);
+        e->half_window = (int)v[0];
+        return 0;
+    }
     if (std::strcmp(name, "config.position_padding_idx") != 0)
-        return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx, config.rotary_inv_freq)", name);
+        return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx, config.rotary_inv_freq, config.rotary_inv_freq_local, "
+                               "config.attention_half_window, config.local_attention_layers)", name);
     if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
     float v = 0.f;
     KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
@@ -559,22 +673,29 @@ static int build_bias_table(Encoder* e) {
 
 // cos / sin [max_pos][d_h / 2] with HF's arithmetic (NomicBertRotaryEmbedding.forward): the angle is the fp32 product float(pos) * inv_freq[j], the entry the
 // cosine / sine of that fp32 angle (evaluated in double and rounded once).  Also the zero row the embedding adds in place of a position row.
-static int build_rotary_tables(Encoder* e) {
-    const int half = (int)e->inv_freq.size(), P = e->cfg.max_pos, H = e->cfg.hidden;
+// One pair of tables per frequency vector: the handle's (global) one, and for ModernBert handles with local layers the local one.
+static int build_rotary_table(Encoder* e, const std::vector<float>& inv_freq, float** cos_tab, float** sin_tab) {
+    const int half = (int)inv_freq.size(), P = e->cfg.max_pos;
     std::vector<float> cs((size_t)P * half), sn((size_t)P * half);
     for (int p = 0; p < P; ++p)
         for (int j = 0; j < half; ++j) {
-            const float ang = (float)p * e->inv_freq[j];
+            const float ang = (float)p * inv_freq[j];
             cs[(size_t)p * half + j] = (float)std::cos((double)ang);
             sn[(size_t)p * half + j] = (float)std::sin((double)ang);
         }
-    if (!e->rot_cos) {
-        KR_TRY(dmalloc(e->own_bufs, &e->rot_cos, cs.size() * 4)); KR_TRY(dmalloc(e->own_bufs, &e->rot_sin, sn.size() * 4));
+    if (!*cos_tab) { KR_TRY(dmalloc(e->own_bufs, cos_tab, cs.size() * 4)); KR_TRY(dmalloc(e->own_bufs, sin_tab, sn.size() * 4)); }
+    KR_HIP(hipMemcpy(*cos_tab, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+    KR_HIP(hipMemcpy(*sin_tab, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+static int build_rotary_tables(Encoder* e) {
+    const int H = e->cfg.hidden;
+    if (!e->pos_zero) {
         KR_TRY(dmalloc(e->own_bufs, &e->pos_zero, (size_t)H * 4));
         KR_HIP(hipMemset(e->pos_zero, 0, (size_t)H * 4));
     }
-    KR_HIP(hipMemcpy(e->rot_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-    KR_HIP(hipMemcpy(e->rot_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+    KR_TRY(build_rotary_table(e, e->inv_freq, &e->rot_cos, &e->rot_sin));
+    if (!e->inv_freq_local.empty()) KR_TRY(build_rotary_table(e, e->inv_freq_local, &e->rot_cos_l, &e->rot_sin_l));
     return 0;
 }
 
@@ -583,10 +704,11 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(select_device(e->device));
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
-    int slot = -1; int64_t want = 0; bool nomic = false;
-    KR_TRY(parse_name(e, hf_name, slot, want, nomic));
+    int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
+    KR_TRY(parse_name(e, hf_name, slot, want, fam, layer));
+    const bool paired = fam != FAM_BERT;     // NomicBert's and ModernBert's names: q / k / the gated projection's rows go into tile-pair order
     if (slot == T_RELBIAS) return load_rel_bias(e, hf_name, data, numel, want);
-    if (slot < 0) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
+    if (slot == -1) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
     if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", hf_name, (long long)numel, (long long)want);
     if ((size_t)numel > e->stage_elems) {
         if (e->stage) (void)hipFree(e->stage);
@@ -599,12 +721,60 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     const float qscale = (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
     const unsigned grid = (unsigned)((numel + 255) / 256);
     auto to_bf16 = [&](uint16_t* dst, float scale) { hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
+    // a row block [n / cols, cols] of a fused ModernBert tensor, from element `first` of the staged copy
+    auto block_to_bf16 = [&](uint16_t* dst, int64_t first, int64_t n, int cols, float scale, int mode) {
+        const unsigned g = (unsigned)((n + 255) / 256);
+        if (mode < 0) hipLaunchKernelGGL(k_f32_to_bf16, dim3(g), dim3(256), 0, 0, e->stage + first, dst, n, scale);
+        else hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(g), dim3(256), 0, 0, e->stage + first, dst, n, cols, scale, mode);
+    };
     auto to_f32 = [&](float* dst, float scale) { hipLaunchKernelGGL(k_scale_copy, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
-    // NomicBert's matrices whose rows go into tile-pair order (k_f32_to_bf16_rows)
+    // the matrices whose rows go into tile-pair order (k_f32_to_bf16_rows)
     auto to_bf16_rows = [&](uint16_t* dst, float scale, int mode) {
         hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, (int)H, scale, mode);
     };
-    const bool head64 = nomic && H == 64 * e->cfg.heads;
+    const bool head64 = paired && H == 64 * e->cfg.heads;
+    if (slot == T_WQKV || slot == T_WI || slot == T_WIB || slot == T_WQKVB) {
+        // ModernBert's fused tensors.  Wqkv [3H, H] = q | k | v row blocks (heads contiguous inside each): the blocks the loader fills for the other families, q with
+        // the log2(e) / sqrt(d_h) fold, q and k in the rotary row order.  mlp.Wi [2 FF, H] = input | gate: input (the half the GELU is applied to) takes the place
+        // of NomicBert's gate_proj, gate that of up_proj.  mlp.Wi.bias in the same order.
+        LayerW& l = e->L[layer];
+        uint8_t* g = &e->got[T_LAYER0 + (size_t)layer * L_COUNT];
+        const int64_t FF = e->cfg.intermediate;
+        if (slot == T_WQKV) {
+            block_to_bf16(l.wqkv, 0, H * H, (int)H, qscale, head64 ? ROWS_HEAD64 : -1);
+            block_to_bf16(l.wqkv + H * H, H * H, H * H, (int)H, 1.f, head64 ? ROWS_HEAD64 : -1);
+            block_to_bf16(l.wqkv + 2 * H * H, 2 * H * H, H * H, (int)H, 1.f, -1);
+            g[L_QW] = g[L_KW] = g[L_VW] = FAM_MODERN;
+        } else if (slot == T_WQKVB) {
+            // q | k | v biases: q with the fold, q and k in their rows' order (added before the rotation: EPI_QKV_ROTB), v as always (folded into bo_eff)
+            std::vector<float> b((size_t)numel), pb((size_t)numel);
+            KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < H; ++i) {
+                const int64_t d = head64 ? tile_pair_row(i, ROWS_HEAD64) : i;
+                pb[(size_t)d] = b[(size_t)i] * qscale; pb[(size_t)(H + d)] = b[(size_t)(H + i)]; pb[(size_t)(2 * H + i)] = b[(size_t)(2 * H + i)];
+            }
+            KR_HIP(hipMemcpy(l.bqkv, pb.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
+            g[L_QB] = g[L_KB] = g[L_VB] = FAM_MODERN;
+        } else if (slot == T_WI) {
+            if (l.w1 && !l.gated) return fail(KR_EINVAL, "'%s': layer %d already holds intermediate.dense", hf_name, layer);
+            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * 2));
+            l.gated = true;
+            block_to_bf16(l.w1, 0, H * FF, (int)H, 1.f, ROWS_GATE);
+            block_to_bf16(l.w1, H * FF, H * FF, (int)H, 1.f, ROWS_UP);
+            g[L_IW] = g[L_UW] = FAM_MODERN;
+        } else {
+            if (!l.b1p) KR_TRY(dmalloc(e->own_bufs, &l.b1p, (size_t)numel * 4));
+            std::vector<float> b((size_t)numel), pb((size_t)numel);
+            KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < FF; ++i) { pb[(size_t)tile_pair_row(i, ROWS_GATE)] = b[(size_t)i]; pb[(size_t)tile_pair_row(i, ROWS_UP)] = b[(size_t)(FF + i)]; }
+            KR_HIP(hipMemcpy(l.b1p, pb.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
+            g[L_IB] = FAM_MODERN;
+        }
+        KR_HIP(hipGetLastError());
+        KR_HIP(hipDeviceSynchronize());
+        e->ready = false;
+        return 0;
+    }
     if (slot < T_LAYER0) {
         if (slot == T_POS && !e->pos) KR_TRY(dmalloc(e->own_bufs, &e->pos, (size_t)numel * 4));
         float* dst[] = {e->word, e->pos, e->type, e->elng, e->elnb};
@@ -613,10 +783,10 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
         LayerW& l = e->L[(slot - T_LAYER0) / L_COUNT];
         const int id = (slot - T_LAYER0) % L_COUNT;
         if (id == L_IW || id == L_UW) {
-            if (l.w1 && l.gated != nomic)
-                return fail(KR_EINVAL, "'%s': layer %d already holds %s", hf_name, (slot - T_LAYER0) / L_COUNT, nomic ? "intermediate.dense" : "a gated projection (gate_proj / up_proj)");
-            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * (nomic ? 4 : 2)));
-            l.gated = nomic;
+            if (l.w1 && l.gated != paired)
+                return fail(KR_EINVAL, "'%s': layer %d already holds %s", hf_name, (slot - T_LAYER0) / L_COUNT, paired ? "intermediate.dense" : "a gated projection (gate_proj / up_proj)");
+            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * (paired ? 4 : 2)));
+            l.gated = paired;
         }
         switch (id) {
             // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2.  The
@@ -631,7 +801,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             case L_OB: to_f32(l.bo, 1.f); break;
             case L_LN1G: to_f32(l.ln1g, 1.f); break;
             case L_LN1B: to_f32(l.ln1b, 1.f); break;
-            case L_IW: if (nomic) to_bf16_rows(l.w1, 1.f, ROWS_GATE); else to_bf16(l.w1, 1.f); break;
+            case L_IW: if (paired) to_bf16_rows(l.w1, 1.f, ROWS_GATE); else to_bf16(l.w1, 1.f); break;
             case L_UW: to_bf16_rows(l.w1, 1.f, ROWS_UP); break;
             case L_IB: to_f32(l.b1, 1.f); break;
             case L_FW: to_bf16(l.w2, 1.f); break;
@@ -642,7 +812,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     }
     KR_HIP(hipGetLastError());
     KR_HIP(hipDeviceSynchronize());
-    e->got[slot] = nomic ? 2 : 1;
+    e->got[slot] = (uint8_t)fam;
     e->ready = false;
     return 0;
 }
@@ -650,12 +820,34 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
 int enc_finalize(void* h) {
     if (!h) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
-    const bool rot = e->rotary();
+    const bool rot = e->rotary(), modern = e->modern();
+    if (!modern && (!e->inv_freq_local.empty() || e->half_window > 0))
+        return fail(KR_EINVAL, "config.rotary_inv_freq_local / config.attention_half_window without config.local_attention_layers: they are settings of a ModernBert handle");
+    if (modern) {
+        if (e->pad_idx >= 0 || !e->rel_w.empty())
+            return fail(KR_EINVAL, "config.local_attention_layers next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
+        if (!rot) return fail(KR_EINVAL, "config.local_attention_layers without config.rotary_inv_freq: a ModernBert handle rotates q and k");
+        if ((int)e->local_layers.size() != e->cfg.layers)
+            return fail(KR_EINVAL, "config.local_attention_layers holds %zu flags, the handle has %d layers", e->local_layers.size(), e->cfg.layers);
+        bool any_local = false;
+        for (int li = 0; li < e->cfg.layers; ++li) any_local = any_local || e->local_layer(li);
+        if (any_local && (e->inv_freq_local.empty() || e->half_window < 1))
+            return fail(KR_EINVAL, "config.local_attention_layers flags local layers, but %s was never loaded",
+                        e->inv_freq_local.empty() ? "config.rotary_inv_freq_local" : "config.attention_half_window");
+    }
+    // names and handle kind agree: ModernBert's names on a ModernBert handle only, and nothing but them there (the token-type row has no ModernBert name)
+    for (size_t i = 0; i < e->got.size(); ++i) {
+        if (!e->got[i] || i == T_TYPE) continue;
+        if ((e->got[i] == FAM_MODERN) != modern)
+            return fail(KR_EINVAL, modern ? "weight slot %zu was loaded under a BERT / NomicBert name: a handle with config.local_attention_layers takes ModernBert's names"
+                                          : "weight slot %zu was loaded under a ModernBert name but config.local_attention_layers was never loaded: load it before kr_encoder_finalize", i);
+    }
     if (rot && (e->pad_idx >= 0 || !e->rel_w.empty()))
         return fail(KR_EINVAL, "config.rotary_inv_freq next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
     // q / k and the intermediate projection are packed in another row order under NomicBert's names (enc_load_weight): names and handle kind must agree
     for (int li = 0; li < e->cfg.layers; ++li) {
         const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
+        if (modern) continue;
         if (rot && (g[L_QW] == 1 || g[L_KW] == 1 || g[L_IW] == 1))
             return fail(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj and mlp.{gate,up}_proj under NomicBert's names", li);
         if (rot && (g[L_QB] || g[L_KB] || g[L_IB]))
@@ -665,8 +857,9 @@ int enc_finalize(void* h) {
     }
     // a NomicBert handle has no position table and needs up_proj; its linear biases are zero unless loaded
     auto optional = [&](size_t i) {
-        if (i < T_LAYER0) return rot && i == T_POS;
+        if (i < T_LAYER0) return (rot && i == T_POS) || (modern && i == T_ELNB);
         const int id = (int)((i - T_LAYER0) % L_COUNT);
+        if (modern && (id == L_LN1B || id == L_LN2B)) return true;
         if (id == L_UW) return !rot;
         return rot && (id == L_QB || id == L_KB || id == L_VB || id == L_OB || id == L_IB || id == L_FB);
     };
@@ -677,10 +870,19 @@ int enc_finalize(void* h) {
     KR_TRY(select_device(e->device));
     const int H = e->cfg.hidden;
     if (rot) {
+        if (modern && !e->got[T_ELNB]) KR_HIP(hipMemset(e->elnb, 0, (size_t)H * 4));
         for (int li = 0; li < e->cfg.layers; ++li) {
             const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
             LayerW& l = e->L[li];
-            KR_HIP(hipMemset(l.bqkv, 0, (size_t)2 * H * 4));
+            if (modern) {      // LayerNorm betas and the gated projection's bias are zero unless loaded
+                if (!g[L_LN1B]) KR_HIP(hipMemset(l.ln1b, 0, (size_t)H * 4));
+                if (!g[L_LN2B]) KR_HIP(hipMemset(l.ln2b, 0, (size_t)H * 4));
+                if (!l.b1p) {
+                    KR_TRY(dmalloc(e->own_bufs, &l.b1p, (size_t)2 * e->cfg.intermediate * 4));
+                    KR_HIP(hipMemset(l.b1p, 0, (size_t)2 * e->cfg.intermediate * 4));
+                }
+            }
+            if (!(modern && g[L_QB])) KR_HIP(hipMemset(l.bqkv, 0, (size_t)2 * H * 4));     // (a ModernBert layer with attn.Wqkv.bias: EPI_QKV_ROTB adds it)
             if (!g[L_VB]) KR_HIP(hipMemset(l.bqkv + 2 * H, 0, (size_t)H * 4));
             if (!g[L_OB]) KR_HIP(hipMemset(l.bo, 0, (size_t)H * 4));
             if (!g[L_FB]) KR_HIP(hipMemset(l.b2, 0, (size_t)H * 4));
@@ -709,6 +911,7 @@ struct RowSet {
     int* rows;                   // device word: how many rows are live
     int64_t max_rows;
     unsigned ln_grid;
+    uint16_t* rb; uint8_t* rlo;  // ModernBert handles: the pre-LN residual stream of these rows (rlo: nullptr without use_lo)
 };
 
 // every kernel of one forward, enqueued on `st` (input already in the workspace, result left in e->out)
@@ -730,6 +933,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // non-temporally — they do not displace the 16-bit stream the next GEMM reads: -1.3 % forward at 1024 x 128 tokens, -0.1...0.5 % at 1000 x 32; 8 blocks
     // per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
     auto ln_kernel = H <= 512 ? &k_ln16<1, 7> : H <= 1024 ? &k_ln16<2, 7> : &k_ln16<4, 7>;
+    auto ln_pre_kernel = H <= 512 ? &k_ln16_pre<1, 1> : H <= 1024 ? &k_ln16_pre<2, 1> : &k_ln16_pre<4, 1>;      // ModernBert handles (y non-temporal as above)
+    const bool modern = e->modern();
     auto pool_kernel = H <= 256 ? &k_pool<1> : H <= 512 ? &k_pool<2> : H <= 1024 ? &k_pool<4> : &k_pool<8>;
     const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
     unsigned ln_mult = 8u;
@@ -741,9 +946,28 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
                        e->use_lo ? e->xlo : nullptr, e->xb);
     const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr;
     e->last_shortcut = shortcut;
-    const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid};
+    const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid,
+                          e->rb, e->use_lo ? e->rlo : nullptr};
     const RowSet cls_rows{e->c_ctx, e->c_xb, e->c_y, e->c_h, e->use_lo ? e->c_xlo : nullptr, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, B,
-                          std::min((unsigned)((B + 3) / 4), (unsigned)e->num_cu_all * ln_mult)};
+                          std::min((unsigned)((B + 3) / 4), (unsigned)e->num_cu_all * ln_mult), e->c_rb, e->use_lo ? e->c_rlo : nullptr};
+    // the pre-LN tail of a ModernBert layer on the same five launches.  (rin, rin_lo): the residual stream as this layer finds it — r.rb / r.rlo, or for layer
+    // 0 on all rows the embedding LayerNorm's output itself (xb / xlo: attn_norm of layer 0 is the identity)
+    auto tail_pre = [&](ProjArgs a, const LayerW& l, const RowSet& r, bool last, const uint16_t* rin, const uint8_t* rin_lo) {
+        a.Tp = r.rows;
+        // attn.Wo; r += y + b; xb = mlp_norm(r)
+        a.W = l.wo; a.X = r.ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = r.y; a.ldx = 0; a.ldo = 0;
+        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
+        hipLaunchKernelGGL(ln_pre_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, rin, rin_lo, r.rb, r.rlo, (uint8_t*)nullptr, r.xb);
+        // mlp.Wi (input | gate as one GEMM of 2 FF columns) + GEGLU: h [rows, FF]
+        a.W = l.w1; a.X = r.xb; a.F = 2 * FF; a.K = H; a.bias = l.b1p; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
+        KR_TRY(launch_proj(EPI_GEGLU, a, r.max_rows, e, st));
+        // mlp.Wo; r += y + b; xb = the next layer's attn_norm(r), or final_norm(r) with its low half for the readers of the final hidden state
+        a.W = l.w2; a.X = r.h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = r.y; a.ldx = FF; a.ldo = 0;
+        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
+        hipLaunchKernelGGL(ln_pre_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.b2, r.rows, l.ln2g, l.ln2b, eps, H, (const uint16_t*)r.rb, (const uint8_t*)r.rlo,
+                           last ? (uint16_t*)nullptr : r.rb, r.rlo, last ? r.lo_last : (uint8_t*)nullptr, r.xb);
+        return 0;
+    };
     auto tail = [&](ProjArgs a, const LayerW& l, const RowSet& r, bool last) {
         a.Tp = r.rows;
         // attention.output.dense + residual -> LayerNorm
@@ -762,24 +986,40 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     };
     for (const LayerW& l : e->L) {
         const bool last = (&l == &e->L.back());
+        const bool first = (&l == &e->L.front());
+        const bool local = e->local_layer((int)(&l - &e->L.front()));      // a ModernBert handle's sliding-window layer: its own rotary table, windowed attention
         ProjArgs a{};
         a.Tp = e->d_T; a.H = H;
-        a.rot_cos = e->rot_cos; a.rot_sin = e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
+        a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
         // q | k | v^T in one GEMM (F = 3H)
         a.W = l.wqkv; a.X = e->xb; a.F = 3 * H; a.K = H; a.bias = l.bqkv; a.out0 = e->q; a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv; a.ldx = 0; a.ldo = 0;
-        KR_TRY(launch_proj(rot ? EPI_QKV_ROT : EPI_QKV, a, maxT, e, st));
+        const bool qk_bias = modern && e->got[T_LAYER0 + (size_t)(&l - &e->L.front()) * L_COUNT + L_QB] != 0;      // attn.Wqkv.bias was loaded
+        KR_TRY(launch_proj(!rot ? EPI_QKV : qk_bias ? EPI_QKV_ROTB : EPI_QKV_ROT, a, maxT, e, st));
         {
             const int cap = (int)round_up(S, 32);
-            const bool bias = e->bias_tab != nullptr;      // an MPNet handle: the instantiations with the relative attention bias
-            if (H == 32 * e->cfg.heads) KR_TRY((bias ? launch_attention<32, true>(e, B, cap, nqt_max, long_seq, st) : launch_attention<32, false>(e, B, cap, nqt_max, long_seq, st)));
-            else KR_TRY((bias ? launch_attention<64, true>(e, B, cap, nqt_max, long_seq, st) : launch_attention<64, false>(e, B, cap, nqt_max, long_seq, st)));
+            // an MPNet handle: the instantiations with the relative attention bias; a local layer of a ModernBert handle: those with the window
+            const int am = e->bias_tab != nullptr ? AM_BIAS : local ? AM_WIN : AM_PLAIN;
+            auto go = [&](auto dh) -> int {
+                constexpr int DH = decltype(dh)::value;
+                return am == AM_BIAS ? launch_attention<DH, AM_BIAS>(e, B, cap, nqt_max, long_seq, st)
+                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, st);
+            };
+            if (H == 32 * e->cfg.heads) KR_TRY(go(std::integral_constant<int, 32>{})); else KR_TRY(go(std::integral_constant<int, 64>{}));
         }
         // CLS shortcut: only the CLS row of every sequence is read after the last layer: gather those rows and finish the layer on B rows (same kernels, same
         // arithmetic per row: the projection loops are bit-identical for every tiling and LayerNorm is per row, so the embedding does not change by one bit)
+        // (a ModernBert handle: the residual stream travels in the place of xb — the operand is rewritten by the first LayerNorm of the tail)
+        const uint16_t* rin = modern && !first ? e->rb : e->xb;
+        const uint8_t* rin_lo = modern && !first ? all_rows.rlo : all_rows.lo;
         if (last && shortcut)
-            hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, e->xb, all_rows.lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, e->c_xb, e->c_xlo, e->c_off,
-                               e->c_nk, e->c_cls, e->d_B);
-        KR_TRY(tail(a, l, last && shortcut ? cls_rows : all_rows, last));
+            hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, modern ? e->c_rb : e->c_xb,
+                               modern ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B);
+        if (modern) {
+            if (last && shortcut) KR_TRY(tail_pre(a, l, cls_rows, last, e->c_rb, cls_rows.rlo));
+            else KR_TRY(tail_pre(a, l, all_rows, last, rin, rin_lo));
+        } else {
+            KR_TRY(tail(a, l, last && shortcut ? cls_rows : all_rows, last));
+        }
     }
     const RowSet& r = shortcut ? cls_rows : all_rows;
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));

@@ -75,29 +75,57 @@ struct AttnBiasArgs {
     int gather;           // != 0: take every key's column from `col` even when they are consecutive
 };
 struct AttnNoBiasArgs {};
-template <bool BIAS> using AttnBiasArg = std::conditional_t<BIAS, AttnBiasArgs, AttnNoBiasArgs>;
+// Sliding-window ("local") attention (ModernBert's sliding_attention layers): key admitted iff |col_key - col_query| <= w, col = the token's column in the
+// padded batch (tok_pos), on top of the padding mask.  The key columns come the same two ways as for the bias.  An excluded score becomes -inf after the
+// S^T chains; the steps that can hold no admitted key for a wave's whole 32-query tile are skipped (AttnBand), by ONE rule in both kernels.
+struct AttnWinArgs {
+    const int* col;       // tok_pos
+    int w;                // half-window (>= 1)
+    int gather;           // != 0: take every key's column from `col` even when they are consecutive
+};
+template <bool BIAS, bool WIN = false> using AttnBiasArg = std::conditional_t<BIAS, AttnBiasArgs, std::conditional_t<WIN, AttnWinArgs, AttnNoBiasArgs>>;
 
-// BM (bias mode of a kernel body, block-uniform): 0 no bias, 1 consecutive key columns, 2 gathered key columns.  The choice between 1 and 2 is made once per
-// block, outside the key loops (a branch inside them costs the accumulators register copies at every join)
-struct AttnNoBias { static constexpr bool on = false; };
+// BM (mode of a kernel body, block-uniform): 0 plain, 1 bias with consecutive key columns, 2 bias with gathered key columns, 3 window with consecutive key
+// columns, 4 / 5 window with gathered key columns (4: k_attn_dma, 16-byte loads; 5: k_attn_lds, one load per key — the same values either way).  The choice between 1 and 2 (3 and 4) is made once per block, outside the key loops (a branch inside them
+// costs the accumulators register copies at every join)
+template <int BM> using AttnModeArg = AttnBiasArg<BM == 1 || BM == 2, BM >= 3>;
+struct AttnNoBias { static constexpr bool on = false, win = false; };
+template <int GATHER>       // 0: consecutive key columns, 1: gathered with 16-byte loads, 2: gathered key by key
+struct AttnWinLane {
+    static constexpr bool on = false, win = true;
+    const int* col;       // columns of the sequence's packed rows (GATHER)
+    int base;             // w - column of this lane's query (+ 8 hf + the column of key 0 when the columns are consecutive)
+    unsigned w2;          // 2 w: admitted <=> (unsigned)(col_key - col_query + w) <= 2 w
+    int nk;
+};
 template <bool GATHER>
 struct AttnBiasLane {
-    static constexpr bool on = true;
+    static constexpr bool on = true, win = false;
     const float* tab;     // table of the head (wave-uniform)
     const int* col;       // columns of the sequence's packed rows (GATHER)
     int lane0;            // width / 2 - column of this lane's query + 8 hf (+ the column of key 0 when the columns are consecutive)
     int nk;
 };
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load at a 4-byte aligned address (one global_load_dwordx4)
+typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 // does sequence (off, nk) need the gathered key columns?  (the packers write the attended columns in increasing order: consecutive <=> last - first = nk - 1)
-__device__ __forceinline__ bool attn_bias_gathers(const AttnBiasArgs& ba, int64_t off, int nk) {
+template <class Args>
+__device__ __forceinline__ bool attn_bias_gathers(const Args& ba, int64_t off, int nk) {
     return ba.gather != 0 || (nk >= 2 && ba.col[off + nk - 1] - ba.col[off] != nk - 1);
 }
 
 template <int BM>
-__device__ __forceinline__ auto attn_bias_lane(const AttnBiasArg<BM != 0>& ba, int64_t off, int nk, int head, int qi, int hf) {
-    if constexpr (BM != 0) {
+__device__ __forceinline__ auto attn_bias_lane(const AttnModeArg<BM>& ba, int64_t off, int nk, int head, int qi, int hf) {
+    if constexpr (BM >= 3) {
+        const int* col = ba.col + off;
+        AttnWinLane<BM - 3> wl;
+        wl.col = col;
+        wl.base = ba.w - col[qi] + (BM == 3 ? 8 * hf + (nk > 0 ? col[0] : 0) : 0);
+        wl.w2 = 2u * (unsigned)ba.w;
+        wl.nk = nk;
+        return wl;
+    } else if constexpr (BM != 0) {
         const int* col = ba.col + off;
         AttnBiasLane<BM == 2> bl;
         bl.tab = ba.tab + (int64_t)head * ba.width;
@@ -130,6 +158,52 @@ __device__ __forceinline__ void attn_bias_tile(f32x16& st, const AttnBiasLane<GA
         }
     }
 }
+// the window of one 32-key tile: scores of keys outside |col_key - col_query| <= w become -inf (kb = index of the tile's first key in its sequence)
+template <int GATHER>
+__device__ __forceinline__ void attn_window_tile(f32x16& st, const AttnWinLane<GATHER>& wl, int kb, int hf) {
+    if constexpr (GATHER == 0) {
+        const int t0 = wl.base + kb;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = ((unsigned)(t0 + 16 * (r >> 3) + (r & 7)) <= wl.w2) ? st[r] : -INFINITY;
+    } else if constexpr (GATHER == 2) {
+        // (k_attn_lds runs at its 168-register limit: four consecutive registers per load do not fit there)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = kb + 16 * (r >> 3) + 8 * hf + (r & 7);
+            st[r] = ((unsigned)(wl.base + wl.col[(unsigned)min(key, wl.nk - 1)]) <= wl.w2) ? st[r] : -INFINITY;     // keys >= nk are masked by the step's MODE
+        }
+    } else {
+        // a lane's 8 consecutive keys of a 16-key group are 8 consecutive entries of the column table: two 16-byte loads on one lane address.  The entries of
+        // keys >= nk (other sequences' rows; tok_pos has 64 entries of slack behind the last token, ensure_ws) are masked by the step's MODE
+        const int* p = wl.col + (unsigned)(kb + 8 * hf);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const i32x4u x = *reinterpret_cast<const i32x4u*>(p + 16 * a), y = *reinterpret_cast<const i32x4u*>(p + 16 * a + 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                st[8 * a + i] = ((unsigned)(wl.base + x[i]) <= wl.w2) ? st[8 * a + i] : -INFINITY;
+                st[8 * a + 4 + i] = ((unsigned)(wl.base + y[i]) <= wl.w2) ? st[8 * a + 4 + i] : -INFINITY;
+            }
+        }
+    }
+}
+
+// Which 64-key steps a wave's 32-query tile (first query q0) visits under a window.  Attended columns are packed in increasing order, so
+// |col_i - col_j| >= |i - j|: every admissible key of packed query i < nk lies in packed [i - w, i + w], with or without holes in the mask.  The query-only
+// CLS row (packed last, index nk, column 0; nq == nk + 1) admits keys of column <= w: packed [0, w].  A step [kb, kb + 64) is visited iff it meets the
+// union of the tile's bands; both kernels apply this rule to the same 64-aligned steps, so they run the same steps on a tile.
+struct AttnBand {
+    int lo, hi, xhi;      // packed keys [lo, hi] of the tile's key-bearing queries (hi < lo: none); [0, xhi] of the CLS row (xhi < 0: not in this tile)
+    __device__ __forceinline__ bool visits(int kb) const { return (kb <= hi && kb + 63 >= lo) || kb <= xhi; }
+};
+__device__ __forceinline__ AttnBand attn_band(int q0, int q1, int nk, int nq, int w) {      // queries [q0, q1] (q1 may lie past nq - 1)
+    AttnBand b;
+    b.lo = max(q0 - w, 0);
+    b.hi = q0 < nk ? min(q1, nk - 1) + w : -1;
+    b.xhi = (nq > nk && q1 >= nk) ? w : -1;
+    return b;
+}
+
 // first half of a step: the shifted-score tiles S^T = K . Q^T (st1 = -inf when the second 32-key tile does not exist)
 // MODE (wave-uniform, picked from the number of valid keys of the step): 0 = 64, 1 = fewer than 32 (first tile masked, no second tile),
 // 2 = exactly 32 (one full tile: a 32-token sequence), 3 = 33 .. 63 (second tile masked)
@@ -194,6 +268,10 @@ __device__ __forceinline__ void attn_scores(f32x16& st0, f32x16& st1, const uint
     if constexpr (MODE == 3) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) st1[r] = (16 * (r >> 3) + 8 * hf + (r & 7) + 32 < nvalid) ? st1[r] : -INFINITY;
+    }
+    if constexpr (BL::win) {
+        attn_window_tile(st0, bl, kb, hf);
+        if constexpr (two) attn_window_tile(st1, bl, kb + 32, hf);
     }
 }
 
@@ -272,13 +350,15 @@ __device__ __forceinline__ void attn_step64(AttnState<DH>& s, const uint4 (&qf)[
 
 // normalise a finished 32-query tile and store it as whole 2 DH-byte rows of ctx (columns head * DH ..) through the wave-private LDS block Os of
 // 32 x 2 DH bytes (8-byte chunk index XOR the row)
-template <int DH>
+// ZERO_EMPTY (window instantiations): a query whose window holds no attended key (the CLS row of a masked column 0 whose sequence starts beyond column w)
+// gets a zero context row instead of 0 / 0
+template <int DH, bool ZERO_EMPTY = false>
 __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os, uint16_t* __restrict__ ctx, int64_t off, int q0, int nq, int H, int head, int lane) {
     constexpr int RB = 2 * DH, C8 = DH / 4, LR = DH / 8;  // row bytes, 8-byte chunks per row, lanes per row in the store
     asm volatile("" : "+v"(lane));   // opaque: the store addresses are computed here, after the key loop, instead of living in registers (or scratch) across it
     const int c = lane & 31, hf = lane >> 5;
     // a query with no attendable key (all-masked sequence) is 0/0 = NaN, as under HF's -inf masking
-    const float inv = 1.0f / s.l;
+    const float inv = (ZERO_EMPTY && s.l == 0.f) ? 0.f : 1.0f / s.l;
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
         uint2 w[DH / 32];
@@ -311,7 +391,8 @@ template <int DH> constexpr int attn_lds_blocks() { return DH == 64 ? 3 : 4; }
 template <int DH, int HPB, int BM>
 __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                              int H, int heads, int kchunk, uint16_t* __restrict__ ctx, const AttnBiasArg<BM != 0>& ba, char* smem) {
+                                              int H, int heads, int kchunk, uint16_t* __restrict__ ctx, const AttnModeArg<BM>& ba, char* smem) {
+    constexpr bool WIN = BM >= 3;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; as a scalar, the head / q-tile / LDS bases derived from it cost no VGPRs
     const int hb = blockIdx.x, b = blockIdx.y;            // heads fastest: the heads of one sequence (same 2-KiB q/k rows) run together
@@ -343,15 +424,26 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
     }
     AttnState<DH> st;
     attn_init(st);
+    // window: the steps this wave's tile visits, and the chunks any tile of the block visits (block-uniform: the others are not staged)
+    AttnBand band{}, bband{};
+    if constexpr (WIN) {
+        band = attn_band(q0, q0 + 31, nk, nq, ba.w);
+        bband = attn_band((int)blockIdx.z * QT * 32, (int)blockIdx.z * QT * 32 + QT * 32 - 1, nk, nq, ba.w);
+    }
     constexpr int NB = HPB == 1 ? 4 : 2;                  // loads in flight per thread, head and batch (register budget: 3 blocks per CU = 168 VGPRs; HPB = 4 means <= 32 keys: 2 cover a head)
     for (int kc0 = 0; kc0 < nk; kc0 += kchunk) {
         // ---- stage keys [kc0, kc0 + kchunk) of the block's heads: every global load of a batch is issued before the first LDS store
         // (a load -> store loop would serialise one memory round trip per iteration)
         const int nkc = min(nk - kc0, kchunk);            // keys of this chunk
+        if constexpr (WIN) {
+            bool any = false;
+            for (int k0 = 0; k0 < nkc; k0 += 64) any = any || bband.visits(kc0 + k0);
+            if (!any) continue;
+        }
         const int nkp = (nkc + 31) & ~31;
         const int cpr = nkp >> 2;                         // 8-byte chunks (4 keys) per V^T row
         const unsigned cpr_magic = 0xFFFFFFFFu / (unsigned)cpr + 1u;
-        if (kc0 > 0) __syncthreads();                     // every wave is done with the previous chunk
+        if (kc0 > 0) __syncthreads();                     // every wave is done with the previous chunk (or nothing was staged yet: harmless)
         {
             // all heads of the block in ONE batch: every global load (K and V^T of up to HPB heads) is issued before the first LDS store, so a block with
             // 2 / 4 heads pays one memory round trip per batch, not one per head (a 32-token sequence is a single batch)
@@ -432,9 +524,10 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
                 const uint2 a0 = *reinterpret_cast<const uint2*>(v), a1 = *reinterpret_cast<const uint2*>(v + 8);
                 return make_uint4(a0.x, a0.y, a1.x, a1.y);
             };
+            if constexpr (WIN) { if (!band.visits(kc0 + k0)) continue; }
             attn_step64<false>(st, qf, Kh, k0, 64, c, hf, vfrag, bl, kc0 + k0);
         }
-        if (kfull < nkc) {
+        if (kfull < nkc && (!WIN || band.visits(kc0 + kfull))) {
             auto vfrag = [&](int dh, int ks) {
                 const char* v = Vh + (c + 32 * dh) * vpitch + (kfull + 16 * ks + 8 * hf) * 2;
                 const uint2 a0 = *reinterpret_cast<const uint2*>(v), a1 = *reinterpret_cast<const uint2*>(v + 8);
@@ -444,15 +537,20 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
         }
     }
     if (!active) return;
-    attn_store_tile(st, Os, ctx, off, q0, nq, H, head, lane);
+    attn_store_tile<DH, WIN>(st, Os, ctx, off, q0, nq, H, head, lane);
 }
 
-template <int DH, int HPB, bool BIAS = false>
+template <int DH, int HPB, bool BIAS = false, bool WIN = false>
 __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS> ba) {
+                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS, WIN> ba) {
+    static_assert(!(BIAS && WIN), "a relative attention bias under a window is not instantiated");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (BIAS) {
+    if constexpr (WIN) {
+        const int b = blockIdx.y;
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 5>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        else attn_lds_body<DH, HPB, 3>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+    } else if constexpr (BIAS) {
         const int b = blockIdx.y;
         if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 2>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
         else attn_lds_body<DH, HPB, 1>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
@@ -486,13 +584,21 @@ struct AdmaGeom {
 // marked as not aliasing it, which lets the compiler's waitcnt pass leave the COUNTED vmcnt waits alone; see coarse_q32_body in search.hip)
 template <int DH, int BM>
 __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
-                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, const AttnBiasArg<BM != 0>& ba) {
+                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, const AttnModeArg<BM>& ba) {
+    constexpr bool WIN = BM >= 3;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hf = lane >> 5;
     using G = AdmaGeom<DH>;
     constexpr int ADMA_PIECES = G::PIECES, KB = G::KB, ADMA_STAGE = G::STAGE;
     constexpr int NC = DH / 8, NCS = DH == 64 ? 3 : 2, KROWS = 1024 / (2 * DH);  // 16-B chunks per K row (1 << NCS), keys per 1-KiB K piece
-    const int nchunks = (nk + 63) >> 6;
+    // chunks [c_lo, nchunks) are streamed: all of them, or under a window those that meet the band of the block's 256 queries (at w = 64 at most 7; a block
+    // that holds the query-only CLS row starts at chunk 0)
+    int c_lo = 0, nchunks = (nk + 63) >> 6;
+    if constexpr (WIN) {
+        const AttnBand bb = attn_band(qg * ADMA_QT * 32, qg * ADMA_QT * 32 + ADMA_QT * 32 - 1, nk, nq, ba.w);
+        c_lo = bb.xhi >= 0 ? 0 : (bb.lo >> 6);
+        nchunks = min(nchunks, max(bb.hi, bb.xhi) / 64 + 1);      // hi, xhi >= -1
+    }
     // DMA of one chunk: 2 DH / 8 pieces of 1 KiB (DH / 8 K pieces of 1024 / (2 DH) keys each, DH / 8 V^T pieces = 8 d rows x 128 B each); wave w issues
     // pieces w * ADMA_PIECES .. + ADMA_PIECES - 1 of both.  K: lane -> key KROWS p + lane / NC, 16-B chunk (lane % NC) ^ attn_kswz(key); V^T: lane -> d row
     // 8 p + (lane >> 3), 16-B chunk (lane & 7) ^ ((d >> 1) & 7) (the LDS destination is lane-linear: the swizzle sits on the source)
@@ -523,8 +629,8 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void*)(stg + KB + p * 1024), 16, vlane[pp], vc, 0, 0);
         }
     };
-    issue(0);
-    if (nchunks > 1) issue(1);
+    if (!WIN || c_lo < nchunks) issue(c_lo);      // (window: no chunk at all for the CLS row of an all-masked sequence)
+    if (c_lo + 1 < nchunks) issue(c_lo + 1);
     // The Q fragments are loaded behind the first two chunks' DMA and waited for HERE with a wait the compiler sees (a builtin, not inline asm):
     // otherwise its waitcnt pass keeps them "possibly pending" around the loop's back edge and puts s_waitcnt vmcnt(0) in front of the first MFMA of
     // every chunk, which drains the DMA ring (one memory round trip per chunk, as without a ring)
@@ -545,6 +651,11 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
         }
         attn_init(st[j]);
     }
+    AttnBand band[2] = {};
+    if constexpr (WIN) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) band[j] = attn_band(q0[j], q0[j] + 31, nk, nq, ba.w);
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): Q fragments (and chunks 0, 1) have landed
     auto turn = [&](int ci) {
         if (ci + 1 < nchunks) wait_vmcnt<2 * ADMA_PIECES>(); else wait_vmcnt<0>();   // this wave's pieces of chunk ci have landed; chunk ci + 1 may be in flight
@@ -553,7 +664,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     };
     // The chunks with 64 valid keys run in loops of their own (one per number of active q-tiles) that hold nothing but the unmasked step: with the masked
     // variants and the act[] tests inside one loop the accumulators of both tiles went through copies at every join (32 v_mov_b64 per step)
-    const int nfull = nk >> 6;
+    const int nfull = WIN ? min(nk >> 6, nchunks) : nk >> 6;
     auto full_chunk = [&](int ci, auto two_tiles) {
         turn(ci);
         char* stg = smem + (ci % ADMA_RING) * ADMA_STAGE;
@@ -562,15 +673,21 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
             return *reinterpret_cast<const uint4*>(stg + KB + d * 128 + (((2 * ks + hf) ^ ((d >> 1) & 7)) << 4));
         };
         // (gathered key columns: without the fragment prefetch — the gather's indices and the prefetched fragments together do not fit the register file)
-        attn_step64<false, BM != 2>(st[0], qf[0], stg, 0, 64, c, hf, vfrag, bl[0], ci * 64);
-        if constexpr (decltype(two_tiles)::value) attn_step64<false, BM != 2>(st[1], qf[1], stg, 0, 64, c, hf, vfrag, bl[1], ci * 64);
+        constexpr bool PF = BM != 2 && BM != 4;
+        if constexpr (WIN) {
+            if (band[0].visits(ci * 64)) attn_step64<false, PF>(st[0], qf[0], stg, 0, 64, c, hf, vfrag, bl[0], ci * 64);
+            if constexpr (decltype(two_tiles)::value) { if (band[1].visits(ci * 64)) attn_step64<false, PF>(st[1], qf[1], stg, 0, 64, c, hf, vfrag, bl[1], ci * 64); }
+        } else {
+            attn_step64<false, PF>(st[0], qf[0], stg, 0, 64, c, hf, vfrag, bl[0], ci * 64);
+            if constexpr (decltype(two_tiles)::value) attn_step64<false, PF>(st[1], qf[1], stg, 0, 64, c, hf, vfrag, bl[1], ci * 64);
+        }
     };
     if (act[1]) {
-        for (int ci = 0; ci < nfull; ++ci) full_chunk(ci, std::true_type{});
+        for (int ci = c_lo; ci < nfull; ++ci) full_chunk(ci, std::true_type{});
     } else {
-        for (int ci = 0; ci < nfull; ++ci) full_chunk(ci, std::false_type{});
+        for (int ci = c_lo; ci < nfull; ++ci) full_chunk(ci, std::false_type{});
     }
-    for (int ci = nfull; ci < nchunks; ++ci) {             // at most one: the partial last chunk
+    for (int ci = WIN ? max(nfull, c_lo) : nfull; ci < nchunks; ++ci) {             // at most one: the partial last chunk
         turn(ci);
         char* stg = smem + (ci % ADMA_RING) * ADMA_STAGE;
         const int nkc = min(nk - ci * 64, 64);
@@ -599,6 +716,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (!act[j]) continue;
+            if constexpr (WIN) { if (!band[j].visits(ci * 64)) continue; }
             if (nkc < 64) attn_step64<true>(st[j], qf[j], stg, 0, nkc, c, hf, vfrag, bl[j], ci * 64);
             else attn_step64<false>(st[j], qf[j], stg, 0, 64, c, hf, vfrag, bl[j], ci * 64);
         }
@@ -607,13 +725,14 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     char* Os = smem + wave * (32 * 2 * DH);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-        if (act[j]) attn_store_tile(st[j], Os, ctx, off, q0[j], nq, H, head, lane);
+        if (act[j]) attn_store_tile<DH, WIN>(st[j], Os, ctx, off, q0[j], nq, H, head, lane);
 }
 
-template <int DH, bool BIAS = false>
+template <int DH, bool BIAS = false, bool WIN = false>
 __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* __restrict__ seq_off,
                                                              const int* __restrict__ seq_nk, const int* __restrict__ seq_nq, int H, int64_t capT, uint16_t* ctx, int heads, int nseq, int qgroups,
-                                                             AttnBiasArg<BIAS> ba) {
+                                                             AttnBiasArg<BIAS, WIN> ba) {
+    static_assert(!(BIAS && WIN), "a relative attention bias under a window is not instantiated");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // linear block id -> (pair p = b * heads + head, q-group qg).  Consecutive workgroups go to consecutive XCDs (id mod 8), and each XCD has its own L2:
     // the q-groups of one (sequence, head) read the same K / V^T stream, so they are placed 8 ids apart — same XCD, dispatched together — and the second
@@ -627,7 +746,10 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
     if (b >= nseq) return;                                 // the grid is padded to whole groups of 8 pairs
     const int nq = seq_nq[b];
     if (qg * ADMA_QT * 32 >= nq) return;                   // block-uniform (nq == 0 included)
-    if constexpr (BIAS) {
+    if constexpr (WIN) {
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 4>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+        else attn_dma_body<DH, 3>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+    } else if constexpr (BIAS) {
         if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 2>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
         else attn_dma_body<DH, 1>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
     } else {

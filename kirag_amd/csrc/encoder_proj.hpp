@@ -39,7 +39,8 @@ struct ProjArgs {
     const float* rot_cos; const float* rot_sin; const int* tpos; int max_pos; int dh;
 };
 
-enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4 };
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6 };
+constexpr bool epi_rotates(int epi) { return epi == EPI_QKV_ROT || epi == EPI_QKV_ROTB; }
 
 // The two epilogues of NomicBert handles combine feature pairs: a rotary pair (j, j + d_h / 2) of q or k, or gate and up of one intermediate feature.  The
 // packed weights are laid out (tile_pair_row, encoder_rows.hpp) so that on EVERY main loop both partners sit in one 32x32 accumulator tile, column cc < 16 with
@@ -67,6 +68,19 @@ __device__ __forceinline__ void rotate_tile(f32x16& v, const float* __restrict__
 __device__ __forceinline__ int64_t rot_row(const ProjArgs& a, int64_t t) {
     const int p = a.tpos[t];
     return (int64_t)((unsigned)p < (unsigned)a.max_pos ? p : 0) * (a.dh >> 1);
+}
+
+// the gated products of one register quad of a tile in tile-pair order (registers 4g .. 4g + 3 with 4g + 8 ..): silu(gate) * up, and ModernBert's
+// erf_gelu(input + b) * (gate + b') with EPI_GELU's erf-GELU (bi / bg: the biases of the quad's input and gate features)
+__device__ __forceinline__ float silu_mul(float g, float u);
+__device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x);
+__device__ __forceinline__ f32x4 swiglu_quad(const f32x16& v, int g) {
+    return f32x4{silu_mul(v[4 * g], v[4 * g + 8]), silu_mul(v[4 * g + 1], v[4 * g + 9]), silu_mul(v[4 * g + 2], v[4 * g + 10]), silu_mul(v[4 * g + 3], v[4 * g + 11])};
+}
+__device__ __forceinline__ f32x4 geglu_quad(const f32x16& v, int g, f32x4 bi, f32x4 bg) {
+    const f32x4 x = f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]} + bi, u = f32x4{v[4 * g + 8], v[4 * g + 9], v[4 * g + 10], v[4 * g + 11]} + bg;
+    const f32x2 lo = gelu_erf_fast2(f32x2{x.x, x.y}), hi = gelu_erf_fast2(f32x2{x.z, x.w});
+    return f32x4{lo.x, lo.y, hi.x, hi.y} * u;
 }
 
 // silu(g) u = g u / (1 + exp(-g)) in fp32: one v_exp_f32 and one v_rcp_f32 per element (exp overflows to +inf for g < -88: the quotient is then -0)
@@ -148,8 +162,9 @@ __device__ __forceinline__ void store_rows_bf16(AccTile<Shape>& acc, char* stage
 // EPI_SWIGLU: the wave's 64 GEMM columns are 2 tiles of (16 gate | 16 up) = 32 consecutive intermediate features: out[token, col0 + ni*16 + 8g + 4h ..] =
 // silu(gate) * up from registers 4g.. and 4g + 8.. (g < 2).  Staged like store_rows_bf16, as bf16 [32 tokens][64 B] (16-B chunk index XOR (token >> 2) & 3: 2-way
 // conflicts), read back 16 B per lane: every global store instruction writes sixteen whole aligned 64-B runs.  Same software pipeline over the mi blocks.
-template <class Shape, bool NT>
-__device__ __forceinline__ void store_rows_gated(AccTile<Shape>& acc, char* stage, uint16_t* __restrict__ out, int64_t ld, int64_t row0, int col0) {
+// f(v, ni, g) = the 4 products of registers 4g .. 4g + 3 of tile v with their partners 4g + 8 .. (EPI_SWIGLU: silu_mul; EPI_GEGLU: erf-GELU, with the biases)
+template <class Shape, bool NT, class F>
+__device__ __forceinline__ void store_rows_gated(AccTile<Shape>& acc, char* stage, uint16_t* __restrict__ out, int64_t ld, int64_t row0, int col0, F&& f) {
     static_assert(Shape::TN == 2, "stage geometry assumes 64 GEMM columns per wave");
     const int c = acc.lane & 31, h = acc.lane >> 5;
     const int r4 = acc.lane >> 2, ch = acc.lane & 3;
@@ -163,10 +178,10 @@ __device__ __forceinline__ void store_rows_gated(AccTile<Shape>& acc, char* stag
             for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    const f32x16& v = acc.v[mi][ni];
+                    const f32x4 p = f(acc.v[mi][ni], ni, g);
                     uint2 w;
-                    w.x = pack_bf16x2(silu_mul(v[4 * g], v[4 * g + 8]), silu_mul(v[4 * g + 1], v[4 * g + 9]));
-                    w.y = pack_bf16x2(silu_mul(v[4 * g + 2], v[4 * g + 10]), silu_mul(v[4 * g + 3], v[4 * g + 11]));
+                    w.x = pack_bf16x2(p.x, p.y);
+                    w.y = pack_bf16x2(p.z, p.w);
                     *reinterpret_cast<uint2*>(stage + c * 64 + (((ni * 2 + g) ^ ((c >> 2) & 3)) << 4) + h * 8) = w;
                 }
 #pragma unroll
@@ -218,8 +233,11 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
 //   EPI_QKV:   F = 3H: features [0,H) -> q (bias, log2(e) / sqrt(d_h) folded into the weights), [H,2H) -> k, [2H,3H) -> V^T (its bias lives in bo_eff)
 //   EPI_DENSE: out0[T,F] = acc as bf16 (k_ln adds the bias and the residual in fp32)
 //   EPI_GELU:  out0[T,F] = gelu(acc + bias)
+//   EPI_QKV_ROTB: EPI_QKV_ROT with the bias of q and k (in the rows' order, q's with the log2(e) / sqrt(d_h) fold) added BEFORE the rotation, as HF rotates
+//              Wqkv x + b (ModernBert handles that were given attn.Wqkv.bias)
 //   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV)
 //   EPI_SWIGLU:  F = 2 FF, gate | up interleaved per tile: out0[T, F / 2] = silu(gate) * up, no bias (NomicBert handles)
+//   EPI_GEGLU:   F = 2 FF, input | gate interleaved the same way: out0[T, F / 2] = erf_gelu(input + b) * (gate + b') (ModernBert handles; bias in the rows' order)
 template <int EPI, class ShapeE, bool NT>
 __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>& acc, int64_t m0, int64_t n0, char* stage) {
     const int64_t t0 = m0 + acc.m_wave;
@@ -230,7 +248,7 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
     if (a.epi_prio && ((a.epi_prio == 1) == (acc.m_wave >= 128))) __builtin_amdgcn_s_setprio(1);
     const int h = acc.lane >> 5;
     f32x4 b[2][4];                                // bias of the lane's 32 features: (ni, g) -> features ni*32 + 8g + 4h .. +3
-    if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {
+    if constexpr (EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_GEGLU) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -244,7 +262,7 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H,
                                     [&](f32x4 v, int mi, int ni, int g) { return v + b[ni][g]; });
         }
-    } else if constexpr (EPI == EPI_QKV_ROT) {
+    } else if constexpr (epi_rotates(EPI)) {
         const int region = f0 / a.H;
         if (region == 2) {
             store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - 2 * a.H);
@@ -258,6 +276,22 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             f32x4 cs[2][2], sn[2][2];
             store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H, [&](f32x4 v, int mi, int ni, int g) {
                 if (ni == 0 && g == 0) {
+                    if constexpr (EPI == EPI_QKV_ROTB) {
+                        // the bias of this block's 64 features goes into its accumulators first, a quad at a time.  The offset is opaque per block: hoisted
+                        // out of the store loop, the eight bias quads would be 32 more live registers next to the accumulators (the 256 x 256 tile, with 128 of them, has no
+                        // room even so: launch_proj gives this epilogue the 128 x 128 loops)
+                        int boff = f0 + 4 * h;
+                        asm volatile("" : "+v"(boff));
+#pragma unroll
+                        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                            for (int g2 = 0; g2 < 4; ++g2) {
+                                const f32x4 bq = *reinterpret_cast<const f32x4*>(a.bias + boff + n2 * 32 + 8 * g2);
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) acc.v[mi][n2][4 * g2 + i] += bq[i];
+                            }
+                        v = f32x4{acc.v[mi][0][0], acc.v[mi][0][1], acc.v[mi][0][2], acc.v[mi][0][3]};
+                    }
 #pragma unroll
                     for (int n2 = 0; n2 < 2; ++n2)
 #pragma unroll
@@ -274,7 +308,10 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             });
         }
     } else if constexpr (EPI == EPI_SWIGLU) {
-        store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1);
+        store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1, [](const f32x16& v, int, int g) { return swiglu_quad(v, g); });
+    } else if constexpr (EPI == EPI_GEGLU) {
+        // bias (tile-pair order like the rows): b[ni][g] are the input features of quad g < 2, b[ni][g + 2] their gates
+        store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1, [&](const f32x16& v, int ni, int g) { return geglu_quad(v, g, b[ni][g], b[ni][g + 2]); });
     } else if constexpr (EPI == EPI_DENSE) {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int, int, int) { return v; });   // the bias is added in k_ln (fp32)
     } else {
@@ -334,7 +371,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
     f32x4 bias4[4];                                       // multiplying waves: the bias of the lane's 16 features, requested before the main loop
     gemm_nt_skinny<ET, RING, WM, WN, true>(a.X, a.ldx, a.Tp, m0, a.W, a.K, a.F, n0, a.K, smem,
         [&](int64_t, int64_t f0) {
-            if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {
+            if constexpr (EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_GEGLU || EPI == EPI_QKV_ROTB) {
                 const int h = (threadIdx.x & 63) >> 5;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) bias4[g] = *reinterpret_cast<const f32x4*>(a.bias + f0 + 8 * g + 4 * h);   // QKV: the V third's slots are never used
@@ -342,19 +379,24 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         },
         [&](AccTile<ShapeSkinny>& acc, int64_t t0, int64_t f0) {
         const int c = acc.lane & 31, h = acc.lane >> 5;
-        if constexpr (EPI == EPI_SWIGLU) {                // the tile's 16 features: 8-byte row stores of silu(gate) * up
+        if constexpr (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) {      // the tile's 16 features: 8-byte row stores of silu(gate) * up / erf_gelu(input) * gate
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                const f32x16& v = acc.v[0][0];
+                f32x4 p;
+                if constexpr (EPI == EPI_SWIGLU) p = swiglu_quad(acc.v[0][0], g); else p = geglu_quad(acc.v[0][0], g, bias4[g], bias4[g + 2]);
                 uint2 w;
-                w.x = pack_bf16x2(silu_mul(v[4 * g], v[4 * g + 8]), silu_mul(v[4 * g + 1], v[4 * g + 9]));
-                w.y = pack_bf16x2(silu_mul(v[4 * g + 2], v[4 * g + 10]), silu_mul(v[4 * g + 3], v[4 * g + 11]));
+                w.x = pack_bf16x2(p.x, p.y);
+                w.y = pack_bf16x2(p.z, p.w);
                 *reinterpret_cast<uint2*>(a.out0 + (t0 + c) * a.ldo + ((int)f0 >> 1) + 8 * g + 4 * h) = w;
             }
             return;
         }
-        if constexpr (EPI == EPI_QKV_ROT) {
-            if ((int)f0 < 2 * a.H) {                      // q and k: rotated in place, then stored like EPI_QKV's
+        if constexpr (epi_rotates(EPI)) {
+            if ((int)f0 < 2 * a.H) {                      // q and k: (biased and) rotated in place, then stored like EPI_QKV's
+                if constexpr (EPI == EPI_QKV_ROTB) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc.v[0][0][r] += bias4[r >> 2][r & 3];
+                }
                 const int64_t o = rot_row(a, t0 + c) + 4 * h + rot_jbase(a.dh, (int)f0);
                 rotate_tile(acc.v[0][0], a.rot_cos + o, a.rot_sin + o);
             }
@@ -363,7 +405,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         for (int g = 0; g < 4; ++g) {
             f32x4 v = {acc.v[0][0][4 * g], acc.v[0][0][4 * g + 1], acc.v[0][0][4 * g + 2], acc.v[0][0][4 * g + 3]};
             const int f = (int)f0 + 8 * g + 4 * h;        // first of the lane's 4 consecutive features
-            if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_ROT) {
+            if constexpr (EPI == EPI_QKV || epi_rotates(EPI)) {
                 const int region = (int)f0 / a.H;
                 if (region == 2) {                        // V^T [feature, token]; its bias lives in bo_eff
 #pragma unroll

@@ -222,15 +222,39 @@ struct Ln16 {
             }
         }
     }
-    // v = (y + bias) + residual, the residual decoded from its 16-bit half and its low-half byte
+    // v = (y + bias) + residual, the residual decoded from its 16-bit half and its low-half byte.  KEEP_INF (k_ln16_pre): a non-finite high half decodes to
+    // itself (lo_decode_final).  The post-LN stack needs no such care — its residual is the GEMM operand, so an overflow reaches the next LayerNorm through y —
+    // but nothing else ever reads the pre-LN residual stream: decoded on the bit patterns, an overflowed element would come back as a finite 3.4e38, the row
+    // would normalise to beta and the overflow would never reach the error word
+    template <bool KEEP_INF = false>
     __device__ __forceinline__ void combine(const uint4 (&a)[NS], const uint4 (&rh)[NS], const uint2 (&rl)[NS], float (&v)[NS][8]) const {
+        auto dec = [](unsigned int byte, float hf) { if constexpr (KEEP_INF) return lo_decode_final(byte, hf); else return lo_decode(byte, hf); };
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const unsigned int aw[4] = {a[j].x, a[j].y, a[j].z, a[j].w}, hw[4] = {rh[j].x, rh[j].y, rh[j].z, rh[j].w}, lw[2] = {rl[j].x, rl[j].y};
 #pragma unroll
             for (int c = 0; c < 4; ++c) {   // elements 2c, 2c + 1: low-half bytes 2c, 2c + 1 of the 8
-                v[j][2 * c] = (unpack_lo16(aw[c]) + yb[j][2 * c]) + lo_decode((lw[c >> 1] >> (16 * (c & 1))) & 0xffu, unpack_lo16(hw[c]));
-                v[j][2 * c + 1] = (unpack_hi16(aw[c]) + yb[j][2 * c + 1]) + lo_decode((lw[c >> 1] >> (16 * (c & 1) + 8)) & 0xffu, unpack_hi16(hw[c]));
+                v[j][2 * c] = (unpack_lo16(aw[c]) + yb[j][2 * c]) + dec((lw[c >> 1] >> (16 * (c & 1))) & 0xffu, unpack_lo16(hw[c]));
+                v[j][2 * c + 1] = (unpack_hi16(aw[c]) + yb[j][2 * c + 1]) + dec((lw[c >> 1] >> (16 * (c & 1) + 8)) & 0xffu, unpack_hi16(hw[c]));
+            }
+        }
+    }
+    // pre-LN residual stream: the 16-bit high half of v and (rlo_row != nullptr) its low-half bytes, the same codec as the LayerNorm output's
+    __device__ __forceinline__ void store_residual(const float (&v)[NS][8], int H, int lane, uint16_t* rb_row, uint8_t* rlo_row) const {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+            if (i < H) {
+                unsigned int ob[4], ol[2] = {0u, 0u};
+#pragma unroll
+                for (int c = 0; c < 4; ++c) ob[c] = pack_bf16x2(v[j][2 * c], v[j][2 * c + 1]);
+                *reinterpret_cast<uint4*>(rb_row + i) = make_uint4(ob[0], ob[1], ob[2], ob[3]);
+                if (rlo_row) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        ol[c >> 1] |= (lo_encode(v[j][2 * c], unpack_lo16(ob[c])) | (lo_encode(v[j][2 * c + 1], unpack_hi16(ob[c])) << 8)) << (16 * (c & 1));
+                    *reinterpret_cast<uint2*>(rlo_row + i) = make_uint2(ol[0], ol[1]);
+                }
             }
         }
     }
@@ -313,6 +337,43 @@ __global__ __launch_bounds__(256) void k_ln16(const uint16_t* __restrict__ y, co
         ln.combine(a, rh, rl, v);
         load_row(t + step);                                   // next row's loads in flight while this one is reduced and stored
         ln.template normalize_store<(POL & 4) != 0>(v, H, eps, lane, xb + t * H, xlo ? xlo + t * H : nullptr);
+    }
+}
+
+// Pre-LN stacks (ModernBert handles): the residual stream r (rb 16-bit high half + optional rlo low-half bytes) is kept apart from the normalised MFMA operand
+// xb.  One launch does  r = (y + bias) + r_in;  store r (rb_out != nullptr: not behind the last layer);  xb = LayerNorm(r)  (+ its low half into xlo, the final
+// LayerNorm only: pooling and kr_encoder_last_hidden read it).  r_in may be the embedding LayerNorm's output in xb itself (layer 0): a wave reads its whole row
+// before it stores it.  Same row arithmetic as k_ln16 (Ln16).
+template <int NS, int POL = 0>
+__global__ __launch_bounds__(256) void k_ln16_pre(const uint16_t* __restrict__ y, const float* __restrict__ ybias, const int* __restrict__ Tp, const float* __restrict__ g,
+                                                  const float* __restrict__ bta, float eps, int H, const uint16_t* rb_in, const uint8_t* rlo_in, uint16_t* rb_out,
+                                                  uint8_t* rlo_out, uint8_t* xlo, uint16_t* xb) {
+    const int lane = threadIdx.x & 63;
+    const int T = *Tp;
+    Ln16<NS> ln;
+    ln.load_params(g, bta, ybias, H, lane);
+    const int64_t step = (int64_t)gridDim.x * 4;
+    int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    uint4 a[NS], rh[NS]; uint2 rl[NS];
+    auto load_row = [&](int64_t row) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+            a[j] = rh[j] = make_uint4(0u, 0u, 0u, 0u); rl[j] = make_uint2(0x80808080u, 0x80808080u);      // byte 128 = a zero low half
+            if (i < H && row < T) {
+                a[j] = (POL & 1) ? __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(y + row * H + i))) : *reinterpret_cast<const uint4*>(y + row * H + i);
+                rh[j] = *reinterpret_cast<const uint4*>(rb_in + row * H + i);
+                if (rlo_in) rl[j] = *reinterpret_cast<const uint2*>(rlo_in + row * H + i);
+            }
+        }
+    };
+    load_row(t);
+    for (; t < T; t += step) {
+        float v[NS][8];
+        ln.template combine<true>(a, rh, rl, v);          // an overflowed residual element stays inf: the row becomes NaN and reaches the error word (k_pool)
+        load_row(t + step);                                   // next row's loads in flight while this one is reduced and stored
+        if (rb_out) ln.store_residual(v, H, lane, rb_out + t * H, rlo_out ? rlo_out + t * H : nullptr);
+        ln.template normalize_store<false>(v, H, eps, lane, xb + t * H, xlo ? xlo + t * H : nullptr);
     }
 }
 

@@ -30,6 +30,13 @@ of every head are rotated by the token's column (rotary embeddings, NeoX pairing
 ``down(silu(gate(x)) * up(x))`` (gate | up run as one projection whose epilogue writes the product), no linear biases, and state-dict names of its own.  The
 handle learns the frequencies through ``config.rotary_inv_freq`` (HF's ``rotary_emb.inv_freq``, so every static rope variant of HF is covered).
 ``NomicBertE5Encoder`` / ``NomicBertBGEEncoder`` are the twins over ``transformers.NomicBertModel``, reached through the same dispatch.
+
+ModernBERT checkpoints (``model_type`` modernbert: gte-modernbert-base, modernbert-embed, granite-embedding-english-r2, ModernBERT fine-tunes): a PRE-LN stack
+— the residual stream is kept apart from the normalised operand — without a position table or token types, rotary q / k with one frequency vector per layer
+type, the gated MLP ``Wo(gelu(input) * gate)`` with input | gate as one projection, and sliding-window attention (``|column distance| <= sliding_window``) in
+the layers ``config.layer_types`` names.  The handle learns all of it through reserved names (``MODERN_SETTINGS``).  An ``intermediate_size`` that is no
+multiple of 128 (ModernBERT-large: 2624) is zero-padded to the next one (``pad_modernbert_ff``: exact).  ``ModernBertE5Encoder`` / ``ModernBertBGEEncoder``
+are the twins over ``transformers.ModernBertModel``.
 """
 from __future__ import annotations
 
@@ -39,7 +46,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, MPNetModel, NomicBertModel, PretrainedConfig, XLMRobertaModel
+from transformers import BertModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, XLMRobertaModel
 
 from .. import _lib
 
@@ -49,6 +56,10 @@ ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
 MPNET_TYPE = "mpnet"
 MPNET_PADDING_IDX = 1    # MPNetEmbeddings.padding_idx: a class constant of HF's implementation, not config.pad_token_id
 NOMIC_TYPE = "nomic_bert"
+MODERN_TYPE = "modernbert"
+# reserved names of a ModernBert handle's settings (include/kirag_amd.h): the local layers' rotary frequencies, the half-window, one 0 / 1 flag per layer
+MODERN_SETTINGS = ("config.rotary_inv_freq_local", "config.attention_half_window", "config.local_attention_layers")
+MODERN_LAYER_TYPES = ("full_attention", "sliding_attention")
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
 
 
@@ -56,6 +67,27 @@ def average_pool(last_hidden_states: Tensor, attention_mask: Tensor) -> Tensor:
     """retriever/encoders.py:56-58 (used by the training path only; the HIP path pools in-kernel)."""
     last_hidden = last_hidden_states.masked_fill(~attention_mask[..., None].bool(), 0.0)
     return last_hidden.sum(dim=1) / attention_mask.sum(dim=1)[..., None]
+
+
+def pad_modernbert_ff(name: str, w, ff: int, ff_pad: int):
+    """A ModernBERT MLP tensor for a handle whose intermediate size is ``ff_pad`` >= ``ff`` (the next multiple of 128): zero rows behind BOTH halves of
+    ``mlp.Wi`` (input | gate, so the halves stay ``chunk(2)``-able) and its bias, zero columns behind ``mlp.Wo``.  Exact: a padded intermediate feature is
+    ``gelu(0) * 0 = 0`` and meets a zero column.  Every other tensor (and ``ff_pad == ff``) is returned as it is.  ``w``: torch tensor or numpy array."""
+    if ff_pad == ff or ".mlp." not in "." + name:
+        return w
+    is_np = not isinstance(w, Tensor)
+    t = torch.as_tensor(w)
+    if name.endswith("mlp.Wi.weight") or name.endswith("mlp.Wi.bias"):
+        halves = t.reshape(2, ff, *t.shape[1:])
+        out = torch.zeros((2, ff_pad) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        out[:, :ff] = halves
+        out = out.reshape(2 * ff_pad, *t.shape[1:])
+    elif name.endswith("mlp.Wo.weight"):
+        out = torch.zeros((t.shape[0], ff_pad), dtype=t.dtype, device=t.device)
+        out[:, :ff] = t
+    else:
+        return w
+    return out.numpy() if is_np else out
 
 
 class HipBertForward:
@@ -66,8 +98,10 @@ class HipBertForward:
         low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it)."""
         lib = _lib.load()
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
+        self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
         inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
-        if not self.is_nomic and getattr(config, "hidden_act", "gelu") != "gelu":
+        modern = self._modern_settings(config) if self.is_modern else None      # likewise
+        if not self.is_nomic and not self.is_modern and getattr(config, "hidden_act", "gelu") != "gelu":
             raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
         if getattr(config, "position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only absolute position embeddings are implemented")
@@ -76,9 +110,13 @@ class HipBertForward:
             raise ValueError(f"relative_attention_num_buckets={config.relative_attention_num_buckets}: MPNet's bias table has {MPNET_BUCKETS} buckets "
                              "(the only size HF's MPNetEncoder computes with)")
         # MPNet has no token types: one row of zeros stands in for the table (sync supplies it)
-        type_vocab = 1 if self.is_mpnet else config.type_vocab_size
-        cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, config.intermediate_size,
-                           config.vocab_size, config.max_position_embeddings, type_vocab, float(config.layer_norm_eps))
+        # ... and neither has ModernBERT; its intermediate size is rounded up to the projections' 128 (pad_modernbert_ff)
+        type_vocab = 1 if self.is_mpnet or self.is_modern else config.type_vocab_size
+        self.ff = int(config.intermediate_size)
+        self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
+        eps = float(config.norm_eps if self.is_modern else config.layer_norm_eps)
+        cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff_pad,
+                           config.vocab_size, config.max_position_embeddings, type_vocab, eps)
         h = C.c_void_p()
         dt = -1 if operand_dtype is None else {"bf16": 0, "f16": 1}[operand_dtype]
         lo = -1 if residual_lo is None else int(bool(residual_lo))
@@ -101,6 +139,43 @@ class HipBertForward:
         # rotary positions travel the same way ("config.rotary_inv_freq", d_h / 2 values) and make the handle a NomicBert handle for life
         if inv_freq is not None:
             _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", inv_freq.data_ptr(), inv_freq.numel()))
+        # a ModernBert handle: the global frequencies under the same name, then its own three settings
+        if modern is not None:
+            for name, t in modern.items():
+                _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
+
+    @staticmethod
+    def _modern_settings(config) -> dict:
+        """The settings of a ModernBert handle from an HF ``ModernBertConfig``, by reserved name: both ``inv_freq`` vectors from HF's own
+        ``ModernBertRotaryEmbedding`` built on the CPU, the half-window (``config.sliding_window`` = ``local_attention // 2``, inclusive) and one flag per layer
+        (1 = ``sliding_attention``).  ``NotImplementedError`` naming the field for what the kernels do not compute."""
+        from transformers.models.modernbert.modeling_modernbert import ModernBertRotaryEmbedding
+        if getattr(config, "hidden_activation", "gelu") != "gelu":
+            raise NotImplementedError(f"hidden_activation={config.hidden_activation!r}: the gated MLP of a {MODERN_TYPE} handle implements erf-GELU only")
+        d_h = config.hidden_size // config.num_attention_heads
+        if (getattr(config, "head_dim", None) or d_h) != d_h:
+            raise NotImplementedError(f"head_dim={config.head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+        types = list(config.layer_types)
+        unknown = sorted(set(types) - set(MODERN_LAYER_TYPES))
+        if unknown or len(types) != config.num_hidden_layers:
+            raise NotImplementedError(f"layer_types={types!r}: one of {MODERN_LAYER_TYPES} per layer is implemented")
+        rope = ModernBertRotaryEmbedding(config)
+        freq = {}
+        for t in set(types):
+            scaling = float(getattr(rope, f"{t}_attention_scaling"))
+            if scaling != 1.0:
+                raise NotImplementedError(f"attention_scaling={scaling} ({t}, rope_type {rope.rope_type[t]!r}): only rope variants with attention_scaling 1.0 "
+                                          "are implemented")
+            freq[t] = getattr(rope, f"{t}_inv_freq").detach().to(device="cpu", dtype=torch.float32).contiguous()
+        out = {"config.rotary_inv_freq": freq.get("full_attention", freq.get("sliding_attention"))}
+        if "sliding_attention" in freq:
+            w = int(config.sliding_window)
+            if w < 1:
+                raise NotImplementedError(f"local_attention={config.local_attention}: the half-window local_attention // 2 must be at least 1")
+            out[MODERN_SETTINGS[0]] = freq["sliding_attention"]
+            out[MODERN_SETTINGS[1]] = torch.tensor([float(w)], dtype=torch.float32)
+        out[MODERN_SETTINGS[2]] = torch.tensor([1.0 if t == "sliding_attention" else 0.0 for t in types], dtype=torch.float32)
+        return out
 
     @staticmethod
     def _nomic_inv_freq(config) -> Tensor:
@@ -160,7 +235,7 @@ class HipBertForward:
         if fp == self.fingerprint:
             return
         for name, p in params:
-            t = p.detach()
+            t = pad_modernbert_ff(name, p.detach(), self.ff, self.ff_pad)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
@@ -169,7 +244,7 @@ class HipBertForward:
         self.fingerprint = fp
 
     def _load_zero_token_types(self) -> None:
-        if self.is_mpnet:
+        if self.is_mpnet or self.is_modern:
             z = torch.zeros(self.hidden, dtype=torch.float32)
             _lib.check(self._lib.kr_encoder_load_weight(self._h, b"embeddings.token_type_embeddings.weight", z.data_ptr(), z.numel()))
 
@@ -177,6 +252,7 @@ class HipBertForward:
         """Load weights from a mapping HF-state-dict-name -> numpy array / tensor (host or device)."""
         import numpy as np
         for name, w in state.items():
+            w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
             if isinstance(w, np.ndarray):
                 w = np.ascontiguousarray(w, dtype=np.float32)
                 ptr, n = w.ctypes.data, w.size
@@ -351,7 +427,7 @@ class _HipSentenceMixin:
         return out
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        kw = {} if self._hf_base is MPNetModel else {"token_type_ids": token_type_ids}     # MPNet has no token types
+        kw = {} if self._hf_base in (MPNetModel, ModernBertModel) else {"token_type_ids": token_type_ids}     # MPNet and ModernBERT have no token types
         out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
@@ -377,6 +453,7 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _roberta_twin = None             # the same encoder over XLMRobertaModel (set below)
     _mpnet_twin = None               # ... and over MPNetModel
     _nomic_twin = None               # ... and over NomicBertModel
+    _modern_twin = None              # ... and over ModernBertModel
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -399,6 +476,9 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
         if model_type == NOMIC_TYPE:
             # other layer names, no position table, a gated MLP: nothing of it fits BertModel
             return cls._nomic_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type == MODERN_TYPE:
+            # a pre-LN stack under names of its own
+            return cls._modern_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -412,6 +492,15 @@ class _HipMPNetSentenceEncoder(_HipSentenceMixin, MPNetModel):
 
 class _HipNomicSentenceEncoder(_HipSentenceMixin, NomicBertModel):
     _hf_base = NomicBertModel
+
+
+class _HipModernBertSentenceEncoder(_HipSentenceMixin, ModernBertModel):
+    _hf_base = ModernBertModel
+
+    def __init__(self, config, add_pooling_layer=False, **kwargs):
+        ModernBertModel.__init__(self, config)      # ModernBertModel has no pooling layer to ask for
+        self.kwargs = kwargs
+        self._hip = None
 
 
 class E5Encoder(_HipSentenceEncoder):
@@ -454,12 +543,24 @@ class NomicBertBGEEncoder(_HipNomicSentenceEncoder):
     _pool = POOL_CLS
 
 
+class ModernBertE5Encoder(_HipModernBertSentenceEncoder):
+    """ModernBertModel -> masked mean -> L2 normalise (nomic-ai/modernbert-embed-base)"""
+    _pool = POOL_MEAN
+
+
+class ModernBertBGEEncoder(_HipModernBertSentenceEncoder):
+    """ModernBertModel -> [:, 0] -> L2 normalise (Alibaba-NLP/gte-modernbert-base, ibm-granite/granite-embedding-english-r2)"""
+    _pool = POOL_CLS
+
+
 E5Encoder._roberta_twin = XLMRobertaE5Encoder
 BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
 E5Encoder._mpnet_twin = MPNetE5Encoder
 BGEEncoder._mpnet_twin = MPNetBGEEncoder
 E5Encoder._nomic_twin = NomicBertE5Encoder
 BGEEncoder._nomic_twin = NomicBertBGEEncoder
+E5Encoder._modern_twin = ModernBertE5Encoder
+BGEEncoder._modern_twin = ModernBertBGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:

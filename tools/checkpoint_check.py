@@ -6,7 +6,10 @@ tolerance on YOUR weights, and could a cheaper mode be used?
 
 <hf_dir> is any HF BERT-family checkpoint directory (config.json + weights; e5-large-v2 / bge-large-en: retriever/e5.py:18-19 of the reference) or a
 MPNet one (model_type mpnet: all-mpnet-base-v2, multi-qa-mpnet-*; reference MPNetModel in fp32, GPU only), a NomicBert one (model_type nomic_bert:
-nomic-embed-text-v1 / -v1.5; reference NomicBertModel in fp32, GPU only: rotary positions and the gated MLP are not in the torch emulation) or a
+nomic-embed-text-v1 / -v1.5; reference NomicBertModel in fp32, GPU only: rotary positions and the gated MLP are not in the torch emulation), a ModernBERT
+one (model_type modernbert: gte-modernbert-base, modernbert-embed, granite-embedding-english-r2; reference ModernBertModel in fp32 with eager attention, GPU
+only; "LN1" / "LN2" are then the PRE-LN residual stream behind the attention and behind the MLP — the stream whose large-magnitude channels decide whether
+f16 operands stay in range, which no synthetic recipe of this repository was fitted to: this tool is how to find out) or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -94,7 +97,18 @@ def reference_and_stats(model, batches, pool, dev):
             stats[li]["max16"] = max(stats[li]["max16"], float(t.detach()[cur["mask"]].abs().max()))
         return fn
     nomic = hasattr(model, "layers")                   # NomicBertModel: layers.N.{self_attn, mlp, post_attention_layernorm, post_mlp_layernorm}
+    modern = nomic and hasattr(model, "final_norm")    # ModernBertModel: layers.N.{attn_norm, attn, mlp_norm, mlp}
     for li, layer in enumerate(model.layers if nomic else model.encoder.layer):
+        if modern:
+            # the residual stream itself (16-bit high half + low byte on the device) is what mlp_norm reads (behind the attention) and what the layer returns;
+            # 16-bit-stored: q | k | v, the attention output projection, the LayerNorm outputs (the operands), the gated product, the MLP output
+            att, mlp = layer.attn, layer.mlp
+            hooks.append(layer.mlp_norm.register_forward_pre_hook(lambda _m, inp, f=grab(li, "ln1"): f(_m, inp, inp[0])))
+            hooks.append(layer.register_forward_hook(grab(li, "ln2")))
+            for key, mod in (("qkv", att.Wqkv), ("y1", att.Wo), ("x1", layer.mlp_norm), ("y2", mlp.Wo)):
+                hooks.append(mod.register_forward_hook(grab(li, key)))
+            hooks.append(mlp.Wo.register_forward_pre_hook(lambda _m, inp, f=grab(li, "h"): f(_m, inp, inp[0])))
+            continue
         if nomic:
             att, mlp = layer.self_attn, layer.mlp      # q / k before the rotation (a rotation keeps their size); "h" = what the gated projection stores
             for key, mod in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("y1", att.o_proj), ("ln1", layer.post_attention_layernorm),
@@ -153,17 +167,20 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
-    from kirag_amd.retriever.encoders import MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
-    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE) + ROBERTA_TYPES:
+    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
+    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2) and NomicBert (nomic-embed-text-v1 / -v1.5)")
-    model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5) and ModernBERT")
+    if cfg.model_type == MODERN_TYPE:
+        model = AutoModel.from_pretrained(hf_dir, attn_implementation="eager")      # ModernBertModel has no pooling layer
+    else:
+        model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
     return check_model(model, args, hf_dir)
 
 
 def check_model(model, args, hf_dir="(in-memory model)"):
     """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
-    from kirag_amd.retriever.encoders import MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
+    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
     mpnet = getattr(cfg, "model_type", "bert") == MPNET_TYPE
@@ -173,6 +190,9 @@ def check_model(model, args, hf_dir="(in-memory model)"):
                          ", which the torch emulation does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == NOMIC_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has rotary positions and a gated MLP, which the torch emulation does not implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") == MODERN_TYPE and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with rotary positions, a gated MLP and sliding-window attention, which the torch "
+                         "emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
     batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)

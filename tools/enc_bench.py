@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global ...] [--pool mean|cls] [--hf-fp16]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -29,7 +29,16 @@ MPNET_BASE_NOBIAS = dict(XLMR_BASE, vocab_size=30527)
 NOMIC_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, vocab_size=30528, max_position_embeddings=8192,
                   type_vocab_size=2, layer_norm_eps=1e-12, hidden_act="silu", model_type="nomic_bert", head_dim=64,
                   rope_parameters={"rope_theta": 1000.0, "rope_type": "default"})
-SHAPES = dict(BS.ENCODER_SHAPES, **{"xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# ModernBERT-base (gte-modernbert-base, modernbert-embed-base, granite-embedding-english-r2): pre-LN, GeGLU with FF 1152 (2 FF = 2304 columns in one
+# projection), two of every three layers under a sliding window of +-64 columns; modernbert-base-global: the same with every layer global (a handle-level
+# setting: transformers' own config cannot say it) — what the window saves is the difference of the two
+MODERNBERT_BASE = dict(hidden_size=768, num_hidden_layers=22, num_attention_heads=12, intermediate_size=1152, vocab_size=50368, max_position_embeddings=8192,
+                       norm_eps=1e-5, hidden_activation="gelu", model_type="modernbert", local_attention=128, sliding_window=64,
+                       layer_types=["sliding_attention" if i % 3 else "full_attention" for i in range(22)],
+                       rope_parameters={"full_attention": {"rope_type": "default", "rope_theta": 160000.0},
+                                        "sliding_attention": {"rope_type": "default", "rope_theta": 10000.0}})
+MODERNBERT_BASE_GLOBAL = dict(MODERNBERT_BASE, layer_types=["full_attention"] * 22)
+SHAPES = dict(BS.ENCODER_SHAPES, **{"modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -61,6 +70,8 @@ def hf_classes(cfg):
     """(config class, model class, sentence-encoder module) of a shape: the RoBERTa family by its model_type"""
     import transformers as T
     from kirag_amd.retriever import encoders as ENC
+    if cfg.get("model_type") == ENC.MODERN_TYPE:
+        return T.ModernBertConfig, T.ModernBertModel, (ENC.ModernBertE5Encoder if args.pool == "mean" else ENC.ModernBertBGEEncoder)
     if cfg.get("model_type") == ENC.NOMIC_TYPE:
         return T.NomicBertConfig, T.NomicBertModel, (ENC.NomicBertE5Encoder if args.pool == "mean" else ENC.NomicBertBGEEncoder)
     if cfg.get("model_type") == ENC.MPNET_TYPE:
@@ -73,15 +84,32 @@ def hf_classes(cfg):
 def make_encoder(cfg):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw)"""
-    if cfg.get("model_type") not in ("mpnet", "nomic_bert"):
+    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert"):
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
     from kirag_amd.retriever.encoders import HipBertForward
     ns = SimpleNamespace(**cfg)
     enc = HipBertForward(ns, 0)
+    if cfg["model_type"] == "modernbert":      # synthetic_state reads BERT's field names
+        ns = SimpleNamespace(**dict(cfg, type_vocab_size=1, layer_norm_eps=cfg["norm_eps"]))
     state = dict(BS.synthetic_state(ns, dev, 0))
     g = torch.Generator(device=dev); g.manual_seed(977)
-    if cfg["model_type"] == "nomic_bert":
+    if cfg["model_type"] == "modernbert":
+        # the same draws under ModernBert's names: Wqkv = q | k | v, mlp.Wi = the intermediate matrix | a second draw, LayerNorm weights in their pre-LN places
+        L, b = cfg["num_hidden_layers"], "encoder.layer."
+        st = {"embeddings.tok_embeddings.weight": state["embeddings.word_embeddings.weight"], "embeddings.norm.weight": state["embeddings.LayerNorm.weight"],
+              "final_norm.weight": state[f"{b}{L - 1}.output.LayerNorm.weight"]}
+        for l in range(L):
+            if l:
+                st[f"layers.{l}.attn_norm.weight"] = state[f"{b}{l - 1}.output.LayerNorm.weight"]
+            st[f"layers.{l}.attn.Wqkv.weight"] = torch.cat([state[f"{b}{l}.attention.self.{n}.weight"] for n in ("query", "key", "value")])
+            st[f"layers.{l}.attn.Wo.weight"] = state[f"{b}{l}.attention.output.dense.weight"]
+            st[f"layers.{l}.mlp_norm.weight"] = state[f"{b}{l}.attention.output.LayerNorm.weight"]
+            wi = state[f"{b}{l}.intermediate.dense.weight"]
+            st[f"layers.{l}.mlp.Wi.weight"] = torch.cat([wi, 0.02 * torch.randn(wi.shape, generator=g, device=dev)])
+            st[f"layers.{l}.mlp.Wo.weight"] = state[f"{b}{l}.output.dense.weight"]
+        state = st
+    elif cfg["model_type"] == "nomic_bert":
         names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),
                  ("attention.output.dense.", "self_attn.o_proj."), ("attention.output.LayerNorm.", "post_attention_layernorm."),
                  ("intermediate.dense.", "mlp.gate_proj."), ("output.dense.", "mlp.down_proj."), ("output.LayerNorm.", "post_mlp_layernorm."))
@@ -134,6 +162,9 @@ for shape in args.shape or ["e5-large"]:
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
     if cfg.get("model_type") == "nomic_bert":      # the third intermediate matrix: + 8 H^2 per token and layer (FF = 4 H)
         fl += float(mask.sum()) * cfg["num_hidden_layers"] * 8.0 * cfg["hidden_size"] ** 2
+    if cfg.get("model_type") == "modernbert":      # FF is not 4 H: 8 H^2 (q, k, v, o) + 6 H FF (input, gate, out) per token and layer; the attention FLOPs are
+        lens = mask.sum(1).double()                # counted as global in both shapes (what the window saves shows as rate)
+        fl = float((cfg["num_hidden_layers"] * lens * (8.0 * cfg["hidden_size"] ** 2 + 6.0 * cfg["hidden_size"] * cfg["intermediate_size"] + 4.0 * lens * cfg["hidden_size"])).sum())
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
           f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
