@@ -92,6 +92,11 @@ int kr_index_add_raw(kr_index* ix, const float* xf, const uint16_t* xc, int64_t 
  * Result definition (identical to oracle/search_c.c): score = the EXACT inner product of the fp32 inputs rounded once to
  * fp32 (round-to-nearest-even; independent of any summation order); ranking by (score desc, row asc); rows whose score is
  * NaN are never returned.  0 < k <= min(ntotal, 1024), else KR_EINVAL.
+ * Magnitudes: the guarantee covers ALL of fp32 - rows and queries of any norm, subnormal elements, scores that round to zero, to a subnormal
+ * or to +-inf, rows and queries with +-inf or NaN elements (a score is then +-inf or NaN as in IEEE arithmetic; +inf scores tie and resolve by
+ * row asc).  The certificate's error bounds are computed in fp64 and rounded up, so no magnitude makes pass 1 claim more than it knows.
+ * Zero rule: -0.0 and +0.0 are ONE score.  They tie (the lower row wins), and a zero score may come back with either sign (today: +0.0
+ * from every search and from kr_score_topk; the merges pass on what they are given).  Every non-zero score is bit-exact.
  * `mode`: 0 = auto: pass 1 = 16-bit MFMA scan + certified exact re-rank for all queries; pass 2 = fp64 MFMA scan of the fp32 rows
  *             + certified re-rank for the queries pass 1 could not certify (they share one pass over the corpus per group of
  *             32); pass 3 = exact scan, query by query, for what is left (mass ties);

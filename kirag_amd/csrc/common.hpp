@@ -63,7 +63,10 @@ struct F16 {
 };
 
 // ---- order-preserving float <-> uint ------------------------------------------------------------------------
-// larger float  <=> larger uint; NaN maps to 0 (ranks below everything, never beats a real score)
+// larger float  <=> larger uint; NaN maps to 0 (ranks below everything, never beats a real score).  -0.0 and +0.0 are ONE score (they compare equal
+// in the header's rule, in the oracle and in the merges), so -0.0 takes the ordinal of +0.0: zeros tie, the lower row wins, and a zero score that went
+// through a key comes back as +0.0.  (With distinct ordinals every +0 row ranked above every -0 row, and a shard's list was not sorted in the sense
+// kr_topk_merge / k_merge_lists assume.)
 __host__ __device__ __forceinline__ uint32_t f32_ord(float f) {
     uint32_t u;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -72,10 +75,10 @@ __host__ __device__ __forceinline__ uint32_t f32_ord(float f) {
     __builtin_memcpy(&u, &f, 4);
 #endif
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return (u & 0x80000000u) ? 0u - u : (u | 0x80000000u);   // negatives: two's-complement negation, so -0.0 (0x80000000) lands on +0.0's ordinal
 }
 __host__ __device__ __forceinline__ float ord_f32(uint32_t o) {
-    uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : (o ? 0u - o : 0x7fc00000u);   // ordinal 0 is NaN
     float f;
 #if defined(__HIP_DEVICE_COMPILE__)
     f = __builtin_bit_cast(float, u);
@@ -96,6 +99,24 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int m) {
     lo = __shfl_xor(lo, m, 64);
     hi = __shfl_xor(hi, m, 64);
     return __hiloint2double(hi, lo);
+}
+
+// ---- error bounds over the whole fp32 range --------------------------------------------------------------------------------------------
+// The norms that enter a certificate's error bound are accumulated in fp64: the square of ANY finite fp32 value is an exact, normal fp64 number
+// ((2^-149)^2 = 2^-298, (2^128)^2 = 2^256), whereas in fp32 the squares of values below ~2^-64 are subnormal or 0 and the bound silently loses the
+// rows / queries it is about.  A bound is stored as fp32 rounded UP; a non-zero value below FLT_MIN is stored as FLT_MIN (products of stored
+// bounds then keep their relative precision), NaN and inf pass through.
+__device__ __forceinline__ float bound_up_f32(double v) {
+    float f = (float)v;                                            // round to nearest; v >= 0, inf or NaN
+    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);   // next float up (f finite and >= 0 here: FLT_MAX + 1 ulp is inf)
+    if (v > 0.0 && f < 1.17549435e-38f) f = 1.17549435e-38f;
+    return f;
+}
+__device__ __forceinline__ void sq_acc(double& acc, double a) { acc = __builtin_fma(a, a, acc); }
+// one element of a 16-bit rounding: |c|^2 and |v - c|^2 (the difference of two fp32 values is exact in fp64)
+__device__ __forceinline__ void sq_acc_pair(double& e2, double& c2, float v, float c) {
+    const double dc = (double)c;
+    sq_acc(e2, (double)v - dc); sq_acc(c2, dc);
 }
 
 // ---- canonical score ----------------------------------------------------------------------------------------------------------------------

@@ -199,21 +199,25 @@ __global__ __launch_bounds__(256) void k_add_rows(const float* __restrict__ xf, 
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
         const float* src = xf + row * d;
         uint16_t* dst = xc + row * dpad;
-        float e2 = 0.f, c2 = 0.f;
+        double e2 = 0.0, c2 = 0.0;                       // fp64: rigorous for rows of any fp32 magnitude (common.hpp, bound_up_f32)
         for (int i = lane * 4; i < dpad; i += 256) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < d) v = *reinterpret_cast<const float4*>(src + i);
             ushort4 o;
             o.x = T::from_f32(v.x); o.y = T::from_f32(v.y); o.z = T::from_f32(v.z); o.w = T::from_f32(v.w);
-            const float cx = T::to_f32(o.x), cy = T::to_f32(o.y), cz = T::to_f32(o.z), cw = T::to_f32(o.w);
-            e2 += (v.x - cx) * (v.x - cx) + (v.y - cy) * (v.y - cy) + (v.z - cz) * (v.z - cz) + (v.w - cw) * (v.w - cw);
-            c2 += cx * cx + cy * cy + cz * cz + cw * cw;
+            sq_acc_pair(e2, c2, v.x, T::to_f32(o.x)); sq_acc_pair(e2, c2, v.y, T::to_f32(o.y));
+            sq_acc_pair(e2, c2, v.z, T::to_f32(o.z)); sq_acc_pair(e2, c2, v.w, T::to_f32(o.w));
             *reinterpret_cast<ushort4*>(dst + i) = o;
         }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { e2 += __shfl_xor(e2, m, 64); c2 += __shfl_xor(c2, m, 64); }
-        // slack factor covers the fp32 rounding of these sums themselves; NaN rows (never retrievable) are skipped
-        const float e = sqrtf(e2) * 1.0001f, c = sqrtf(c2) * 1.0001f;
+        for (int m = 32; m >= 1; m >>= 1) { e2 += shfl_xor_f64(e2, m); c2 += shfl_xor_f64(c2, m); }
+        // the slack factor covers the rounding of the sums (<= dpad 2^-53 relative) and of the square root many times over;
+        // the result is rounded up.
+        // A row whose e2 is NaN is skipped although its error is unknown, and that is safe: e2 is NaN only when the row holds a NaN element - then its
+        // score is NaN for every query and it is never returned - or an inf element (v - c = inf - inf) - then c2 = inf, cmax = inf, the eps of
+        // passes 1 and 2 is inf for every query, neither certificate passes and the exact scan (which uses no bound) answers.  An f16 copy that
+        // overflows a finite element gives e2 = inf, not NaN: emax = inf, the same way out.
+        const float e = bound_up_f32(sqrt(e2) * 1.0001), c = bound_up_f32(sqrt(c2) * 1.0001);
         if (e == e) emax = fmaxf(emax, e);
         if (c == c) cmax = fmaxf(cmax, c);
     }
@@ -231,30 +235,37 @@ __global__ __launch_bounds__(64) void k_prep_queries(const float* __restrict__ q
     const int q = blockIdx.x, lane = threadIdx.x;
     for (int i = q * 64 + lane; i < nzero; i += (int)gridDim.x * 64) zero[i] = 0u;     // the wave-list counters of the scans behind this kernel
     uint16_t* dst = qc + (int64_t)q * dpad;
-    float q2 = 0.f, e2 = 0.f, c2 = 0.f;
+    double q2 = 0.0, e2 = 0.0, c2 = 0.0;                  // fp64 sums of squares and an fp64 bound: rigorous for queries and rows of any fp32 magnitude
     for (int i = lane * 4; i < dpad; i += 256) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (q < nq && i < d) v = *reinterpret_cast<const float4*>(qf + (int64_t)q * d + i);
         ushort4 o;
         o.x = T::from_f32(v.x); o.y = T::from_f32(v.y); o.z = T::from_f32(v.z); o.w = T::from_f32(v.w);
-        const float cx = T::to_f32(o.x), cy = T::to_f32(o.y), cz = T::to_f32(o.z), cw = T::to_f32(o.w);
-        q2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        e2 += (v.x - cx) * (v.x - cx) + (v.y - cy) * (v.y - cy) + (v.z - cz) * (v.z - cz) + (v.w - cw) * (v.w - cw);
-        c2 += cx * cx + cy * cy + cz * cz + cw * cw;
+        sq_acc(q2, (double)v.x); sq_acc(q2, (double)v.y); sq_acc(q2, (double)v.z); sq_acc(q2, (double)v.w);
+        sq_acc_pair(e2, c2, v.x, T::to_f32(o.x)); sq_acc_pair(e2, c2, v.y, T::to_f32(o.y));
+        sq_acc_pair(e2, c2, v.z, T::to_f32(o.z)); sq_acc_pair(e2, c2, v.w, T::to_f32(o.w));
         *reinterpret_cast<ushort4*>(dst + i) = o;
     }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { q2 += __shfl_xor(q2, m, 64); e2 += __shfl_xor(e2, m, 64); c2 += __shfl_xor(c2, m, 64); }
+    for (int m = 32; m >= 1; m >>= 1) { q2 += shfl_xor_f64(q2, m); e2 += shfl_xor_f64(e2, m); c2 += shfl_xor_f64(c2, m); }
     if (lane == 0) {
-        const float max_ex = bounds[0], max_cx = bounds[1];
-        const float qn = sqrtf(q2) * 1.0001f, qe = sqrtf(e2) * 1.0001f, qcn = sqrtf(c2) * 1.0001f;
+        const double max_ex = (double)bounds[0], max_cx = (double)bounds[1];
+        const double qn = sqrt(q2) * 1.0001, qe = sqrt(e2) * 1.0001, qcn = sqrt(c2) * 1.0001;
         // |q.x - qc.xc| <= |q|.|x - xc| + |q - qc|.|xc|          (Cauchy-Schwarz, exact arithmetic)
         //  + fp32 accumulation of the MFMA chain <= 1.1 * dpad * 2^-24 * |qc|.|xc|
         //  + the final fp32 rounding of the canonical score and of the coarse score (2^-22 * |q|.|x|, |x| <= |xc| + |x-xc|)
-        const float acc = 1.1f * (float)dpad * 5.9604645e-8f;
-        float e = qn * max_ex + qe * max_cx + acc * qcn * max_cx + 2.4e-7f * qn * (max_cx + max_ex);
-        e = e * 1.001f + 1e-30f;
-        eps[q] = (q < nq) ? e : 0.f;
+        //  + what a matrix pipe that flushes subnormal operands, products or sums can lose (operands below FLT_MIN taken as 0:
+        //    FLT_MIN * (sum |qc_i| + sum |xc_i|) <= FLT_MIN * sqrt(dpad) * (|qc| + |xc|); one FLT_MIN per product and per addition)
+        // evaluated in fp64 (the products of two small norms underflow in fp32) and rounded up.  The absolute floor covers the roundings of
+        // subnormal scores (2^-149 each) and of theta = b_k - 2 eps itself.
+        const double acc = 1.1 * (double)dpad * 5.9604645e-8;
+        double e = qn * max_ex + qe * max_cx + acc * qcn * max_cx + 2.4e-7 * qn * (max_cx + max_ex);
+        e += 1.1754944e-38 * (sqrt((double)dpad) * (qcn + max_cx) + 2.0 * (double)dpad);
+        e = e * 1.001 + 1e-30;
+        // 0 * inf (a query that the 16-bit type holds exactly over an index with an inf row): the bound is unknown, i.e. infinite.  As inf it also
+        // survives the fmaxf of k_global_theta, which would drop a NaN.
+        const float ef = (e == e) ? bound_up_f32(e) : INFINITY;
+        eps[q] = (q < nq) ? ef : 0.f;
         thr[q] = (q < nq) ? -INFINITY : INFINITY;   // padded queries never emit
         cnt[q] = 0u;
         flags[q] = 0u;
@@ -799,20 +810,21 @@ template <int DUMMY = 0>
 __global__ __launch_bounds__(64) void k_prep_fine(const float* __restrict__ qf, int nq, int d, const float* __restrict__ bounds, float* __restrict__ eps,
                                                   float* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* __restrict__ flags) {
     const int q = blockIdx.x, lane = threadIdx.x;
-    float q2 = 0.f;
+    double q2 = 0.0;                                      // fp64, as in k_prep_queries
     if (q < nq)
         for (int i = lane * 4; i < d; i += 256) {
             const float4 v = *reinterpret_cast<const float4*>(qf + (int64_t)q * d + i);
-            q2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            sq_acc(q2, (double)v.x); sq_acc(q2, (double)v.y); sq_acc(q2, (double)v.z); sq_acc(q2, (double)v.w);
         }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) q2 += __shfl_xor(q2, m, 64);
+    for (int m = 32; m >= 1; m >>= 1) q2 += shfl_xor_f64(q2, m);
     if (lane == 0) {
-        const float xn = bounds[0] + bounds[1];          // max |x| <= max |c(x)| + max |x - c(x)|
-        const float qn = sqrtf(q2) * 1.0001f;
-        float e = (2.4e-7f + 4.5e-16f * (float)(d + 8)) * qn * xn;
-        e = e * 1.001f + 1e-37f;
-        eps[q] = (q < nq) ? e : 0.f;
+        const double xn = (double)bounds[0] + (double)bounds[1];   // max |x| <= max |c(x)| + max |x - c(x)|
+        const double qn = sqrt(q2) * 1.0001;
+        double e = (2.4e-7 + 4.5e-16 * (double)(d + 8)) * qn * xn;
+        e = e * 1.001 + 1e-37;                            // the floor covers the rounding of subnormal scores (2^-149 each)
+        const float ef = (e == e) ? bound_up_f32(e) : INFINITY;
+        eps[q] = (q < nq) ? ef : 0.f;
         thr[q] = (q < nq) ? -INFINITY : INFINITY;
         cnt[q] = 0u;
         flags[q] = 0u;
@@ -1124,36 +1136,37 @@ __global__ __launch_bounds__(256) void k_quant8_rows(const float* __restrict__ x
             v.x = (v.x - c.x) * w.x; v.y = (v.y - c.y) * w.y; v.z = (v.z - c.z) * w.z; v.w = (v.w - c.w) * w.w;
             return v;
         };
-        float amax = 0.f, r2 = 0.f;
+        float amax = 0.f;
+        double r2 = 0.0, e2 = 0.0;                       // fp64 sums of squares: rigorous for rows of any fp32 magnitude
         bool fin = true;
         for (int i = lane * 4; i < d; i += 256) {
             const float4 v = centred(i);
             const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
             fin = fin && (fabsf(v.x) <= 3.4028235e38f) && (fabsf(v.y) <= 3.4028235e38f) && (fabsf(v.z) <= 3.4028235e38f) && (fabsf(v.w) <= 3.4028235e38f);
             amax = fmaxf(amax, m);
-            r2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            sq_acc(r2, (double)v.x); sq_acc(r2, (double)v.y); sq_acc(r2, (double)v.z); sq_acc(r2, (double)v.w);
         }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { amax = fmaxf(amax, __shfl_xor(amax, m, 64)); r2 += __shfl_xor(r2, m, 64); }
+        for (int m = 32; m >= 1; m >>= 1) { amax = fmaxf(amax, __shfl_xor(amax, m, 64)); r2 += shfl_xor_f64(r2, m); }
         fin = __all(fin);
         const float sx = fin ? amax / 127.f : 0.f;
         const float inv = (fin && amax > 0.f) ? 127.f / amax : 0.f;
-        float e2 = 0.f;
         for (int i = lane * 4; i < dpad8; i += 256) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < d && fin) v = centred(i);
             const float a0 = fminf(fmaxf(rintf(v.x * inv), -127.f), 127.f), a1 = fminf(fmaxf(rintf(v.y * inv), -127.f), 127.f);
             const float a2 = fminf(fmaxf(rintf(v.z * inv), -127.f), 127.f), a3 = fminf(fmaxf(rintf(v.w * inv), -127.f), 127.f);
             const float d0 = v.x - sx * a0, d1 = v.y - sx * a1, d2 = v.z - sx * a2, d3 = v.w - sx * a3;
-            e2 += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+            sq_acc(e2, (double)d0); sq_acc(e2, (double)d1); sq_acc(e2, (double)d2); sq_acc(e2, (double)d3);
             dst[i >> 2] = ((uint32_t)(int)a0 & 255u) | (((uint32_t)(int)a1 & 255u) << 8) | (((uint32_t)(int)a2 & 255u) << 16) | (((uint32_t)(int)a3 & 255u) << 24);
         }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) e2 += __shfl_xor(e2, m, 64);
-        // slack: the fp32 roundings of x - mu, of sx * a and of the residual (each <= 2^-24 relative per component: together <= 3.6e-7 |r| in the norm,
-        // |r| <= amax sqrt(d)) and of the sums themselves
-        const float e = sqrtf(e2) * 1.0001f + 3.6e-7f * amax * sqrtf((float)d);
-        const float rn = sqrtf(r2) * 1.0001f + 1.2e-7f * amax * sqrtf((float)d);
+        for (int m = 32; m >= 1; m >>= 1) e2 += shfl_xor_f64(e2, m);
+        // slack: the fp32 roundings of x - mu, of sx * a and of the residual (each <= 2^-24 relative per component, or 2^-149 where the result is
+        // subnormal: together <= 3.6e-7 |r| + 3 sqrt(d) 2^-149 in the norm, |r| <= amax sqrt(d)) and of the sums themselves; evaluated in fp64, rounded up
+        const double sd = sqrt((double)d);
+        const float e = bound_up_f32(sqrt(e2) * 1.0001 + (3.6e-7 * (double)amax + 4.3e-45) * sd);
+        const float rn = bound_up_f32(sqrt(r2) * 1.0001 + (1.2e-7 * (double)amax + 1.5e-45) * sd);
         if (fin && e == e && rn == rn) { emax = fmaxf(emax, e); nmax = fmaxf(nmax, rn); } else bad = true;
         if (lane == 0) sx8[row] = sx;
     }
@@ -1171,7 +1184,8 @@ __global__ __launch_bounds__(256) void k_scan8_prep(const uint64_t* __restrict__
                                                     const float* __restrict__ mu8, int8_t* __restrict__ q8, float* __restrict__ thr8,
                                                     unsigned int* __restrict__ mark_count, float* __restrict__ thr16, uint32_t* __restrict__ cnt_spread, float eps8_scale) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float red[5][4];
+    __shared__ float red[3][4];
+    __shared__ double red2[2][4];
     if (blockIdx.x == 0 && threadIdx.x == 0) *mark_count = 0u;          // the list the scan behind this kernel appends to
     uint64_t* s = reinterpret_cast<uint64_t*>(smem);
     unsigned int* hist = reinterpret_cast<unsigned int*>(s + cand_cap);                 // 256 + 4
@@ -1205,7 +1219,8 @@ __global__ __launch_bounds__(256) void k_scan8_prep(const uint64_t* __restrict__
     amax = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
     const float sq = amax / 127.f;
     const float inv = amax > 0.f ? 127.f / amax : 0.f;
-    float e2 = 0.f, u2 = 0.f, qm = 0.f, qma = 0.f;
+    double e2 = 0.0, u2 = 0.0;                            // fp64 sums of squares: rigorous for queries of any fp32 magnitude
+    float qm = 0.f, qma = 0.f;
     for (int i = tid; i < dpad8; i += 256) {
         const float v = i < d ? qv[i] : 0.f;
         const float u = v * winv[i];
@@ -1213,8 +1228,8 @@ __global__ __launch_bounds__(256) void k_scan8_prep(const uint64_t* __restrict__
         const float a = fminf(fmaxf(rintf(t), -127.f), 127.f);
         const float b = fminf(fmaxf(rintf(254.f * (t - a)), -127.f), 127.f);
         const float uh = sq * (a + b * (1.f / 254.f));
-        e2 += (u - uh) * (u - uh);
-        u2 += u * u;
+        sq_acc(e2, (double)u - (double)uh);
+        sq_acc(u2, (double)u);
         const float c = mu[i];
         qm += v * c; qma += fabsf(v * c);
         pa[i] = (a == a) ? (int8_t)(int)a : (int8_t)0;
@@ -1222,31 +1237,35 @@ __global__ __launch_bounds__(256) void k_scan8_prep(const uint64_t* __restrict__
     }
 #pragma unroll
     for (int mm = 32; mm >= 1; mm >>= 1) {
-        e2 += __shfl_xor(e2, mm, 64); u2 += __shfl_xor(u2, mm, 64); qm += __shfl_xor(qm, mm, 64); qma += __shfl_xor(qma, mm, 64);
+        e2 += shfl_xor_f64(e2, mm); u2 += shfl_xor_f64(u2, mm); qm += __shfl_xor(qm, mm, 64); qma += __shfl_xor(qma, mm, 64);
     }
-    if (lane == 0) { red[1][wave] = e2; red[2][wave] = u2; red[3][wave] = qm; red[4][wave] = qma; }
+    if (lane == 0) { red2[0][wave] = e2; red2[1][wave] = u2; red[1][wave] = qm; red[2][wave] = qma; }
     __syncthreads();
     if (tid == 0) {
-        e2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        u2 = red[2][0] + red[2][1] + red[2][2] + red[2][3];
-        qm = red[3][0] + red[3][1] + red[3][2] + red[3][3];
-        qma = red[4][0] + red[4][1] + red[4][2] + red[4][3];
-        const float un = sqrtf(u2) * 1.0001f;
-        const float du = sqrtf(e2) * 1.0001f + 4.8e-7f * un;               // |u - u^|, + the fp32 rounding of u^ itself in the residual above
-        const float dx = bounds8[0];                                       // max |r - r^|,  r = (x - mu) w,  r^ = sx8 x8
-        const float rn = bounds8[2] + dx;                                  // max |r^| <= max |r| + dx
-        // q.x = q.mu + u.r;  |u.r - u^.r^| <= |u| dx + |u - u^| |r^|;  q.mu in fp32: any order of <= d additions, <= (d + 2) 2^-24 sum |q_i mu_i|;
-        // the device's arithmetic on the byte score (one fma rounding, the scale product, the threshold's own scaling): <= 4 x 2^-23 relative
-        float e8 = un * dx + du * rn + 4.8e-7f * un * rn + (float)(d + 2) * 6.0e-8f * qma * 1.01f;
+        e2 = red2[0][0] + red2[0][1] + red2[0][2] + red2[0][3];
+        u2 = red2[1][0] + red2[1][1] + red2[1][2] + red2[1][3];
+        qm = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        qma = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+        const double un = sqrt(u2) * 1.0001;
+        const double du = sqrt(e2) * 1.0001 + 4.8e-7 * un;                 // |u - u^|, + the fp32 rounding of u^ itself in the residual above
+        const double dx = (double)bounds8[0];                              // max |r - r^|,  r = (x - mu) w,  r^ = sx8 x8
+        const double rn = (double)bounds8[2] + dx;                         // max |r^| <= max |r| + dx
+        // q.x = q.mu + u.r;  |u.r - u^.r^| <= |u| dx + |u - u^| |r^|;  q.mu in fp32: any order of <= d additions, <= (d + 2) 2^-24 sum |q_i mu_i|
+        // (+ 2^-149 per product that lands in the subnormal range: inside the absolute floor below);
+        // the device's arithmetic on the byte score (one fma rounding, the scale product, the threshold's own scaling): <= 4 x 2^-23 relative.
+        // Evaluated in fp64 (products of two small norms underflow in fp32) and rounded up.
+        double e8d = un * dx + du * rn + 4.8e-7 * un * rn + (double)(d + 2) * 6.0e-8 * (double)qma * 1.01;
         // + the three fp32 subtractions that form theta below, and a few ulps of distance from the canonical (fp32-rounded) scores of the k rows the bound
         // rests on: an unmarked row must not even TIE with them (a tie would be decided by the row index)
-        e8 += 1e-6f * (fabsf(kth) + fabsf(qm) + eps16[q]);
-        e8 = e8 * 1.001f + 1e-30f;
+        e8d += 1e-6 * ((double)fabsf(kth) + (double)fabsf(qm) + (double)eps16[q]);
+        e8d = e8d * 1.001 + 1e-30;
+        float e8 = (e8d == e8d) ? bound_up_f32(e8d) : INFINITY;
         e8 *= eps8_scale;                                                  // 1 in production; kr_set_option("debug_eps8_permille") lets a test run with a bound that is too small
         const float theta = kth - eps16[q] - e8 - qm;                      // bound on the byte score u^.r^ of a row that can still matter
         const bool usable = (fabsf(theta) <= 3.4028235e38f) && sq > 0.f && (sq <= 3.4028235e38f) && reinterpret_cast<const unsigned int*>(bounds8)[1] == 0u;
         float t = -INFINITY;                                               // unusable: every row is marked (slow, exact)
         if (usable) { t = theta * (254.f / sq); t -= fabsf(t) * 1e-6f; }
+        if (!(fabsf(t) <= 3.4028235e38f)) t = -INFINITY;                   // 254 / sq overflows for a query below ~2^-118: +inf or NaN would mark NO row
         thr8[q] = t;
         // the 16-bit threshold of the round as well: a row whose 16-bit score is below kth16 - 2 eps16 has an exact score below kth16 - eps16, i.e. below k rows
         // already seen — for small k that is far above the round's own survivor-budget threshold (the rank-55 score of the sample): a few hundred listed rows

@@ -516,7 +516,8 @@ def _score_topk1(q, x):
 def test_canonical_score_golden_vectors_on_gpu(golden, force):
     """tests/golden/g9_exact_dot.npz (351 known answers from Python rationals: exact midpoints, sticky bits, subnormal and vanishing results,
     overflow to inf, cancellation, 120-bit exponent spreads) through the library's scoring kernel, with the certified fp64 fast path (force = 0)
-    and with every score sent through the integer super-accumulator (force = 1): every bit must match."""
+    and with every score sent through the integer super-accumulator (force = 1): every bit must match - except the sign of a zero score: -0.0 and +0.0 are
+    one score, and the scan's sort key does not carry the sign (the oracle's own test pins the signed zeros of these vectors)."""
     from kirag_amd import _lib
     lib = _lib.load()
     g = golden("g9_exact_dot.npz")
@@ -526,7 +527,11 @@ def test_canonical_score_golden_vectors_on_gpu(golden, force):
         for c in range(len(off) - 1):
             q = g["q_bits"][off[c]:off[c + 1]].view(np.float32); x = g["x_bits"][off[c]:off[c + 1]].view(np.float32)
             got = np.float32(_score_topk1(q, x)).view(np.uint32)
-            assert got == g["expected_bits"][c], (c, len(q), hex(int(got)), hex(int(g["expected_bits"][c])))
+            want = g["expected_bits"][c]
+            if (int(want) & 0x7FFFFFFF) == 0:                              # a zero score may come back with either sign (include/kirag_amd.h, zero rule)
+                assert (int(got) & 0x7FFFFFFF) == 0, (c, len(q), hex(int(got)), hex(int(want)))
+                continue
+            assert got == want, (c, len(q), hex(int(got)), hex(int(want)))
     finally:
         _lib.check(lib.kr_set_option(b"force_exact_scores", 0))
     with pytest.raises(_lib.KiragAmdError):
