@@ -222,7 +222,7 @@ def test_batch_invariance_and_padding_layouts(golden):
         ok = [0, 1, 2, 3, 5]
         _check(out[ok], ref[ok], 4e-3, f"pool{pool}")
         single = h.forward_np(ids[[2]], mask[[2]], pool)
-        np.testing.assert_allclose(single[0], out[2], atol=2e-6)       # batch composition does not change a row
+        assert np.array_equal(single[0].view(np.uint32), out[2].view(np.uint32))       # batch composition does not change a row by one bit (the embedding cache)
     with pytest.raises(Exception) as ei:
         bad = ids.copy(); bad[0, 3] = cfg.vocab_size
         h.forward_np(bad, mask, 0)
