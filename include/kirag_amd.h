@@ -308,18 +308,43 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   kr_encoder_forward_packed, the index inside its sequence), and with n = |d|:  bucket = n for n < 8, else min(15, 8 + max{ j >= 0 : 64 * 2^j <= n * n });
  *   plus 16 when d > 0 (key after query).  Buckets 8 .. 15 begin at n = 8, 12, 16, 23, 32, 46, 64, 91.  Like the position rule this is fixed at the first
  *   finalize: a handle finalized with the tensor takes new values for it later (followed by kr_encoder_finalize, as for every tensor), a handle finalized
- *   without it refuses it with KR_EINVAL.  Handles without it run the same kernels, bit for bit, as before the tensor was known. */
+ *   without it refuses it with KR_EINVAL.  Handles without it run the same kernels, bit for bit, as before the tensor was known.
+ * T5EncoderModel (sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*: the encoder half of T5 v1.0 / v1.1 / flan):
+ *   "config.t5_feed_forward": data = ONE float, 0 = the feed-forward wo(relu(wi x)), 1 = the gated wo(gelu_new(wi_0 x) * wi_1 x) with HF's gelu_new
+ *   0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))); anything else is KR_EINVAL.  Loading it before the handle's first finalize makes the handle a T5 handle
+ *   for life; afterwards the same value is a no-op and another value, or loading it onto a handle that was finalized without it, is KR_EINVAL.
+ *   kr_encoder_finalize refuses it (KR_EINVAL, naming it) next to any of "config.position_padding_idx", "config.rotary_inv_freq*",
+ *   "config.local_attention_layers" and "config.attention_half_window", refuses T5's tensor names on a handle of another kind and other families' names on
+ *   this one.  In kr_bert_cfg: hidden = d_model, heads = num_heads (d_kv * num_heads must be d_model, d_kv 32 or 64), intermediate = d_ff, type_vocab = 1,
+ *   ln_eps = layer_norm_epsilon; max_pos only bounds S (no table is sized by it).  On such a handle
+ *     - the stack is PRE-LN with RMS norms (T5LayerNorm: w * x * rsqrt(mean(x^2) + eps), no mean subtracted, no bias): x = shared[id] — no embedding norm,
+ *       no positions, no token types —, x += o . attention(q, k, v of layer_norm_0(x)), x += wo . ff(layer_norm_1(x)), output = final_layer_norm(x);
+ *     - every attention score is q.k + W[bucket(d)][head] — NO 1 / sqrt(d_h) —, with the ONE table that block 0 holds, in every layer; d, the columns and the
+ *       bucket rule are those of the MPNet handles above (T5's bidirectional rule with 32 buckets and max_distance 128 gives the same bucket for every d);
+ *     - no linear layer has a bias;
+ *     - T5EncoderModel's state dict loads unchanged: "shared.weight" (and its tied alias "encoder.embed_tokens.weight": last write wins),
+ *       "encoder.block.N.layer.0.SelfAttention.{q,k,v,o}.weight", "encoder.block.N.layer.0.layer_norm.weight",
+ *       "encoder.block.N.layer.1.DenseReluDense.{wi,wo}.weight" (setting 0) or "....DenseReluDense.{wi_0,wi_1,wo}.weight" (setting 1; the other spelling is
+ *       KR_EINVAL at finalize), "encoder.block.N.layer.1.layer_norm.weight", "encoder.final_layer_norm.weight" and
+ *       "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight": 32 x heads floats ([bucket][head]; any other count, or a block other than 0, is
+ *       KR_EINVAL).  A missing tensor, the table included, fails finalize as "never loaded"; no position table and no token-type table are required.
+ *   "dense.weight": optional, T5 handles only (KR_EINVAL at finalize elsewhere): data = [P, hidden] fp32, 4 <= P <= 2048, P % 4 == 0 — the bias-free
+ *   sentence_transformers.models.Dense module with an identity activation that GTR / Sentence-T5 / Instructor put between the pooling and the normalisation
+ *   (P = 768 for every GTR size).  A count that is no multiple of hidden, or a P outside that range, is KR_EINVAL.  With it EVERY forward entry point writes
+ *   out [B, P] = normalize(W . pooled) instead of [B, hidden] (the caller knows P from the tensor it loaded); an all-masked sequence still gives a NaN row.
+ *   Like the settings it is fixed at the first finalize: later the same P takes new values, another P — or the tensor on a handle finalized without it — is
+ *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]). */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);
 /* forward(input_ids, attention_mask) (encoders.py:67-77 / :106-118); token_type_ids are 0 as in every caller.
- *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised.
+ *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised ([B,P] on a handle that was given "dense.weight" [P, hidden]).
  *   A sequence whose mask is all zero yields NaN (mean pool) exactly like the reference. */
 int kr_encoder_forward(kr_encoder* enc, const int64_t* input_ids, const int64_t* attention_mask, int B, int S,
                        int pool, float* out, void* stream);
 /* The same with token_type_ids [B,S] int64 (HF BertModel.forward's third input; NULL = all zero = kr_encoder_forward).  No KiRAG caller passes non-zero
  * types (the collators encode single texts), but the encoders' forward signature has the argument (encoders.py:67,106).  A value outside
- * [0, type_vocab) is reported as KR_EINVAL through the same deferred channel as token ids. */
+ * [0, type_vocab) is reported as KR_EINVAL through the same deferred channel as token ids.  out is [B,P] on a handle with "dense.weight" [P, hidden]. */
 int kr_encoder_forward_tt(kr_encoder* enc, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, int B, int S,
                           int pool, float* out, void* stream);
 /* The same forward from RAGGED input: token_ids = int32 ids of the attended positions of every sequence back to back (total_tokens of them, host or device),
@@ -328,7 +353,8 @@ int kr_encoder_forward_tt(kr_encoder* enc, const int64_t* input_ids, const int64
  * processes of compute_corpus_embeddings.py:77-81 to the GPU.  S = the padded width the equivalent [B,S] call would have (>= every length, <= max_pos; it selects
  * the attention kernel exactly as kr_encoder_forward does).  Rows are BIT-IDENTICAL to kr_encoder_forward on the equivalent padded batch (the same kernels run
  * on the same packed token tables).  A length outside [0, S] or lengths that do not add up to total_tokens are reported as KR_EINVAL through the deferred
- * channel below (the sequence is read as empty, nothing is read out of bounds); an empty sequence yields NaN (mean pool) like an all-zero mask. */
+ * channel below (the sequence is read as empty, nothing is read out of bounds); an empty sequence yields NaN (mean pool) like an all-zero mask.
+ * out is [B,P] on a handle with "dense.weight" [P, hidden]. */
 int kr_encoder_forward_packed(kr_encoder* enc, const int32_t* token_ids, const int32_t* seq_lens, int B, int S, int64_t total_tokens, int pool, float* out,
                               void* stream);
 /* kr_encoder_forward with a DEVICE `out` pointer only enqueues work on `stream` and returns (no host synchronisation); with a host `out`

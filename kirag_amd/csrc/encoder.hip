@@ -25,6 +25,11 @@
 // layer's mlp_norm, then the next layer's attn_norm (final_norm behind the last layer).  Rotary q / k as above with one table per layer type, the MLP
 // Wo (erf_gelu(input) * gate) as one [2 FF, H] projection (EPI_GEGLU), and in the layers flagged local a sliding window over the key columns (k_attn_*<.., WIN>).
 //
+// T5 handles (config.t5_feed_forward, see Encoder::t5_ff): ModernBert's pre-LN schedule with T5LayerNorm (RMS: k_ln16_pre<.., true>), the embedding row straight
+// into the residual stream (k_embed_rms), MPNet's relative attention bias in every layer with scores q.k + bias (no 1 / sqrt(d_h): log2(e) alone is folded into
+// Wq), no linear bias, the FF wo(relu(wi x)) (EPI_RELU) or wo(gelu_new(wi_0 x) * wi_1 x) (EPI_GEGLU_TANH), and optionally the sentence-transformers Dense head
+// behind the pooling ("dense.weight", k_pool_dense: out [B, P]).
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -117,6 +122,16 @@ struct Encoder {
     float *rot_cos_l = nullptr, *rot_sin_l = nullptr;
     bool modern() const { return !local_layers.empty(); }
     bool local_layer(int li) const { return (size_t)li < local_layers.size() && local_layers[li] != 0.f; }
+    // T5 (transformers.T5EncoderModel: gtr-t5, sentence-t5, instructor): loading "config.t5_feed_forward" (0 = relu, 1 = gated gelu_new) before the first finalize
+    // makes the handle a T5 handle for life.  rel_fam: the family of the name the bias table came under (MPNet's or T5's; enc_finalize: name and kind agree).
+    int t5_ff = -1;
+    int rel_fam = 0;
+    bool t5() const { return t5_ff >= 0; }
+    bool pre_ln() const { return modern() || t5(); }
+    // "dense.weight" [P, H] fp32 (T5 handles only): the Dense head behind the pooling.  dense_rows = P (0: none); pooled: k_pool's [B, H] rows, the head's input
+    float* dense_w = nullptr; int dense_rows = 0;
+    float* pooled = nullptr;
+    int out_dim() const { return dense_rows > 0 ? dense_rows : cfg.hidden; }
     uint16_t *rb = nullptr, *c_rb = nullptr;   // the pre-LN residual stream (and its CLS-row copy): 16-bit high half
     uint8_t *rlo = nullptr, *c_rlo = nullptr;  // ... and the low-half bytes (use_lo)
     float *out = nullptr;
@@ -193,7 +208,8 @@ static int ensure_ws(Encoder* e, int B, int S) {
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_rpos, capT * 4)); KR_HIP(hipMemset(e->tok_rpos, 0, (size_t)capT * 4));
     }
-    KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * H * 4));
+    KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_dim() * 4));
+    if (e->dense_rows > 0) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
     KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * H * 2));
@@ -201,7 +217,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
     KR_TRY(dmalloc(e->ws_bufs, &e->vT, (size_t)H * e->ldv * 2));
     KR_HIP(hipMemset(e->vT, 0, (size_t)H * e->ldv * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->ctx, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->h, capT * FF * 2));
-    if (e->modern()) {
+    if (e->pre_ln()) {
         KR_TRY(dmalloc(e->ws_bufs, &e->rb, capT * H * 2));
         if (e->use_lo) KR_TRY(dmalloc(e->ws_bufs, &e->rlo, capT * H));
     }
@@ -209,7 +225,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
         const int64_t capC = round_up(capB, 256);                 // token-indexed buffers come in multiples of the 256-row tile (see k_proj)
         KR_TRY(dmalloc(e->ws_bufs, &e->c_ctx, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xb, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_y, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xlo, capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_h, capC * FF * 2));
-        if (e->modern()) {
+        if (e->pre_ln()) {
             KR_TRY(dmalloc(e->ws_bufs, &e->c_rb, capC * H * 2)); KR_HIP(hipMemset(e->c_rb, 0, (size_t)capC * H * 2));
             if (e->use_lo) { KR_TRY(dmalloc(e->ws_bufs, &e->c_rlo, capC * H)); KR_HIP(hipMemset(e->c_rlo, 0x80, (size_t)capC * H)); }
         }
@@ -224,7 +240,8 @@ static int ensure_ws(Encoder* e, int B, int S) {
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
 constexpr int T_RELBIAS = -2;          // not a slot of `got`: an optional tensor (parse_name)
 constexpr int T_WQKV = -3, T_WI = -4, T_WIB = -5, T_WQKVB = -6;   // ModernBert's fused tensors of layer `layer` (parse_name): attn.Wqkv.weight, mlp.Wi.weight, mlp.Wi.bias, attn.Wqkv.bias
-enum { FAM_BERT = 1, FAM_NOMIC = 2, FAM_MODERN = 3 };   // whose state-dict name a tensor came under
+enum { FAM_BERT = 1, FAM_NOMIC = 2, FAM_MODERN = 3, FAM_T5 = 4, FAM_T5G = 5 };   // whose state-dict name a tensor came under (FAM_T5G: T5's gated FF, wi_0 / wi_1)
+static bool fam_t5(int fam) { return fam == FAM_T5 || fam == FAM_T5G; }
 constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says
 enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
 
@@ -245,6 +262,38 @@ static int parse_name(const Encoder* e, const char* name, int& slot, int64_t& nu
     const int64_t H = e->cfg.hidden, FF = e->cfg.intermediate;
     if (s.find("position_ids") != std::string::npos || s.find("pooler.") != std::string::npos) { slot = -1; return 0; }
     auto ends_with = [&](const char* t) { const size_t n = strlen(t); return s.size() >= n && s.compare(s.size() - n, n, t) == 0 && (s.size() == n || s[s.size() - n - 1] == '.'); };
+    // T5EncoderModel's names.  The norms sit in ModernBert's places: layer_norm of block N's attention is the norm behind the FF of block N - 1 (the launch that
+    // applies it; block 0's: the embedding launch), layer.1.layer_norm the one behind the attention output, final_layer_norm the last one
+    // (matched as T5EncoderModel spells them, with or without its "encoder." prefix: another family's tensor that merely contains "block." or ends in
+    // "embed_tokens.weight" stays an unknown tensor name at load time)
+    if (s == "shared.weight" || s == "encoder.embed_tokens.weight" || s == "embed_tokens.weight") { fam = FAM_T5; slot = T_WORD; numel = (int64_t)e->cfg.vocab * H; return 0; }
+    if (s == "encoder.final_layer_norm.weight" || s == "final_layer_norm.weight") { fam = FAM_T5; slot = T_LAYER0 + (e->cfg.layers - 1) * L_COUNT + L_LN2G; numel = H; return 0; }
+    if (const size_t pb = s.compare(0, 14, "encoder.block.") == 0 ? 8 : s.compare(0, 6, "block.") == 0 ? 0 : std::string::npos; pb != std::string::npos) {
+        const char* c = s.c_str() + pb + strlen("block.");
+        char* end = nullptr;
+        const long l = strtol(c, &end, 10);
+        if (end == c || *end != '.' || l < 0 || l >= e->cfg.layers) return fail(KR_EINVAL, "bad layer index in '%s'", name);
+        const std::string r(end + 1);
+        struct T5Name { const char* n; int id; };
+        static const T5Name t5_tbl[] = {{"layer.0.SelfAttention.q.weight", L_QW}, {"layer.0.SelfAttention.k.weight", L_KW}, {"layer.0.SelfAttention.v.weight", L_VW},
+                                        {"layer.0.SelfAttention.o.weight", L_OW}, {"layer.0.layer_norm.weight", L_LN2G}, {"layer.1.layer_norm.weight", L_LN1G},
+                                        {"layer.1.DenseReluDense.wi.weight", L_IW}, {"layer.1.DenseReluDense.wi_0.weight", L_IW},
+                                        {"layer.1.DenseReluDense.wi_1.weight", L_UW}, {"layer.1.DenseReluDense.wo.weight", L_FW}};
+        if (r == "layer.0.SelfAttention.relative_attention_bias.weight") {
+            if (l != 0) return fail(KR_EINVAL, "'%s': block 0 holds a T5 encoder's one relative attention bias", name);
+            fam = FAM_T5; slot = T_RELBIAS; numel = (int64_t)REL_BUCKETS * e->cfg.heads;
+            return 0;
+        }
+        for (const T5Name& t : t5_tbl)
+            if (r == t.n) {
+                fam = (t.id == L_UW || r == "layer.1.DenseReluDense.wi_0.weight") ? FAM_T5G : FAM_T5;
+                const bool attn_norm = t.id == L_LN2G;
+                slot = attn_norm && l == 0 ? (int)T_ELNG : T_LAYER0 + (int)(attn_norm ? l - 1 : l) * L_COUNT + t.id;
+                numel = t.id == L_IW || t.id == L_UW || t.id == L_FW ? H * FF : t.id == L_LN1G || t.id == L_LN2G ? H : H * H;
+                return 0;
+            }
+        return fail(KR_EINVAL, "unknown layer tensor '%s'", name);
+    }
     // ModernBert: final_norm is the LayerNorm behind the last layer's MLP
     if (ends_with("final_norm.weight") || ends_with("final_norm.bias")) {
         fam = FAM_MODERN; numel = H;
@@ -397,6 +446,8 @@ static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int devi
             else return go(&k_proj<EPI_QKV_ROTB, Shape, STAGES, NT>);
         case EPI_SWIGLU: return go(&k_proj<EPI_SWIGLU, Shape, STAGES, NT>);
         case EPI_GEGLU: return go(&k_proj<EPI_GEGLU, Shape, STAGES, NT>);
+        case EPI_RELU: return go(&k_proj<EPI_RELU, Shape, STAGES, NT>);
+        case EPI_GEGLU_TANH: return go(&k_proj<EPI_GEGLU_TANH, Shape, STAGES, NT>);
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }
@@ -431,7 +482,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     a.pw = kn.pw;
     a.epi_prio = kn.epi_prio;
     // store policy by output size (see ProjArgs::nt)
-    a.nt = max_tokens * (int64_t)(epi == EPI_SWIGLU || epi == EPI_GEGLU ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
+    a.nt = max_tokens * (int64_t)(epi_gated(epi) ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
     // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
     // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
     // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
@@ -466,6 +517,8 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
                 case EPI_QKV_ROTB: return launch(shape_tag, &k_proj_skinny<EPI_QKV_ROTB, RING, WM, WM>);
                 case EPI_SWIGLU: return launch(shape_tag, &k_proj_skinny<EPI_SWIGLU, RING, WM, WM>);
                 case EPI_GEGLU: return launch(shape_tag, &k_proj_skinny<EPI_GEGLU, RING, WM, WM>);
+                case EPI_RELU: return launch(shape_tag, &k_proj_skinny<EPI_RELU, RING, WM, WM>);
+                case EPI_GEGLU_TANH: return launch(shape_tag, &k_proj_skinny<EPI_GEGLU_TANH, RING, WM, WM>);
                 default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
             }
         };
@@ -489,6 +542,8 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
             case EPI_QKV_ROTB: return go(&k_proj_split<EPI_QKV_ROTB>);
             case EPI_SWIGLU: return go(&k_proj_split<EPI_SWIGLU>);
             case EPI_GEGLU: return go(&k_proj_split<EPI_GEGLU>);
+            case EPI_RELU: return go(&k_proj_split<EPI_RELU>);
+            case EPI_GEGLU_TANH: return go(&k_proj_split<EPI_GEGLU_TANH>);
             default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
         }
     }
@@ -613,9 +668,25 @@ static int set_config(Encoder* e, const char* name, const float* data, int64_t n
         e->half_window = (int)v[0];
         return 0;
     }
+    if (std::strcmp(name, "config.t5_feed_forward") == 0) {
+        // 0 = wo(relu(wi x)), 1 = wo(gelu_new(wi_0 x) * wi_1 x): makes the handle a T5 handle, under the rule of the other settings
+        if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
+        float v = -1.f;
+        KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
+        if (v != 0.f && v != 1.f) return fail(KR_EINVAL, "%s = %g: expected 0 (relu) or 1 (gated gelu_new)", name, (double)v);
+        if (e->finalized_once) {
+            if ((int)v == e->t5_ff) return 0;
+            return fail(KR_EINVAL, e->t5() ? "%s = %d after kr_encoder_finalize: the handle's feed-forward kind is fixed (it has %d)"
+                                           : "%s = %d after kr_encoder_finalize: the handle was finalized without it and stays what it is (%d = not a T5 handle)",
+                        name, (int)v, e->t5_ff);
+        }
+        e->t5_ff = (int)v;
+        e->ready = false;
+        return 0;
+    }
     if (std::strcmp(name, "config.position_padding_idx") != 0)
         return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx, config.rotary_inv_freq, config.rotary_inv_freq_local, "
-                               "config.attention_half_window, config.local_attention_layers)", name);
+                               "config.attention_half_window, config.local_attention_layers, config.t5_feed_forward)", name);
     if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
     float v = 0.f;
     KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
@@ -643,22 +714,23 @@ static int rel_bucket(int d) {
 
 // encoder.relative_attention_bias.weight [32, heads].  Before the first finalize it makes the handle an MPNet handle; afterwards a handle that has it takes
 // new values (the weight sync reloads every parameter) and a handle finalized without it refuses it.
-static int load_rel_bias(Encoder* e, const char* name, const float* data, int64_t numel, int64_t want) {
+static int load_rel_bias(Encoder* e, const char* name, const float* data, int64_t numel, int64_t want, int fam) {
     if (numel != want)
-        return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets)", name, (long long)numel, (long long)want,
-                    REL_BUCKETS, e->cfg.heads, REL_BUCKETS);
+        return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets, and so do the T5 handles)", name,
+                    (long long)numel, (long long)want, REL_BUCKETS, e->cfg.heads, REL_BUCKETS);
     if (e->finalized_once && e->rel_w.empty())
         return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a relative attention bias and stays a BERT / RoBERTa handle", name);
     std::vector<float> w((size_t)numel);
     KR_HIP(hipMemcpy(w.data(), data, (size_t)numel * 4, hipMemcpyDefault));
     e->rel_w.swap(w);
+    e->rel_fam = fam;
     e->ready = false;
     return 0;
 }
 
 // the table the attention kernels read (AttnBiasArgs): per head, log2(e) * W[bucket(d)][head] at entry width / 2 + d, |d| < max_pos + 64 (every column
 // difference the position table allows; the slack covers the keys a masked tile reads past the end of its sequence).  The scores are in log2 units
-// (enc_load_weight folds log2(e) / sqrt(d_h) into W_q): the same fp32 multiply here.
+// (enc_load_weight folds log2(e) / sqrt(d_h) into W_q; a T5 handle, whose scores are q.k + bias, log2(e) alone): the same fp32 multiply here.
 static int build_bias_table(Encoder* e) {
     const int heads = e->cfg.heads, half = e->cfg.max_pos + 64, width = 2 * half;
     std::vector<float> tab((size_t)heads * width);
@@ -699,15 +771,36 @@ static int build_rotary_tables(Encoder* e) {
     return 0;
 }
 
+// "dense.weight" [P, H]: the Dense head behind the pooling of a T5 handle (that it IS one is enc_finalize's business).  The output width of every forward
+// depends on it, so it follows the rule of the settings: before the first finalize; later the same P takes new values (the weight sync reloads every
+// parameter), another P or a handle finalized without it is refused.
+static int load_dense(Encoder* e, const float* data, int64_t numel) {
+    const int64_t H = e->cfg.hidden, P = numel / H;
+    if (numel <= 0 || numel % H != 0 || P < 4 || P > 2048 || P % 4 != 0)
+        return fail(KR_EINVAL, "'dense.weight' has %lld elements: expected [P, %lld] with 4 <= P <= 2048 and P %% 4 == 0", (long long)numel, (long long)H);
+    if (e->finalized_once && e->dense_rows != (int)P)
+        return fail(KR_EINVAL, e->dense_rows ? "'dense.weight' with P = %d after kr_encoder_finalize: the handle's output width is fixed (it has P = %d)"
+                                             : "'dense.weight' (P = %d) after kr_encoder_finalize: the handle was finalized without a Dense head (%d)", (int)P, e->dense_rows);
+    if (e->dense_w && e->dense_rows != (int)P) return fail(KR_EINVAL, "'dense.weight' with P = %d: the handle already holds one with P = %d", (int)P, e->dense_rows);
+    if (!e->dense_w) KR_TRY(dmalloc(e->own_bufs, &e->dense_w, (size_t)numel * 4));
+    KR_HIP(hipMemcpy(e->dense_w, data, (size_t)numel * 4, hipMemcpyDefault));
+    if (e->dense_rows != (int)P) free_ws(e);       // e->out is sized by the output width
+    e->dense_rows = (int)P;
+    e->ready = false;
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(select_device(e->device));
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
+    if (std::strcmp(hf_name, "dense.weight") == 0) return load_dense(e, data, numel);
     int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want, fam, layer));
-    const bool paired = fam != FAM_BERT;     // NomicBert's and ModernBert's names: q / k / the gated projection's rows go into tile-pair order
-    if (slot == T_RELBIAS) return load_rel_bias(e, hf_name, data, numel, want);
+    // NomicBert's and ModernBert's names: q / k (rotary partners) and the gated projection's rows go into tile-pair order; T5's: wi_0 | wi_1 only
+    const bool paired = fam == FAM_NOMIC || fam == FAM_MODERN, gated = paired || fam == FAM_T5G;
+    if (slot == T_RELBIAS) return load_rel_bias(e, hf_name, data, numel, want, fam);
     if (slot == -1) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
     if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", hf_name, (long long)numel, (long long)want);
     if ((size_t)numel > e->stage_elems) {
@@ -718,7 +811,8 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     }
     KR_HIP(hipMemcpy(e->stage, data, (size_t)numel * 4, hipMemcpyDefault));
     const int64_t H = e->cfg.hidden;
-    const float qscale = (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
+    // (T5 scores are q.k + bias, no 1 / sqrt(d_h): under T5's names log2(e) alone is folded in)
+    const float qscale = fam_t5(fam) ? (float)1.4426950408889634 : (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
     const unsigned grid = (unsigned)((numel + 255) / 256);
     auto to_bf16 = [&](uint16_t* dst, float scale) { hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid), dim3(256), 0, 0, e->stage, dst, numel, scale); };
     // a row block [n / cols, cols] of a fused ModernBert tensor, from element `first` of the staged copy
@@ -783,10 +877,10 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
         LayerW& l = e->L[(slot - T_LAYER0) / L_COUNT];
         const int id = (slot - T_LAYER0) % L_COUNT;
         if (id == L_IW || id == L_UW) {
-            if (l.w1 && l.gated != paired)
-                return fail(KR_EINVAL, "'%s': layer %d already holds %s", hf_name, (slot - T_LAYER0) / L_COUNT, paired ? "intermediate.dense" : "a gated projection (gate_proj / up_proj)");
-            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * (paired ? 4 : 2)));
-            l.gated = paired;
+            if (l.w1 && l.gated != gated)
+                return fail(KR_EINVAL, "'%s': layer %d already holds %s", hf_name, (slot - T_LAYER0) / L_COUNT, gated ? "a plain intermediate projection" : "a gated projection (gate_proj / up_proj, wi_0 / wi_1)");
+            if (!l.w1) KR_TRY(dmalloc(e->own_bufs, &l.w1, (size_t)numel * (gated ? 4 : 2)));
+            l.gated = gated;
         }
         switch (id) {
             // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2.  The
@@ -801,7 +895,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             case L_OB: to_f32(l.bo, 1.f); break;
             case L_LN1G: to_f32(l.ln1g, 1.f); break;
             case L_LN1B: to_f32(l.ln1b, 1.f); break;
-            case L_IW: if (paired) to_bf16_rows(l.w1, 1.f, ROWS_GATE); else to_bf16(l.w1, 1.f); break;
+            case L_IW: if (gated) to_bf16_rows(l.w1, 1.f, ROWS_GATE); else to_bf16(l.w1, 1.f); break;
             case L_UW: to_bf16_rows(l.w1, 1.f, ROWS_UP); break;
             case L_IB: to_f32(l.b1, 1.f); break;
             case L_FW: to_bf16(l.w2, 1.f); break;
@@ -820,7 +914,10 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
 int enc_finalize(void* h) {
     if (!h) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
-    const bool rot = e->rotary(), modern = e->modern();
+    const bool rot = e->rotary(), modern = e->modern(), t5 = e->t5();
+    if (t5 && (e->pad_idx >= 0 || rot || modern || !e->inv_freq_local.empty() || e->half_window > 0))
+        return fail(KR_EINVAL, "config.t5_feed_forward next to config.position_padding_idx / config.rotary_inv_freq* / config.local_attention_layers / "
+                               "config.attention_half_window: a T5 handle's one position scheme is its relative attention bias");
     if (!modern && (!e->inv_freq_local.empty() || e->half_window > 0))
         return fail(KR_EINVAL, "config.rotary_inv_freq_local / config.attention_half_window without config.local_attention_layers: they are settings of a ModernBert handle");
     if (modern) {
@@ -842,12 +939,33 @@ int enc_finalize(void* h) {
             return fail(KR_EINVAL, modern ? "weight slot %zu was loaded under a BERT / NomicBert name: a handle with config.local_attention_layers takes ModernBert's names"
                                           : "weight slot %zu was loaded under a ModernBert name but config.local_attention_layers was never loaded: load it before kr_encoder_finalize", i);
     }
+    // ... and T5's names on a T5 handle only, and nothing but them there; the bias table under the family's own name; the Dense head on T5 handles only
+    for (size_t i = 0; i < e->got.size(); ++i) {
+        if (!e->got[i] || i == T_TYPE) continue;
+        if (fam_t5(e->got[i]) != t5)
+            return fail(KR_EINVAL, t5 ? "weight slot %zu was loaded under another family's name: a handle with config.t5_feed_forward takes T5EncoderModel's names"
+                                      : "weight slot %zu was loaded under a T5 name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize", i);
+    }
+    if (!e->rel_w.empty() && fam_t5(e->rel_fam) != t5)
+        return fail(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
+                                  : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
+    if (e->dense_rows > 0 && !t5) return fail(KR_EINVAL, "'dense.weight' without config.t5_feed_forward: the Dense head is part of T5 handles only");
+    if (t5) {
+        for (int li = 0; li < e->cfg.layers; ++li) {
+            const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
+            if (g[L_IW] && (g[L_IW] == FAM_T5G) != (e->t5_ff == 1))
+                return fail(KR_EINVAL, "layer %d: config.t5_feed_forward = %d takes DenseReluDense.%s", li, e->t5_ff, e->t5_ff ? "wi_0 / wi_1, not wi" : "wi, not wi_0 / wi_1");
+            if (g[L_UW] && e->t5_ff == 0) return fail(KR_EINVAL, "layer %d: config.t5_feed_forward = 0 takes DenseReluDense.wi, not wi_0 / wi_1", li);
+        }
+        if (e->rel_w.empty())
+            return fail(KR_ESTATE, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight was never loaded");
+    }
     if (rot && (e->pad_idx >= 0 || !e->rel_w.empty()))
         return fail(KR_EINVAL, "config.rotary_inv_freq next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
     // q / k and the intermediate projection are packed in another row order under NomicBert's names (enc_load_weight): names and handle kind must agree
     for (int li = 0; li < e->cfg.layers; ++li) {
         const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
-        if (modern) continue;
+        if (modern || t5) continue;
         if (rot && (g[L_QW] == 1 || g[L_KW] == 1 || g[L_IW] == 1))
             return fail(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj and mlp.{gate,up}_proj under NomicBert's names", li);
         if (rot && (g[L_QB] || g[L_KB] || g[L_IB]))
@@ -857,6 +975,11 @@ int enc_finalize(void* h) {
     }
     // a NomicBert handle has no position table and needs up_proj; its linear biases are zero unless loaded
     auto optional = [&](size_t i) {
+        if (t5) {      // no position table, no token types, no beta, no linear bias; wi_1 with the gated FF only
+            if (i < T_LAYER0) return i == T_POS || i == T_TYPE || i == T_ELNB;
+            const int id = (int)((i - T_LAYER0) % L_COUNT);
+            return id == L_UW ? e->t5_ff == 0 : !(id == L_QW || id == L_KW || id == L_VW || id == L_OW || id == L_LN1G || id == L_IW || id == L_FW || id == L_LN2G);
+        }
         if (i < T_LAYER0) return (rot && i == T_POS) || (modern && i == T_ELNB);
         const int id = (int)((i - T_LAYER0) % L_COUNT);
         if (modern && (id == L_LN1B || id == L_LN2B)) return true;
@@ -889,6 +1012,10 @@ int enc_finalize(void* h) {
         }
         KR_TRY(build_rotary_tables(e));
     }
+    if (t5)      // no linear bias anywhere: the QKV epilogue adds zeros, v's fold into bo_eff is zero (the RMS norms read no beta)
+        for (auto& l : e->L) {
+            KR_HIP(hipMemset(l.bqkv, 0, (size_t)3 * H * 4)); KR_HIP(hipMemset(l.bo, 0, (size_t)H * 4)); KR_HIP(hipMemset(l.b2, 0, (size_t)H * 4));
+        }
     for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * H, l.bo_eff, H);
     if (!e->rel_w.empty()) KR_TRY(build_bias_table(e));
     KR_HIP(hipGetLastError());
@@ -934,16 +1061,23 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
     auto ln_kernel = H <= 512 ? &k_ln16<1, 7> : H <= 1024 ? &k_ln16<2, 7> : &k_ln16<4, 7>;
     auto ln_pre_kernel = H <= 512 ? &k_ln16_pre<1, 1> : H <= 1024 ? &k_ln16_pre<2, 1> : &k_ln16_pre<4, 1>;      // ModernBert handles (y non-temporal as above)
-    const bool modern = e->modern();
+    const bool modern = e->modern(), t5 = e->t5(), pre = modern || t5;
+    auto ln_rms_kernel = H <= 512 ? &k_ln16_pre<1, 1, true> : H <= 1024 ? &k_ln16_pre<2, 1, true> : &k_ln16_pre<4, 1, true>;    // T5 handles
+    const auto ln_tail_kernel = t5 ? ln_rms_kernel : ln_pre_kernel;
     auto pool_kernel = H <= 256 ? &k_pool<1> : H <= 512 ? &k_pool<2> : H <= 1024 ? &k_pool<4> : &k_pool<8>;
     const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
     unsigned ln_mult = 8u;
     const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
     const bool rot = e->rotary();       // a NomicBert handle: no position row in the embedding (a zero row through tok_zero), rotary QKV and SwiGLU epilogues
     if (rot) hipLaunchKernelGGL(k_rot_pos, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nq, align, e->tok_pos, e->tok_rpos);
-    hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, rot ? e->tok_zero : e->pad_idx >= 0 ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word,
-                       rot ? e->pos_zero : e->pos, e->type, e->elng, e->elnb, eps, H,
-                       e->use_lo ? e->xlo : nullptr, e->xb);
+    if (t5) {     // the embedding row is the residual stream; xb = block 0's attention norm of it
+        auto embed_kernel = H <= 512 ? &k_embed_rms<1> : H <= 1024 ? &k_embed_rms<2> : &k_embed_rms<4>;
+        hipLaunchKernelGGL(embed_kernel, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->d_T, e->word, e->elng, eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
+    } else {
+        hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, rot ? e->tok_zero : e->pad_idx >= 0 ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word,
+                           rot ? e->pos_zero : e->pos, e->type, e->elng, e->elnb, eps, H,
+                           e->use_lo ? e->xlo : nullptr, e->xb);
+    }
     const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr;
     e->last_shortcut = shortcut;
     const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid,
@@ -957,14 +1091,15 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         // attn.Wo; r += y + b; xb = mlp_norm(r)
         a.W = l.wo; a.X = r.ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = r.y; a.ldx = 0; a.ldo = 0;
         KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        hipLaunchKernelGGL(ln_pre_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, rin, rin_lo, r.rb, r.rlo, (uint8_t*)nullptr, r.xb);
-        // mlp.Wi (input | gate as one GEMM of 2 FF columns) + GEGLU: h [rows, FF]
-        a.W = l.w1; a.X = r.xb; a.F = 2 * FF; a.K = H; a.bias = l.b1p; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
-        KR_TRY(launch_proj(EPI_GEGLU, a, r.max_rows, e, st));
+        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, rin, rin_lo, r.rb, r.rlo, (uint8_t*)nullptr, r.xb);
+        // mlp.Wi (input | gate as one GEMM of 2 FF columns) + GEGLU: h [rows, FF].  A T5 handle: wi + relu, or wi_0 | wi_1 the same way + gelu_new, no bias
+        const bool plain = t5 && e->t5_ff == 0;
+        a.W = l.w1; a.X = r.xb; a.F = plain ? FF : 2 * FF; a.K = H; a.bias = l.b1p; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
+        KR_TRY(launch_proj(plain ? EPI_RELU : t5 ? EPI_GEGLU_TANH : EPI_GEGLU, a, r.max_rows, e, st));
         // mlp.Wo; r += y + b; xb = the next layer's attn_norm(r), or final_norm(r) with its low half for the readers of the final hidden state
         a.W = l.w2; a.X = r.h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = r.y; a.ldx = FF; a.ldo = 0;
         KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        hipLaunchKernelGGL(ln_pre_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.b2, r.rows, l.ln2g, l.ln2b, eps, H, (const uint16_t*)r.rb, (const uint8_t*)r.rlo,
+        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.b2, r.rows, l.ln2g, l.ln2b, eps, H, (const uint16_t*)r.rb, (const uint8_t*)r.rlo,
                            last ? (uint16_t*)nullptr : r.rb, r.rlo, last ? r.lo_last : (uint8_t*)nullptr, r.xb);
         return 0;
     };
@@ -1009,12 +1144,13 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         // CLS shortcut: only the CLS row of every sequence is read after the last layer: gather those rows and finish the layer on B rows (same kernels, same
         // arithmetic per row: the projection loops are bit-identical for every tiling and LayerNorm is per row, so the embedding does not change by one bit)
         // (a ModernBert handle: the residual stream travels in the place of xb — the operand is rewritten by the first LayerNorm of the tail)
-        const uint16_t* rin = modern && !first ? e->rb : e->xb;
-        const uint8_t* rin_lo = modern && !first ? all_rows.rlo : all_rows.lo;
+        // (a T5 handle: the embedding launch has stored the residual stream itself, layer 0 finds it like every layer)
+        const uint16_t* rin = (modern && !first) || t5 ? e->rb : e->xb;
+        const uint8_t* rin_lo = (modern && !first) || t5 ? all_rows.rlo : all_rows.lo;
         if (last && shortcut)
-            hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, modern ? e->c_rb : e->c_xb,
-                               modern ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B);
-        if (modern) {
+            hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
+                               pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B);
+        if (pre) {
             if (last && shortcut) KR_TRY(tail_pre(a, l, cls_rows, last, e->c_rb, cls_rows.rlo));
             else KR_TRY(tail_pre(a, l, all_rows, last, rin, rin_lo));
         } else {
@@ -1023,7 +1159,14 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     }
     const RowSet& r = shortcut ? cls_rows : all_rows;
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
-    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool, e->out, e->d_err);
+    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool,
+                       e->dense_rows > 0 ? e->pooled : e->out, e->d_err);
+    if (e->dense_rows > 0) {     // the Dense head: out [B, P] = normalize(W . pooled)
+        const int P = e->dense_rows, dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
+        // one kernel, an LDS size per handle: the attribute is set once per device (set_lds_once) to what the largest handle needs, H = P = 2048 (64 KiB + 16 B)
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(&k_pool_dense), PD_SEQ * (2048 + 2048) * 4 + PD_SEQ * 4, e->device));
+        hipLaunchKernelGGL(k_pool_dense, dim3((B + PD_SEQ - 1) / PD_SEQ), dim3(256), dense_lds, st, e->pooled, e->dense_w, B, H, P, e->out);
+    }
     KR_HIP(hipGetLastError());
     return 0;
 }
@@ -1120,7 +1263,7 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 
 // behind the kernels of a forward: the result and the error word travel to the caller
 static int finish_forward(Encoder* e, int B, int S, float* out, hipStream_t st) {
-    KR_HIP(hipMemcpyAsync(out, e->out, (size_t)B * e->cfg.hidden * 4, hipMemcpyDefault, st));
+    KR_HIP(hipMemcpyAsync(out, e->out, (size_t)B * e->out_dim() * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;
     KR_HIP(hipMemcpyAsync(e->h_err, e->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     if (is_device_pointer(out)) {

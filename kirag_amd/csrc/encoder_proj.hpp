@@ -39,8 +39,9 @@ struct ProjArgs {
     const float* rot_cos; const float* rot_sin; const int* tpos; int max_pos; int dh;
 };
 
-enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6 };
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6, EPI_RELU = 7, EPI_GEGLU_TANH = 8 };
 constexpr bool epi_rotates(int epi) { return epi == EPI_QKV_ROT || epi == EPI_QKV_ROTB; }
+constexpr bool epi_gated(int epi) { return epi == EPI_SWIGLU || epi == EPI_GEGLU || epi == EPI_GEGLU_TANH; }   // F = 2 FF GEMM columns -> FF stored
 
 // The two epilogues of NomicBert handles combine feature pairs: a rotary pair (j, j + d_h / 2) of q or k, or gate and up of one intermediate feature.  The
 // packed weights are laid out (tile_pair_row, encoder_rows.hpp) so that on EVERY main loop both partners sit in one 32x32 accumulator tile, column cc < 16 with
@@ -82,6 +83,21 @@ __device__ __forceinline__ f32x4 geglu_quad(const f32x16& v, int g, f32x4 bi, f3
     const f32x2 lo = gelu_erf_fast2(f32x2{x.x, x.y}), hi = gelu_erf_fast2(f32x2{x.z, x.w});
     return f32x4{lo.x, lo.y, hi.x, hi.y} * u;
 }
+
+// T5 v1.1 / flan handles: gelu_new(wi_0 x) * wi_1 x, no bias.  HF's gelu_new is the tanh form 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3), and
+// 0.5 (1 + tanh(u)) = 1 / (1 + exp(-2 u)) exactly: one v_exp_f32 and one v_rcp_f32 per element like silu_mul (exp overflows to +inf for very negative x:
+// the quotient is then -0, the limit of the tanh form)
+__device__ __forceinline__ float gelu_tanh_mul(float x, float u) {
+    const float t = 0.7978845608028654f * (x + 0.044715f * (x * x * x));
+    return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(t * -2.8853900817779268f)) * u;
+}
+__device__ __forceinline__ f32x4 geglu_tanh_quad(const f32x16& v, int g) {
+    return f32x4{gelu_tanh_mul(v[4 * g], v[4 * g + 8]), gelu_tanh_mul(v[4 * g + 1], v[4 * g + 9]), gelu_tanh_mul(v[4 * g + 2], v[4 * g + 10]),
+                 gelu_tanh_mul(v[4 * g + 3], v[4 * g + 11])};
+}
+
+// relu of a register quad; NaN stays NaN (fmaxf would drop it, and a non-finite activation has to reach the error word)
+__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{v.x < 0.f ? 0.f : v.x, v.y < 0.f ? 0.f : v.y, v.z < 0.f ? 0.f : v.z, v.w < 0.f ? 0.f : v.w}; }
 
 // silu(g) u = g u / (1 + exp(-g)) in fp32: one v_exp_f32 and one v_rcp_f32 per element (exp overflows to +inf for g < -88: the quotient is then -0)
 __device__ __forceinline__ float silu_mul(float g, float u) {
@@ -238,6 +254,8 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
 //   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV)
 //   EPI_SWIGLU:  F = 2 FF, gate | up interleaved per tile: out0[T, F / 2] = silu(gate) * up, no bias (NomicBert handles)
 //   EPI_GEGLU:   F = 2 FF, input | gate interleaved the same way: out0[T, F / 2] = erf_gelu(input + b) * (gate + b') (ModernBert handles; bias in the rows' order)
+//   EPI_RELU:    out0[T,F] = max(acc, 0), no bias (T5 v1.0 handles: DenseReluDense.wi)
+//   EPI_GEGLU_TANH: F = 2 FF, wi_0 | wi_1 interleaved like EPI_GEGLU: out0[T, F / 2] = gelu_new(wi_0 x) * wi_1 x, no bias (T5 v1.1 / flan handles)
 template <int EPI, class ShapeE, bool NT>
 __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>& acc, int64_t m0, int64_t n0, char* stage) {
     const int64_t t0 = m0 + acc.m_wave;
@@ -312,8 +330,13 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
     } else if constexpr (EPI == EPI_GEGLU) {
         // bias (tile-pair order like the rows): b[ni][g] are the input features of quad g < 2, b[ni][g + 2] their gates
         store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1, [&](const f32x16& v, int ni, int g) { return geglu_quad(v, g, b[ni][g], b[ni][g + 2]); });
+    } else if constexpr (EPI == EPI_GEGLU_TANH) {
+        store_rows_gated<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0 >> 1, [](const f32x16& v, int, int g) { return geglu_tanh_quad(v, g); });
     } else if constexpr (EPI == EPI_DENSE) {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int, int, int) { return v; });   // the bias is added in k_ln (fp32)
+    } else if constexpr (EPI == EPI_RELU) {
+        store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0,
+                                    [&](f32x4 v, int, int, int) { return relu4(v); });
     } else {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int mi, int ni, int g) {
             const f32x4 x = v + b[ni][g];
@@ -379,11 +402,13 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         },
         [&](AccTile<ShapeSkinny>& acc, int64_t t0, int64_t f0) {
         const int c = acc.lane & 31, h = acc.lane >> 5;
-        if constexpr (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) {      // the tile's 16 features: 8-byte row stores of silu(gate) * up / erf_gelu(input) * gate
+        if constexpr (epi_gated(EPI)) {      // the tile's 16 features: 8-byte row stores of silu(gate) * up / erf_gelu(input) * gate / gelu_new(wi_0 x) * wi_1 x
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
                 f32x4 p;
-                if constexpr (EPI == EPI_SWIGLU) p = swiglu_quad(acc.v[0][0], g); else p = geglu_quad(acc.v[0][0], g, bias4[g], bias4[g + 2]);
+                if constexpr (EPI == EPI_SWIGLU) p = swiglu_quad(acc.v[0][0], g);
+                else if constexpr (EPI == EPI_GEGLU_TANH) p = geglu_tanh_quad(acc.v[0][0], g);
+                else p = geglu_quad(acc.v[0][0], g, bias4[g], bias4[g + 2]);
                 uint2 w;
                 w.x = pack_bf16x2(p.x, p.y);
                 w.y = pack_bf16x2(p.z, p.w);
@@ -421,6 +446,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
                     const f32x2 lo = gelu_erf_fast2(f32x2{v.x, v.y}), hi = gelu_erf_fast2(f32x2{v.z, v.w});
                     v = f32x4{lo.x, lo.y, hi.x, hi.y};
                 }
+                if constexpr (EPI == EPI_RELU) v = relu4(v);
                 uint2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
                 *reinterpret_cast<uint2*>(a.out0 + (t0 + c) * a.ldo + f) = w;
             }

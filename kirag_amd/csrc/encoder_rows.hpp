@@ -202,7 +202,8 @@ __global__ __launch_bounds__(64) void k_rot_pos(const int* __restrict__ seq_off,
 // LayerNorm(y + bias + residual) with 16-byte accesses: a lane owns 8 consecutive elements per 512-element step (one global_load_dwordx4 per tensor and step:
 // 8-byte accesses reach 0.54-0.70 of the 16-byte rate, MI355X_MICROARCH.md).  NS 512-element steps cover a row (H <= 512 NS, H % 8 == 0).
 // The row arithmetic lives in Ln16<NS> (one definition for every kernel that normalises a row).
-template <int NS>
+// RMS (T5 handles, T5LayerNorm): w * x * rsqrt(mean(x^2) + eps) — no mean is subtracted and there is no beta (bta is never read).
+template <int NS, bool RMS = false>
 struct Ln16 {
     float gg[NS][8], bb[NS][8], yb[NS][8];     // gamma, beta, the projection's bias (added in fp32) of the lane's elements
     __device__ __forceinline__ void load_params(const float* __restrict__ g, const float* __restrict__ bta, const float* __restrict__ ybias, int H, int lane) {
@@ -214,9 +215,12 @@ struct Ln16 {
             if (i < H) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const float4 a = *reinterpret_cast<const float4*>(g + i + 4 * h), b = *reinterpret_cast<const float4*>(bta + i + 4 * h), c = *reinterpret_cast<const float4*>(ybias + i + 4 * h);
+                    const float4 a = *reinterpret_cast<const float4*>(g + i + 4 * h), c = *reinterpret_cast<const float4*>(ybias + i + 4 * h);
                     gg[j][4 * h] = a.x; gg[j][4 * h + 1] = a.y; gg[j][4 * h + 2] = a.z; gg[j][4 * h + 3] = a.w;
-                    bb[j][4 * h] = b.x; bb[j][4 * h + 1] = b.y; bb[j][4 * h + 2] = b.z; bb[j][4 * h + 3] = b.w;
+                    if constexpr (!RMS) {
+                        const float4 b = *reinterpret_cast<const float4*>(bta + i + 4 * h);
+                        bb[j][4 * h] = b.x; bb[j][4 * h + 1] = b.y; bb[j][4 * h + 2] = b.z; bb[j][4 * h + 3] = b.w;
+                    }
                     yb[j][4 * h] = c.x; yb[j][4 * h + 1] = c.y; yb[j][4 * h + 2] = c.z; yb[j][4 * h + 3] = c.w;
                 }
             }
@@ -263,14 +267,16 @@ struct Ln16 {
     __device__ __forceinline__ void normalize_store(const float (&v)[NS][8], int H, float eps, int lane, uint16_t* xb_row, uint8_t* xlo_row) const {
         typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
         float s = 0.f;
+        if constexpr (!RMS) {
 #pragma unroll
-        for (int j = 0; j < NS; ++j)
-            if (lane * 8 + j * 512 < H)
+            for (int j = 0; j < NS; ++j)
+                if (lane * 8 + j * 512 < H)
 #pragma unroll
-                for (int c = 0; c < 8; ++c) s += v[j][c];
+                    for (int c = 0; c < 8; ++c) s += v[j][c];
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-        const float mu = s / (float)H;
+            for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+        }
+        const float mu = s / (float)H;      // RMS: 0, and x - 0 is x bit for bit
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < NS; ++j)
@@ -287,7 +293,10 @@ struct Ln16 {
                 float o[8];
                 unsigned int ob[4], ol[4];
 #pragma unroll
-                for (int c = 0; c < 8; ++c) o[c] = (v[j][c] - mu) * rstd * gg[j][c] + bb[j][c];
+                for (int c = 0; c < 8; ++c) {
+                    if constexpr (RMS) o[c] = v[j][c] * rstd * gg[j][c];
+                    else o[c] = (v[j][c] - mu) * rstd * gg[j][c] + bb[j][c];
+                }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) ob[c] = pack_bf16x2(o[2 * c], o[2 * c + 1]);
                 *reinterpret_cast<uint4*>(xb_row + i) = make_uint4(ob[0], ob[1], ob[2], ob[3]);
@@ -343,14 +352,14 @@ __global__ __launch_bounds__(256) void k_ln16(const uint16_t* __restrict__ y, co
 // Pre-LN stacks (ModernBert handles): the residual stream r (rb 16-bit high half + optional rlo low-half bytes) is kept apart from the normalised MFMA operand
 // xb.  One launch does  r = (y + bias) + r_in;  store r (rb_out != nullptr: not behind the last layer);  xb = LayerNorm(r)  (+ its low half into xlo, the final
 // LayerNorm only: pooling and kr_encoder_last_hidden read it).  r_in may be the embedding LayerNorm's output in xb itself (layer 0): a wave reads its whole row
-// before it stores it.  Same row arithmetic as k_ln16 (Ln16).
-template <int NS, int POL = 0>
+// before it stores it.  Same row arithmetic as k_ln16 (Ln16).  RMS: T5 handles (Ln16<NS, true>); everything around the row arithmetic is the same.
+template <int NS, int POL = 0, bool RMS = false>
 __global__ __launch_bounds__(256) void k_ln16_pre(const uint16_t* __restrict__ y, const float* __restrict__ ybias, const int* __restrict__ Tp, const float* __restrict__ g,
                                                   const float* __restrict__ bta, float eps, int H, const uint16_t* rb_in, const uint8_t* rlo_in, uint16_t* rb_out,
                                                   uint8_t* rlo_out, uint8_t* xlo, uint16_t* xb) {
     const int lane = threadIdx.x & 63;
     const int T = *Tp;
-    Ln16<NS> ln;
+    Ln16<NS, RMS> ln;
     ln.load_params(g, bta, ybias, H, lane);
     const int64_t step = (int64_t)gridDim.x * 4;
     int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -463,6 +472,90 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __rest
     for (int j = 0; j < VJ; ++j) {
         const int i = tid + j * POOL_WAVES * 64;
         if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] / den : NAN;
+    }
+}
+
+// T5 handles: the embedding row IS the residual stream (no embedding norm, no positions, no token types): r = shared[id] -> rb / rlo, and
+// xb = RMS(block 0's attention norm)(r).  One wave per token, the row arithmetic and the residual codec of k_ln16_pre.
+template <int NS>
+__global__ __launch_bounds__(256) void k_embed_rms(const int* __restrict__ tok_id, const int* __restrict__ Tp, const float* __restrict__ word, const float* __restrict__ g,
+                                                   float eps, int H, uint16_t* __restrict__ rb, uint8_t* __restrict__ rlo, uint16_t* __restrict__ xb) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= *Tp) return;
+    Ln16<NS, true> ln;
+    const float* w = word + (int64_t)tok_id[t] * H;
+    float v[NS][8];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int i = lane * 8 + j * 512;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { v[j][c] = 0.f; ln.gg[j][c] = 0.f; }
+        if (i < H) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float4 a = *reinterpret_cast<const float4*>(w + i + 4 * h), b = *reinterpret_cast<const float4*>(g + i + 4 * h);
+                v[j][4 * h] = a.x; v[j][4 * h + 1] = a.y; v[j][4 * h + 2] = a.z; v[j][4 * h + 3] = a.w;
+                ln.gg[j][4 * h] = b.x; ln.gg[j][4 * h + 1] = b.y; ln.gg[j][4 * h + 2] = b.z; ln.gg[j][4 * h + 3] = b.w;
+            }
+        }
+    }
+    ln.store_residual(v, H, lane, rb + t * H, rlo ? rlo + t * H : nullptr);
+    ln.template normalize_store<false>(v, H, eps, lane, xb + t * H, nullptr);
+}
+
+// The sentence-transformers Dense head behind the pooling (T5 handles with "dense.weight"): out[b, :] = normalize(W . p_b), W [P, H] fp32 without a bias,
+// p = k_pool's normalised [B, H] rows (normalize(W . p / |p|) = normalize(W . p)), fp32 throughout, F.normalize's 1e-12 floor; a NaN pooled row stays NaN.
+// One block of 4 waves per PD_SEQ sequences: the pooled rows sit in LDS, wave w computes features w, w + 4, ... (a lane owns 4 consecutive columns per
+// 256-column step, the partial sums are added in a fixed order), so a W row is read once per PD_SEQ sequences and a row does not depend on its batch.
+constexpr int PD_SEQ = 4;      // = the block's waves: wave s reduces sequence s's norm
+__global__ __launch_bounds__(256) void k_pool_dense(const float* __restrict__ pooled, const float* __restrict__ W, int B, int H, int P, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* p = reinterpret_cast<float*>(smem);          // [PD_SEQ][H]
+    float* y = p + PD_SEQ * H;                          // [PD_SEQ][P]
+    float* red = y + PD_SEQ * P;                        // [PD_SEQ][4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * PD_SEQ;
+    for (int i = tid; i < PD_SEQ * H; i += 256) {
+        const int s = i / H;
+        p[i] = b0 + s < B ? pooled[(int64_t)(b0 + s) * H + (i - s * H)] : 0.f;
+    }
+    __syncthreads();
+    for (int f = wave; f < P; f += 4) {
+        float acc[PD_SEQ];
+#pragma unroll
+        for (int s = 0; s < PD_SEQ; ++s) acc[s] = 0.f;
+        for (int i = lane * 4; i < H; i += 256) {
+            const float4 w = *reinterpret_cast<const float4*>(W + (int64_t)f * H + i);
+#pragma unroll
+            for (int s = 0; s < PD_SEQ; ++s) {
+                const float4 x = *reinterpret_cast<const float4*>(p + s * H + i);
+                acc[s] += (w.x * x.x + w.y * x.y) + (w.z * x.z + w.w * x.w);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < PD_SEQ; ++s) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) acc[s] += __shfl_xor(acc[s], m, 64);
+            if (lane == 0) y[s * P + f] = acc[s];
+        }
+    }
+    __syncthreads();
+    // |y_s|^2: wave w sums sequence w's features (lane-strided, then across the wave): one fixed order per row
+    {
+        float ss = 0.f;
+        for (int f = lane; f < P; f += 64) ss += y[wave * P + f] * y[wave * P + f];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+        if (lane == 0) red[wave] = ss;
+    }
+    __syncthreads();
+    for (int i = tid; i < PD_SEQ * P; i += 256) {
+        const int s = i / P;
+        if (b0 + s >= B) continue;
+        const float nrm = sqrtf(red[s]);
+        const float den = fmaxf(nrm, 1e-12f);           // NaN norm stays NaN (fmaxf would drop it)
+        out[(int64_t)(b0 + s) * P + (i - s * P)] = (nrm == nrm) ? y[i] / den : NAN;
     }
 }
 

@@ -37,16 +37,26 @@ type, the gated MLP ``Wo(gelu(input) * gate)`` with input | gate as one projecti
 the layers ``config.layer_types`` names.  The handle learns all of it through reserved names (``MODERN_SETTINGS``).  An ``intermediate_size`` that is no
 multiple of 128 (ModernBERT-large: 2624) is zero-padded to the next one (``pad_modernbert_ff``: exact).  ``ModernBertE5Encoder`` / ``ModernBertBGEEncoder``
 are the twins over ``transformers.ModernBertModel``.
+
+T5 encoder checkpoints (``model_type`` t5: sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*): ModernBERT's pre-LN schedule with RMS norms
+(``T5LayerNorm``), the embedding row straight into the residual stream, MPNet's bias per (head, bucket of the column distance) — one table, held by block 0,
+added in every layer — on unscaled scores ``q.k + bias``, no linear bias anywhere, and the feed-forward ``wo(relu(wi x))`` (v1.0) or
+``wo(gelu_new(wi_0 x) * wi_1 x)`` (v1.1 / flan).  The handle learns the kind through ``config.t5_feed_forward`` (``T5_SETTING``).  The sentence-transformers
+``Dense`` module of such a checkpoint (a bias-free ``Linear(H -> P)`` between the pooling and the normalisation) is read into ``self.dense`` by
+``from_pretrained`` and runs inside the library (``dense.weight``): the embeddings are then ``[B, P]``.  ``T5E5Encoder`` / ``T5BGEEncoder`` are the twins over
+``transformers.T5EncoderModel``.
 """
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 from typing import Optional
 
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, XLMRobertaModel
+from transformers import BertModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, T5EncoderModel, XLMRobertaModel
 
 from .. import _lib
 
@@ -60,6 +70,12 @@ MODERN_TYPE = "modernbert"
 # reserved names of a ModernBert handle's settings (include/kirag_amd.h): the local layers' rotary frequencies, the half-window, one 0 / 1 flag per layer
 MODERN_SETTINGS = ("config.rotary_inv_freq_local", "config.attention_half_window", "config.local_attention_layers")
 MODERN_LAYER_TYPES = ("full_attention", "sliding_attention")
+T5_TYPE = "t5"
+T5_SETTING = "config.t5_feed_forward"        # reserved name (include/kirag_amd.h): one float, 0 = relu, 1 = gated gelu_new
+T5_FEED_FORWARDS = {("relu", False): 0.0, ("gelu_new", True): 1.0}      # (config.dense_act_fn, config.is_gated_act) -> the setting
+T5_BUCKETS, T5_MAX_DISTANCE = 32, 128        # the bucket rule the attention kernels compute (MPNet's: the same rule as T5's bidirectional one)
+ST_DENSE_TYPE = "sentence_transformers.models.Dense"
+ST_IDENTITY = "torch.nn.modules.linear.Identity"
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
 
 
@@ -99,9 +115,11 @@ class HipBertForward:
         lib = _lib.load()
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
         self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
+        self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
         inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
         modern = self._modern_settings(config) if self.is_modern else None      # likewise
-        if not self.is_nomic and not self.is_modern and getattr(config, "hidden_act", "gelu") != "gelu":
+        t5 = self._t5_settings(config) if self.is_t5 else None                  # likewise
+        if not self.is_nomic and not self.is_modern and not self.is_t5 and getattr(config, "hidden_act", "gelu") != "gelu":
             raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
         if getattr(config, "position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only absolute position embeddings are implemented")
@@ -111,12 +129,16 @@ class HipBertForward:
                              "(the only size HF's MPNetEncoder computes with)")
         # MPNet has no token types: one row of zeros stands in for the table (sync supplies it)
         # ... and neither has ModernBERT; its intermediate size is rounded up to the projections' 128 (pad_modernbert_ff)
-        type_vocab = 1 if self.is_mpnet or self.is_modern else config.type_vocab_size
-        self.ff = int(config.intermediate_size)
+        # ... and T5 has neither token types nor positions: kr_bert_cfg comes from T5Config's own fields (_t5_settings)
+        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 else config.type_vocab_size
+        self.ff = int(t5["intermediate"] if self.is_t5 else config.intermediate_size)
         self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
-        eps = float(config.norm_eps if self.is_modern else config.layer_norm_eps)
-        cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff_pad,
-                           config.vocab_size, config.max_position_embeddings, type_vocab, eps)
+        if self.is_t5:
+            cfg = _lib.BertCfg(t5["hidden"], t5["layers"], t5["heads"], self.ff, config.vocab_size, t5["max_pos"], type_vocab, t5["ln_eps"])
+        else:
+            eps = float(config.norm_eps if self.is_modern else config.layer_norm_eps)
+            cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff_pad,
+                               config.vocab_size, config.max_position_embeddings, type_vocab, eps)
         h = C.c_void_p()
         dt = -1 if operand_dtype is None else {"bf16": 0, "f16": 1}[operand_dtype]
         lo = -1 if residual_lo is None else int(bool(residual_lo))
@@ -124,7 +146,8 @@ class HipBertForward:
         self._lib, self._h, self.device_index = lib, h, device_index
         self.operand_dtype = ("bf16", "f16")[lib.kr_encoder_operand_dtype(h)]
         self.residual_lo = bool(lib.kr_encoder_residual_lo(h))
-        self.hidden = config.hidden_size
+        self.hidden = t5["hidden"] if self.is_t5 else config.hidden_size
+        self.out_dim = self.hidden        # width of the embeddings: P once a Dense head ("dense.weight" [P, hidden], T5 handles) has been loaded
         self.fingerprint = None
         # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P.  It travels through the
         # name-addressed loader under the reserved name "config.position_padding_idx", before the first finalize, and holds for the handle's life
@@ -143,6 +166,35 @@ class HipBertForward:
         if modern is not None:
             for name, t in modern.items():
                 _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
+
+        # a T5 handle: its feed-forward kind
+        if t5 is not None:
+            v = C.c_float(t5["feed_forward"])
+            _lib.check(lib.kr_encoder_load_weight(h, T5_SETTING.encode(), C.addressof(v), 1))
+
+    @staticmethod
+    def _t5_settings(config) -> dict:
+        """``kr_bert_cfg`` and the feed-forward setting of a T5 handle from an HF ``T5Config``; ``NotImplementedError`` naming the field for what the kernels do
+        not compute.  ``max_pos`` only bounds the sequence length (no table is sized by it)."""
+        d_model, d_kv, heads = int(config.d_model), int(config.d_kv), int(config.num_heads)
+        if d_kv * heads != d_model:
+            raise NotImplementedError(f"d_kv={d_kv} x num_heads={heads} != d_model={d_model}: the HIP encoder needs an inner width equal to d_model")
+        if d_kv not in (32, 64):
+            raise NotImplementedError(f"d_kv={d_kv}: the attention kernels are built for heads of width 32 and 64")
+        buckets = getattr(config, "relative_attention_num_buckets", T5_BUCKETS)
+        if buckets != T5_BUCKETS:
+            raise NotImplementedError(f"relative_attention_num_buckets={buckets}: the attention kernels compute {T5_BUCKETS} buckets")
+        max_distance = getattr(config, "relative_attention_max_distance", T5_MAX_DISTANCE)
+        if max_distance != T5_MAX_DISTANCE:
+            raise NotImplementedError(f"relative_attention_max_distance={max_distance}: the attention kernels compute max_distance {T5_MAX_DISTANCE}")
+        kind = (getattr(config, "dense_act_fn", "relu"), bool(getattr(config, "is_gated_act", False)))
+        if kind not in T5_FEED_FORWARDS:
+            raise NotImplementedError(f"dense_act_fn={kind[0]!r} with is_gated_act={kind[1]} (feed_forward_proj={getattr(config, 'feed_forward_proj', None)!r}): "
+                                      "relu and gated gelu_new are implemented")
+        if int(config.d_ff) % 128:
+            raise NotImplementedError(f"d_ff={config.d_ff}: the projections need a multiple of 128")
+        return {"hidden": d_model, "layers": int(config.num_layers), "heads": heads, "intermediate": int(config.d_ff),
+                "max_pos": int(getattr(config, "n_positions", None) or 512), "ln_eps": float(config.layer_norm_epsilon), "feed_forward": T5_FEED_FORWARDS[kind]}
 
     @staticmethod
     def _modern_settings(config) -> dict:
@@ -239,9 +291,15 @@ class HipBertForward:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
+            self._note_dense(name, t.numel())
         self._load_zero_token_types()
         _lib.check(self._lib.kr_encoder_finalize(self._h))
         self.fingerprint = fp
+
+    def _note_dense(self, name: str, numel: int) -> None:
+        """``dense.weight`` [P, hidden] was accepted by the library: the forwards now write [B, P]"""
+        if name == "dense.weight":
+            self.out_dim = int(numel) // self.hidden
 
     def _load_zero_token_types(self) -> None:
         if self.is_mpnet or self.is_modern:
@@ -260,6 +318,7 @@ class HipBertForward:
                 w = w.detach().float().contiguous()
                 ptr, n = w.data_ptr(), w.numel()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), ptr, n))
+            self._note_dense(name, n)
         if not any(name.endswith("token_type_embeddings.weight") for name in state):
             self._load_zero_token_types()
         _lib.check(self._lib.kr_encoder_finalize(self._h))
@@ -270,7 +329,7 @@ class HipBertForward:
         import numpy as np
         ids = np.ascontiguousarray(input_ids, dtype=np.int64); mask = np.ascontiguousarray(attention_mask, dtype=np.int64)
         B, S = ids.shape
-        out = np.empty((B, self.hidden), np.float32)
+        out = np.empty((B, self.out_dim), np.float32)
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.ctypes.data, mask.ctypes.data, B, S, pool, out.ctypes.data, None))
         else:
@@ -287,7 +346,7 @@ class HipBertForward:
         ids = input_ids.to(torch.int64).contiguous()
         mask = attention_mask.to(device=ids.device, dtype=torch.int64).contiguous()
         B, S = ids.shape
-        out = torch.empty((B, self.hidden), dtype=torch.float32, device=ids.device)
+        out = torch.empty((B, self.out_dim), dtype=torch.float32, device=ids.device)
         stream = _lib.current_stream_ptr() if ids.is_cuda else None
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.data_ptr(), mask.data_ptr(), B, S, pool, out.data_ptr(), stream))
@@ -322,7 +381,7 @@ class HipBertForward:
         buf[:n].view(B, S).copy_(input_ids)
         buf[n:2 * n].view(B, S).copy_(attention_mask)
         dev = torch.device("cuda", self.device_index)
-        out = torch.empty((B, self.hidden), dtype=torch.float32, device=dev)
+        out = torch.empty((B, self.out_dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(self.device_index):
             _lib.check(self._lib.kr_encoder_forward(self._h, buf.data_ptr(), buf.data_ptr() + 8 * n, B, S, pool, out.data_ptr(), _lib.current_stream_ptr()))
             ev = torch.cuda.Event(); ev.record()
@@ -342,7 +401,7 @@ class HipBertForward:
             raise ValueError(f"total_tokens {T} exceeds the {token_ids.numel()} entries of token_ids")
         dev = torch.device("cuda", self.device_index)
         if out is None:
-            out = torch.empty((B, self.hidden), dtype=torch.float32, device=dev)
+            out = torch.empty((B, self.out_dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(self.device_index):
             _lib.check(self._lib.kr_encoder_forward_packed(self._h, token_ids.data_ptr(), seq_lens.data_ptr(), B, int(S), T, pool, out.data_ptr(),
                                                            _lib.current_stream_ptr()))
@@ -427,7 +486,7 @@ class _HipSentenceMixin:
         return out
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        kw = {} if self._hf_base in (MPNetModel, ModernBertModel) else {"token_type_ids": token_type_ids}     # MPNet and ModernBERT have no token types
+        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT and T5 have no token types
         out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
@@ -436,8 +495,16 @@ class _HipSentenceMixin:
             return self._hip_forward(input_ids, attention_mask, token_type_ids)
         last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
         embeddings = average_pool(last_hidden_states, attention_mask) if self._pool == POOL_MEAN else last_hidden_states[:, 0]
+        if getattr(self, "dense", None) is not None:         # the sentence-transformers Dense head of a T5 checkpoint
+            embeddings = self.dense(embeddings)
         embeddings = F.normalize(embeddings, p=2, dim=1)
         return embeddings
+
+    @property
+    def embedding_size(self) -> int:
+        """width of the embeddings ``forward`` returns: ``out_features`` of the Dense head where the checkpoint has one, else ``config.hidden_size``"""
+        dense = getattr(self, "dense", None)
+        return int(dense.out_features) if dense is not None else int(self.config.hidden_size)
 
     def hip_last_hidden_state(self, B: int, S: int) -> Tensor:
         """last_hidden_state [B,S,H] (CPU, fp32) of the previous HIP forward; rows of masked positions are zero."""
@@ -454,6 +521,7 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _mpnet_twin = None               # ... and over MPNetModel
     _nomic_twin = None               # ... and over NomicBertModel
     _modern_twin = None              # ... and over ModernBertModel
+    _t5_twin = None                  # ... and over T5EncoderModel
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -479,6 +547,9 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
         if model_type == MODERN_TYPE:
             # a pre-LN stack under names of its own
             return cls._modern_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type == T5_TYPE:
+            # an encoder-only T5: RMS norms, a relative attention bias, and (sentence-transformers checkpoints) a Dense head behind the pooling
+            return cls._t5_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -501,6 +572,119 @@ class _HipModernBertSentenceEncoder(_HipSentenceMixin, ModernBertModel):
         ModernBertModel.__init__(self, config)      # ModernBertModel has no pooling layer to ask for
         self.kwargs = kwargs
         self._hip = None
+
+
+def _st_file(where, name: str, kwargs: dict) -> Optional[str]:
+    """path of file ``name`` of the checkpoint ``where`` (a folder, or a hub id through transformers' cache), ``None`` when it has none"""
+    from transformers.utils import cached_file
+    loc = {k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs and k != "trust_remote_code"}
+    return cached_file(where, name, _raise_exceptions_for_missing_entries=False, _raise_exceptions_for_gated_repo=False,
+                       _raise_exceptions_for_connection_errors=False, **loc)
+
+
+def read_st_dense(where, d_model: int, **kwargs) -> Optional[Tensor]:
+    """The weight ``[P, d_model]`` of the ``sentence_transformers.models.Dense`` module that the checkpoint's ``modules.json`` lists, ``None`` when there is no
+    ``modules.json`` or no such module.  Only what the library computes is accepted — ``in_features == d_model``, no bias, an identity activation — anything
+    else is a ``NotImplementedError`` naming the field.  Needs no ``sentence_transformers``: the files are read as they are."""
+    listing = _st_file(where, "modules.json", kwargs)
+    if listing is None:
+        return None
+    with open(listing) as f:
+        dense = [m for m in json.load(f) if m.get("type") == ST_DENSE_TYPE]
+    if not dense:
+        return None
+    if len(dense) > 1:
+        raise NotImplementedError(f"modules.json lists {len(dense)} Dense modules: one is implemented")
+    sub = dense[0]["path"]
+    cfg_path = _st_file(where, f"{sub}/config.json", kwargs)
+    if cfg_path is None:
+        raise FileNotFoundError(f"modules.json lists the Dense module {sub!r}, which has no config.json")
+    with open(cfg_path) as f:
+        dc = json.load(f)
+    if dc.get("in_features") != d_model:
+        raise NotImplementedError(f"Dense in_features={dc.get('in_features')}: the head must read the pooled d_model={d_model}")
+    if dc.get("bias", True):
+        raise NotImplementedError("Dense bias=True: a head without a bias is implemented")
+    if dc.get("activation_function", ST_IDENTITY) != ST_IDENTITY:
+        raise NotImplementedError(f"Dense activation_function={dc.get('activation_function')!r}: the identity is implemented")
+    st = _st_file(where, f"{sub}/model.safetensors", kwargs)
+    if st is not None:
+        from safetensors.torch import load_file
+        state = load_file(st)
+    else:
+        pt = _st_file(where, f"{sub}/pytorch_model.bin", kwargs)
+        if pt is None:
+            raise FileNotFoundError(f"the Dense module {sub!r} has neither model.safetensors nor pytorch_model.bin")
+        state = torch.load(pt, map_location="cpu", weights_only=True)
+    w = state["linear.weight"].float()
+    if w.dim() != 2 or w.shape[1] != d_model or w.shape[0] != dc.get("out_features", w.shape[0]):
+        raise ValueError(f"Dense linear.weight has shape {tuple(w.shape)}, its config says [{dc.get('out_features')}, {d_model}]")
+    return w
+
+
+class _HipT5SentenceEncoder(_HipSentenceMixin, T5EncoderModel):
+    """``self.dense``: the checkpoint's sentence-transformers Dense head (``None`` without one), a parameter like any other — the weight sync loads it as
+    ``dense.weight`` and ``train()`` mode applies it in torch.  ``save_pretrained`` writes it back the way it was found (``modules.json`` + ``2_Dense/``), next
+    to a ``T5EncoderModel`` checkpoint that any T5 loader reads."""
+    _hf_base = T5EncoderModel
+    ST_DENSE_DIR = "2_Dense"
+
+    def __init__(self, config, add_pooling_layer=False, **kwargs):
+        T5EncoderModel.__init__(self, config)       # T5EncoderModel has no pooling layer to ask for
+        self.kwargs = kwargs
+        self._hip = None
+        self.dense = None
+        HipBertForward._t5_settings(config)         # refuses what the kernels do not compute when the model is made, not at its first forward
+
+    def set_dense(self, weight: Optional[Tensor]) -> None:
+        """install (or, with ``None``, remove) the Dense head ``[P, d_model]``"""
+        if weight is None:
+            self.dense = None
+        else:
+            P, H = weight.shape
+            p = next(self.parameters())
+            self.dense = torch.nn.Linear(H, P, bias=False, device=p.device, dtype=p.dtype)
+            with torch.no_grad():
+                self.dense.weight.copy_(weight)
+        self.invalidate_hip_weights()
+        if self._hip is not None and self._hip.out_dim != self.embedding_size:
+            self._hip = None                        # the output width of a handle is fixed at its first finalize
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        w = read_st_dense(pretrained_model_name_or_path, int(model.config.d_model), **kwargs)
+        if w is not None:
+            model.set_dense(w)
+        return model
+
+    def save_pretrained(self, save_directory, *args, **kwargs):
+        dense = self.dense
+        if dense is None:
+            return super().save_pretrained(save_directory, *args, **kwargs)
+        del self.dense                              # the transformer's own files hold T5EncoderModel's state dict and nothing else
+        try:
+            out = super().save_pretrained(save_directory, *args, **kwargs)
+        finally:
+            self.dense = dense
+        from safetensors.torch import save_file
+        sub = os.path.join(save_directory, self.ST_DENSE_DIR)
+        os.makedirs(sub, exist_ok=True)
+        P, H = dense.weight.shape
+        with open(os.path.join(sub, "config.json"), "w") as f:
+            json.dump({"in_features": H, "out_features": P, "bias": False, "activation_function": ST_IDENTITY}, f, indent=2)
+        save_file({"linear.weight": dense.weight.detach().float().cpu().contiguous()}, os.path.join(sub, "model.safetensors"))
+        pool = {"word_embedding_dimension": H, "pooling_mode_cls_token": self._pool == POOL_CLS, "pooling_mode_mean_tokens": self._pool == POOL_MEAN}
+        os.makedirs(os.path.join(save_directory, "1_Pooling"), exist_ok=True)
+        with open(os.path.join(save_directory, "1_Pooling", "config.json"), "w") as f:
+            json.dump(pool, f, indent=2)
+        modules = [{"idx": 0, "name": "0", "path": "", "type": "sentence_transformers.models.Transformer"},
+                   {"idx": 1, "name": "1", "path": "1_Pooling", "type": "sentence_transformers.models.Pooling"},
+                   {"idx": 2, "name": "2", "path": self.ST_DENSE_DIR, "type": ST_DENSE_TYPE},
+                   {"idx": 3, "name": "3", "path": "3_Normalize", "type": "sentence_transformers.models.Normalize"}]
+        with open(os.path.join(save_directory, "modules.json"), "w") as f:
+            json.dump(modules, f, indent=2)
+        return out
 
 
 class E5Encoder(_HipSentenceEncoder):
@@ -553,6 +737,16 @@ class ModernBertBGEEncoder(_HipModernBertSentenceEncoder):
     _pool = POOL_CLS
 
 
+class T5E5Encoder(_HipT5SentenceEncoder):
+    """T5EncoderModel -> masked mean -> Dense -> L2 normalise (sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*)"""
+    _pool = POOL_MEAN
+
+
+class T5BGEEncoder(_HipT5SentenceEncoder):
+    """T5EncoderModel -> [:, 0] -> Dense -> L2 normalise"""
+    _pool = POOL_CLS
+
+
 E5Encoder._roberta_twin = XLMRobertaE5Encoder
 BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
 E5Encoder._mpnet_twin = MPNetE5Encoder
@@ -561,6 +755,8 @@ E5Encoder._nomic_twin = NomicBertE5Encoder
 BGEEncoder._nomic_twin = NomicBertBGEEncoder
 E5Encoder._modern_twin = ModernBertE5Encoder
 BGEEncoder._modern_twin = ModernBertBGEEncoder
+E5Encoder._t5_twin = T5E5Encoder
+BGEEncoder._t5_twin = T5BGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:

@@ -9,7 +9,10 @@ MPNet one (model_type mpnet: all-mpnet-base-v2, multi-qa-mpnet-*; reference MPNe
 nomic-embed-text-v1 / -v1.5; reference NomicBertModel in fp32, GPU only: rotary positions and the gated MLP are not in the torch emulation), a ModernBERT
 one (model_type modernbert: gte-modernbert-base, modernbert-embed, granite-embedding-english-r2; reference ModernBertModel in fp32 with eager attention, GPU
 only; "LN1" / "LN2" are then the PRE-LN residual stream behind the attention and behind the MLP — the stream whose large-magnitude channels decide whether
-f16 operands stay in range, which no synthetic recipe of this repository was fitted to: this tool is how to find out) or a
+f16 operands stay in range, which no synthetic recipe of this repository was fitted to: this tool is how to find out), a T5 encoder one (model_type t5:
+sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*, loaded as the T5 twin of the encoders with the folder's sentence-transformers Dense
+head where modules.json lists one; reference T5EncoderModel in fp32 + pooling + that head, GPU only; "LN1" / "LN2" are again the pre-LN residual stream, and
+the feed-forward's hidden state is among the 16-bit-stored tensors: HF's own fp16 runs of v1.1 / flan sizes are known to overflow there) or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -96,9 +99,20 @@ def reference_and_stats(model, batches, pool, dev):
                 stats[li][key].append(t.detach()[cur["mask"]].abs().float().flatten().cpu())
             stats[li]["max16"] = max(stats[li]["max16"], float(t.detach()[cur["mask"]].abs().max()))
         return fn
+    t5 = hasattr(model.encoder, "block") if hasattr(model, "encoder") else False       # T5EncoderModel: encoder.block.N.layer.{0: SelfAttention, 1: DenseReluDense}
+    for li, block in enumerate(model.encoder.block if t5 else ()):
+        # as for ModernBERT: the residual stream is what layer.1.layer_norm reads and what the block returns; 16-bit-stored: q, k, v, the attention output
+        # projection, both norm outputs (the operands), the feed-forward's hidden state and its output
+        att, ff = block.layer[0], block.layer[1]
+        hooks.append(ff.layer_norm.register_forward_pre_hook(lambda _m, inp, f=grab(li, "ln1"): f(_m, inp, inp[0])))
+        hooks.append(block.register_forward_hook(grab(li, "ln2")))
+        for key, mod in (("q", att.SelfAttention.q), ("k", att.SelfAttention.k), ("v", att.SelfAttention.v), ("y1", att.SelfAttention.o), ("x0", att.layer_norm),
+                         ("x1", ff.layer_norm), ("y2", ff.DenseReluDense.wo)):
+            hooks.append(mod.register_forward_hook(grab(li, key)))
+        hooks.append(ff.DenseReluDense.wo.register_forward_pre_hook(lambda _m, inp, f=grab(li, "h"): f(_m, inp, inp[0])))
     nomic = hasattr(model, "layers")                   # NomicBertModel: layers.N.{self_attn, mlp, post_attention_layernorm, post_mlp_layernorm}
     modern = nomic and hasattr(model, "final_norm")    # ModernBertModel: layers.N.{attn_norm, attn, mlp_norm, mlp}
-    for li, layer in enumerate(model.layers if nomic else model.encoder.layer):
+    for li, layer in enumerate(() if t5 else model.layers if nomic else model.encoder.layer):
         if modern:
             # the residual stream itself (16-bit high half + low byte on the device) is what mlp_norm reads (behind the attention) and what the layer returns;
             # 16-bit-stored: q | k | v, the attention output projection, the LayerNorm outputs (the operands), the gated product, the MLP output
@@ -124,15 +138,18 @@ def reference_and_stats(model, batches, pool, dev):
         for key, mod in mods + (("h", layer.intermediate), ("y2", layer.output.dense), ("ln2", layer.output.LayerNorm)):
             hooks.append(mod.register_forward_hook(grab(li, key)))
     embs = []
+    hf_forward = getattr(model, "_hf_base", type(model)).forward      # a twin of the encoders (T5): its HF base class's forward, not the HIP path
     with torch.no_grad():
         for ids, mask in batches:
             cur["mask"] = torch.from_numpy(mask).bool().to(dev)
-            out = model(input_ids=torch.from_numpy(ids).to(dev), attention_mask=torch.from_numpy(mask).to(dev)).last_hidden_state
+            out = hf_forward(model, input_ids=torch.from_numpy(ids).to(dev), attention_mask=torch.from_numpy(mask).to(dev)).last_hidden_state
             if pool == "mean":
                 m = torch.from_numpy(mask).to(dev)[..., None].bool()
                 e = out.masked_fill(~m, 0.0).sum(1) / m.sum(1)
             else:
                 e = out[:, 0]
+            if getattr(model, "dense", None) is not None:      # the sentence-transformers Dense head of a T5 checkpoint
+                e = model.dense(e)
             embs.append(torch.nn.functional.normalize(e, dim=-1).cpu().numpy())
     for h in hooks:
         h.remove()
@@ -167,10 +184,13 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
-    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
+    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
+    if getattr(cfg, "model_type", "bert") == T5_TYPE:
+        # the encoder half alone, as the twin of the pooling asked for: its from_pretrained also reads the folder's Dense head (modules.json)
+        return check_model((T5E5Encoder if args.pool == "mean" else T5BGEEncoder).from_pretrained(hf_dir), args, hf_dir)
     if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5) and ModernBERT")
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT and T5 encoders")
     if cfg.model_type == MODERN_TYPE:
         model = AutoModel.from_pretrained(hf_dir, attn_implementation="eager")      # ModernBertModel has no pooling layer
     else:
@@ -180,7 +200,7 @@ def check(hf_dir, args):
 
 def check_model(model, args, hf_dir="(in-memory model)"):
     """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
-    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES
+    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
     mpnet = getattr(cfg, "model_type", "bert") == MPNET_TYPE
@@ -193,6 +213,9 @@ def check_model(model, args, hf_dir="(in-memory model)"):
     if getattr(cfg, "model_type", "bert") == MODERN_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with rotary positions, a gated MLP and sliding-window attention, which the torch "
                          "emulation does not implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") == T5_TYPE and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms and a relative attention bias, which the torch emulation does not "
+                         "implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
     batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated ...] [--pool mean|cls] [--hf-fp16]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -38,7 +38,17 @@ MODERNBERT_BASE = dict(hidden_size=768, num_hidden_layers=22, num_attention_head
                        rope_parameters={"full_attention": {"rope_type": "default", "rope_theta": 160000.0},
                                         "sliding_attention": {"rope_type": "default", "rope_theta": 10000.0}})
 MODERNBERT_BASE_GLOBAL = dict(MODERNBERT_BASE, layer_types=["full_attention"] * 22)
-SHAPES = dict(BS.ENCODER_SHAPES, **{"modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# T5 encoders (gtr-t5-base, sentence-t5-base: t5-base, relu feed-forward; instructor-base / flan: t5-base-gated = v1.1, FF 2048 with wi_0 | wi_1 as one
+# projection of 4096 columns).  t5-base has mpnet-base's H, heads, FF, bias table, 24 H^2 projection FLOPs per token and layer and launch count: what the
+# separate residual stream of the pre-LN stack costs is the difference of the two.  The BERT-style fields serve the synthetic draws and the FLOP count.
+T5_KEYS = ("d_model", "d_kv", "num_heads", "d_ff", "num_layers", "vocab_size", "feed_forward_proj", "layer_norm_epsilon", "relative_attention_num_buckets",
+           "relative_attention_max_distance")
+T5_BASE = dict(d_model=768, d_kv=64, num_heads=12, d_ff=3072, num_layers=12, vocab_size=32128, feed_forward_proj="relu", dense_act_fn="relu", is_gated_act=False,
+               layer_norm_epsilon=1e-6, relative_attention_num_buckets=32, relative_attention_max_distance=128, n_positions=512, model_type="t5",
+               hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=512, type_vocab_size=1,
+               layer_norm_eps=1e-6)
+T5_BASE_GATED = dict(T5_BASE, d_ff=2048, intermediate_size=2048, feed_forward_proj="gated-gelu", dense_act_fn="gelu_new", is_gated_act=True)
+SHAPES = dict(BS.ENCODER_SHAPES, **{"t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -50,7 +60,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--hf-fp16", action="store_true")
 ap.add_argument("--pool", default="mean", choices=["mean", "cls"])
 ap.add_argument("--first-forward", action="store_true")
-args = ap.parse_args()
+args = ap.parse_args() if __name__ == "__main__" else ap.parse_args([])      # imported (tools/one_shape.py): SHAPES and make_encoder only
 n, S, ragged = args.n, args.S, args.ragged == "ragged"
 dev = torch.device("cuda:0")
 
@@ -70,6 +80,12 @@ def hf_classes(cfg):
     """(config class, model class, sentence-encoder module) of a shape: the RoBERTa family by its model_type"""
     import transformers as T
     from kirag_amd.retriever import encoders as ENC
+    if cfg.get("model_type") == ENC.T5_TYPE:
+        def T5Config(**kw):
+            return T.T5Config(**{k: kw[k] for k in T5_KEYS}, dropout_rate=0.0)
+        def T5EncoderModel(config, add_pooling_layer=False):
+            return T.T5EncoderModel(config)
+        return T5Config, T5EncoderModel, (ENC.T5E5Encoder if args.pool == "mean" else ENC.T5BGEEncoder)
     if cfg.get("model_type") == ENC.MODERN_TYPE:
         return T.ModernBertConfig, T.ModernBertModel, (ENC.ModernBertE5Encoder if args.pool == "mean" else ENC.ModernBertBGEEncoder)
     if cfg.get("model_type") == ENC.NOMIC_TYPE:
@@ -84,7 +100,7 @@ def hf_classes(cfg):
 def make_encoder(cfg):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw)"""
-    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert"):
+    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5"):
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
     from kirag_amd.retriever.encoders import HipBertForward
@@ -108,6 +124,26 @@ def make_encoder(cfg):
             wi = state[f"{b}{l}.intermediate.dense.weight"]
             st[f"layers.{l}.mlp.Wi.weight"] = torch.cat([wi, 0.02 * torch.randn(wi.shape, generator=g, device=dev)])
             st[f"layers.{l}.mlp.Wo.weight"] = state[f"{b}{l}.output.dense.weight"]
+        state = st
+    elif cfg["model_type"] == "t5":
+        # the same draws under T5EncoderModel's names: no biases, no position table, the norms in their pre-LN places, wi_1 = a second draw, a table N(0, 1)
+        L, b = cfg["num_layers"], "encoder.layer."
+        st = {"shared.weight": state["embeddings.word_embeddings.weight"], "encoder.final_layer_norm.weight": state[f"{b}{L - 1}.output.LayerNorm.weight"],
+              "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight": torch.randn(32, cfg["num_heads"], generator=g, device=dev)}
+        for l in range(L):
+            p = f"encoder.block.{l}.layer."
+            for n, t in (("query", "q"), ("key", "k"), ("value", "v")):
+                st[f"{p}0.SelfAttention.{t}.weight"] = state[f"{b}{l}.attention.self.{n}.weight"]
+            st[f"{p}0.SelfAttention.o.weight"] = state[f"{b}{l}.attention.output.dense.weight"]
+            st[f"{p}0.layer_norm.weight"] = state[f"{b}{l - 1}.output.LayerNorm.weight"] if l else state["embeddings.LayerNorm.weight"]
+            st[f"{p}1.layer_norm.weight"] = state[f"{b}{l}.attention.output.LayerNorm.weight"]
+            wi = state[f"{b}{l}.intermediate.dense.weight"]
+            if cfg["is_gated_act"]:
+                st[f"{p}1.DenseReluDense.wi_0.weight"] = wi
+                st[f"{p}1.DenseReluDense.wi_1.weight"] = 0.02 * torch.randn(wi.shape, generator=g, device=dev)
+            else:
+                st[f"{p}1.DenseReluDense.wi.weight"] = wi
+            st[f"{p}1.DenseReluDense.wo.weight"] = state[f"{b}{l}.output.dense.weight"]
         state = st
     elif cfg["model_type"] == "nomic_bert":
         names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),
@@ -149,7 +185,7 @@ def first_forward(shape, cfg, ids, mask):
 
 
 pool = 0 if args.pool == "mean" else 1
-for shape in args.shape or ["e5-large"]:
+for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
     cfg = SHAPES[shape]
     ids, mask = BS.synthetic_tokens(dev, n, S, seed=1, ragged=ragged)
     if "pad_token_id" in cfg:
@@ -165,6 +201,9 @@ for shape in args.shape or ["e5-large"]:
     if cfg.get("model_type") == "modernbert":      # FF is not 4 H: 8 H^2 (q, k, v, o) + 6 H FF (input, gate, out) per token and layer; the attention FLOPs are
         lens = mask.sum(1).double()                # counted as global in both shapes (what the window saves shows as rate)
         fl = float((cfg["num_hidden_layers"] * lens * (8.0 * cfg["hidden_size"] ** 2 + 6.0 * cfg["hidden_size"] * cfg["intermediate_size"] + 4.0 * lens * cfg["hidden_size"])).sum())
+    if cfg.get("model_type") == "t5" and cfg["is_gated_act"]:      # 8 H^2 (q, k, v, o) + 6 H FF (wi_0, wi_1, wo) per token and layer
+        lens = mask.sum(1).double()
+        fl = float((cfg["num_layers"] * lens * (8.0 * cfg["hidden_size"] ** 2 + 6.0 * cfg["hidden_size"] * cfg["d_ff"] + 4.0 * lens * cfg["hidden_size"])).sum())
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
           f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
