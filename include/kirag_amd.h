@@ -232,6 +232,7 @@ typedef struct {
 
 #define KR_POOL_MEAN 0 /* E5: average_pool (encoders.py:56-58) then F.normalize */
 #define KR_POOL_CLS 1  /* BGE: last_hidden[:,0] (encoders.py:116) then F.normalize */
+#define KR_POOL_CLASSIFY 2 /* cross-encoder rerankers: last_hidden[:,0] -> the classification head -> raw logits [B, L] (needs "classifier.*", below) */
 
 /* 16-bit type of the MFMA operands and of every stored activation (weights, residual stream, q / k / v, P, ctx, h); accumulation is fp32 and the
  * LayerNorms run in fp32 either way.  f16 has 11 significand bits (|x| <= 65504), bf16 8: with outlier hidden channels (what real BERT-family
@@ -333,12 +334,28 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   (P = 768 for every GTR size).  A count that is no multiple of hidden, or a P outside that range, is KR_EINVAL.  With it EVERY forward entry point writes
  *   out [B, P] = normalize(W . pooled) instead of [B, hidden] (the caller knows P from the tensor it loaded); an all-masked sequence still gives a NaN row.
  *   Like the settings it is fixed at the first finalize: later the same P takes new values, another P — or the tensor on a handle finalized without it — is
- *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]). */
+ *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]).
+ * Sequence classification (cross-encoder rerankers: BAAI/bge-reranker-base / -large / -v2-m3 = XLMRobertaForSequenceClassification,
+ * cross-encoder/ms-marco-MiniLM-L-6-v2 / -L-12-v2 / ms-marco-TinyBERT = BertForSequenceClassification): the head travels under ONE spelling,
+ * RobertaClassificationHead's,
+ *   "classifier.dense.weight" [hidden, hidden], "classifier.dense.bias" [hidden], "classifier.out_proj.weight" [L, hidden], "classifier.out_proj.bias" [L],
+ *   fp32, 1 <= L <= 64 (L = the rows of out_proj; any other count is KR_EINVAL).  All four or none: a partial set fails kr_encoder_finalize as "never loaded".
+ *   With the head, pool = KR_POOL_CLASSIFY is accepted by the three forward entry points and writes out [B, L] fp32,
+ *       logits = out_proj.weight . tanh(dense.weight . x + dense.bias) + out_proj.bias,     x = last_hidden[:, 0] (NOT normalised),
+ *   raw logits (a sigmoid / softmax is the caller's), fp32 arithmetic throughout; a sequence's logits do not depend on the batch around it.  For the packing
+ *   front end, the attention kernel choice and the last layer on the CLS rows it behaves exactly as KR_POOL_CLS; an all-masked sequence gives a NaN row; a
+ *   non-finite CLS row is reported as KR_ERANGE like a non-finite embedding.  Pools 0 and 1 on such a handle run as on a handle without the head and still
+ *   write [B, hidden].  KR_POOL_CLASSIFY on a handle without the head is KR_ESTATE, naming the missing tensors.  The head follows the rule of "dense.weight":
+ *   fixed at the first finalize — later the same L takes new values, another L, or any of the four on a handle finalized without them, is KR_EINVAL.
+ *   kr_encoder_finalize refuses it (KR_EINVAL, naming it) on NomicBert, ModernBert and T5 handles — their classification heads are other functions — and next
+ *   to "dense.weight".  BertForSequenceClassification's spelling of the same arithmetic (pooler.dense.* -> tanh -> classifier.{weight,bias}) is mapped onto
+ *   these names by the Python layer (kirag_amd.retriever.rerankers.BertReranker); the library itself keeps ignoring "pooler.*". */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);
 /* forward(input_ids, attention_mask) (encoders.py:67-77 / :106-118); token_type_ids are 0 as in every caller.
- *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised ([B,P] on a handle that was given "dense.weight" [P, hidden]).
+ *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised ([B,P] on a handle that was given "dense.weight" [P, hidden];
+ *   [B,L] raw logits with pool = KR_POOL_CLASSIFY).
  *   A sequence whose mask is all zero yields NaN (mean pool) exactly like the reference. */
 int kr_encoder_forward(kr_encoder* enc, const int64_t* input_ids, const int64_t* attention_mask, int B, int S,
                        int pool, float* out, void* stream);

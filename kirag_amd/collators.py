@@ -122,3 +122,59 @@ class BGECollator(RetrieverCollator):
 
 
 COLLATOR_MAP = {"E5Retriever": E5Collator, "BGERetriever": BGECollator}   # utils/const.py:5-8
+
+
+class RerankerCollator:
+    """(query, passage) pairs for a cross-encoder: the HF pair call, ``<s> query </s></s> passage </s>`` (XLM-R) or ``[CLS] query [SEP] passage [SEP]`` with
+    token types 0…0 1…1 (BERT), whatever the tokenizer's template says.  Only the passage side is truncated (``truncation="only_second"``): the query survives
+    whole at ``maxlength``.  ``token_type_ids`` are returned when the tokenizer emits them."""
+    KEYS = ("input_ids", "attention_mask", "token_type_ids")
+
+    def __init__(self, tokenizer, maxlength=512, **kwargs):
+        self.tokenizer = tokenizer
+        self.maxlength = maxlength
+        self.kwargs = kwargs
+
+    def _check(self, queries, passages):
+        if not queries or not passages or len(queries) != len(passages):
+            raise ValueError("queries and passages must be non-empty lists of the same length")
+
+    def encode_pairs(self, queries, passages, **kwargs):
+        self._check(queries, passages)
+        maxlen = kwargs.get("max_length", None) or self.maxlength
+        enc = self.tokenizer(list(queries), list(passages), max_length=maxlen, padding=True, truncation="only_second", return_tensors="pt")
+        return {k: enc[k] for k in self.KEYS if k in enc}
+
+    def tokenize_pairs(self, queries, passages, **kwargs):
+        """the same pairs without padding: one dict of id lists per pair (``pad`` makes a batch of any subset)"""
+        self._check(queries, passages)
+        maxlen = kwargs.get("max_length", None) or self.maxlength
+        enc = self.tokenizer(list(queries), list(passages), max_length=maxlen, padding=False, truncation="only_second")
+        keys = [k for k in self.KEYS if k in enc]
+        return [{k: enc[k][i] for k in keys} for i in range(len(queries))]
+
+    def pad(self, rows):
+        enc = self.tokenizer.pad(rows, padding=True, return_tensors="pt")
+        return {k: enc[k] for k in self.KEYS if k in enc}
+
+
+class BGEKGChainRerankerCollator(RerankerCollator):
+    """The collator ``knowledge_graph/models.py:217,424-433`` calls and the reference never defines: a list of
+    ``{"index", "questions", "reasoning_chains", "labels"}`` -> ``(args, labels, index)``, one pair per (question, reasoning chain) over the whole list.
+    The passage of a pair is the chain's texts joined by ONE space — this project's definition."""
+
+    def __init__(self, tokenizer, maxlength=512, **kwargs):
+        super().__init__(tokenizer, maxlength, **kwargs)
+
+    @staticmethod
+    def chain_text(chain):
+        return chain if isinstance(chain, str) else " ".join(chain)
+
+    def __call__(self, batch):
+        import torch
+        questions = [q for ex in batch for q in ex["questions"]]
+        chains = [self.chain_text(c) for ex in batch for c in ex["reasoning_chains"]]
+        args = self.encode_pairs(questions, chains)
+        labels = torch.tensor([l for ex in batch for l in ex["labels"]], dtype=torch.long)
+        index = torch.tensor([ex["index"] for ex in batch], dtype=torch.long)
+        return args, labels, index

@@ -30,6 +30,9 @@
 // Wq), no linear bias, the FF wo(relu(wi x)) (EPI_RELU) or wo(gelu_new(wi_0 x) * wi_1 x) (EPI_GEGLU_TANH), and optionally the sentence-transformers Dense head
 // behind the pooling ("dense.weight", k_pool_dense: out [B, P]).
 //
+// Sequence classification (cross-encoder rerankers, KR_POOL_CLASSIFY): BERT / RoBERTa handles with the four "classifier.*" tensors run CLS pooling's forward up
+// to the last LayerNorm, then k_pool<.., RAW> (the un-normalised CLS row) and k_cls_head: out [B, L] = Wo . tanh(Wd . x + bd) + bo, raw logits.
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -132,6 +135,12 @@ struct Encoder {
     float* dense_w = nullptr; int dense_rows = 0;
     float* pooled = nullptr;
     int out_dim() const { return dense_rows > 0 ? dense_rows : cfg.hidden; }
+    // "classifier.{dense,out_proj}.{weight,bias}" fp32: the sequence-classification head behind the raw CLS row (KR_POOL_CLASSIFY, k_cls_head).  cls_labels = L,
+    // the rows of out_proj (0: none yet); cls_got: one bit per tensor (CLS_*), all four or none at finalize; with it `pooled` holds the head's input
+    float *cls_wd = nullptr, *cls_bd = nullptr, *cls_wo = nullptr, *cls_bo = nullptr;
+    int cls_labels = 0; unsigned cls_got = 0;
+    bool has_head() const { return cls_got == 15u; }
+    int out_width() const { return std::max(out_dim(), cls_labels); }      // what a row of `out` must hold, whatever the pool
     uint16_t *rb = nullptr, *c_rb = nullptr;   // the pre-LN residual stream (and its CLS-row copy): 16-bit high half
     uint8_t *rlo = nullptr, *c_rlo = nullptr;  // ... and the low-half bytes (use_lo)
     float *out = nullptr;
@@ -208,8 +217,8 @@ static int ensure_ws(Encoder* e, int B, int S) {
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_rpos, capT * 4)); KR_HIP(hipMemset(e->tok_rpos, 0, (size_t)capT * 4));
     }
-    KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_dim() * 4));
-    if (e->dense_rows > 0) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
+    KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_width() * 4));
+    if (e->dense_rows > 0 || e->cls_got) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
     KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * H * 2));
@@ -790,12 +799,46 @@ static int load_dense(Encoder* e, const float* data, int64_t numel) {
     return 0;
 }
 
+// "classifier.dense.{weight,bias}" [H, H] / [H] and "classifier.out_proj.{weight,bias}" [L, H] / [L], 1 <= L <= 64: the sequence-classification head
+// (RobertaClassificationHead's names).  L is fixed by the first of the two out_proj tensors; like "dense.weight" the head belongs to the handle from its
+// first finalize on: later the same shapes take new values, another L — or any of the four on a handle finalized without the head — is refused.
+enum { CLS_DW = 1, CLS_DB = 2, CLS_OW = 4, CLS_OB = 8, CLS_MAX_LABELS = 64 };
+static const char* const CLS_NAMES[4] = {"classifier.dense.weight", "classifier.dense.bias", "classifier.out_proj.weight", "classifier.out_proj.bias"};
+static int load_cls_head(Encoder* e, int which, const float* data, int64_t numel) {
+    const char* name = CLS_NAMES[which];
+    const unsigned bit = 1u << which;
+    const int64_t H = e->cfg.hidden;
+    int64_t L = e->cls_labels;
+    if (bit == CLS_DW || bit == CLS_DB) {
+        const int64_t want = bit == CLS_DW ? H * H : H;
+        if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)want);
+    } else {
+        L = bit == CLS_OW ? numel / H : numel;
+        if (numel <= 0 || (bit == CLS_OW && numel % H != 0) || L < 1 || L > CLS_MAX_LABELS)
+            return fail(KR_EINVAL, "'%s' has %lld elements: expected %s with 1 <= L <= %d", name, (long long)numel, bit == CLS_OW ? "[L, hidden]" : "[L]", (int)CLS_MAX_LABELS);
+        if (e->finalized_once && e->has_head() && e->cls_labels != (int)L)
+            return fail(KR_EINVAL, "'%s' with L = %d after kr_encoder_finalize: the handle's classification head is fixed (it has L = %d)", name, (int)L, e->cls_labels);
+    }
+    if (e->finalized_once && !e->has_head())
+        return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a classification head", name);
+    if (e->cls_labels && e->cls_labels != (int)L) return fail(KR_EINVAL, "'%s' with L = %d: the handle already holds an out_proj tensor with L = %d", name, (int)L, e->cls_labels);
+    float** dst = bit == CLS_DW ? &e->cls_wd : bit == CLS_DB ? &e->cls_bd : bit == CLS_OW ? &e->cls_wo : &e->cls_bo;
+    if (!*dst) KR_TRY(dmalloc(e->own_bufs, dst, (size_t)numel * 4));
+    KR_HIP(hipMemcpy(*dst, data, (size_t)numel * 4, hipMemcpyDefault));
+    if (e->cls_labels != (int)L || !e->cls_got) free_ws(e);      // e->out is sized by the widest row, `pooled` exists with the head
+    e->cls_labels = (int)L;
+    e->cls_got |= bit;
+    e->ready = false;
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(select_device(e->device));
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
     if (std::strcmp(hf_name, "dense.weight") == 0) return load_dense(e, data, numel);
+    for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, CLS_NAMES[i]) == 0) return load_cls_head(e, i, data, numel);
     int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want, fam, layer));
     // NomicBert's and ModernBert's names: q / k (rotary partners) and the gated projection's rows go into tile-pair order; T5's: wi_0 | wi_1 only
@@ -950,6 +993,15 @@ int enc_finalize(void* h) {
         return fail(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
                                   : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
     if (e->dense_rows > 0 && !t5) return fail(KR_EINVAL, "'dense.weight' without config.t5_feed_forward: the Dense head is part of T5 handles only");
+    // the classification head: on BERT / RoBERTa / MPNet-shaped handles only (the other families' heads are other functions), never next to the Dense head, whole
+    if (e->cls_got) {
+        if (rot || modern || t5)
+            return fail(KR_EINVAL, "'classifier.*' on a %s handle: the classification head Wo . tanh(Wd . x + bd) + bo is BERT's and RoBERTa's; this family's is not implemented",
+                        t5 ? "T5" : modern ? "ModernBert" : "NomicBert");
+        if (e->dense_rows > 0) return fail(KR_EINVAL, "'classifier.*' next to 'dense.weight': a handle has one head");
+        for (int i = 0; i < 4; ++i)
+            if (!(e->cls_got & (1u << i))) return fail(KR_ESTATE, "'%s' was never loaded: the classification head takes all four classifier.* tensors or none", CLS_NAMES[i]);
+    }
     if (t5) {
         for (int li = 0; li < e->cfg.layers; ++li) {
             const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
@@ -1046,6 +1098,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const int H = e->cfg.hidden, FF = e->cfg.intermediate;
     const float eps = e->cfg.ln_eps;
     e->kn.read();
+    // KR_POOL_CLASSIFY reads the CLS row like KR_POOL_CLS — the query row of a masked column 0, the packed token count, the CLS shortcut — and differs behind
+    // the last LayerNorm only (k_pool's raw rows, then k_cls_head): everything up to there sees KR_POOL_CLS
+    const bool classify = pool == KR_POOL_CLASSIFY;
+    if (classify) pool = KR_POOL_CLS;
     const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
     const bool long_seq = nqt_max > 4 && !e->kn.attn_lds;                          // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
     const int align = long_seq ? 8 : 4;                                            // sequence offsets: multiple of 8 tokens so that V^T chunks start 16-B aligned
@@ -1064,7 +1120,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const bool modern = e->modern(), t5 = e->t5(), pre = modern || t5;
     auto ln_rms_kernel = H <= 512 ? &k_ln16_pre<1, 1, true> : H <= 1024 ? &k_ln16_pre<2, 1, true> : &k_ln16_pre<4, 1, true>;    // T5 handles
     const auto ln_tail_kernel = t5 ? ln_rms_kernel : ln_pre_kernel;
-    auto pool_kernel = H <= 256 ? &k_pool<1> : H <= 512 ? &k_pool<2> : H <= 1024 ? &k_pool<4> : &k_pool<8>;
+    auto pool_kernel = classify ? (H <= 256 ? &k_pool<1, true> : H <= 512 ? &k_pool<2, true> : H <= 1024 ? &k_pool<4, true> : &k_pool<8, true>)
+                                : (H <= 256 ? &k_pool<1> : H <= 512 ? &k_pool<2> : H <= 1024 ? &k_pool<4> : &k_pool<8>);
     const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
     unsigned ln_mult = 8u;
     const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
@@ -1160,7 +1217,14 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const RowSet& r = shortcut ? cls_rows : all_rows;
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
     hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool,
-                       e->dense_rows > 0 ? e->pooled : e->out, e->d_err);
+                       e->dense_rows > 0 || classify ? e->pooled : e->out, e->d_err);
+    if (classify) {              // the classification head: out [B, L] = Wo . tanh(Wd . pooled + bd) + bo
+        const int NJ = H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8, head_lds = CH_SEQ * 2 * H * 4;
+        auto head_kernel = NJ == 1 ? &k_cls_head<1> : NJ == 2 ? &k_cls_head<2> : NJ == 4 ? &k_cls_head<4> : &k_cls_head<8>;
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(head_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));      // the widest H of the instantiation (64 KiB at 2048)
+        hipLaunchKernelGGL(head_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->cls_wd, e->cls_bd, e->cls_wo, e->cls_bo, B, H,
+                           e->cls_labels, e->out);
+    } else
     if (e->dense_rows > 0) {     // the Dense head: out [B, P] = normalize(W . pooled)
         const int P = e->dense_rows, dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
         // one kernel, an LDS size per handle: the attribute is set once per device (set_lds_once) to what the largest handle needs, H = P = 2048 (64 KiB + 16 B)
@@ -1243,7 +1307,10 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
         return fail(KR_EINVAL, "sequence length %d + padding index %d + 1 exceeds max_position_embeddings %d (fairseq position rule: at most %d tokens)", S, e->pad_idx,
                     e->cfg.max_pos, e->cfg.max_pos - e->pad_idx - 1);
     if (total_tokens > (int64_t)B * S) return fail(KR_EINVAL, "total_tokens %lld exceeds B * S = %lld", (long long)total_tokens, (long long)B * S);
-    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS) return fail(KR_EINVAL, "pool must be 0 (mean) or 1 (cls)");
+    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY) return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls) or 2 (classify)");
+    if (pool == KR_POOL_CLASSIFY && !e->has_head())
+        return fail(KR_ESTATE, "pool = 2 (classify) on a handle without a classification head: classifier.dense.{weight,bias} and classifier.out_proj.{weight,bias} "
+                               "were never loaded");
     if (B > 65535) return fail(KR_EINVAL, "at most 65535 sequences per call");
     return 0;
 }
@@ -1262,8 +1329,8 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 }
 
 // behind the kernels of a forward: the result and the error word travel to the caller
-static int finish_forward(Encoder* e, int B, int S, float* out, hipStream_t st) {
-    KR_HIP(hipMemcpyAsync(out, e->out, (size_t)B * e->out_dim() * 4, hipMemcpyDefault, st));
+static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st) {
+    KR_HIP(hipMemcpyAsync(out, e->out, (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim()) * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;
     KR_HIP(hipMemcpyAsync(e->h_err, e->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     if (is_device_pointer(out)) {
@@ -1288,7 +1355,7 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     KR_HIP(hipMemcpyAsync(e->d_mask, attention_mask, (size_t)B * S * 8, hipMemcpyDefault, st));
     if (token_type_ids) KR_HIP(hipMemcpyAsync(e->d_tt, token_type_ids, (size_t)B * S * 8, hipMemcpyDefault, st));
     KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
-    return finish_forward(e, B, S, out, st);
+    return finish_forward(e, B, S, pool, out, st);
 }
 
 // kr_encoder_forward_packed: the same forward from the ragged token list (int32 ids of the attended positions + int32 length per sequence)
@@ -1301,7 +1368,7 @@ int enc_forward_packed(void* h, const int32_t* token_ids, const int32_t* seq_len
     if (total_tokens > 0) KR_HIP(hipMemcpyAsync(e->rag_ids(), token_ids, (size_t)total_tokens * 4, hipMemcpyDefault, st));
     KR_HIP(hipMemcpyAsync(e->rag_lens(), seq_lens, (size_t)B * 4, hipMemcpyDefault, st));
     KR_TRY(enqueue_forward(e, B, S, pool, st, Input{true, false, (int)total_tokens}));
-    return finish_forward(e, B, S, out, st);
+    return finish_forward(e, B, S, pool, out, st);
 }
 
 int enc_check(void* h) {

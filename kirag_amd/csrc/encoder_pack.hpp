@@ -12,7 +12,7 @@ struct SeqTables { int *nk, *has0, *nq, *off, *cls, *T; };
 // word (bit 1: id outside the vocabulary, 4: token type outside its vocabulary, 8: bad ragged lengths), cleared by the host once it has been reported
 struct TokTables { int *id, *pos, *type, *epos, *err; };
 // align = 4, or 8 when the long-sequence attention kernel stages V^T by 16-byte LDS-DMA; P: fairseq's padding index (read only with epos)
-struct PackRules { int vocab, type_vocab, pool, align, P; };
+struct PackRules { int vocab, type_vocab, pool, align, P; };      // pool: KR_POOL_MEAN or KR_POOL_CLS (KR_POOL_CLASSIFY packs as KR_POOL_CLS: enqueue_forward passes that)
 
 // padded input: ids / mask / tt [B,S] int64 on the device, tt or nullptr (= all zero).  One launch for a small batch, three otherwise.
 void pack_padded(const int64_t* ids, const int64_t* mask, const int64_t* tt, int B, int S, const PackRules& r, const SeqTables& t, const TokTables& k, hipStream_t st);

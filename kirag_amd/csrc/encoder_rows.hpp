@@ -391,8 +391,9 @@ __global__ __launch_bounds__(256) void k_ln16_pre(const uint16_t* __restrict__ y
 // pooling + L2 normalisation: one block of 16 waves per sequence.  Masked mean: wave w sums tokens w, w + 16, ... (in that order), the 16 partial rows are added
 // in wave order — a fixed order per sequence, whatever the batch.  (Rounds 1-4 used 4 waves: the kernel is bound by the VALU work of decoding and adding
 // 262 k elements for a 256-token sequence on ONE block, 37 us — 2.7 % of a one-sequence forward; 16 waves: see profiles/r05.)
+// RAW (KR_POOL_CLASSIFY, the input of k_cls_head): the pooled row is written as it is, not divided by its norm; the norm is still formed, for the error word.
 constexpr int POOL_WAVES = 16;
-template <int NJ>     // 256-element steps that cover a row: H <= 256 NJ
+template <int NJ, bool RAW = false>     // 256-element steps that cover a row: H <= 256 NJ
 __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo, const int* __restrict__ seq_off,
                                                          const int* __restrict__ seq_nk, const int* __restrict__ seq_cls, int H, int pool, float* __restrict__ out,
                                                          int* __restrict__ err) {
@@ -471,7 +472,8 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __rest
 #pragma unroll
     for (int j = 0; j < VJ; ++j) {
         const int i = tid + j * POOL_WAVES * 64;
-        if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] / den : NAN;
+        if constexpr (RAW) { if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] : NAN; }
+        else if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] / den : NAN;
     }
 }
 
@@ -557,6 +559,86 @@ __global__ __launch_bounds__(256) void k_pool_dense(const float* __restrict__ po
         const float den = fmaxf(nrm, 1e-12f);           // NaN norm stays NaN (fmaxf would drop it)
         out[(int64_t)(b0 + s) * P + (i - s * P)] = (nrm == nrm) ? y[i] / den : NAN;
     }
+}
+
+// The sequence-classification head behind the raw CLS row (KR_POOL_CLASSIFY; RobertaClassificationHead, and BertForSequenceClassification's pooler + classifier
+// under the same names): logits[b, :] = Wo . tanh(Wd . x_b + bd) + bo, x = k_pool<NJ, true>'s [B, H] rows, Wd [H, H], Wo [L, H], fp32 throughout.
+// One block of CH_WAVES waves per CH_SEQ sequences, their rows in LDS.  Stage 1: a wave takes CH_ROWS rows of Wd at a time and computes those features of
+// all CH_SEQ sequences from ONE read of the rows — a lane owns 4 consecutive columns per 256-column step and adds its products with fp32 FMAs in column
+// order, the 64 lane sums are folded by a shuffle butterfly in a fixed order — and stores t = tanhf(sum + bd) to LDS.  Stage 2: the same over Wo and t, + bo,
+// to out [B, L].  Every slot of the group runs the same instructions on its own row and a feature is summed by one wave whatever its row's place in the
+// wave's batch, so a sequence's logits depend neither on its slot nor on the batch around it.
+// The weights stay fp32 (4 MiB at H = 1024, re-read from L2 by every group): 2 H^2 flops per sequence are not a GEMM worth the MFMA units at a few hundred
+// sequences, and fp32 keeps the head inside an a-priori bound of (H + 2) 2^-24 per sum (tests/test_gpu_reranker.py).  What bounds the kernel is the latency of
+// the weight rows — one block streams all of Wd — hence 16 waves with CH_ROWS x NJ row loads each in flight before the first FMA (4 waves with one row each:
+// 0.6 ms at any batch size; profiles/reranker/measurements.txt).
+constexpr int CH_SEQ = 4, CH_WAVES = 16;
+template <int NJ>     // 256-column steps that cover a row: H <= 256 NJ
+__global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restrict__ pooled, const float* __restrict__ Wd, const float* __restrict__ bd,
+                                                           const float* __restrict__ Wo, const float* __restrict__ bo, int B, int H, int L,
+                                                           float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* x = reinterpret_cast<float*>(smem);          // [CH_SEQ][H]
+    float* t = x + CH_SEQ * H;                          // [CH_SEQ][H]
+    constexpr int CH_ROWS = NJ <= 2 ? 4 : 2;            // weight rows per wave and step: CH_ROWS * NJ float4 per lane (16 waves per block: 128 registers per lane)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * CH_SEQ;
+    for (int i = tid; i < CH_SEQ * H; i += CH_WAVES * 64) {
+        const int s = i / H;
+        x[i] = b0 + s < B ? pooled[(int64_t)(b0 + s) * H + (i - s * H)] : 0.f;
+    }
+    __syncthreads();
+    // y[f][s] = W[f, :] . v[s, :] for every row f < rows of W and the CH_SEQ rows of v (LDS); lane 0 of the wave that owns f hands the sums to `store`
+    auto rows_dot = [&](const float* __restrict__ W, int rows, const float* v, auto&& store) {
+        for (int f0 = wave * CH_ROWS; f0 < rows; f0 += CH_WAVES * CH_ROWS) {
+            float4 w[CH_ROWS][NJ];
+#pragma unroll
+            for (int r = 0; r < CH_ROWS; ++r)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const int i = lane * 4 + j * 256;
+                    w[r][j] = (i < H && f0 + r < rows) ? *reinterpret_cast<const float4*>(W + (int64_t)(f0 + r) * H + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            float acc[CH_ROWS][CH_SEQ];
+#pragma unroll
+            for (int r = 0; r < CH_ROWS; ++r)
+#pragma unroll
+                for (int s = 0; s < CH_SEQ; ++s) acc[r][s] = 0.f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int i = lane * 4 + j * 256;
+                if (i < H) {
+#pragma unroll
+                    for (int s = 0; s < CH_SEQ; ++s) {
+                        const float4 a = *reinterpret_cast<const float4*>(v + s * H + i);
+#pragma unroll
+                        for (int r = 0; r < CH_ROWS; ++r)
+                            acc[r][s] = fmaf(w[r][j].w, a.w, fmaf(w[r][j].z, a.z, fmaf(w[r][j].y, a.y, fmaf(w[r][j].x, a.x, acc[r][s]))));
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < CH_ROWS; ++r) {
+#pragma unroll
+                for (int s = 0; s < CH_SEQ; ++s)
+#pragma unroll
+                    for (int m = 32; m >= 1; m >>= 1) acc[r][s] += __shfl_xor(acc[r][s], m, 64);
+                if (lane == 0 && f0 + r < rows) store(f0 + r, acc[r]);
+            }
+        }
+    };
+    rows_dot(Wd, H, x, [&](int f, const float (&y)[CH_SEQ]) {
+        const float b = bd[f];
+#pragma unroll
+        for (int s = 0; s < CH_SEQ; ++s) t[s * H + f] = tanhf(y[s] + b);
+    });
+    __syncthreads();
+    rows_dot(Wo, L, t, [&](int l, const float (&y)[CH_SEQ]) {
+        const float b = bo[l];
+#pragma unroll
+        for (int s = 0; s < CH_SEQ; ++s)
+            if (b0 + s < B) out[(int64_t)(b0 + s) * L + l] = y[s] + b;
+    });
 }
 
 // CLS shortcut: row seq_off[b] + seq_cls[b] of ctx / the residual stream (hi, lo) -> row b of the compact buffers; also the compact "sequence" tables

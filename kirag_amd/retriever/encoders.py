@@ -61,6 +61,8 @@ from transformers import BertModel, ModernBertModel, MPNetModel, NomicBertModel,
 from .. import _lib
 
 POOL_MEAN, POOL_CLS = 0, 1
+POOL_CLASSIFY = 2        # KR_POOL_CLASSIFY: the CLS row -> the classification head -> raw logits [B, num_labels] (kirag_amd.retriever.rerankers)
+CLASSIFIER_OUT = "classifier.out_proj.weight"    # [num_labels, hidden]: its rows are the width of a classify forward
 # model_type values whose position ids follow fairseq's rule on BERT's post-LN layer stack ("xlm-roberta-xl" is pre-LN: not one of them)
 ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
 MPNET_TYPE = "mpnet"
@@ -109,10 +111,14 @@ def pad_modernbert_ff(name: str, w, ff: int, ff_pad: int):
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
 
-    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None):
+    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None):
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
-        low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it)."""
+        low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it).
+        ``rename``: optional callable, parameter name of the module -> the name the library knows (``sync`` / ``load_state`` apply it to every name; a
+        task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``)."""
         lib = _lib.load()
+        self.rename = rename
+        self.num_labels = 0               # rows of "classifier.out_proj.weight" once the library has accepted it: the width of a POOL_CLASSIFY forward
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
         self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
         self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
@@ -282,6 +288,8 @@ class HipBertForward:
             if tuple(p._version for _, p in cached) == self._versions and all(p.data_ptr() == q for (_, p), q in zip(cached[k::8], self._ptrs[k::8])):
                 return
         params = [(n, p) for n, p in module.named_parameters() if not n.startswith("pooler.")]
+        if self.rename is not None:
+            params = [(self.rename(n), p) for n, p in params]
         fp = tuple((p.data_ptr(), p._version) for _, p in params)
         self._plist, self._versions, self._ptrs, self._since_full = params, tuple(v for _, v in fp), tuple(q for q, _ in fp), 0
         if fp == self.fingerprint:
@@ -297,9 +305,16 @@ class HipBertForward:
         self.fingerprint = fp
 
     def _note_dense(self, name: str, numel: int) -> None:
-        """``dense.weight`` [P, hidden] was accepted by the library: the forwards now write [B, P]"""
+        """``dense.weight`` [P, hidden] was accepted by the library: the forwards now write [B, P]; ``classifier.out_proj.weight`` [L, hidden]: a
+        ``POOL_CLASSIFY`` forward writes [B, L]"""
         if name == "dense.weight":
             self.out_dim = int(numel) // self.hidden
+        elif name == CLASSIFIER_OUT:
+            self.num_labels = int(numel) // self.hidden
+
+    def _width(self, pool: int) -> int:
+        """columns of a forward's output: the logits of ``POOL_CLASSIFY``, else the embedding"""
+        return self.num_labels if pool == POOL_CLASSIFY else self.out_dim
 
     def _load_zero_token_types(self) -> None:
         if self.is_mpnet or self.is_modern:
@@ -310,6 +325,8 @@ class HipBertForward:
         """Load weights from a mapping HF-state-dict-name -> numpy array / tensor (host or device)."""
         import numpy as np
         for name, w in state.items():
+            if self.rename is not None:
+                name = self.rename(name)
             w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
             if isinstance(w, np.ndarray):
                 w = np.ascontiguousarray(w, dtype=np.float32)
@@ -329,7 +346,7 @@ class HipBertForward:
         import numpy as np
         ids = np.ascontiguousarray(input_ids, dtype=np.int64); mask = np.ascontiguousarray(attention_mask, dtype=np.int64)
         B, S = ids.shape
-        out = np.empty((B, self.out_dim), np.float32)
+        out = np.empty((B, self._width(pool)), np.float32)
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.ctypes.data, mask.ctypes.data, B, S, pool, out.ctypes.data, None))
         else:
@@ -346,7 +363,7 @@ class HipBertForward:
         ids = input_ids.to(torch.int64).contiguous()
         mask = attention_mask.to(device=ids.device, dtype=torch.int64).contiguous()
         B, S = ids.shape
-        out = torch.empty((B, self.out_dim), dtype=torch.float32, device=ids.device)
+        out = torch.empty((B, self._width(pool)), dtype=torch.float32, device=ids.device)
         stream = _lib.current_stream_ptr() if ids.is_cuda else None
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.data_ptr(), mask.data_ptr(), B, S, pool, out.data_ptr(), stream))
@@ -381,7 +398,7 @@ class HipBertForward:
         buf[:n].view(B, S).copy_(input_ids)
         buf[n:2 * n].view(B, S).copy_(attention_mask)
         dev = torch.device("cuda", self.device_index)
-        out = torch.empty((B, self.out_dim), dtype=torch.float32, device=dev)
+        out = torch.empty((B, self._width(pool)), dtype=torch.float32, device=dev)
         with torch.cuda.device(self.device_index):
             _lib.check(self._lib.kr_encoder_forward(self._h, buf.data_ptr(), buf.data_ptr() + 8 * n, B, S, pool, out.data_ptr(), _lib.current_stream_ptr()))
             ev = torch.cuda.Event(); ev.record()
@@ -401,7 +418,7 @@ class HipBertForward:
             raise ValueError(f"total_tokens {T} exceeds the {token_ids.numel()} entries of token_ids")
         dev = torch.device("cuda", self.device_index)
         if out is None:
-            out = torch.empty((B, self.out_dim), dtype=torch.float32, device=dev)
+            out = torch.empty((B, self._width(pool)), dtype=torch.float32, device=dev)
         with torch.cuda.device(self.device_index):
             _lib.check(self._lib.kr_encoder_forward_packed(self._h, token_ids.data_ptr(), seq_lens.data_ptr(), B, int(S), T, pool, out.data_ptr(),
                                                            _lib.current_stream_ptr()))
@@ -418,17 +435,13 @@ class HipBertForward:
         return out
 
 
-class _HipSentenceMixin:
-    """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel``, ``XLMRobertaModel`` or ``MPNetModel``, the next class in the MRO): the HIP
-    eval forward, weight sync, ``forward_packed``, the train / eval switch and the pooled autograd forward of ``train()`` mode."""
+class _HipModuleMixin:
+    """What every HF model class whose eval forward runs in the library shares (the sentence encoders below, the cross-encoder rerankers of
+    ``kirag_amd.retriever.rerankers``): the handle kept in sync with the parameters, the HIP forward on ``_pool``, and the invalidation of the weight copy on
+    ``train()`` / ``eval()`` transitions, ``load_state_dict`` and ``_apply``."""
     _pool = POOL_MEAN
-    _hf_base = None
+    _hip_rename = None               # HipBertForward's ``rename``: None = the parameter names are the library's
     accepts_host_inputs = True       # eval forward takes the collator's CPU tensors and uploads them itself (DenseRetriever skips its to_device)
-
-    def __init__(self, config, add_pooling_layer=True, **kwargs):
-        super().__init__(config, add_pooling_layer)
-        self.kwargs = kwargs
-        self._hip: Optional[HipBertForward] = None
 
     def _synced_hip(self) -> HipBertForward:
         """The ``HipBertForward`` of the device the parameters are on, holding their current values."""
@@ -439,7 +452,7 @@ class _HipSentenceMixin:
                 "Move the model to a GPU (kirag_amd has no CPU fallback).")
         idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
         if self._hip is None or self._hip.device_index != idx:
-            self._hip = HipBertForward(self.config, idx)
+            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename)
         self._hip.sync(self)
         return self._hip
 
@@ -453,14 +466,6 @@ class _HipSentenceMixin:
         with torch.cuda.device(hip.device_index):
             # CPU inputs (the collator's tensors as they are) are uploaded by the library from pinned staging; token types go to the kernels (kr_encoder_forward_tt)
             return hip.forward(input_ids, attention_mask, self._pool, token_type_ids)
-
-    def forward_packed(self, token_ids: Tensor, seq_lens: Tensor, max_len: int, total_tokens: Optional[int] = None) -> Tensor:
-        """Sentence embeddings [B, hidden] from the ragged token list of a right-padded batch (int32 attended ids back to back + int32 lengths; see
-        ``HipBertForward.forward_packed``) — what the tokenizer processes of ``compute_corpus_embeddings`` ship instead of padded int64 ``input_ids`` +
-        ``attention_mask``.  Bit-identical to ``forward(input_ids, attention_mask)`` on the padded batch; eval mode only (the HIP path)."""
-        if self.training:
-            raise RuntimeError("forward_packed is the inference (HIP) path: call model.eval() first")
-        return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def invalidate_hip_weights(self) -> None:
         if self._hip is not None:
@@ -484,6 +489,25 @@ class _HipSentenceMixin:
         if getattr(self, "_hip", None) is not None:
             self._hip.invalidate()
         return out
+
+
+class _HipSentenceMixin(_HipModuleMixin):
+    """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel``, ``XLMRobertaModel`` or ``MPNetModel``, the next class in the MRO): the HIP
+    eval forward, weight sync, ``forward_packed``, the train / eval switch and the pooled autograd forward of ``train()`` mode."""
+    _hf_base = None
+
+    def __init__(self, config, add_pooling_layer=True, **kwargs):
+        super().__init__(config, add_pooling_layer)
+        self.kwargs = kwargs
+        self._hip: Optional[HipBertForward] = None
+
+    def forward_packed(self, token_ids: Tensor, seq_lens: Tensor, max_len: int, total_tokens: Optional[int] = None) -> Tensor:
+        """Sentence embeddings [B, hidden] from the ragged token list of a right-padded batch (int32 attended ids back to back + int32 lengths; see
+        ``HipBertForward.forward_packed``) — what the tokenizer processes of ``compute_corpus_embeddings`` ship instead of padded int64 ``input_ids`` +
+        ``attention_mask``.  Bit-identical to ``forward(input_ids, attention_mask)`` on the padded batch; eval mode only (the HIP path)."""
+        if self.training:
+            raise RuntimeError("forward_packed is the inference (HIP) path: call model.eval() first")
+        return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
         kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT and T5 have no token types

@@ -27,6 +27,10 @@ BERT-family checkpoints show).  This tool replaces that assertion by a measureme
     encoder (GPU present) or, with --emulate or without a GPU, the torch emulation of its rounding points (tools/precision_emulation.py);
  3. a recommendation: the cheapest mode whose error stays below HALF the 1e-3 tolerance, else the default.
 
+A sequence-classification checkpoint (config.json names an ...ForSequenceClassification architecture: BAAI/bge-reranker-*, cross-encoder/ms-marco-MiniLM-*)
+is loaded as its reranker twin (kirag_amd.retriever.rerankers) instead, GPU only, and the report is the worst |logit - HF fp32 logit| over the built-in
+(question, passage) pairs — every question against every passage — for the four precision modes; the f16 range risk is the encoder's, as above.
+
 Texts: --texts (one per line; the first half are used as queries, the rest as passages, E5 prefixes added) needs the checkpoint's tokenizer; without a
 tokenizer in the directory (or with --random-tokens) seeded random token ids of ragged lengths are used."""
 import argparse
@@ -181,9 +185,78 @@ def run_mode_emulated(model, batches, pool, dtype, lo, dev):
     return outs
 
 
+BASE_QUESTIONS = ["who discovered penicillin", "capital of the country that hosted the 1992 olympics", "when was the eiffel tower completed",
+                  "what is the boiling point of water at altitude"]
+BASE_PASSAGES = ["Alexander Fleming discovered penicillin in 1928 at St Mary's Hospital in London.",
+                 "Barcelona hosted the 1992 Summer Olympics; the capital of Spain is Madrid.", "The Eiffel Tower was completed in March 1889 for the World's Fair.",
+                 "Water boils at lower temperatures at higher altitudes because the air pressure is lower."]
+
+
+def reranker_inputs(args, hf_dir, cfg):
+    """{"input_ids", "attention_mask"[, "token_type_ids"]} int64 tensors of the pairs: the checkpoint's tokenizer on every built-in question x passage, or
+    (no tokenizer / --random-tokens) seeded random pairs in the family's template"""
+    from kirag_amd.collators import RerankerCollator
+    tok = None
+    if not args.random_tokens and os.path.isdir(hf_dir):
+        try:
+            from transformers import AutoTokenizer
+            tok = AutoTokenizer.from_pretrained(hf_dir)
+        except Exception as e:      # noqa: BLE001 — a directory without tokenizer files
+            print(f"# no tokenizer in {hf_dir} ({type(e).__name__}): seeded random token pairs instead", file=sys.stderr)
+    if tok is not None:
+        qs = [q for q in BASE_QUESTIONS for _ in BASE_PASSAGES]
+        return RerankerCollator(tok, maxlength=args.max_length).encode_pairs(qs, BASE_PASSAGES * len(BASE_QUESTIONS))
+    rng = np.random.default_rng(args.seed)
+    roberta = cfg.model_type != "bert"
+    S, lo = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000)
+    pad = cfg.pad_token_id if roberta else 0
+    ids = np.full((args.n, S), pad, np.int64); mask = np.zeros((args.n, S), np.int64); tt = np.zeros((args.n, S), np.int64)
+    for r in range(args.n):
+        n = int(np.clip(rng.normal(0.8 * S, 0.2 * S), 8, S))
+        nq = int(rng.integers(1, max(2, min(16, n - 6))))
+        q, p = rng.integers(lo, cfg.vocab_size, nq), rng.integers(lo, cfg.vocab_size, n - nq - (4 if roberta else 3))
+        row = [0, *q, 2, 2, *p, 2] if roberta else [101 if cfg.vocab_size > 2000 else 2, *q, 102 if cfg.vocab_size > 2000 else 3, *p, 102 if cfg.vocab_size > 2000 else 3]
+        ids[r, :n] = row; mask[r, :n] = 1; tt[r, nq + 2:n] = 0 if roberta else 1
+    out = {"input_ids": torch.from_numpy(ids), "attention_mask": torch.from_numpy(mask)}
+    if not roberta:
+        out["token_type_ids"] = torch.from_numpy(tt)
+    return out
+
+
+def check_reranker(hf_dir, args):
+    """worst |logit - HF fp32 logit| of a sequence-classification checkpoint, per precision mode"""
+    from kirag_amd.retriever.encoders import POOL_CLASSIFY, HipBertForward
+    from kirag_amd.retriever.rerankers import BGEReranker
+    if not torch.cuda.is_available() or args.emulate:
+        raise SystemExit(f"{hf_dir}: a sequence-classification checkpoint is checked on the GPU (the torch emulation has no classification head)")
+    model = BGEReranker.from_pretrained(hf_dir).float().eval().to("cuda:0")
+    a = {k: v.to("cuda:0") for k, v in reranker_inputs(args, hf_dir, model.config).items()}
+    with torch.no_grad():
+        ref = model._hf_base.forward(model, **a).logits.double().cpu().numpy()
+    print(f"# {hf_dir}: {type(model).__name__}, {model.config.num_hidden_layers} layers, hidden {model.config.hidden_size}, {model.config.num_labels} label(s); "
+          f"{len(ref)} pairs of up to {a['input_ids'].shape[1]} tokens; HF fp32 logits {ref.min():.3f} .. {ref.max():.3f}")
+    results = []
+    for dtype, lo in MODES:
+        h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename)
+        h.sync(model)
+        tt = a.get("token_type_ids") if model.config.type_vocab_size > 1 else None
+        out = h.forward(a["input_ids"], a["attention_mask"], POOL_CLASSIFY, tt).double().cpu().numpy()
+        finite = bool(np.isfinite(out).all())
+        err = float(np.abs(out - ref).max()) if finite else float("inf")
+        results.append({"operand_dtype": dtype, "residual_lo": lo, "worst_logit_error": err, "finite": finite})
+        print(f"  {dtype:4s} {'+ low half' if lo else '          '}  worst |logit - HF fp32| = {err:.2e}" + ("" if finite else "   NON-FINITE OUTPUT"))
+    out = {"checkpoint": hf_dir, "tested_path": "hip", "kind": "sequence-classification", "pairs": len(ref), "modes": results}
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
+    if any(a.endswith("ForSequenceClassification") for a in (getattr(cfg, "architectures", None) or [])):
+        return check_reranker(hf_dir, args)
     from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
     if getattr(cfg, "model_type", "bert") == T5_TYPE:
         # the encoder half alone, as the twin of the pooling asked for: its from_pretrained also reads the folder's Dense head (modules.json)
