@@ -233,6 +233,12 @@ typedef struct {
 #define KR_POOL_MEAN 0 /* E5: average_pool (encoders.py:56-58) then F.normalize */
 #define KR_POOL_CLS 1  /* BGE: last_hidden[:,0] (encoders.py:116) then F.normalize */
 #define KR_POOL_CLASSIFY 2 /* cross-encoder rerankers: last_hidden[:,0] -> the classification head -> raw logits [B, L] (needs "classifier.*", below) */
+/* bge-m3's token-level heads: flag bits ORed onto a base pool of KR_POOL_MEAN or KR_POOL_CLS (kr_encoder_forward / kr_encoder_forward_tt only).  `out` then
+ * holds, back to back and all fp32: the dense block [B, hidden] (the bits of the unflagged call with the same base pool), with KR_POOL_WITH_SPARSE the sparse
+ * block [B, S], with KR_POOL_WITH_COLBERT the colbert block [B, S, P] ("sparse_linear.*" / "colbert_linear.*" under kr_encoder_load_weight below).  Any other
+ * bit, the flags on KR_POOL_CLASSIFY or in kr_encoder_forward_packed: KR_EINVAL; a flag whose head was never loaded: KR_ESTATE. */
+#define KR_POOL_WITH_SPARSE 0x10
+#define KR_POOL_WITH_COLBERT 0x20
 
 /* 16-bit type of the MFMA operands and of every stored activation (weights, residual stream, q / k / v, P, ctx, h); accumulation is fp32 and the
  * LayerNorms run in fp32 either way.  f16 has 11 significand bits (|x| <= 65504), bf16 8: with outlier hidden channels (what real BERT-family
@@ -349,13 +355,32 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   fixed at the first finalize — later the same L takes new values, another L, or any of the four on a handle finalized without them, is KR_EINVAL.
  *   kr_encoder_finalize refuses it (KR_EINVAL, naming it) on NomicBert, ModernBert and T5 handles — their classification heads are other functions — and next
  *   to "dense.weight".  BertForSequenceClassification's spelling of the same arithmetic (pooler.dense.* -> tanh -> classifier.{weight,bias}) is mapped onto
- *   these names by the Python layer (kirag_amd.retriever.rerankers.BertReranker); the library itself keeps ignoring "pooler.*". */
+ *   these names by the Python layer (kirag_amd.retriever.rerankers.BertReranker); the library itself keeps ignoring "pooler.*".
+ * BAAI/bge-m3's sparse and multi-vector heads (an XLM-R backbone; the same two Linear modules on a BERT backbone are accepted too), fp32:
+ *   "colbert_linear.weight" [P, hidden], "colbert_linear.bias" [P]: P % 128 == 0 and 128 <= P <= 2048, any other count is KR_EINVAL;
+ *   "sparse_linear.weight" [1, hidden], "sparse_linear.bias" [1].
+ *   The two heads are independent; each is weight + bias or nothing (a partial pair fails kr_encoder_finalize as "never loaded").  They follow the rule of
+ *   "classifier.*" and "dense.weight": a head is fixed at the first finalize — later the same P takes new values, another P, or a head arriving on a handle
+ *   that was finalized without it, is KR_EINVAL.  kr_encoder_finalize refuses them (KR_EINVAL, naming the tensor) on MPNet, NomicBert, ModernBert and T5
+ *   handles, next to "classifier.*" and next to "dense.weight".  With x[b, s] = the row of last_hidden_state,
+ *       KR_POOL_WITH_SPARSE:   w[b, s] = max(0, sparse_linear.weight . x[b, s] + bias)                    out block [B, S]
+ *       KR_POOL_WITH_COLBERT:  v[b, s] = normalize(colbert_linear.weight . x[b, s] + bias)                out block [B, S, P]   (F.normalize, 1e-12 floor)
+ *   for an attended column and +0.0 for a masked one.  Columns are those of the padded [B, S] input (left padding and masks with holes place rows where
+ *   their columns are); column 0 (<s> / [CLS]) is written like any attended column — dropping it is the caller's business —, and the extra query row
+ *   that CLS pooling packs for a MASKED column 0 is never emitted.  A flagged forward runs its last layer on every row (the CLS-rows-only shortcut is off);
+ *   its dense block still equals the unflagged call bit for bit.  The colbert product runs on the MFMA projection loops from the 16-bit rows the stack itself
+ *   reads (a 16-bit copy of the weight, fp32 accumulation) and is STORED IN THE HANDLE'S 16-BIT OPERAND TYPE, like every projection output of the stack (f16: 11
+ *   significand bits, bf16: 8), before bias, norm and division run in fp32: the head is not fp32 end to end, and on a bf16 handle a vector's elements carry that
+ *   rounding (measured figures for both types: profiles/m3/measurements.txt).  The sparse dot product reads the final rows with their low
+ *   half, in fp32 with a fixed order.  A token's weight and vector do not depend on the batch around it.  A non-finite weight or vector of an attended
+ *   token is reported as KR_ERANGE like a non-finite embedding.  A device `out` receives the token-level blocks straight from the kernels; a host `out` is
+ *   staged on the device.  kr_encoder_forward_packed refuses the flags: the corpus pipeline behind it stores no token vectors, so the refusal costs nothing. */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);
 /* forward(input_ids, attention_mask) (encoders.py:67-77 / :106-118); token_type_ids are 0 as in every caller.
  *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised ([B,P] on a handle that was given "dense.weight" [P, hidden];
- *   [B,L] raw logits with pool = KR_POOL_CLASSIFY).
+ *   [B,L] raw logits with pool = KR_POOL_CLASSIFY; with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT the blocks [B,hidden] | [B,S] | [B,S,P], see above).
  *   A sequence whose mask is all zero yields NaN (mean pool) exactly like the reference. */
 int kr_encoder_forward(kr_encoder* enc, const int64_t* input_ids, const int64_t* attention_mask, int B, int S,
                        int pool, float* out, void* stream);

@@ -33,6 +33,10 @@
 // Sequence classification (cross-encoder rerankers, KR_POOL_CLASSIFY): BERT / RoBERTa handles with the four "classifier.*" tensors run CLS pooling's forward up
 // to the last LayerNorm, then k_pool<.., RAW> (the un-normalised CLS row) and k_cls_head: out [B, L] = Wo . tanh(Wd . x + bd) + bo, raw logits.
 //
+// bge-m3's token-level heads (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT on BERT / RoBERTa handles with "sparse_linear.*" / "colbert_linear.*"): a flagged forward
+// runs its last layer on every row; behind the pooling k_m3_slots maps the [B, S] columns to packed rows, k_m3_sparse writes max(0, w . x + b) per column, and
+// the colbert vectors are one more EPI_DENSE projection of the packed rows followed by k_m3_rows (bias, norm, scatter to [b, s], zeros for masked columns).
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -141,6 +145,16 @@ struct Encoder {
     int cls_labels = 0; unsigned cls_got = 0;
     bool has_head() const { return cls_got == 15u; }
     int out_width() const { return std::max(out_dim(), cls_labels); }      // what a row of `out` must hold, whatever the pool
+    // bge-m3's heads.  "colbert_linear.{weight,bias}": col_w = the 16-bit copy [P, H] the projection loops read, col_b fp32 [P], col_rows = P (0: none yet).
+    // "sparse_linear.{weight,bias}": sp_w fp32 [H], sp_b fp32 [1].  *_got: bit 1 = weight, bit 2 = bias; a head is both or nothing at finalize.
+    // cy: the colbert product of the packed rows [capT, P] (16-bit, EPI_DENSE); slot_row: packed row of every [b, s] column or -1 (k_m3_slots);
+    // tok_stage: the token-level blocks of a forward whose `out` is host memory (grown on demand, freed with the handle)
+    uint16_t* col_w = nullptr; float* col_b = nullptr; int col_rows = 0; unsigned col_got = 0;
+    float *sp_w = nullptr, *sp_b = nullptr; unsigned sp_got = 0;
+    bool has_colbert() const { return col_got == 3u; }
+    bool has_sparse() const { return sp_got == 3u; }
+    uint16_t* cy = nullptr; int* slot_row = nullptr;
+    float* tok_stage = nullptr; size_t tok_stage_elems = 0;
     uint16_t *rb = nullptr, *c_rb = nullptr;   // the pre-LN residual stream (and its CLS-row copy): 16-bit high half
     uint8_t *rlo = nullptr, *c_rlo = nullptr;  // ... and the low-half bytes (use_lo)
     float *out = nullptr;
@@ -219,6 +233,8 @@ static int ensure_ws(Encoder* e, int B, int S) {
     }
     KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_width() * 4));
     if (e->dense_rows > 0 || e->cls_got) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
+    if (e->col_got || e->sp_got) KR_TRY(dmalloc(e->ws_bufs, &e->slot_row, capBS * 4));
+    if (e->col_rows > 0) KR_TRY(dmalloc(e->ws_bufs, &e->cy, capT * e->col_rows * 2));      // capT rows: the projection's tiles are whole (see k_proj)
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
     KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * H * 2));
@@ -610,6 +626,7 @@ void enc_destroy(void* h) {
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     if (e->gstream) (void)hipStreamDestroy(e->gstream);
     if (e->stage) (void)hipFree(e->stage);
+    if (e->tok_stage) (void)hipFree(e->tok_stage);
     free_bufs(e->own_bufs);
     delete e;
 }
@@ -832,6 +849,58 @@ static int load_cls_head(Encoder* e, int which, const float* data, int64_t numel
     return 0;
 }
 
+// "colbert_linear.{weight,bias}" [P, H] / [P] (P % 128 == 0, 128 <= P <= 2048) and "sparse_linear.{weight,bias}" [1, H] / [1]: bge-m3's token-level heads.
+// Two independent heads under the rule of "classifier.*": a head belongs to the handle from its first finalize on — later the same P takes new values,
+// another P, or a head on a handle finalized without it, is refused.
+static const char* const M3_NAMES[4] = {"colbert_linear.weight", "colbert_linear.bias", "sparse_linear.weight", "sparse_linear.bias"};
+constexpr int M3_FLAGS = KR_POOL_WITH_SPARSE | KR_POOL_WITH_COLBERT;
+static int load_m3_head(Encoder* e, int which, const float* data, int64_t numel) {
+    const char* name = M3_NAMES[which];
+    const bool colbert = which < 2, weight = (which & 1) == 0;
+    const unsigned bit = weight ? 1u : 2u;
+    const int64_t H = e->cfg.hidden;
+    if (!colbert) {
+        const int64_t want = weight ? H : 1;
+        if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)want);
+        if (e->finalized_once && !e->has_sparse()) return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a sparse head", name);
+        float** dst = weight ? &e->sp_w : &e->sp_b;
+        if (!*dst) KR_TRY(dmalloc(e->own_bufs, dst, (size_t)numel * 4));
+        KR_HIP(hipMemcpy(*dst, data, (size_t)numel * 4, hipMemcpyDefault));
+        if (!e->sp_got) free_ws(e);           // slot_row exists with a head
+        e->sp_got |= bit;
+        e->ready = false;
+        return 0;
+    }
+    const int64_t P = weight ? numel / H : numel;
+    if (numel <= 0 || (weight && numel % H != 0) || P < 128 || P > 2048 || P % 128 != 0)
+        return fail(KR_EINVAL, "'%s' has %lld elements: expected %s with P %% 128 == 0 and 128 <= P <= 2048", name, (long long)numel, weight ? "[P, hidden]" : "[P]");
+    if (e->finalized_once && !e->has_colbert()) return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a colbert head", name);
+    if (e->finalized_once && e->col_rows != (int)P)
+        return fail(KR_EINVAL, "'%s' with P = %d after kr_encoder_finalize: the handle's colbert head is fixed (it has P = %d)", name, (int)P, e->col_rows);
+    if (e->col_rows && e->col_rows != (int)P) return fail(KR_EINVAL, "'%s' with P = %d: the handle already holds a colbert_linear tensor with P = %d", name, (int)P, e->col_rows);
+    if (weight) {
+        if (!e->col_w) KR_TRY(dmalloc(e->own_bufs, &e->col_w, (size_t)numel * 2));
+        float* tmp = nullptr;
+        KR_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)numel * 4));
+        hipError_t rc = hipMemcpy(tmp, data, (size_t)numel * 4, hipMemcpyDefault);
+        if (rc == hipSuccess) {
+            hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, tmp, e->col_w, numel, 1.f);
+            rc = hipGetLastError();
+            if (rc == hipSuccess) rc = hipDeviceSynchronize();
+        }
+        (void)hipFree(tmp);
+        KR_HIP(rc);
+    } else {
+        if (!e->col_b) KR_TRY(dmalloc(e->own_bufs, &e->col_b, (size_t)numel * 4));
+        KR_HIP(hipMemcpy(e->col_b, data, (size_t)numel * 4, hipMemcpyDefault));
+    }
+    if (!e->col_got) free_ws(e);              // cy is sized by P, slot_row exists with a head
+    e->col_rows = (int)P;
+    e->col_got |= bit;
+    e->ready = false;
+    return 0;
+}
+
 int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t numel) {
     if (!h || !hf_name || !data) return fail(KR_EINVAL, "NULL argument");
     Encoder* e = reinterpret_cast<Encoder*>(h);
@@ -839,6 +908,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
     if (std::strcmp(hf_name, "dense.weight") == 0) return load_dense(e, data, numel);
     for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, CLS_NAMES[i]) == 0) return load_cls_head(e, i, data, numel);
+    for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, M3_NAMES[i]) == 0) return load_m3_head(e, i, data, numel);
     int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want, fam, layer));
     // NomicBert's and ModernBert's names: q / k (rotary partners) and the gated projection's rows go into tile-pair order; T5's: wi_0 | wi_1 only
@@ -992,6 +1062,21 @@ int enc_finalize(void* h) {
     if (!e->rel_w.empty() && fam_t5(e->rel_fam) != t5)
         return fail(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
                                   : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
+    // bge-m3's heads: on BERT / RoBERTa handles only, never next to another head, each one whole (checked before the Dense head's own rule, so
+    // that 'dense.weight' + a token-level head on a BERT handle is refused by both names)
+    for (int hd = 0; hd < 2; ++hd) {
+        const unsigned got = hd == 0 ? e->col_got : e->sp_got;
+        if (!got) continue;
+        const char* first = M3_NAMES[2 * hd + ((got & 1u) ? 0 : 1)];
+        const bool mpnet = !e->rel_w.empty() && !t5;
+        if (rot || modern || t5 || mpnet)
+            return fail(KR_EINVAL, "'%s' on a %s handle: bge-m3's token-level heads are accepted on BERT and RoBERTa / XLM-R handles", first,
+                        t5 ? "T5" : modern ? "ModernBert" : rot ? "NomicBert" : "MPNet");
+        if (e->cls_got) return fail(KR_EINVAL, "'%s' next to 'classifier.*': a handle has the classification head or the token-level heads", first);
+        if (e->dense_rows > 0) return fail(KR_EINVAL, "'%s' next to 'dense.weight': a handle has the Dense head or the token-level heads", first);
+        for (int i = 0; i < 2; ++i)
+            if (!(got & (1u << i))) return fail(KR_ESTATE, "'%s' was never loaded: a token-level head takes its weight and its bias or neither", M3_NAMES[2 * hd + i]);
+    }
     if (e->dense_rows > 0 && !t5) return fail(KR_EINVAL, "'dense.weight' without config.t5_feed_forward: the Dense head is part of T5 handles only");
     // the classification head: on BERT / RoBERTa / MPNet-shaped handles only (the other families' heads are other functions), never next to the Dense head, whole
     if (e->cls_got) {
@@ -1094,7 +1179,8 @@ struct RowSet {
 };
 
 // every kernel of one forward, enqueued on `st` (input already in the workspace, result left in e->out)
-static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, const Input& in) {
+// flags: KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT (pool is the base pool); tok_out: device memory for the token-level blocks, [B, S] then [B, S, P]
+static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, const Input& in, int flags = 0, float* tok_out = nullptr) {
     const int H = e->cfg.hidden, FF = e->cfg.intermediate;
     const float eps = e->cfg.ln_eps;
     e->kn.read();
@@ -1135,7 +1221,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
                            rot ? e->pos_zero : e->pos, e->type, e->elng, e->elnb, eps, H,
                            e->use_lo ? e->xlo : nullptr, e->xb);
     }
-    const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr;
+    const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr && !flags;      // the token-level heads read every row of the last layer
     e->last_shortcut = shortcut;
     const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid,
                           e->rb, e->use_lo ? e->rlo : nullptr};
@@ -1231,6 +1317,22 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         KR_TRY(set_lds_once(reinterpret_cast<const void*>(&k_pool_dense), PD_SEQ * (2048 + 2048) * 4 + PD_SEQ * 4, e->device));
         hipLaunchKernelGGL(k_pool_dense, dim3((B + PD_SEQ - 1) / PD_SEQ), dim3(256), dense_lds, st, e->pooled, e->dense_w, B, H, P, e->out);
     }
+    if (flags) {                 // bge-m3's token-level blocks, straight into tok_out: sparse [B, S], then colbert [B, S, P]
+        const int64_t slots = (int64_t)B * S;
+        const unsigned slot_grid = (unsigned)((slots + 3) / 4);
+        hipLaunchKernelGGL(k_m3_slots, dim3(B), dim3(64), 0, st, e->d_mask, e->seq_off, S, e->slot_row);
+        float* o = tok_out;
+        if (flags & KR_POOL_WITH_SPARSE) {
+            hipLaunchKernelGGL(k_m3_sparse, dim3(slot_grid), dim3(256), 0, st, e->xb, e->xlo, e->sp_w, e->sp_b, e->slot_row, slots, H, o, e->d_err);
+            o += slots;
+        }
+        if (flags & KR_POOL_WITH_COLBERT) {      // one more projection of the packed rows on the loops every layer uses, then bias + norm + scatter
+            ProjArgs a{};
+            a.Tp = e->d_T; a.H = H; a.W = e->col_w; a.X = e->xb; a.F = e->col_rows; a.K = H; a.bias = e->col_b; a.out0 = e->cy;
+            KR_TRY(launch_proj(EPI_DENSE, a, maxT, e, st));
+            hipLaunchKernelGGL(k_m3_rows, dim3(slot_grid), dim3(256), 0, st, e->cy, e->col_b, e->slot_row, slots, e->col_rows, o, e->d_err);
+        }
+    }
     KR_HIP(hipGetLastError());
     return 0;
 }
@@ -1307,7 +1409,17 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
         return fail(KR_EINVAL, "sequence length %d + padding index %d + 1 exceeds max_position_embeddings %d (fairseq position rule: at most %d tokens)", S, e->pad_idx,
                     e->cfg.max_pos, e->cfg.max_pos - e->pad_idx - 1);
     if (total_tokens > (int64_t)B * S) return fail(KR_EINVAL, "total_tokens %lld exceeds B * S = %lld", (long long)total_tokens, (long long)B * S);
-    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY) return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls) or 2 (classify)");
+    const int flags = pool & M3_FLAGS;
+    pool &= ~M3_FLAGS;
+    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY)
+        return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls) or 2 (classify), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)");
+    if (flags && pool == KR_POOL_CLASSIFY) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 2 (classify)");
+    if (flags && total_tokens >= 0)
+        return fail(KR_EINVAL, "kr_encoder_forward_packed takes no KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT: the token-level blocks are laid out by the columns of a padded batch");
+    if ((flags & KR_POOL_WITH_SPARSE) && !e->has_sparse())
+        return fail(KR_ESTATE, "KR_POOL_WITH_SPARSE on a handle without a sparse head: sparse_linear.weight and sparse_linear.bias were never loaded");
+    if ((flags & KR_POOL_WITH_COLBERT) && !e->has_colbert())
+        return fail(KR_ESTATE, "KR_POOL_WITH_COLBERT on a handle without a colbert head: colbert_linear.weight and colbert_linear.bias were never loaded");
     if (pool == KR_POOL_CLASSIFY && !e->has_head())
         return fail(KR_ESTATE, "pool = 2 (classify) on a handle without a classification head: classifier.dense.{weight,bias} and classifier.out_proj.{weight,bias} "
                                "were never loaded");
@@ -1329,8 +1441,11 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 }
 
 // behind the kernels of a forward: the result and the error word travel to the caller
-static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st) {
-    KR_HIP(hipMemcpyAsync(out, e->out, (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim()) * 4, hipMemcpyDefault, st));
+// (tok_elems > 0: the token-level blocks of a flagged forward with a host `out` wait in e->tok_stage and follow the dense block)
+static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st, size_t tok_elems = 0) {
+    const size_t dense_elems = (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim());
+    KR_HIP(hipMemcpyAsync(out, e->out, dense_elems * 4, hipMemcpyDefault, st));
+    if (tok_elems) KR_HIP(hipMemcpyAsync(out + dense_elems, e->tok_stage, tok_elems * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;
     KR_HIP(hipMemcpyAsync(e->h_err, e->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     if (is_device_pointer(out)) {
@@ -1354,8 +1469,26 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     KR_HIP(hipMemcpyAsync(e->d_ids, input_ids, (size_t)B * S * 8, hipMemcpyDefault, st));
     KR_HIP(hipMemcpyAsync(e->d_mask, attention_mask, (size_t)B * S * 8, hipMemcpyDefault, st));
     if (token_type_ids) KR_HIP(hipMemcpyAsync(e->d_tt, token_type_ids, (size_t)B * S * 8, hipMemcpyDefault, st));
-    KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
-    return finish_forward(e, B, S, pool, out, st);
+    const int flags = pool & M3_FLAGS;
+    if (!flags) {
+        KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
+        return finish_forward(e, B, S, pool, out, st);
+    }
+    // bge-m3's token-level blocks: a device `out` takes them straight from the kernels (0.5 GB at 1024 x 128 x 1024: no second trip through the workspace), a
+    // host `out` is staged.  The kernels hold the caller's pointer, so a flagged forward is never replayed from a captured graph.
+    pool &= ~M3_FLAGS;
+    const size_t slots = (size_t)B * S;
+    const size_t tok_elems = ((flags & KR_POOL_WITH_SPARSE) ? slots : 0) + ((flags & KR_POOL_WITH_COLBERT) ? slots * e->col_rows : 0);
+    const bool direct = is_device_pointer(out);
+    if (!direct && tok_elems > e->tok_stage_elems) {
+        KR_HIP(hipStreamSynchronize(e->last_stream));      // an earlier staged copy may still read the old buffer
+        if (e->tok_stage) (void)hipFree(e->tok_stage);
+        e->tok_stage = nullptr; e->tok_stage_elems = 0;
+        KR_HIP(hipMalloc(reinterpret_cast<void**>(&e->tok_stage), tok_elems * 4));
+        e->tok_stage_elems = tok_elems;
+    }
+    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, flags, direct ? out + (size_t)B * e->out_dim() : e->tok_stage));
+    return finish_forward(e, B, S, pool, out, st, direct ? 0 : tok_elems);
 }
 
 // kr_encoder_forward_packed: the same forward from the ragged token list (int32 ids of the attended positions + int32 length per sequence)

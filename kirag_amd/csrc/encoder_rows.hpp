@@ -641,6 +641,85 @@ __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restr
     });
 }
 
+// bge-m3's token-level heads (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT).  Both blocks are laid out by the columns of the padded [B, S] input, so the kernels
+// run one wave per SLOT (b, s) and find their packed row through slot_row: k_m3_slots writes off[b] + (rank of column s among the attended columns of its
+// row) — the order fill_seq packs them in — or -1 for a masked column.  The query-only row of a masked column 0 (CLS pooling) sits behind the attended ones
+// and has no slot.  No slot is written twice and none is skipped: no atomics, no zero-fill pass.
+__global__ __launch_bounds__(64) void k_m3_slots(const int64_t* __restrict__ mask, const int* __restrict__ seq_off, int S, int* __restrict__ slot_row) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int64_t* m = mask + (int64_t)b * S;
+    const int off = seq_off[b];
+    int run = 0;
+    for (int base = 0; base < S; base += 64) {
+        const int p = base + lane;
+        const bool v = p < S && m[p] != 0;
+        const unsigned long long bal = __ballot(v);
+        if (p < S) slot_row[(int64_t)b * S + p] = v ? off + run + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+        run += __popcll(bal);
+    }
+}
+
+// colbert rows: y [T, P] = colbert_linear.weight . x as the projection loops stored it (EPI_DENSE: 16-bit, no bias) -> out[b, s, :] = (y + bias) / max(|y + bias|, 1e-12)
+// in fp32, or P times +0.0 for a masked slot.  One wave per slot, lane l owns columns l, l + 64, ...: 4-byte stores (the block starts wherever the caller's
+// dense and sparse blocks end, so nothing wider is aligned), 256 contiguous bytes per store instruction.  The row is read twice (norm, then values: the second
+// pass hits the cache) instead of being held in P / 64 registers; squares are added in column order per lane, then by a shuffle butterfly: one order per row.
+__global__ __launch_bounds__(256) void k_m3_rows(const uint16_t* __restrict__ y, const float* __restrict__ bias, const int* __restrict__ slot_row, int64_t slots, int P,
+                                                 float* __restrict__ out, int* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= slots) return;
+    float* o = out + slot * P;
+    const int r = slot_row[slot];
+    if (r < 0) {
+        for (int c = lane; c < P; c += 64) o[c] = 0.f;
+        return;
+    }
+    const uint16_t* yr = y + (int64_t)r * P;
+    float ss = 0.f;
+    for (int c = lane; c < P; c += 64) {
+        const float v = ET::to_f32(yr[c]) + bias[c];
+        ss += v * v;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    const float nrm = sqrtf(ss);
+    if (lane == 0 && !(nrm < INFINITY)) atomicOr(err, 2);      // an attended token's vector is not finite: KR_ERANGE, like a non-finite embedding (k_pool)
+    const float den = fmaxf(nrm, 1e-12f);                       // F.normalize's floor; a NaN norm stays NaN below
+    for (int c = lane; c < P; c += 64) {
+        const float v = ET::to_f32(yr[c]) + bias[c];
+        o[c] = (nrm == nrm) ? v / den : NAN;
+    }
+}
+
+// sparse weights: out[b, s] = max(0, w . x + bias) over the decoded final row x (the (hi, lo) stream, read as k_pool reads it), +0.0 for a masked slot.  One
+// wave per slot: a lane owns 4 consecutive columns per 256-column step and adds its products with fp32 FMAs in column order, the 64 lane sums are folded by a
+// shuffle butterfly — one order per token, whatever the batch.
+__global__ __launch_bounds__(256) void k_m3_sparse(const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   const int* __restrict__ slot_row, int64_t slots, int H, float* __restrict__ out, int* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= slots) return;
+    const int r = slot_row[slot];
+    if (r < 0) { if (lane == 0) out[slot] = 0.f; return; }
+    float acc = 0.f;
+    for (int i = lane * 4; i < H; i += 256) {
+        const ushort4 hi = *reinterpret_cast<const ushort4*>(xb + (int64_t)r * H + i);
+        const unsigned int lo = *reinterpret_cast<const unsigned int*>(xlo + (int64_t)r * H + i);
+        const float4 ww = *reinterpret_cast<const float4*>(w + i);
+        acc = fmaf(ww.x, lo_decode_final(lo & 0xffu, ET::to_f32(hi.x)), acc);
+        acc = fmaf(ww.y, lo_decode_final((lo >> 8) & 0xffu, ET::to_f32(hi.y)), acc);
+        acc = fmaf(ww.z, lo_decode_final((lo >> 16) & 0xffu, ET::to_f32(hi.z)), acc);
+        acc = fmaf(ww.w, lo_decode_final(lo >> 24, ET::to_f32(hi.w)), acc);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    const float v = acc + bias[0];
+    if (lane == 0) {
+        if (!(fabsf(v) < INFINITY)) atomicOr(err, 2);          // NaN / Inf weight of an attended token: KR_ERANGE
+        out[slot] = (v != v) ? v : (v > 0.f ? v : 0.f);
+    }
+}
+
 // CLS shortcut: row seq_off[b] + seq_cls[b] of ctx / the residual stream (hi, lo) -> row b of the compact buffers; also the compact "sequence" tables
 // (one token per sequence) and the row count for the B-row kernels that follow
 __global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__ ctx, const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,

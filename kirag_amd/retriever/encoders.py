@@ -45,6 +45,10 @@ added in every layer — on unscaled scores ``q.k + bias``, no linear bias anywh
 ``Dense`` module of such a checkpoint (a bias-free ``Linear(H -> P)`` between the pooling and the normalisation) is read into ``self.dense`` by
 ``from_pretrained`` and runs inside the library (``dense.weight``): the embeddings are then ``[B, P]``.  ``T5E5Encoder`` / ``T5BGEEncoder`` are the twins over
 ``transformers.T5EncoderModel``.
+
+bge-m3's token-level heads (``colbert_linear`` / ``sparse_linear`` on BERT / RoBERTa handles): ``POOL_WITH_SPARSE`` / ``POOL_WITH_COLBERT`` ORed onto pool 0 / 1
+make ``HipBertForward.forward`` / ``forward_np`` return ``(dense [B, H], sparse [B, S] or None, colbert [B, S, P] or None)``, three views into the one tensor
+the library wrote (``_layout``); the twins with the heads and the scoring on top of them live in ``kirag_amd.retriever.m3``.
 """
 from __future__ import annotations
 
@@ -63,6 +67,18 @@ from .. import _lib
 POOL_MEAN, POOL_CLS = 0, 1
 POOL_CLASSIFY = 2        # KR_POOL_CLASSIFY: the CLS row -> the classification head -> raw logits [B, num_labels] (kirag_amd.retriever.rerankers)
 CLASSIFIER_OUT = "classifier.out_proj.weight"    # [num_labels, hidden]: its rows are the width of a classify forward
+# bge-m3's token-level heads: flag bits ORed onto POOL_MEAN / POOL_CLS (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT).  A flagged forward returns the three
+# blocks of its one output tensor (HipBertForward._blocks): dense [B, hidden], sparse [B, S] or None, colbert [B, S, P] or None
+POOL_WITH_SPARSE, POOL_WITH_COLBERT = 0x10, 0x20
+POOL_M3_FLAGS = POOL_WITH_SPARSE | POOL_WITH_COLBERT
+COLBERT_WEIGHT = "colbert_linear.weight"         # [P, hidden]: its rows are the width of a token vector
+COLBERT_MIN, COLBERT_MAX, COLBERT_STEP = 128, 2048, 128      # the library's rule for P (kirag_amd.h)
+
+
+def check_colbert_dim(P: int) -> None:
+    """``ValueError`` naming the field for a colbert width the library refuses (``colbert_linear.weight`` [P, hidden])"""
+    if P % COLBERT_STEP or not COLBERT_MIN <= P <= COLBERT_MAX:
+        raise ValueError(f"colbert_linear.out_features={P}: the library takes a multiple of {COLBERT_STEP} with {COLBERT_MIN} <= P <= {COLBERT_MAX}")
 # model_type values whose position ids follow fairseq's rule on BERT's post-LN layer stack ("xlm-roberta-xl" is pre-LN: not one of them)
 ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
 MPNET_TYPE = "mpnet"
@@ -118,6 +134,7 @@ class HipBertForward:
         task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``)."""
         lib = _lib.load()
         self.rename = rename
+        self.colbert_dim = 0              # rows of "colbert_linear.weight" once the library has accepted it: the width of a token vector
         self.num_labels = 0               # rows of "classifier.out_proj.weight" once the library has accepted it: the width of a POOL_CLASSIFY forward
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
         self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
@@ -311,10 +328,50 @@ class HipBertForward:
             self.out_dim = int(numel) // self.hidden
         elif name == CLASSIFIER_OUT:
             self.num_labels = int(numel) // self.hidden
+        elif name == COLBERT_WEIGHT:
+            self.colbert_dim = int(numel) // self.hidden
 
     def _width(self, pool: int) -> int:
-        """columns of a forward's output: the logits of ``POOL_CLASSIFY``, else the embedding"""
+        """columns of an unflagged forward's output: the logits of ``POOL_CLASSIFY``, else the embedding"""
         return self.num_labels if pool == POOL_CLASSIFY else self.out_dim
+
+    def _layout(self, pool: int, B: int, S: int):
+        """The blocks of a forward's ONE output tensor as (elements, shape) per block, in the library's order: dense, then with ``POOL_WITH_SPARSE`` [B, S],
+        then with ``POOL_WITH_COLBERT`` [B, S, P].  An unflagged pool has the dense block only."""
+        blocks = [(B, self._width(pool & ~POOL_M3_FLAGS))]
+        if pool & POOL_WITH_SPARSE:
+            blocks.append((B, S))
+        if pool & POOL_WITH_COLBERT:
+            blocks.append((B, S, self.colbert_dim))
+        return blocks
+
+    def _out_shape(self, pool: int, B: int, S: int):
+        """shape of the tensor a forward writes: [B, width] unflagged, flat with flags"""
+        if not pool & POOL_M3_FLAGS:
+            return (B, self._width(pool))
+        total = 0
+        for shape in self._layout(pool, B, S):
+            n = 1
+            for d in shape:
+                n *= d
+            total += n
+        return (total,)
+
+    def _blocks(self, out, pool: int, B: int, S: int):
+        """What a forward returns: the [B, width] tensor itself unflagged; with flags the triple (dense, sparse or None, colbert or None) of views into it"""
+        if not pool & POOL_M3_FLAGS:
+            return out
+        views, at = [], 0
+        for shape in self._layout(pool, B, S):
+            n = 1
+            for d in shape:
+                n *= d
+            views.append(out[at:at + n].reshape(shape))
+            at += n
+        dense = views.pop(0)
+        sparse = views.pop(0) if pool & POOL_WITH_SPARSE else None
+        colbert = views.pop(0) if pool & POOL_WITH_COLBERT else None
+        return dense, sparse, colbert
 
     def _load_zero_token_types(self) -> None:
         if self.is_mpnet or self.is_modern:
@@ -346,24 +403,25 @@ class HipBertForward:
         import numpy as np
         ids = np.ascontiguousarray(input_ids, dtype=np.int64); mask = np.ascontiguousarray(attention_mask, dtype=np.int64)
         B, S = ids.shape
-        out = np.empty((B, self._width(pool)), np.float32)
+        out = np.empty(self._out_shape(pool, B, S), np.float32)
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.ctypes.data, mask.ctypes.data, B, S, pool, out.ctypes.data, None))
         else:
             tt = np.ascontiguousarray(token_type_ids, dtype=np.int64)
             assert tt.shape == ids.shape
             _lib.check(self._lib.kr_encoder_forward_tt(self._h, ids.ctypes.data, mask.ctypes.data, tt.ctypes.data, B, S, pool, out.ctypes.data, None))
-        return out
+        return self._blocks(out, pool, B, S)
 
     def forward(self, input_ids: Tensor, attention_mask: Tensor, pool: int, token_type_ids: Optional[Tensor] = None) -> Tensor:
-        """Enqueue-only for device tensors.  ``token_type_ids`` (HF BertModel's third input; None = zeros, what every KiRAG caller passes) go to the
+        """Enqueue-only for device tensors.  A ``pool`` with ``POOL_WITH_SPARSE`` / ``POOL_WITH_COLBERT`` returns the triple of ``_blocks``, any other the
+        ``[B, width]`` tensor.  ``token_type_ids`` (HF BertModel's third input; None = zeros, what every KiRAG caller passes) go to the
         kernels like the token ids: a value outside ``[0, type_vocab_size)`` is reported by ``check()`` / the next call (``kr_encoder_forward_tt``)."""
         if not input_ids.is_cuda and token_type_ids is None and torch.cuda.is_available():
             return self._forward_host_inputs(input_ids, attention_mask, pool)
         ids = input_ids.to(torch.int64).contiguous()
         mask = attention_mask.to(device=ids.device, dtype=torch.int64).contiguous()
         B, S = ids.shape
-        out = torch.empty((B, self._width(pool)), dtype=torch.float32, device=ids.device)
+        out = torch.empty(self._out_shape(pool, B, S), dtype=torch.float32, device=ids.device)
         stream = _lib.current_stream_ptr() if ids.is_cuda else None
         if token_type_ids is None:
             _lib.check(self._lib.kr_encoder_forward(self._h, ids.data_ptr(), mask.data_ptr(), B, S, pool, out.data_ptr(), stream))
@@ -372,7 +430,7 @@ class HipBertForward:
             if tuple(tt.shape) != (B, S):
                 raise ValueError(f"token_type_ids must be [B,S] = {(B, S)}, got {tuple(tt.shape)}")
             _lib.check(self._lib.kr_encoder_forward_tt(self._h, ids.data_ptr(), mask.data_ptr(), tt.data_ptr(), B, S, pool, out.data_ptr(), stream))
-        return out
+        return self._blocks(out, pool, B, S)
 
     PIN_SLOTS = 4
 
@@ -398,12 +456,12 @@ class HipBertForward:
         buf[:n].view(B, S).copy_(input_ids)
         buf[n:2 * n].view(B, S).copy_(attention_mask)
         dev = torch.device("cuda", self.device_index)
-        out = torch.empty((B, self._width(pool)), dtype=torch.float32, device=dev)
+        out = torch.empty(self._out_shape(pool, B, S), dtype=torch.float32, device=dev)
         with torch.cuda.device(self.device_index):
             _lib.check(self._lib.kr_encoder_forward(self._h, buf.data_ptr(), buf.data_ptr() + 8 * n, B, S, pool, out.data_ptr(), _lib.current_stream_ptr()))
             ev = torch.cuda.Event(); ev.record()
         slot[1] = ev
-        return out
+        return self._blocks(out, pool, B, S)
 
     def forward_packed(self, token_ids, seq_lens, S: int, pool: int, total_tokens: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
         """The forward from RAGGED input (``kr_encoder_forward_packed``): ``token_ids`` int32 = the attended ids of every sequence back to back, ``seq_lens`` int32

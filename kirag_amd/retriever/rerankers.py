@@ -26,6 +26,7 @@ from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
 from .encoders import _CONFIG_KWARGS, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
+from .m3 import BGEM3Model
 
 MAX_LABELS = 64          # the library's bound on the rows of classifier.out_proj (include/kirag_amd.h)
 
@@ -106,13 +107,18 @@ class BGEReranker:
 
 
 RERANKER_MAP = {"BGEReranker": BGEReranker}
+# second stages that are no cross-encoder, reached through load_reranker under these names.  "BGEM3": hybrid dense + sparse + multi-vector scoring with the
+# retriever's own bge-m3 checkpoint (kirag_amd.retriever.m3), no second model in HBM.  Kept apart from RERANKER_MAP: that map lists the models
+# BaseReranker.score() can drive (a forward that returns logits), which a BGEM3Model is not.
+HYBRID_RERANKER_MAP = {"BGEM3": BGEM3Model}
 
 
 def load_reranker(reranker_name, model_name_or_path, **kwargs):
-    if reranker_name not in RERANKER_MAP:
-        raise KeyError(f"{reranker_name} is not implemented! Current available rerankers: {list(RERANKER_MAP.keys())}")
+    known = {**RERANKER_MAP, **HYBRID_RERANKER_MAP}
+    if reranker_name not in known:
+        raise KeyError(f"{reranker_name} is not implemented! Current available rerankers: {list(known.keys())}")
     print(f"loading {reranker_name} model from {model_name_or_path} ...")
-    return RERANKER_MAP[reranker_name].from_pretrained(model_name_or_path, **kwargs)
+    return known[reranker_name].from_pretrained(model_name_or_path, **kwargs)
 
 
 def rank_order(scores: Sequence[float]) -> np.ndarray:

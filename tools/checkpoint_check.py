@@ -31,6 +31,10 @@ A sequence-classification checkpoint (config.json names an ...ForSequenceClassif
 is loaded as its reranker twin (kirag_amd.retriever.rerankers) instead, GPU only, and the report is the worst |logit - HF fp32 logit| over the built-in
 (question, passage) pairs — every question against every passage — for the four precision modes; the f16 range risk is the encoder's, as above.
 
+A bge-m3 folder (colbert_linear.pt and / or sparse_linear.pt next to the backbone's files: BAAI/bge-m3) is loaded as its M3 twin (kirag_amd.retriever.m3), GPU
+only, and the report is, against HF fp32 + the two heads in torch, the worst per-token 1 - cos of the multi-vector block and the worst |weight difference| of the
+sparse block over the built-in texts, for the four precision modes.
+
 Texts: --texts (one per line; the first half are used as queries, the rest as passages, E5 prefixes added) needs the checkpoint's tokenizer; without a
 tokenizer in the directory (or with --random-tokens) seeded random token ids of ragged lengths are used."""
 import argparse
@@ -252,9 +256,57 @@ def check_reranker(hf_dir, args):
     return out
 
 
+def check_m3(hf_dir, args):
+    """worst per-token 1 - cos (colbert block) and worst |dw| (sparse block) of a bge-m3 folder against HF fp32 + torch heads, per precision mode"""
+    from kirag_amd.retriever.encoders import POOL_CLS, POOL_WITH_COLBERT, POOL_WITH_SPARSE, HipBertForward
+    from kirag_amd.retriever.m3 import BGEM3Model
+    if not torch.cuda.is_available() or args.emulate:
+        raise SystemExit(f"{hf_dir}: a bge-m3 folder is checked on the GPU (the torch emulation has no token-level heads)")
+    model = BGEM3Model(hf_dir, tokenizer=False, device="cuda:0").model.float().eval()
+    cfg = model.config
+    roberta = cfg.model_type != "bert"
+    results = []
+    batches = load_inputs(args, hf_dir, cfg.vocab_size, cfg.pad_token_id if roberta else None)
+    refs = []
+    with torch.no_grad():
+        for ids, mask in batches:
+            k = torch.from_numpy(mask).to("cuda:0")
+            lh = model._hf_base.forward(model, input_ids=torch.from_numpy(ids).to("cuda:0"), attention_mask=k).last_hidden_state
+            c = torch.nn.functional.normalize(model.colbert_linear(lh), dim=-1) * k[..., None] if model.colbert_linear is not None else None
+            w = torch.relu(model.sparse_linear(lh)).squeeze(-1) * k if model.sparse_linear is not None else None
+            refs.append((None if c is None else c.double().cpu().numpy(), None if w is None else w.double().cpu().numpy()))
+    flags = (POOL_WITH_SPARSE if model.sparse_linear is not None else 0) | (POOL_WITH_COLBERT if model.colbert_linear is not None else 0)
+    print(f"# {hf_dir}: {type(model).__name__}, {cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}; heads: "
+          f"{'colbert P = %d' % model.colbert_linear.out_features if model.colbert_linear is not None else 'no colbert'}, "
+          f"{'sparse' if model.sparse_linear is not None else 'no sparse'}; {sum(len(b[0]) for b in batches)} sequences")
+    for dtype, lo in MODES:
+        h = HipBertForward(cfg, 0, operand_dtype=dtype, residual_lo=lo)
+        h.sync(model)
+        cos = dw = 0.0
+        finite = True
+        for (ids, mask), (rc, rw) in zip(batches, refs):
+            _, w, c = h.forward_np(ids, mask, POOL_CLS | flags)
+            k = mask != 0
+            if c is not None:
+                finite = finite and bool(np.isfinite(c).all())
+                cos = max(cos, float((1.0 - (c.astype(np.float64)[k] * rc[k]).sum(-1)).max()))
+            if w is not None:
+                finite = finite and bool(np.isfinite(w).all())
+                dw = max(dw, float(np.abs(w.astype(np.float64) - rw)[k].max()))
+        results.append({"operand_dtype": dtype, "residual_lo": lo, "worst_token_1_minus_cos": cos, "worst_sparse_weight_error": dw, "finite": finite})
+        print(f"  {dtype:4s} {'+ low half' if lo else '          '}  worst per-token 1 - cos = {cos:.2e}   worst |dw| = {dw:.2e}" + ("" if finite else "   NON-FINITE OUTPUT"))
+    out = {"checkpoint": hf_dir, "tested_path": "hip", "kind": "bge-m3", "modes": results}
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
     cfg = AutoConfig.from_pretrained(hf_dir)
+    if os.path.isdir(hf_dir) and (os.path.exists(os.path.join(hf_dir, "colbert_linear.pt")) or os.path.exists(os.path.join(hf_dir, "sparse_linear.pt"))):
+        return check_m3(hf_dir, args)
     if any(a.endswith("ForSequenceClassification") for a in (getattr(cfg, "architectures", None) or [])):
         return check_reranker(hf_dir, args)
     from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
