@@ -237,6 +237,10 @@ typedef struct {
  * holds, back to back and all fp32: the dense block [B, hidden] (the bits of the unflagged call with the same base pool), with KR_POOL_WITH_SPARSE the sparse
  * block [B, S], with KR_POOL_WITH_COLBERT the colbert block [B, S, P] ("sparse_linear.*" / "colbert_linear.*" under kr_encoder_load_weight below).  Any other
  * bit, the flags on KR_POOL_CLASSIFY or in kr_encoder_forward_packed: KR_EINVAL; a flag whose head was never loaded: KR_ESTATE. */
+/* SPLADE (learned sparse retrieval): the MLM head of a BertForMaskedLM checkpoint, max-pooled over the attended tokens.  `out` is [B, vocab] fp32, every entry
+ * >= 0 (needs the six "cls.predictions.*" tensors, below; without them KR_ESTATE).  Accepted by kr_encoder_forward, kr_encoder_forward_tt and
+ * kr_encoder_forward_packed; combined with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT: KR_EINVAL.  The value 3 stays refused. */
+#define KR_POOL_SPLADE 4
 #define KR_POOL_WITH_SPARSE 0x10
 #define KR_POOL_WITH_COLBERT 0x20
 
@@ -374,13 +378,31 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   rounding (measured figures for both types: profiles/m3/measurements.txt).  The sparse dot product reads the final rows with their low
  *   half, in fp32 with a fixed order.  A token's weight and vector do not depend on the batch around it.  A non-finite weight or vector of an attended
  *   token is reported as KR_ERANGE like a non-finite embedding.  A device `out` receives the token-level blocks straight from the kernels; a host `out` is
- *   staged on the device.  kr_encoder_forward_packed refuses the flags: the corpus pipeline behind it stores no token vectors, so the refusal costs nothing. */
+ *   staged on the device.  kr_encoder_forward_packed refuses the flags: the corpus pipeline behind it stores no token vectors, so the refusal costs nothing.
+ * SPLADE's MLM head (transformers.BertForMaskedLM: naver/splade-cocondenser-ensembledistil, naver/splade-v3, ...), fp32, V = cfg.vocab:
+ *   "cls.predictions.transform.dense.weight" [hidden, hidden], "cls.predictions.transform.dense.bias" [hidden],
+ *   "cls.predictions.transform.LayerNorm.weight" [hidden], "cls.predictions.transform.LayerNorm.bias" [hidden],
+ *   "cls.predictions.decoder.weight" [V, hidden], "cls.predictions.decoder.bias" [V]: any other row count is KR_EINVAL.
+ *   The decoder weight is loaded explicitly — that HF ties it to the word table is the caller's business ("cls.predictions.bias" is HF's alias of the decoder
+ *   bias: send one).  All six or none (a partial set fails kr_encoder_finalize as "never loaded"); under the rule of "classifier.*" the head is fixed at the
+ *   first finalize — later the same shapes take new values, a head arriving on a handle finalized without it is KR_EINVAL.  kr_encoder_finalize refuses it
+ *   (KR_EINVAL, naming the tensor) on MPNet, NomicBert, ModernBert and T5 handles, next to "classifier.*", next to "dense.weight" and next to bge-m3's heads.
+ *   With x[b, s] = the row of last_hidden_state, the LayerNorm at cfg.ln_eps and the erf-GELU of the stack:
+ *       t      = LayerNorm(gelu(transform.dense.weight . x + bias))
+ *       w[b,v] = max over the ATTENDED tokens s of log(1 + relu(decoder.weight[v] . t[b, s] + decoder.bias[v]))          out [B, V]
+ *   computed as log1p(max(0, bias[v] + max_s acc[b, s, v])) — log1p(relu(.)) is monotone —: the decoder runs on the MFMA projection loops over a 16-bit copy
+ *   [Vpad, hidden] of the weight (V rounded up to a multiple of 128 by zero rows that never reach `out`; t is rounded to the 16-bit operand type like every
+ *   activation of the stack) and its epilogue reduces the fp32 accumulators over the rows of each sequence: no [tokens, V] logits exist in any precision.
+ *   The last layer runs on every row; packing and attention are those of KR_POOL_MEAN.  A sequence without attended tokens yields V times +0.0.  The
+ *   result is exact in the sense that max is: a sequence's row does not depend on the batch, the tiling or the call.  A non-finite value (NaN / Inf in the head's
+ *   weights, a non-finite row of t) is reported as KR_ERANGE like a non-finite embedding.  A device `out` is the reduction buffer itself; a host `out` is staged.
+ *   (The definition is recalled from naver's Splade module and sentence-transformers' SpladePooling("max"); neither was at hand to compare against.) */
 int kr_encoder_load_weight(kr_encoder* enc, const char* hf_name, const float* data, int64_t numel);
 /* verifies every tensor was supplied and builds the fused/packed device copies */
 int kr_encoder_finalize(kr_encoder* enc);
 /* forward(input_ids, attention_mask) (encoders.py:67-77 / :106-118); token_type_ids are 0 as in every caller.
  *   input_ids, attention_mask [B,S] int64 (S <= max_pos), out [B,hidden] fp32 L2-normalised ([B,P] on a handle that was given "dense.weight" [P, hidden];
- *   [B,L] raw logits with pool = KR_POOL_CLASSIFY; with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT the blocks [B,hidden] | [B,S] | [B,S,P], see above).
+ *   [B,L] raw logits with pool = KR_POOL_CLASSIFY; [B,vocab] with pool = KR_POOL_SPLADE; with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT the blocks [B,hidden] | [B,S] | [B,S,P], see above).
  *   A sequence whose mask is all zero yields NaN (mean pool) exactly like the reference. */
 int kr_encoder_forward(kr_encoder* enc, const int64_t* input_ids, const int64_t* attention_mask, int B, int S,
                        int pool, float* out, void* stream);

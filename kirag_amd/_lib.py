@@ -13,6 +13,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KIRAG_AMD_LIB") or os.path.join(_HERE, "libkirag_amd.so")   # KIRAG_AMD_LIB: another build of the library (A/B)
 ABI_VERSION = 9
+POOL_SPLADE = 4          # KR_POOL_SPLADE (include/kirag_amd.h): the MLM head max-pooled over the attended tokens, out [B, vocab]
 
 
 class KiragAmdError(RuntimeError):

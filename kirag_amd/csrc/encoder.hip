@@ -37,6 +37,10 @@
 // runs its last layer on every row; behind the pooling k_m3_slots maps the [B, S] columns to packed rows, k_m3_sparse writes max(0, w . x + b) per column, and
 // the colbert vectors are one more EPI_DENSE projection of the packed rows followed by k_m3_rows (bias, norm, scatter to [b, s], zeros for masked columns).
 //
+// SPLADE (KR_POOL_SPLADE on BERT handles with the six "cls.predictions.*" tensors of BertForMaskedLM): the stack runs as for mean pooling, then one EPI_GELU
+// projection H -> H and k_ln16_head give the transform's rows, and the decoder [Vpad, H] runs on the projection loops with the EPI_SPLADE epilogue
+// (encoder_proj.hpp): the max over each sequence's rows lands in the [B, V] output itself by atomicMax, no [T, V] logits exist; k_splade_finish applies log1p.
+//
 // Files.  This one: the Encoder handle, launch selection, the entry points.  Device code per operand type, included here: encoder_rows.hpp (residual-stream
 // codec, embedding, LayerNorm, pooling), encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
@@ -154,6 +158,13 @@ struct Encoder {
     bool has_colbert() const { return col_got == 3u; }
     bool has_sparse() const { return sp_got == 3u; }
     uint16_t* cy = nullptr; int* slot_row = nullptr;
+    // SPLADE's MLM head, "cls.predictions.{transform.dense,transform.LayerNorm,decoder}.{weight,bias}" (MLM_NAMES, one bit of mlm_got each; all six or none at
+    // finalize).  mlm_wt: the 16-bit copy [H, H]; mlm_wd: the 16-bit copy [Vpad, H] of the decoder, Vpad = vocab rounded up to MLM_COLS by zero rows; mlm_bd fp32
+    // [Vpad] (zero behind V); mlm_zero: H zeros (k_ln16_head).  row_seq: the sequence of every packed row or -1 (workspace, k_splade_rowseq)
+    uint16_t *mlm_wt = nullptr, *mlm_wd = nullptr; float *mlm_bt = nullptr, *mlm_g = nullptr, *mlm_b = nullptr, *mlm_bd = nullptr, *mlm_zero = nullptr;
+    unsigned mlm_got = 0;
+    bool has_mlm() const { return mlm_got == 63u; }
+    int* row_seq = nullptr;
     float* tok_stage = nullptr; size_t tok_stage_elems = 0;
     uint16_t *rb = nullptr, *c_rb = nullptr;   // the pre-LN residual stream (and its CLS-row copy): 16-bit high half
     uint8_t *rlo = nullptr, *c_rlo = nullptr;  // ... and the low-half bytes (use_lo)
@@ -234,6 +245,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
     KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_width() * 4));
     if (e->dense_rows > 0 || e->cls_got) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
     if (e->col_got || e->sp_got) KR_TRY(dmalloc(e->ws_bufs, &e->slot_row, capBS * 4));
+    if (e->mlm_got) KR_TRY(dmalloc(e->ws_bufs, &e->row_seq, capT * 4));
     if (e->col_rows > 0) KR_TRY(dmalloc(e->ws_bufs, &e->cy, capT * e->col_rows * 2));      // capT rows: the projection's tiles are whole (see k_proj)
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
@@ -473,6 +485,9 @@ static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int devi
         case EPI_GEGLU: return go(&k_proj<EPI_GEGLU, Shape, STAGES, NT>);
         case EPI_RELU: return go(&k_proj<EPI_RELU, Shape, STAGES, NT>);
         case EPI_GEGLU_TANH: return go(&k_proj<EPI_GEGLU_TANH, Shape, STAGES, NT>);
+        case EPI_SPLADE:        // stores no rows: one instantiation per shape (launch_proj clears nt)
+            if constexpr (NT) return fail(KR_EINVAL, "projection epilogue %d has no non-temporal stores", epi);
+            else return go(&k_proj<EPI_SPLADE, Shape, STAGES, false>);
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }
@@ -507,7 +522,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
     a.pw = kn.pw;
     a.epi_prio = kn.epi_prio;
     // store policy by output size (see ProjArgs::nt)
-    a.nt = max_tokens * (int64_t)(epi_gated(epi) ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
+    a.nt = epi != EPI_SPLADE && max_tokens * (int64_t)(epi_gated(epi) ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
     // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
     // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
     // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
@@ -544,6 +559,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
                 case EPI_GEGLU: return launch(shape_tag, &k_proj_skinny<EPI_GEGLU, RING, WM, WM>);
                 case EPI_RELU: return launch(shape_tag, &k_proj_skinny<EPI_RELU, RING, WM, WM>);
                 case EPI_GEGLU_TANH: return launch(shape_tag, &k_proj_skinny<EPI_GEGLU_TANH, RING, WM, WM>);
+                case EPI_SPLADE: return launch(shape_tag, &k_proj_skinny<EPI_SPLADE, RING, WM, WM>);
                 default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
             }
         };
@@ -569,6 +585,7 @@ static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const 
             case EPI_GEGLU: return go(&k_proj_split<EPI_GEGLU>);
             case EPI_RELU: return go(&k_proj_split<EPI_RELU>);
             case EPI_GEGLU_TANH: return go(&k_proj_split<EPI_GEGLU_TANH>);
+            case EPI_SPLADE: return go(&k_proj_split<EPI_SPLADE>);
             default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
         }
     }
@@ -849,6 +866,20 @@ static int load_cls_head(Encoder* e, int which, const float* data, int64_t numel
     return 0;
 }
 
+// fp32 [numel] from the caller -> the handle's 16-bit operand type at dst
+static int upload_16bit(const float* data, int64_t numel, uint16_t* dst) {
+    float* tmp = nullptr;
+    KR_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)numel * 4));
+    hipError_t rc = hipMemcpy(tmp, data, (size_t)numel * 4, hipMemcpyDefault);
+    if (rc == hipSuccess) {
+        hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, tmp, dst, numel, 1.f);
+        rc = hipGetLastError();
+        if (rc == hipSuccess) rc = hipDeviceSynchronize();
+    }
+    (void)hipFree(tmp);
+    KR_HIP(rc);
+    return 0;
+}
 // "colbert_linear.{weight,bias}" [P, H] / [P] (P % 128 == 0, 128 <= P <= 2048) and "sparse_linear.{weight,bias}" [1, H] / [1]: bge-m3's token-level heads.
 // Two independent heads under the rule of "classifier.*": a head belongs to the handle from its first finalize on — later the same P takes new values,
 // another P, or a head on a handle finalized without it, is refused.
@@ -880,16 +911,7 @@ static int load_m3_head(Encoder* e, int which, const float* data, int64_t numel)
     if (e->col_rows && e->col_rows != (int)P) return fail(KR_EINVAL, "'%s' with P = %d: the handle already holds a colbert_linear tensor with P = %d", name, (int)P, e->col_rows);
     if (weight) {
         if (!e->col_w) KR_TRY(dmalloc(e->own_bufs, &e->col_w, (size_t)numel * 2));
-        float* tmp = nullptr;
-        KR_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)numel * 4));
-        hipError_t rc = hipMemcpy(tmp, data, (size_t)numel * 4, hipMemcpyDefault);
-        if (rc == hipSuccess) {
-            hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, tmp, e->col_w, numel, 1.f);
-            rc = hipGetLastError();
-            if (rc == hipSuccess) rc = hipDeviceSynchronize();
-        }
-        (void)hipFree(tmp);
-        KR_HIP(rc);
+        KR_TRY(upload_16bit(data, numel, e->col_w));
     } else {
         if (!e->col_b) KR_TRY(dmalloc(e->own_bufs, &e->col_b, (size_t)numel * 4));
         KR_HIP(hipMemcpy(e->col_b, data, (size_t)numel * 4, hipMemcpyDefault));
@@ -897,6 +919,49 @@ static int load_m3_head(Encoder* e, int which, const float* data, int64_t numel)
     if (!e->col_got) free_ws(e);              // cy is sized by P, slot_row exists with a head
     e->col_rows = (int)P;
     e->col_got |= bit;
+    e->ready = false;
+    return 0;
+}
+
+// SPLADE's MLM head: BertForMaskedLM's "cls.predictions.transform.dense.{weight,bias}" [H, H] / [H], "cls.predictions.transform.LayerNorm.{weight,bias}" [H] and
+// "cls.predictions.decoder.{weight,bias}" [V, H] / [V] with V = cfg.vocab exactly (the decoder is loaded explicitly: tying it to the word table is the caller's
+// business).  Under the rule of "classifier.*": the head belongs to the handle from its first finalize on — later the same shapes take new values, a head
+// arriving on a handle finalized without it is refused.
+static const char* const MLM_NAMES[6] = {"cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias", "cls.predictions.transform.LayerNorm.weight",
+                                         "cls.predictions.transform.LayerNorm.bias", "cls.predictions.decoder.weight", "cls.predictions.decoder.bias"};
+constexpr int MLM_COLS = 128;          // column granularity of the projection loops (a wave owns 64 columns, the 128 x 128 tiles are whole)
+static int64_t mlm_vpad(const Encoder* e) { return round_up((int64_t)e->cfg.vocab, MLM_COLS); }
+static int load_mlm_head(Encoder* e, int which, const float* data, int64_t numel) {
+    const char* name = MLM_NAMES[which];
+    const int64_t H = e->cfg.hidden, V = e->cfg.vocab, Vpad = mlm_vpad(e);
+    const int64_t want = which == 0 ? H * H : which == 4 ? V * H : which == 5 ? V : H;
+    if (numel != want)
+        return fail(KR_EINVAL, which >= 4 ? "tensor '%s' has %lld elements, expected %lld (vocab_size = %d rows)" : "tensor '%s' has %lld elements, expected %lld", name,
+                    (long long)numel, (long long)want, e->cfg.vocab);
+    if (e->finalized_once && !e->has_mlm()) return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without an MLM head", name);
+    if (which == 0 || which == 4) {
+        uint16_t** dst = which == 0 ? &e->mlm_wt : &e->mlm_wd;
+        if (!*dst) {
+            const size_t bytes = (size_t)(which == 0 ? H : Vpad) * H * 2;
+            KR_TRY(dmalloc(e->own_bufs, dst, bytes));
+            KR_HIP(hipMemset(*dst, 0, bytes));       // the decoder's rows V .. Vpad - 1 stay zero
+        }
+        KR_TRY(upload_16bit(data, numel, *dst));
+    } else {
+        float** dst = which == 1 ? &e->mlm_bt : which == 2 ? &e->mlm_g : which == 3 ? &e->mlm_b : &e->mlm_bd;
+        if (!*dst) {
+            const size_t bytes = (size_t)(which == 5 ? Vpad : H) * 4;
+            KR_TRY(dmalloc(e->own_bufs, dst, bytes));
+            KR_HIP(hipMemset(*dst, 0, bytes));
+        }
+        KR_HIP(hipMemcpy(*dst, data, (size_t)numel * 4, hipMemcpyDefault));
+    }
+    if (!e->mlm_zero) {
+        KR_TRY(dmalloc(e->own_bufs, &e->mlm_zero, (size_t)H * 4));
+        KR_HIP(hipMemset(e->mlm_zero, 0, (size_t)H * 4));
+    }
+    if (!e->mlm_got) free_ws(e);              // row_seq exists with the head
+    e->mlm_got |= 1u << which;
     e->ready = false;
     return 0;
 }
@@ -909,6 +974,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     if (std::strcmp(hf_name, "dense.weight") == 0) return load_dense(e, data, numel);
     for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, CLS_NAMES[i]) == 0) return load_cls_head(e, i, data, numel);
     for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, M3_NAMES[i]) == 0) return load_m3_head(e, i, data, numel);
+    for (int i = 0; i < 6; ++i) if (std::strcmp(hf_name, MLM_NAMES[i]) == 0) return load_mlm_head(e, i, data, numel);
     int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
     KR_TRY(parse_name(e, hf_name, slot, want, fam, layer));
     // NomicBert's and ModernBert's names: q / k (rotary partners) and the gated projection's rows go into tile-pair order; T5's: wi_0 | wi_1 only
@@ -1062,6 +1128,22 @@ int enc_finalize(void* h) {
     if (!e->rel_w.empty() && fam_t5(e->rel_fam) != t5)
         return fail(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
                                   : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
+    // SPLADE's MLM head: on BERT / RoBERTa handles only, never next to another head, whole
+    if (e->mlm_got) {
+        int fi = 0;
+        while (!(e->mlm_got & (1u << fi))) ++fi;
+        const char* first = MLM_NAMES[fi];
+        const bool mpnet = !e->rel_w.empty() && !t5;
+        if (rot || modern || t5 || mpnet)
+            return fail(KR_EINVAL, "'%s' on a %s handle: the MLM head of SPLADE is BertForMaskedLM's and is accepted on BERT handles", first,
+                        t5 ? "T5" : modern ? "ModernBert" : rot ? "NomicBert" : "MPNet");
+        if (e->cls_got) return fail(KR_EINVAL, "'%s' next to 'classifier.*': a handle has the classification head or the MLM head", first);
+        if (e->dense_rows > 0) return fail(KR_EINVAL, "'%s' next to 'dense.weight': a handle has the Dense head or the MLM head", first);
+        if (e->col_got || e->sp_got)
+            return fail(KR_EINVAL, "'%s' next to '%s': a handle has bge-m3's token-level heads or the MLM head", first, e->col_got ? "colbert_linear.*" : "sparse_linear.*");
+        for (int i = 0; i < 6; ++i)
+            if (!(e->mlm_got & (1u << i))) return fail(KR_ESTATE, "'%s' was never loaded: the MLM head takes all six cls.predictions.* tensors or none", MLM_NAMES[i]);
+    }
     // bge-m3's heads: on BERT / RoBERTa handles only, never next to another head, each one whole (checked before the Dense head's own rule, so
     // that 'dense.weight' + a token-level head on a BERT handle is refused by both names)
     for (int hd = 0; hd < 2; ++hd) {
@@ -1180,6 +1262,7 @@ struct RowSet {
 
 // every kernel of one forward, enqueued on `st` (input already in the workspace, result left in e->out)
 // flags: KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT (pool is the base pool); tok_out: device memory for the token-level blocks, [B, S] then [B, S, P]
+// pool = KR_POOL_SPLADE: tok_out is the [B, vocab] result, used as the reduction buffer of the decoder launch; nothing is left in e->out
 static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, const Input& in, int flags = 0, float* tok_out = nullptr) {
     const int H = e->cfg.hidden, FF = e->cfg.intermediate;
     const float eps = e->cfg.ln_eps;
@@ -1188,6 +1271,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // the last LayerNorm only (k_pool's raw rows, then k_cls_head): everything up to there sees KR_POOL_CLS
     const bool classify = pool == KR_POOL_CLASSIFY;
     if (classify) pool = KR_POOL_CLS;
+    // KR_POOL_SPLADE packs and attends like KR_POOL_MEAN (no query-only rows) and differs behind the last LayerNorm only
+    const bool splade = pool == KR_POOL_SPLADE;
+    if (splade) pool = KR_POOL_MEAN;
     const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
     const bool long_seq = nqt_max > 4 && !e->kn.attn_lds;                          // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
     const int align = long_seq ? 8 : 4;                                            // sequence offsets: multiple of 8 tokens so that V^T chunks start 16-B aligned
@@ -1300,6 +1386,27 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
             KR_TRY(tail(a, l, last && shortcut ? cls_rows : all_rows, last));
         }
     }
+    if (splade) {
+        // t = LayerNorm(gelu(Wt x + bt)) of the packed rows: y <- EPI_GELU, q <- k_ln16_head (both buffers are free behind the last layer; xb / xlo keep the
+        // final hidden state for kr_encoder_last_hidden)
+        ProjArgs a{};
+        a.Tp = e->d_T; a.H = H; a.W = e->mlm_wt; a.X = e->xb; a.F = H; a.K = H; a.bias = e->mlm_bt; a.out0 = e->y;
+        KR_TRY(launch_proj(EPI_GELU, a, maxT, e, st));
+        KR_HIP(hipMemsetAsync(e->row_seq, 0xff, (size_t)e->capT * 4, st));
+        hipLaunchKernelGGL(k_splade_rowseq, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nk, e->row_seq);
+        auto head_ln = H <= 512 ? &k_ln16_head<1> : H <= 1024 ? &k_ln16_head<2> : &k_ln16_head<4>;
+        hipLaunchKernelGGL(head_ln, dim3(ln_grid), dim3(256), 0, st, e->y, e->mlm_zero, e->d_T, e->mlm_g, e->mlm_b, eps, H, e->row_seq, e->q, e->d_err);
+        // the decoder: [rows] x [Vpad, H]^T reduced over each sequence's rows inside the launch (EPI_SPLADE), then log1p in place
+        const int V = e->cfg.vocab;
+        KR_HIP(hipMemsetAsync(tok_out, 0, (size_t)B * V * 4, st));
+        a.W = e->mlm_wd; a.X = e->q; a.F = (int)mlm_vpad(e); a.bias = e->mlm_bd; a.out0 = nullptr;
+        a.row_seq = e->row_seq; a.smax = reinterpret_cast<unsigned int*>(tok_out); a.V = V;
+        KR_TRY(launch_proj(EPI_SPLADE, a, maxT, e, st));
+        const int64_t n = (int64_t)B * V;
+        hipLaunchKernelGGL(k_splade_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tok_out, n, e->d_err);
+        KR_HIP(hipGetLastError());
+        return 0;
+    }
     const RowSet& r = shortcut ? cls_rows : all_rows;
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
     hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool,
@@ -1411,9 +1518,13 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
     if (total_tokens > (int64_t)B * S) return fail(KR_EINVAL, "total_tokens %lld exceeds B * S = %lld", (long long)total_tokens, (long long)B * S);
     const int flags = pool & M3_FLAGS;
     pool &= ~M3_FLAGS;
-    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY)
-        return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls) or 2 (classify), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)");
+    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY && pool != KR_POOL_SPLADE)
+        return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls), 2 (classify) or 4 (splade), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)");
     if (flags && pool == KR_POOL_CLASSIFY) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 2 (classify)");
+    if (flags && pool == KR_POOL_SPLADE) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 4 (splade)");
+    if (pool == KR_POOL_SPLADE && !e->has_mlm())
+        return fail(KR_ESTATE, "pool = 4 (splade) on a handle without an MLM head: cls.predictions.transform.dense.{weight,bias}, cls.predictions.transform.LayerNorm.{weight,bias} "
+                               "and cls.predictions.decoder.{weight,bias} were never loaded");
     if (flags && total_tokens >= 0)
         return fail(KR_EINVAL, "kr_encoder_forward_packed takes no KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT: the token-level blocks are laid out by the columns of a padded batch");
     if ((flags & KR_POOL_WITH_SPARSE) && !e->has_sparse())
@@ -1443,8 +1554,9 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 // behind the kernels of a forward: the result and the error word travel to the caller
 // (tok_elems > 0: the token-level blocks of a flagged forward with a host `out` wait in e->tok_stage and follow the dense block)
 static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st, size_t tok_elems = 0) {
-    const size_t dense_elems = (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim());
-    KR_HIP(hipMemcpyAsync(out, e->out, dense_elems * 4, hipMemcpyDefault, st));
+    // (KR_POOL_SPLADE has no dense block: its [B, vocab] result is written to a device `out` by the kernels, or waits in e->tok_stage like a token-level block)
+    const size_t dense_elems = pool == KR_POOL_SPLADE ? 0 : (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim());
+    if (dense_elems) KR_HIP(hipMemcpyAsync(out, e->out, dense_elems * 4, hipMemcpyDefault, st));
     if (tok_elems) KR_HIP(hipMemcpyAsync(out + dense_elems, e->tok_stage, tok_elems * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;
     KR_HIP(hipMemcpyAsync(e->h_err, e->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1460,6 +1572,25 @@ static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStr
     return report_token_error(e, st);
 }
 
+// host-staging buffer of the token-level blocks / the SPLADE result: at least `elems` floats
+static int grow_tok_stage(Encoder* e, size_t elems) {
+    if (elems <= e->tok_stage_elems) return 0;
+    KR_HIP(hipStreamSynchronize(e->last_stream));      // an earlier staged copy may still read the old buffer
+    if (e->tok_stage) (void)hipFree(e->tok_stage);
+    e->tok_stage = nullptr; e->tok_stage_elems = 0;
+    KR_HIP(hipMalloc(reinterpret_cast<void**>(&e->tok_stage), elems * 4));
+    e->tok_stage_elems = elems;
+    return 0;
+}
+// where a KR_POOL_SPLADE forward reduces into: a device `out` is the reduction buffer itself (the kernels hold the caller's pointer: never replayed from a
+// captured graph), a host `out` is staged
+static int splade_target(Encoder* e, int B, float* out, float** red) {
+    if (is_device_pointer(out)) { *red = out; return 0; }
+    KR_TRY(grow_tok_stage(e, (size_t)B * e->cfg.vocab));
+    *red = e->tok_stage;
+    return 0;
+}
+
 int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids, int B, int S, int pool, float* out, void* stream) {
     Encoder* e = reinterpret_cast<Encoder*>(h);
     KR_TRY(check_forward_args(e, B < 0 || S <= 0 || (B > 0 && (!input_ids || !attention_mask || !out)), B, S, -1, pool));
@@ -1470,6 +1601,12 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     KR_HIP(hipMemcpyAsync(e->d_mask, attention_mask, (size_t)B * S * 8, hipMemcpyDefault, st));
     if (token_type_ids) KR_HIP(hipMemcpyAsync(e->d_tt, token_type_ids, (size_t)B * S * 8, hipMemcpyDefault, st));
     const int flags = pool & M3_FLAGS;
+    if (pool == KR_POOL_SPLADE) {
+        float* red = nullptr;
+        KR_TRY(splade_target(e, B, out, &red));
+        KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, 0, red));
+        return finish_forward(e, B, S, pool, out, st, red == out ? 0 : (size_t)B * e->cfg.vocab);
+    }
     if (!flags) {
         KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
         return finish_forward(e, B, S, pool, out, st);
@@ -1480,13 +1617,7 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     const size_t slots = (size_t)B * S;
     const size_t tok_elems = ((flags & KR_POOL_WITH_SPARSE) ? slots : 0) + ((flags & KR_POOL_WITH_COLBERT) ? slots * e->col_rows : 0);
     const bool direct = is_device_pointer(out);
-    if (!direct && tok_elems > e->tok_stage_elems) {
-        KR_HIP(hipStreamSynchronize(e->last_stream));      // an earlier staged copy may still read the old buffer
-        if (e->tok_stage) (void)hipFree(e->tok_stage);
-        e->tok_stage = nullptr; e->tok_stage_elems = 0;
-        KR_HIP(hipMalloc(reinterpret_cast<void**>(&e->tok_stage), tok_elems * 4));
-        e->tok_stage_elems = tok_elems;
-    }
+    if (!direct) KR_TRY(grow_tok_stage(e, tok_elems));
     KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, flags, direct ? out + (size_t)B * e->out_dim() : e->tok_stage));
     return finish_forward(e, B, S, pool, out, st, direct ? 0 : tok_elems);
 }
@@ -1500,8 +1631,10 @@ int enc_forward_packed(void* h, const int32_t* token_ids, const int32_t* seq_len
     KR_TRY(begin_forward(e, B, S, st));
     if (total_tokens > 0) KR_HIP(hipMemcpyAsync(e->rag_ids(), token_ids, (size_t)total_tokens * 4, hipMemcpyDefault, st));
     KR_HIP(hipMemcpyAsync(e->rag_lens(), seq_lens, (size_t)B * 4, hipMemcpyDefault, st));
-    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{true, false, (int)total_tokens}));
-    return finish_forward(e, B, S, pool, out, st);
+    float* red = nullptr;
+    if (pool == KR_POOL_SPLADE) KR_TRY(splade_target(e, B, out, &red));
+    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{true, false, (int)total_tokens}, 0, red));
+    return finish_forward(e, B, S, pool, out, st, red && red != out ? (size_t)B * e->cfg.vocab : 0);
 }
 
 int enc_check(void* h) {

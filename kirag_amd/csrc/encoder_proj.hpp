@@ -37,9 +37,11 @@ struct ProjArgs {
               // (small launches: the whole output fits in L2 / Infinity Cache, the next kernel reads it from there)
     // EPI_QKV_ROT (NomicBert handles): cos / sin tables [max_pos][dh / 2] fp32, the position every token row is rotated by (k_rot_pos), the head width (32 or 64)
     const float* rot_cos; const float* rot_sin; const int* tpos; int max_pos; int dh;
+    // EPI_SPLADE: the sequence of every packed row or -1 (k_splade_rowseq), the [B, V] reduction buffer (bit patterns, zero-initialised), V <= F real columns
+    const int* row_seq; unsigned int* smax; int V;
 };
 
-enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6, EPI_RELU = 7, EPI_GEGLU_TANH = 8 };
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6, EPI_RELU = 7, EPI_GEGLU_TANH = 8, EPI_SPLADE = 9 };
 constexpr bool epi_rotates(int epi) { return epi == EPI_QKV_ROT || epi == EPI_QKV_ROTB; }
 constexpr bool epi_gated(int epi) { return epi == EPI_SWIGLU || epi == EPI_GEGLU || epi == EPI_GEGLU_TANH; }   // F = 2 FF GEMM columns -> FF stored
 
@@ -242,6 +244,86 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
         }
 }
 
+// EPI_SPLADE (the MLM decoder of a SPLADE handle, KR_POOL_SPLADE): nothing is stored per token.  log1p(relu(.)) is monotone and the decoder's bias is constant per
+// column, so w[b, v] = log1p(max(0, bias[v] + max over the sequence's rows of acc[row, v])): the epilogue reduces the fp32 accumulators over the token rows of
+// each sequence and hands max(0, max + bias) to smax[b, v] by atomicMax on its BIT PATTERN — non-negative floats order like unsigned integers, a zeroed buffer
+// is the identity, a NaN (either sign) is larger than every finite value and so survives to k_splade_finish.  Max is exact and order-independent: the result
+// does not depend on the tiling, the batch or the order of the atomics.
+// In the exchanged layout a lane holds 16 features of ONE token row per (mi, ni) and lane & 31 is the row, so the reduction runs across the 32 lanes of a
+// half-wave.  row_seq[row] names the row's sequence (-1: an alignment row between two sequences, or a row >= T of a partial tile, computed from clamped
+// loads: such a row never enters a max).  Per 32-row block mi:
+//   all 32 rows in one sequence (the common case): when the next block belongs to the same sequence the block is folded into it in the registers (no
+//     cross-lane traffic); else every register is reduced over the half-wave (4 DPP steps + one cross-row shuffle) and lanes 0..15 of each half issue one
+//     atomicMax each per tile: 32 consecutive columns per instruction.  A zero is never sent (it is the identity): with a trained model most columns are.
+//   anything else (a sequence boundary or the end of the packed rows inside the block): every lane sends its own row's values.
+template <int CTRL>
+__device__ __forceinline__ float dpp_fmax(float x) {
+    const int xi = __builtin_bit_cast(int, x);
+    return fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, CTRL, 0xf, 0xf, false)));
+}
+// max over the 32 lanes of each half-wave, in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror (every group of 4 / 8 lanes is
+// uniform by then, so a mirror pairs it with its neighbour), then lanes l and l ^ 16.  fmaxf keeps a NaN only when both sides are NaN: a column of NaN
+// (a NaN in the weights) survives, a single NaN row is caught where it arises (k_ln16_head)
+__device__ __forceinline__ float half_wave_max(float x) {
+    x = dpp_fmax<0xB1>(x); x = dpp_fmax<0x4E>(x); x = dpp_fmax<0x141>(x); x = dpp_fmax<0x140>(x);
+    return fmaxf(x, __shfl_xor(x, 16, 64));
+}
+__device__ __forceinline__ unsigned int splade_key(float v) { return (v > 0.f || v != v) ? __builtin_bit_cast(unsigned int, v) : 0u; }
+
+template <class Shape>
+__device__ __forceinline__ void splade_reduce(const ProjArgs& a, AccTile<Shape>& acc, int64_t t0, int f0) {
+    const int c = acc.lane & 31, h = acc.lane >> 5;
+    int s[Shape::TM];
+#pragma unroll
+    for (int mi = 0; mi < Shape::TM; ++mi) s[mi] = a.row_seq[t0 + mi * 32 + c];
+#pragma unroll
+    for (int mi = 0; mi < Shape::TM; ++mi) {
+        const int sf = __builtin_amdgcn_readfirstlane(s[mi]);
+        if (__ballot(s[mi] != sf) == 0ull) {             // wave-uniform from here on: all 64 lanes are active in the DPP steps
+            if (sf < 0) continue;
+            if (mi + 1 < Shape::TM) {
+                const int mn = mi + 1 < Shape::TM ? mi + 1 : mi;      // (an index inside the array for the unrolled last block, where this branch is dead)
+                const int sn = __builtin_amdgcn_readfirstlane(s[mn]);
+                if (sn == sf && __ballot(s[mn] != sn) == 0ull) {
+#pragma unroll
+                    for (int ni = 0; ni < Shape::TN; ++ni)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc.v[mn][ni][r] = fmaxf(acc.v[mn][ni][r], acc.v[mi][ni][r]);
+                    continue;
+                }
+            }
+#pragma unroll
+            for (int ni = 0; ni < Shape::TN; ++ni) {
+                float m = 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float x = half_wave_max(acc.v[mi][ni][r]);
+                    if ((c & 15) == r) m = x;
+                }
+                const int f = f0 + ni * 32 + (c & 3) + 8 * ((c >> 2) & 3) + 4 * h;      // the feature of register c & 15
+                if (c < 16 && f < a.V) {
+                    const unsigned int key = splade_key(m + a.bias[f]);
+                    if (key) atomicMax(a.smax + (int64_t)sf * a.V + f, key);
+                }
+            }
+        } else if (s[mi] >= 0) {
+            unsigned int* dst = a.smax + (int64_t)s[mi] * a.V;
+#pragma unroll
+            for (int ni = 0; ni < Shape::TN; ++ni)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int f = f0 + ni * 32 + 8 * g + 4 * h;
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(a.bias + f);      // the bias is padded to F like the weight
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const unsigned int key = splade_key(acc.v[mi][ni][4 * g + i] + b[i]);
+                        if (key && f + i < a.V) atomicMax(dst + f + i, key);
+                    }
+                }
+        }
+    }
+}
+
 // persistent streaming projections (256x256 ping-pong or 128x128 streaming main loop).  rows = tokens, cols = output features; bias is
 // one value per lane and ni.  Token-indexed buffers are allocated in multiples of 256 rows, so a partial last token tile needs no bounds
 // test (rows >= T are written with values computed from clamped loads and never read).
@@ -256,6 +338,7 @@ __device__ __forceinline__ void store_transposed_bf16(AccTile<Shape>& acc, char*
 //   EPI_GEGLU:   F = 2 FF, input | gate interleaved the same way: out0[T, F / 2] = erf_gelu(input + b) * (gate + b') (ModernBert handles; bias in the rows' order)
 //   EPI_RELU:    out0[T,F] = max(acc, 0), no bias (T5 v1.0 handles: DenseReluDense.wi)
 //   EPI_GEGLU_TANH: F = 2 FF, wi_0 | wi_1 interleaved like EPI_GEGLU: out0[T, F / 2] = gelu_new(wi_0 x) * wi_1 x, no bias (T5 v1.1 / flan handles)
+//   EPI_SPLADE:  nothing stored per token: smax[seq, f] = max(smax, max(0, acc + bias)) over the rows of each sequence (splade_reduce)
 template <int EPI, class ShapeE, bool NT>
 __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>& acc, int64_t m0, int64_t n0, char* stage) {
     const int64_t t0 = m0 + acc.m_wave;
@@ -337,6 +420,8 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
     } else if constexpr (EPI == EPI_RELU) {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0,
                                     [&](f32x4 v, int, int, int) { return relu4(v); });
+    } else if constexpr (EPI == EPI_SPLADE) {
+        splade_reduce<ShapeE>(a, acc, t0, f0);
     } else {
         store_rows_bf16<ShapeE, NT>(acc, stage, a.out0, a.ldo, t0, f0, [&](f32x4 v, int mi, int ni, int g) {
             const f32x4 x = v + b[ni][g];
@@ -402,6 +487,10 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         },
         [&](AccTile<ShapeSkinny>& acc, int64_t t0, int64_t f0) {
         const int c = acc.lane & 31, h = acc.lane >> 5;
+        if constexpr (EPI == EPI_SPLADE) {
+            splade_reduce<ShapeSkinny>(a, acc, t0, (int)f0);
+            return;
+        }
         if constexpr (epi_gated(EPI)) {      // the tile's 16 features: 8-byte row stores of silu(gate) * up / erf_gelu(input) * gate / gelu_new(wi_0 x) * wi_1 x
 #pragma unroll
             for (int g = 0; g < 2; ++g) {

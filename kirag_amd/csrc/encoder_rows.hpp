@@ -720,6 +720,53 @@ __global__ __launch_bounds__(256) void k_m3_sparse(const uint16_t* __restrict__ 
     }
 }
 
+// SPLADE's MLM head (KR_POOL_SPLADE).  k_ln16_head: the transform LayerNorm, t = LayerNorm(y) of rows that already hold gelu(Wt x + bt) (EPI_GELU), no
+// residual: Ln16's row arithmetic with a zero residual ((y + 0) + 0 is y bit for bit; `zero` = H zeros in the place of the projection's bias), 16-bit out for
+// the decoder's MFMAs.  A row OF A SEQUENCE (row_seq >= 0: the alignment rows between two sequences hold whatever the attention left there, nobody reads them)
+// with a non-finite element raises the error word here: behind the decoder the max over a sequence would drop a lone NaN.
+template <int NS>
+__global__ __launch_bounds__(256) void k_ln16_head(const uint16_t* __restrict__ y, const float* __restrict__ zero, const int* __restrict__ Tp, const float* __restrict__ g,
+                                                   const float* __restrict__ bta, float eps, int H, const int* __restrict__ row_seq, uint16_t* __restrict__ out,
+                                                   int* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int T = *Tp;
+    Ln16<NS> ln;
+    ln.load_params(g, bta, zero, H, lane);
+    const int64_t step = (int64_t)gridDim.x * 4;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < T; t += step) {
+        uint4 a[NS], rh[NS]; uint2 rl[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int i = lane * 8 + j * 512;
+            a[j] = rh[j] = make_uint4(0u, 0u, 0u, 0u); rl[j] = make_uint2(0x80808080u, 0x80808080u);      // byte 128 = a zero low half
+            if (i < H) a[j] = *reinterpret_cast<const uint4*>(y + t * H + i);
+        }
+        float v[NS][8];
+        ln.combine(a, rh, rl, v);
+        float chk = 0.f;
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) chk += v[j][c] * 0.f;      // 0 for finite elements, NaN for NaN / Inf
+        if (__ballot(chk != chk) != 0ull && lane == 0 && row_seq[t] >= 0) atomicOr(err, 2);
+        ln.template normalize_store<false>(v, H, eps, lane, out + t * H, nullptr);
+    }
+}
+// row_seq[row] = b for the nk[b] attended rows of sequence b (the buffer was filled with -1: alignment rows and everything behind the packed rows stay -1)
+__global__ __launch_bounds__(64) void k_splade_rowseq(const int* __restrict__ seq_off, const int* __restrict__ seq_nk, int* __restrict__ row_seq) {
+    const int b = blockIdx.x, off = seq_off[b], n = seq_nk[b];
+    for (int i = threadIdx.x; i < n; i += 64) row_seq[off + i] = b;
+}
+// in place over the [B, V] reduction buffer: the bit pattern of m = max(0, bias + max over the rows) -> w = log1p(m); a sequence without attended rows kept its
+// zeros: +0.0.  A non-finite m (NaN / Inf weights) is passed on and raises the error word: KR_ERANGE, like a non-finite embedding (k_pool)
+__global__ __launch_bounds__(256) void k_splade_finish(float* __restrict__ w, int64_t n, int* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float m = w[i];
+    if (!(m < INFINITY)) { atomicOr(err, 2); return; }
+    if (m != 0.f) w[i] = log1pf(m);
+}
+
 // CLS shortcut: row seq_off[b] + seq_cls[b] of ctx / the residual stream (hi, lo) -> row b of the compact buffers; also the compact "sequence" tables
 // (one token per sequence) and the row count for the B-row kernels that follow
 __global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__ ctx, const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,

@@ -49,6 +49,9 @@ added in every layer — on unscaled scores ``q.k + bias``, no linear bias anywh
 bge-m3's token-level heads (``colbert_linear`` / ``sparse_linear`` on BERT / RoBERTa handles): ``POOL_WITH_SPARSE`` / ``POOL_WITH_COLBERT`` ORed onto pool 0 / 1
 make ``HipBertForward.forward`` / ``forward_np`` return ``(dense [B, H], sparse [B, S] or None, colbert [B, S, P] or None)``, three views into the one tensor
 the library wrote (``_layout``); the twins with the heads and the scoring on top of them live in ``kirag_amd.retriever.m3``.
+
+SPLADE (``POOL_SPLADE`` on a BERT handle that was given ``cls.predictions.*``): the forward returns ``[B, vocab_size]``; the ``BertForMaskedLM`` twin and
+``SpladeModel`` live in ``kirag_amd.retriever.splade``.
 """
 from __future__ import annotations
 
@@ -70,6 +73,7 @@ CLASSIFIER_OUT = "classifier.out_proj.weight"    # [num_labels, hidden]: its row
 # bge-m3's token-level heads: flag bits ORed onto POOL_MEAN / POOL_CLS (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT).  A flagged forward returns the three
 # blocks of its one output tensor (HipBertForward._blocks): dense [B, hidden], sparse [B, S] or None, colbert [B, S, P] or None
 POOL_WITH_SPARSE, POOL_WITH_COLBERT = 0x10, 0x20
+POOL_SPLADE = _lib.POOL_SPLADE  # KR_POOL_SPLADE: log1p(relu(MLM logits)) max-pooled over the attended tokens, [B, vocab_size] (kirag_amd.retriever.splade)
 POOL_M3_FLAGS = POOL_WITH_SPARSE | POOL_WITH_COLBERT
 COLBERT_WEIGHT = "colbert_linear.weight"         # [P, hidden]: its rows are the width of a token vector
 COLBERT_MIN, COLBERT_MAX, COLBERT_STEP = 128, 2048, 128      # the library's rule for P (kirag_amd.h)
@@ -127,13 +131,16 @@ def pad_modernbert_ff(name: str, w, ff: int, ff_pad: int):
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
 
-    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None):
+    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None):
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
         low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it).
         ``rename``: optional callable, parameter name of the module -> the name the library knows (``sync`` / ``load_state`` apply it to every name; a
-        task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``)."""
+        task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``).
+        ``extra``: optional callable, module -> [(library name, tensor)] that ``sync`` sends besides ``named_parameters()`` unless a parameter already has
+        that name (a TIED parameter appears once in ``named_parameters()``; the library wants it under both names: ``kirag_amd.retriever.splade``)."""
         lib = _lib.load()
         self.rename = rename
+        self.extra = extra
         self.colbert_dim = 0              # rows of "colbert_linear.weight" once the library has accepted it: the width of a token vector
         self.num_labels = 0               # rows of "classifier.out_proj.weight" once the library has accepted it: the width of a POOL_CLASSIFY forward
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
@@ -170,6 +177,7 @@ class HipBertForward:
         self.operand_dtype = ("bf16", "f16")[lib.kr_encoder_operand_dtype(h)]
         self.residual_lo = bool(lib.kr_encoder_residual_lo(h))
         self.hidden = t5["hidden"] if self.is_t5 else config.hidden_size
+        self.vocab = int(config.vocab_size)      # the width of a POOL_SPLADE forward
         self.out_dim = self.hidden        # width of the embeddings: P once a Dense head ("dense.weight" [P, hidden], T5 handles) has been loaded
         self.fingerprint = None
         # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P.  It travels through the
@@ -307,6 +315,9 @@ class HipBertForward:
         params = [(n, p) for n, p in module.named_parameters() if not n.startswith("pooler.")]
         if self.rename is not None:
             params = [(self.rename(n), p) for n, p in params]
+        if self.extra is not None:
+            have = {n for n, _ in params}
+            params += [(n, p) for n, p in self.extra(module) if n not in have]
         fp = tuple((p.data_ptr(), p._version) for _, p in params)
         self._plist, self._versions, self._ptrs, self._since_full = params, tuple(v for _, v in fp), tuple(q for q, _ in fp), 0
         if fp == self.fingerprint:
@@ -332,8 +343,8 @@ class HipBertForward:
             self.colbert_dim = int(numel) // self.hidden
 
     def _width(self, pool: int) -> int:
-        """columns of an unflagged forward's output: the logits of ``POOL_CLASSIFY``, else the embedding"""
-        return self.num_labels if pool == POOL_CLASSIFY else self.out_dim
+        """columns of an unflagged forward's output: the logits of ``POOL_CLASSIFY``, the vocabulary of ``POOL_SPLADE``, else the embedding"""
+        return self.num_labels if pool == POOL_CLASSIFY else self.vocab if pool == POOL_SPLADE else self.out_dim
 
     def _layout(self, pool: int, B: int, S: int):
         """The blocks of a forward's ONE output tensor as (elements, shape) per block, in the library's order: dense, then with ``POOL_WITH_SPARSE`` [B, S],
@@ -499,6 +510,7 @@ class _HipModuleMixin:
     ``train()`` / ``eval()`` transitions, ``load_state_dict`` and ``_apply``."""
     _pool = POOL_MEAN
     _hip_rename = None               # HipBertForward's ``rename``: None = the parameter names are the library's
+    _hip_extra = None                # HipBertForward's ``extra``: None = named_parameters() is everything the library needs
     accepts_host_inputs = True       # eval forward takes the collator's CPU tensors and uploads them itself (DenseRetriever skips its to_device)
 
     def _synced_hip(self) -> HipBertForward:
@@ -510,7 +522,7 @@ class _HipModuleMixin:
                 "Move the model to a GPU (kirag_amd has no CPU fallback).")
         idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
         if self._hip is None or self._hip.device_index != idx:
-            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename)
+            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename, extra=type(self)._hip_extra)
         self._hip.sync(self)
         return self._hip
 

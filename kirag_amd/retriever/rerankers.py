@@ -27,6 +27,7 @@ from transformers.modeling_outputs import SequenceClassifierOutput
 from ..collators import RerankerCollator
 from .encoders import _CONFIG_KWARGS, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
 from .m3 import BGEM3Model
+from .splade import SpladeModel
 
 MAX_LABELS = 64          # the library's bound on the rows of classifier.out_proj (include/kirag_amd.h)
 
@@ -110,7 +111,8 @@ RERANKER_MAP = {"BGEReranker": BGEReranker}
 # second stages that are no cross-encoder, reached through load_reranker under these names.  "BGEM3": hybrid dense + sparse + multi-vector scoring with the
 # retriever's own bge-m3 checkpoint (kirag_amd.retriever.m3), no second model in HBM.  Kept apart from RERANKER_MAP: that map lists the models
 # BaseReranker.score() can drive (a forward that returns logits), which a BGEM3Model is not.
-HYBRID_RERANKER_MAP = {"BGEM3": BGEM3Model}
+# "SPLADE": learned sparse scoring with a BertForMaskedLM checkpoint (kirag_amd.retriever.splade), the dot product of two vocabulary-sized vectors.
+HYBRID_RERANKER_MAP = {"BGEM3": BGEM3Model, "SPLADE": SpladeModel}
 
 
 def load_reranker(reranker_name, model_name_or_path, **kwargs):

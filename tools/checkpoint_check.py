@@ -35,6 +35,10 @@ A bge-m3 folder (colbert_linear.pt and / or sparse_linear.pt next to the backbon
 only, and the report is, against HF fp32 + the two heads in torch, the worst per-token 1 - cos of the multi-vector block and the worst |weight difference| of the
 sparse block over the built-in texts, for the four precision modes.
 
+A masked-LM checkpoint (config.json names BertForMaskedLM: the SPLADE models) is loaded as its SPLADE twin (kirag_amd.retriever.splade), GPU only, and the
+report is the worst |w - w_ref| over all [sequences, vocab] weights against HF fp32 logits + log1p(relu(.)) max-pooled over the attended tokens in fp64, for the
+four precision modes, next to the reference's share of exact zeros and its largest weight.
+
 Texts: --texts (one per line; the first half are used as queries, the rest as passages, E5 prefixes added) needs the checkpoint's tokenizer; without a
 tokenizer in the directory (or with --random-tokens) seeded random token ids of ragged lengths are used."""
 import argparse
@@ -256,6 +260,52 @@ def check_reranker(hf_dir, args):
     return out
 
 
+def check_splade(hf_dir, args):
+    """worst |w - w_ref| of a BertForMaskedLM folder against HF fp32 logits + the SPLADE formula in fp64, per precision mode"""
+    from kirag_amd.retriever.encoders import POOL_SPLADE, HipBertForward
+    from kirag_amd.retriever.splade import BertSpladeEncoder
+    if not torch.cuda.is_available() or args.emulate:
+        raise SystemExit(f"{hf_dir}: a masked-LM checkpoint is checked on the GPU (the torch emulation has no MLM head)")
+    model = BertSpladeEncoder.from_pretrained(hf_dir).float().eval().to("cuda:0")
+    cfg = model.config
+    batches = load_inputs(args, hf_dir, cfg.vocab_size)
+    refs = []
+    with torch.no_grad():
+        for ids, mask in batches:
+            k = torch.from_numpy(mask).to("cuda:0")
+            rows = []
+            for b in range(len(ids)):          # one sequence at a time: [S, vocab] fp64 logits, never [B, S, vocab]
+                lg = model._hf_base.forward(model, input_ids=torch.from_numpy(ids[b:b + 1]).to("cuda:0"), attention_mask=k[b:b + 1]).logits[0].double()
+                w = torch.log1p(torch.relu(lg))[k[b] != 0]
+                rows.append(w.max(dim=0).values if len(w) else torch.zeros(cfg.vocab_size, dtype=torch.float64, device=lg.device))
+            refs.append(torch.stack(rows).cpu().numpy())
+    allref = np.concatenate(refs)
+    print(f"# {hf_dir}: {type(model).__name__}, {cfg.num_hidden_layers} layers, hidden {cfg.hidden_size}, vocab {cfg.vocab_size}; {len(allref)} sequences; "
+          f"HF fp32 weights: {float((allref == 0).mean()):.1%} exact zeros, largest {allref.max():.3f}")
+    results = []
+    for dtype, lo in MODES:
+        h = HipBertForward(cfg, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename, extra=type(model)._hip_extra)
+        h.sync(model)
+        err, finite = 0.0, True
+        for (ids, mask), ref in zip(batches, refs):
+            try:
+                out = h.forward_np(ids, mask, POOL_SPLADE).astype(np.float64)
+            except Exception as e:      # noqa: BLE001 — KR_ERANGE: non-finite activations
+                print(f"  {dtype:4s}: {e}", file=sys.stderr)
+                finite = False
+                continue
+            finite = finite and bool(np.isfinite(out).all())
+            err = max(err, float(np.abs(out - ref).max()))
+        results.append({"operand_dtype": dtype, "residual_lo": lo, "worst_weight_error": err if finite else float("inf"), "finite": finite})
+        print(f"  {dtype:4s} {'+ low half' if lo else '          '}  worst |w - HF fp32| = {err:.2e}" + ("" if finite else "   NON-FINITE OUTPUT"))
+    out = {"checkpoint": hf_dir, "tested_path": "hip", "kind": "splade", "sequences": int(len(allref)), "reference_zero_share": float((allref == 0).mean()),
+           "reference_largest_weight": float(allref.max()), "modes": results}
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
 def check_m3(hf_dir, args):
     """worst per-token 1 - cos (colbert block) and worst |dw| (sparse block) of a bge-m3 folder against HF fp32 + torch heads, per precision mode"""
     from kirag_amd.retriever.encoders import POOL_CLS, POOL_WITH_COLBERT, POOL_WITH_SPARSE, HipBertForward
@@ -307,6 +357,8 @@ def check(hf_dir, args):
     cfg = AutoConfig.from_pretrained(hf_dir)
     if os.path.isdir(hf_dir) and (os.path.exists(os.path.join(hf_dir, "colbert_linear.pt")) or os.path.exists(os.path.join(hf_dir, "sparse_linear.pt"))):
         return check_m3(hf_dir, args)
+    if any(a.endswith("ForMaskedLM") or a == "BertSpladeEncoder" for a in (getattr(cfg, "architectures", None) or [])):      # (the twin's save_pretrained writes its own name)
+        return check_splade(hf_dir, args)
     if any(a.endswith("ForSequenceClassification") for a in (getattr(cfg, "architectures", None) or [])):
         return check_reranker(hf_dir, args)
     from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
