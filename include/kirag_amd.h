@@ -360,6 +360,23 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   kr_encoder_finalize refuses it (KR_EINVAL, naming it) on NomicBert, ModernBert and T5 handles — their classification heads are other functions — and next
  *   to "dense.weight".  BertForSequenceClassification's spelling of the same arithmetic (pooler.dense.* -> tanh -> classifier.{weight,bias}) is mapped onto
  *   these names by the Python layer (kirag_amd.retriever.rerankers.BertReranker); the library itself keeps ignoring "pooler.*".
+ * ModernBertForSequenceClassification (Alibaba-NLP/gte-reranker-modernbert-base, ibm-granite/granite-embedding-reranker-english-r2, CrossEncoder fine-tunes of
+ * answerdotai/ModernBERT-*): on ModernBert handles the head travels under HF's own names, fp32,
+ *   "head.dense.weight" [hidden, hidden], "head.norm.weight" [hidden], "classifier.weight" [L, hidden], "classifier.bias" [L], 1 <= L <= 64: together or not at
+ *   all (a partial set fails kr_encoder_finalize with KR_ESTATE as "never loaded", naming the missing tensor); "head.dense.bias" [hidden] (classifier_bias) and
+ *   "head.norm.bias" [hidden] (norm_bias): optional, zero unless loaded.  L outside 1 .. 64, a "classifier.weight" count that is no multiple of hidden or a
+ *   "classifier.bias" count other than L is KR_EINVAL at load.  With the head, KR_POOL_CLASSIFY writes out [B, L] fp32,
+ *       logits = classifier.weight . LayerNorm_{ln_eps}(erf_gelu(head.dense.weight . x + head.dense.bias)) + classifier.bias     (head.norm's weight and bias),
+ *   raw logits in fp32 arithmetic that do not depend on the batch around a sequence, its slot or the entry point.
+ *   "config.classifier_pooling": data = ONE float selecting x: 0 (the default) = last_hidden[:, 0], the forward of KR_POOL_CLS up to the pooled row; 1 = the
+ *   masked mean, the forward of KR_POOL_MEAN up to the pooled row (kr_encoder_forward_packed then packs without a CLS query row); x is NOT normalised.  Any
+ *   other number is KR_EINVAL.  Accepted before the first finalize; later the same value is a no-op and another value is KR_EINVAL.  kr_encoder_finalize
+ *   refuses it (KR_EINVAL, naming it) on a handle without this head or of another kind.
+ *   An all-masked sequence gives a NaN row; a non-finite pooled row or logit of a sequence with attended tokens is KR_ERANGE.  Pools 0 and 1 write the
+ *   [B, hidden] rows of a handle without the head.  The rule of "classifier.*" above holds: fixed at the first finalize — the same L takes new values, another
+ *   L or a head arriving on a handle finalized without one is KR_EINVAL.  KR_POOL_CLASSIFY without the head is KR_ESTATE, naming the four required tensors.
+ *   kr_encoder_finalize refuses these six names (KR_EINVAL, naming the tensor) on a handle of any other kind; RobertaClassificationHead's four names stay
+ *   refused on ModernBert handles.
  * BAAI/bge-m3's sparse and multi-vector heads (an XLM-R backbone; the same two Linear modules on a BERT backbone are accepted too), fp32:
  *   "colbert_linear.weight" [P, hidden], "colbert_linear.bias" [P]: P % 128 == 0 and 128 <= P <= 2048, any other count is KR_EINVAL;
  *   "sparse_linear.weight" [1, hidden], "sparse_linear.bias" [1].

@@ -32,6 +32,8 @@
 //
 // Sequence classification (cross-encoder rerankers, KR_POOL_CLASSIFY): BERT / RoBERTa handles with the four "classifier.*" tensors run CLS pooling's forward up
 // to the last LayerNorm, then k_pool<.., RAW> (the un-normalised CLS row) and k_cls_head: out [B, L] = Wo . tanh(Wd . x + bd) + bo, raw logits.
+// ModernBert handles with "head.dense.*" / "head.norm.*" / "classifier.{weight,bias}" (ModernBertForSequenceClassification): x = the raw CLS row or, with
+// config.classifier_pooling = 1, the raw masked mean (the forward of KR_POOL_MEAN), and k_cls_head<.., true>: Wo . LayerNorm(erf_gelu(Wd . x + bd)) + bo.
 //
 // bge-m3's token-level heads (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT on BERT / RoBERTa handles with "sparse_linear.*" / "colbert_linear.*"): a flagged forward
 // runs its last layer on every row; behind the pooling k_m3_slots maps the [B, S] columns to packed rows, k_m3_sparse writes max(0, w . x + b) per column, and
@@ -85,6 +87,8 @@ struct Knobs {
         attn_lds = getenv("KIRAG_AMD_ATTN_LDS") != nullptr;
     }
 };
+
+enum { MH_DW = 1, MH_DB = 2, MH_NW = 4, MH_NB = 8, MH_CW = 16, MH_CB = 32, MH_REQUIRED = MH_DW | MH_NW | MH_CW | MH_CB };
 
 struct Encoder {
     kr_bert_cfg cfg{};
@@ -147,8 +151,16 @@ struct Encoder {
     // the rows of out_proj (0: none yet); cls_got: one bit per tensor (CLS_*), all four or none at finalize; with it `pooled` holds the head's input
     float *cls_wd = nullptr, *cls_bd = nullptr, *cls_wo = nullptr, *cls_bo = nullptr;
     int cls_labels = 0; unsigned cls_got = 0;
-    bool has_head() const { return cls_got == 15u; }
-    int out_width() const { return std::max(out_dim(), cls_labels); }      // what a row of `out` must hold, whatever the pool
+    // ModernBert's head (MH_NAMES, one bit of mh_got each): "head.dense.{weight,bias}" [H, H] / [H], "head.norm.{weight,bias}" [H], "classifier.{weight,bias}"
+    // [L, H] / [L]; the two head.*.bias are optional (zero unless loaded), the other four come together or not at all.  mh_labels = L (0: none yet).
+    // cls_pooling: "config.classifier_pooling", -1 = never set (the [CLS] row), 0 = the [CLS] row, 1 = the masked mean
+    float *mh_wd = nullptr, *mh_bd = nullptr, *mh_g = nullptr, *mh_b = nullptr, *mh_wo = nullptr, *mh_bo = nullptr;
+    int mh_labels = 0; unsigned mh_got = 0; int cls_pooling = -1;
+    bool has_tanh_head() const { return cls_got == 15u; }
+    bool has_modern_head() const { return (mh_got & MH_REQUIRED) == MH_REQUIRED; }
+    bool has_head() const { return has_tanh_head() || has_modern_head(); }
+    int head_labels() const { return std::max(cls_labels, mh_labels); }    // a finalized handle holds one of the two heads
+    int out_width() const { return std::max(out_dim(), head_labels()); }   // what a row of `out` must hold, whatever the pool
     // bge-m3's heads.  "colbert_linear.{weight,bias}": col_w = the 16-bit copy [P, H] the projection loops read, col_b fp32 [P], col_rows = P (0: none yet).
     // "sparse_linear.{weight,bias}": sp_w fp32 [H], sp_b fp32 [1].  *_got: bit 1 = weight, bit 2 = bias; a head is both or nothing at finalize.
     // cy: the colbert product of the packed rows [capT, P] (16-bit, EPI_DENSE); slot_row: packed row of every [b, s] column or -1 (k_m3_slots);
@@ -243,7 +255,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_rpos, capT * 4)); KR_HIP(hipMemset(e->tok_rpos, 0, (size_t)capT * 4));
     }
     KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * e->out_width() * 4));
-    if (e->dense_rows > 0 || e->cls_got) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
+    if (e->dense_rows > 0 || e->cls_got || e->mh_got) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
     if (e->col_got || e->sp_got) KR_TRY(dmalloc(e->ws_bufs, &e->slot_row, capBS * 4));
     if (e->mlm_got) KR_TRY(dmalloc(e->ws_bufs, &e->row_seq, capT * 4));
     if (e->col_rows > 0) KR_TRY(dmalloc(e->ws_bufs, &e->cy, capT * e->col_rows * 2));      // capT rows: the projection's tiles are whole (see k_proj)
@@ -727,9 +739,26 @@ static int set_config(Encoder* e, const char* name, const float* data, int64_t n
         e->ready = false;
         return 0;
     }
+    if (std::strcmp(name, "config.classifier_pooling") == 0) {
+        // the row ModernBert's classification head reads: 0 = the [CLS] row (the default), 1 = the masked mean.  Under the rule of the other settings; that the
+        // handle is a ModernBert handle with that head is enc_finalize's business
+        if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
+        float v = -1.f;
+        KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
+        if (v != 0.f && v != 1.f) return fail(KR_EINVAL, "%s = %g: expected 0 ([CLS] row) or 1 (masked mean)", name, (double)v);
+        if (e->finalized_once) {
+            if (!e->has_modern_head())
+                return fail(KR_EINVAL, "%s after kr_encoder_finalize: the handle was finalized without ModernBert's classification head (head.dense / head.norm / classifier)", name);
+            if ((int)v == std::max(e->cls_pooling, 0)) return 0;
+            return fail(KR_EINVAL, "%s = %d after kr_encoder_finalize: the row the classification head reads is fixed (it has %d)", name, (int)v, std::max(e->cls_pooling, 0));
+        }
+        e->cls_pooling = (int)v;
+        e->ready = false;
+        return 0;
+    }
     if (std::strcmp(name, "config.position_padding_idx") != 0)
         return fail(KR_EINVAL, "unknown setting '%s' (known: config.position_padding_idx, config.rotary_inv_freq, config.rotary_inv_freq_local, "
-                               "config.attention_half_window, config.local_attention_layers, config.t5_feed_forward)", name);
+                               "config.attention_half_window, config.local_attention_layers, config.t5_feed_forward, config.classifier_pooling)", name);
     if (numel != 1) return fail(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel);
     float v = 0.f;
     KR_HIP(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
@@ -850,10 +879,10 @@ static int load_cls_head(Encoder* e, int which, const float* data, int64_t numel
         L = bit == CLS_OW ? numel / H : numel;
         if (numel <= 0 || (bit == CLS_OW && numel % H != 0) || L < 1 || L > CLS_MAX_LABELS)
             return fail(KR_EINVAL, "'%s' has %lld elements: expected %s with 1 <= L <= %d", name, (long long)numel, bit == CLS_OW ? "[L, hidden]" : "[L]", (int)CLS_MAX_LABELS);
-        if (e->finalized_once && e->has_head() && e->cls_labels != (int)L)
+        if (e->finalized_once && e->has_tanh_head() && e->cls_labels != (int)L)
             return fail(KR_EINVAL, "'%s' with L = %d after kr_encoder_finalize: the handle's classification head is fixed (it has L = %d)", name, (int)L, e->cls_labels);
     }
-    if (e->finalized_once && !e->has_head())
+    if (e->finalized_once && !e->has_tanh_head())
         return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a classification head", name);
     if (e->cls_labels && e->cls_labels != (int)L) return fail(KR_EINVAL, "'%s' with L = %d: the handle already holds an out_proj tensor with L = %d", name, (int)L, e->cls_labels);
     float** dst = bit == CLS_DW ? &e->cls_wd : bit == CLS_DB ? &e->cls_bd : bit == CLS_OW ? &e->cls_wo : &e->cls_bo;
@@ -862,6 +891,39 @@ static int load_cls_head(Encoder* e, int which, const float* data, int64_t numel
     if (e->cls_labels != (int)L || !e->cls_got) free_ws(e);      // e->out is sized by the widest row, `pooled` exists with the head
     e->cls_labels = (int)L;
     e->cls_got |= bit;
+    e->ready = false;
+    return 0;
+}
+
+// ModernBertForSequenceClassification's head under HF's own names: "head.dense.{weight,bias}" [H, H] / [H], "head.norm.{weight,bias}" [H] and
+// "classifier.{weight,bias}" [L, H] / [L], 1 <= L <= 64.  The rule of "classifier.{dense,out_proj}.*": L is fixed by the first of the two classifier tensors,
+// and the head belongs to the handle from its first finalize on — later the same shapes take new values, another L, or any of the six on a handle finalized
+// without the head, is refused.  (That the handle is a ModernBert handle is enc_finalize's business.)
+static const char* const MH_NAMES[6] = {"head.dense.weight", "head.dense.bias", "head.norm.weight", "head.norm.bias", "classifier.weight", "classifier.bias"};
+static int load_modern_head(Encoder* e, int which, const float* data, int64_t numel) {
+    const char* name = MH_NAMES[which];
+    const unsigned bit = 1u << which;
+    const int64_t H = e->cfg.hidden;
+    int64_t L = e->mh_labels;
+    if (bit != MH_CW && bit != MH_CB) {
+        const int64_t want = bit == MH_DW ? H * H : H;
+        if (numel != want) return fail(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)want);
+    } else {
+        L = bit == MH_CW ? numel / H : numel;
+        if (numel <= 0 || (bit == MH_CW && numel % H != 0) || L < 1 || L > CLS_MAX_LABELS)
+            return fail(KR_EINVAL, "'%s' has %lld elements: expected %s with 1 <= L <= %d", name, (long long)numel, bit == MH_CW ? "[L, hidden]" : "[L]", (int)CLS_MAX_LABELS);
+        if (e->finalized_once && e->has_modern_head() && e->mh_labels != (int)L)
+            return fail(KR_EINVAL, "'%s' with L = %d after kr_encoder_finalize: the handle's classification head is fixed (it has L = %d)", name, (int)L, e->mh_labels);
+    }
+    if (e->finalized_once && !e->has_modern_head())
+        return fail(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without ModernBert's classification head", name);
+    if (e->mh_labels && e->mh_labels != (int)L) return fail(KR_EINVAL, "'%s' with L = %d: the handle already holds a classifier tensor with L = %d", name, (int)L, e->mh_labels);
+    float** dst = bit == MH_DW ? &e->mh_wd : bit == MH_DB ? &e->mh_bd : bit == MH_NW ? &e->mh_g : bit == MH_NB ? &e->mh_b : bit == MH_CW ? &e->mh_wo : &e->mh_bo;
+    if (!*dst) KR_TRY(dmalloc(e->own_bufs, dst, (size_t)numel * 4));
+    KR_HIP(hipMemcpy(*dst, data, (size_t)numel * 4, hipMemcpyDefault));
+    if (e->mh_labels != (int)L || !e->mh_got) free_ws(e);        // e->out is sized by the widest row, `pooled` exists with the head
+    e->mh_labels = (int)L;
+    e->mh_got |= bit;
     e->ready = false;
     return 0;
 }
@@ -973,6 +1035,7 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     if (std::strncmp(hf_name, "config.", 7) == 0) return set_config(e, hf_name, data, numel);
     if (std::strcmp(hf_name, "dense.weight") == 0) return load_dense(e, data, numel);
     for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, CLS_NAMES[i]) == 0) return load_cls_head(e, i, data, numel);
+    for (int i = 0; i < 6; ++i) if (std::strcmp(hf_name, MH_NAMES[i]) == 0) return load_modern_head(e, i, data, numel);
     for (int i = 0; i < 4; ++i) if (std::strcmp(hf_name, M3_NAMES[i]) == 0) return load_m3_head(e, i, data, numel);
     for (int i = 0; i < 6; ++i) if (std::strcmp(hf_name, MLM_NAMES[i]) == 0) return load_mlm_head(e, i, data, numel);
     int slot = -1, fam = FAM_BERT, layer = -1; int64_t want = 0;
@@ -1169,6 +1232,22 @@ int enc_finalize(void* h) {
         for (int i = 0; i < 4; ++i)
             if (!(e->cls_got & (1u << i))) return fail(KR_ESTATE, "'%s' was never loaded: the classification head takes all four classifier.* tensors or none", CLS_NAMES[i]);
     }
+    // ModernBert's classification head: on ModernBert handles only (a refusal names the first of its tensors that was loaded), its four required tensors
+    // together; the pooling setting goes with that head
+    if (e->mh_got) {
+        int fi = 0;
+        while (!(e->mh_got & (1u << fi))) ++fi;
+        if (!modern)
+            return fail(KR_EINVAL, "'%s' on a handle without config.local_attention_layers: the head classifier . LayerNorm(gelu(head.dense . x)) is "
+                                   "ModernBertForSequenceClassification's and is accepted on ModernBert handles", MH_NAMES[fi]);
+        for (int i = 0; i < 6; ++i)
+            if ((MH_REQUIRED & (1u << i)) && !(e->mh_got & (1u << i)))
+                return fail(KR_ESTATE, "'%s' was never loaded: ModernBert's classification head takes head.dense.weight, head.norm.weight, classifier.weight and "
+                                       "classifier.bias together or none of them", MH_NAMES[i]);
+    }
+    if (e->cls_pooling >= 0 && !(modern && e->mh_got))
+        return fail(KR_EINVAL, "config.classifier_pooling on a %s: it selects the row ModernBert's classification head reads",
+                    modern ? "ModernBert handle without head.dense / head.norm / classifier" : "handle that is no ModernBert handle");
     if (t5) {
         for (int li = 0; li < e->cfg.layers; ++li) {
             const uint8_t* g = &e->got[T_LAYER0 + (size_t)li * L_COUNT];
@@ -1211,6 +1290,10 @@ int enc_finalize(void* h) {
     if (e->stage) { (void)hipFree(e->stage); e->stage = nullptr; e->stage_elems = 0; }
     KR_TRY(select_device(e->device));
     const int H = e->cfg.hidden;
+    if (e->mh_got) {      // head.dense.bias / head.norm.bias are zero unless loaded (classifier_bias / norm_bias false)
+        for (float** b : {&e->mh_bd, &e->mh_b})
+            if (!*b) { KR_TRY(dmalloc(e->own_bufs, b, (size_t)H * 4)); KR_HIP(hipMemset(*b, 0, (size_t)H * 4)); }
+    }
     if (rot) {
         if (modern && !e->got[T_ELNB]) KR_HIP(hipMemset(e->elnb, 0, (size_t)H * 4));
         for (int li = 0; li < e->cfg.layers; ++li) {
@@ -1269,8 +1352,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     e->kn.read();
     // KR_POOL_CLASSIFY reads the CLS row like KR_POOL_CLS — the query row of a masked column 0, the packed token count, the CLS shortcut — and differs behind
     // the last LayerNorm only (k_pool's raw rows, then k_cls_head): everything up to there sees KR_POOL_CLS
-    const bool classify = pool == KR_POOL_CLASSIFY;
-    if (classify) pool = KR_POOL_CLS;
+    // (ModernBert's head with config.classifier_pooling = 1 reads the masked mean: everything up to the last LayerNorm sees KR_POOL_MEAN)
+    const bool classify = pool == KR_POOL_CLASSIFY, modern_head = classify && e->has_modern_head();
+    if (classify) pool = modern_head && e->cls_pooling == 1 ? KR_POOL_MEAN : KR_POOL_CLS;
     // KR_POOL_SPLADE packs and attends like KR_POOL_MEAN (no query-only rows) and differs behind the last LayerNorm only
     const bool splade = pool == KR_POOL_SPLADE;
     if (splade) pool = KR_POOL_MEAN;
@@ -1415,8 +1499,14 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         const int NJ = H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8, head_lds = CH_SEQ * 2 * H * 4;
         auto head_kernel = NJ == 1 ? &k_cls_head<1> : NJ == 2 ? &k_cls_head<2> : NJ == 4 ? &k_cls_head<4> : &k_cls_head<8>;
         KR_TRY(set_lds_once(reinterpret_cast<const void*>(head_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));      // the widest H of the instantiation (64 KiB at 2048)
+        if (modern_head) {       // ModernBert's: Wo . LayerNorm(erf_gelu(Wd . pooled + bd)) + bo, same LDS
+            auto gln_kernel = NJ == 1 ? &k_cls_head<1, true> : NJ == 2 ? &k_cls_head<2, true> : NJ == 4 ? &k_cls_head<4, true> : &k_cls_head<8, true>;
+            KR_TRY(set_lds_once(reinterpret_cast<const void*>(gln_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));
+            hipLaunchKernelGGL(gln_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->mh_wd, e->mh_bd, e->mh_wo, e->mh_bo, B, H,
+                               e->mh_labels, e->out, e->mh_g, e->mh_b, eps, r.nk, e->d_err);
+        } else
         hipLaunchKernelGGL(head_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->cls_wd, e->cls_bd, e->cls_wo, e->cls_bo, B, H,
-                           e->cls_labels, e->out);
+                           e->cls_labels, e->out, nullptr, nullptr, 0.f, nullptr, nullptr);
     } else
     if (e->dense_rows > 0) {     // the Dense head: out [B, P] = normalize(W . pooled)
         const int P = e->dense_rows, dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
@@ -1532,8 +1622,10 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
     if ((flags & KR_POOL_WITH_COLBERT) && !e->has_colbert())
         return fail(KR_ESTATE, "KR_POOL_WITH_COLBERT on a handle without a colbert head: colbert_linear.weight and colbert_linear.bias were never loaded");
     if (pool == KR_POOL_CLASSIFY && !e->has_head())
-        return fail(KR_ESTATE, "pool = 2 (classify) on a handle without a classification head: classifier.dense.{weight,bias} and classifier.out_proj.{weight,bias} "
-                               "were never loaded");
+        return fail(KR_ESTATE, e->modern() ? "pool = 2 (classify) on a ModernBert handle without a classification head: head.dense.weight, head.norm.weight, "
+                                             "classifier.weight and classifier.bias were never loaded"
+                                           : "pool = 2 (classify) on a handle without a classification head: classifier.dense.{weight,bias} and "
+                                             "classifier.out_proj.{weight,bias} were never loaded");
     if (B > 65535) return fail(KR_EINVAL, "at most 65535 sequences per call");
     return 0;
 }
@@ -1555,7 +1647,7 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 // (tok_elems > 0: the token-level blocks of a flagged forward with a host `out` wait in e->tok_stage and follow the dense block)
 static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st, size_t tok_elems = 0) {
     // (KR_POOL_SPLADE has no dense block: its [B, vocab] result is written to a device `out` by the kernels, or waits in e->tok_stage like a token-level block)
-    const size_t dense_elems = pool == KR_POOL_SPLADE ? 0 : (size_t)B * (pool == KR_POOL_CLASSIFY ? e->cls_labels : e->out_dim());
+    const size_t dense_elems = pool == KR_POOL_SPLADE ? 0 : (size_t)B * (pool == KR_POOL_CLASSIFY ? e->head_labels() : e->out_dim());
     if (dense_elems) KR_HIP(hipMemcpyAsync(out, e->out, dense_elems * 4, hipMemcpyDefault, st));
     if (tok_elems) KR_HIP(hipMemcpyAsync(out + dense_elems, e->tok_stage, tok_elems * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;

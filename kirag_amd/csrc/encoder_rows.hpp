@@ -572,11 +572,18 @@ __global__ __launch_bounds__(256) void k_pool_dense(const float* __restrict__ po
 // sequences, and fp32 keeps the head inside an a-priori bound of (H + 2) 2^-24 per sum (tests/test_gpu_reranker.py).  What bounds the kernel is the latency of
 // the weight rows — one block streams all of Wd — hence 16 waves with CH_ROWS x NJ row loads each in flight before the first FMA (4 waves with one row each:
 // 0.6 ms at any batch size; profiles/reranker/measurements.txt).
+//
+// GLN (ModernBert handles; ModernBertForSequenceClassification's head.dense -> gelu -> head.norm -> classifier): logits[b, :] = Wo . LayerNorm(erf_gelu(Wd . x_b + bd)) + bo.
+// Stage 1 stores the exact erf-GELU where the tanh stood; then wave s < CH_SEQ takes the H values of slot s in LDS: lane l sums columns l, l + 64, ... in
+// that order and a shuffle butterfly folds the 64 sums — first the mean, then the variance of the values centred on it (two passes, fp32), then
+// t = (t - mean) / sqrt(var + eps) * g + beta in place — a fixed order per sequence whatever its slot.  Stage 2 is the same code.  This variant also
+// guards its result: a non-finite logit of a sequence with attended tokens (seq_nk > 0) sets bit 1 of the error word, like a non-finite embedding (k_pool).
 constexpr int CH_SEQ = 4, CH_WAVES = 16;
-template <int NJ>     // 256-column steps that cover a row: H <= 256 NJ
+template <int NJ, bool GLN = false>     // 256-column steps that cover a row: H <= 256 NJ
 __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restrict__ pooled, const float* __restrict__ Wd, const float* __restrict__ bd,
                                                            const float* __restrict__ Wo, const float* __restrict__ bo, int B, int H, int L,
-                                                           float* __restrict__ out) {
+                                                           float* __restrict__ out, const float* __restrict__ ng = nullptr, const float* __restrict__ nb = nullptr,
+                                                           float eps = 0.f, const int* __restrict__ seq_nk = nullptr, int* __restrict__ err = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* x = reinterpret_cast<float*>(smem);          // [CH_SEQ][H]
     float* t = x + CH_SEQ * H;                          // [CH_SEQ][H]
@@ -630,14 +637,38 @@ __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restr
     rows_dot(Wd, H, x, [&](int f, const float (&y)[CH_SEQ]) {
         const float b = bd[f];
 #pragma unroll
-        for (int s = 0; s < CH_SEQ; ++s) t[s * H + f] = tanhf(y[s] + b);
+        for (int s = 0; s < CH_SEQ; ++s) {
+            if constexpr (GLN) { const float a = y[s] + b; t[s * H + f] = 0.5f * a * (1.f + erff(a * 0.70710678118654752f)); }
+            else t[s * H + f] = tanhf(y[s] + b);
+        }
     });
     __syncthreads();
+    if constexpr (GLN) {
+        if (wave < CH_SEQ) {
+            float* ts = t + wave * H;
+            float sum = 0.f;
+            for (int i = lane; i < H; i += 64) sum += ts[i];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
+            const float mean = sum / (float)H;
+            float sq = 0.f;
+            for (int i = lane; i < H; i += 64) { const float d = ts[i] - mean; sq = fmaf(d, d, sq); }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sq += __shfl_xor(sq, m, 64);
+            const float rstd = 1.f / sqrtf(sq / (float)H + eps);
+            for (int i = lane; i < H; i += 64) ts[i] = (ts[i] - mean) * rstd * ng[i] + nb[i];
+        }
+        __syncthreads();
+    }
     rows_dot(Wo, L, t, [&](int l, const float (&y)[CH_SEQ]) {
         const float b = bo[l];
 #pragma unroll
         for (int s = 0; s < CH_SEQ; ++s)
-            if (b0 + s < B) out[(int64_t)(b0 + s) * L + l] = y[s] + b;
+            if (b0 + s < B) {
+                const float v = y[s] + b;
+                out[(int64_t)(b0 + s) * L + l] = v;
+                if constexpr (GLN) { if (!(fabsf(v) < INFINITY) && seq_nk[b0 + s] > 0) atomicOr(err, 2); }
+            }
     });
 }
 

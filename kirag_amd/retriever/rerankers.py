@@ -6,9 +6,12 @@ A cross-encoder is the encoder stack plus a head on the ``[CLS]`` / ``<s>`` row,
   * ``XLMRobertaForSequenceClassification`` (BAAI/bge-reranker-base / -large / -v2-m3): ``RobertaClassificationHead``, ``classifier.dense`` and
     ``classifier.out_proj`` — the names the library knows (``include/kirag_amd.h``);
   * ``BertForSequenceClassification`` (cross-encoder/ms-marco-MiniLM-L-6-v2 / -L-12-v2 / ms-marco-TinyBERT): the same arithmetic spelled
-    ``classifier(tanh(pooler.dense(x)))``, mapped onto those names, with token types for the second segment.
+    ``classifier(tanh(pooler.dense(x)))``, mapped onto those names, with token types for the second segment;
+  * ``ModernBertForSequenceClassification`` (Alibaba-NLP/gte-reranker-modernbert-base, ibm-granite/granite-embedding-reranker-english-r2, CrossEncoder
+    fine-tunes of answerdotai/ModernBERT-*): another function, ``classifier(LayerNorm(gelu(head.dense(x))))`` on the ``[CLS]`` row or the masked mean
+    (``config.classifier_pooling``), under HF's own names; no token types, up to 8192 tokens.
 
-``XLMRobertaReranker`` / ``BertReranker`` ARE those HF classes (``from_pretrained`` / ``save_pretrained`` / ``.to()`` keep working); in ``eval()`` mode their
+``XLMRobertaReranker`` / ``BertReranker`` / ``ModernBertReranker`` ARE those HF classes (``from_pretrained`` / ``save_pretrained`` / ``.to()`` keep working); in ``eval()`` mode their
 forward runs in ``libkirag_amd.so`` (``KR_POOL_CLASSIFY``) and returns ``SequenceClassifierOutput(logits=[B, num_labels])`` on the GPU without autograd
 history; in ``train()`` mode it is HF's own forward (dropout included).  There is no CPU fallback, as for the encoders.  Raw logits: a sigmoid or softmax is
 the caller's.
@@ -21,11 +24,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
-from transformers import BertForSequenceClassification, PretrainedConfig, XLMRobertaForSequenceClassification
+from transformers import (BertForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification, PretrainedConfig,
+                          XLMRobertaForSequenceClassification)
 from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
-from .encoders import _CONFIG_KWARGS, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
+from .encoders import _CONFIG_KWARGS, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
 from .m3 import BGEM3Model
 from .splade import SpladeModel
 
@@ -87,6 +91,72 @@ class BertReranker(_HipClassifierMixin, BertForSequenceClassification):
     _hip_rename = staticmethod(bert_rename)
 
 
+MODERN_POOLINGS = {"cls": 0.0, "mean": 1.0}       # config.classifier_pooling -> the library's setting "config.classifier_pooling"
+MODERN_POOLING_SETTING = "config.classifier_pooling"
+MODERN_HIDDEN_STEP, MODERN_HIDDEN_MAX, MODERN_HEAD_WIDTHS = 128, 2048, (32, 64)      # kr_encoder_create's shape rule
+
+
+def modern_rename(name: str) -> str:
+    """``ModernBertForSequenceClassification`` parameter name -> the library's: the backbone loses its ``model.`` prefix, ``head.*`` and ``classifier.*`` are
+    the library's own spelling"""
+    return _strip(name, "model.")
+
+
+def check_modern_config(config) -> None:
+    """``NotImplementedError`` beginning ``model_type='modernbert':`` and naming the field, for everything the kernels do not compute — from the config alone:
+    no weight has been read and the library is not loaded.  ``config``: a ``ModernBertConfig`` or the dict of a ``config.json`` (HF's defaults fill the rest)."""
+    def refuse(msg):
+        raise NotImplementedError(f"model_type={MODERN_TYPE!r}: {msg}")
+    is_dict = isinstance(config, dict)
+    get = (lambda k, d: config.get(k, d)) if is_dict else (lambda k, d: getattr(config, k, d))
+    # the raw fields first: HF's own config class validates some of them with errors of its own
+    H, heads = int(get("hidden_size", 768)), int(get("num_attention_heads", 12))
+    if H % MODERN_HIDDEN_STEP or not 0 < H <= MODERN_HIDDEN_MAX:
+        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of {MODERN_HIDDEN_STEP} up to {MODERN_HIDDEN_MAX}")
+    if heads <= 0 or H % heads or H // heads not in MODERN_HEAD_WIDTHS:
+        refuse(f"num_attention_heads={heads} with hidden_size={H}: the attention kernels are built for heads of width {MODERN_HEAD_WIDTHS}")
+    if get("classifier_activation", "gelu") != "gelu":
+        refuse(f"classifier_activation={get('classifier_activation', None)!r}: the classification head implements erf-GELU only")
+    if get("classifier_pooling", "cls") not in MODERN_POOLINGS:
+        refuse(f"classifier_pooling={get('classifier_pooling', None)!r}: {tuple(MODERN_POOLINGS)} are implemented")
+    labels = len(config["id2label"]) if is_dict and config.get("id2label") is not None else int(get("num_labels", 2))
+    if labels > MAX_LABELS:
+        refuse(f"num_labels={labels}: the classification head of the HIP encoder holds at most {MAX_LABELS} labels")
+    types = get("layer_types", None)
+    if types is not None and set(types) - set(MODERN_LAYER_TYPES):
+        refuse(f"layer_types={list(types)!r}: one of {MODERN_LAYER_TYPES} per layer is implemented")
+    if is_dict:
+        config = ModernBertConfig.from_dict(config)
+    try:
+        with torch.device("cpu"):                      # (from_pretrained constructs the model under a meta-device context)
+            HipBertForward._modern_settings(config)    # hidden_activation, head_dim, layer_types, attention_scaling: the encoders' own rules
+    except NotImplementedError as e:
+        refuse(str(e))
+
+
+class ModernBertReranker(_HipClassifierMixin, ModernBertForSequenceClassification):
+    """ModernBertModel -> ``[CLS]`` row or masked mean (``config.classifier_pooling``) -> head.dense -> gelu -> head.norm -> classifier
+    (Alibaba-NLP/gte-reranker-modernbert-base, ibm-granite/granite-embedding-reranker-english-r2).  Frequencies, half-window, layer types and the FF
+    zero-padding are the encoders' ModernBERT path (``HipBertForward``); the pooling travels as the library's setting next to the parameters."""
+    _hf_base = ModernBertForSequenceClassification
+    _hip_rename = staticmethod(modern_rename)
+
+    def __init__(self, config, **kwargs):
+        check_modern_config(config)
+        super().__init__(config, **kwargs)
+        # one float on the host, sent with every weight sync under the setting's reserved name (no parameter, no buffer: the state dict stays HF's)
+        self._hip_pooling = torch.tensor([MODERN_POOLINGS[config.classifier_pooling]], dtype=torch.float32, device="cpu")
+
+    @staticmethod
+    def _hip_extra(module):
+        return [(MODERN_POOLING_SETTING, module._hip_pooling)]
+
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, **kwargs):
+        if self.training:        # ModernBERT has no token types: whatever a tokenizer emits there is dropped
+            return ModernBertForSequenceClassification.forward(self, input_ids=input_ids, attention_mask=attention_mask, **kwargs)
+        return super().forward(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=None)
+
+
 class BGEReranker:
     """The registry's entry: ``from_pretrained`` reads the checkpoint's ``config.json`` and returns the twin of its ``model_type``."""
 
@@ -94,7 +164,7 @@ class BGEReranker:
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
         config = kwargs.get("config")
         if isinstance(config, PretrainedConfig):
-            model_type = config.model_type
+            model_type, cfg_dict = config.model_type, config
         else:
             where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
             cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
@@ -103,7 +173,10 @@ class BGEReranker:
             return BertReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         if model_type in ROBERTA_TYPES:
             return XLMRobertaReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert' and {ROBERTA_TYPES} checkpoints "
+        if model_type == MODERN_TYPE:
+            check_modern_config(cfg_dict)          # from config.json alone: before a weight is read
+            return ModernBertReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r} and {ROBERTA_TYPES} checkpoints "
                                   "(the classification heads of other families are other functions)")
 
 

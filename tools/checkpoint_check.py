@@ -27,7 +27,8 @@ BERT-family checkpoints show).  This tool replaces that assertion by a measureme
     encoder (GPU present) or, with --emulate or without a GPU, the torch emulation of its rounding points (tools/precision_emulation.py);
  3. a recommendation: the cheapest mode whose error stays below HALF the 1e-3 tolerance, else the default.
 
-A sequence-classification checkpoint (config.json names an ...ForSequenceClassification architecture: BAAI/bge-reranker-*, cross-encoder/ms-marco-MiniLM-*)
+A sequence-classification checkpoint (config.json names an ...ForSequenceClassification architecture: BAAI/bge-reranker-*, cross-encoder/ms-marco-MiniLM-*,
+and ModernBertForSequenceClassification: gte-reranker-modernbert-base, granite-embedding-reranker-english-r2, against HF fp32 with eager attention)
 is loaded as its reranker twin (kirag_amd.retriever.rerankers) instead, GPU only, and the report is the worst |logit - HF fp32 logit| over the built-in
 (question, passage) pairs — every question against every passage — for the four precision modes; the f16 range risk is the encoder's, as above.
 
@@ -215,6 +216,15 @@ def reranker_inputs(args, hf_dir, cfg):
         qs = [q for q in BASE_QUESTIONS for _ in BASE_PASSAGES]
         return RerankerCollator(tok, maxlength=args.max_length).encode_pairs(qs, BASE_PASSAGES * len(BASE_QUESTIONS))
     rng = np.random.default_rng(args.seed)
+    if cfg.model_type == "modernbert":      # [CLS] q [SEP] p [SEP] with the config's special ids, no token types
+        S, lo = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000)
+        ids = np.full((args.n, S), cfg.pad_token_id, np.int64); mask = np.zeros((args.n, S), np.int64)
+        for r in range(args.n):
+            n = int(np.clip(rng.normal(0.8 * S, 0.2 * S), 8, S))
+            nq = int(rng.integers(1, max(2, min(16, n - 6))))
+            ids[r, :n] = [cfg.cls_token_id, *rng.integers(lo, cfg.vocab_size, nq), cfg.sep_token_id, *rng.integers(lo, cfg.vocab_size, n - nq - 3), cfg.sep_token_id]
+            mask[r, :n] = 1
+        return {"input_ids": torch.from_numpy(ids), "attention_mask": torch.from_numpy(mask)}
     roberta = cfg.model_type != "bert"
     S, lo = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000)
     pad = cfg.pad_token_id if roberta else 0
@@ -237,17 +247,20 @@ def check_reranker(hf_dir, args):
     from kirag_amd.retriever.rerankers import BGEReranker
     if not torch.cuda.is_available() or args.emulate:
         raise SystemExit(f"{hf_dir}: a sequence-classification checkpoint is checked on the GPU (the torch emulation has no classification head)")
-    model = BGEReranker.from_pretrained(hf_dir).float().eval().to("cuda:0")
-    a = {k: v.to("cuda:0") for k, v in reranker_inputs(args, hf_dir, model.config).items()}
+    from transformers import AutoConfig
+    modern = AutoConfig.from_pretrained(hf_dir).model_type == "modernbert"
+    kw = {"attn_implementation": "eager"} if modern else {}      # ModernBertForSequenceClassification: the reference is HF fp32 with eager attention
+    model = BGEReranker.from_pretrained(hf_dir, **kw).float().eval().to("cuda:0")
+    a = {k: v.to("cuda:0") for k, v in reranker_inputs(args, hf_dir, model.config).items() if not (modern and k == "token_type_ids")}
     with torch.no_grad():
         ref = model._hf_base.forward(model, **a).logits.double().cpu().numpy()
     print(f"# {hf_dir}: {type(model).__name__}, {model.config.num_hidden_layers} layers, hidden {model.config.hidden_size}, {model.config.num_labels} label(s); "
           f"{len(ref)} pairs of up to {a['input_ids'].shape[1]} tokens; HF fp32 logits {ref.min():.3f} .. {ref.max():.3f}")
     results = []
     for dtype, lo in MODES:
-        h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename)
+        h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename, extra=type(model)._hip_extra)
         h.sync(model)
-        tt = a.get("token_type_ids") if model.config.type_vocab_size > 1 else None
+        tt = a.get("token_type_ids") if getattr(model.config, "type_vocab_size", 1) > 1 else None
         out = h.forward(a["input_ids"], a["attention_mask"], POOL_CLASSIFY, tt).double().cpu().numpy()
         finite = bool(np.isfinite(out).all())
         err = float(np.abs(out - ref).max()) if finite else float("inf")

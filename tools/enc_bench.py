@@ -97,10 +97,12 @@ def hf_classes(cfg):
     return T.BertConfig, T.BertModel, (ENC.E5Encoder if args.pool == "mean" else ENC.BGEEncoder)
 
 
-def make_encoder(cfg):
+def make_encoder(cfg, extra_state=None):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
-    shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw)"""
+    shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw).  extra_state: tensors and settings that must
+    arrive with the first load (a head: tools/rerank_bench.py), by library name"""
     if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5"):
+        assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
     from kirag_amd.retriever.encoders import HipBertForward
@@ -162,7 +164,7 @@ def make_encoder(cfg):
         state = renamed
     else:
         state["encoder.relative_attention_bias.weight"] = torch.randn(32, cfg["num_attention_heads"], generator=g, device=dev)
-    enc.load_state(state)
+    enc.load_state(dict(state, **(extra_state or {})))
     enc.cfg = ns
     return enc
 

@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """What the classification head costs: KR_POOL_CLASSIFY against KR_POOL_CLS on ONE handle with a head (synthetic weights), alternated in one process.
 
-    python tools/rerank_bench.py [--shape xlmr-large] [--batches 100x256,1000x128,1x64] [--rounds 6] [--labels 1] [--once]
+    python tools/rerank_bench.py [--shape xlmr-large|modernbert-base] [--pooling cls|mean] [--batches 100x256,1000x128,1x64] [--rounds 6] [--labels 1] [--once]
 
 The two forwards differ behind the last LayerNorm only (k_pool's raw rows + k_cls_head instead of the normalising k_pool), so the difference of the medians is
-the head.  --once runs one classify forward per batch shape and nothing else: the run to put under a kernel trace (the k_cls_head row is the head's launch)."""
+the head.  --once runs one classify forward per batch shape and nothing else: the run to put under a kernel trace (the k_cls_head row is the head's launch).
+--shape modernbert-base (22 layers, H 768, 12 heads of 64, FF 1152, vocab 50368): ModernBertForSequenceClassification's head, dense -> gelu -> LayerNorm ->
+classifier; --pooling mean makes it read the masked mean, and the plain pool it is compared with is then KR_POOL_MEAN."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from kirag_amd import bench_support as BS
-from kirag_amd.retriever.encoders import POOL_CLASSIFY, POOL_CLS, HipBertForward
+from kirag_amd.retriever.encoders import POOL_CLASSIFY, POOL_CLS, POOL_MEAN, HipBertForward
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="xlmr-large")
@@ -19,22 +21,31 @@ ap.add_argument("--batches", default="100x256,1000x128,1x64")
 ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--labels", type=int, default=1)
 ap.add_argument("--once", action="store_true")
+ap.add_argument("--pooling", default="cls", choices=["cls", "mean"])
 args = ap.parse_args()
 sys.argv = sys.argv[:1]
 import enc_bench as EB  # noqa: E402  (its shape table)
 
 dev = torch.device("cuda:0")
 cfg = EB.SHAPES[args.shape]
-assert cfg.get("model_type", "bert") in ("bert", "xlm-roberta", "roberta", "camembert"), "the head runs on BERT / RoBERTa handles"
-ns = BS.SimpleNamespace(**cfg)
+modern = cfg.get("model_type", "bert") == "modernbert"
+assert modern or cfg.get("model_type", "bert") in ("bert", "xlm-roberta", "roberta", "camembert"), "the heads run on BERT / RoBERTa and ModernBert handles"
+assert modern or args.pooling == "cls", "--pooling mean is ModernBERT's"
 H = cfg["hidden_size"]
-state = dict(BS.synthetic_state(ns, dev, 0))
 g = torch.Generator(device=dev); g.manual_seed(31)
-state.update({"classifier.dense.weight": torch.randn(H, H, generator=g, device=dev) / H ** 0.5, "classifier.dense.bias": 0.5 * torch.randn(H, generator=g, device=dev),
-              "classifier.out_proj.weight": 4 * torch.randn(args.labels, H, generator=g, device=dev) / H ** 0.5,
-              "classifier.out_proj.bias": torch.randn(args.labels, generator=g, device=dev)})
-enc = HipBertForward(ns, 0)
-enc.load_state(state)
+randn = lambda *s: torch.randn(*s, generator=g, device=dev)
+PLAIN = POOL_MEAN if args.pooling == "mean" else POOL_CLS
+if modern:
+    head = {"head.dense.weight": randn(H, H) / H ** 0.5, "head.norm.weight": 1 + 0.5 * randn(H), "classifier.weight": 4 * randn(args.labels, H) / H ** 0.5,
+            "classifier.bias": randn(args.labels), "config.classifier_pooling": torch.tensor([float(args.pooling == "mean")])}
+    enc = EB.make_encoder(cfg, extra_state=head)
+else:
+    ns = BS.SimpleNamespace(**cfg)
+    state = dict(BS.synthetic_state(ns, dev, 0))
+    state.update({"classifier.dense.weight": randn(H, H) / H ** 0.5, "classifier.dense.bias": 0.5 * randn(H),
+                  "classifier.out_proj.weight": 4 * randn(args.labels, H) / H ** 0.5, "classifier.out_proj.bias": randn(args.labels)})
+    enc = HipBertForward(ns, 0)
+    enc.load_state(state)
 for B, S in (tuple(int(v) for v in t.split("x")) for t in args.batches.split(",")):
     ids, mask = BS.synthetic_tokens(dev, B, S, seed=1)
     if "pad_token_id" in cfg:
@@ -43,10 +54,10 @@ for B, S in (tuple(int(v) for v in t.split("x")) for t in args.batches.split(","
         enc.forward(ids, mask, POOL_CLASSIFY); torch.cuda.synchronize()
         print(f"{args.shape} {B} x {S}: one classify forward", flush=True)
         continue
-    res = {POOL_CLASSIFY: [], POOL_CLS: []}
+    res = {POOL_CLASSIFY: [], PLAIN: []}
     reps = 5 if B * S > 20000 else 20
     for rnd in range(args.rounds):
-        for pool in (POOL_CLASSIFY, POOL_CLS):
+        for pool in (POOL_CLASSIFY, PLAIN):
             for _ in range(2):
                 enc.forward(ids, mask, pool)
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -54,7 +65,7 @@ for B, S in (tuple(int(v) for v in t.split("x")) for t in args.batches.split(","
                 enc.forward(ids, mask, pool)
             torch.cuda.synchronize()
             res[pool].append((time.perf_counter() - t0) / reps * 1e3)
-    c, e = np.array(res[POOL_CLASSIFY]), np.array(res[POOL_CLS])
-    print(f"{args.shape} {B} x {S} labels={args.labels}: classify median {np.median(c):.3f} ms (min {c.min():.3f}, max {c.max():.3f})  cls median {np.median(e):.3f} ms "
+    c, e = np.array(res[POOL_CLASSIFY]), np.array(res[PLAIN])
+    print(f"{args.shape} {B} x {S} labels={args.labels}: classify median {np.median(c):.3f} ms (min {c.min():.3f}, max {c.max():.3f})  {args.pooling} median {np.median(e):.3f} ms "
           f"(min {e.min():.3f}, max {e.max():.3f})  difference of medians {1e3 * (np.median(c) - np.median(e)):+.1f} us", flush=True)
 enc.check()
