@@ -1,0 +1,534 @@
+// What an encoder handle IS, decided in one place and without a device: the state-dict names of the five model families, the heads, the settings, and
+// describe(), which turns what was loaded into a ModelPlan (or the refusal kr_encoder_finalize returns).  Host-only: nothing here includes HIP, so the
+// tables are tested by a stand-alone program (tests/capi/encoder_model_check.cpp).  The device side of every row lives in encoder_weights.hpp (where a
+// slot is stored) and encoder.hip (enqueue_forward: which launches a plan selects).  Adding a family or a head: DESIGN.md, "Adding a family / a head".
+#pragma once
+#include "../../include/kirag_amd.h"
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace kr {
+namespace model {
+
+struct Error { int code = 0; std::string msg; };
+inline Error err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+inline Error err(int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return Error{code, buf};
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// families
+// ---------------------------------------------------------------------------------------------------------
+// BERT: BertModel / RobertaModel / XLMRobertaModel, post-LN, position table (fairseq's position rule is the setting config.position_padding_idx of BERT and
+//   MPNet handles, not a family).  MPNET: the same stack under MPNetModel's names with "encoder.relative_attention_bias.weight" [32, heads] added to the scores.
+// NOMIC (config.rotary_inv_freq): no position table, q and k rotated in the QKV epilogue, [gate | up] x as one GEMM with the SwiGLU epilogue, no linear bias
+//   unless loaded.  MODERN (config.local_attention_layers, needs config.rotary_inv_freq): a PRE-LN stack — the residual stream is kept apart from the normalised
+//   operand, attn_norm of layer N runs in the launch behind the MLP of layer N - 1 — with GEGLU and, in the layers flagged local, a sliding window and the
+//   local rotary table.  T5 (config.t5_feed_forward, T5EncoderModel): MODERN's schedule with RMS norms, the embedding row straight into the residual stream, a
+//   relative attention bias in every layer with scores q.k + bias (no 1 / sqrt(d_h)), no linear bias, relu or gated gelu_new.
+enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5 };
+constexpr uint8_t GATED_NAME = 0x80;   // or-ed into a slot's family: the tensor came as one half of a gated projection under T5's names (wi_0 / wi_1)
+inline Family fam_of(uint8_t got) { return (Family)(got & 0x7f); }
+inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5"}; return n[f]; }
+
+// tensor slots: 0..4 embeddings, then L_COUNT per layer (L_UW: the second half of a gated intermediate projection); below zero what is no slot of `got`
+enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
+enum { T_IGNORED = -1, T_RELBIAS = -2, T_WQKV = -3, T_WI = -4, T_WIB = -5, T_WQKVB = -6 };   // ModernBert's fused tensors of one layer: attn.Wqkv.{weight,bias}, mlp.Wi.{weight,bias}
+enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
+constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says, and so do the T5 handles
+constexpr int MLM_COLS = 128;          // column granularity of the projection loops: the MLM decoder is stored with vocab rounded up to it by zero rows
+
+// the extents every shape rule is written in
+enum Ext : uint8_t { X1, XH, X3H, XFF, X2FF, XV, XVPAD, XPOS, XTYPE, XBUCKETS, XHEADS, XHALF_DH, XFREE, XANY };
+inline int64_t extent(const kr_bert_cfg& c, Ext x, int64_t free_dim = 0) {
+    switch (x) {
+        case X1: return 1;
+        case XH: return c.hidden;
+        case X3H: return 3 * (int64_t)c.hidden;
+        case XFF: return c.intermediate;
+        case X2FF: return 2 * (int64_t)c.intermediate;
+        case XV: return c.vocab;
+        case XVPAD: return ((int64_t)c.vocab + MLM_COLS - 1) / MLM_COLS * MLM_COLS;
+        case XPOS: return c.max_pos;
+        case XTYPE: return c.type_vocab;
+        case XBUCKETS: return REL_BUCKETS;
+        case XHEADS: return c.heads;
+        case XHALF_DH: return c.hidden / c.heads / 2;
+        default: return free_dim;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// state-dict names
+// ---------------------------------------------------------------------------------------------------------
+// How a row's text is matched: the whole name; the name's tail behind a '.' (or the whole name); the name's tail; what follows "embeddings."; what follows
+// the layer prefix of the row's family and the layer index.  The layer prefixes (layer_prefix): "encoder.layer." anywhere for BERT's and MPNet's rows,
+// else "layers." at the start or behind a '.' for NomicBert's and ModernBert's, "encoder.block." / "block." at the start for T5's.
+enum Match : uint8_t { WHOLE, TAIL, ENDS, EMB, LAYER };
+// NORM_BEFORE: a pre-LN family's norm in front of the attention of layer N is applied by the launch behind the FF of layer N - 1 and stored there (L_LN2*);
+//   layer 0's is the embedding norm's slot under T5's names and the identity (refused) under ModernBert's.  LAST_LAYER: the stack's final norm, the L_LN2* of
+//   the last layer.  BLOCK0: T5's one bias table is spelled as a tensor of block 0.  GATED: see GATED_NAME.
+enum : uint8_t { NORM_BEFORE = 1, LAST_LAYER = 2, BLOCK0 = 4, GATED = 8 };
+struct NameRow { const char* text; Match match; Family fam; int id; Ext r, c; uint8_t flags; };
+static const NameRow NAME_ROWS[] = {
+    {"shared.weight", WHOLE, T5, T_WORD, XV, XH, 0}, {"encoder.embed_tokens.weight", WHOLE, T5, T_WORD, XV, XH, 0}, {"embed_tokens.weight", WHOLE, T5, T_WORD, XV, XH, 0},
+    {"encoder.final_layer_norm.weight", WHOLE, T5, L_LN2G, XH, X1, LAST_LAYER}, {"final_layer_norm.weight", WHOLE, T5, L_LN2G, XH, X1, LAST_LAYER},
+    {"layer.0.SelfAttention.q.weight", LAYER, T5, L_QW, XH, XH, 0}, {"layer.0.SelfAttention.k.weight", LAYER, T5, L_KW, XH, XH, 0},
+    {"layer.0.SelfAttention.v.weight", LAYER, T5, L_VW, XH, XH, 0}, {"layer.0.SelfAttention.o.weight", LAYER, T5, L_OW, XH, XH, 0},
+    {"layer.0.SelfAttention.relative_attention_bias.weight", LAYER, T5, T_RELBIAS, XBUCKETS, XHEADS, BLOCK0},
+    {"layer.0.layer_norm.weight", LAYER, T5, L_LN2G, XH, X1, NORM_BEFORE}, {"layer.1.layer_norm.weight", LAYER, T5, L_LN1G, XH, X1, 0},
+    {"layer.1.DenseReluDense.wi.weight", LAYER, T5, L_IW, XFF, XH, 0}, {"layer.1.DenseReluDense.wi_0.weight", LAYER, T5, L_IW, XFF, XH, GATED},
+    {"layer.1.DenseReluDense.wi_1.weight", LAYER, T5, L_UW, XFF, XH, GATED}, {"layer.1.DenseReluDense.wo.weight", LAYER, T5, L_FW, XH, XFF, 0},
+    {"final_norm.weight", TAIL, MODERN, L_LN2G, XH, X1, LAST_LAYER}, {"final_norm.bias", TAIL, MODERN, L_LN2B, XH, X1, LAST_LAYER},
+    {"encoder.relative_attention_bias.weight", ENDS, MPNET, T_RELBIAS, XBUCKETS, XHEADS, 0},
+    // ModernBertModel: Wqkv [3H, H] = q | k | v row blocks, mlp.Wi [2 FF, H] = input | gate (input, the half the GELU is applied to, in the place of NomicBert's
+    // gate_proj, gate in that of up_proj); mlp_norm is the norm behind the attention output
+    {"attn.Wqkv.weight", LAYER, MODERN, T_WQKV, X3H, XH, 0}, {"attn.Wqkv.bias", LAYER, MODERN, T_WQKVB, X3H, X1, 0}, {"mlp.Wi.weight", LAYER, MODERN, T_WI, X2FF, XH, 0},
+    {"mlp.Wi.bias", LAYER, MODERN, T_WIB, X2FF, X1, 0}, {"attn.Wo.weight", LAYER, MODERN, L_OW, XH, XH, 0}, {"attn.Wo.bias", LAYER, MODERN, L_OB, XH, X1, 0},
+    {"mlp_norm.weight", LAYER, MODERN, L_LN1G, XH, X1, 0}, {"mlp_norm.bias", LAYER, MODERN, L_LN1B, XH, X1, 0}, {"mlp.Wo.weight", LAYER, MODERN, L_FW, XH, XFF, 0},
+    {"mlp.Wo.bias", LAYER, MODERN, L_FB, XH, X1, 0}, {"attn_norm.weight", LAYER, MODERN, L_LN2G, XH, X1, NORM_BEFORE}, {"attn_norm.bias", LAYER, MODERN, L_LN2B, XH, X1, NORM_BEFORE},
+    // NomicBertModel
+    {"self_attn.q_proj.weight", LAYER, NOMIC, L_QW, XH, XH, 0}, {"self_attn.k_proj.weight", LAYER, NOMIC, L_KW, XH, XH, 0}, {"self_attn.v_proj.weight", LAYER, NOMIC, L_VW, XH, XH, 0},
+    {"self_attn.o_proj.weight", LAYER, NOMIC, L_OW, XH, XH, 0}, {"post_attention_layernorm.weight", LAYER, NOMIC, L_LN1G, XH, X1, 0},
+    {"post_attention_layernorm.bias", LAYER, NOMIC, L_LN1B, XH, X1, 0}, {"mlp.gate_proj.weight", LAYER, NOMIC, L_IW, XFF, XH, 0}, {"mlp.up_proj.weight", LAYER, NOMIC, L_UW, XFF, XH, 0},
+    {"mlp.down_proj.weight", LAYER, NOMIC, L_FW, XH, XFF, 0}, {"post_mlp_layernorm.weight", LAYER, NOMIC, L_LN2G, XH, X1, 0}, {"post_mlp_layernorm.bias", LAYER, NOMIC, L_LN2B, XH, X1, 0},
+    // MPNetModel's spelling of the attention block, then BertModel's / RobertaModel's / XLMRobertaModel's names (a handle takes either spelling per tensor)
+    {"attention.attn.q.weight", LAYER, MPNET, L_QW, XH, XH, 0}, {"attention.attn.q.bias", LAYER, MPNET, L_QB, XH, X1, 0}, {"attention.attn.k.weight", LAYER, MPNET, L_KW, XH, XH, 0},
+    {"attention.attn.k.bias", LAYER, MPNET, L_KB, XH, X1, 0}, {"attention.attn.v.weight", LAYER, MPNET, L_VW, XH, XH, 0}, {"attention.attn.v.bias", LAYER, MPNET, L_VB, XH, X1, 0},
+    {"attention.attn.o.weight", LAYER, MPNET, L_OW, XH, XH, 0}, {"attention.attn.o.bias", LAYER, MPNET, L_OB, XH, X1, 0},
+    {"attention.LayerNorm.weight", LAYER, MPNET, L_LN1G, XH, X1, 0}, {"attention.LayerNorm.bias", LAYER, MPNET, L_LN1B, XH, X1, 0},
+    {"attention.self.query.weight", LAYER, BERT, L_QW, XH, XH, 0}, {"attention.self.query.bias", LAYER, BERT, L_QB, XH, X1, 0}, {"attention.self.key.weight", LAYER, BERT, L_KW, XH, XH, 0},
+    {"attention.self.key.bias", LAYER, BERT, L_KB, XH, X1, 0}, {"attention.self.value.weight", LAYER, BERT, L_VW, XH, XH, 0}, {"attention.self.value.bias", LAYER, BERT, L_VB, XH, X1, 0},
+    {"attention.output.dense.weight", LAYER, BERT, L_OW, XH, XH, 0}, {"attention.output.dense.bias", LAYER, BERT, L_OB, XH, X1, 0},
+    {"attention.output.LayerNorm.weight", LAYER, BERT, L_LN1G, XH, X1, 0}, {"attention.output.LayerNorm.bias", LAYER, BERT, L_LN1B, XH, X1, 0},
+    {"intermediate.dense.weight", LAYER, BERT, L_IW, XFF, XH, 0}, {"intermediate.dense.bias", LAYER, BERT, L_IB, XFF, X1, 0}, {"output.dense.weight", LAYER, BERT, L_FW, XH, XFF, 0},
+    {"output.dense.bias", LAYER, BERT, L_FB, XH, X1, 0}, {"output.LayerNorm.weight", LAYER, BERT, L_LN2G, XH, X1, 0}, {"output.LayerNorm.bias", LAYER, BERT, L_LN2B, XH, X1, 0},
+    // embeddings (NomicBert and MPNet spell theirs as BERT does)
+    {"tok_embeddings.weight", EMB, MODERN, T_WORD, XV, XH, 0}, {"norm.weight", EMB, MODERN, T_ELNG, XH, X1, 0}, {"norm.bias", EMB, MODERN, T_ELNB, XH, X1, 0},
+    {"word_embeddings.weight", EMB, BERT, T_WORD, XV, XH, 0}, {"position_embeddings.weight", EMB, BERT, T_POS, XPOS, XH, 0},
+    {"token_type_embeddings.weight", EMB, BERT, T_TYPE, XTYPE, XH, 0}, {"LayerNorm.weight", EMB, BERT, T_ELNG, XH, X1, 0}, {"LayerNorm.bias", EMB, BERT, T_ELNB, XH, X1, 0},
+};
+
+// the rows a layer prefix leads to: 0 = BERT's and MPNet's, 1 = NomicBert's and ModernBert's, 2 = T5's
+inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN ? 1 : 0; }
+// the layer prefix of `s`, T5's only or the other two: its group and where the layer index starts, or -1
+inline int layer_prefix(const std::string& s, bool t5, size_t& at) {
+    if (t5) {
+        if (s.compare(0, 14, "encoder.block.") == 0) { at = 14; return 2; }
+        if (s.compare(0, 6, "block.") == 0) { at = 6; return 2; }
+        return -1;
+    }
+    if (const size_t p = s.find("encoder.layer."); p != std::string::npos) { at = p + 14; return 0; }
+    if (s.compare(0, 7, "layers.") == 0) { at = 7; return 1; }
+    if (const size_t p = s.find(".layers."); p != std::string::npos) { at = p + 8; return 1; }
+    return -1;
+}
+
+// slot >= 0: a slot of `got`; T_RELBIAS; a fused ModernBert tensor of layer `layer`; T_IGNORED ("pooler.*", "position_ids": the encoders read last_hidden_state)
+struct Resolved { int slot = T_IGNORED; Family fam = BERT; int layer = -1; int64_t numel = 0; bool gated = false; };
+
+inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& out) {
+    const std::string s(name);
+    out = Resolved{};
+    if (s.find("position_ids") != std::string::npos || s.find("pooler.") != std::string::npos) return Error{};
+    auto tail = [&](const char* t, bool dot) {
+        const size_t n = strlen(t);
+        return s.size() >= n && s.compare(s.size() - n, n, t) == 0 && (!dot || s.size() == n || s[s.size() - n - 1] == '.');
+    };
+    auto take = [&](const NameRow& r, long l) -> Error {
+        out.fam = r.fam; out.gated = (r.flags & GATED) != 0; out.numel = extent(cfg, r.r) * extent(cfg, r.c); out.layer = (int)l;
+        if ((r.flags & BLOCK0) && l != 0) return err(KR_EINVAL, "'%s': block 0 holds a T5 encoder's one relative attention bias", name);
+        if ((r.flags & NORM_BEFORE) && l == 0 && r.fam != T5) return err(KR_EINVAL, "'%s': attn_norm of layer 0 is the identity in ModernBert", name);
+        if (r.flags & LAST_LAYER) l = cfg.layers - 1;
+        if ((r.flags & NORM_BEFORE) && l == 0) out.slot = T_ELNG;
+        else out.slot = r.id < 0 || (r.match != LAYER && !(r.flags & LAST_LAYER)) ? r.id : T_LAYER0 + (int)((r.flags & NORM_BEFORE) ? l - 1 : l) * L_COUNT + r.id;
+        return Error{};
+    };
+    // in this order: whole names, T5's blocks, tails, the other layer prefixes, embeddings
+    for (int pass = 0; pass < 5; ++pass) {
+        if (pass == 1 || pass == 3) {
+            size_t at = 0;
+            const int group = layer_prefix(s, pass == 1, at);
+            if (group < 0) continue;
+            char* end = nullptr;
+            const long l = strtol(s.c_str() + at, &end, 10);
+            if (end == s.c_str() + at || *end != '.' || l < 0 || l >= cfg.layers) return err(KR_EINVAL, "bad layer index in '%s'", name);
+            for (const NameRow& r : NAME_ROWS)
+                if (r.match == LAYER && prefix_group(r.fam) == group && strcmp(end + 1, r.text) == 0) return take(r, l);
+            return err(KR_EINVAL, "unknown layer tensor '%s'", name);
+        }
+        const size_t emb = s.find("embeddings.");
+        for (const NameRow& r : NAME_ROWS)
+            if ((pass == 0 && r.match == WHOLE && s == r.text) || (pass == 2 && (r.match == TAIL || r.match == ENDS) && tail(r.text, r.match == TAIL)) ||
+                (pass == 4 && r.match == EMB && emb != std::string::npos && s.compare(emb + 11, std::string::npos, r.text) == 0))
+                return take(r, -1);
+    }
+    return err(KR_EINVAL, "unknown tensor name '%s'", name);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// heads
+// ---------------------------------------------------------------------------------------------------------
+// The rule of every head.  It belongs to the handle from its first finalize on: later loads with the same shape take new values (the weight sync reloads
+// every parameter); another free dimension, or a head arriving on a handle finalized without it, is KR_EINVAL.  At finalize a head is accepted on its
+// families only, never next to the heads it excludes, and whole (every REQUIRED tensor) or absent; an optional tensor is zero unless loaded.
+//   HEAD_MLM: SPLADE's BertForMaskedLM head (KR_POOL_SPLADE): one EPI_GELU projection H -> H, k_ln16_head, the decoder [Vpad, H] with the EPI_SPLADE epilogue.
+//   HEAD_COLBERT / HEAD_SPARSE: bge-m3's token-level heads (KR_POOL_WITH_COLBERT / KR_POOL_WITH_SPARSE): a flagged forward runs its last layer on every row.
+//   HEAD_DENSE: the sentence-transformers Dense head behind the pooling of a T5 handle (k_pool_dense: out [B, P]).
+//   HEAD_CLS: RobertaClassificationHead (KR_POOL_CLASSIFY): out [B, L] = Wo . tanh(Wd . x + bd) + bo of the raw CLS row.
+//   HEAD_MODERN_CLS: ModernBertForSequenceClassification's, Wo . LayerNorm(erf_gelu(Wd . x + bd)) + bo of the raw CLS row or (config.classifier_pooling = 1) mean.
+enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT };
+enum : uint8_t { REQUIRED = 1, HALF = 2 };       // HALF: stored as the handle's 16-bit operand (a projection of the loops every layer uses), else fp32
+// workspace buffers that exist because of a head: the head's input rows [B, H]; the packed row of every [b, s] column; the sequence of every packed row; the
+// colbert product [T, P]
+enum : unsigned { WS_POOLED = 1, WS_SLOT_ROW = 2, WS_ROW_SEQ = 4, WS_CY = 8 };
+constexpr int HEAD_MAX_TENSORS = 6;
+struct HeadTensor { const char* name; Ext r, c, store_r; uint8_t flags; };     // store_r: the rows it is stored with (zero rows behind r)
+struct HeadDesc {
+    const char* subject;         // what a refusal calls the head's tensors (nullptr: the first one that was loaded)
+    const char* noun;            // "... finalized without <noun>"
+    const char* accepted;        // why another family does not take it
+    const char* whole;           // what "whole" means
+    int n; HeadTensor t[HEAD_MAX_TENSORS];
+    char dim; int dim_min, dim_max, dim_step;    // the free dimension XFREE (0: none)
+    unsigned families;           // bit per Family
+    int excludes[4];             // heads it is never next to, in the order they are reported; -1 ends the list
+    unsigned ws;
+};
+static const HeadDesc HEADS[HEAD_COUNT] = {
+    {nullptr, "an MLM head", "the MLM head of SPLADE is BertForMaskedLM's and is accepted on BERT handles", "the MLM head takes all six cls.predictions.* tensors or none", 6,
+     {{"cls.predictions.transform.dense.weight", XH, XH, XH, REQUIRED | HALF}, {"cls.predictions.transform.dense.bias", XH, X1, XH, REQUIRED},
+      {"cls.predictions.transform.LayerNorm.weight", XH, X1, XH, REQUIRED}, {"cls.predictions.transform.LayerNorm.bias", XH, X1, XH, REQUIRED},
+      {"cls.predictions.decoder.weight", XV, XH, XVPAD, REQUIRED | HALF}, {"cls.predictions.decoder.bias", XV, X1, XVPAD, REQUIRED}},
+     0, 0, 0, 0, 1u << BERT, {HEAD_CLS, HEAD_DENSE, HEAD_COLBERT, HEAD_SPARSE}, WS_ROW_SEQ},
+    {nullptr, "a colbert head", "bge-m3's token-level heads are accepted on BERT and RoBERTa / XLM-R handles", "a token-level head takes its weight and its bias or neither", 2,
+     {{"colbert_linear.weight", XFREE, XH, XFREE, REQUIRED | HALF}, {"colbert_linear.bias", XFREE, X1, XFREE, REQUIRED}},
+     'P', 128, 2048, 128, 1u << BERT, {HEAD_CLS, HEAD_DENSE, -1}, WS_SLOT_ROW | WS_CY},
+    {nullptr, "a sparse head", "bge-m3's token-level heads are accepted on BERT and RoBERTa / XLM-R handles", "a token-level head takes its weight and its bias or neither", 2,
+     {{"sparse_linear.weight", X1, XH, X1, REQUIRED}, {"sparse_linear.bias", X1, X1, X1, REQUIRED}},
+     0, 0, 0, 0, 1u << BERT, {HEAD_CLS, HEAD_DENSE, -1}, WS_SLOT_ROW},
+    {"dense.weight", "a Dense head", "the Dense head is part of T5 handles only (config.t5_feed_forward)", "", 1,
+     {{"dense.weight", XFREE, XH, XFREE, REQUIRED}}, 'P', 4, 2048, 4, 1u << T5, {-1}, WS_POOLED},
+    {"classifier.*", "a classification head", "the classification head Wo . tanh(Wd . x + bd) + bo is BERT's and RoBERTa's; this family's is not implemented",
+     "the classification head takes all four classifier.* tensors or none", 4,
+     {{"classifier.dense.weight", XH, XH, XH, REQUIRED}, {"classifier.dense.bias", XH, X1, XH, REQUIRED}, {"classifier.out_proj.weight", XFREE, XH, XFREE, REQUIRED},
+      {"classifier.out_proj.bias", XFREE, X1, XFREE, REQUIRED}},
+     'L', 1, 64, 1, 1u << BERT | 1u << MPNET, {HEAD_DENSE, -1}, WS_POOLED},
+    {nullptr, "ModernBert's classification head (head.dense / head.norm / classifier)",
+     "the head classifier . LayerNorm(gelu(head.dense . x)) is ModernBertForSequenceClassification's and is accepted on ModernBert handles (config.local_attention_layers)",
+     "ModernBert's classification head takes head.dense.weight, head.norm.weight, classifier.weight and classifier.bias together or none of them", 6,
+     {{"head.dense.weight", XH, XH, XH, REQUIRED}, {"head.dense.bias", XH, X1, XH, 0}, {"head.norm.weight", XH, X1, XH, REQUIRED}, {"head.norm.bias", XH, X1, XH, 0},
+      {"classifier.weight", XFREE, XH, XFREE, REQUIRED}, {"classifier.bias", XFREE, X1, XFREE, REQUIRED}},
+     'L', 1, 64, 1, 1u << MODERN, {-1}, WS_POOLED},
+};
+
+struct HeadState { int dim = 0; unsigned got = 0; };      // the free dimension (0: not known yet), one bit per tensor that was loaded
+inline bool head_whole(int head, const HeadState& s) {
+    for (int i = 0; i < HEADS[head].n; ++i)
+        if ((HEADS[head].t[i].flags & REQUIRED) && !(s.got & (1u << i))) return false;
+    return true;
+}
+inline const char* head_first(int head, const HeadState& s) {
+    if (HEADS[head].subject) return HEADS[head].subject;
+    int i = 0;
+    while (i < HEADS[head].n - 1 && !(s.got & (1u << i))) ++i;
+    return HEADS[head].t[i].name;
+}
+inline bool find_head_tensor(const char* name, int& head, int& idx) {
+    for (head = 0; head < HEAD_COUNT; ++head)
+        for (idx = 0; idx < HEADS[head].n; ++idx)
+            if (strcmp(name, HEADS[head].t[idx].name) == 0) return true;
+    return false;
+}
+// tensor `idx` of `head` arriving with `numel` elements: its shape, then the rule above.  dim: the head's free dimension after this load
+inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_t numel, const HeadState& s, bool finalized_once, int& dim) {
+    const HeadDesc& d = HEADS[head];
+    const HeadTensor& t = d.t[idx];
+    dim = s.dim;
+    if (t.r != XFREE) {
+        const int64_t want = extent(cfg, t.r) * extent(cfg, t.c);
+        if (numel != want && t.r == XV) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (vocab_size = %d rows)", t.name, (long long)numel, (long long)want, cfg.vocab);
+        if (numel != want) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", t.name, (long long)numel, (long long)want);
+    } else {
+        const int64_t cols = extent(cfg, t.c), n = numel / cols;
+        if (numel <= 0 || numel % cols != 0 || n < d.dim_min || n > d.dim_max || n % d.dim_step != 0)
+        {
+            char step[32] = "";
+            if (d.dim_step > 1) snprintf(step, sizeof(step), " and %c %% %d == 0", d.dim, d.dim_step);
+            return err(KR_EINVAL, "'%s' has %lld elements: expected [%c%s] with %d <= %c <= %d%s", t.name, (long long)numel, d.dim, t.c == XH ? ", hidden" : "", d.dim_min,
+                       d.dim, d.dim_max, step);
+        }
+        dim = (int)n;
+    }
+    if (finalized_once && !(s.got && head_whole(head, s))) return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without %s", t.name, d.noun);
+    if (finalized_once && dim != s.dim)
+        return err(KR_EINVAL, "'%s' with %c = %d after kr_encoder_finalize: the shape of the handle's head is fixed (it has %c = %d)", t.name, d.dim, dim, d.dim, s.dim);
+    if (s.dim && dim != s.dim) return err(KR_EINVAL, "'%s' with %c = %d: the handle already holds a tensor of this head with %c = %d", t.name, d.dim, dim, d.dim, s.dim);
+    return Error{};
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// settings
+// ---------------------------------------------------------------------------------------------------------
+// Settings travel through the name-addressed loader under the reserved prefix "config." (no tensor of an HF state dict starts with it), as floats.  One rule:
+// accepted before the handle's first finalize; later the same values are a no-op and anything else is refused (the family, the workspace and the meaning of
+// every tensor depend on them).  What the settings of a handle must add up to is describe()'s business.
+//   config.position_padding_idx = P: fairseq's position rule (RoBERTa / XLM-R: P + number of ids != P up to and including the column, P where the id is P).
+//   config.rotary_inv_freq: d_h / 2 values, HF's rotary_emb.inv_freq; config.rotary_inv_freq_local: the same for ModernBert's local layers.
+//   config.attention_half_window: local layers admit key columns within it of the query's.  config.local_attention_layers: one 0 / 1 flag per layer.
+//   config.t5_feed_forward: 0 = wo(relu(wi x)), 1 = wo(gelu_new(wi_0 x) * wi_1 x).
+//   config.classifier_pooling: the row ModernBert's classification head reads, 0 = [CLS] (also when never set), 1 = the masked mean; after the first finalize it
+//   is known to handles with that head only.
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_COUNT };
+enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
+struct SettingRow {
+    const char* name;
+    Ext count;             // how many values it takes (XANY: 1 .. SETTING_MAX_VALUES)
+    ValueRule rule;        // finite floats, 0 / 1 flags, or ONE integer in [lo, hi] (hi < 0: max_pos + hi), described by `expects`
+    int lo, hi;
+    const char* expects;
+    const char* unset;     // what a handle finalized without the setting is
+    int max_pos_limit;     // > 0: refused on a handle with more position rows (the rotary tables are built for at most 8192)
+    int dflt;              // >= 0: the value a handle finalized without the setting runs with, so that loading it later is a no-op
+    int needs_head;        // >= 0: after the first finalize the setting is known to handles with this head only
+};
+static const SettingRow SETTINGS[SET_COUNT] = {
+    {"config.position_padding_idx", X1, V_INT, 0, -2, "an integer in [0, max_position_embeddings - 2]", "BERT's position rule", 0, -1, -1},
+    {"config.rotary_inv_freq", XHALF_DH, V_FINITE, 0, 0, "", "no rotary positions: a BERT / RoBERTa / MPNet handle", 8192, -1, -1},
+    {"config.rotary_inv_freq_local", XHALF_DH, V_FINITE, 0, 0, "", "no local rotary table", 0, -1, -1},
+    {"config.attention_half_window", X1, V_INT, 1, 65536, "an integer >= 1", "no attention window", 0, -1, -1},
+    {"config.local_attention_layers", XANY, V_FLAGS, 0, 1, "", "not a ModernBert handle", 0, -1, -1},
+    {"config.t5_feed_forward", X1, V_INT, 0, 1, "0 (relu) or 1 (gated gelu_new)", "not a T5 handle", 0, -1, -1},
+    {"config.classifier_pooling", X1, V_INT, 0, 1, "0 ([CLS] row) or 1 (masked mean)", "the [CLS] row", 0, 0, HEAD_MODERN_CLS},
+};
+constexpr int64_t SETTING_MAX_VALUES = 4096;
+struct Settings {
+    std::vector<float> v[SET_COUNT];      // empty: never set
+    bool has(Setting s) const { return !v[s].empty(); }
+    int value(Setting s, int unset = -1) const { return v[s].empty() ? unset : (int)v[s][0]; }
+};
+inline int find_setting(const char* name) {
+    for (int i = 0; i < SET_COUNT; ++i) if (strcmp(name, SETTINGS[i].name) == 0) return i;
+    return -1;
+}
+// vals: `numel` host floats (not read when the count is wrong).  stored: whether `set` changed
+inline Error set_setting(const kr_bert_cfg& cfg, Settings& set, const HeadState* heads, bool finalized_once, const char* name, const float* vals, int64_t numel, bool& stored) {
+    stored = false;
+    const int si = find_setting(name);
+    if (si < 0) {
+        std::string known;
+        for (const SettingRow& r : SETTINGS) known += std::string(known.empty() ? "" : ", ") + r.name;
+        return err(KR_EINVAL, "unknown setting '%s' (known: %s)", name, known.c_str());
+    }
+    const SettingRow& r = SETTINGS[si];
+    if (r.count == XANY ? (numel < 1 || numel > SETTING_MAX_VALUES) : numel != extent(cfg, r.count))
+        return r.count == XHALF_DH ? err(KR_EINVAL, "%s takes d_h / 2 = %lld values, got %lld", name, (long long)extent(cfg, r.count), (long long)numel)
+             : r.count == X1 ? err(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel) : err(KR_EINVAL, "'%s': %lld values", name, (long long)numel);
+    if (r.max_pos_limit && cfg.max_pos > r.max_pos_limit)
+        return err(KR_EINVAL, "%s: max_position_embeddings = %d, rotary tables are built for at most %d", name, cfg.max_pos, r.max_pos_limit);
+    const int hi = r.hi < 0 ? cfg.max_pos + r.hi : r.hi;
+    for (int64_t i = 0; i < numel; ++i) {
+        const float x = vals[i];
+        if (r.rule != V_INT && !std::isfinite(x)) return err(KR_EINVAL, "'%s' holds a non-finite value", name);
+        if (r.rule == V_INT && (!(x >= (float)r.lo && x <= (float)hi) || x != (float)(int)x)) return err(KR_EINVAL, "%s = %g: expected %s (%d .. %d)", name, (double)x, r.expects, r.lo, hi);
+    }
+    const std::vector<float> v(vals, vals + numel);
+    if (finalized_once) {
+        if (r.needs_head >= 0 && !(heads[r.needs_head].got && head_whole(r.needs_head, heads[r.needs_head])))
+            return err(KR_EINVAL, "%s after kr_encoder_finalize: the handle was finalized without %s", name, HEADS[r.needs_head].noun);
+        const std::vector<float> now = set.v[si].empty() && r.dflt >= 0 ? std::vector<float>(1, (float)r.dflt) : set.v[si];
+        if (v == now) return Error{};
+        const char* more = numel > 1 ? ", ..." : "";
+        if (now.empty())
+            return err(KR_EINVAL, "%s = %g%s after kr_encoder_finalize: the handle was finalized without it (%s) and stays what it is", name, (double)v[0], more, r.unset);
+        return err(KR_EINVAL, "%s = %g%s after kr_encoder_finalize: it is fixed at the handle's first finalize (it has %g%s)", name, (double)v[0], more, (double)now[0],
+                   now.size() > 1 ? ", ..." : "");
+    }
+    if (r.rule == V_FLAGS)
+        for (float x : v) if (x != 0.f && x != 1.f) return err(KR_EINVAL, "'%s' takes one 0 / 1 flag per layer, got %g", name, (double)x);
+    set.v[si] = v;
+    stored = true;
+    return Error{};
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the plan
+// ---------------------------------------------------------------------------------------------------------
+// what was loaded: per slot 0 = never, else the Family of the name it came under (| GATED_NAME); the family of the bias table's name; the heads
+struct Loaded {
+    std::vector<uint8_t> got;
+    Family rel_fam = FAM_NONE;
+    HeadState heads[HEAD_COUNT];
+    explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0) {}
+};
+// A resolved tensor arriving with `numel` elements: its count.  The bias table [32, heads] (MPNet's name or T5's) has the rule of the heads: before the first
+// finalize it makes the handle an MPNet handle (a T5 handle needs it); afterwards a handle that has it takes new values (the weight sync reloads every
+// parameter) and a handle finalized without it refuses it.
+inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolved& r, int64_t numel, const Loaded& ld, bool finalized_once) {
+    if (r.slot == T_IGNORED) return Error{};
+    if (r.slot == T_RELBIAS && numel != r.numel)
+        return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets, and so do the T5 handles)", name,
+                   (long long)numel, (long long)r.numel, REL_BUCKETS, cfg.heads, REL_BUCKETS);
+    if (numel != r.numel) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)r.numel);
+    if (r.slot == T_RELBIAS && finalized_once && ld.rel_fam == FAM_NONE)
+        return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a relative attention bias and stays a BERT / RoBERTa handle", name);
+    return Error{};
+}
+// a resolved tensor has been stored: its slot (a fused ModernBert tensor: the slots it fills) carries the family of its name
+inline void mark_loaded(Loaded& ld, const Resolved& r) {
+    const uint8_t tag = (uint8_t)(r.fam | (r.gated ? GATED_NAME : 0));
+    uint8_t* g = r.layer >= 0 ? &ld.got[T_LAYER0 + (size_t)r.layer * L_COUNT] : nullptr;
+    if (r.slot == T_RELBIAS) ld.rel_fam = r.fam;
+    else if (r.slot == T_WQKV) g[L_QW] = g[L_KW] = g[L_VW] = tag;
+    else if (r.slot == T_WQKVB) g[L_QB] = g[L_KB] = g[L_VB] = tag;
+    else if (r.slot == T_WI) g[L_IW] = g[L_UW] = tag;
+    else if (r.slot == T_WIB) g[L_IB] = tag;
+    else if (r.slot >= 0) ld.got[r.slot] = tag;
+}
+// the slots a family needs; every other one is optional and zero unless loaded (T5's wi_1: needed with the gated FF)
+struct FamilyRow { Family fam; bool pre_ln, rms; unsigned embed, layer; };
+constexpr unsigned bits() { return 0; }
+template <class... T> constexpr unsigned bits(int b, T... rest) { return 1u << b | bits(rest...); }
+constexpr unsigned LAYER_MATRICES = bits(L_QW, L_KW, L_VW, L_OW, L_IW, L_FW), LAYER_NORMS = bits(L_LN1G, L_LN1B, L_LN2G, L_LN2B);
+static const FamilyRow FAMILIES[] = {
+    {FAM_NONE, false, false, 0, 0},
+    {BERT, false, false, bits(T_WORD, T_POS, T_TYPE, T_ELNG, T_ELNB), (1u << L_COUNT) - 1 - bits(L_UW)},
+    {MPNET, false, false, bits(T_WORD, T_POS, T_TYPE, T_ELNG, T_ELNB), (1u << L_COUNT) - 1 - bits(L_UW)},
+    {NOMIC, false, false, bits(T_WORD, T_TYPE, T_ELNG, T_ELNB), LAYER_MATRICES | LAYER_NORMS | bits(L_UW)},
+    {MODERN, true, false, bits(T_WORD, T_TYPE, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G, L_UW)},
+    {T5, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G)},
+};
+
+enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table)
+enum QkvKind : uint8_t { QKV_PLAIN, QKV_ROT, QKV_ROT_BIAS };                       // EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB (a ModernBert layer with attn.Wqkv.bias)
+enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2 };                 // plain, with the relative attention bias, under the sliding window (and the local rotary table)
+enum FfKind : uint8_t { FF_GELU, FF_SWIGLU, FF_GEGLU, FF_RELU, FF_GEGLU_TANH };    // EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH
+struct LayerPlan { QkvKind qkv; AttnMode attn; };
+struct ModelPlan {
+    Family family = FAM_NONE;
+    bool pre_ln = false, rms = false, rotary = false, rotary_local = false, rel_bias = false;
+    PosSource pos = POS_COLUMN;
+    int pad_idx = -1, half_window = 0;
+    std::vector<LayerPlan> layers;
+    FfKind ff = FF_GELU;
+    bool ff_gated = false;                 // w1 is [2 FF, H]
+    std::vector<int> zero_fill;            // optional slots that were not loaded
+    bool head[HEAD_COUNT] = {};
+    int head_dim[HEAD_COUNT] = {};
+    int classifier = -1;                   // the head KR_POOL_CLASSIFY runs (HEAD_CLS / HEAD_MODERN_CLS), -1: none
+    bool classify_mean = false;            // ... on the masked mean (config.classifier_pooling = 1)
+    int out_dim = 0, out_width = 0;        // columns of a pooled row; of the widest row `out` must hold, whatever the pool
+    unsigned ws = 0;                       // WS_*
+};
+
+inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded& ld, ModelPlan& plan) {
+    const bool rot = set.has(SET_ROTARY), modern = set.has(SET_LOCAL_LAYERS), t5 = set.has(SET_T5_FF), rel = ld.rel_fam != FAM_NONE;
+    const bool local_set = set.has(SET_ROTARY_LOCAL) || set.has(SET_HALF_WINDOW);
+    const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF);
+    const Family fam = t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
+    const std::vector<float>& flags = set.v[SET_LOCAL_LAYERS];
+    if (t5 && (pad_idx >= 0 || rot || modern || local_set))
+        return err(KR_EINVAL, "config.t5_feed_forward next to config.position_padding_idx / config.rotary_inv_freq* / config.local_attention_layers / "
+                              "config.attention_half_window: a T5 handle's one position scheme is its relative attention bias");
+    if (!modern && local_set)
+        return err(KR_EINVAL, "config.rotary_inv_freq_local / config.attention_half_window without config.local_attention_layers: they are settings of a ModernBert handle");
+    if (modern) {
+        if (pad_idx >= 0 || rel) return err(KR_EINVAL, "config.local_attention_layers next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
+        if (!rot) return err(KR_EINVAL, "config.local_attention_layers without config.rotary_inv_freq: a ModernBert handle rotates q and k");
+        if ((int)flags.size() != cfg.layers) return err(KR_EINVAL, "config.local_attention_layers holds %zu flags, the handle has %d layers", flags.size(), cfg.layers);
+        bool any_local = false;
+        for (float f : flags) any_local = any_local || f != 0.f;
+        if (any_local && (!set.has(SET_ROTARY_LOCAL) || !set.has(SET_HALF_WINDOW)))
+            return err(KR_EINVAL, "config.local_attention_layers flags local layers, but %s was never loaded", SETTINGS[set.has(SET_ROTARY_LOCAL) ? SET_HALF_WINDOW : SET_ROTARY_LOCAL].name);
+    }
+    // names and family agree: ModernBert's and T5's names on their own handles only, and nothing but them there (the token-type row has no name of theirs);
+    // the bias table under the family's own name
+    for (const Family f : {MODERN, T5})
+        for (size_t i = 0; i < ld.got.size(); ++i) {
+            if (!ld.got[i] || i == T_TYPE || (fam_of(ld.got[i]) == f) == (fam == f)) continue;
+            return fam == f ? err(KR_EINVAL, "weight slot %zu was loaded under another family's name: a handle with %s takes %s's names", i, SETTINGS[f == T5 ? SET_T5_FF : SET_LOCAL_LAYERS].name, family_name(f))
+                            : err(KR_EINVAL, "weight slot %zu was loaded under a %s name but %s was never loaded: load it before kr_encoder_finalize", i, family_name(f),
+                                  SETTINGS[f == T5 ? SET_T5_FF : SET_LOCAL_LAYERS].name);
+        }
+    if (rel && (ld.rel_fam == T5) != t5)
+        return err(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
+                                 : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
+    // the heads, in the table's order (a refusal names the first tensor of the head that was loaded): family, neighbours, whole
+    for (int h = 0; h < HEAD_COUNT; ++h) {
+        const HeadDesc& d = HEADS[h];
+        const HeadState& s = ld.heads[h];
+        if (!s.got) continue;
+        if (!(d.families & (1u << fam))) return err(KR_EINVAL, "'%s' on a %s handle: %s", head_first(h, s), family_name(fam), d.accepted);
+        for (int x = 0; x < 4 && d.excludes[x] >= 0; ++x)
+            if (const int o = d.excludes[x]; ld.heads[o].got)
+                return err(KR_EINVAL, "'%s' next to '%s': a handle has %s or %s, not both", head_first(h, s), HEADS[o].subject ? HEADS[o].subject : HEADS[o].t[0].name, d.noun, HEADS[o].noun);
+        for (int i = 0; i < d.n; ++i)
+            if ((d.t[i].flags & REQUIRED) && !(s.got & (1u << i))) return err(KR_ESTATE, "'%s' was never loaded: %s", d.t[i].name, d.whole);
+    }
+    if (set.has(SET_CLS_POOLING) && !(modern && ld.heads[HEAD_MODERN_CLS].got))
+        return err(KR_EINVAL, "config.classifier_pooling on a %s: it selects the row ModernBert's classification head reads",
+                   modern ? "ModernBert handle without head.dense / head.norm / classifier" : "handle that is no ModernBert handle");
+    if (t5) {
+        for (int li = 0; li < cfg.layers; ++li) {
+            const uint8_t* g = &ld.got[T_LAYER0 + (size_t)li * L_COUNT];
+            if (g[L_IW] && ((g[L_IW] & GATED_NAME) != 0) != (t5_ff == 1))
+                return err(KR_EINVAL, "layer %d: config.t5_feed_forward = %d takes DenseReluDense.%s", li, t5_ff, t5_ff ? "wi_0 / wi_1, not wi" : "wi, not wi_0 / wi_1");
+            if (g[L_UW] && t5_ff == 0) return err(KR_EINVAL, "layer %d: config.t5_feed_forward = 0 takes DenseReluDense.wi, not wi_0 / wi_1", li);
+        }
+        if (!rel) return err(KR_ESTATE, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight was never loaded");
+    }
+    if (rot && (pad_idx >= 0 || rel)) return err(KR_EINVAL, "config.rotary_inv_freq next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
+    // q / k and the intermediate projection are packed in another row order under NomicBert's names (enc_load_weight): names and family must agree
+    for (int li = 0; li < cfg.layers && !modern && !t5; ++li) {
+        const uint8_t* g = &ld.got[T_LAYER0 + (size_t)li * L_COUNT];
+        auto under = [&](int id, bool nomic) { return g[id] && (fam_of(g[id]) == NOMIC) == nomic; };
+        if (rot && (under(L_QW, false) || under(L_KW, false) || under(L_IW, false)))
+            return err(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj and mlp.{gate,up}_proj under NomicBert's names", li);
+        if (rot && (g[L_QB] || g[L_KB] || g[L_IB])) return err(KR_EINVAL, "layer %d: the q / k / gate / up projections of a NomicBert handle have no bias", li);
+        if (!rot && (under(L_QW, true) || under(L_KW, true) || under(L_IW, true) || g[L_UW]))
+            return err(KR_EINVAL, "layer %d holds tensors under NomicBert's names but config.rotary_inv_freq was never loaded: load it before kr_encoder_finalize", li);
+    }
+    const FamilyRow& fr = FAMILIES[fam];
+    plan = ModelPlan{};
+    for (size_t i = 0; i < ld.got.size(); ++i) {
+        const int layer = i < T_LAYER0 ? -1 : (int)((i - T_LAYER0) / L_COUNT), id = i < T_LAYER0 ? (int)i : (int)((i - T_LAYER0) % L_COUNT);
+        const bool needed = layer < 0 ? (fr.embed >> id) & 1u : ((fr.layer >> id) & 1u) || (id == L_UW && t5_ff == 1);
+        if (ld.got[i]) continue;
+        if (needed) return err(KR_ESTATE, "weight slot %zu (layer %d, tensor %d) was never loaded", i, layer, id);
+        plan.zero_fill.push_back((int)i);
+    }
+    plan.family = fam; plan.pre_ln = fr.pre_ln; plan.rms = fr.rms; plan.rotary = rot; plan.rotary_local = set.has(SET_ROTARY_LOCAL); plan.rel_bias = rel;
+    plan.pos = t5 ? POS_BIAS_ONLY : rot ? POS_ROTARY : pad_idx >= 0 ? POS_FAIRSEQ : POS_COLUMN;
+    plan.pad_idx = pad_idx; plan.half_window = set.value(SET_HALF_WINDOW, 0);
+    for (int li = 0; li < cfg.layers; ++li)
+        plan.layers.push_back({!rot ? QKV_PLAIN : modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] ? QKV_ROT_BIAS : QKV_ROT,
+                               rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
+    plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot ? FF_SWIGLU : FF_GELU;
+    plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
+    plan.out_dim = cfg.hidden;
+    for (int h = 0; h < HEAD_COUNT; ++h) {
+        plan.head[h] = ld.heads[h].got != 0;
+        plan.head_dim[h] = ld.heads[h].dim;
+        if (plan.head[h]) plan.ws |= HEADS[h].ws;
+    }
+    if (plan.head[HEAD_DENSE]) plan.out_dim = plan.head_dim[HEAD_DENSE];
+    plan.classifier = plan.head[HEAD_CLS] ? (int)HEAD_CLS : plan.head[HEAD_MODERN_CLS] ? (int)HEAD_MODERN_CLS : -1;
+    plan.classify_mean = set.value(SET_CLS_POOLING) == 1;
+    plan.out_width = plan.classifier >= 0 && plan.head_dim[plan.classifier] > plan.out_dim ? plan.head_dim[plan.classifier] : plan.out_dim;
+    return Error{};
+}
+
+}  // namespace model
+}  // namespace kr
