@@ -345,6 +345,30 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   out [B, P] = normalize(W . pooled) instead of [B, hidden] (the caller knows P from the tensor it loaded); an all-masked sequence still gives a NaN row.
  *   Like the settings it is fixed at the first finalize: later the same P takes new values, another P — or the tensor on a handle finalized without it — is
  *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]).
+ *   "config.deberta_position_buckets" + "config.deberta_max_relative_positions": data = ONE float each, Bk (even, 2 .. 256) and M (M - 1 > Bk / 2):
+ *   DebertaV2Config's position_buckets and max_relative_positions (max_position_embeddings where that is < 1).  The two together, loaded before the first
+ *   finalize, make the handle a DeBERTa handle (DebertaV2Model: microsoft/deberta-v3-* and their fine-tunes) for life; the usual rule of the settings holds
+ *   (later the same value is a no-op, another is KR_EINVAL); one without the other, or either next to any other position scheme, is KR_EINVAL at finalize;
+ *   max_pos <= 8192.  On such a handle
+ *     - the stack is BERT's post-LN layer with erf-GELU; the embedding is LayerNorm(word[id]): no position table and no token-type table are required (a
+ *       position table is refused), type_vocab = 1;
+ *     - every attention score is (q_i . k_j + q_i . PK[p] + k_j . PQ[p]) / sqrt(3 d_h), p = clamp(delta(c_i - c_j) + Bk, 0, 2 Bk - 1), c = the token's column
+ *       in the padded [B, S] batch, delta(r) = r for |r| <= Bk / 2, else sign(r) (ceil(ln(|r| / mid) / ln((M - 1) / mid) (mid - 1)) + mid), mid = Bk / 2
+ *       (make_log_bucket_position); PQ = query_proj(R), PK = key_proj(R) with the layer's OWN projections, biases included (share_att_key), R =
+ *       LayerNorm(rel_embeddings) or, without "encoder.LayerNorm.*", the raw table.  PQ / PK are built at finalize; only column differences enter, so a
+ *       sequence gives the same rows under right and left padding;
+ *     - DebertaV2Model's state dict loads unchanged: "embeddings.word_embeddings.weight", "embeddings.LayerNorm.{weight,bias}",
+ *       "encoder.layer.N.attention.self.{query_proj,key_proj,value_proj}.{weight,bias}", every other layer tensor under BERT's names,
+ *       "encoder.rel_embeddings.weight" [2 Bk, hidden] (missing: KR_ESTATE "never loaded"; another row count: KR_EINVAL) and "encoder.LayerNorm.{weight,bias}"
+ *       [hidden] (both or neither).  These names on a handle of another kind, and other families' names for q / k / v on this one, are KR_EINVAL at
+ *       finalize, naming the tensor;
+ *     - pools 0, 1 and (with the head below) 2 run through all three forward entry points, kr_encoder_forward_packed included; S <= max_pos; under CLS
+ *       pooling / classify a row whose column 0 is masked is finite but has no HF counterpart (HF attends uniformly over masked columns there);
+ *     - "classifier.dense.*" / "classifier.out_proj.*" (below) are accepted and compute DebertaV2ForSequenceClassification's ContextPooler + classifier:
+ *       logits = out_proj.weight . gelu(dense.weight . x + dense.bias) + out_proj.bias — erf-GELU where BERT's head has tanh; bge-m3's heads, the MLM head
+ *       and "dense.weight" are refused;
+ *     - the workspace holds heads x 2 x W fp32 position scores per token (W <= 512: the buckets the batch's S reaches, rounded up to 32), the handle one
+ *       fp32 copy of every layer's query_proj / key_proj matrix.
  * Sequence classification (cross-encoder rerankers: BAAI/bge-reranker-base / -large / -v2-m3 = XLMRobertaForSequenceClassification,
  * cross-encoder/ms-marco-MiniLM-L-6-v2 / -L-12-v2 / ms-marco-TinyBERT = BertForSequenceClassification): the head travels under ONE spelling,
  * RobertaClassificationHead's,

@@ -17,10 +17,11 @@
 //
 // Files.  This one: the Encoder handle, the workspace, launch selection, the forward, the entry points.  encoder_model.hpp: what a handle is (host-only).
 // encoder_weights.hpp: creation, the loader, finalize.  Device code per operand type: encoder_rows.hpp (residual-stream codec, embedding, LayerNorm, pooling),
-// encoder_proj.hpp (projections), encoder_attn.hpp (attention).  encoder_pack.hip: the token-packing front end.
+// encoder_proj.hpp (projections), encoder_attn.hpp (attention), encoder_pos.hpp (DeBERTa's position scores).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
 #include "encoder_proj.hpp"
 #include "encoder_attn.hpp"
+#include "encoder_pos.hpp"
 #include "encoder_pack.hpp"
 #include "encoder_model.hpp"
 
@@ -43,6 +44,9 @@ struct LayerW {
     // per 32-row tile)
     bool gated = false;
     float* b1p = nullptr;   // ModernBert handles: the bias of the [2 FF, H] projection in its rows' order (zero unless mlp.Wi.bias was loaded)
+    // DeBERTa handles: query_proj / key_proj as loaded (fp32 [H, H]); PQ / PK = their projections of the position table, [heads][TP][d_h] 16-bit (build_disent_tables)
+    float *wq32 = nullptr, *wk32 = nullptr;
+    uint16_t *pq16 = nullptr, *pk16 = nullptr;
 };
 
 // A/B switches of the projection / attention launches, read from the environment ONCE per forward (enqueue_forward), not per launch: a forward is 96
@@ -65,6 +69,7 @@ struct Knobs {
 using model::AM_PLAIN;
 using model::AM_BIAS;
 using model::AM_WIN;
+using model::AM_DISENT;
 
 struct Encoder {
     kr_bert_cfg cfg{};
@@ -89,6 +94,11 @@ struct Encoder {
     // the relative attention bias as loaded (host) and the table the attention kernels read (AttnBiasArgs), built by finalize
     std::vector<float> rel_w;
     float* bias_tab = nullptr; int bias_width = 0;
+    // DeBERTa handles: the position table and its norm as loaded (host); the bucket of every column difference (device, [2 max_pos - 1]); the workspace of
+    // k_pos_scores, [capT][heads][2][capW] fp32 (ensure_ws)
+    std::vector<float> rel_emb, rel_lng, rel_lnb;
+    int* deb_bucket = nullptr;
+    float* pos_sc = nullptr; int capW = 0;
     bool bias_gather = false;  // KIRAG_AMD_ATTN_BIAS_GATHER=1 at kr_encoder_create: key columns always from tok_pos (the path of masks with holes), for tests
     // rotary handles: cos / sin [max_pos][d_h / 2] of the global and the local frequencies; zero_row: H zeros (the embedding's position row; k_ln16_head's bias)
     float *rot_cos = nullptr, *rot_sin = nullptr, *rot_cos_l = nullptr, *rot_sin_l = nullptr, *zero_row = nullptr;
@@ -156,12 +166,23 @@ static void free_bufs(std::vector<void**>& owner) {
 static void free_ws(Encoder* e) {
     if (!e->graphs.empty()) { (void)hipDeviceSynchronize(); drop_graphs(e); }   // captured kernels hold workspace pointers
     free_bufs(e->ws_bufs);
-    e->capT = 0; e->capB = 0; e->capBS = 0;
+    e->capT = 0; e->capB = 0; e->capBS = 0; e->capW = 0;
+}
+
+// DeBERTa handles: the buckets a batch of width S can reach, [p0, p0 + W) with p0 and W multiples of 32 inside the table's TP = round_up(2 Bk, 32) rows: column
+// differences lie in [-(S - 1), S - 1], the bucket rule is odd and monotonic
+static void pos_span(const Encoder* e, int S, int& p0, int& W) {
+    const int Bk = e->plan.deb_buckets;
+    const int lo = model::deberta_bucket(-(S - 1), Bk, e->plan.deb_max_rel), hi = model::deberta_bucket(S - 1, Bk, e->plan.deb_max_rel);
+    p0 = lo & ~31;
+    W = (int)round_up(hi + 1 - p0, 32);
 }
 
 static int ensure_ws(Encoder* e, int B, int S) {
     const int64_t maxT = (int64_t)B * (S + 8);
     const int H = e->cfg.hidden, FF = e->cfg.intermediate;
+    int span_p0 = 0, span_W = 0;
+    if (e->plan.family == model::DEBERTA) pos_span(e, S, span_p0, span_W);
     if (!e->d_T) {
         KR_TRY(dmalloc(e->own_bufs, &e->d_T, sizeof(int))); KR_TRY(dmalloc(e->own_bufs, &e->d_err, sizeof(int)));
         KR_HIP(hipMemset(e->d_err, 0, sizeof(int)));
@@ -169,7 +190,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
         *e->h_err = 0;
         KR_HIP(hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming));
     }
-    if (maxT <= e->capT && B <= e->capB && (int64_t)B * S <= e->capBS) return 0;
+    if (maxT <= e->capT && B <= e->capB && (int64_t)B * S <= e->capBS && span_W <= e->capW) return 0;
     if (maxT > (int64_t)1 << 24) return fail(KR_EINVAL, "batch of %lld tokens: at most 2^24 per forward (32-bit offsets inside the attention kernels)", (long long)maxT);
     free_ws(e);
     const int64_t capT = round_up(maxT, 256), capB = B, capBS = (int64_t)B * S;   // multiple of the 256-token tile: see k_proj
@@ -184,6 +205,10 @@ static int ensure_ws(Encoder* e, int B, int S) {
     if (p.rotary) {
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
         KR_TRY(dmalloc(e->ws_bufs, &e->tok_rpos, capT * 4)); KR_HIP(hipMemset(e->tok_rpos, 0, (size_t)capT * 4));
+    }
+    if (p.pos == model::POS_DISENT) {      // no position row either (a zero row), and the position scores of every packed row: heads x 2 x W floats per token
+        KR_TRY(dmalloc(e->ws_bufs, &e->tok_zero, capT * 4)); KR_HIP(hipMemset(e->tok_zero, 0, (size_t)capT * 4));
+        KR_TRY(dmalloc(e->ws_bufs, &e->pos_sc, (size_t)capT * e->cfg.heads * 2 * span_W * 4));
     }
     KR_TRY(dmalloc(e->ws_bufs, &e->xlo, capT * H)); KR_TRY(dmalloc(e->ws_bufs, &e->y, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->out, (size_t)capB * p.out_width * 4));
     if (p.ws & model::WS_POOLED) KR_TRY(dmalloc(e->ws_bufs, &e->pooled, (size_t)capB * H * 4));
@@ -212,7 +237,7 @@ static int ensure_ws(Encoder* e, int B, int S) {
         KR_HIP(hipMemset(e->c_ctx, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xb, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xlo, 0x80, (size_t)capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_off, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_nk, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_cls, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->d_B, sizeof(int)));
     }
-    e->capT = capT; e->capB = (int)capB; e->capBS = capBS;
+    e->capT = capT; e->capB = (int)capB; e->capBS = capBS; e->capW = span_W;
     return 0;
 }
 
@@ -227,30 +252,32 @@ namespace KR_ENC_NS {
 static AttnBiasArgs bias_args(const Encoder* e) { return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0}; }
 static AttnWinArgs win_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->plan.half_window, e->bias_gather ? 1 : 0}; }
 // AM: the attention of a layer (model::AttnMode)
+// (p0, W: pos_span of the forward's S — the layout k_pos_scores wrote this layer's scores in)
 template <int AM>
-static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN> attn_mode_args(const Encoder* e) {
-    if constexpr (AM == AM_BIAS) return bias_args(e);
+static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN, AM == AM_DISENT> attn_mode_args(const Encoder* e, int p0, int W) {
+    if constexpr (AM == AM_DISENT) return AttnDisentArgs{e->pos_sc, e->tok_pos, e->deb_bucket, e->cfg.max_pos - 1, p0, W, e->cfg.heads};
+    else if constexpr (AM == AM_BIAS) return bias_args(e);
     else if constexpr (AM == AM_WIN) return win_args(e);
     else return AttnNoBiasArgs{};
 }
 
 template <int DH, int HPB, int AM>
-static int launch_attn(const Encoder* e, int B, int cap, int nqt, hipStream_t st) {
+static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W, hipStream_t st) {
     const int H = e->cfg.hidden, heads = e->cfg.heads;
     // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
     // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
     const int kchunk = cap < 128 ? cap : 128;
     const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
-    constexpr bool BIAS = AM == AM_BIAS, WIN = AM == AM_WIN;
+    constexpr bool BIAS = AM == AM_BIAS, WIN = AM == AM_WIN, DIS = AM == AM_DISENT;
     static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance (one per instantiation of this function)
     int& attr_lds = attr_lds_dev[e->device & 63];
     if (lds > attr_lds) {
-        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN, DIS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_lds = lds;
     }
     const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
-    const auto ba = attn_mode_args<AM>(e);
-    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
+    const auto ba = attn_mode_args<AM>(e, p0, W);
+    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN, DIS>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
                        e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, ba);
     return 0;
 }
@@ -260,19 +287,20 @@ static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
     const int64_t pairs = (int64_t)B * e->cfg.heads;
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
-    const auto ba = attn_mode_args<AM>(e);
+    const auto ba = attn_mode_args<AM>(e, 0, 0);
     hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, AM == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
                        e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, ba);
     return 0;
 }
 
 // the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
+// (AM_DISENT is built into the register-staged kernel only: a DeBERTa forward never asks for the ring, see enqueue_forward)
 template <int DH, int AM>
-static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, hipStream_t st) {
-    if (long_seq) return launch_attn_dma<DH, AM>(e, B, nqt, st);
-    if (nqt >= 3) return launch_attn<DH, 1, AM>(e, B, cap, nqt, st);
-    if (nqt == 2) return launch_attn<DH, 2, AM>(e, B, cap, nqt, st);
-    return launch_attn<DH, 4, AM>(e, B, cap, nqt, st);
+static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, int p0, int W, hipStream_t st) {
+    if constexpr (AM != AM_DISENT) { if (long_seq) return launch_attn_dma<DH, AM>(e, B, nqt, st); }
+    if (nqt >= 3) return launch_attn<DH, 1, AM>(e, B, cap, nqt, p0, W, st);
+    if (nqt == 2) return launch_attn<DH, 2, AM>(e, B, cap, nqt, p0, W, st);
+    return launch_attn<DH, 4, AM>(e, B, cap, nqt, p0, W, st);
 }
 
 // The runtime epilogue as a compile-time constant: f(std::integral_constant<int, EPI>{}) for the epilogues of encoder_proj.hpp.  What a launch site does not
@@ -426,7 +454,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const bool splade = pool == KR_POOL_SPLADE;
     if (splade) pool = KR_POOL_MEAN;
     const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
-    const bool long_seq = nqt_max > 4 && !e->kn.attn_lds;                          // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
+    const bool disent = p.pos == POS_DISENT;                                       // a DeBERTa handle: every sequence through k_attn_lds (the mode is not built into k_attn_dma)
+    const bool long_seq = nqt_max > 4 && !e->kn.attn_lds && !disent;               // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
+    int span_p0 = 0, span_W = 0;
+    if (disent) pos_span(e, S, span_p0, span_W);
     const int align = long_seq ? 8 : 4;                                            // sequence offsets: multiple of 8 tokens so that V^T chunks start 16-B aligned
     const PackRules rules{e->cfg.vocab, e->cfg.type_vocab, pool, align, p.pad_idx};
     const SeqTables seq{e->seq_nk, e->seq_has0, e->seq_nq, e->seq_off, e->seq_cls, e->d_T};
@@ -454,8 +485,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         auto embed_kernel = H <= 512 ? &k_embed_rms<1> : H <= 1024 ? &k_embed_rms<2> : &k_embed_rms<4>;
         hipLaunchKernelGGL(embed_kernel, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->d_T, e->word, e->elng, eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
     } else {
-        hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, p.pos == POS_ROTARY ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T,
-                           e->word, p.pos == POS_ROTARY ? e->zero_row : e->pos, e->type, e->elng, e->elnb, eps, H,
+        const bool no_pos = p.pos == POS_ROTARY || disent;      // a zero row in place of a position row
+        hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, no_pos ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T,
+                           e->word, no_pos ? e->zero_row : e->pos, e->type, e->elng, e->elnb, eps, H,
                            e->use_lo ? e->xlo : nullptr, e->xb);
     }
     const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr && !flags;      // the token-level heads read every row of the last layer
@@ -516,8 +548,13 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
             const int am = lp.attn;
             auto go = [&](auto dh) -> int {
                 constexpr int DH = decltype(dh)::value;
-                return am == AM_BIAS ? launch_attention<DH, AM_BIAS>(e, B, cap, nqt_max, long_seq, st)
-                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, st);
+                if (am == AM_DISENT) {      // q . PK and k . PQ of every packed row, for the bias tiles of this layer's attention
+                    const dim3 grid((unsigned)((maxT + POS_ROWS - 1) / POS_ROWS), (unsigned)e->cfg.heads);
+                    hipLaunchKernelGGL(k_pos_scores<DH>, grid, dim3(256), 0, st, e->q, e->k, e->d_T, H, e->cfg.heads, l.pk16, l.pq16, (int)round_up(2 * p.deb_buckets, 32), span_p0, span_W, e->pos_sc);
+                    return launch_attention<DH, AM_DISENT>(e, B, cap, nqt_max, long_seq, span_p0, span_W, st);
+                }
+                return am == AM_BIAS ? launch_attention<DH, AM_BIAS>(e, B, cap, nqt_max, long_seq, 0, 0, st)
+                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, 0, 0, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, 0, 0, st);
             };
             if (H == 32 * e->cfg.heads) KR_TRY(go(std::integral_constant<int, 32>{})); else KR_TRY(go(std::integral_constant<int, 64>{}));
         }
@@ -572,6 +609,11 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
             KR_TRY(set_lds_once(reinterpret_cast<const void*>(gln_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));
             hipLaunchKernelGGL(gln_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_MODERN_CLS, 0), e->hf(HEAD_MODERN_CLS, 1),
                                e->hf(HEAD_MODERN_CLS, 4), e->hf(HEAD_MODERN_CLS, 5), B, H, p.head_dim[HEAD_MODERN_CLS], e->out, e->hf(HEAD_MODERN_CLS, 2), e->hf(HEAD_MODERN_CLS, 3), eps, r.nk, e->d_err);
+        } else if (p.cls_gelu) {                     // DeBERTa's: Wo . erf_gelu(Wd . pooled + bd) + bo, same LDS
+            auto gelu_kernel = NJ == 1 ? &k_cls_head<1, false, true> : NJ == 2 ? &k_cls_head<2, false, true> : NJ == 4 ? &k_cls_head<4, false, true> : &k_cls_head<8, false, true>;
+            KR_TRY(set_lds_once(reinterpret_cast<const void*>(gelu_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));
+            hipLaunchKernelGGL(gelu_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_CLS, 0), e->hf(HEAD_CLS, 1), e->hf(HEAD_CLS, 2),
+                               e->hf(HEAD_CLS, 3), B, H, p.head_dim[HEAD_CLS], e->out, nullptr, nullptr, 0.f, r.nk, e->d_err);
         } else
         hipLaunchKernelGGL(head_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_CLS, 0), e->hf(HEAD_CLS, 1), e->hf(HEAD_CLS, 2), e->hf(HEAD_CLS, 3), B, H,
                            p.head_dim[HEAD_CLS], e->out, nullptr, nullptr, 0.f, nullptr, nullptr);

@@ -13,6 +13,7 @@ namespace KR_ENC_NS {
 //   k_attn_lds  sequences of at most 128 tokens: K / V^T of the block's heads staged through registers, one block per (sequence, HPB heads, 4 / HPB q-tiles)
 //   k_attn_dma  longer sequences: K / V^T chunks of 64 keys stream through a 3-stage LDS ring by LDS-DMA (two chunks in flight behind the one being
 //               multiplied, one barrier per chunk), one block per (sequence, head, 8 q-tiles): two q-tiles per wave share every staged chunk
+// (DeBERTa's disentangled position terms, AttnDisentArgs below, are built into k_attn_lds only: such a handle runs it at every length.)
 // Common scheme per wave and 32-query tile: S^T = K.Q^T (keys on accumulator rows, so the softmax row reductions are in-lane + one shfl_xor 32), online
 // softmax over 64-key steps, P^T fed from the accumulator straight into the V^T.P^T MFMA.  The key that sits on A-tile row i of a 32-key tile is
 // perm(i) = i with bits 2 and 3 exchanged: a lane's registers 8a .. 8a+7 then hold 8 CONSECUTIVE keys (16 a + 8 hf .. + 7), i.e. the P^T fragment of a
@@ -83,12 +84,27 @@ struct AttnWinArgs {
     int w;                // half-window (>= 1)
     int gather;           // != 0: take every key's column from `col` even when they are consecutive
 };
-template <bool BIAS, bool WIN = false> using AttnBiasArg = std::conditional_t<BIAS, AttnBiasArgs, std::conditional_t<WIN, AttnWinArgs, AttnNoBiasArgs>>;
+// Disentangled attention (DeBERTa-v2 / v3): score(head, query i, key j) += q_i . PK[p] + k_j . PQ[p], p = deberta_bucket(col_i - col_j) (encoder_model.hpp),
+// in the log2 units of q . k (the scale log2(e) / sqrt(3 d_h) is folded into query_proj and into PQ).  Both products of every packed row with every table row a
+// batch can reach are computed per layer by k_pos_scores (encoder_pos.hpp) into `sc`: [row][head][C2P | P2C][W] fp32, entry w = bucket p0 + w.  The bias TILE
+// of a step is gathered from there — C2P from the lane's own query row, P2C from each key's row (for a fixed key the 32 lanes read consecutive entries) — and
+// handed to the first S^T MFMA as its C operand, where attn_bias_tile puts MPNet's values.  Every key's column comes from tok_pos (the gather path), so right
+// padding, left padding and holes in the mask are one code path, and a sequence's rows depend on column DIFFERENCES only.
+struct AttnDisentArgs {
+    const float* sc;      // [rows][heads][2][W]
+    const int* col;       // tok_pos
+    const int* bucket;    // [2 max_pos - 1]: entry max_pos - 1 + r = deberta_bucket(r)
+    int center;           // max_pos - 1
+    int p0, W;            // the buckets [p0, p0 + W) are computed for this batch
+    int heads;
+};
+template <bool BIAS, bool WIN = false, bool DIS = false>
+using AttnBiasArg = std::conditional_t<DIS, AttnDisentArgs, std::conditional_t<BIAS, AttnBiasArgs, std::conditional_t<WIN, AttnWinArgs, AttnNoBiasArgs>>>;
 
 // BM (mode of a kernel body, block-uniform): 0 plain, 1 bias with consecutive key columns, 2 bias with gathered key columns, 3 window with consecutive key
 // columns, 4 / 5 window with gathered key columns (4: k_attn_dma, 16-byte loads; 5: k_attn_lds, one load per key — the same values either way).  The choice between 1 and 2 (3 and 4) is made once per block, outside the key loops (a branch inside them
-// costs the accumulators register copies at every join)
-template <int BM> using AttnModeArg = AttnBiasArg<BM == 1 || BM == 2, BM >= 3>;
+// costs the accumulators register copies at every join).  6: disentangled position terms (gathered key columns, k_attn_lds only)
+template <int BM> using AttnModeArg = AttnBiasArg<BM == 1 || BM == 2, BM >= 3 && BM <= 5, BM == 6>;
 struct AttnNoBias { static constexpr bool on = false, win = false; };
 template <int GATHER>       // 0: consecutive key columns, 1: gathered with 16-byte loads, 2: gathered key by key
 struct AttnWinLane {
@@ -106,6 +122,17 @@ struct AttnBiasLane {
     int lane0;            // width / 2 - column of this lane's query + 8 hf (+ the column of key 0 when the columns are consecutive)
     int nk;
 };
+struct AttnDisentLane {
+    static constexpr bool on = true, win = false;
+    const float* sc;      // row 0 of the sequence in AttnDisentArgs::sc (wave-uniform)
+    const int* col;       // columns of the sequence's packed rows
+    const int* bucket;
+    int i0;               // center + column of this lane's query: bucket[i0 - col_key] = p
+    unsigned qoff;        // this lane's C2P row (query, head) in floats from sc, less p0
+    unsigned hoff;        // the head's P2C row of key 0 in floats from sc, less p0 (wave-uniform)
+    unsigned stride;      // floats per packed row
+    int nk;
+};
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load at a 4-byte aligned address (one global_load_dwordx4)
 typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -117,7 +144,20 @@ __device__ __forceinline__ bool attn_bias_gathers(const Args& ba, int64_t off, i
 
 template <int BM>
 __device__ __forceinline__ auto attn_bias_lane(const AttnModeArg<BM>& ba, int64_t off, int nk, int head, int qi, int hf) {
-    if constexpr (BM >= 3) {
+    if constexpr (BM == 6) {
+        // offsets inside one sequence: (max_pos + 1 <= 8193 rows) x (stride <= 2^16 floats) < 2^30 floats
+        const int* col = ba.col + off;
+        AttnDisentLane dl;
+        dl.stride = 2u * (unsigned)ba.W * (unsigned)ba.heads;
+        dl.sc = ba.sc + off * (int64_t)dl.stride;
+        dl.col = col;
+        dl.bucket = ba.bucket;
+        dl.i0 = ba.center + col[qi];
+        dl.hoff = (unsigned)(head * 2 * ba.W + ba.W - ba.p0);
+        dl.qoff = (unsigned)qi * dl.stride + (unsigned)(head * 2 * ba.W - ba.p0);
+        dl.nk = nk;
+        return dl;
+    } else if constexpr (BM >= 3) {
         const int* col = ba.col + off;
         AttnWinLane<BM - 3> wl;
         wl.col = col;
@@ -156,6 +196,16 @@ __device__ __forceinline__ void attn_bias_tile(f32x16& st, const AttnBiasLane<GA
             const int key = kb + 16 * (r >> 3) + 8 * hf + (r & 7);
             st[r] = bl.tab[(unsigned)(bl.lane0 - 8 * hf + bl.col[(unsigned)min(key, bl.nk - 1)])];     // keys >= nk are masked below: any entry will do
         }
+    }
+}
+// the disentangled position terms of one 32-key tile, same register layout
+__device__ __forceinline__ void attn_bias_tile(f32x16& st, const AttnDisentLane& dl, int kb, int hf) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int key = min(kb + 16 * (r >> 3) + 8 * hf + (r & 7), dl.nk - 1);      // keys >= nk are masked below: any entry will do
+        const unsigned p = (unsigned)dl.bucket[(unsigned)(dl.i0 - dl.col[(unsigned)key])];
+        st[r] = dl.sc[dl.qoff + p] + dl.sc[(unsigned)key * dl.stride + dl.hoff + p];
     }
 }
 // the window of one 32-key tile: scores of keys outside |col_key - col_query| <= w become -inf (kb = index of the tile's first key in its sequence)
@@ -392,7 +442,7 @@ template <int DH, int HPB, int BM>
 __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
                                               int H, int heads, int kchunk, uint16_t* __restrict__ ctx, const AttnModeArg<BM>& ba, char* smem) {
-    constexpr bool WIN = BM >= 3;
+    constexpr bool WIN = BM >= 3 && BM <= 5;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; as a scalar, the head / q-tile / LDS bases derived from it cost no VGPRs
     const int hb = blockIdx.x, b = blockIdx.y;            // heads fastest: the heads of one sequence (same 2-KiB q/k rows) run together
@@ -540,13 +590,15 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
     attn_store_tile<DH, WIN>(st, Os, ctx, off, q0, nq, H, head, lane);
 }
 
-template <int DH, int HPB, bool BIAS = false, bool WIN = false>
+template <int DH, int HPB, bool BIAS = false, bool WIN = false, bool DIS = false>
 __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS, WIN> ba) {
-    static_assert(!(BIAS && WIN), "a relative attention bias under a window is not instantiated");
+                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS, WIN, DIS> ba) {
+    static_assert(!(BIAS && WIN) && !(DIS && (BIAS || WIN)), "a relative attention bias under a window is not instantiated, nor either next to the disentangled terms");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (WIN) {
+    if constexpr (DIS) {
+        attn_lds_body<DH, HPB, 6>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+    } else if constexpr (WIN) {
         const int b = blockIdx.y;
         if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 5>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
         else attn_lds_body<DH, HPB, 3>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
@@ -585,7 +637,7 @@ struct AdmaGeom {
 template <int DH, int BM>
 __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, const AttnModeArg<BM>& ba) {
-    constexpr bool WIN = BM >= 3;
+    constexpr bool WIN = BM >= 3;      // (never 6: the disentangled terms are built into k_attn_lds only)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hf = lane >> 5;
     using G = AdmaGeom<DH>;

@@ -1,4 +1,4 @@
-// What an encoder handle IS, decided in one place and without a device: the state-dict names of the five model families, the heads, the settings, and
+// What an encoder handle IS, decided in one place and without a device: the state-dict names of the six model families, the heads, the settings, and
 // describe(), which turns what was loaded into a ModelPlan (or the refusal kr_encoder_finalize returns).  Host-only: nothing here includes HIP, so the
 // tables are tested by a stand-alone program (tests/capi/encoder_model_check.cpp).  The device side of every row lives in encoder_weights.hpp (where a
 // slot is stored) and encoder.hip (enqueue_forward: which launches a plan selects).  Adding a family or a head: DESIGN.md, "Adding a family / a head".
@@ -37,15 +37,20 @@ inline Error err(int code, const char* fmt, ...) {
 //   unless loaded.  MODERN (config.local_attention_layers, needs config.rotary_inv_freq): a PRE-LN stack — the residual stream is kept apart from the normalised
 //   operand, attn_norm of layer N runs in the launch behind the MLP of layer N - 1 — with GEGLU and, in the layers flagged local, a sliding window and the
 //   local rotary table.  T5 (config.t5_feed_forward, T5EncoderModel): MODERN's schedule with RMS norms, the embedding row straight into the residual stream, a
-//   relative attention bias in every layer with scores q.k + bias (no 1 / sqrt(d_h)), no linear bias, relu or gated gelu_new.
-enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5 };
+//   relative attention bias in every layer with scores q.k + bias (no 1 / sqrt(d_h)), no linear bias, relu or gated gelu_new.  DEBERTA
+//   (config.deberta_position_buckets + config.deberta_max_relative_positions, DebertaV2Model): BERT's post-LN layer under the projections' names query_proj /
+//   key_proj / value_proj, no position table and no token types, and disentangled attention: every score carries q_i . PK[p] + k_j . PQ[p] with p the log bucket
+//   of the column difference (deberta_bucket), PQ / PK the layer's own q / k projections of the (normalised) table encoder.rel_embeddings, scale 1 / sqrt(3 d_h).
+enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA };
 constexpr uint8_t GATED_NAME = 0x80;   // or-ed into a slot's family: the tensor came as one half of a gated projection under T5's names (wi_0 / wi_1)
 inline Family fam_of(uint8_t got) { return (Family)(got & 0x7f); }
-inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5"}; return n[f]; }
+inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5", "DeBERTa-v2"}; return n[f]; }
 
 // tensor slots: 0..4 embeddings, then L_COUNT per layer (L_UW: the second half of a gated intermediate projection); below zero what is no slot of `got`
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
 enum { T_IGNORED = -1, T_RELBIAS = -2, T_WQKV = -3, T_WI = -4, T_WIB = -5, T_WQKVB = -6 };   // ModernBert's fused tensors of one layer: attn.Wqkv.{weight,bias}, mlp.Wi.{weight,bias}
+enum { T_RELEMB = -7, T_RELLNG = -8, T_RELLNB = -9 };      // DeBERTa's position table encoder.rel_embeddings.weight [2 Bk, H] and the norm over its rows, encoder.LayerNorm.{weight,bias}
+constexpr int DEB_MAX_BUCKETS = 256;   // position_buckets of every v3 checkpoint, and the most a handle takes: 512 table rows
 enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
 constexpr int REL_BUCKETS = 32;        // HF's MPNetEncoder uses 32 buckets and max_distance 128 whatever the config says, and so do the T5 handles
 constexpr int MLM_COLS = 128;          // column granularity of the projection loops: the MLM decoder is stored with vocab rounded up to it by zero rows
@@ -93,6 +98,13 @@ static const NameRow NAME_ROWS[] = {
     {"layer.1.DenseReluDense.wi_1.weight", LAYER, T5, L_UW, XFF, XH, GATED}, {"layer.1.DenseReluDense.wo.weight", LAYER, T5, L_FW, XH, XFF, 0},
     {"final_norm.weight", TAIL, MODERN, L_LN2G, XH, X1, LAST_LAYER}, {"final_norm.bias", TAIL, MODERN, L_LN2B, XH, X1, LAST_LAYER},
     {"encoder.relative_attention_bias.weight", ENDS, MPNET, T_RELBIAS, XBUCKETS, XHEADS, 0},
+    // DebertaV2Model: the position table (its row count is 2 Bk: check_tensor) and its norm; the attention projections into BERT's slots, every other tensor
+    // under BERT's own names
+    {"encoder.rel_embeddings.weight", TAIL, DEBERTA, T_RELEMB, XANY, XH, 0}, {"encoder.LayerNorm.weight", TAIL, DEBERTA, T_RELLNG, XH, X1, 0},
+    {"encoder.LayerNorm.bias", TAIL, DEBERTA, T_RELLNB, XH, X1, 0},
+    {"attention.self.query_proj.weight", LAYER, DEBERTA, L_QW, XH, XH, 0}, {"attention.self.query_proj.bias", LAYER, DEBERTA, L_QB, XH, X1, 0},
+    {"attention.self.key_proj.weight", LAYER, DEBERTA, L_KW, XH, XH, 0}, {"attention.self.key_proj.bias", LAYER, DEBERTA, L_KB, XH, X1, 0},
+    {"attention.self.value_proj.weight", LAYER, DEBERTA, L_VW, XH, XH, 0}, {"attention.self.value_proj.bias", LAYER, DEBERTA, L_VB, XH, X1, 0},
     // ModernBertModel: Wqkv [3H, H] = q | k | v row blocks, mlp.Wi [2 FF, H] = input | gate (input, the half the GELU is applied to, in the place of NomicBert's
     // gate_proj, gate in that of up_proj); mlp_norm is the norm behind the attention output
     {"attn.Wqkv.weight", LAYER, MODERN, T_WQKV, X3H, XH, 0}, {"attn.Wqkv.bias", LAYER, MODERN, T_WQKVB, X3H, X1, 0}, {"mlp.Wi.weight", LAYER, MODERN, T_WI, X2FF, XH, 0},
@@ -122,7 +134,7 @@ static const NameRow NAME_ROWS[] = {
 };
 
 // the rows a layer prefix leads to: 0 = BERT's and MPNet's, 1 = NomicBert's and ModernBert's, 2 = T5's
-inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN ? 1 : 0; }
+inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN ? 1 : 0; }      // (DeBERTa's layers are "encoder.layer.N.": group 0)
 // the layer prefix of `s`, T5's only or the other two: its group and where the layer index starts, or -1
 inline int layer_prefix(const std::string& s, bool t5, size_t& at) {
     if (t5) {
@@ -136,7 +148,7 @@ inline int layer_prefix(const std::string& s, bool t5, size_t& at) {
     return -1;
 }
 
-// slot >= 0: a slot of `got`; T_RELBIAS; a fused ModernBert tensor of layer `layer`; T_IGNORED ("pooler.*", "position_ids": the encoders read last_hidden_state)
+// slot >= 0: a slot of `got`; T_RELBIAS; T_RELEMB / T_RELLNG / T_RELLNB; a fused ModernBert tensor of layer `layer`; T_IGNORED ("pooler.*", "position_ids": the encoders read last_hidden_state)
 struct Resolved { int slot = T_IGNORED; Family fam = BERT; int layer = -1; int64_t numel = 0; bool gated = false; };
 
 inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& out) {
@@ -187,7 +199,8 @@ inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& ou
 //   HEAD_MLM: SPLADE's BertForMaskedLM head (KR_POOL_SPLADE): one EPI_GELU projection H -> H, k_ln16_head, the decoder [Vpad, H] with the EPI_SPLADE epilogue.
 //   HEAD_COLBERT / HEAD_SPARSE: bge-m3's token-level heads (KR_POOL_WITH_COLBERT / KR_POOL_WITH_SPARSE): a flagged forward runs its last layer on every row.
 //   HEAD_DENSE: the sentence-transformers Dense head behind the pooling of a T5 handle (k_pool_dense: out [B, P]).
-//   HEAD_CLS: RobertaClassificationHead (KR_POOL_CLASSIFY): out [B, L] = Wo . tanh(Wd . x + bd) + bo of the raw CLS row.
+//   HEAD_CLS: RobertaClassificationHead (KR_POOL_CLASSIFY): out [B, L] = Wo . tanh(Wd . x + bd) + bo of the raw CLS row.  On a DeBERTa handle the same four
+//   names are DebertaV2ForSequenceClassification's ContextPooler + classifier: erf-GELU where the tanh stands (ModelPlan::cls_gelu).
 //   HEAD_MODERN_CLS: ModernBertForSequenceClassification's, Wo . LayerNorm(erf_gelu(Wd . x + bd)) + bo of the raw CLS row or (config.classifier_pooling = 1) mean.
 enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT };
 enum : uint8_t { REQUIRED = 1, HALF = 2 };       // HALF: stored as the handle's 16-bit operand (a projection of the loops every layer uses), else fp32
@@ -221,11 +234,11 @@ static const HeadDesc HEADS[HEAD_COUNT] = {
      0, 0, 0, 0, 1u << BERT, {HEAD_CLS, HEAD_DENSE, -1}, WS_SLOT_ROW},
     {"dense.weight", "a Dense head", "the Dense head is part of T5 handles only (config.t5_feed_forward)", "", 1,
      {{"dense.weight", XFREE, XH, XFREE, REQUIRED}}, 'P', 4, 2048, 4, 1u << T5, {-1}, WS_POOLED},
-    {"classifier.*", "a classification head", "the classification head Wo . tanh(Wd . x + bd) + bo is BERT's and RoBERTa's; this family's is not implemented",
+    {"classifier.*", "a classification head", "the classification head Wo . act(Wd . x + bd) + bo is BERT's and RoBERTa's (tanh) and DeBERTa's (gelu); this family's is not implemented",
      "the classification head takes all four classifier.* tensors or none", 4,
      {{"classifier.dense.weight", XH, XH, XH, REQUIRED}, {"classifier.dense.bias", XH, X1, XH, REQUIRED}, {"classifier.out_proj.weight", XFREE, XH, XFREE, REQUIRED},
       {"classifier.out_proj.bias", XFREE, X1, XFREE, REQUIRED}},
-     'L', 1, 64, 1, 1u << BERT | 1u << MPNET, {HEAD_DENSE, -1}, WS_POOLED},
+     'L', 1, 64, 1, 1u << BERT | 1u << MPNET | 1u << DEBERTA, {HEAD_DENSE, -1}, WS_POOLED},
     {nullptr, "ModernBert's classification head (head.dense / head.norm / classifier)",
      "the head classifier . LayerNorm(gelu(head.dense . x)) is ModernBertForSequenceClassification's and is accepted on ModernBert handles (config.local_attention_layers)",
      "ModernBert's classification head takes head.dense.weight, head.norm.weight, classifier.weight and classifier.bias together or none of them", 6,
@@ -291,7 +304,9 @@ inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_
 //   config.t5_feed_forward: 0 = wo(relu(wi x)), 1 = wo(gelu_new(wi_0 x) * wi_1 x).
 //   config.classifier_pooling: the row ModernBert's classification head reads, 0 = [CLS] (also when never set), 1 = the masked mean; after the first finalize it
 //   is known to handles with that head only.
-enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_COUNT };
+//   config.deberta_position_buckets = Bk (even, 2 .. 256) and config.deberta_max_relative_positions = M (M - 1 > Bk / 2): DebertaV2Config's position_buckets and
+//   max_relative_positions (max_position_embeddings where that is < 1); the two together make the handle a DeBERTa handle.
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_COUNT };
 enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
 struct SettingRow {
     const char* name;
@@ -303,15 +318,18 @@ struct SettingRow {
     int max_pos_limit;     // > 0: refused on a handle with more position rows (the rotary tables are built for at most 8192)
     int dflt;              // >= 0: the value a handle finalized without the setting runs with, so that loading it later is a no-op
     int needs_head;        // >= 0: after the first finalize the setting is known to handles with this head only
+    int step;              // > 1: a V_INT setting takes multiples of it only
 };
 static const SettingRow SETTINGS[SET_COUNT] = {
-    {"config.position_padding_idx", X1, V_INT, 0, -2, "an integer in [0, max_position_embeddings - 2]", "BERT's position rule", 0, -1, -1},
-    {"config.rotary_inv_freq", XHALF_DH, V_FINITE, 0, 0, "", "no rotary positions: a BERT / RoBERTa / MPNet handle", 8192, -1, -1},
-    {"config.rotary_inv_freq_local", XHALF_DH, V_FINITE, 0, 0, "", "no local rotary table", 0, -1, -1},
-    {"config.attention_half_window", X1, V_INT, 1, 65536, "an integer >= 1", "no attention window", 0, -1, -1},
-    {"config.local_attention_layers", XANY, V_FLAGS, 0, 1, "", "not a ModernBert handle", 0, -1, -1},
-    {"config.t5_feed_forward", X1, V_INT, 0, 1, "0 (relu) or 1 (gated gelu_new)", "not a T5 handle", 0, -1, -1},
-    {"config.classifier_pooling", X1, V_INT, 0, 1, "0 ([CLS] row) or 1 (masked mean)", "the [CLS] row", 0, 0, HEAD_MODERN_CLS},
+    {"config.position_padding_idx", X1, V_INT, 0, -2, "an integer in [0, max_position_embeddings - 2]", "BERT's position rule", 0, -1, -1, 0},
+    {"config.rotary_inv_freq", XHALF_DH, V_FINITE, 0, 0, "", "no rotary positions: a BERT / RoBERTa / MPNet handle", 8192, -1, -1, 0},
+    {"config.rotary_inv_freq_local", XHALF_DH, V_FINITE, 0, 0, "", "no local rotary table", 0, -1, -1, 0},
+    {"config.attention_half_window", X1, V_INT, 1, 65536, "an integer >= 1", "no attention window", 0, -1, -1, 0},
+    {"config.local_attention_layers", XANY, V_FLAGS, 0, 1, "", "not a ModernBert handle", 0, -1, -1, 0},
+    {"config.t5_feed_forward", X1, V_INT, 0, 1, "0 (relu) or 1 (gated gelu_new)", "not a T5 handle", 0, -1, -1, 0},
+    {"config.classifier_pooling", X1, V_INT, 0, 1, "0 ([CLS] row) or 1 (masked mean)", "the [CLS] row", 0, 0, HEAD_MODERN_CLS, 0},
+    {"config.deberta_position_buckets", X1, V_INT, 2, DEB_MAX_BUCKETS, "an even integer", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 2},
+    {"config.deberta_max_relative_positions", X1, V_INT, 2, 65536, "an integer M with M - 1 > position_buckets / 2", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 0},
 };
 constexpr int64_t SETTING_MAX_VALUES = 4096;
 struct Settings {
@@ -342,7 +360,7 @@ inline Error set_setting(const kr_bert_cfg& cfg, Settings& set, const HeadState*
     for (int64_t i = 0; i < numel; ++i) {
         const float x = vals[i];
         if (r.rule != V_INT && !std::isfinite(x)) return err(KR_EINVAL, "'%s' holds a non-finite value", name);
-        if (r.rule == V_INT && (!(x >= (float)r.lo && x <= (float)hi) || x != (float)(int)x)) return err(KR_EINVAL, "%s = %g: expected %s (%d .. %d)", name, (double)x, r.expects, r.lo, hi);
+        if (r.rule == V_INT && (!(x >= (float)r.lo && x <= (float)hi) || x != (float)(int)x || (r.step > 1 && (int)x % r.step != 0))) return err(KR_EINVAL, "%s = %g: expected %s (%d .. %d)", name, (double)x, r.expects, r.lo, hi);
     }
     const std::vector<float> v(vals, vals + numel);
     if (finalized_once) {
@@ -364,20 +382,60 @@ inline Error set_setting(const kr_bert_cfg& cfg, Settings& set, const HeadState*
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// DeBERTa's bucket rule
+// ---------------------------------------------------------------------------------------------------------
+// make_log_bucket_position of modeling_deberta_v2.py for the column difference r = col_query - col_key: the identity up to mid = Bk / 2, beyond it
+// sign(r) (ceil(ln(|r| / mid) / ln((M - 1) / mid) (mid - 1)) + mid).  In float64 it equals HF's float32 tensor arithmetic for every |r| < M at
+// (Bk, M) = (256, 512), (32, 128) and (64, 512) (tests/test_deberta_host.py).  Needs Bk >= 2 and M - 1 > mid (describe()).
+inline int deberta_delta(int r, int Bk, int M) {
+    const int mid = Bk / 2, a = r < 0 ? -r : r;
+    if (a <= mid) return r;
+    const double lp = std::ceil(std::log((double)a / mid) / std::log((double)(M - 1) / mid) * (mid - 1)) + mid;
+    const double big = 1 << 20;      // far outside every table: the clamp of deberta_bucket decides
+    const int d = (int)(lp < big ? lp : big);
+    return r < 0 ? -d : d;
+}
+// the row of PQ / PK a pair reads (c2p_pos / p2c_pos of HF's disentangled_attention_bias, which agree because the rule is odd): clamped into the table
+inline int deberta_bucket(int r, int Bk, int M) {
+    const int p = deberta_delta(r, Bk, M) + Bk;
+    return p < 0 ? 0 : p > 2 * Bk - 1 ? 2 * Bk - 1 : p;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // the plan
 // ---------------------------------------------------------------------------------------------------------
 // what was loaded: per slot 0 = never, else the Family of the name it came under (| GATED_NAME); the family of the bias table's name; the heads
 struct Loaded {
     std::vector<uint8_t> got;
     Family rel_fam = FAM_NONE;
+    int rel_rows = 0, rel_rows_seen = 0;   // rows of DeBERTa's position table as loaded (0: never); of the tensor check_tensor saw last (mark_loaded takes it over)
+    bool rel_ln[2] = {false, false};       // encoder.LayerNorm.weight / .bias were loaded
     HeadState heads[HEAD_COUNT];
     explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0) {}
 };
 // A resolved tensor arriving with `numel` elements: its count.  The bias table [32, heads] (MPNet's name or T5's) has the rule of the heads: before the first
 // finalize it makes the handle an MPNet handle (a T5 handle needs it); afterwards a handle that has it takes new values (the weight sync reloads every
 // parameter) and a handle finalized without it refuses it.
-inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolved& r, int64_t numel, const Loaded& ld, bool finalized_once) {
+// DeBERTa's position table [2 Bk, H] and its norm have the same rule; the table's row count is fixed with it (describe() holds it against the setting).
+inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolved& r, int64_t numel, Loaded& ld, bool finalized_once) {
     if (r.slot == T_IGNORED) return Error{};
+    if (r.slot == T_RELEMB) {
+        const int64_t rows = numel / cfg.hidden;
+        if (numel <= 0 || numel % cfg.hidden != 0 || rows % 2 != 0 || rows < 4 || rows > 2 * DEB_MAX_BUCKETS)
+            return err(KR_EINVAL, "tensor '%s' has %lld elements, expected [2 * position_buckets, hidden] with 2 <= position_buckets <= %d", name, (long long)numel, DEB_MAX_BUCKETS);
+        if (finalized_once && ld.rel_rows && rows != ld.rel_rows)
+            return err(KR_EINVAL, "'%s' with %lld rows after kr_encoder_finalize: the table of the handle is fixed (it has %d rows)", name, (long long)rows, ld.rel_rows);
+        ld.rel_rows_seen = (int)rows;
+    } else if (r.slot == T_RELLNG || r.slot == T_RELLNB) {
+        if (numel != r.numel) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)r.numel);
+        if (finalized_once && ld.rel_rows && !ld.rel_ln[0])
+            return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without encoder.LayerNorm (norm_rel_ebd none) and stays what it is", name);
+    }
+    if (r.slot <= T_RELEMB) {
+        if (finalized_once && !ld.rel_rows)
+            return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without config.deberta_position_buckets and is no DeBERTa handle", name);
+        return Error{};
+    }
     if (r.slot == T_RELBIAS && numel != r.numel)
         return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets, and so do the T5 handles)", name,
                    (long long)numel, (long long)r.numel, REL_BUCKETS, cfg.heads, REL_BUCKETS);
@@ -391,6 +449,8 @@ inline void mark_loaded(Loaded& ld, const Resolved& r) {
     const uint8_t tag = (uint8_t)(r.fam | (r.gated ? GATED_NAME : 0));
     uint8_t* g = r.layer >= 0 ? &ld.got[T_LAYER0 + (size_t)r.layer * L_COUNT] : nullptr;
     if (r.slot == T_RELBIAS) ld.rel_fam = r.fam;
+    else if (r.slot == T_RELEMB) ld.rel_rows = ld.rel_rows_seen;
+    else if (r.slot == T_RELLNG || r.slot == T_RELLNB) ld.rel_ln[r.slot == T_RELLNB] = true;
     else if (r.slot == T_WQKV) g[L_QW] = g[L_KW] = g[L_VW] = tag;
     else if (r.slot == T_WQKVB) g[L_QB] = g[L_KB] = g[L_VB] = tag;
     else if (r.slot == T_WI) g[L_IW] = g[L_UW] = tag;
@@ -409,11 +469,12 @@ static const FamilyRow FAMILIES[] = {
     {NOMIC, false, false, bits(T_WORD, T_TYPE, T_ELNG, T_ELNB), LAYER_MATRICES | LAYER_NORMS | bits(L_UW)},
     {MODERN, true, false, bits(T_WORD, T_TYPE, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G, L_UW)},
     {T5, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G)},
+    {DEBERTA, false, false, bits(T_WORD, T_ELNG, T_ELNB), (1u << L_COUNT) - 1 - bits(L_UW)},
 };
 
-enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table)
+enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY, POS_DISENT };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table), none (DeBERTa: a zero row)
 enum QkvKind : uint8_t { QKV_PLAIN, QKV_ROT, QKV_ROT_BIAS };                       // EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB (a ModernBert layer with attn.Wqkv.bias)
-enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2 };                 // plain, with the relative attention bias, under the sliding window (and the local rotary table)
+enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2, AM_DISENT = 3 };  // plain, with the relative attention bias, under the sliding window (and the local rotary table), DeBERTa's disentangled position terms
 enum FfKind : uint8_t { FF_GELU, FF_SWIGLU, FF_GEGLU, FF_RELU, FF_GEGLU_TANH };    // EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH
 struct LayerPlan { QkvKind qkv; AttnMode attn; };
 struct ModelPlan {
@@ -421,6 +482,9 @@ struct ModelPlan {
     bool pre_ln = false, rms = false, rotary = false, rotary_local = false, rel_bias = false;
     PosSource pos = POS_COLUMN;
     int pad_idx = -1, half_window = 0;
+    int deb_buckets = 0, deb_max_rel = 0;  // DeBERTa: Bk and M of deberta_bucket (0: no such handle)
+    bool deb_norm = false;                 // ... and whether the table goes through encoder.LayerNorm
+    bool cls_gelu = false;                 // HEAD_CLS computes erf-GELU where BERT's computes tanh (DeBERTa's ContextPooler)
     std::vector<LayerPlan> layers;
     FfKind ff = FF_GELU;
     bool ff_gated = false;                 // w1 is [2 FF, H]
@@ -433,12 +497,60 @@ struct ModelPlan {
     unsigned ws = 0;                       // WS_*
 };
 
+// the state-dict name a slot was loaded under, for refusals: the first row of `f` that fills it ("weight slot N" when the table has none)
+inline std::string slot_tensor_name(size_t slot, Family f) {
+    const int layer = slot < T_LAYER0 ? -1 : (int)((slot - T_LAYER0) / L_COUNT), id = slot < T_LAYER0 ? (int)slot : (int)((slot - T_LAYER0) % L_COUNT);
+    static const char* const prefix[] = {"encoder.layer.", "layers.", "encoder.block."};
+    for (const NameRow& r : NAME_ROWS) {
+        if (r.fam != f || r.id != id || (r.match == LAYER) != (layer >= 0)) continue;
+        if (layer >= 0) return std::string(prefix[prefix_group(f)]) + std::to_string(layer) + "." + r.text;
+        return std::string(r.match == EMB ? "embeddings." : "") + r.text;
+    }
+    return "weight slot " + std::to_string(slot);
+}
+
 inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded& ld, ModelPlan& plan) {
     const bool rot = set.has(SET_ROTARY), modern = set.has(SET_LOCAL_LAYERS), t5 = set.has(SET_T5_FF), rel = ld.rel_fam != FAM_NONE;
     const bool local_set = set.has(SET_ROTARY_LOCAL) || set.has(SET_HALF_WINDOW);
-    const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF);
-    const Family fam = t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
+    const bool deb = set.has(SET_DEB_BUCKETS) || set.has(SET_DEB_MAX_REL);
+    const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF), Bk = set.value(SET_DEB_BUCKETS, 0), max_rel = set.value(SET_DEB_MAX_REL, 0);
+    const Family fam = deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
     const std::vector<float>& flags = set.v[SET_LOCAL_LAYERS];
+    if (deb) {
+        if (!set.has(SET_DEB_BUCKETS) || !set.has(SET_DEB_MAX_REL))
+            return err(KR_EINVAL, "%s without %s: a DeBERTa handle takes both", SETTINGS[set.has(SET_DEB_BUCKETS) ? SET_DEB_BUCKETS : SET_DEB_MAX_REL].name,
+                       SETTINGS[set.has(SET_DEB_BUCKETS) ? SET_DEB_MAX_REL : SET_DEB_BUCKETS].name);
+        if (pad_idx >= 0 || rot || modern || local_set || t5 || rel)
+            return err(KR_EINVAL, "config.deberta_position_buckets / config.deberta_max_relative_positions next to config.position_padding_idx / config.rotary_inv_freq* / "
+                                  "config.local_attention_layers / config.attention_half_window / config.t5_feed_forward / a relative attention bias: a handle has one position scheme");
+        if (!(max_rel - 1 > Bk / 2))
+            return err(KR_EINVAL, "config.deberta_max_relative_positions = %d with config.deberta_position_buckets = %d: the bucket rule needs M - 1 > position_buckets / 2", max_rel, Bk);
+        if (cfg.max_pos > 8192) return err(KR_EINVAL, "max_position_embeddings = %d: a DeBERTa handle's bucket table is built for at most 8192 columns", cfg.max_pos);
+        // names and family agree: the attention projections under DeBERTa's names (the score scale 1 / sqrt(3 d_h) is folded into query_proj as it is loaded), no
+        // position table, nothing under a third family's name
+        for (size_t i = 0; i < ld.got.size(); ++i) {
+            const Family g = fam_of(ld.got[i]);
+            const int id = i < T_LAYER0 ? -1 : (int)((i - T_LAYER0) % L_COUNT);
+            const bool qkv = id >= L_QW && id <= L_VB;
+            if (!ld.got[i] || i == T_TYPE || (qkv ? g == DEBERTA : g == BERT && i != T_POS)) continue;
+            return i == T_POS ? err(KR_EINVAL, "'embeddings.position_embeddings.weight' on a DeBERTa handle: position_biased_input is not implemented, the positions enter the attention only")
+                              : err(KR_EINVAL, "'%s' on a DeBERTa handle (config.deberta_position_buckets): it takes attention.self.{query,key,value}_proj and BERT's names for every other tensor",
+                                    slot_tensor_name(i, g).c_str());
+        }
+        if (!ld.rel_rows) return err(KR_ESTATE, "'encoder.rel_embeddings.weight' was never loaded");
+        if (ld.rel_rows != 2 * Bk)
+            return err(KR_EINVAL, "'encoder.rel_embeddings.weight' has %d rows, config.deberta_position_buckets = %d needs %d", ld.rel_rows, Bk, 2 * Bk);
+        if (ld.rel_ln[0] != ld.rel_ln[1])
+            return err(KR_ESTATE, "'encoder.LayerNorm.%s' was never loaded: the norm over the position table takes its weight and its bias or neither", ld.rel_ln[0] ? "bias" : "weight");
+    } else {
+        if (ld.rel_rows || ld.rel_ln[0] || ld.rel_ln[1])
+            return err(KR_EINVAL, "'%s' but config.deberta_position_buckets was never loaded: load it and config.deberta_max_relative_positions before kr_encoder_finalize",
+                       ld.rel_rows ? "encoder.rel_embeddings.weight" : ld.rel_ln[0] ? "encoder.LayerNorm.weight" : "encoder.LayerNorm.bias");
+        for (size_t i = 0; i < ld.got.size(); ++i)
+            if (fam_of(ld.got[i]) == DEBERTA)
+                return err(KR_EINVAL, "'%s' but config.deberta_position_buckets was never loaded: load it and config.deberta_max_relative_positions before kr_encoder_finalize",
+                           slot_tensor_name(i, DEBERTA).c_str());
+    }
     if (t5 && (pad_idx >= 0 || rot || modern || local_set))
         return err(KR_EINVAL, "config.t5_feed_forward next to config.position_padding_idx / config.rotary_inv_freq* / config.local_attention_layers / "
                               "config.attention_half_window: a T5 handle's one position scheme is its relative attention bias");
@@ -510,11 +622,12 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
         plan.zero_fill.push_back((int)i);
     }
     plan.family = fam; plan.pre_ln = fr.pre_ln; plan.rms = fr.rms; plan.rotary = rot; plan.rotary_local = set.has(SET_ROTARY_LOCAL); plan.rel_bias = rel;
-    plan.pos = t5 ? POS_BIAS_ONLY : rot ? POS_ROTARY : pad_idx >= 0 ? POS_FAIRSEQ : POS_COLUMN;
+    plan.pos = deb ? POS_DISENT : t5 ? POS_BIAS_ONLY : rot ? POS_ROTARY : pad_idx >= 0 ? POS_FAIRSEQ : POS_COLUMN;
+    plan.deb_buckets = Bk; plan.deb_max_rel = max_rel; plan.deb_norm = deb && ld.rel_ln[0]; plan.cls_gelu = deb;
     plan.pad_idx = pad_idx; plan.half_window = set.value(SET_HALF_WINDOW, 0);
     for (int li = 0; li < cfg.layers; ++li)
         plan.layers.push_back({!rot ? QKV_PLAIN : modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] ? QKV_ROT_BIAS : QKV_ROT,
-                               rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
+                               deb ? AM_DISENT : rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
     plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot ? FF_SWIGLU : FF_GELU;
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;

@@ -578,8 +578,11 @@ __global__ __launch_bounds__(256) void k_pool_dense(const float* __restrict__ po
 // that order and a shuffle butterfly folds the 64 sums — first the mean, then the variance of the values centred on it (two passes, fp32), then
 // t = (t - mean) / sqrt(var + eps) * g + beta in place — a fixed order per sequence whatever its slot.  Stage 2 is the same code.  This variant also
 // guards its result: a non-finite logit of a sequence with attended tokens (seq_nk > 0) sets bit 1 of the error word, like a non-finite embedding (k_pool).
+//
+// GELU without GLN (DeBERTa handles; DebertaV2ForSequenceClassification's ContextPooler + classifier under HEAD_CLS's names): logits[b, :] =
+// Wo . erf_gelu(Wd . x_b + bd) + bo — the erf-GELU of the GLN variant where the tanh stands, no norm, and the same guard of the result.
 constexpr int CH_SEQ = 4, CH_WAVES = 16;
-template <int NJ, bool GLN = false>     // 256-column steps that cover a row: H <= 256 NJ
+template <int NJ, bool GLN = false, bool GELU = GLN>     // 256-column steps that cover a row: H <= 256 NJ
 __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restrict__ pooled, const float* __restrict__ Wd, const float* __restrict__ bd,
                                                            const float* __restrict__ Wo, const float* __restrict__ bo, int B, int H, int L,
                                                            float* __restrict__ out, const float* __restrict__ ng = nullptr, const float* __restrict__ nb = nullptr,
@@ -638,7 +641,7 @@ __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restr
         const float b = bd[f];
 #pragma unroll
         for (int s = 0; s < CH_SEQ; ++s) {
-            if constexpr (GLN) { const float a = y[s] + b; t[s * H + f] = 0.5f * a * (1.f + erff(a * 0.70710678118654752f)); }
+            if constexpr (GELU) { const float a = y[s] + b; t[s * H + f] = 0.5f * a * (1.f + erff(a * 0.70710678118654752f)); }
             else t[s * H + f] = tanhf(y[s] + b);
         }
     });
@@ -667,7 +670,7 @@ __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restr
             if (b0 + s < B) {
                 const float v = y[s] + b;
                 out[(int64_t)(b0 + s) * L + l] = v;
-                if constexpr (GLN) { if (!(fabsf(v) < INFINITY) && seq_nk[b0 + s] > 0) atomicOr(err, 2); }
+                if constexpr (GELU) { if (!(fabsf(v) < INFINITY) && seq_nk[b0 + s] > 0) atomicOr(err, 2); }
             }
     });
 }

@@ -100,6 +100,51 @@ static int build_bias_table(Encoder* e) {
     return 0;
 }
 
+// A DeBERTa handle's tables (encoder_pos.hpp, AttnDisentArgs): the bucket of every column difference the position table allows, and per layer PQ = query_proj(R),
+// PK = key_proj(R) of R = LayerNorm(rel_embeddings) (the raw table without encoder.LayerNorm), [heads][TP][d_h] in the 16-bit operand type.  R is normalised
+// on the host in double and rounded once; the projections are fp32 sums from the fp32 copies of the two matrices the loader kept (LayerW::wq32 / wk32).  PQ
+// carries the score scale log2(e) / sqrt(3 d_h) that the loader folded into query_proj's matrix for the 16-bit copy and into its bias.
+static int build_disent_tables(Encoder* e) {
+    const model::ModelPlan& p = e->plan;
+    const int H = e->cfg.hidden, dh = H / e->cfg.heads, Bk = p.deb_buckets, rows = 2 * Bk, TP = (int)round_up(rows, 32), P = e->cfg.max_pos;
+    std::vector<int> bucket((size_t)2 * P - 1);
+    for (int r = -(P - 1); r <= P - 1; ++r) bucket[(size_t)(r + P - 1)] = model::deberta_bucket(r, Bk, p.deb_max_rel);
+    if (!e->deb_bucket) KR_TRY(dmalloc(e->own_bufs, &e->deb_bucket, bucket.size() * 4));
+    KR_HIP(hipMemcpy(e->deb_bucket, bucket.data(), bucket.size() * 4, hipMemcpyHostToDevice));
+    std::vector<float> R((size_t)rows * H);
+    for (int r = 0; r < rows; ++r) {
+        const float* x = &e->rel_emb[(size_t)r * H];
+        if (!p.deb_norm) { std::copy(x, x + H, &R[(size_t)r * H]); continue; }
+        double mean = 0.0, var = 0.0;
+        for (int c = 0; c < H; ++c) mean += x[c];
+        mean /= H;
+        for (int c = 0; c < H; ++c) var += ((double)x[c] - mean) * ((double)x[c] - mean);
+        const double rstd = 1.0 / std::sqrt(var / H + (double)e->cfg.ln_eps);
+        for (int c = 0; c < H; ++c) R[(size_t)r * H + c] = (float)(((double)x[c] - mean) * rstd * (double)e->rel_lng[c] + (double)e->rel_lnb[c]);
+    }
+    const float qscale = (float)(1.4426950408889634 / std::sqrt(3.0 * dh));
+    const size_t tab_bytes = (size_t)e->cfg.heads * TP * dh * 2;
+    for (auto& l : e->L) {
+        if (l.pq16) continue;
+        KR_TRY(dmalloc(e->own_bufs, &l.pq16, tab_bytes)); KR_TRY(dmalloc(e->own_bufs, &l.pk16, tab_bytes));
+        KR_HIP(hipMemset(l.pq16, 0, tab_bytes)); KR_HIP(hipMemset(l.pk16, 0, tab_bytes));      // the rows behind 2 Bk stay zero
+    }
+    float* dR = nullptr;
+    KR_HIP(hipMalloc(reinterpret_cast<void**>(&dR), R.size() * 4));
+    hipError_t rc = hipMemcpy(dR, R.data(), R.size() * 4, hipMemcpyHostToDevice);
+    for (auto& l : e->L) {
+        if (rc != hipSuccess) break;
+        const unsigned g = (unsigned)(((int64_t)rows * H + 255) / 256);
+        hipLaunchKernelGGL(k_pos_table, dim3(g), dim3(256), 0, 0, dR, l.wq32, l.bqkv, qscale, rows, TP, H, dh, l.pq16);
+        hipLaunchKernelGGL(k_pos_table, dim3(g), dim3(256), 0, 0, dR, l.wk32, l.bqkv + H, 1.f, rows, TP, H, dh, l.pk16);
+    }
+    if (rc == hipSuccess) rc = hipGetLastError();
+    if (rc == hipSuccess) rc = hipDeviceSynchronize();
+    (void)hipFree(dR);
+    KR_HIP(rc);
+    return 0;
+}
+
 // cos / sin [max_pos][d_h / 2] with HF's arithmetic (NomicBertRotaryEmbedding.forward): the angle is the fp32 product float(pos) * inv_freq[j], the entry the
 // cosine / sine of that fp32 angle (evaluated in double and rounded once).  One pair of tables per frequency vector: the handle's (global) one, and for
 // ModernBert handles with local layers the local one.
@@ -201,6 +246,14 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     const bool paired = r.fam == NOMIC || r.fam == MODERN, gated = paired || r.gated;
     KR_TRY(refuse(check_tensor(e->cfg, hf_name, r, numel, e->ld, e->finalized_once)));
     if (slot == T_IGNORED) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
+    if (slot <= T_RELEMB) {            // DeBERTa's position table and its norm, kept as loaded on the host: finalize builds every layer's PQ / PK from them (build_disent_tables)
+        std::vector<float>& dst = slot == T_RELEMB ? e->rel_emb : slot == T_RELLNG ? e->rel_lng : e->rel_lnb;
+        dst.resize((size_t)numel);
+        KR_HIP(hipMemcpy(dst.data(), data, (size_t)numel * 4, hipMemcpyDefault));
+        mark_loaded(e->ld, r);
+        e->ready = false;
+        return 0;
+    }
     if (slot == T_RELBIAS) {           // kept as loaded on the host: finalize builds the table the attention kernels read (build_bias_table)
         e->rel_w.resize((size_t)numel);
         KR_HIP(hipMemcpy(e->rel_w.data(), data, (size_t)numel * 4, hipMemcpyDefault));
@@ -219,7 +272,9 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     // log2(e) / sqrt(d_h) is folded into the query projection: the attention scores come out in log2 units and the softmax is a bare exp2.  The multiply is
     // fp32, before the 16-bit conversion (d_h = 32: the factor is not a power of two; d_h = 64: the same bits as log2(e) / 8).  T5's scores are q.k + bias,
     // no 1 / sqrt(d_h): under T5's names log2(e) alone is folded in
-    const float qscale = r.fam == T5 ? (float)1.4426950408889634 : (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
+    // DeBERTa's scores are (q.k + q.PK + k.PQ) / sqrt(3 d_h): under DeBERTa's names that factor
+    const float qscale = r.fam == T5 ? (float)1.4426950408889634
+                       : r.fam == DEBERTA ? (float)(1.4426950408889634 / std::sqrt(3.0 * (double)(H / e->cfg.heads))) : (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
     // rows [n / H, H] from element `first` of the staged copy; mode >= 0: into tile-pair order (k_f32_to_bf16_rows)
     auto to_bf16 = [&](uint16_t* dst, int64_t first, int64_t n, float scale, int mode) {
         const unsigned g = (unsigned)((n + 255) / 256);
@@ -266,6 +321,11 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, e->stage, dst, numel, id == L_QB ? qscale : 1.f);
         else {
             LayerW& l = e->L[li];
+            if (r.fam == DEBERTA && (id == L_QW || id == L_KW)) {      // the fp32 matrix stays: finalize projects the position table with it (build_disent_tables)
+                float*& keep = id == L_QW ? l.wq32 : l.wk32;
+                if (!keep) KR_TRY(dmalloc(e->own_bufs, &keep, (size_t)numel * 4));
+                KR_HIP(hipMemcpy(keep, e->stage, (size_t)numel * 4, hipMemcpyDeviceToDevice));
+            }
             switch (id) {
                 case L_QW: to_bf16(l.wqkv, 0, numel, qscale, head64); break;
                 case L_KW: to_bf16(l.wqkv + H * H, 0, numel, 1.f, head64); break;
@@ -309,12 +369,13 @@ int enc_finalize(void* h) {
         for (int i = 0; p.head[hd] && i < HEADS[hd].n; ++i) KR_TRY(zeros(&e->head_p[hd][i], head_tensor_bytes(e, hd, i, p.head_dim[hd])));
     if (p.ff == FF_GEGLU)
         for (auto& l : e->L) KR_TRY(zeros(&l.b1p, (size_t)2 * e->cfg.intermediate * 4));
-    if (p.rotary || p.head[HEAD_MLM]) KR_TRY(zeros(&e->zero_row, (size_t)H * 4));
+    if (p.rotary || p.head[HEAD_MLM] || p.pos == POS_DISENT) KR_TRY(zeros(&e->zero_row, (size_t)H * 4));
     if (p.rotary) KR_TRY(build_rotary_table(e, e->set.v[SET_ROTARY], &e->rot_cos, &e->rot_sin));
     if (p.rotary_local) KR_TRY(build_rotary_table(e, e->set.v[SET_ROTARY_LOCAL], &e->rot_cos_l, &e->rot_sin_l));
     for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * H, l.bo_eff, H);
     if (p.rel_bias) KR_TRY(build_bias_table(e));
     KR_HIP(hipGetLastError());
+    if (p.family == DEBERTA) KR_TRY(build_disent_tables(e));
     KR_HIP(hipDeviceSynchronize());
     e->ready = true;
     e->finalized_once = true;

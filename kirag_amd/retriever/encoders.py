@@ -63,7 +63,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, T5EncoderModel, XLMRobertaModel
+from transformers import BertModel, DebertaV2Model, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, T5EncoderModel, XLMRobertaModel
 
 from .. import _lib
 
@@ -97,6 +97,11 @@ T5_TYPE = "t5"
 T5_SETTING = "config.t5_feed_forward"        # reserved name (include/kirag_amd.h): one float, 0 = relu, 1 = gated gelu_new
 T5_FEED_FORWARDS = {("relu", False): 0.0, ("gelu_new", True): 1.0}      # (config.dense_act_fn, config.is_gated_act) -> the setting
 T5_BUCKETS, T5_MAX_DISTANCE = 32, 128        # the bucket rule the attention kernels compute (MPNet's: the same rule as T5's bidirectional one)
+DEBERTA_TYPE = "deberta-v2"
+# reserved names of a DeBERTa handle's settings (include/kirag_amd.h): position_buckets, max_relative_positions (max_position_embeddings where that is < 1)
+DEBERTA_SETTINGS = ("config.deberta_position_buckets", "config.deberta_max_relative_positions")
+DEBERTA_MAX_BUCKETS = 256                    # the library's bound on position_buckets: 512 rows of encoder.rel_embeddings
+DEBERTA_MAX_POS = 8192                       # ... and on max_position_embeddings of such a handle
 ST_DENSE_TYPE = "sentence_transformers.models.Dense"
 ST_IDENTITY = "torch.nn.modules.linear.Identity"
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
@@ -129,6 +134,73 @@ def pad_modernbert_ff(name: str, w, ff: int, ff_pad: int):
     return out.numpy() if is_np else out
 
 
+def check_deberta_config(config, head: bool = False) -> dict:
+    """``NotImplementedError`` beginning ``model_type='deberta-v2':`` and naming the field, for everything of a DeBERTa-v2 / v3 config the kernels do not compute —
+    from the config alone: no weight has been read and the library is not loaded.  ``config``: a ``DebertaV2Config`` or the dict of a ``config.json`` (HF's
+    defaults fill the rest).  ``head``: also the fields of ``DebertaV2ForSequenceClassification``'s ContextPooler + classifier.  Returns the two settings of the
+    handle, ``{"buckets": position_buckets, "max_rel": max_relative_positions}``."""
+    def refuse(msg):
+        raise NotImplementedError(f"model_type={DEBERTA_TYPE!r}: {msg}")
+    is_dict = isinstance(config, dict)
+    get = (lambda k, d: config.get(k, d)) if is_dict else (lambda k, d: getattr(config, k, d))
+    model_type = get("model_type", DEBERTA_TYPE)
+    if model_type != DEBERTA_TYPE:
+        refuse(f"model_type={model_type!r}: DeBERTa v1 (its own relative-position rule, no shared projections) is not implemented")
+    H, heads, ff = int(get("hidden_size", 1536)), int(get("num_attention_heads", 24)), int(get("intermediate_size", 6144))
+    if H % 128 or not 0 < H <= 2048:
+        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
+    if heads <= 0 or H % heads or H // heads not in (32, 64):
+        refuse(f"num_attention_heads={heads} with hidden_size={H}: the attention kernels are built for heads of width 32 and 64")
+    if ff <= 0 or ff % 128:
+        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
+    max_pos = int(get("max_position_embeddings", 512))
+    if not 0 < max_pos <= DEBERTA_MAX_POS:
+        refuse(f"max_position_embeddings={max_pos}: a DeBERTa handle takes at most {DEBERTA_MAX_POS}")
+    if not get("relative_attention", False):
+        refuse("relative_attention=False: a DeBERTa handle's one position scheme is the disentangled attention")
+    if get("position_biased_input", True):
+        refuse("position_biased_input=True: absolute positions added to the embedding are not implemented")
+    pat = get("pos_att_type", None)
+    if isinstance(pat, str):
+        pat = [x.strip() for x in pat.lower().split("|")]
+    if sorted(pat or []) != ["c2p", "p2c"]:
+        refuse(f"pos_att_type={pat!r}: exactly ['c2p', 'p2c'] is implemented")
+    if not get("share_att_key", False):
+        refuse("share_att_key=False: position projections of their own (pos_key_proj / pos_query_proj) are not implemented")
+    Bk = int(get("position_buckets", -1))
+    if Bk <= 0 or Bk % 2 or Bk > DEBERTA_MAX_BUCKETS:
+        refuse(f"position_buckets={Bk}: an even number from 2 to {DEBERTA_MAX_BUCKETS} is implemented (log buckets; no linear relative positions)")
+    M = int(get("max_relative_positions", -1))
+    if M < 1:
+        M = max_pos
+    if not M - 1 > Bk // 2:
+        refuse(f"max_relative_positions={M} with position_buckets={Bk}: the bucket rule needs max_relative_positions - 1 > position_buckets / 2")
+    if int(get("conv_kernel_size", 0) or 0) > 0:
+        refuse(f"conv_kernel_size={get('conv_kernel_size', 0)}: the convolution layer of deberta-v2-xlarge / -xxlarge is not implemented")
+    emb = get("embedding_size", None)
+    if emb is not None and int(emb) != H:
+        refuse(f"embedding_size={emb}: an embedding projection (embedding_size != hidden_size) is not implemented")
+    if int(get("type_vocab_size", 0) or 0) > 0:
+        refuse(f"type_vocab_size={get('type_vocab_size', 0)}: token types are not implemented for this family")
+    if get("hidden_act", "gelu") != "gelu":
+        refuse(f"hidden_act={get('hidden_act', None)!r}: erf-GELU only")
+    ahs = get("attention_head_size", None)
+    if ahs is not None and int(ahs) != H // heads:
+        refuse(f"attention_head_size={ahs}: the HIP encoder needs hidden_size / num_attention_heads = {H // heads}")
+    norm = [x.strip() for x in str(get("norm_rel_ebd", "none")).lower().split("|")]
+    if norm not in (["none"], ["layer_norm"]):
+        refuse(f"norm_rel_ebd={get('norm_rel_ebd', None)!r}: 'none' and 'layer_norm' are implemented")
+    if head:
+        if get("pooler_hidden_act", "gelu") != "gelu":
+            refuse(f"pooler_hidden_act={get('pooler_hidden_act', None)!r}: the classification head implements erf-GELU only")
+        if int(get("pooler_hidden_size", H)) != H:
+            refuse(f"pooler_hidden_size={get('pooler_hidden_size', H)}: the classification head reads and writes hidden_size={H} features")
+        labels = len(config["id2label"]) if is_dict and config.get("id2label") is not None else int(get("num_labels", 2))
+        if labels > 64:
+            refuse(f"num_labels={labels}: the classification head of the HIP encoder holds at most 64 labels")
+    return {"buckets": Bk, "max_rel": M}
+
+
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
 
@@ -147,6 +219,8 @@ class HipBertForward:
         self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
         self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
         self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
+        self.is_deberta = getattr(config, "model_type", "bert") in (DEBERTA_TYPE, "deberta")
+        deberta = check_deberta_config(config) if self.is_deberta else None     # refuses what the kernels do not compute, before a handle exists
         inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
         modern = self._modern_settings(config) if self.is_modern else None      # likewise
         t5 = self._t5_settings(config) if self.is_t5 else None                  # likewise
@@ -161,7 +235,8 @@ class HipBertForward:
         # MPNet has no token types: one row of zeros stands in for the table (sync supplies it)
         # ... and neither has ModernBERT; its intermediate size is rounded up to the projections' 128 (pad_modernbert_ff)
         # ... and T5 has neither token types nor positions: kr_bert_cfg comes from T5Config's own fields (_t5_settings)
-        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 else config.type_vocab_size
+        # ... and DeBERTa-v2 / v3 has neither token types nor a position table (both are optional on its handles)
+        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 or self.is_deberta else config.type_vocab_size
         self.ff = int(t5["intermediate"] if self.is_t5 else config.intermediate_size)
         self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
         if self.is_t5:
@@ -199,6 +274,11 @@ class HipBertForward:
             for name, t in modern.items():
                 _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
 
+        # a DeBERTa handle: the two numbers of its bucket rule
+        if deberta is not None:
+            for name, val in zip(DEBERTA_SETTINGS, (deberta["buckets"], deberta["max_rel"])):
+                v = C.c_float(float(val))
+                _lib.check(lib.kr_encoder_load_weight(h, name.encode(), C.addressof(v), 1))
         # a T5 handle: its feed-forward kind
         if t5 is not None:
             v = C.c_float(t5["feed_forward"])
@@ -581,7 +661,7 @@ class _HipSentenceMixin(_HipModuleMixin):
         return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT and T5 have no token types
+        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel, DebertaV2Model) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT, T5 and DeBERTa-v3 have no token types
         out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
@@ -617,6 +697,7 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _nomic_twin = None               # ... and over NomicBertModel
     _modern_twin = None              # ... and over ModernBertModel
     _t5_twin = None                  # ... and over T5EncoderModel
+    _deberta_twin = None             # ... and over DebertaV2Model
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -645,6 +726,10 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
         if model_type == T5_TYPE:
             # an encoder-only T5: RMS norms, a relative attention bias, and (sentence-transformers checkpoints) a Dense head behind the pooling
             return cls._t5_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type in (DEBERTA_TYPE, "deberta"):
+            # disentangled attention under projection names of its own; what the kernels do not compute is refused from config.json alone
+            check_deberta_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
+            return cls._deberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -665,6 +750,16 @@ class _HipModernBertSentenceEncoder(_HipSentenceMixin, ModernBertModel):
 
     def __init__(self, config, add_pooling_layer=False, **kwargs):
         ModernBertModel.__init__(self, config)      # ModernBertModel has no pooling layer to ask for
+        self.kwargs = kwargs
+        self._hip = None
+
+
+class _HipDebertaSentenceEncoder(_HipSentenceMixin, DebertaV2Model):
+    _hf_base = DebertaV2Model
+
+    def __init__(self, config, add_pooling_layer=False, **kwargs):
+        check_deberta_config(config)                # refuses what the kernels do not compute when the model is made, not at its first forward
+        DebertaV2Model.__init__(self, config)       # DebertaV2Model has no pooling layer to ask for
         self.kwargs = kwargs
         self._hip = None
 
@@ -842,6 +937,16 @@ class T5BGEEncoder(_HipT5SentenceEncoder):
     _pool = POOL_CLS
 
 
+class DebertaV2E5Encoder(_HipDebertaSentenceEncoder):
+    """DebertaV2Model -> masked mean -> L2 normalise (fine-tunes of microsoft/deberta-v3-*)"""
+    _pool = POOL_MEAN
+
+
+class DebertaV2BGEEncoder(_HipDebertaSentenceEncoder):
+    """DebertaV2Model -> [:, 0] -> L2 normalise"""
+    _pool = POOL_CLS
+
+
 E5Encoder._roberta_twin = XLMRobertaE5Encoder
 BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
 E5Encoder._mpnet_twin = MPNetE5Encoder
@@ -852,6 +957,8 @@ E5Encoder._modern_twin = ModernBertE5Encoder
 BGEEncoder._modern_twin = ModernBertBGEEncoder
 E5Encoder._t5_twin = T5E5Encoder
 BGEEncoder._t5_twin = T5BGEEncoder
+E5Encoder._deberta_twin = DebertaV2E5Encoder
+BGEEncoder._deberta_twin = DebertaV2BGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:

@@ -24,12 +24,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
-from transformers import (BertForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification, PretrainedConfig,
+from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification, PretrainedConfig,
                           XLMRobertaForSequenceClassification)
 from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
-from .encoders import _CONFIG_KWARGS, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
+from .encoders import _CONFIG_KWARGS, DEBERTA_TYPE, check_deberta_config, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
 from .m3 import BGEM3Model
 from .splade import SpladeModel
 
@@ -157,6 +157,30 @@ class ModernBertReranker(_HipClassifierMixin, ModernBertForSequenceClassificatio
         return super().forward(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=None)
 
 
+def deberta_rename(name: str) -> str:
+    """``DebertaV2ForSequenceClassification`` parameter name -> the library's: the backbone loses its ``deberta.`` prefix, ``pooler.dense`` (the Linear in
+    front of the ContextPooler's GELU) is the head's ``classifier.dense`` and ``classifier`` its ``classifier.out_proj``, as for ``BertReranker``"""
+    name = _strip(name, "deberta.")
+    return _BERT_HEAD.get(name, name)
+
+
+class DebertaV2Reranker(_HipClassifierMixin, DebertaV2ForSequenceClassification):
+    """DebertaV2Model -> ``[CLS]`` row -> pooler.dense -> gelu -> classifier (mixedbread-ai/mxbai-rerank-*-v1, cross-encoder/nli-deberta-v3-*,
+    naver/trecdl22-crossencoder-debertav3).  On a DeBERTa handle the library's ``classifier.*`` names compute the erf-GELU of the ContextPooler where BERT's
+    head computes tanh."""
+    _hf_base = DebertaV2ForSequenceClassification
+    _hip_rename = staticmethod(deberta_rename)
+
+    def __init__(self, config, **kwargs):
+        check_deberta_config(config, head=True)
+        super().__init__(config, **kwargs)
+
+    @staticmethod
+    def _hip_extra(module):
+        # the weight sync leaves out every parameter named ``pooler.*`` (the encoders never read a pooler); here it is half of the head
+        return [("classifier.dense.weight", module.pooler.dense.weight), ("classifier.dense.bias", module.pooler.dense.bias)]
+
+
 class BGEReranker:
     """The registry's entry: ``from_pretrained`` reads the checkpoint's ``config.json`` and returns the twin of its ``model_type``."""
 
@@ -176,7 +200,10 @@ class BGEReranker:
         if model_type == MODERN_TYPE:
             check_modern_config(cfg_dict)          # from config.json alone: before a weight is read
             return ModernBertReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r} and {ROBERTA_TYPES} checkpoints "
+        if model_type in (DEBERTA_TYPE, "deberta"):
+            check_deberta_config(cfg_dict, head=True)      # from config.json alone: before a weight is read
+            return DebertaV2Reranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r}, {DEBERTA_TYPE!r} and {ROBERTA_TYPES} checkpoints "
                                   "(the classification heads of other families are other functions)")
 
 

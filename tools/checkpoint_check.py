@@ -13,6 +13,8 @@ f16 operands stay in range, which no synthetic recipe of this repository was fit
 sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*, loaded as the T5 twin of the encoders with the folder's sentence-transformers Dense
 head where modules.json lists one; reference T5EncoderModel in fp32 + pooling + that head, GPU only; "LN1" / "LN2" are again the pre-LN residual stream, and
 the feed-forward's hidden state is among the 16-bit-stored tensors: HF's own fp16 runs of v1.1 / flan sizes are known to overflow there) or a
+DeBERTa-v2 / v3 one (model_type deberta-v2: fine-tunes of microsoft/deberta-v3-*; reference DebertaV2Model in fp32, GPU only: the disentangled attention is not in
+the torch emulation) or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -28,7 +30,8 @@ BERT-family checkpoints show).  This tool replaces that assertion by a measureme
  3. a recommendation: the cheapest mode whose error stays below HALF the 1e-3 tolerance, else the default.
 
 A sequence-classification checkpoint (config.json names an ...ForSequenceClassification architecture: BAAI/bge-reranker-*, cross-encoder/ms-marco-MiniLM-*,
-and ModernBertForSequenceClassification: gte-reranker-modernbert-base, granite-embedding-reranker-english-r2, against HF fp32 with eager attention)
+ModernBertForSequenceClassification: gte-reranker-modernbert-base, granite-embedding-reranker-english-r2, against HF fp32 with eager attention, and
+DebertaV2ForSequenceClassification: mxbai-rerank-*-v1, nli-deberta-v3-*)
 is loaded as its reranker twin (kirag_amd.retriever.rerankers) instead, GPU only, and the report is the worst |logit - HF fp32 logit| over the built-in
 (question, passage) pairs — every question against every passage — for the four precision modes; the f16 range risk is the encoder's, as above.
 
@@ -108,6 +111,8 @@ def reference_and_stats(model, batches, pool, dev):
     def grab(li, key):
         def fn(_m, _inp, out):
             t = out[0] if isinstance(out, tuple) else out
+            if tuple(t.shape[:2]) != tuple(cur["mask"].shape):      # (DeBERTa's query_proj / key_proj also project the position table: no token rows)
+                return
             if key in ("ln1", "ln2"):
                 stats[li][key].append(t.detach()[cur["mask"]].abs().float().flatten().cpu())
             stats[li]["max16"] = max(stats[li]["max16"], float(t.detach()[cur["mask"]].abs().max()))
@@ -144,7 +149,9 @@ def reference_and_stats(model, batches, pool, dev):
                               mod.register_forward_hook(grab(li, key))))
             continue
         att = layer.attention
-        if hasattr(att, "attn"):                       # MPNetModel: q / k / v / o live in attention.attn (whose output is already o's), the LayerNorm in attention
+        if hasattr(att.self if hasattr(att, "self") else att, "query_proj"):      # DebertaV2Model: BERT's layer with the projections' own names
+            mods = (("q", att.self.query_proj), ("k", att.self.key_proj), ("v", att.self.value_proj), ("ctx", att.self), ("y1", att.output.dense), ("ln1", att.output.LayerNorm))
+        elif hasattr(att, "attn"):                     # MPNetModel: q / k / v / o live in attention.attn (whose output is already o's), the LayerNorm in attention
             mods = (("q", att.attn.q), ("k", att.attn.k), ("v", att.attn.v), ("y1", att.attn.o), ("ln1", att.LayerNorm))
         else:
             mods = (("q", att.self.query), ("k", att.self.key), ("v", att.self.value), ("ctx", att.self), ("y1", att.output.dense), ("ln1", att.output.LayerNorm))
@@ -216,13 +223,14 @@ def reranker_inputs(args, hf_dir, cfg):
         qs = [q for q in BASE_QUESTIONS for _ in BASE_PASSAGES]
         return RerankerCollator(tok, maxlength=args.max_length).encode_pairs(qs, BASE_PASSAGES * len(BASE_QUESTIONS))
     rng = np.random.default_rng(args.seed)
-    if cfg.model_type == "modernbert":      # [CLS] q [SEP] p [SEP] with the config's special ids, no token types
+    if cfg.model_type in ("modernbert", "deberta-v2"):      # [CLS] q [SEP] p [SEP] with the config's special ids (DeBERTa-v3's tokenizer: 1 and 2), no token types
         S, lo = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000)
+        cls_id, sep_id = (cfg.cls_token_id, cfg.sep_token_id) if cfg.model_type == "modernbert" else (1, 2)
         ids = np.full((args.n, S), cfg.pad_token_id, np.int64); mask = np.zeros((args.n, S), np.int64)
         for r in range(args.n):
             n = int(np.clip(rng.normal(0.8 * S, 0.2 * S), 8, S))
             nq = int(rng.integers(1, max(2, min(16, n - 6))))
-            ids[r, :n] = [cfg.cls_token_id, *rng.integers(lo, cfg.vocab_size, nq), cfg.sep_token_id, *rng.integers(lo, cfg.vocab_size, n - nq - 3), cfg.sep_token_id]
+            ids[r, :n] = [cls_id, *rng.integers(lo, cfg.vocab_size, nq), sep_id, *rng.integers(lo, cfg.vocab_size, n - nq - 3), sep_id]
             mask[r, :n] = 1
         return {"input_ids": torch.from_numpy(ids), "attention_mask": torch.from_numpy(mask)}
     roberta = cfg.model_type != "bert"
@@ -374,15 +382,17 @@ def check(hf_dir, args):
         return check_splade(hf_dir, args)
     if any(a.endswith("ForSequenceClassification") for a in (getattr(cfg, "architectures", None) or [])):
         return check_reranker(hf_dir, args)
-    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
+    from kirag_amd.retriever.encoders import DEBERTA_TYPE, MODERN_TYPE, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE, T5BGEEncoder, T5E5Encoder
     if getattr(cfg, "model_type", "bert") == T5_TYPE:
         # the encoder half alone, as the twin of the pooling asked for: its from_pretrained also reads the folder's Dense head (modules.json)
         return check_model((T5E5Encoder if args.pool == "mean" else T5BGEEncoder).from_pretrained(hf_dir), args, hf_dir)
-    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE) + ROBERTA_TYPES:
+    if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE, DEBERTA_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT and T5 encoders")
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3 and T5 encoders")
     if cfg.model_type == MODERN_TYPE:
         model = AutoModel.from_pretrained(hf_dir, attn_implementation="eager")      # ModernBertModel has no pooling layer
+    elif cfg.model_type == DEBERTA_TYPE:
+        model = AutoModel.from_pretrained(hf_dir)                                   # nor has DebertaV2Model
     else:
         model = AutoModel.from_pretrained(hf_dir, add_pooling_layer=False)
     return check_model(model, args, hf_dir)
@@ -390,7 +400,7 @@ def check(hf_dir, args):
 
 def check_model(model, args, hf_dir="(in-memory model)"):
     """the same check on an already constructed HF BertModel / XLMRobertaModel (tests build one from the synthetic outlier recipes)"""
-    from kirag_amd.retriever.encoders import MODERN_TYPE, MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE
+    from kirag_amd.retriever.encoders import DEBERTA_TYPE, MODERN_TYPE, MPNET_PADDING_IDX, MPNET_TYPE, NOMIC_TYPE, ROBERTA_TYPES, T5_TYPE
     cfg = model.config
     use_hip = torch.cuda.is_available() and not args.emulate
     mpnet = getattr(cfg, "model_type", "bert") == MPNET_TYPE
@@ -406,6 +416,8 @@ def check_model(model, args, hf_dir="(in-memory model)"):
     if getattr(cfg, "model_type", "bert") == T5_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms and a relative attention bias, which the torch emulation does not "
                          "implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") == DEBERTA_TYPE and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has disentangled attention, which the torch emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     model = model.float().eval().to(dev)
     batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated|deberta-v3-base ...] [--pool mean|cls] [--hf-fp16]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -48,7 +48,12 @@ T5_BASE = dict(d_model=768, d_kv=64, num_heads=12, d_ff=3072, num_layers=12, voc
                hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=512, type_vocab_size=1,
                layer_norm_eps=1e-6)
 T5_BASE_GATED = dict(T5_BASE, d_ff=2048, intermediate_size=2048, feed_forward_proj="gated-gelu", dense_act_fn="gelu_new", is_gated_act=True)
-SHAPES = dict(BS.ENCODER_SHAPES, **{"t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# DeBERTa-v3-base (mxbai-rerank-base-v1, nli-deberta-v3-base): xlmr-base's H, heads and FF on a DeBERTa handle — no position table, 256 log buckets over 512
+# relative positions, the two position terms of every score from k_pos_scores + the AM_DISENT attention: what they cost is the difference to xlmr-base
+DEBERTA_V3_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, vocab_size=128100, max_position_embeddings=512,
+                       type_vocab_size=0, layer_norm_eps=1e-7, hidden_act="gelu", model_type="deberta-v2", relative_attention=True, position_buckets=256,
+                       max_relative_positions=-1, norm_rel_ebd="layer_norm", share_att_key=True, pos_att_type=["p2c", "c2p"], position_biased_input=False)
+SHAPES = dict(BS.ENCODER_SHAPES, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -86,6 +91,10 @@ def hf_classes(cfg):
         def T5EncoderModel(config, add_pooling_layer=False):
             return T.T5EncoderModel(config)
         return T5Config, T5EncoderModel, (ENC.T5E5Encoder if args.pool == "mean" else ENC.T5BGEEncoder)
+    if cfg.get("model_type") == ENC.DEBERTA_TYPE:
+        def DebertaV2Model(config, add_pooling_layer=False):
+            return T.DebertaV2Model(config)
+        return T.DebertaV2Config, DebertaV2Model, (ENC.DebertaV2E5Encoder if args.pool == "mean" else ENC.DebertaV2BGEEncoder)
     if cfg.get("model_type") == ENC.MODERN_TYPE:
         return T.ModernBertConfig, T.ModernBertModel, (ENC.ModernBertE5Encoder if args.pool == "mean" else ENC.ModernBertBGEEncoder)
     if cfg.get("model_type") == ENC.NOMIC_TYPE:
@@ -101,7 +110,7 @@ def make_encoder(cfg, extra_state=None):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw).  extra_state: tensors and settings that must
     arrive with the first load (a head: tools/rerank_bench.py), by library name"""
-    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5"):
+    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2"):
         assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
@@ -110,6 +119,8 @@ def make_encoder(cfg, extra_state=None):
     enc = HipBertForward(ns, 0)
     if cfg["model_type"] == "modernbert":      # synthetic_state reads BERT's field names
         ns = SimpleNamespace(**dict(cfg, type_vocab_size=1, layer_norm_eps=cfg["norm_eps"]))
+    if cfg["model_type"] == "deberta-v2":
+        ns = SimpleNamespace(**dict(cfg, type_vocab_size=1))
     state = dict(BS.synthetic_state(ns, dev, 0))
     g = torch.Generator(device=dev); g.manual_seed(977)
     if cfg["model_type"] == "modernbert":
@@ -146,6 +157,19 @@ def make_encoder(cfg, extra_state=None):
             else:
                 st[f"{p}1.DenseReluDense.wi.weight"] = wi
             st[f"{p}1.DenseReluDense.wo.weight"] = state[f"{b}{l}.output.dense.weight"]
+        state = st
+    elif cfg["model_type"] == "deberta-v2":
+        # the same draws under DebertaV2Model's names: no position and token-type tables, a position table N(0, 1) behind a unit LayerNorm
+        st = {}
+        for k, v in state.items():
+            if "position_embeddings" in k or "token_type_embeddings" in k:
+                continue
+            for nm in ("query", "key", "value"):
+                k = k.replace(f"attention.self.{nm}.", f"attention.self.{nm}_proj.")
+            st[k] = v
+        st["encoder.rel_embeddings.weight"] = torch.randn(2 * cfg["position_buckets"], cfg["hidden_size"], generator=g, device=dev)
+        st["encoder.LayerNorm.weight"] = torch.ones(cfg["hidden_size"], device=dev)
+        st["encoder.LayerNorm.bias"] = torch.zeros(cfg["hidden_size"], device=dev)
         state = st
     elif cfg["model_type"] == "nomic_bert":
         names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """What the classification head costs: KR_POOL_CLASSIFY against KR_POOL_CLS on ONE handle with a head (synthetic weights), alternated in one process.
 
-    python tools/rerank_bench.py [--shape xlmr-large|modernbert-base] [--pooling cls|mean] [--batches 100x256,1000x128,1x64] [--rounds 6] [--labels 1] [--once]
+    python tools/rerank_bench.py [--shape xlmr-large|modernbert-base|deberta-v3-base] [--pooling cls|mean] [--batches 100x256,1000x128,1x64] [--rounds 6] [--labels 1] [--once]
 
 The two forwards differ behind the last LayerNorm only (k_pool's raw rows + k_cls_head instead of the normalising k_pool), so the difference of the medians is
 the head.  --once runs one classify forward per batch shape and nothing else: the run to put under a kernel trace (the k_cls_head row is the head's launch).
 --shape modernbert-base (22 layers, H 768, 12 heads of 64, FF 1152, vocab 50368): ModernBertForSequenceClassification's head, dense -> gelu -> LayerNorm ->
-classifier; --pooling mean makes it read the masked mean, and the plain pool it is compared with is then KR_POOL_MEAN."""
+classifier; --pooling mean makes it read the masked mean, and the plain pool it is compared with is then KR_POOL_MEAN.
+--shape deberta-v3-base (12 layers, H 768, 12 heads of 64, FF 3072, 256 buckets): DebertaV2ForSequenceClassification's head under the library's classifier.* names,
+dense -> gelu -> classifier."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,7 +31,8 @@ import enc_bench as EB  # noqa: E402  (its shape table)
 dev = torch.device("cuda:0")
 cfg = EB.SHAPES[args.shape]
 modern = cfg.get("model_type", "bert") == "modernbert"
-assert modern or cfg.get("model_type", "bert") in ("bert", "xlm-roberta", "roberta", "camembert"), "the heads run on BERT / RoBERTa and ModernBert handles"
+deberta = cfg.get("model_type", "bert") == "deberta-v2"
+assert modern or deberta or cfg.get("model_type", "bert") in ("bert", "xlm-roberta", "roberta", "camembert"), "the heads run on BERT / RoBERTa, DeBERTa and ModernBert handles"
 assert modern or args.pooling == "cls", "--pooling mean is ModernBERT's"
 H = cfg["hidden_size"]
 g = torch.Generator(device=dev); g.manual_seed(31)
@@ -38,6 +41,10 @@ PLAIN = POOL_MEAN if args.pooling == "mean" else POOL_CLS
 if modern:
     head = {"head.dense.weight": randn(H, H) / H ** 0.5, "head.norm.weight": 1 + 0.5 * randn(H), "classifier.weight": 4 * randn(args.labels, H) / H ** 0.5,
             "classifier.bias": randn(args.labels), "config.classifier_pooling": torch.tensor([float(args.pooling == "mean")])}
+    enc = EB.make_encoder(cfg, extra_state=head)
+elif deberta:
+    head = {"classifier.dense.weight": randn(H, H) / H ** 0.5, "classifier.dense.bias": 0.5 * randn(H), "classifier.out_proj.weight": 4 * randn(args.labels, H) / H ** 0.5,
+            "classifier.out_proj.bias": randn(args.labels)}
     enc = EB.make_encoder(cfg, extra_state=head)
 else:
     ns = BS.SimpleNamespace(**cfg)
