@@ -241,6 +241,11 @@ typedef struct {
  * >= 0 (needs the six "cls.predictions.*" tensors, below; without them KR_ESTATE).  Accepted by kr_encoder_forward, kr_encoder_forward_tt and
  * kr_encoder_forward_packed; combined with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT: KR_EINVAL.  The value 3 stays refused. */
 #define KR_POOL_SPLADE 4
+/* Last-token pooling (decoder-LLM embedders): out [B, hidden] = normalize(the final row of the sequence's highest attended column).  Accepted by the three
+ * forward entry points on decoder handles ("config.decoder_attention", below) only — on every other handle it stays KR_EINVAL, and the message says so —
+ * and never with KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT.  Packing, attention and the last layer (on every row) are KR_POOL_MEAN's; a sequence without
+ * attended tokens gives a NaN row (not an error), like the mean. */
+#define KR_POOL_LAST 5
 #define KR_POOL_WITH_SPARSE 0x10
 #define KR_POOL_WITH_COLBERT 0x20
 
@@ -345,6 +350,23 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   out [B, P] = normalize(W . pooled) instead of [B, hidden] (the caller knows P from the tensor it loaded); an all-masked sequence still gives a NaN row.
  *   Like the settings it is fixed at the first finalize: later the same P takes new values, another P — or the tensor on a handle finalized without it — is
  *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]).
+ *   "config.decoder_attention": data = ONE float, 1 = causal attention, 0 = bidirectional attention on the same stack; anything else is KR_EINVAL.  Loading it
+ *   before the handle's first finalize makes the handle a DECODER handle for life (transformers Qwen2Model / LlamaModel / MistralModel used as embedders:
+ *   the Qwen2.5-0.5B family such as KaLM-embedding-multilingual-mini, Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes); the usual rule of the settings holds.  It
+ *   needs "config.rotary_inv_freq" (max_pos <= 8192; max_pos only bounds S) and is refused at finalize (KR_EINVAL) next to
+ *   "config.position_padding_idx", "config.local_attention_layers" and its two companions, "config.t5_feed_forward", the DeBERTa settings or a relative
+ *   attention bias: a handle has one position scheme.  In kr_bert_cfg: ln_eps = rms_norm_eps, type_vocab = 1.  On such a handle
+ *     - the stack is PRE-LN with RMS norms: x = embed_tokens[id] — no embedding norm, no position table, no token types —,
+ *       x += o_proj . attention(rot(q), rot(k), v of input_layernorm(x)), x += down_proj . (silu(gate_proj . n) * up_proj . n) with
+ *       n = post_attention_layernorm(x), output = norm(x); rotation and pairing are those of "config.rotary_inv_freq" above;
+ *     - with the value 1 a key is admitted iff its column <= the query's column (columns of the padded [B, S] batch, so masks with holes and left padding
+ *       need no further rule), on top of the padding mask; the 64-key steps above a 32-query tile's diagonal are skipped;
+ *     - the state dict loads unchanged, with or without a leading "model.": "embed_tokens.weight", "layers.N.input_layernorm.weight",
+ *       "layers.N.self_attn.{q,k,v,o}_proj.weight" [hidden, hidden], "layers.N.post_attention_layernorm.weight", "layers.N.mlp.{gate,up,down}_proj.weight",
+ *       "norm.weight", and optionally "layers.N.self_attn.{q,k,v}_proj.bias" (Qwen2; zero unless loaded; q's and k's are added before the rotation).  o_proj and
+ *       the MLP have no bias.  Grouped-query checkpoints arrive EXPANDED: each KV head's rows of k_proj / v_proj repeated heads / kv_heads times (exact);
+ *       any other name on the handle, a head's tensors included, is KR_EINVAL at finalize, and these names' decoder-only rows on another handle likewise;
+ *     - the forwards take KR_POOL_MEAN and KR_POOL_LAST; KR_POOL_CLS / KR_POOL_CLASSIFY / KR_POOL_SPLADE are KR_EINVAL.
  *   "config.deberta_position_buckets" + "config.deberta_max_relative_positions": data = ONE float each, Bk (even, 2 .. 256) and M (M - 1 > Bk / 2):
  *   DebertaV2Config's position_buckets and max_relative_positions (max_position_embeddings where that is < 1).  The two together, loaded before the first
  *   finalize, make the handle a DeBERTa handle (DebertaV2Model: microsoft/deberta-v3-* and their fine-tunes) for life; the usual rule of the settings holds

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KIRAG_AMD_LIB") or os.path.join(_HERE, "libkirag_amd.so")   # KIRAG_AMD_LIB: another build of the library (A/B)
 ABI_VERSION = 9
 POOL_SPLADE = 4          # KR_POOL_SPLADE (include/kirag_amd.h): the MLM head max-pooled over the attended tokens, out [B, vocab]
+POOL_LAST = 5            # KR_POOL_LAST: the row of the highest attended column, normalised (decoder handles: config.decoder_attention)
 
 
 class KiragAmdError(RuntimeError):

@@ -70,6 +70,7 @@ using model::AM_PLAIN;
 using model::AM_BIAS;
 using model::AM_WIN;
 using model::AM_DISENT;
+using model::AM_CAUSAL;
 
 struct Encoder {
     kr_bert_cfg cfg{};
@@ -250,15 +251,26 @@ namespace kr {
 namespace KR_ENC_NS {
 
 static AttnBiasArgs bias_args(const Encoder* e) { return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0}; }
-static AttnWinArgs win_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->plan.half_window, e->bias_gather ? 1 : 0}; }
+static AttnWinArgs win_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->plan.half_window, e->plan.half_window, e->bias_gather ? 1 : 0}; }
+// causal: the window's kernels with a one-sided window — every column to the left (no column difference reaches max_pos), none to the right
+static AttnWinArgs causal_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->cfg.max_pos, 0, e->bias_gather ? 1 : 0}; }
+// the kernel instantiation a layer's attention runs: AM_CAUSAL has none of its own
+constexpr int attn_kernel_mode(int am) { return am == AM_CAUSAL ? (int)AM_WIN : am; }
 // AM: the attention of a layer (model::AttnMode)
 // (p0, W: pos_span of the forward's S — the layout k_pos_scores wrote this layer's scores in)
 template <int AM>
-static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN, AM == AM_DISENT> attn_mode_args(const Encoder* e, int p0, int W) {
+static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN || AM == AM_CAUSAL, AM == AM_DISENT> attn_mode_args(const Encoder* e, int p0, int W) {
     if constexpr (AM == AM_DISENT) return AttnDisentArgs{e->pos_sc, e->tok_pos, e->deb_bucket, e->cfg.max_pos - 1, p0, W, e->cfg.heads};
     else if constexpr (AM == AM_BIAS) return bias_args(e);
     else if constexpr (AM == AM_WIN) return win_args(e);
+    else if constexpr (AM == AM_CAUSAL) return causal_args(e);
     else return AttnNoBiasArgs{};
+}
+
+template <int DH, int HPB, int KM>
+static int& attn_lds_attr(int device) {
+    static int attr_lds_dev[64] = {};
+    return attr_lds_dev[device & 63];
 }
 
 template <int DH, int HPB, int AM>
@@ -268,9 +280,9 @@ static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W,
     // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
     const int kchunk = cap < 128 ? cap : 128;
     const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
-    constexpr bool BIAS = AM == AM_BIAS, WIN = AM == AM_WIN, DIS = AM == AM_DISENT;
-    static int attr_lds_dev[64] = {};   // per device: function attributes belong to the device's code object instance (one per instantiation of this function)
-    int& attr_lds = attr_lds_dev[e->device & 63];
+    constexpr bool BIAS = AM == AM_BIAS, WIN = attn_kernel_mode(AM) == AM_WIN, DIS = AM == AM_DISENT;
+    // per device: function attributes belong to the device's code object instance (one per kernel instantiation: AM_CAUSAL shares AM_WIN's)
+    int& attr_lds = attn_lds_attr<DH, HPB, attn_kernel_mode(AM)>(e->device);
     if (lds > attr_lds) {
         KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN, DIS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_lds = lds;
@@ -288,7 +300,7 @@ static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int64_t pairs = (int64_t)B * e->cfg.heads;
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
     const auto ba = attn_mode_args<AM>(e, 0, 0);
-    hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, AM == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
+    hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, attn_kernel_mode(AM) == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
                        e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, ba);
     return 0;
 }
@@ -453,6 +465,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // KR_POOL_SPLADE packs and attends like KR_POOL_MEAN (no query-only rows) and differs behind the last LayerNorm only
     const bool splade = pool == KR_POOL_SPLADE;
     if (splade) pool = KR_POOL_MEAN;
+    // KR_POOL_LAST packs and attends like KR_POOL_MEAN too (no query-only row, the last layer on every row); k_pool alone sees the difference
+    const int pool_select = pool;
+    if (pool == KR_POOL_LAST) pool = KR_POOL_MEAN;
     const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
     const bool disent = p.pos == POS_DISENT;                                       // a DeBERTa handle: every sequence through k_attn_lds (the mode is not built into k_attn_dma)
     const bool long_seq = nqt_max > 4 && !e->kn.attn_lds && !disent;               // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
@@ -480,8 +495,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     unsigned ln_mult = 8u;
     const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
     if (p.rotary) hipLaunchKernelGGL(k_rot_pos, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nq, align, e->tok_pos, e->tok_rpos);
-    const bool embed_rms = p.pos == POS_BIAS_ONLY;
-    if (embed_rms) {     // the embedding row is the residual stream; xb = block 0's attention norm of it
+    const bool embed_rms = p.pos == POS_BIAS_ONLY || p.family == DECODER;
+    if (embed_rms) {     // the embedding row is the residual stream; xb = block 0's attention norm of it (T5 and decoder handles)
         auto embed_kernel = H <= 512 ? &k_embed_rms<1> : H <= 1024 ? &k_embed_rms<2> : &k_embed_rms<4>;
         hipLaunchKernelGGL(embed_kernel, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->d_T, e->word, e->elng, eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
     } else {
@@ -554,7 +569,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
                     return launch_attention<DH, AM_DISENT>(e, B, cap, nqt_max, long_seq, span_p0, span_W, st);
                 }
                 return am == AM_BIAS ? launch_attention<DH, AM_BIAS>(e, B, cap, nqt_max, long_seq, 0, 0, st)
-                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, 0, 0, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, 0, 0, st);
+                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, 0, 0, st)
+                     : am == AM_CAUSAL ? launch_attention<DH, AM_CAUSAL>(e, B, cap, nqt_max, long_seq, 0, 0, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, 0, 0, st);
             };
             if (H == 32 * e->cfg.heads) KR_TRY(go(std::integral_constant<int, 32>{})); else KR_TRY(go(std::integral_constant<int, 64>{}));
         }
@@ -598,7 +614,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     }
     const RowSet& r = shortcut ? cls_rows : all_rows;
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
-    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool,
+    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool_select,
                        p.head[HEAD_DENSE] || classify ? e->pooled : e->out, e->d_err);
     if (classify) {              // the classification head: out [B, L] = Wo . tanh(Wd . pooled + bd) + bo
         const int NJ = H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8, head_lds = CH_SEQ * 2 * H * 4;
@@ -720,8 +736,17 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
     if (total_tokens > (int64_t)B * S) return fail(KR_EINVAL, "total_tokens %lld exceeds B * S = %lld", (long long)total_tokens, (long long)B * S);
     const int flags = pool & M3_FLAGS;
     pool &= ~M3_FLAGS;
-    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY && pool != KR_POOL_SPLADE)
+    const bool decoder = p.family == model::DECODER;
+    if (pool == KR_POOL_LAST && !decoder)
+        return fail(KR_EINVAL, "pool = 5 (last token) on a %s handle: last-token pooling is accepted on decoder handles (config.decoder_attention) only; elsewhere "
+                               "pool must be 0 (mean), 1 (cls), 2 (classify) or 4 (splade), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)",
+                    model::family_name(p.family));
+    if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY && pool != KR_POOL_SPLADE && pool != KR_POOL_LAST)
         return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls), 2 (classify) or 4 (splade), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)");
+    if (flags && pool == KR_POOL_LAST) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 5 (last token)");
+    if (decoder && pool != KR_POOL_MEAN && pool != KR_POOL_LAST)
+        return fail(KR_EINVAL, "pool = %d (%s) on a decoder handle: it takes KR_POOL_MEAN (0) and KR_POOL_LAST (5) — under a causal mask the first token sees itself alone, "
+                               "and the handle has no head", pool, pool == KR_POOL_CLS ? "KR_POOL_CLS" : pool == KR_POOL_CLASSIFY ? "KR_POOL_CLASSIFY" : "KR_POOL_SPLADE");
     if (flags && pool == KR_POOL_CLASSIFY) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 2 (classify)");
     if (flags && pool == KR_POOL_SPLADE) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 4 (splade)");
     if (pool == KR_POOL_SPLADE && !p.head[model::HEAD_MLM])

@@ -79,9 +79,12 @@ struct AttnNoBiasArgs {};
 // Sliding-window ("local") attention (ModernBert's sliding_attention layers): key admitted iff |col_key - col_query| <= w, col = the token's column in the
 // padded batch (tok_pos), on top of the padding mask.  The key columns come the same two ways as for the bias.  An excluded score becomes -inf after the
 // S^T chains; the steps that can hold no admitted key for a wave's whole 32-query tile are skipped (AttnBand), by ONE rule in both kernels.
+// The window has a left and a right extent: admitted iff -wl <= col_key - col_query <= wr.  ModernBert's is symmetric (wl = wr = w).  CAUSAL attention (decoder
+// handles: key column <= query column) is the same test with wr = 0 and a wl no column difference reaches (max_pos): one compare per score, the band's upper
+// end is the tile's own last query, so every 64-key step above a tile's diagonal is skipped and k_attn_dma stages about half the chunks of a long sequence.
 struct AttnWinArgs {
     const int* col;       // tok_pos
-    int w;                // half-window (>= 1)
+    int wl, wr;           // extents to the left (keys before the query) and to the right, wl + wr >= 1
     int gather;           // != 0: take every key's column from `col` even when they are consecutive
 };
 // Disentangled attention (DeBERTa-v2 / v3): score(head, query i, key j) += q_i . PK[p] + k_j . PQ[p], p = deberta_bucket(col_i - col_j) (encoder_model.hpp),
@@ -110,8 +113,8 @@ template <int GATHER>       // 0: consecutive key columns, 1: gathered with 16-b
 struct AttnWinLane {
     static constexpr bool on = false, win = true;
     const int* col;       // columns of the sequence's packed rows (GATHER)
-    int base;             // w - column of this lane's query (+ 8 hf + the column of key 0 when the columns are consecutive)
-    unsigned w2;          // 2 w: admitted <=> (unsigned)(col_key - col_query + w) <= 2 w
+    int base;             // wl - column of this lane's query (+ 8 hf + the column of key 0 when the columns are consecutive)
+    unsigned w2;          // wl + wr: admitted <=> (unsigned)(col_key - col_query + wl) <= wl + wr
     int nk;
 };
 template <bool GATHER>
@@ -161,8 +164,8 @@ __device__ __forceinline__ auto attn_bias_lane(const AttnModeArg<BM>& ba, int64_
         const int* col = ba.col + off;
         AttnWinLane<BM - 3> wl;
         wl.col = col;
-        wl.base = ba.w - col[qi] + (BM == 3 ? 8 * hf + (nk > 0 ? col[0] : 0) : 0);
-        wl.w2 = 2u * (unsigned)ba.w;
+        wl.base = ba.wl - col[qi] + (BM == 3 ? 8 * hf + (nk > 0 ? col[0] : 0) : 0);
+        wl.w2 = (unsigned)ba.wl + (unsigned)ba.wr;
         wl.nk = nk;
         return wl;
     } else if constexpr (BM != 0) {
@@ -208,7 +211,7 @@ __device__ __forceinline__ void attn_bias_tile(f32x16& st, const AttnDisentLane&
         st[r] = dl.sc[dl.qoff + p] + dl.sc[(unsigned)key * dl.stride + dl.hoff + p];
     }
 }
-// the window of one 32-key tile: scores of keys outside |col_key - col_query| <= w become -inf (kb = index of the tile's first key in its sequence)
+// the window of one 32-key tile: scores of keys outside -wl <= col_key - col_query <= wr become -inf (kb = index of the tile's first key in its sequence)
 template <int GATHER>
 __device__ __forceinline__ void attn_window_tile(f32x16& st, const AttnWinLane<GATHER>& wl, int kb, int hf) {
     if constexpr (GATHER == 0) {
@@ -239,18 +242,19 @@ __device__ __forceinline__ void attn_window_tile(f32x16& st, const AttnWinLane<G
 }
 
 // Which 64-key steps a wave's 32-query tile (first query q0) visits under a window.  Attended columns are packed in increasing order, so
-// |col_i - col_j| >= |i - j|: every admissible key of packed query i < nk lies in packed [i - w, i + w], with or without holes in the mask.  The query-only
-// CLS row (packed last, index nk, column 0; nq == nk + 1) admits keys of column <= w: packed [0, w].  A step [kb, kb + 64) is visited iff it meets the
+// |col_i - col_j| >= |i - j|: every admissible key of packed query i < nk lies in packed [i - wl, i + wr], with or without holes in the mask (causal, wr = 0:
+// packed index order IS column order, so the band [0, i] is exact).  The query-only
+// CLS row (packed last, index nk, column 0; nq == nk + 1) admits keys of column <= wr: packed [0, wr] (a causal handle never packs one).  A step [kb, kb + 64) is visited iff it meets the
 // union of the tile's bands; both kernels apply this rule to the same 64-aligned steps, so they run the same steps on a tile.
 struct AttnBand {
     int lo, hi, xhi;      // packed keys [lo, hi] of the tile's key-bearing queries (hi < lo: none); [0, xhi] of the CLS row (xhi < 0: not in this tile)
     __device__ __forceinline__ bool visits(int kb) const { return (kb <= hi && kb + 63 >= lo) || kb <= xhi; }
 };
-__device__ __forceinline__ AttnBand attn_band(int q0, int q1, int nk, int nq, int w) {      // queries [q0, q1] (q1 may lie past nq - 1)
+__device__ __forceinline__ AttnBand attn_band(int q0, int q1, int nk, int nq, int wl, int wr) {      // queries [q0, q1] (q1 may lie past nq - 1)
     AttnBand b;
-    b.lo = max(q0 - w, 0);
-    b.hi = q0 < nk ? min(q1, nk - 1) + w : -1;
-    b.xhi = (nq > nk && q1 >= nk) ? w : -1;
+    b.lo = max(q0 - wl, 0);
+    b.hi = q0 < nk ? min(q1, nk - 1) + wr : -1;
+    b.xhi = (nq > nk && q1 >= nk) ? wr : -1;
     return b;
 }
 
@@ -477,8 +481,8 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
     // window: the steps this wave's tile visits, and the chunks any tile of the block visits (block-uniform: the others are not staged)
     AttnBand band{}, bband{};
     if constexpr (WIN) {
-        band = attn_band(q0, q0 + 31, nk, nq, ba.w);
-        bband = attn_band((int)blockIdx.z * QT * 32, (int)blockIdx.z * QT * 32 + QT * 32 - 1, nk, nq, ba.w);
+        band = attn_band(q0, q0 + 31, nk, nq, ba.wl, ba.wr);
+        bband = attn_band((int)blockIdx.z * QT * 32, (int)blockIdx.z * QT * 32 + QT * 32 - 1, nk, nq, ba.wl, ba.wr);
     }
     constexpr int NB = HPB == 1 ? 4 : 2;                  // loads in flight per thread, head and batch (register budget: 3 blocks per CU = 168 VGPRs; HPB = 4 means <= 32 keys: 2 cover a head)
     for (int kc0 = 0; kc0 < nk; kc0 += kchunk) {
@@ -643,11 +647,11 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     using G = AdmaGeom<DH>;
     constexpr int ADMA_PIECES = G::PIECES, KB = G::KB, ADMA_STAGE = G::STAGE;
     constexpr int NC = DH / 8, NCS = DH == 64 ? 3 : 2, KROWS = 1024 / (2 * DH);  // 16-B chunks per K row (1 << NCS), keys per 1-KiB K piece
-    // chunks [c_lo, nchunks) are streamed: all of them, or under a window those that meet the band of the block's 256 queries (at w = 64 at most 7; a block
+    // chunks [c_lo, nchunks) are streamed: all of them, or under a window those that meet the band of the block's 256 queries (at w = 64 at most 7, causal: up to the block's last query; a block
     // that holds the query-only CLS row starts at chunk 0)
     int c_lo = 0, nchunks = (nk + 63) >> 6;
     if constexpr (WIN) {
-        const AttnBand bb = attn_band(qg * ADMA_QT * 32, qg * ADMA_QT * 32 + ADMA_QT * 32 - 1, nk, nq, ba.w);
+        const AttnBand bb = attn_band(qg * ADMA_QT * 32, qg * ADMA_QT * 32 + ADMA_QT * 32 - 1, nk, nq, ba.wl, ba.wr);
         c_lo = bb.xhi >= 0 ? 0 : (bb.lo >> 6);
         nchunks = min(nchunks, max(bb.hi, bb.xhi) / 64 + 1);      // hi, xhi >= -1
     }
@@ -706,7 +710,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     AttnBand band[2] = {};
     if constexpr (WIN) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) band[j] = attn_band(q0[j], q0[j] + 31, nk, nq, ba.w);
+        for (int j = 0; j < 2; ++j) band[j] = attn_band(q0[j], q0[j] + 31, nk, nq, ba.wl, ba.wr);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): Q fragments (and chunks 0, 1) have landed
     auto turn = [&](int ci) {

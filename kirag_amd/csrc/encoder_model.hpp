@@ -1,4 +1,4 @@
-// What an encoder handle IS, decided in one place and without a device: the state-dict names of the six model families, the heads, the settings, and
+// What an encoder handle IS, decided in one place and without a device: the state-dict names of the seven model families, the heads, the settings, and
 // describe(), which turns what was loaded into a ModelPlan (or the refusal kr_encoder_finalize returns).  Host-only: nothing here includes HIP, so the
 // tables are tested by a stand-alone program (tests/capi/encoder_model_check.cpp).  The device side of every row lives in encoder_weights.hpp (where a
 // slot is stored) and encoder.hip (enqueue_forward: which launches a plan selects).  Adding a family or a head: DESIGN.md, "Adding a family / a head".
@@ -41,10 +41,13 @@ inline Error err(int code, const char* fmt, ...) {
 //   (config.deberta_position_buckets + config.deberta_max_relative_positions, DebertaV2Model): BERT's post-LN layer under the projections' names query_proj /
 //   key_proj / value_proj, no position table and no token types, and disentangled attention: every score carries q_i . PK[p] + k_j . PQ[p] with p the log bucket
 //   of the column difference (deberta_bucket), PQ / PK the layer's own q / k projections of the (normalised) table encoder.rel_embeddings, scale 1 / sqrt(3 d_h).
-enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA };
+//   DECODER (config.decoder_attention, needs config.rotary_inv_freq; Qwen2Model / LlamaModel / MistralModel used as embedders): T5's schedule — pre-LN, RMS
+//   norms, the embedding row straight into the residual stream — with NOMIC's rotary q / k and SwiGLU under NOMIC's projection names, optional q / k / v biases
+//   (Qwen2), and with the setting's value 1 a causal mask: key column <= query column (AM_CAUSAL).  Grouped-query attention arrives expanded to [H, H].
+enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA, DECODER };
 constexpr uint8_t GATED_NAME = 0x80;   // or-ed into a slot's family: the tensor came as one half of a gated projection under T5's names (wi_0 / wi_1)
 inline Family fam_of(uint8_t got) { return (Family)(got & 0x7f); }
-inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5", "DeBERTa-v2"}; return n[f]; }
+inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5", "DeBERTa-v2", "decoder"}; return n[f]; }
 
 // tensor slots: 0..4 embeddings, then L_COUNT per layer (L_UW: the second half of a gated intermediate projection); below zero what is no slot of `got`
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
@@ -83,7 +86,7 @@ inline int64_t extent(const kr_bert_cfg& c, Ext x, int64_t free_dim = 0) {
 // else "layers." at the start or behind a '.' for NomicBert's and ModernBert's, "encoder.block." / "block." at the start for T5's.
 enum Match : uint8_t { WHOLE, TAIL, ENDS, EMB, LAYER };
 // NORM_BEFORE: a pre-LN family's norm in front of the attention of layer N is applied by the launch behind the FF of layer N - 1 and stored there (L_LN2*);
-//   layer 0's is the embedding norm's slot under T5's names and the identity (refused) under ModernBert's.  LAST_LAYER: the stack's final norm, the L_LN2* of
+//   layer 0's is the embedding norm's slot under T5's and the decoders' names and the identity (refused) under ModernBert's.  LAST_LAYER: the stack's final norm, the L_LN2* of
 //   the last layer.  BLOCK0: T5's one bias table is spelled as a tensor of block 0.  GATED: see GATED_NAME.
 enum : uint8_t { NORM_BEFORE = 1, LAST_LAYER = 2, BLOCK0 = 4, GATED = 8 };
 struct NameRow { const char* text; Match match; Family fam; int id; Ext r, c; uint8_t flags; };
@@ -96,6 +99,11 @@ static const NameRow NAME_ROWS[] = {
     {"layer.0.layer_norm.weight", LAYER, T5, L_LN2G, XH, X1, NORM_BEFORE}, {"layer.1.layer_norm.weight", LAYER, T5, L_LN1G, XH, X1, 0},
     {"layer.1.DenseReluDense.wi.weight", LAYER, T5, L_IW, XFF, XH, 0}, {"layer.1.DenseReluDense.wi_0.weight", LAYER, T5, L_IW, XFF, XH, GATED},
     {"layer.1.DenseReluDense.wi_1.weight", LAYER, T5, L_UW, XFF, XH, GATED}, {"layer.1.DenseReluDense.wo.weight", LAYER, T5, L_FW, XH, XFF, 0},
+    // Qwen2Model / LlamaModel / MistralModel (with or without the "model." prefix of the ...ForCausalLM state dicts): the projections come under NomicBert's rows
+    // below; the final norm by its WHOLE names (a tail "norm.weight" would be ModernBert's embeddings.norm.weight); embed_tokens.weight is T5's row above
+    {"model.embed_tokens.weight", WHOLE, DECODER, T_WORD, XV, XH, 0}, {"norm.weight", WHOLE, DECODER, L_LN2G, XH, X1, LAST_LAYER}, {"model.norm.weight", WHOLE, DECODER, L_LN2G, XH, X1, LAST_LAYER},
+    {"input_layernorm.weight", LAYER, DECODER, L_LN2G, XH, X1, NORM_BEFORE}, {"self_attn.q_proj.bias", LAYER, DECODER, L_QB, XH, X1, 0},
+    {"self_attn.k_proj.bias", LAYER, DECODER, L_KB, XH, X1, 0}, {"self_attn.v_proj.bias", LAYER, DECODER, L_VB, XH, X1, 0},
     {"final_norm.weight", TAIL, MODERN, L_LN2G, XH, X1, LAST_LAYER}, {"final_norm.bias", TAIL, MODERN, L_LN2B, XH, X1, LAST_LAYER},
     {"encoder.relative_attention_bias.weight", ENDS, MPNET, T_RELBIAS, XBUCKETS, XHEADS, 0},
     // DebertaV2Model: the position table (its row count is 2 Bk: check_tensor) and its norm; the attention projections into BERT's slots, every other tensor
@@ -134,7 +142,7 @@ static const NameRow NAME_ROWS[] = {
 };
 
 // the rows a layer prefix leads to: 0 = BERT's and MPNet's, 1 = NomicBert's and ModernBert's, 2 = T5's
-inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN ? 1 : 0; }      // (DeBERTa's layers are "encoder.layer.N.": group 0)
+inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN || f == DECODER ? 1 : 0; }      // (DeBERTa's layers are "encoder.layer.N.": group 0)
 // the layer prefix of `s`, T5's only or the other two: its group and where the layer index starts, or -1
 inline int layer_prefix(const std::string& s, bool t5, size_t& at) {
     if (t5) {
@@ -162,7 +170,7 @@ inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& ou
     auto take = [&](const NameRow& r, long l) -> Error {
         out.fam = r.fam; out.gated = (r.flags & GATED) != 0; out.numel = extent(cfg, r.r) * extent(cfg, r.c); out.layer = (int)l;
         if ((r.flags & BLOCK0) && l != 0) return err(KR_EINVAL, "'%s': block 0 holds a T5 encoder's one relative attention bias", name);
-        if ((r.flags & NORM_BEFORE) && l == 0 && r.fam != T5) return err(KR_EINVAL, "'%s': attn_norm of layer 0 is the identity in ModernBert", name);
+        if ((r.flags & NORM_BEFORE) && l == 0 && r.fam == MODERN) return err(KR_EINVAL, "'%s': attn_norm of layer 0 is the identity in ModernBert", name);
         if (r.flags & LAST_LAYER) l = cfg.layers - 1;
         if ((r.flags & NORM_BEFORE) && l == 0) out.slot = T_ELNG;
         else out.slot = r.id < 0 || (r.match != LAYER && !(r.flags & LAST_LAYER)) ? r.id : T_LAYER0 + (int)((r.flags & NORM_BEFORE) ? l - 1 : l) * L_COUNT + r.id;
@@ -306,7 +314,8 @@ inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_
 //   is known to handles with that head only.
 //   config.deberta_position_buckets = Bk (even, 2 .. 256) and config.deberta_max_relative_positions = M (M - 1 > Bk / 2): DebertaV2Config's position_buckets and
 //   max_relative_positions (max_position_embeddings where that is < 1); the two together make the handle a DeBERTa handle.
-enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_COUNT };
+//   config.decoder_attention: the handle is a decoder-LLM stack (needs config.rotary_inv_freq); 1 = causal attention, 0 = bidirectional on the same stack.
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_DECODER_ATTN, SET_COUNT };
 enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
 struct SettingRow {
     const char* name;
@@ -330,6 +339,7 @@ static const SettingRow SETTINGS[SET_COUNT] = {
     {"config.classifier_pooling", X1, V_INT, 0, 1, "0 ([CLS] row) or 1 (masked mean)", "the [CLS] row", 0, 0, HEAD_MODERN_CLS, 0},
     {"config.deberta_position_buckets", X1, V_INT, 2, DEB_MAX_BUCKETS, "an even integer", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 2},
     {"config.deberta_max_relative_positions", X1, V_INT, 2, 65536, "an integer M with M - 1 > position_buckets / 2", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 0},
+    {"config.decoder_attention", X1, V_INT, 0, 1, "0 (bidirectional) or 1 (causal)", "not a decoder handle", 0, -1, -1, 0},
 };
 constexpr int64_t SETTING_MAX_VALUES = 4096;
 struct Settings {
@@ -470,11 +480,12 @@ static const FamilyRow FAMILIES[] = {
     {MODERN, true, false, bits(T_WORD, T_TYPE, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G, L_UW)},
     {T5, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G)},
     {DEBERTA, false, false, bits(T_WORD, T_ELNG, T_ELNB), (1u << L_COUNT) - 1 - bits(L_UW)},
+    {DECODER, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G, L_UW)},
 };
 
 enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY, POS_DISENT };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table), none (DeBERTa: a zero row)
 enum QkvKind : uint8_t { QKV_PLAIN, QKV_ROT, QKV_ROT_BIAS };                       // EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB (a ModernBert layer with attn.Wqkv.bias)
-enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2, AM_DISENT = 3 };  // plain, with the relative attention bias, under the sliding window (and the local rotary table), DeBERTa's disentangled position terms
+enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2, AM_DISENT = 3, AM_CAUSAL = 4 };  // plain, with the relative attention bias, under the sliding window (and the local rotary table), DeBERTa's disentangled position terms, key column <= query column (the window's kernels with a one-sided window)
 enum FfKind : uint8_t { FF_GELU, FF_SWIGLU, FF_GEGLU, FF_RELU, FF_GEGLU_TANH };    // EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH
 struct LayerPlan { QkvKind qkv; AttnMode attn; };
 struct ModelPlan {
@@ -512,10 +523,33 @@ inline std::string slot_tensor_name(size_t slot, Family f) {
 inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded& ld, ModelPlan& plan) {
     const bool rot = set.has(SET_ROTARY), modern = set.has(SET_LOCAL_LAYERS), t5 = set.has(SET_T5_FF), rel = ld.rel_fam != FAM_NONE;
     const bool local_set = set.has(SET_ROTARY_LOCAL) || set.has(SET_HALF_WINDOW);
-    const bool deb = set.has(SET_DEB_BUCKETS) || set.has(SET_DEB_MAX_REL);
+    const bool deb = set.has(SET_DEB_BUCKETS) || set.has(SET_DEB_MAX_REL), dec = set.has(SET_DECODER_ATTN);
     const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF), Bk = set.value(SET_DEB_BUCKETS, 0), max_rel = set.value(SET_DEB_MAX_REL, 0);
-    const Family fam = deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
+    const Family fam = dec ? DECODER : deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
     const std::vector<float>& flags = set.v[SET_LOCAL_LAYERS];
+    if (dec) {
+        if (pad_idx >= 0 || modern || local_set || t5 || deb || rel)
+            return err(KR_EINVAL, "config.decoder_attention next to config.position_padding_idx / config.local_attention_layers / config.rotary_inv_freq_local / "
+                                  "config.attention_half_window / config.t5_feed_forward / config.deberta_* / a relative attention bias: a handle has one position scheme");
+        if (!rot) return err(KR_EINVAL, "config.decoder_attention without config.rotary_inv_freq: a decoder handle rotates q and k");
+        // names and family agree: the projections, post_attention_layernorm.weight under NomicBert's names (their packed row order), the norms in front of the
+        // attention, the final norm and the q / k / v biases under the decoders' own, the embedding under either spelling — and nothing else
+        for (size_t i = 0; i < ld.got.size(); ++i) {
+            if (!ld.got[i]) continue;
+            const Family g = fam_of(ld.got[i]);
+            const int id = i < T_LAYER0 ? -1 : (int)((i - T_LAYER0) % L_COUNT);
+            const bool nomic_slot = id == L_QW || id == L_KW || id == L_VW || id == L_OW || id == L_LN1G || id == L_IW || id == L_UW || id == L_FW;
+            const bool own_slot = i == T_ELNG || id == L_QB || id == L_KB || id == L_VB || id == L_LN2G;
+            if (i == T_WORD ? (g == DECODER || g == T5) : nomic_slot ? g == NOMIC : own_slot && g == DECODER) continue;
+            return err(KR_EINVAL, "'%s' on a decoder handle (config.decoder_attention): it takes embed_tokens, layers.N.{input_layernorm,post_attention_layernorm}.weight, "
+                                  "layers.N.self_attn.{q,k,v,o}_proj.weight, layers.N.self_attn.{q,k,v}_proj.bias, layers.N.mlp.{gate,up,down}_proj.weight and norm.weight",
+                       slot_tensor_name(i, g).c_str());
+        }
+    } else {
+        for (size_t i = 0; i < ld.got.size(); ++i)
+            if (fam_of(ld.got[i]) == DECODER)
+                return err(KR_EINVAL, "'%s' but config.decoder_attention was never loaded: load it before kr_encoder_finalize", slot_tensor_name(i, DECODER).c_str());
+    }
     if (deb) {
         if (!set.has(SET_DEB_BUCKETS) || !set.has(SET_DEB_MAX_REL))
             return err(KR_EINVAL, "%s without %s: a DeBERTa handle takes both", SETTINGS[set.has(SET_DEB_BUCKETS) ? SET_DEB_BUCKETS : SET_DEB_MAX_REL].name,
@@ -569,7 +603,7 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     // the bias table under the family's own name
     for (const Family f : {MODERN, T5})
         for (size_t i = 0; i < ld.got.size(); ++i) {
-            if (!ld.got[i] || i == T_TYPE || (fam_of(ld.got[i]) == f) == (fam == f)) continue;
+            if (!ld.got[i] || i == T_TYPE || (fam_of(ld.got[i]) == f) == (fam == f) || (dec && i == T_WORD)) continue;
             return fam == f ? err(KR_EINVAL, "weight slot %zu was loaded under another family's name: a handle with %s takes %s's names", i, SETTINGS[f == T5 ? SET_T5_FF : SET_LOCAL_LAYERS].name, family_name(f))
                             : err(KR_EINVAL, "weight slot %zu was loaded under a %s name but %s was never loaded: load it before kr_encoder_finalize", i, family_name(f),
                                   SETTINGS[f == T5 ? SET_T5_FF : SET_LOCAL_LAYERS].name);
@@ -603,7 +637,7 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     }
     if (rot && (pad_idx >= 0 || rel)) return err(KR_EINVAL, "config.rotary_inv_freq next to config.position_padding_idx / a relative attention bias: a handle has one position scheme");
     // q / k and the intermediate projection are packed in another row order under NomicBert's names (enc_load_weight): names and family must agree
-    for (int li = 0; li < cfg.layers && !modern && !t5; ++li) {
+    for (int li = 0; li < cfg.layers && !modern && !t5 && !dec; ++li) {
         const uint8_t* g = &ld.got[T_LAYER0 + (size_t)li * L_COUNT];
         auto under = [&](int id, bool nomic) { return g[id] && (fam_of(g[id]) == NOMIC) == nomic; };
         if (rot && (under(L_QW, false) || under(L_KW, false) || under(L_IW, false)))
@@ -626,8 +660,9 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     plan.deb_buckets = Bk; plan.deb_max_rel = max_rel; plan.deb_norm = deb && ld.rel_ln[0]; plan.cls_gelu = deb;
     plan.pad_idx = pad_idx; plan.half_window = set.value(SET_HALF_WINDOW, 0);
     for (int li = 0; li < cfg.layers; ++li)
-        plan.layers.push_back({!rot ? QKV_PLAIN : modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] ? QKV_ROT_BIAS : QKV_ROT,
-                               deb ? AM_DISENT : rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
+        plan.layers.push_back({!rot ? QKV_PLAIN : (modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB]) ||
+                                                    (dec && (ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] || ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_KB])) ? QKV_ROT_BIAS : QKV_ROT,
+                               dec ? (set.value(SET_DECODER_ATTN) == 1 ? AM_CAUSAL : AM_PLAIN) : deb ? AM_DISENT : rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
     plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot ? FF_SWIGLU : FF_GELU;
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;

@@ -391,6 +391,7 @@ __global__ __launch_bounds__(256) void k_ln16_pre(const uint16_t* __restrict__ y
 // pooling + L2 normalisation: one block of 16 waves per sequence.  Masked mean: wave w sums tokens w, w + 16, ... (in that order), the 16 partial rows are added
 // in wave order — a fixed order per sequence, whatever the batch.  (Rounds 1-4 used 4 waves: the kernel is bound by the VALU work of decoding and adding
 // 262 k elements for a 256-token sequence on ONE block, 37 us — 2.7 % of a one-sequence forward; 16 waves: see profiles/r05.)
+// KR_POOL_LAST (decoder handles): the sequence's last packed row in the CLS row's place.
 // RAW (KR_POOL_CLASSIFY, the input of k_cls_head): the pooled row is written as it is, not divided by its norm; the norm is still formed, for the error word.
 constexpr int POOL_WAVES = 16;
 template <int NJ, bool RAW = false>     // 256-element steps that cover a row: H <= 256 NJ
@@ -407,8 +408,12 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __rest
     float4 acc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int t_begin = pool == KR_POOL_CLS ? (wave == 0 ? seq_cls[b] : 1 << 30) : wave;
-    const int t_end = pool == KR_POOL_CLS ? (wave == 0 ? seq_cls[b] + 1 : 0) : nk;
+    // one row — the CLS row, or KR_POOL_LAST's last packed row (attended columns are packed in increasing order: the highest attended column; nk == 0: none,
+    // and the row is NaN like the mean of nothing) — is wave 0's alone
+    const bool one_row = pool == KR_POOL_CLS || pool == KR_POOL_LAST;
+    const int row = pool == KR_POOL_CLS ? seq_cls[b] : nk - 1;
+    const int t_begin = one_row ? (wave == 0 && row >= 0 ? row : 1 << 30) : wave;
+    const int t_end = one_row ? (wave == 0 && row >= 0 ? row + 1 : 0) : nk;
     // PU of the wave's tokens per step: all their loads are issued before the first add; the adds keep the order t, t + 16, t + 32, ... so the result does
     // not depend on the unrolling
     constexpr int PU = NJ <= 4 ? 4 : 2;       // 16 waves per block: 128 registers per lane
@@ -452,7 +457,7 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __rest
             float s = part[i];
 #pragma unroll
             for (int w = 1; w < POOL_WAVES; ++w) s += part[w * HP + i];
-            v[j] = pool == KR_POOL_CLS ? s : s / (float)nk;   // nk == 0 -> 0/0 = NaN like average_pool (encoders.py:56-58)
+            v[j] = pool == KR_POOL_CLS ? s : pool == KR_POOL_LAST ? (nk > 0 ? s : NAN) : s / (float)nk;   // nk == 0 -> 0/0 = NaN like average_pool (encoders.py:56-58)
             ss += v[j] * v[j];
         }
     }

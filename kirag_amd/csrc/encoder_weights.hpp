@@ -317,7 +317,15 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
         const int li = slot < T_LAYER0 ? -1 : (slot - T_LAYER0) / L_COUNT, id = slot < T_LAYER0 ? -1 : (slot - T_LAYER0) % L_COUNT;
         if (slot == T_POS && !e->pos) KR_TRY(dmalloc(e->own_bufs, &e->pos, (size_t)numel * 4));
         if (id == L_IW || id == L_UW) KR_TRY(claim_w1(e->L[li], li));
-        if (float* dst = slot == T_WORD ? e->word : slot_f32(e, slot))
+        if (r.fam == DECODER && (id == L_QB || id == L_KB)) {
+            // a decoder's q / k bias (Qwen2): in the order of the projection's packed rows and, q's, with its fold — added before the rotation (EPI_QKV_ROTB),
+            // as ModernBert's attn.Wqkv.bias above
+            std::vector<float> b((size_t)numel), pb((size_t)numel);
+            KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
+            const bool h64 = H == 64 * e->cfg.heads;
+            for (int64_t i = 0; i < H; ++i) pb[(size_t)(h64 ? tile_pair_row(i, ROWS_HEAD64) : i)] = b[(size_t)i] * (id == L_QB ? qscale : 1.f);
+            KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
+        } else if (float* dst = slot == T_WORD ? e->word : slot_f32(e, slot))
             hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, e->stage, dst, numel, id == L_QB ? qscale : 1.f);
         else {
             LayerW& l = e->L[li];

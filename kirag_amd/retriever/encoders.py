@@ -50,6 +50,13 @@ bge-m3's token-level heads (``colbert_linear`` / ``sparse_linear`` on BERT / RoB
 make ``HipBertForward.forward`` / ``forward_np`` return ``(dense [B, H], sparse [B, S] or None, colbert [B, S, P] or None)``, three views into the one tensor
 the library wrote (``_layout``); the twins with the heads and the scoring on top of them live in ``kirag_amd.retriever.m3``.
 
+Decoder-LLM embedders (``model_type`` qwen2 / llama / mistral: the Qwen2.5-0.5B family such as KaLM-embedding-multilingual-mini, Llama-3.2-1B, TinyLlama,
+SmolLM2 fine-tunes): T5's schedule (pre-LN, RMS norms, the embedding row straight into the residual stream) with NomicBert's rotary q / k and SwiGLU, optional
+q / k / v biases, CAUSAL attention (``config.decoder_attention`` = 1) and mean or last-token pooling (``POOL_LAST``; ``pooling=`` kwarg, else the checkpoint's
+``1_Pooling/config.json``, else E5 -> mean, BGE -> last).  Grouped-query attention reaches the library expanded (``expand_kv``: each KV head's rows of
+``k_proj`` / ``v_proj`` repeated ``heads / kv_heads`` times, exact).  ``check_decoder_config`` refuses from ``config.json`` alone what the kernels do not
+compute (128-wide heads among it).
+
 SPLADE (``POOL_SPLADE`` on a BERT handle that was given ``cls.predictions.*``): the forward returns ``[B, vocab_size]``; the ``BertForMaskedLM`` twin and
 ``SpladeModel`` live in ``kirag_amd.retriever.splade``.
 """
@@ -63,7 +70,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import BertModel, DebertaV2Model, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, T5EncoderModel, XLMRobertaModel
+from transformers import (BertModel, DebertaV2Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, Qwen2Model,
+                          T5EncoderModel, XLMRobertaModel)
 
 from .. import _lib
 
@@ -76,6 +84,7 @@ MODERN_CLASSIFIER_OUT = "classifier.weight"      # ... and ModernBertForSequence
 POOL_WITH_SPARSE, POOL_WITH_COLBERT = 0x10, 0x20
 POOL_SPLADE = _lib.POOL_SPLADE  # KR_POOL_SPLADE: log1p(relu(MLM logits)) max-pooled over the attended tokens, [B, vocab_size] (kirag_amd.retriever.splade)
 POOL_M3_FLAGS = POOL_WITH_SPARSE | POOL_WITH_COLBERT
+POOL_LAST = _lib.POOL_LAST      # KR_POOL_LAST: the row of the highest attended column, normalised (decoder handles only)
 COLBERT_WEIGHT = "colbert_linear.weight"         # [P, hidden]: its rows are the width of a token vector
 COLBERT_MIN, COLBERT_MAX, COLBERT_STEP = 128, 2048, 128      # the library's rule for P (kirag_amd.h)
 
@@ -102,6 +111,12 @@ DEBERTA_TYPE = "deberta-v2"
 DEBERTA_SETTINGS = ("config.deberta_position_buckets", "config.deberta_max_relative_positions")
 DEBERTA_MAX_BUCKETS = 256                    # the library's bound on position_buckets: 512 rows of encoder.rel_embeddings
 DEBERTA_MAX_POS = 8192                       # ... and on max_position_embeddings of such a handle
+# decoder-LLM embedders: model_type -> the HF base model the twins are built over
+DECODER_BASES = {"qwen2": Qwen2Model, "llama": LlamaModel, "mistral": MistralModel}
+DECODER_SETTING = "config.decoder_attention"     # reserved name (include/kirag_amd.h): one float, 1 = causal, 0 = bidirectional on the same stack
+DECODER_MAX_POS = 8192                           # the rotary tables' limit: it only bounds the sequence length
+DECODER_POOLINGS = {"mean": POOL_MEAN, "last": _lib.POOL_LAST}
+ST_POOLING_DIR = "1_Pooling"
 ST_DENSE_TYPE = "sentence_transformers.models.Dense"
 ST_IDENTITY = "torch.nn.modules.linear.Identity"
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
@@ -201,8 +216,106 @@ def check_deberta_config(config, head: bool = False) -> dict:
     return {"buckets": Bk, "max_rel": M}
 
 
+def check_decoder_config(config) -> dict:
+    """``NotImplementedError`` beginning ``model_type='<type>':`` and naming the field, for everything of a Qwen2 / Llama / Mistral config the kernels do not
+    compute — from the config alone: no weight has been read and the library is not loaded.  ``config``: the HF config or the dict of a ``config.json`` (HF's
+    defaults fill the rest).  Returns what the handle is created with: hidden, layers, heads, kv_heads, intermediate, ``max_pos`` =
+    min(max_position_embeddings, 8192), ``ln_eps`` = rms_norm_eps, and ``inv_freq`` from HF's own rotary module (so static rope variants such as ``llama3`` are
+    covered)."""
+    if isinstance(config, dict):
+        from transformers import CONFIG_MAPPING
+        mt = config.get("model_type")
+        if mt not in DECODER_BASES:
+            raise NotImplementedError(f"model_type={mt!r}: the decoder path is built for {sorted(DECODER_BASES)}")
+        config = CONFIG_MAPPING[mt](**{k: v for k, v in config.items() if k not in ("model_type", "transformers_version", "architectures")})
+    mt = config.model_type
+
+    def refuse(msg):
+        raise NotImplementedError(f"model_type={mt!r}: {msg}")
+    if mt not in DECODER_BASES:
+        refuse(f"the decoder path is built for {sorted(DECODER_BASES)}")
+    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
+    kv = int(getattr(config, "num_key_value_heads", None) or heads)
+    if heads <= 0 or H % heads:
+        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
+    d_h = H // heads
+    head_dim = getattr(config, "head_dim", None) or d_h
+    if int(head_dim) != d_h:
+        refuse(f"head_dim={head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+    if d_h not in (32, 64):
+        refuse(f"head_dim={d_h} (hidden_size={H} / num_attention_heads={heads}): the attention kernels are built for heads of width 32 and 64")
+    if H % 128 or not 0 < H <= 2048:
+        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
+    if ff <= 0 or ff % 128:
+        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
+    if getattr(config, "hidden_act", "silu") != "silu":
+        refuse(f"hidden_act={config.hidden_act!r}: the gated MLP of a decoder handle implements silu only")
+    if kv <= 0 or heads % kv:
+        refuse(f"num_key_value_heads={kv} does not divide num_attention_heads={heads}")
+    if getattr(config, "attention_bias", False):
+        refuse("attention_bias=True: a bias on o_proj is not implemented (the q / k / v biases of Qwen2 are)")
+    if getattr(config, "mlp_bias", False):
+        refuse("mlp_bias=True: the MLP of a decoder handle has no bias")
+    max_pos = min(int(config.max_position_embeddings), DECODER_MAX_POS)
+    usw, sw = getattr(config, "use_sliding_window", None), getattr(config, "sliding_window", None)
+    if usw:
+        refuse(f"use_sliding_window=True (sliding_window={sw}): sliding-window causal layers are not implemented")
+    if usw is None and sw is not None and int(sw) < max_pos:
+        refuse(f"sliding_window={sw} is shorter than the {max_pos} tokens a sequence may have: sliding-window causal layers are not implemented")
+    types = list(getattr(config, "layer_types", None) or [])
+    if any(t != "full_attention" for t in types):
+        refuse(f"layer_types={types!r}: full_attention layers only")
+    rope = _decoder_rope(config)
+    if float(rope.attention_scaling) != 1.0:
+        refuse(f"attention_scaling={float(rope.attention_scaling)} (rope_type {getattr(rope, 'rope_type', None)!r}): only rope variants with attention_scaling 1.0 are implemented")
+    inv = rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    if inv.numel() != d_h // 2:
+        refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
+    return {"hidden": H, "layers": int(config.num_hidden_layers), "heads": heads, "kv_heads": kv, "intermediate": ff, "max_pos": max_pos,
+            "ln_eps": float(config.rms_norm_eps), "inv_freq": inv}
+
+
+def _decoder_rope(config):
+    """HF's own rotary module of the config's model type, built on the CPU"""
+    import importlib
+    mod = importlib.import_module(type(config).__module__.replace("configuration_", "modeling_"))
+    cls = next(getattr(mod, n) for n in dir(mod) if n.endswith("RotaryEmbedding"))
+    with torch.device("cpu"):       # from_pretrained builds models under the meta device: the frequencies are wanted as numbers
+        return cls(config)
+
+
+def expand_kv(name: str, w, heads: int, kv_heads: int):
+    """A ``k_proj`` / ``v_proj`` weight ``[kv_heads d_h, H]`` or bias ``[kv_heads d_h]`` of a grouped-query checkpoint as the ``[H, H]`` / ``[H]`` tensor the
+    library takes: every KV head's rows repeated ``heads / kv_heads`` times (``repeat_interleave`` over heads — query head h reads KV head h // group, as HF's
+    ``repeat_kv``).  Exact.  Every other tensor (and ``kv_heads == heads``) is returned as it is.  ``w``: torch tensor or numpy array."""
+    if kv_heads == heads or not any(name.endswith(f"self_attn.{p}_proj.{t}") for p in "kv" for t in ("weight", "bias")):
+        return w
+    is_np = not isinstance(w, Tensor)
+    t = torch.as_tensor(w)
+    d_h = t.shape[0] // kv_heads
+    out = t.reshape(kv_heads, d_h, *t.shape[1:]).repeat_interleave(heads // kv_heads, dim=0).reshape(heads * d_h, *t.shape[1:]).contiguous()
+    return out.numpy() if is_np else out
+
+
+def read_st_pooling(where, **kwargs) -> Optional[str]:
+    """"mean" / "last" from the sentence-transformers ``1_Pooling/config.json`` next to the checkpoint (``pooling_mode_mean_tokens`` /
+    ``pooling_mode_lasttoken``), ``None`` when there is no such file; any other mode, or more than one, is a ``NotImplementedError`` naming it."""
+    path = _st_file(where, f"{ST_POOLING_DIR}/config.json", kwargs)
+    if path is None:
+        return None
+    with open(path) as f:
+        pc = json.load(f)
+    on = sorted(k for k, v in pc.items() if k.startswith("pooling_mode_") and v is True)
+    known = {"pooling_mode_mean_tokens": "mean", "pooling_mode_lasttoken": "last"}
+    if len(on) != 1 or on[0] not in known:
+        raise NotImplementedError(f"{ST_POOLING_DIR}/config.json selects {on!r}: exactly one of {sorted(known)} is implemented for decoder checkpoints")
+    return known[on[0]]
+
+
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
+
+    DECODER_ATTENTION = 1.0          # what a decoder handle's "config.decoder_attention" is given: causal (0.0, bidirectional, exists in the library and its tests)
 
     def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None):
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
@@ -220,11 +333,14 @@ class HipBertForward:
         self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
         self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
         self.is_deberta = getattr(config, "model_type", "bert") in (DEBERTA_TYPE, "deberta")
+        self.is_decoder = getattr(config, "model_type", "bert") in DECODER_BASES
+        decoder = check_decoder_config(config) if self.is_decoder else None     # refuses what the kernels do not compute, before a handle exists
+        self.heads, self.kv_heads = (decoder["heads"], decoder["kv_heads"]) if decoder else (0, 0)
         deberta = check_deberta_config(config) if self.is_deberta else None     # refuses what the kernels do not compute, before a handle exists
         inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
         modern = self._modern_settings(config) if self.is_modern else None      # likewise
         t5 = self._t5_settings(config) if self.is_t5 else None                  # likewise
-        if not self.is_nomic and not self.is_modern and not self.is_t5 and getattr(config, "hidden_act", "gelu") != "gelu":
+        if not self.is_nomic and not self.is_modern and not self.is_t5 and not self.is_decoder and getattr(config, "hidden_act", "gelu") != "gelu":
             raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
         if getattr(config, "position_embedding_type", "absolute") != "absolute":
             raise NotImplementedError("only absolute position embeddings are implemented")
@@ -236,11 +352,14 @@ class HipBertForward:
         # ... and neither has ModernBERT; its intermediate size is rounded up to the projections' 128 (pad_modernbert_ff)
         # ... and T5 has neither token types nor positions: kr_bert_cfg comes from T5Config's own fields (_t5_settings)
         # ... and DeBERTa-v2 / v3 has neither token types nor a position table (both are optional on its handles)
-        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 or self.is_deberta else config.type_vocab_size
+        # ... and a decoder has neither; kr_bert_cfg comes from check_decoder_config (max_pos capped at the rotary tables' 8192)
+        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 or self.is_deberta or self.is_decoder else config.type_vocab_size
         self.ff = int(t5["intermediate"] if self.is_t5 else config.intermediate_size)
         self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
         if self.is_t5:
             cfg = _lib.BertCfg(t5["hidden"], t5["layers"], t5["heads"], self.ff, config.vocab_size, t5["max_pos"], type_vocab, t5["ln_eps"])
+        elif self.is_decoder:
+            cfg = _lib.BertCfg(decoder["hidden"], decoder["layers"], decoder["heads"], self.ff, config.vocab_size, decoder["max_pos"], type_vocab, decoder["ln_eps"])
         else:
             eps = float(config.norm_eps if self.is_modern else config.layer_norm_eps)
             cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff_pad,
@@ -274,6 +393,12 @@ class HipBertForward:
             for name, t in modern.items():
                 _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
 
+        # a decoder handle: HF's own frequencies, then the setting that makes it one (1 = causal)
+        if decoder is not None:
+            f = decoder["inv_freq"]
+            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", f.data_ptr(), f.numel()))
+            v = C.c_float(self.DECODER_ATTENTION)
+            _lib.check(lib.kr_encoder_load_weight(h, DECODER_SETTING.encode(), C.addressof(v), 1))
         # a DeBERTa handle: the two numbers of its bucket rule
         if deberta is not None:
             for name, val in zip(DEBERTA_SETTINGS, (deberta["buckets"], deberta["max_rel"])):
@@ -405,6 +530,8 @@ class HipBertForward:
             return
         for name, p in params:
             t = pad_modernbert_ff(name, p.detach(), self.ff, self.ff_pad)
+            if self.is_decoder:
+                t = expand_kv(name, t, self.heads, self.kv_heads)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
@@ -477,6 +604,8 @@ class HipBertForward:
             if self.rename is not None:
                 name = self.rename(name)
             w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
+            if self.is_decoder:
+                w = expand_kv(name, w, self.heads, self.kv_heads)
             if isinstance(w, np.ndarray):
                 w = np.ascontiguousarray(w, dtype=np.float32)
                 ptr, n = w.ctypes.data, w.size
@@ -661,7 +790,7 @@ class _HipSentenceMixin(_HipModuleMixin):
         return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel, DebertaV2Model) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT, T5 and DeBERTa-v3 have no token types
+        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel, DebertaV2Model) + tuple(DECODER_BASES.values()) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT, T5 and DeBERTa-v3 have no token types
         out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
@@ -669,7 +798,12 @@ class _HipSentenceMixin(_HipModuleMixin):
         if not self.training:
             return self._hip_forward(input_ids, attention_mask, token_type_ids)
         last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
-        embeddings = average_pool(last_hidden_states, attention_mask) if self._pool == POOL_MEAN else last_hidden_states[:, 0]
+        if self._pool == POOL_LAST:      # the row of the highest attended column
+            cols = torch.arange(attention_mask.shape[1], device=attention_mask.device)
+            last = ((attention_mask != 0) * (cols + 1)).argmax(dim=1)
+            embeddings = last_hidden_states[torch.arange(last_hidden_states.shape[0], device=last.device), last]
+        else:
+            embeddings = average_pool(last_hidden_states, attention_mask) if self._pool == POOL_MEAN else last_hidden_states[:, 0]
         if getattr(self, "dense", None) is not None:         # the sentence-transformers Dense head of a T5 checkpoint
             embeddings = self.dense(embeddings)
         embeddings = F.normalize(embeddings, p=2, dim=1)
@@ -698,6 +832,7 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _modern_twin = None              # ... and over ModernBertModel
     _t5_twin = None                  # ... and over T5EncoderModel
     _deberta_twin = None             # ... and over DebertaV2Model
+    _decoder_twin = None             # ... and over Qwen2Model / LlamaModel / MistralModel (DecoderE5Encoder / DecoderBGEEncoder pick the base)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -730,6 +865,9 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
             # disentangled attention under projection names of its own; what the kernels do not compute is refused from config.json alone
             check_deberta_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
             return cls._deberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type in DECODER_BASES:
+            # a causal pre-LN stack under names of its own; what the kernels do not compute is refused from config.json alone
+            return cls._decoder_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -877,6 +1015,101 @@ class _HipT5SentenceEncoder(_HipSentenceMixin, T5EncoderModel):
         return out
 
 
+class _HipDecoderSentenceMixin(_HipSentenceMixin):
+    """A decoder LLM used as an embedder: HF's own causal forward in ``train()`` mode, the library's in eval mode.  ``self._pool`` is the instance's pooling
+    (``POOL_MEAN`` / ``POOL_LAST``): the ``pooling`` kwarg of ``from_pretrained`` ("mean" / "last"), else the checkpoint's ``1_Pooling/config.json``, else the
+    class default (E5 -> mean, BGE -> last; the first token sees itself alone under a causal mask and is never chosen).  ``save_pretrained`` writes the pooling
+    back as a sentence-transformers ``1_Pooling/config.json`` + ``modules.json``, so a reload keeps it.  Appending an EOS token is the tokenizer's business."""
+
+    def __init__(self, config, add_pooling_layer=False, **kwargs):
+        check_decoder_config(config)                # refuses what the kernels do not compute when the model is made, not at its first forward
+        self._hf_base.__init__(self, config)        # these models have no pooling layer to ask for
+        self.kwargs = kwargs
+        self._hip = None
+
+    def set_pooling(self, pooling: str) -> None:
+        if pooling not in DECODER_POOLINGS:
+            raise ValueError(f"pooling={pooling!r}: one of {sorted(DECODER_POOLINGS)}")
+        self._pool = DECODER_POOLINGS[pooling]
+
+    @property
+    def pooling(self) -> str:
+        return {v: k for k, v in DECODER_POOLINGS.items()}[self._pool]
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        pooling = kwargs.pop("pooling", None)
+        if pooling is not None and pooling not in DECODER_POOLINGS:
+            raise ValueError(f"pooling={pooling!r}: one of {sorted(DECODER_POOLINGS)}")
+        config = kwargs.get("config")
+        if not isinstance(config, PretrainedConfig):
+            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
+            config, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
+        check_decoder_config(config)                # from config.json alone, before a weight is read
+        if pooling is None:
+            pooling = read_st_pooling(pretrained_model_name_or_path, **kwargs)
+        model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if pooling is not None:
+            model.set_pooling(pooling)
+        return model
+
+    def save_pretrained(self, save_directory, *args, **kwargs):
+        out = super().save_pretrained(save_directory, *args, **kwargs)
+        os.makedirs(os.path.join(save_directory, ST_POOLING_DIR), exist_ok=True)
+        pool = {"word_embedding_dimension": int(self.config.hidden_size), "pooling_mode_cls_token": False, "pooling_mode_mean_tokens": self._pool == POOL_MEAN,
+                "pooling_mode_max_tokens": False, "pooling_mode_mean_sqrt_len_tokens": False, "pooling_mode_weightedmean_tokens": False,
+                "pooling_mode_lasttoken": self._pool == POOL_LAST, "include_prompt": True}
+        with open(os.path.join(save_directory, ST_POOLING_DIR, "config.json"), "w") as f:
+            json.dump(pool, f, indent=2)
+        modules = [{"idx": 0, "name": "0", "path": "", "type": "sentence_transformers.models.Transformer"},
+                   {"idx": 1, "name": "1", "path": ST_POOLING_DIR, "type": "sentence_transformers.models.Pooling"},
+                   {"idx": 2, "name": "2", "path": "2_Normalize", "type": "sentence_transformers.models.Normalize"}]
+        with open(os.path.join(save_directory, "modules.json"), "w") as f:
+            json.dump(modules, f, indent=2)
+        return out
+
+
+def _decoder_twin(base, pool: int, doc: str):
+    name = base.__name__[:-len("Model")] + ("E5Encoder" if pool == POOL_MEAN else "BGEEncoder")
+    return type(name, (_HipDecoderSentenceMixin, base), {"_hf_base": base, "_pool": pool, "__doc__": doc, "__module__": __name__})
+
+
+Qwen2E5Encoder = _decoder_twin(Qwen2Model, POOL_MEAN, "Qwen2Model (causal) -> masked mean -> L2 normalise (the Qwen2.5-0.5B embedders: KaLM-embedding-multilingual-mini)")
+Qwen2BGEEncoder = _decoder_twin(Qwen2Model, POOL_LAST, "Qwen2Model (causal) -> last attended token -> L2 normalise")
+LlamaE5Encoder = _decoder_twin(LlamaModel, POOL_MEAN, "LlamaModel (causal) -> masked mean -> L2 normalise (Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes)")
+LlamaBGEEncoder = _decoder_twin(LlamaModel, POOL_LAST, "LlamaModel (causal) -> last attended token -> L2 normalise")
+MistralE5Encoder = _decoder_twin(MistralModel, POOL_MEAN, "MistralModel (causal, no sliding window) -> masked mean -> L2 normalise")
+MistralBGEEncoder = _decoder_twin(MistralModel, POOL_LAST, "MistralModel (causal, no sliding window) -> last attended token -> L2 normalise")
+
+
+class _DecoderDispatch:
+    """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral``); anything else is refused by name"""
+    _twins: dict = {}
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        config = kwargs.get("config")
+        if isinstance(config, PretrainedConfig):
+            model_type = config.model_type
+        else:
+            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
+            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
+            model_type = cfg_dict.get("model_type")
+        if model_type not in cls._twins:
+            raise NotImplementedError(f"model_type={model_type!r}: the decoder path is built for {sorted(cls._twins)}")
+        return cls._twins[model_type].from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+
+
+class DecoderE5Encoder(_DecoderDispatch):
+    """a decoder LLM (causal) -> masked mean -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``last``"""
+    _twins = {"qwen2": Qwen2E5Encoder, "llama": LlamaE5Encoder, "mistral": MistralE5Encoder}
+
+
+class DecoderBGEEncoder(_DecoderDispatch):
+    """a decoder LLM (causal) -> last attended token -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``mean``"""
+    _twins = {"qwen2": Qwen2BGEEncoder, "llama": LlamaBGEEncoder, "mistral": MistralBGEEncoder}
+
+
 class E5Encoder(_HipSentenceEncoder):
     """BertModel -> masked mean -> L2 normalise"""
     _pool = POOL_MEAN
@@ -959,6 +1192,8 @@ E5Encoder._t5_twin = T5E5Encoder
 BGEEncoder._t5_twin = T5BGEEncoder
 E5Encoder._deberta_twin = DebertaV2E5Encoder
 BGEEncoder._deberta_twin = DebertaV2BGEEncoder
+E5Encoder._decoder_twin = DecoderE5Encoder
+BGEEncoder._decoder_twin = DecoderBGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:

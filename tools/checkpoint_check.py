@@ -128,9 +128,20 @@ def reference_and_stats(model, batches, pool, dev):
                          ("x1", ff.layer_norm), ("y2", ff.DenseReluDense.wo)):
             hooks.append(mod.register_forward_hook(grab(li, key)))
         hooks.append(ff.DenseReluDense.wo.register_forward_pre_hook(lambda _m, inp, f=grab(li, "h"): f(_m, inp, inp[0])))
+    decoder = hasattr(model, "layers") and hasattr(model, "embed_tokens")      # Qwen2Model / LlamaModel / MistralModel: layers.N.{input_layernorm, self_attn, post_attention_layernorm, mlp}
+    for li, layer in enumerate(model.layers if decoder else ()):
+        # the residual stream ("LN1" / "LN2": what post_attention_layernorm reads, what the layer returns) is where a trained LLM carries its very large
+        # activations; 16-bit-stored: q, k, v (before the rotation, which keeps their size), the o_proj and down_proj outputs, both norm outputs, the gated product
+        att, mlp = layer.self_attn, layer.mlp
+        hooks.append(layer.post_attention_layernorm.register_forward_pre_hook(lambda _m, inp, f=grab(li, "ln1"): f(_m, inp, inp[0])))
+        hooks.append(layer.register_forward_hook(grab(li, "ln2")))
+        for key, mod in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("y1", att.o_proj), ("x0", layer.input_layernorm), ("x1", layer.post_attention_layernorm),
+                         ("y2", mlp.down_proj)):
+            hooks.append(mod.register_forward_hook(grab(li, key)))
+        hooks.append(mlp.down_proj.register_forward_pre_hook(lambda _m, inp, f=grab(li, "h"): f(_m, inp, inp[0])))
     nomic = hasattr(model, "layers")                   # NomicBertModel: layers.N.{self_attn, mlp, post_attention_layernorm, post_mlp_layernorm}
     modern = nomic and hasattr(model, "final_norm")    # ModernBertModel: layers.N.{attn_norm, attn, mlp_norm, mlp}
-    for li, layer in enumerate(() if t5 else model.layers if nomic else model.encoder.layer):
+    for li, layer in enumerate(() if t5 or decoder else model.layers if nomic else model.encoder.layer):
         if modern:
             # the residual stream itself (16-bit high half + low byte on the device) is what mlp_norm reads (behind the attention) and what the layer returns;
             # 16-bit-stored: q | k | v, the attention output projection, the LayerNorm outputs (the operands), the gated product, the MLP output
@@ -166,6 +177,10 @@ def reference_and_stats(model, batches, pool, dev):
             if pool == "mean":
                 m = torch.from_numpy(mask).to(dev)[..., None].bool()
                 e = out.masked_fill(~m, 0.0).sum(1) / m.sum(1)
+            elif pool == "last":       # the row of the highest attended column
+                mk = torch.from_numpy(mask).to(dev) != 0
+                last = (mk * (torch.arange(mk.shape[1], device=dev) + 1)).argmax(1)
+                e = out[torch.arange(out.shape[0], device=dev), last]
             else:
                 e = out[:, 0]
             if getattr(model, "dense", None) is not None:      # the sentence-transformers Dense head of a T5 checkpoint
@@ -187,7 +202,7 @@ def run_mode_hip(model, batches, pool, dtype, lo):
     from kirag_amd.retriever.encoders import HipBertForward
     h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo)
     h.sync(model)
-    return [h.forward_np(ids, mask, 1 if pool == "cls" else 0) for ids, mask in batches]
+    return [h.forward_np(ids, mask, {"mean": 0, "cls": 1, "last": 5}[pool]) for ids, mask in batches]
 
 
 def run_mode_emulated(model, batches, pool, dtype, lo, dev):
@@ -386,6 +401,14 @@ def check(hf_dir, args):
     if getattr(cfg, "model_type", "bert") == T5_TYPE:
         # the encoder half alone, as the twin of the pooling asked for: its from_pretrained also reads the folder's Dense head (modules.json)
         return check_model((T5E5Encoder if args.pool == "mean" else T5BGEEncoder).from_pretrained(hf_dir), args, hf_dir)
+    from kirag_amd.retriever.encoders import DECODER_BASES, DecoderBGEEncoder, DecoderE5Encoder
+    if getattr(cfg, "model_type", "bert") in DECODER_BASES:
+        # a decoder LLM used as an embedder: the twin of the pooling asked for (mean / last; "cls" is never right under a causal mask), reference = its HF base
+        # class in fp32 with eager attention under its own causal mask.  What the kernels do not compute (128-wide heads, ...) is refused from config.json
+        if args.pool == "cls":
+            raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} runs under a causal mask: --pool mean or --pool last")
+        twin = DecoderE5Encoder if args.pool == "mean" else DecoderBGEEncoder
+        return check_model(twin.from_pretrained(hf_dir, pooling=args.pool, attn_implementation="eager"), args, hf_dir)
     if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE, DEBERTA_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
                          f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3 and T5 encoders")
@@ -416,6 +439,9 @@ def check_model(model, args, hf_dir="(in-memory model)"):
     if getattr(cfg, "model_type", "bert") == T5_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms and a relative attention bias, which the torch emulation does not "
                          "implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") in ("qwen2", "llama", "mistral") and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a causal pre-LN stack with RMS norms, rotary positions and a gated MLP, which the torch emulation "
+                         "does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == DEBERTA_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has disentangled attention, which the torch emulation does not implement: run on the GPU")
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -469,7 +495,7 @@ def parse(argv=None):
     ap.add_argument("--texts", default=None)
     ap.add_argument("--n", type=int, default=32, help="sequences per side (queries / passages)")
     ap.add_argument("--max-length", type=int, default=128)
-    ap.add_argument("--pool", default="mean", choices=["mean", "cls"], help="mean = E5Encoder, cls = BGEEncoder")
+    ap.add_argument("--pool", default="mean", choices=["mean", "cls", "last"], help="mean = E5Encoder, cls = BGEEncoder, last = the last attended token (decoder checkpoints)")
     ap.add_argument("--emulate", action="store_true", help="torch emulation of the rounding points even when a GPU is present")
     ap.add_argument("--random-tokens", action="store_true")
     ap.add_argument("--seed", type=int, default=0)

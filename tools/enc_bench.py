@@ -53,7 +53,19 @@ T5_BASE_GATED = dict(T5_BASE, d_ff=2048, intermediate_size=2048, feed_forward_pr
 DEBERTA_V3_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, vocab_size=128100, max_position_embeddings=512,
                        type_vocab_size=0, layer_norm_eps=1e-7, hidden_act="gelu", model_type="deberta-v2", relative_attention=True, position_buckets=256,
                        max_relative_positions=-1, norm_rel_ebd="layer_norm", share_att_key=True, pos_att_type=["p2c", "c2p"], position_biased_input=False)
-SHAPES = dict(BS.ENCODER_SHAPES, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# Decoder-LLM embedders (causal attention, last-token or mean pooling): the Qwen2 / Qwen2.5-0.5B shape (KaLM-embedding-multilingual-mini: 14 heads of 64 over 2
+# KV heads, q / k / v biases) and Llama-3.2-1B's (32 heads of 64 over 8 KV heads, no bias).  The handle gets k_proj / v_proj expanded to [H, H] by the Python
+# layer (exact; + 9.2 % / + 10.3 % projection MACs).  --bidirectional: config.decoder_attention = 0 on the same stack — the A/B partner of the causal mask
+DECODER_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads", "intermediate_size", "vocab_size", "max_position_embeddings",
+                "rms_norm_eps", "hidden_act", "rope_parameters", "tie_word_embeddings")
+QWEN2_05B = dict(hidden_size=896, num_hidden_layers=24, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, vocab_size=151936,
+                 max_position_embeddings=32768, rms_norm_eps=1e-6, hidden_act="silu", rope_parameters={"rope_theta": 1000000.0, "rope_type": "default"},
+                 tie_word_embeddings=True, model_type="qwen2", type_vocab_size=1, layer_norm_eps=1e-6)
+LLAMA_1B = dict(hidden_size=2048, num_hidden_layers=16, num_attention_heads=32, num_key_value_heads=8, intermediate_size=8192, vocab_size=128256,
+                max_position_embeddings=131072, rms_norm_eps=1e-5, hidden_act="silu", tie_word_embeddings=True, model_type="llama", type_vocab_size=1, layer_norm_eps=1e-5,
+                rope_parameters={"rope_theta": 500000.0, "rope_type": "llama3", "factor": 32.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                                 "original_max_position_embeddings": 8192})
+SHAPES = dict(BS.ENCODER_SHAPES, **{"qwen2-0.5b": QWEN2_05B, "llama-1b": LLAMA_1B}, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -63,7 +75,9 @@ ap.add_argument("ragged", nargs="?", default="")
 ap.add_argument("--shape", action="append", choices=sorted(SHAPES))
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--hf-fp16", action="store_true")
-ap.add_argument("--pool", default="mean", choices=["mean", "cls"])
+ap.add_argument("--pool", default="mean", choices=["mean", "cls", "last"])
+ap.add_argument("--bidirectional", action="store_true", help="decoder shapes: config.decoder_attention = 0 (no causal mask) on the same stack")
+ap.add_argument("--alternate", action="store_true", help="decoder shapes: a causal and a bidirectional handle in this process, timed in turns (--reps rounds)")
 ap.add_argument("--first-forward", action="store_true")
 args = ap.parse_args() if __name__ == "__main__" else ap.parse_args([])      # imported (tools/one_shape.py): SHAPES and make_encoder only
 n, S, ragged = args.n, args.S, args.ragged == "ragged"
@@ -110,6 +124,9 @@ def make_encoder(cfg, extra_state=None):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw).  extra_state: tensors and settings that must
     arrive with the first load (a head: tools/rerank_bench.py), by library name"""
+    if cfg.get("model_type") in ("qwen2", "llama", "mistral"):
+        assert extra_state is None
+        return make_decoder(cfg, not args.bidirectional)
     if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2"):
         assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
@@ -193,6 +210,48 @@ def make_encoder(cfg, extra_state=None):
     return enc
 
 
+def make_decoder(cfg, causal=True):
+    """a decoder handle with synthetic weights under HF's names: the BERT-shaped draws renamed (no position table, no token types, the norms in their pre-LN
+    places, up_proj a second draw), k_proj / v_proj cut to the checkpoint's KV heads — the Python layer expands them again —, q / k / v biases for qwen2"""
+    from types import SimpleNamespace
+    import transformers as T
+    from kirag_amd.retriever.encoders import HipBertForward
+
+    class Handle(HipBertForward):
+        DECODER_ATTENTION = 1.0 if causal else 0.0
+    conf = {"qwen2": T.Qwen2Config, "llama": T.LlamaConfig, "mistral": T.MistralConfig}[cfg["model_type"]](**{k: cfg[k] for k in DECODER_KEYS})
+    enc = Handle(conf, 0)
+    ns = SimpleNamespace(**dict(cfg, max_position_embeddings=8))      # synthetic_state draws a position table of this many rows; it is dropped below
+    state = dict(BS.synthetic_state(ns, dev, 0))
+    g = torch.Generator(device=dev); g.manual_seed(977)
+    L, b, H = cfg["num_hidden_layers"], "encoder.layer.", cfg["hidden_size"]
+    kv_rows = H // cfg["num_attention_heads"] * cfg["num_key_value_heads"]
+    st = {"embed_tokens.weight": state["embeddings.word_embeddings.weight"], "norm.weight": state[f"{b}{L - 1}.output.LayerNorm.weight"]}
+    for l in range(L):
+        p = f"layers.{l}."
+        st[p + "input_layernorm.weight"] = state[f"{b}{l - 1}.output.LayerNorm.weight"] if l else state["embeddings.LayerNorm.weight"]
+        st[p + "post_attention_layernorm.weight"] = state[f"{b}{l}.attention.output.LayerNorm.weight"]
+        for nm, t, rows in (("query", "q", H), ("key", "k", kv_rows), ("value", "v", kv_rows)):
+            st[p + f"self_attn.{t}_proj.weight"] = state[f"{b}{l}.attention.self.{nm}.weight"][:rows].contiguous()
+            if cfg["model_type"] == "qwen2":
+                st[p + f"self_attn.{t}_proj.bias"] = state[f"{b}{l}.attention.self.{nm}.bias"][:rows].contiguous()
+        st[p + "self_attn.o_proj.weight"] = state[f"{b}{l}.attention.output.dense.weight"]
+        wi = state[f"{b}{l}.intermediate.dense.weight"]
+        st[p + "mlp.gate_proj.weight"] = wi
+        st[p + "mlp.up_proj.weight"] = 0.02 * torch.randn(wi.shape, generator=g, device=dev)
+        st[p + "mlp.down_proj.weight"] = state[f"{b}{l}.output.dense.weight"]
+    enc.load_state(st)
+    enc.cfg = SimpleNamespace(**cfg)
+    return enc
+
+
+def decoder_flops(cfg, lens, causal):
+    """8 H^2 (q, k, v, o with k / v expanded) + 6 H FF per token and layer, 4 s H of attention per token — half of it under the causal mask"""
+    lens = lens.double()
+    H, FF = cfg["hidden_size"], cfg["intermediate_size"]
+    return float((cfg["num_hidden_layers"] * lens * (8.0 * H * H + 6.0 * H * FF + (2.0 if causal else 4.0) * lens * H)).sum())
+
+
 def first_forward(shape, cfg, ids, mask):
     conf_cls, _, mod_cls = hf_classes(cfg)
     m = mod_cls(conf_cls(**{k: v for k, v in cfg.items() if k != "model_type" and (k != "hidden_act" or v != "gelu")}), add_pooling_layer=False).to(dev).eval()
@@ -210,7 +269,7 @@ def first_forward(shape, cfg, ids, mask):
           flush=True)
 
 
-pool = 0 if args.pool == "mean" else 1
+pool = {"mean": 0, "cls": 1, "last": 5}[args.pool]
 for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
     cfg = SHAPES[shape]
     ids, mask = BS.synthetic_tokens(dev, n, S, seed=1, ragged=ragged)
@@ -220,8 +279,24 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
         first_forward(shape, cfg, ids, mask)
         torch.cuda.empty_cache()
         continue
+    if cfg.get("model_type") in ("qwen2", "llama", "mistral") and args.alternate:
+        # one process, two handles of the same weights, timed in turns: what the causal mask saves is the difference
+        pair = {"causal": make_decoder(cfg, True), "bidirectional": make_decoder(cfg, False)}
+        times = {k: [] for k in pair}
+        for _ in range(args.reps):
+            for k, e in pair.items():
+                times[k].append(timed(lambda: e.forward(ids, mask, pool), 3) * 1e3)
+        for k in pair:
+            t = sorted(times[k])
+            print(f"{shape} {k} pool={args.pool} n={n} S={S} ragged={ragged}: median {t[len(t) // 2]:.2f} ms (min {t[0]:.2f}, max {t[-1]:.2f}, {len(t)} rounds of 3 in turns)  "
+                  f"{decoder_flops(cfg, mask.sum(1), k == 'causal') / (t[len(t) // 2] * 1e-3) / 1e12:.0f} TFLOP/s", flush=True)
+        del pair
+        torch.cuda.empty_cache()
+        continue
     enc = make_encoder(cfg)
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
+    if cfg.get("model_type") in ("qwen2", "llama", "mistral"):
+        fl = decoder_flops(cfg, mask.sum(1), not args.bidirectional)
     if cfg.get("model_type") == "nomic_bert":      # the third intermediate matrix: + 8 H^2 per token and layer (FF = 4 H)
         fl += float(mask.sum()) * cfg["num_hidden_layers"] * 8.0 * cfg["hidden_size"] ** 2
     if cfg.get("model_type") == "modernbert":      # FF is not 4 H: 8 H^2 (q, k, v, o) + 6 H FF (input, gate, out) per token and layer; the attention FLOPs are
