@@ -364,7 +364,15 @@ void kr_encoder_destroy(kr_encoder* enc);
  *     - the state dict loads unchanged, with or without a leading "model.": "embed_tokens.weight", "layers.N.input_layernorm.weight",
  *       "layers.N.self_attn.{q,k,v,o}_proj.weight" [hidden, hidden], "layers.N.post_attention_layernorm.weight", "layers.N.mlp.{gate,up,down}_proj.weight",
  *       "norm.weight", and optionally "layers.N.self_attn.{q,k,v}_proj.bias" (Qwen2; zero unless loaded; q's and k's are added before the rotation).  o_proj and
- *       the MLP have no bias.  Grouped-query checkpoints arrive EXPANDED: each KV head's rows of k_proj / v_proj repeated heads / kv_heads times (exact);
+ *       the MLP have no bias.  Grouped-query checkpoints load as they are: "layers.N.self_attn.{k,v}_proj.weight" may come as [A, hidden] and
+ *       "layers.N.self_attn.{k,v}_proj.bias" as [A], A = kv_heads * d_h, with kv_heads a divisor of heads and A % 64 == 0 (any other count is KR_EINVAL at
+ *       load).  kv_heads is read off the element count; k and v (and their biases) of every layer must agree (else KR_EINVAL at finalize, naming the
+ *       tensor), and A is fixed at the first finalize.  K and V^T then exist once per KV head and query head h reads KV head h / (heads / kv_heads).  The
+ *       EXPANDED form — each KV head's rows repeated heads / kv_heads times, [hidden, hidden] — is accepted as before and computes the same bits; the
+ *       expansion is no longer needed, except for a checkpoint whose A is no multiple of 64.  A grouped count on a handle without the setting is KR_EINVAL
+ *       at finalize.  k's rows sit in front of v's in the handle's packed matrix, so before the first finalize a k_proj or v_proj matrix that is loaded AGAIN
+ *       with another A than it had makes its partner count as never loaded (finalize then reports the partner by its weight slot): after correcting a
+ *       k / v mismatch, load both matrices of that layer again;
  *       any other name on the handle, a head's tensors included, is KR_EINVAL at finalize, and these names' decoder-only rows on another handle likewise;
  *     - the forwards take KR_POOL_MEAN and KR_POOL_LAST; KR_POOL_CLS / KR_POOL_CLASSIFY / KR_POOL_SPLADE are KR_EINVAL.
  *   "config.deberta_position_buckets" + "config.deberta_max_relative_positions": data = ONE float each, Bk (even, 2 .. 256) and M (M - 1 > Bk / 2):

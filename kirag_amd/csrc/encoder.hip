@@ -217,11 +217,12 @@ static int ensure_ws(Encoder* e, int B, int S) {
     if (p.ws & model::WS_ROW_SEQ) KR_TRY(dmalloc(e->ws_bufs, &e->row_seq, capT * 4));
     if (p.ws & model::WS_CY) KR_TRY(dmalloc(e->ws_bufs, &e->cy, capT * p.head_dim[model::HEAD_COLBERT] * 2));      // capT rows: the projection's tiles are whole (see k_proj)
     KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
-    KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * H * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
-    KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * H * 2));
+    const int64_t A = p.kv_dim;   // k [T, A] and V^T [A, ldv] exist once per KV head: A = H unless the handle is a grouped-query decoder's
+    KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * A * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
+    KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * A * 2));
     e->ldv = capT + 64;   // slack: the last key tile of the last sequence may read up to 43 columns past T
-    KR_TRY(dmalloc(e->ws_bufs, &e->vT, (size_t)H * e->ldv * 2));
-    KR_HIP(hipMemset(e->vT, 0, (size_t)H * e->ldv * 2));
+    KR_TRY(dmalloc(e->ws_bufs, &e->vT, (size_t)A * e->ldv * 2));
+    KR_HIP(hipMemset(e->vT, 0, (size_t)A * e->ldv * 2));
     KR_TRY(dmalloc(e->ws_bufs, &e->ctx, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->h, capT * FF * 2));
     if (p.pre_ln) {
         KR_TRY(dmalloc(e->ws_bufs, &e->rb, capT * H * 2));
@@ -290,7 +291,7 @@ static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W,
     const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
     const auto ba = attn_mode_args<AM>(e, p0, W);
     hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN, DIS>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
-                       e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, ba);
+                       e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, e->plan.kv_dim, attn_kv_mul(H / e->plan.kv_dim), ba);
     return 0;
 }
 
@@ -301,7 +302,7 @@ static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
     const auto ba = attn_mode_args<AM>(e, 0, 0);
     hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, attn_kernel_mode(AM) == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
-                       e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, ba);
+                       e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, e->plan.kv_dim, attn_kv_mul(e->cfg.hidden / e->plan.kv_dim), ba);
     return 0;
 }
 
@@ -555,8 +556,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         ProjArgs a{};
         a.Tp = e->d_T; a.H = H;
         a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
-        // q | k | v^T in one GEMM (F = 3H)
-        a.W = l.wqkv; a.X = e->xb; a.F = 3 * H; a.K = H; a.bias = l.bqkv; a.out0 = e->q; a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv; a.ldx = 0; a.ldo = 0;
+        // q | k | v^T in one GEMM (F = H + 2A: 3H unless k and v are a grouped-query decoder's)
+        a.A = p.kv_dim;
+        a.W = l.wqkv; a.X = e->xb; a.F = H + 2 * p.kv_dim; a.K = H; a.bias = l.bqkv; a.out0 = e->q; a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv; a.ldx = 0; a.ldo = 0;
         KR_TRY(launch_proj(QKV_EPI[lp.qkv], a, maxT, e, st));
         {
             const int cap = (int)round_up(S, 32);
@@ -564,6 +566,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
             auto go = [&](auto dh) -> int {
                 constexpr int DH = decltype(dh)::value;
                 if (am == AM_DISENT) {      // q . PK and k . PQ of every packed row, for the bias tiles of this layer's attention
+                    // (k_pos_scores reads k with q's pitch H and head h of both: a DeBERTa handle has one KV head per query head, describe() refuses any other)
+                    if (p.kv_dim != H) return fail(KR_ESTATE, "a DeBERTa handle with k / v width %d != hidden", p.kv_dim);
                     const dim3 grid((unsigned)((maxT + POS_ROWS - 1) / POS_ROWS), (unsigned)e->cfg.heads);
                     hipLaunchKernelGGL(k_pos_scores<DH>, grid, dim3(256), 0, st, e->q, e->k, e->d_T, H, e->cfg.heads, l.pk16, l.pq16, (int)round_up(2 * p.deb_buckets, 32), span_p0, span_W, e->pos_sc);
                     return launch_attention<DH, AM_DISENT>(e, B, cap, nqt_max, long_seq, span_p0, span_W, st);

@@ -441,11 +441,16 @@ __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os
 // put them in AGPRs and spent 112 of the 276 VALU instructions of a key tile on v_accvgpr_read / _write around the softmax rescale.  A 32-wide head
 // stages half the bytes (<= 25 KiB per block for any HPB, see launch_attn) and keeps half the Q fragments and accumulators: four blocks per CU (<= 128
 // registers).
+// Grouped-query attention: query head h reads KV head h / group, group = heads / kv_heads.  The kernels take the group as kv_mul = 65536 / group + 1
+// (attn_kv_mul, host): (h * kv_mul) >> 16 == h / group for every h < 1024 and group <= 64 (h (kv_mul group - 65536) < 65536) — a multiply and a shift where a
+// division by a kernel argument is a reciprocal sequence in every block of the short-sequence launches.  group = 1: kv_mul = 65537, the head itself.
+__host__ __device__ inline int attn_kv_mul(int group) { return 65536 / group + 1; }
+__device__ __forceinline__ int attn_kv_head(int head, int kv_mul) { return (int)(((unsigned)head * (unsigned)kv_mul) >> 16); }
 template <int DH> constexpr int attn_lds_blocks() { return DH == 64 ? 3 : 4; }
 template <int DH, int HPB, int BM>
 __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                              int H, int heads, int kchunk, uint16_t* __restrict__ ctx, const AttnModeArg<BM>& ba, char* smem) {
+                                              int H, int heads, int kchunk, uint16_t* __restrict__ ctx, int ldk, int kv_mul, const AttnModeArg<BM>& ba, char* smem) {
     constexpr bool WIN = BM >= 3 && BM <= 5;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; as a scalar, the head / q-tile / LDS bases derived from it cost no VGPRs
@@ -508,14 +513,16 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
                 uint4 kv[HPB][NB]; uint2 vv[HPB][NB];
 #pragma unroll
                 for (int h2 = 0; h2 < HPB; ++h2) {
-                    const int head2 = hb * HPB + h2;
+                    // K [T, ldk] and V^T [ldk, ldv] hold one head per KV head: query head h reads head h / group = attn_kv_head(h, kv_mul) (block-uniform: two
+                    // scalar instructions).  The heads of a block are staged one by one even where two of them share a KV head
+                    const int head2 = hb * HPB + h2, kvh = attn_kv_head(head2, kv_mul);
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
                         const int i = base + j * 256 + tid;
                         const int key = i >> NCS, ch = i & (NC - 1);
                         kv[h2][j] = make_uint4(0u, 0u, 0u, 0u);
                         if (head2 < heads && i < nkcs && key < nkc) {
-                            const uint16_t* kp = k + (off + kc0 + key) * H + head2 * DH + ch * 8;
+                            const uint16_t* kp = k + (off + kc0 + key) * ldk + kvh * DH + ch * 8;
                             kv[h2][j] = *reinterpret_cast<const uint4*>(kp);
                         }
                     }
@@ -525,14 +532,14 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
                 auto vsplit = [&](int i, int& d, int& kc) { d = (int)__umulhi((unsigned)i, cpr_magic); kc = i - d * cpr; };
 #pragma unroll
                 for (int h2 = 0; h2 < HPB; ++h2) {
-                    const int head2 = hb * HPB + h2;
+                    const int head2 = hb * HPB + h2, kvh = attn_kv_head(head2, kv_mul);
 #pragma unroll
                     for (int j = 0; j < NB; ++j) {
                         const int i = base + j * 256 + tid;
                         int vd, vk; vsplit(i, vd, vk);
                         vv[h2][j] = make_uint2(0u, 0u);
                         if (head2 < heads && i < nvc && vk * 4 < nkc) {
-                            const uint16_t* vp = vT + (int64_t)(head2 * DH + vd) * ldv + off + kc0 + vk * 4;   // off, kc0 % 4 == 0: 8-B aligned
+                            const uint16_t* vp = vT + (int64_t)(kvh * DH + vd) * ldv + off + kc0 + vk * 4;   // off, kc0 % 4 == 0: 8-B aligned
                             vv[h2][j] = uint2(*reinterpret_cast<const uint2*>(vp));
                         }
                     }
@@ -597,21 +604,21 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
 template <int DH, int HPB, bool BIAS = false, bool WIN = false, bool DIS = false>
 __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
-                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, AttnBiasArg<BIAS, WIN, DIS> ba) {
+                                                  int H, int heads, int kchunk, uint16_t* __restrict__ ctx, int ldk, int kv_mul, AttnBiasArg<BIAS, WIN, DIS> ba) {
     static_assert(!(BIAS && WIN) && !(DIS && (BIAS || WIN)), "a relative attention bias under a window is not instantiated, nor either next to the disentangled terms");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if constexpr (DIS) {
-        attn_lds_body<DH, HPB, 6>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        attn_lds_body<DH, HPB, 6>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     } else if constexpr (WIN) {
         const int b = blockIdx.y;
-        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 5>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
-        else attn_lds_body<DH, HPB, 3>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 5>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
+        else attn_lds_body<DH, HPB, 3>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     } else if constexpr (BIAS) {
         const int b = blockIdx.y;
-        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 2>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
-        else attn_lds_body<DH, HPB, 1>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<DH, HPB, 2>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
+        else attn_lds_body<DH, HPB, 1>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     } else {
-        attn_lds_body<DH, HPB, 0>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ba, smem);
+        attn_lds_body<DH, HPB, 0>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     }
 }
 
@@ -640,7 +647,8 @@ struct AdmaGeom {
 // marked as not aliasing it, which lets the compiler's waitcnt pass leave the COUNTED vmcnt waits alone; see coarse_q32_body in search.hip)
 template <int DH, int BM>
 __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
-                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, const AttnModeArg<BM>& ba) {
+                                              int64_t off, int nk, int nq, int H, int head, int qg, int64_t capT, uint16_t* __restrict__ ctx, char* smem, int ldk, int kv_mul,
+                                              const AttnModeArg<BM>& ba) {
     constexpr bool WIN = BM >= 3;      // (never 6: the disentangled terms are built into k_attn_lds only)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hf = lane >> 5;
@@ -663,21 +671,23 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
     // zero-extended 64-bit lane offsets, spilled them at the 256-register limit and reloaded them — s_waitcnt vmcnt(0) each — in front of the DMA of the
     // partial last chunk.)  Rows past the sequence (last chunk) are read and masked; the K buffer has 64 rows and V^T 64 columns of slack behind the last
     // token (ensure_ws), so nothing is out of range.
+    // K [T, ldk] / V^T [ldk, ldv] hold one head per KV head: query head `head` streams head / group (ldk = H, group = 1 on every handle but a grouped-query decoder's)
+    const int kvh = attn_kv_head(head, kv_mul);
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(k)) + (int64_t)head * 2 * DH + off * H * 2, 0, 0xffffffff, 0x00020000);
+        const_cast<char*>(reinterpret_cast<const char*>(k)) + (int64_t)kvh * 2 * DH + off * ldk * 2, 0, 0xffffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(vT)) + ((int64_t)head * DH) * ldv * 2 + off * 2, 0, 0xffffffff, 0x00020000);
+        const_cast<char*>(reinterpret_cast<const char*>(vT)) + ((int64_t)kvh * DH) * ldv * 2 + off * 2, 0, 0xffffffff, 0x00020000);
     uint32_t klane[ADMA_PIECES], vlane[ADMA_PIECES];
 #pragma unroll
     for (int pp = 0; pp < ADMA_PIECES; ++pp) {
         const int p = wave * ADMA_PIECES + pp;
         const int key = KROWS * p + (lane >> NCS), row = 8 * p + (lane >> 3);   // key inside the chunk / d row
-        klane[pp] = (uint32_t)(key * H * 2 + (((lane & (NC - 1)) ^ attn_kswz<DH>(key)) << 4));
+        klane[pp] = (uint32_t)(key * ldk * 2 + (((lane & (NC - 1)) ^ attn_kswz<DH>(key)) << 4));
         vlane[pp] = (uint32_t)((int64_t)row * ldv * 2 + (((lane & 7) ^ ((row >> 1) & 7)) << 4));   // < 2^32: DH rows x (tokens + 64) x 2 B, tokens <= 2^24 (ensure_ws)
     }
     auto issue = [&](int cidx) {
         char* stg = smem + (cidx % ADMA_RING) * ADMA_STAGE;
-        const int kc = cidx * 64 * H * 2, vc = cidx * 128;             // chunk offsets (bytes): 32 MiB / 16 KiB at 8192 tokens and H = 2048
+        const int kc = cidx * 64 * ldk * 2, vc = cidx * 128;             // chunk offsets (bytes): 32 MiB / 16 KiB at 8192 tokens and H = 2048
 #pragma unroll
         for (int pp = 0; pp < ADMA_PIECES; ++pp) {
             const int p = wave * ADMA_PIECES + pp;
@@ -787,7 +797,7 @@ __device__ __forceinline__ void attn_dma_body(const uint16_t* __restrict__ q, co
 template <int DH, bool BIAS = false, bool WIN = false>
 __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* __restrict__ seq_off,
                                                              const int* __restrict__ seq_nk, const int* __restrict__ seq_nq, int H, int64_t capT, uint16_t* ctx, int heads, int nseq, int qgroups,
-                                                             AttnBiasArg<BIAS, WIN> ba) {
+                                                             int ldk, int kv_mul, AttnBiasArg<BIAS, WIN> ba) {
     static_assert(!(BIAS && WIN), "a relative attention bias under a window is not instantiated");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // linear block id -> (pair p = b * heads + head, q-group qg).  Consecutive workgroups go to consecutive XCDs (id mod 8), and each XCD has its own L2:
@@ -803,13 +813,13 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
     const int nq = seq_nq[b];
     if (qg * ADMA_QT * 32 >= nq) return;                   // block-uniform (nq == 0 included)
     if constexpr (WIN) {
-        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 4>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
-        else attn_dma_body<DH, 3>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 4>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
+        else attn_dma_body<DH, 3>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
     } else if constexpr (BIAS) {
-        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 2>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
-        else attn_dma_body<DH, 1>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_dma_body<DH, 2>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
+        else attn_dma_body<DH, 1>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
     } else {
-        attn_dma_body<DH, 0>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ba);
+        attn_dma_body<DH, 0>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
     }
 }
 

@@ -43,7 +43,9 @@ inline Error err(int code, const char* fmt, ...) {
 //   of the column difference (deberta_bucket), PQ / PK the layer's own q / k projections of the (normalised) table encoder.rel_embeddings, scale 1 / sqrt(3 d_h).
 //   DECODER (config.decoder_attention, needs config.rotary_inv_freq; Qwen2Model / LlamaModel / MistralModel used as embedders): T5's schedule — pre-LN, RMS
 //   norms, the embedding row straight into the residual stream — with NOMIC's rotary q / k and SwiGLU under NOMIC's projection names, optional q / k / v biases
-//   (Qwen2), and with the setting's value 1 a causal mask: key column <= query column (AM_CAUSAL).  Grouped-query attention arrives expanded to [H, H].
+//   (Qwen2), and with the setting's value 1 a causal mask: key column <= query column (AM_CAUSAL).  Grouped-query attention is native: k_proj / v_proj (and their biases) come as
+//   [A, H] (/ [A]), A = kv_heads d_h with kv_heads dividing heads and A % 64 == 0 (kv_dim_ok), or expanded to [H, H]; A is read off the element count, k and v
+//   of every layer must agree (describe()), and query head h reads KV head h / (heads / kv_heads).
 enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA, DECODER };
 constexpr uint8_t GATED_NAME = 0x80;   // or-ed into a slot's family: the tensor came as one half of a gated projection under T5's names (wi_0 / wi_1)
 inline Family fam_of(uint8_t got) { return (Family)(got & 0x7f); }
@@ -417,12 +419,26 @@ inline int deberta_bucket(int r, int Bk, int M) {
 // what was loaded: per slot 0 = never, else the Family of the name it came under (| GATED_NAME); the family of the bias table's name; the heads
 struct Loaded {
     std::vector<uint8_t> got;
+    std::vector<int> kv;                   // per layer the rows A of k_proj.weight, v_proj.weight, k_proj.bias, v_proj.bias as loaded under the shared names (0: never)
+    int kv_seen = 0;                       // ... of the tensor check_tensor saw last (mark_loaded takes it over)
     Family rel_fam = FAM_NONE;
     int rel_rows = 0, rel_rows_seen = 0;   // rows of DeBERTa's position table as loaded (0: never); of the tensor check_tensor saw last (mark_loaded takes it over)
     bool rel_ln[2] = {false, false};       // encoder.LayerNorm.weight / .bias were loaded
     HeadState heads[HEAD_COUNT];
-    explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0) {}
+    explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0), kv((size_t)layers * 4, 0) {}
 };
+// The k / v projections under the names a decoder handle shares with NomicBert (self_attn.{k,v}_proj.weight) and their biases: which of the four a resolved
+// tensor is (-1: none).  They alone come in a grouped-query form.
+inline int kv_index(const Resolved& r) {
+    if (r.slot < T_LAYER0 || (r.fam != NOMIC && r.fam != DECODER)) return -1;
+    switch ((r.slot - T_LAYER0) % L_COUNT) { case L_KW: return 0; case L_VW: return 1; case L_KB: return 2; case L_VB: return 3; default: return -1; }
+}
+// A = kv_heads d_h rows: whole KV heads, their number a divisor of the query heads, and whole 64-column wave slices of the QKV epilogue (no wave straddles
+// q | k | v); A = H is the plain (or expanded) form
+inline bool kv_dim_ok(const kr_bert_cfg& c, int64_t A) {
+    const int64_t dh = c.hidden / c.heads;
+    return A > 0 && A <= c.hidden && A % dh == 0 && c.heads % (A / dh) == 0 && A % 64 == 0;
+}
 // A resolved tensor arriving with `numel` elements: its count.  The bias table [32, heads] (MPNet's name or T5's) has the rule of the heads: before the first
 // finalize it makes the handle an MPNet handle (a T5 handle needs it); afterwards a handle that has it takes new values (the weight sync reloads every
 // parameter) and a handle finalized without it refuses it.
@@ -449,6 +465,18 @@ inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolv
     if (r.slot == T_RELBIAS && numel != r.numel)
         return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (%d buckets x %d heads: MPNet always uses %d buckets, and so do the T5 handles)", name,
                    (long long)numel, (long long)r.numel, REL_BUCKETS, cfg.heads, REL_BUCKETS);
+    if (const int kvi = kv_index(r); kvi >= 0) {
+        // [A, H] / [A]: every valid A is taken here; whether the handle is one that takes A < H, and whether its tensors agree, is describe()'s business.
+        // After the first finalize A is what the handle has (all four kinds and all layers agree by then)
+        const int64_t cols = kvi < 2 ? cfg.hidden : 1, A = numel / cols;
+        if (numel % cols != 0 || !kv_dim_ok(cfg, A))
+            return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld, or the grouped-query form %s with A = kv_heads * %d, kv_heads a divisor of %d and A %% 64 == 0", name,
+                       (long long)numel, (long long)r.numel, kvi < 2 ? "[A, hidden]" : "[A]", cfg.hidden / cfg.heads, cfg.heads);
+        if (finalized_once && ld.kv[0] && A != ld.kv[0])
+            return err(KR_EINVAL, "'%s' with A = %lld rows after kr_encoder_finalize: the k / v width of the handle is fixed (it has A = %d)", name, (long long)A, ld.kv[0]);
+        ld.kv_seen = (int)A;
+        return Error{};
+    }
     if (numel != r.numel) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld", name, (long long)numel, (long long)r.numel);
     if (r.slot == T_RELBIAS && finalized_once && ld.rel_fam == FAM_NONE)
         return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without a relative attention bias and stays a BERT / RoBERTa handle", name);
@@ -466,6 +494,13 @@ inline void mark_loaded(Loaded& ld, const Resolved& r) {
     else if (r.slot == T_WI) g[L_IW] = g[L_UW] = tag;
     else if (r.slot == T_WIB) g[L_IB] = tag;
     else if (r.slot >= 0) ld.got[r.slot] = tag;
+    if (const int kvi = kv_index(r); kvi >= 0) {
+        // k's rows start at H and v's behind k's A rows of the packed matrix: a matrix that comes back with another A has overwritten, or moved away from,
+        // its partner, which therefore counts as never loaded
+        int& have = ld.kv[(size_t)r.layer * 4 + kvi];
+        if (kvi < 2 && have && have != ld.kv_seen) g[kvi == 0 ? L_VW : L_KW] = 0;
+        have = ld.kv_seen;
+    }
 }
 // the slots a family needs; every other one is optional and zero unless loaded (T5's wi_1: needed with the gated FF)
 struct FamilyRow { Family fam; bool pre_ln, rms; unsigned embed, layer; };
@@ -504,6 +539,7 @@ struct ModelPlan {
     int head_dim[HEAD_COUNT] = {};
     int classifier = -1;                   // the head KR_POOL_CLASSIFY runs (HEAD_CLS / HEAD_MODERN_CLS), -1: none
     bool classify_mean = false;            // ... on the masked mean (config.classifier_pooling = 1)
+    int kv_dim = 0;                        // A: columns of k and rows of V^T (hidden, or kv_heads d_h of a grouped-query decoder handle)
     int out_dim = 0, out_width = 0;        // columns of a pooled row; of the widest row `out` must hold, whatever the pool
     unsigned ws = 0;                       // WS_*
 };
@@ -549,6 +585,27 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
         for (size_t i = 0; i < ld.got.size(); ++i)
             if (fam_of(ld.got[i]) == DECODER)
                 return err(KR_EINVAL, "'%s' but config.decoder_attention was never loaded: load it before kr_encoder_finalize", slot_tensor_name(i, DECODER).c_str());
+    }
+    // the k / v width A: one per handle — k and v of a layer agree, the layers agree, the biases agree with the matrices; A < H on decoder handles only (the
+    // attention kernels of every other family read K / V^T of head h, not of head h / group)
+    int kv_dim = cfg.hidden;
+    {
+        static const int ids[4] = {L_KW, L_VW, L_KB, L_VB};
+        int first_l = -1, first_k = 0;
+        for (int li = 0; li < cfg.layers; ++li)
+            for (int x = 0; x < 4; ++x) {
+                const size_t slot = T_LAYER0 + (size_t)li * L_COUNT + ids[x];
+                const int A = ld.kv[(size_t)li * 4 + x];
+                if (!ld.got[slot] || !A) continue;
+                const std::string nm = slot_tensor_name(slot, fam_of(ld.got[slot]));
+                if (!dec && A != cfg.hidden)
+                    return err(KR_EINVAL, "'%s' with A = %d rows on a handle without config.decoder_attention: grouped-query k / v projections are accepted on decoder handles only "
+                                          "(load the setting before kr_encoder_finalize, or expand the tensor to %d rows)", nm.c_str(), A, cfg.hidden);
+                if (first_l < 0) { first_l = li; first_k = x; kv_dim = A; }
+                else if (A != kv_dim)
+                    return err(KR_EINVAL, "'%s' has A = %d rows but '%s' has %d: k_proj and v_proj (and their biases) of every layer of a handle share one width A", nm.c_str(), A,
+                               slot_tensor_name(T_LAYER0 + (size_t)first_l * L_COUNT + ids[first_k], fam_of(ld.got[T_LAYER0 + (size_t)first_l * L_COUNT + ids[first_k]])).c_str(), kv_dim);
+            }
     }
     if (deb) {
         if (!set.has(SET_DEB_BUCKETS) || !set.has(SET_DEB_MAX_REL))
@@ -666,6 +723,7 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot ? FF_SWIGLU : FF_GELU;
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;
+    plan.kv_dim = kv_dim;
     for (int h = 0; h < HEAD_COUNT; ++h) {
         plan.head[h] = ld.heads[h].got != 0;
         plan.head_dim[h] = ld.heads[h].dim;

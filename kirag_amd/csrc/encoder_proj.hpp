@@ -27,8 +27,9 @@ __device__ __forceinline__ void gemm_main(const uint16_t* __restrict__ A, int64_
 // ---------------------------------------------------------------------------------------------------------
 struct ProjArgs {
     const uint16_t* W; const uint16_t* X; const int* Tp; int F; int K; int H;
+    int A;   // the rotating QKV epilogues: columns of k and rows of V^T (F = H + 2A; A = H unless k / v are a grouped-query decoder's, A % 64 == 0)
     const float* bias;
-    uint16_t* out0; uint16_t* out1; uint16_t* outT; int64_t ldT;   // QKV: q, k row-major [T,H]; vT [H, ldT].  Others: out0 [T, F]
+    uint16_t* out0; uint16_t* out1; uint16_t* outT; int64_t ldT;   // QKV: q [T,H], k [T,A] row-major; vT [A, ldT].  Others: out0 [T, F]
     int64_t ldx, ldo;   // row pitch (elements) of X and of out0 (EPI_DENSE / EPI_GELU); 0 = K / F
     int pw;   // feature tiles per XCD patch of the tile walk (patch_coord)
     int epi_prio;   // A/B knob, see proj_epilogue
@@ -333,7 +334,8 @@ __device__ __forceinline__ void splade_reduce(const ProjArgs& a, AccTile<Shape>&
 //   EPI_GELU:  out0[T,F] = gelu(acc + bias)
 //   EPI_QKV_ROTB: EPI_QKV_ROT with the bias of q and k (in the rows' order, q's with the log2(e) / sqrt(d_h) fold) added BEFORE the rotation, as HF rotates
 //              Wqkv x + b (ModernBert handles that were given attn.Wqkv.bias)
-//   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV)
+//   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV).  Both rotating
+//              epilogues take F = H + 2A: [0,H) -> q, [H,H+A) -> k [T,A], [H+A,F) -> V^T [A,ldT] (A < H: a grouped-query decoder handle, one k / V^T per KV head)
 //   EPI_SWIGLU:  F = 2 FF, gate | up interleaved per tile: out0[T, F / 2] = silu(gate) * up, no bias (NomicBert handles)
 //   EPI_GEGLU:   F = 2 FF, input | gate interleaved the same way: out0[T, F / 2] = erf_gelu(input + b) * (gate + b') (ModernBert handles; bias in the rows' order)
 //   EPI_RELU:    out0[T,F] = max(acc, 0), no bias (T5 v1.0 handles: DenseReluDense.wi)
@@ -364,9 +366,10 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
                                     [&](f32x4 v, int mi, int ni, int g) { return v + b[ni][g]; });
         }
     } else if constexpr (epi_rotates(EPI)) {
-        const int region = f0 / a.H;
+        // F = H + 2A: q below H, k below H + A (stored with pitch A), V^T behind; H % 64 == 0 and A % 64 == 0, so a wave's columns never straddle them
+        const int region = f0 < a.H ? 0 : f0 < a.H + a.A ? 1 : 2;
         if (region == 2) {
-            store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - 2 * a.H);
+            store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - a.H - a.A);
         } else {
             // the rotation rides in store_rows_bf16's map: the table rows of ONE mi block are live at a time (requested at its first call; all of them up front
             // left the 256x256 tile's 128 accumulator registers no room), the token columns of all blocks are fetched before the first
@@ -375,7 +378,7 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             for (int mi = 0; mi < ShapeE::TM; ++mi) row[mi] = rot_row(a, t0 + mi * 32 + (acc.lane & 31)) + 4 * h;
             const int jb1 = rot_jbase(a.dh, f0 + 32);     // f0 % 64 == 0: tile ni = 0 starts at 0
             f32x4 cs[2][2], sn[2][2];
-            store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H, [&](f32x4 v, int mi, int ni, int g) {
+            store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, region ? a.A : a.H, t0, f0 - region * a.H, [&](f32x4 v, int mi, int ni, int g) {
                 if (ni == 0 && g == 0) {
                     if constexpr (EPI == EPI_QKV_ROTB) {
                         // the bias of this block's 64 features goes into its accumulators first, a quad at a time.  The offset is opaque per block: hoisted
@@ -506,7 +509,7 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
             return;
         }
         if constexpr (epi_rotates(EPI)) {
-            if ((int)f0 < 2 * a.H) {                      // q and k: (biased and) rotated in place, then stored like EPI_QKV's
+            if ((int)f0 < a.H + a.A) {                    // q and k: (biased and) rotated in place, then stored like EPI_QKV's
                 if constexpr (EPI == EPI_QKV_ROTB) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc.v[0][0][r] += bias4[r >> 2][r & 3];
@@ -520,15 +523,17 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
             f32x4 v = {acc.v[0][0][4 * g], acc.v[0][0][4 * g + 1], acc.v[0][0][4 * g + 2], acc.v[0][0][4 * g + 3]};
             const int f = (int)f0 + 8 * g + 4 * h;        // first of the lane's 4 consecutive features
             if constexpr (EPI == EPI_QKV || epi_rotates(EPI)) {
-                const int region = (int)f0 / a.H;
+                // EPI_QKV: thirds of 3H.  The rotating epilogues: q below H, k below H + A with pitch A, V^T behind (proj_epilogue)
+                const int kv = epi_rotates(EPI) ? a.A : a.H;
+                const int region = (int)f0 < a.H ? 0 : (int)f0 < a.H + kv ? 1 : 2;
                 if (region == 2) {                        // V^T [feature, token]; its bias lives in bo_eff
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) a.outT[(int64_t)(f - 2 * a.H + j) * a.ldT + t0 + c] = ET::from_f32(v[j]);
+                    for (int j = 0; j < 4; ++j) a.outT[(int64_t)(f - a.H - kv + j) * a.ldT + t0 + c] = ET::from_f32(v[j]);
                     continue;
                 }
                 if constexpr (EPI == EPI_QKV) v = v + bias4[g];
                 uint2 w; w.x = pack_bf16x2(v.x, v.y); w.y = pack_bf16x2(v.z, v.w);
-                *reinterpret_cast<uint2*>((region ? a.out1 : a.out0) + (t0 + c) * a.H + (f - region * a.H)) = w;
+                *reinterpret_cast<uint2*>((region ? a.out1 : a.out0) + (t0 + c) * (region ? kv : a.H) + (f - region * a.H)) = w;
             } else {
                 if constexpr (EPI == EPI_GELU) {
                     v = v + bias4[g];

@@ -322,9 +322,18 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             // as ModernBert's attn.Wqkv.bias above
             std::vector<float> b((size_t)numel), pb((size_t)numel);
             KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
+            // (k's comes with its own A = numel entries: whole 64-wide heads, so the row order applies per head as in the matrix)
             const bool h64 = H == 64 * e->cfg.heads;
-            for (int64_t i = 0; i < H; ++i) pb[(size_t)(h64 ? tile_pair_row(i, ROWS_HEAD64) : i)] = b[(size_t)i] * (id == L_QB ? qscale : 1.f);
+            for (int64_t i = 0; i < numel; ++i) pb[(size_t)(h64 ? tile_pair_row(i, ROWS_HEAD64) : i)] = b[(size_t)i] * (id == L_QB ? qscale : 1.f);
             KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
+        } else if (r.fam == DECODER && id == L_VB && numel != H) {
+            // a grouped-query value bias [A]: kept per QUERY head, [H], where the plain one lives — the QKV epilogue never reads it, k_fold_vbias folds
+            // Wo . bv into bo_eff over the context's H columns, and column c of the context is head c / d_h, which reads KV head (c / d_h) / group
+            const int64_t dh = H / e->cfg.heads, group = H / numel;
+            std::vector<float> b((size_t)numel), pb((size_t)H);
+            KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < H; ++i) pb[(size_t)i] = b[(size_t)((i / dh / group) * dh + i % dh)];
+            KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)H * 4, hipMemcpyHostToDevice));
         } else if (float* dst = slot == T_WORD ? e->word : slot_f32(e, slot))
             hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, e->stage, dst, numel, id == L_QB ? qscale : 1.f);
         else {
@@ -336,8 +345,10 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             }
             switch (id) {
                 case L_QW: to_bf16(l.wqkv, 0, numel, qscale, head64); break;
+                // the packed matrix is [H + 2A, H]: q's rows, k's from row H, v's from row H + A, A = numel / H the tensor's own row count (H unless it is a
+                // grouped-query decoder's: describe() holds k's against v's) — so the load order stays free
                 case L_KW: to_bf16(l.wqkv + H * H, 0, numel, 1.f, head64); break;
-                case L_VW: to_bf16(l.wqkv + 2 * H * H, 0, numel, 1.f, -1); break;
+                case L_VW: to_bf16(l.wqkv + H * H + numel, 0, numel, 1.f, -1); break;
                 case L_OW: to_bf16(l.wo, 0, numel, 1.f, -1); break;
                 case L_IW: to_bf16(l.w1, 0, numel, 1.f, gated ? (int)ROWS_GATE : -1); break;
                 case L_UW: to_bf16(l.w1, 0, numel, 1.f, ROWS_UP); break;

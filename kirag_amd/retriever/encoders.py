@@ -53,8 +53,9 @@ the library wrote (``_layout``); the twins with the heads and the scoring on top
 Decoder-LLM embedders (``model_type`` qwen2 / llama / mistral: the Qwen2.5-0.5B family such as KaLM-embedding-multilingual-mini, Llama-3.2-1B, TinyLlama,
 SmolLM2 fine-tunes): T5's schedule (pre-LN, RMS norms, the embedding row straight into the residual stream) with NomicBert's rotary q / k and SwiGLU, optional
 q / k / v biases, CAUSAL attention (``config.decoder_attention`` = 1) and mean or last-token pooling (``POOL_LAST``; ``pooling=`` kwarg, else the checkpoint's
-``1_Pooling/config.json``, else E5 -> mean, BGE -> last).  Grouped-query attention reaches the library expanded (``expand_kv``: each KV head's rows of
-``k_proj`` / ``v_proj`` repeated ``heads / kv_heads`` times, exact).  ``check_decoder_config`` refuses from ``config.json`` alone what the kernels do not
+``1_Pooling/config.json``, else E5 -> mean, BGE -> last).  Grouped-query ``k_proj`` / ``v_proj`` tensors reach the library with their HF shapes
+(``[kv_heads d_h, H]``: the kernels read KV head ``h // group``) whenever ``kv_heads d_h`` is a multiple of 64; any other checkpoint is expanded first
+(``expand_kv``: each KV head's rows repeated ``heads / kv_heads`` times, exact).  ``check_decoder_config`` refuses from ``config.json`` alone what the kernels do not
 compute (128-wide heads among it).
 
 SPLADE (``POOL_SPLADE`` on a BERT handle that was given ``cls.predictions.*``): the forward returns ``[B, vocab_size]``; the ``BertForMaskedLM`` twin and
@@ -297,6 +298,19 @@ def expand_kv(name: str, w, heads: int, kv_heads: int):
     return out.numpy() if is_np else out
 
 
+KV_NATIVE_MULTIPLE = 64     # the library takes [A, H] k / v projections with A = kv_heads d_h a multiple of the QKV epilogue's 64-column wave slice
+
+
+def kv_for_library(name: str, w, heads: int, kv_heads: int, hidden: int):
+    """A decoder checkpoint's tensor as the weight sync sends it: unchanged — grouped-query ``k_proj`` / ``v_proj`` tensors included — when the library
+    takes ``A = kv_heads d_h`` natively (``A % 64 == 0``), else with the KV heads expanded (``expand_kv``; e.g. 4 heads of 32 over 1 KV head: A = 32).  A tensor
+    that already has ``hidden`` rows (a caller who expanded it) passes as it is."""
+    A = kv_heads * (hidden // heads)
+    if A % KV_NATIVE_MULTIPLE == 0 or w.shape[0] != A:
+        return w
+    return expand_kv(name, w, heads, kv_heads)
+
+
 def read_st_pooling(where, **kwargs) -> Optional[str]:
     """"mean" / "last" from the sentence-transformers ``1_Pooling/config.json`` next to the checkpoint (``pooling_mode_mean_tokens`` /
     ``pooling_mode_lasttoken``), ``None`` when there is no such file; any other mode, or more than one, is a ``NotImplementedError`` naming it."""
@@ -531,7 +545,7 @@ class HipBertForward:
         for name, p in params:
             t = pad_modernbert_ff(name, p.detach(), self.ff, self.ff_pad)
             if self.is_decoder:
-                t = expand_kv(name, t, self.heads, self.kv_heads)
+                t = kv_for_library(name, t, self.heads, self.kv_heads, self.hidden)
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
@@ -605,7 +619,7 @@ class HipBertForward:
                 name = self.rename(name)
             w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
             if self.is_decoder:
-                w = expand_kv(name, w, self.heads, self.kv_heads)
+                w = kv_for_library(name, w, self.heads, self.kv_heads, self.hidden)
             if isinstance(w, np.ndarray):
                 w = np.ascontiguousarray(w, dtype=np.float32)
                 ptr, n = w.ctypes.data, w.size

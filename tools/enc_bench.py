@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
-    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated|deberta-v3-base ...] [--pool mean|cls] [--hf-fp16]
+    python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated|deberta-v3-base ...] [--pool mean|cls] [--hf-fp16] [--expanded | --alternate-gqa (decoder shapes)]
                               [--first-forward]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
@@ -54,8 +54,10 @@ DEBERTA_V3_BASE = dict(hidden_size=768, num_hidden_layers=12, num_attention_head
                        type_vocab_size=0, layer_norm_eps=1e-7, hidden_act="gelu", model_type="deberta-v2", relative_attention=True, position_buckets=256,
                        max_relative_positions=-1, norm_rel_ebd="layer_norm", share_att_key=True, pos_att_type=["p2c", "c2p"], position_biased_input=False)
 # Decoder-LLM embedders (causal attention, last-token or mean pooling): the Qwen2 / Qwen2.5-0.5B shape (KaLM-embedding-multilingual-mini: 14 heads of 64 over 2
-# KV heads, q / k / v biases) and Llama-3.2-1B's (32 heads of 64 over 8 KV heads, no bias).  The handle gets k_proj / v_proj expanded to [H, H] by the Python
-# layer (exact; + 9.2 % / + 10.3 % projection MACs).  --bidirectional: config.decoder_attention = 0 on the same stack — the A/B partner of the causal mask
+# KV heads, q / k / v biases) and Llama-3.2-1B's (32 heads of 64 over 8 KV heads, no bias).  The handle gets k_proj / v_proj with the checkpoint's KV heads
+# ([A, H]: native grouped-query attention); --expanded builds it from the [H, H] tensors of expand_kv instead (the same bits; + 9.2 % / + 10.3 % projection MACs
+# by the shapes), --alternate-gqa times one handle of each kind in turns in this process.  --bidirectional: config.decoder_attention = 0 on the same stack —
+# the A/B partner of the causal mask
 DECODER_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads", "intermediate_size", "vocab_size", "max_position_embeddings",
                 "rms_norm_eps", "hidden_act", "rope_parameters", "tie_word_embeddings")
 QWEN2_05B = dict(hidden_size=896, num_hidden_layers=24, num_attention_heads=14, num_key_value_heads=2, intermediate_size=4864, vocab_size=151936,
@@ -78,6 +80,8 @@ ap.add_argument("--hf-fp16", action="store_true")
 ap.add_argument("--pool", default="mean", choices=["mean", "cls", "last"])
 ap.add_argument("--bidirectional", action="store_true", help="decoder shapes: config.decoder_attention = 0 (no causal mask) on the same stack")
 ap.add_argument("--alternate", action="store_true", help="decoder shapes: a causal and a bidirectional handle in this process, timed in turns (--reps rounds)")
+ap.add_argument("--expanded", action="store_true", help="decoder shapes: build the handle from k_proj / v_proj expanded to [H, H] (expand_kv) instead of the grouped tensors")
+ap.add_argument("--alternate-gqa", action="store_true", help="decoder shapes: a native and an expanded handle of the same weights in this process, timed in turns (--reps rounds)")
 ap.add_argument("--first-forward", action="store_true")
 args = ap.parse_args() if __name__ == "__main__" else ap.parse_args([])      # imported (tools/one_shape.py): SHAPES and make_encoder only
 n, S, ragged = args.n, args.S, args.ragged == "ragged"
@@ -126,7 +130,7 @@ def make_encoder(cfg, extra_state=None):
     arrive with the first load (a head: tools/rerank_bench.py), by library name"""
     if cfg.get("model_type") in ("qwen2", "llama", "mistral"):
         assert extra_state is None
-        return make_decoder(cfg, not args.bidirectional)
+        return make_decoder(cfg, not args.bidirectional, args.expanded)
     if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2"):
         assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
@@ -210,12 +214,13 @@ def make_encoder(cfg, extra_state=None):
     return enc
 
 
-def make_decoder(cfg, causal=True):
+def make_decoder(cfg, causal=True, expanded=False):
     """a decoder handle with synthetic weights under HF's names: the BERT-shaped draws renamed (no position table, no token types, the norms in their pre-LN
-    places, up_proj a second draw), k_proj / v_proj cut to the checkpoint's KV heads — the Python layer expands them again —, q / k / v biases for qwen2"""
+    places, up_proj a second draw), k_proj / v_proj cut to the checkpoint's KV heads — loaded as they are, or with `expanded` repeated per query head first
+    (expand_kv) —, q / k / v biases for qwen2"""
     from types import SimpleNamespace
     import transformers as T
-    from kirag_amd.retriever.encoders import HipBertForward
+    from kirag_amd.retriever.encoders import HipBertForward, expand_kv
 
     class Handle(HipBertForward):
         DECODER_ATTENTION = 1.0 if causal else 0.0
@@ -240,6 +245,8 @@ def make_decoder(cfg, causal=True):
         st[p + "mlp.gate_proj.weight"] = wi
         st[p + "mlp.up_proj.weight"] = 0.02 * torch.randn(wi.shape, generator=g, device=dev)
         st[p + "mlp.down_proj.weight"] = state[f"{b}{l}.output.dense.weight"]
+    if expanded:
+        st = {k: expand_kv(k, v, cfg["num_attention_heads"], cfg["num_key_value_heads"]) for k, v in st.items()}
     enc.load_state(st)
     enc.cfg = SimpleNamespace(**cfg)
     return enc
@@ -291,6 +298,22 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
             print(f"{shape} {k} pool={args.pool} n={n} S={S} ragged={ragged}: median {t[len(t) // 2]:.2f} ms (min {t[0]:.2f}, max {t[-1]:.2f}, {len(t)} rounds of 3 in turns)  "
                   f"{decoder_flops(cfg, mask.sum(1), k == 'causal') / (t[len(t) // 2] * 1e-3) / 1e12:.0f} TFLOP/s", flush=True)
         del pair
+        torch.cuda.empty_cache()
+        continue
+    if cfg.get("model_type") in ("qwen2", "llama", "mistral") and args.alternate_gqa:
+        # one process, two handles of the same weights, timed in turns: what the grouped k / v columns save is the difference; the outputs must be the same bits
+        pair = {"native": make_decoder(cfg, not args.bidirectional, False), "expanded": make_decoder(cfg, not args.bidirectional, True)}
+        outs = {k: e.forward(ids, mask, pool).clone() for k, e in pair.items()}
+        same = bool(torch.equal(outs["native"].view(torch.int32), outs["expanded"].view(torch.int32)))
+        times = {k: [] for k in pair}
+        for _ in range(args.reps):
+            for k, e in pair.items():
+                times[k].append(timed(lambda: e.forward(ids, mask, pool), 3) * 1e3)
+        for k in pair:
+            t = sorted(times[k])
+            print(f"{shape} {k} pool={args.pool} n={n} S={S} ragged={ragged}: median {t[len(t) // 2]:.3f} ms (min {t[0]:.3f}, max {t[-1]:.3f}, {len(t)} rounds of 3 in turns)  "
+                  f"outputs bit-identical: {same}", flush=True)
+        del pair, outs
         torch.cuda.empty_cache()
         continue
     enc = make_encoder(cfg)
