@@ -350,6 +350,14 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   out [B, P] = normalize(W . pooled) instead of [B, hidden] (the caller knows P from the tensor it loaded); an all-masked sequence still gives a NaN row.
  *   Like the settings it is fixed at the first finalize: later the same P takes new values, another P — or the tensor on a handle finalized without it — is
  *   KR_EINVAL.  kr_encoder_last_hidden is not affected (it stays [B, S, hidden]).
+ *   "config.rotary_feed_forward": data = ONE float, the feed-forward of a handle with "config.rotary_inv_freq": 0 = NomicBert's SwiGLU (also when never
+ *   loaded), 1 = fc2 . gelu(fc1 . x + b1) + b2 with linear biases — a rotary BERT handle (transformers JinaEmbeddingsV3Model: jina-embeddings-v3); anything
+ *   else is KR_EINVAL, and the usual rule of the settings holds.  The value 1 needs "config.rotary_inv_freq" and is refused at finalize (KR_EINVAL) next to
+ *   every other position scheme and next to "config.decoder_attention".  Such a handle is NomicBert's post-LN stack (word + token-type embedding rows ->
+ *   LayerNorm, no position table, q and k rotated) with "layers.N.self_attn.{q,k,v,o}_proj.{weight,bias}", "layers.N.post_attention_layernorm.{weight,bias}",
+ *   "layers.N.mlp.{fc1,fc2}.{weight,bias}" and "layers.N.post_mlp_layernorm.{weight,bias}": every bias is zero unless loaded, q's and k's are added before
+ *   the rotation; "mlp.gate_proj" / "mlp.up_proj" there, "mlp.fc1" / "mlp.fc2" / "self_attn.o_proj.bias" on any other handle, and grouped-query k / v
+ *   tensors are KR_EINVAL at finalize, naming the tensor.
  *   "config.decoder_attention": data = ONE float, 1 = causal attention, 0 = bidirectional attention on the same stack; anything else is KR_EINVAL.  Loading it
  *   before the handle's first finalize makes the handle a DECODER handle for life (transformers Qwen2Model / LlamaModel / MistralModel used as embedders:
  *   the Qwen2.5-0.5B family such as KaLM-embedding-multilingual-mini, Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes); the usual rule of the settings holds.  It

@@ -1,4 +1,4 @@
-// What an encoder handle IS, decided in one place and without a device: the state-dict names of the seven model families, the heads, the settings, and
+// What an encoder handle IS, decided in one place and without a device: the state-dict names of the eight model families, the heads, the settings, and
 // describe(), which turns what was loaded into a ModelPlan (or the refusal kr_encoder_finalize returns).  Host-only: nothing here includes HIP, so the
 // tables are tested by a stand-alone program (tests/capi/encoder_model_check.cpp).  The device side of every row lives in encoder_weights.hpp (where a
 // slot is stored) and encoder.hip (enqueue_forward: which launches a plan selects).  Adding a family or a head: DESIGN.md, "Adding a family / a head".
@@ -46,10 +46,13 @@ inline Error err(int code, const char* fmt, ...) {
 //   (Qwen2), and with the setting's value 1 a causal mask: key column <= query column (AM_CAUSAL).  Grouped-query attention is native: k_proj / v_proj (and their biases) come as
 //   [A, H] (/ [A]), A = kv_heads d_h with kv_heads dividing heads and A % 64 == 0 (kv_dim_ok), or expanded to [H, H]; A is read off the element count, k and v
 //   of every layer must agree (describe()), and query head h reads KV head h / (heads / kv_heads).
-enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA, DECODER };
+//   ROTARY_BERT (config.rotary_feed_forward = 1, needs config.rotary_inv_freq; JinaEmbeddingsV3Model): NOMIC's post-LN stack and rotary q / k under NOMIC's
+//   projection names, with BERT's feed-forward fc2(gelu(fc1 x + b1)) + b2 in place of SwiGLU (mlp.fc1 in PLAIN row order) and optional biases on q / k / v
+//   (the decoders' rows: q's and k's in the packed rows' order, added before the rotation) and o.
+enum Family : uint8_t { FAM_NONE = 0, BERT, MPNET, NOMIC, MODERN, T5, DEBERTA, DECODER, ROTARY_BERT };
 constexpr uint8_t GATED_NAME = 0x80;   // or-ed into a slot's family: the tensor came as one half of a gated projection under T5's names (wi_0 / wi_1)
 inline Family fam_of(uint8_t got) { return (Family)(got & 0x7f); }
-inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5", "DeBERTa-v2", "decoder"}; return n[f]; }
+inline const char* family_name(Family f) { static const char* const n[] = {"unknown", "BERT / RoBERTa", "MPNet", "NomicBert", "ModernBert", "T5", "DeBERTa-v2", "decoder", "rotary BERT (jina-embeddings-v3)"}; return n[f]; }
 
 // tensor slots: 0..4 embeddings, then L_COUNT per layer (L_UW: the second half of a gated intermediate projection); below zero what is no slot of `got`
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
@@ -121,6 +124,10 @@ static const NameRow NAME_ROWS[] = {
     {"mlp.Wi.bias", LAYER, MODERN, T_WIB, X2FF, X1, 0}, {"attn.Wo.weight", LAYER, MODERN, L_OW, XH, XH, 0}, {"attn.Wo.bias", LAYER, MODERN, L_OB, XH, X1, 0},
     {"mlp_norm.weight", LAYER, MODERN, L_LN1G, XH, X1, 0}, {"mlp_norm.bias", LAYER, MODERN, L_LN1B, XH, X1, 0}, {"mlp.Wo.weight", LAYER, MODERN, L_FW, XH, XFF, 0},
     {"mlp.Wo.bias", LAYER, MODERN, L_FB, XH, X1, 0}, {"attn_norm.weight", LAYER, MODERN, L_LN2G, XH, X1, NORM_BEFORE}, {"attn_norm.bias", LAYER, MODERN, L_LN2B, XH, X1, NORM_BEFORE},
+    // JinaEmbeddingsV3Model: the projections and norms under NomicBert's rows below, the q / k / v biases under the decoders' rows above; fc1 is stored in plain
+    // row order (EPI_GELU), not in the gate / up pairing
+    {"self_attn.o_proj.bias", LAYER, ROTARY_BERT, L_OB, XH, X1, 0}, {"mlp.fc1.weight", LAYER, ROTARY_BERT, L_IW, XFF, XH, 0}, {"mlp.fc1.bias", LAYER, ROTARY_BERT, L_IB, XFF, X1, 0},
+    {"mlp.fc2.weight", LAYER, ROTARY_BERT, L_FW, XH, XFF, 0}, {"mlp.fc2.bias", LAYER, ROTARY_BERT, L_FB, XH, X1, 0},
     // NomicBertModel
     {"self_attn.q_proj.weight", LAYER, NOMIC, L_QW, XH, XH, 0}, {"self_attn.k_proj.weight", LAYER, NOMIC, L_KW, XH, XH, 0}, {"self_attn.v_proj.weight", LAYER, NOMIC, L_VW, XH, XH, 0},
     {"self_attn.o_proj.weight", LAYER, NOMIC, L_OW, XH, XH, 0}, {"post_attention_layernorm.weight", LAYER, NOMIC, L_LN1G, XH, X1, 0},
@@ -144,7 +151,7 @@ static const NameRow NAME_ROWS[] = {
 };
 
 // the rows a layer prefix leads to: 0 = BERT's and MPNet's, 1 = NomicBert's and ModernBert's, 2 = T5's
-inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN || f == DECODER ? 1 : 0; }      // (DeBERTa's layers are "encoder.layer.N.": group 0)
+inline int prefix_group(Family f) { return f == T5 ? 2 : f == NOMIC || f == MODERN || f == DECODER || f == ROTARY_BERT ? 1 : 0; }      // (DeBERTa's layers are "encoder.layer.N.": group 0)
 // the layer prefix of `s`, T5's only or the other two: its group and where the layer index starts, or -1
 inline int layer_prefix(const std::string& s, bool t5, size_t& at) {
     if (t5) {
@@ -317,7 +324,9 @@ inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_
 //   config.deberta_position_buckets = Bk (even, 2 .. 256) and config.deberta_max_relative_positions = M (M - 1 > Bk / 2): DebertaV2Config's position_buckets and
 //   max_relative_positions (max_position_embeddings where that is < 1); the two together make the handle a DeBERTa handle.
 //   config.decoder_attention: the handle is a decoder-LLM stack (needs config.rotary_inv_freq); 1 = causal attention, 0 = bidirectional on the same stack.
-enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_DECODER_ATTN, SET_COUNT };
+//   config.rotary_feed_forward: the feed-forward of a rotary post-LN handle (config.rotary_inv_freq), 0 = NomicBert's SwiGLU (also when never set),
+//   1 = fc2(gelu(fc1 x + b1)) + b2 with linear biases: a rotary BERT handle (jina-embeddings-v3).
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_ROTARY_FF, SET_DECODER_ATTN, SET_COUNT };
 enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
 struct SettingRow {
     const char* name;
@@ -341,6 +350,7 @@ static const SettingRow SETTINGS[SET_COUNT] = {
     {"config.classifier_pooling", X1, V_INT, 0, 1, "0 ([CLS] row) or 1 (masked mean)", "the [CLS] row", 0, 0, HEAD_MODERN_CLS, 0},
     {"config.deberta_position_buckets", X1, V_INT, 2, DEB_MAX_BUCKETS, "an even integer", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 2},
     {"config.deberta_max_relative_positions", X1, V_INT, 2, 65536, "an integer M with M - 1 > position_buckets / 2", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 0},
+    {"config.rotary_feed_forward", X1, V_INT, 0, 1, "0 (SwiGLU) or 1 (gelu with biases)", "NomicBert's SwiGLU", 0, 0, -1, 0},
     {"config.decoder_attention", X1, V_INT, 0, 1, "0 (bidirectional) or 1 (causal)", "not a decoder handle", 0, -1, -1, 0},
 };
 constexpr int64_t SETTING_MAX_VALUES = 4096;
@@ -516,6 +526,7 @@ static const FamilyRow FAMILIES[] = {
     {T5, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G)},
     {DEBERTA, false, false, bits(T_WORD, T_ELNG, T_ELNB), (1u << L_COUNT) - 1 - bits(L_UW)},
     {DECODER, true, true, bits(T_WORD, T_ELNG), LAYER_MATRICES | bits(L_LN1G, L_LN2G, L_UW)},
+    {ROTARY_BERT, false, false, bits(T_WORD, T_TYPE, T_ELNG, T_ELNB), LAYER_MATRICES | LAYER_NORMS},
 };
 
 enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY, POS_DISENT };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table), none (DeBERTa: a zero row)
@@ -561,8 +572,16 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     const bool local_set = set.has(SET_ROTARY_LOCAL) || set.has(SET_HALF_WINDOW);
     const bool deb = set.has(SET_DEB_BUCKETS) || set.has(SET_DEB_MAX_REL), dec = set.has(SET_DECODER_ATTN);
     const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF), Bk = set.value(SET_DEB_BUCKETS, 0), max_rel = set.value(SET_DEB_MAX_REL, 0);
-    const Family fam = dec ? DECODER : deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rot ? NOMIC : rel ? MPNET : BERT;
+    const bool rbert = set.value(SET_ROTARY_FF, 0) == 1;
+    const Family fam = dec ? DECODER : deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rbert ? ROTARY_BERT : rot ? NOMIC : rel ? MPNET : BERT;
     const std::vector<float>& flags = set.v[SET_LOCAL_LAYERS];
+    if (rbert) {
+        if (pad_idx >= 0 || modern || local_set || t5 || deb || dec || rel)
+            return err(KR_EINVAL, "config.rotary_feed_forward = 1 next to config.position_padding_idx / config.local_attention_layers / config.rotary_inv_freq_local / "
+                                  "config.attention_half_window / config.t5_feed_forward / config.deberta_* / config.decoder_attention / a relative attention bias: "
+                                  "a handle has one position scheme");
+        if (!rot) return err(KR_EINVAL, "config.rotary_feed_forward = 1 without config.rotary_inv_freq: a rotary BERT handle rotates q and k");
+    }
     if (dec) {
         if (pad_idx >= 0 || modern || local_set || t5 || deb || rel)
             return err(KR_EINVAL, "config.decoder_attention next to config.position_padding_idx / config.local_attention_layers / config.rotary_inv_freq_local / "
@@ -582,10 +601,21 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
                        slot_tensor_name(i, g).c_str());
         }
     } else {
-        for (size_t i = 0; i < ld.got.size(); ++i)
-            if (fam_of(ld.got[i]) == DECODER)
-                return err(KR_EINVAL, "'%s' but config.decoder_attention was never loaded: load it before kr_encoder_finalize", slot_tensor_name(i, DECODER).c_str());
+        // (a rotary BERT handle takes its q / k / v biases under the decoders' rows, and nothing else of theirs)
+        for (size_t i = 0; i < ld.got.size(); ++i) {
+            if (fam_of(ld.got[i]) != DECODER) continue;
+            const int id = i < T_LAYER0 ? -1 : (int)((i - T_LAYER0) % L_COUNT);
+            if (!rbert) return err(KR_EINVAL, "'%s' but config.decoder_attention was never loaded: load it before kr_encoder_finalize", slot_tensor_name(i, DECODER).c_str());
+            if (id != L_QB && id != L_KB && id != L_VB)
+                return err(KR_EINVAL, "'%s' on a rotary BERT handle (config.rotary_feed_forward = 1): of the decoders' names it takes layers.N.self_attn.{q,k,v}_proj.bias only",
+                           slot_tensor_name(i, DECODER).c_str());
+        }
     }
+    // the rotary BERT rows (self_attn.o_proj.bias, mlp.fc1, mlp.fc2) on their own handles only
+    for (size_t i = 0; i < ld.got.size() && !rbert; ++i)
+        if (fam_of(ld.got[i]) == ROTARY_BERT)
+            return err(KR_EINVAL, "'%s' but config.rotary_feed_forward = 1 was never loaded: load it (and config.rotary_inv_freq) before kr_encoder_finalize",
+                       slot_tensor_name(i, ROTARY_BERT).c_str());
     // the k / v width A: one per handle — k and v of a layer agree, the layers agree, the biases agree with the matrices; A < H on decoder handles only (the
     // attention kernels of every other family read K / V^T of head h, not of head h / group)
     int kv_dim = cfg.hidden;
@@ -697,6 +727,21 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     for (int li = 0; li < cfg.layers && !modern && !t5 && !dec; ++li) {
         const uint8_t* g = &ld.got[T_LAYER0 + (size_t)li * L_COUNT];
         auto under = [&](int id, bool nomic) { return g[id] && (fam_of(g[id]) == NOMIC) == nomic; };
+        if (rbert) {
+            // q / k in the rotary packed-row order (NomicBert's names) and their biases in the same order (the decoders'); fc1 in plain order (its own name)
+            const size_t base = T_LAYER0 + (size_t)li * L_COUNT;
+            if (under(L_QW, false) || under(L_KW, false))
+                return err(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj under NomicBert's names", li);
+            for (const int id : {L_IW, L_UW})
+                if (g[id] && fam_of(g[id]) != ROTARY_BERT)
+                    return err(KR_EINVAL, "'%s' on a rotary BERT handle (config.rotary_feed_forward = 1): its feed-forward is mlp.fc1 / mlp.fc2, not a gated projection",
+                               slot_tensor_name(base + id, fam_of(g[id])).c_str());
+            for (const int id : {L_QB, L_KB, L_IB})
+                if (g[id] && fam_of(g[id]) != (id == L_IB ? ROTARY_BERT : DECODER))
+                    return err(KR_EINVAL, "'%s' on a rotary BERT handle (config.rotary_feed_forward = 1): it takes self_attn.{q,k,v,o}_proj.bias and mlp.{fc1,fc2}.bias",
+                               slot_tensor_name(base + id, fam_of(g[id])).c_str());
+            continue;
+        }
         if (rot && (under(L_QW, false) || under(L_KW, false) || under(L_IW, false)))
             return err(KR_EINVAL, "layer %d: a handle with config.rotary_inv_freq takes self_attn.{q,k}_proj and mlp.{gate,up}_proj under NomicBert's names", li);
         if (rot && (g[L_QB] || g[L_KB] || g[L_IB])) return err(KR_EINVAL, "layer %d: the q / k / gate / up projections of a NomicBert handle have no bias", li);
@@ -718,9 +763,9 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     plan.pad_idx = pad_idx; plan.half_window = set.value(SET_HALF_WINDOW, 0);
     for (int li = 0; li < cfg.layers; ++li)
         plan.layers.push_back({!rot ? QKV_PLAIN : (modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB]) ||
-                                                    (dec && (ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] || ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_KB])) ? QKV_ROT_BIAS : QKV_ROT,
+                                                    ((dec || rbert) && (ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] || ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_KB])) ? QKV_ROT_BIAS : QKV_ROT,
                                dec ? (set.value(SET_DECODER_ATTN) == 1 ? AM_CAUSAL : AM_PLAIN) : deb ? AM_DISENT : rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
-    plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot ? FF_SWIGLU : FF_GELU;
+    plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot && !rbert ? FF_SWIGLU : FF_GELU;
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;
     plan.kv_dim = kv_dim;

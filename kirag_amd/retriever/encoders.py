@@ -58,6 +58,15 @@ q / k / v biases, CAUSAL attention (``config.decoder_attention`` = 1) and mean o
 (``expand_kv``: each KV head's rows repeated ``heads / kv_heads`` times, exact).  ``check_decoder_config`` refuses from ``config.json`` alone what the kernels do not
 compute (128-wide heads among it).
 
+EuroBERT checkpoints (``model_type`` eurobert: EuroBERT-210m / -610m and their fine-tunes): the decoders' stack with a BIDIRECTIONAL mask
+(``config.decoder_attention`` = 0), under the decoders' rules and classes; ``EuroBertE5Encoder`` / ``EuroBertBGEEncoder`` both pool the mean unless told otherwise.
+The Qwen2 / Llama / Mistral twins take the same choice as ``from_pretrained(..., attention="bidirectional")`` (fine-tunes trained without the causal mask).
+
+jina-embeddings-v3 (``model_type`` jina_embeddings_v3, ``transformers.JinaEmbeddingsV3Model``): NomicBert's post-LN rotary stack with linear biases on q / k / v / o
+(q's and k's added before the rotation) and BERT's feed-forward ``fc2(gelu(fc1 x + b1)) + b2`` in place of SwiGLU (``config.rotary_feed_forward`` = 1).
+``check_jina3_config`` refuses from ``config.json`` alone what the kernels do not compute; task LoRA adapters are not applied (merge them into the weights).
+``JinaV3E5Encoder`` / ``JinaV3BGEEncoder`` are the twins.
+
 SPLADE (``POOL_SPLADE`` on a BERT handle that was given ``cls.predictions.*``): the forward returns ``[B, vocab_size]``; the ``BertForMaskedLM`` twin and
 ``SpladeModel`` live in ``kirag_amd.retriever.splade``.
 """
@@ -71,8 +80,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import (BertModel, DebertaV2Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel, PretrainedConfig, Qwen2Model,
-                          T5EncoderModel, XLMRobertaModel)
+from transformers import (BertModel, DebertaV2Model, EuroBertModel, JinaEmbeddingsV3Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel,
+                          PretrainedConfig, Qwen2Model, T5EncoderModel, XLMRobertaModel)
 
 from .. import _lib
 
@@ -113,7 +122,13 @@ DEBERTA_SETTINGS = ("config.deberta_position_buckets", "config.deberta_max_relat
 DEBERTA_MAX_BUCKETS = 256                    # the library's bound on position_buckets: 512 rows of encoder.rel_embeddings
 DEBERTA_MAX_POS = 8192                       # ... and on max_position_embeddings of such a handle
 # decoder-LLM embedders: model_type -> the HF base model the twins are built over
-DECODER_BASES = {"qwen2": Qwen2Model, "llama": LlamaModel, "mistral": MistralModel}
+DECODER_BASES = {"qwen2": Qwen2Model, "llama": LlamaModel, "mistral": MistralModel, "eurobert": EuroBertModel}
+EUROBERT_TYPE = "eurobert"                       # the decoders' stack whose HF forward is bidirectional: its handles get config.decoder_attention = 0
+DECODER_ATTENTIONS = {"causal": 1.0, "bidirectional": 0.0}       # the ``attention`` kwarg of the decoder twins' from_pretrained -> the setting
+ST_ATTENTION_FILE = "attention.json"             # next to 1_Pooling/config.json (whose keys sentence-transformers' Pooling module takes as arguments): {"attention": ...}
+JINA3_TYPE = "jina_embeddings_v3"
+ROTARY_FF_SETTING = "config.rotary_feed_forward"     # reserved name (include/kirag_amd.h): one float, 1 = fc2(gelu(fc1 x + b1)) + b2 on a rotary post-LN handle
+JINA3_MAX_POS = 8192                             # the rotary tables' limit: it only bounds the sequence length (the checkpoint says 8194)
 DECODER_SETTING = "config.decoder_attention"     # reserved name (include/kirag_amd.h): one float, 1 = causal, 0 = bidirectional on the same stack
 DECODER_MAX_POS = 8192                           # the rotary tables' limit: it only bounds the sequence length
 DECODER_POOLINGS = {"mean": POOL_MEAN, "last": _lib.POOL_LAST}
@@ -217,8 +232,42 @@ def check_deberta_config(config, head: bool = False) -> dict:
     return {"buckets": Bk, "max_rel": M}
 
 
+def check_jina3_config(config) -> dict:
+    """``NotImplementedError`` beginning ``model_type='jina_embeddings_v3':`` and naming the field, for everything of a JinaEmbeddingsV3Config the kernels do not
+    compute — from the config alone: no weight has been read and the library is not loaded.  ``config``: the HF config or the dict of a ``config.json`` (HF's
+    defaults fill the rest).  Returns ``max_pos`` = min(max_position_embeddings, 8192) and ``inv_freq`` from HF's own rotary module."""
+    if isinstance(config, dict):
+        from transformers import CONFIG_MAPPING
+        config = CONFIG_MAPPING[JINA3_TYPE](**{k: v for k, v in config.items() if k not in ("model_type", "transformers_version", "architectures")})
+
+    def refuse(msg):
+        raise NotImplementedError(f"model_type={JINA3_TYPE!r}: {msg}")
+    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
+    if heads <= 0 or H % heads:
+        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
+    d_h = H // heads
+    head_dim = getattr(config, "head_dim", None) or d_h
+    if int(head_dim) != d_h:
+        refuse(f"head_dim={head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+    if d_h not in (32, 64):
+        refuse(f"head_dim={d_h} (hidden_size={H} / num_attention_heads={heads}): the attention kernels are built for heads of width 32 and 64")
+    if H % 128 or not 0 < H <= 2048:
+        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
+    if ff <= 0 or ff % 128:
+        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
+    if getattr(config, "hidden_act", "gelu") != "gelu":
+        refuse(f"hidden_act={config.hidden_act!r}: the feed-forward of a {JINA3_TYPE} handle implements erf-GELU only")
+    rope = _decoder_rope(config)
+    if float(rope.attention_scaling) != 1.0:
+        refuse(f"attention_scaling={float(rope.attention_scaling)} (rope_type {getattr(rope, 'rope_type', None)!r}): only rope variants with attention_scaling 1.0 are implemented")
+    inv = rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    if inv.numel() != d_h // 2:
+        refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
+    return {"max_pos": min(int(config.max_position_embeddings), JINA3_MAX_POS), "inv_freq": inv}
+
+
 def check_decoder_config(config) -> dict:
-    """``NotImplementedError`` beginning ``model_type='<type>':`` and naming the field, for everything of a Qwen2 / Llama / Mistral config the kernels do not
+    """``NotImplementedError`` beginning ``model_type='<type>':`` and naming the field, for everything of a Qwen2 / Llama / Mistral / EuroBERT config the kernels do not
     compute — from the config alone: no weight has been read and the library is not loaded.  ``config``: the HF config or the dict of a ``config.json`` (HF's
     defaults fill the rest).  Returns what the handle is created with: hidden, layers, heads, kv_heads, intermediate, ``max_pos`` =
     min(max_position_embeddings, 8192), ``ln_eps`` = rms_norm_eps, and ``inv_freq`` from HF's own rotary module (so static rope variants such as ``llama3`` are
@@ -329,15 +378,18 @@ def read_st_pooling(where, **kwargs) -> Optional[str]:
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
 
-    DECODER_ATTENTION = 1.0          # what a decoder handle's "config.decoder_attention" is given: causal (0.0, bidirectional, exists in the library and its tests)
+    DECODER_ATTENTION = 1.0          # what a decoder handle's "config.decoder_attention" is given unless ``decoder_attention`` says otherwise: causal
 
-    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None):
+    def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None,
+                 decoder_attention: Optional[float] = None):
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
         low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it).
         ``rename``: optional callable, parameter name of the module -> the name the library knows (``sync`` / ``load_state`` apply it to every name; a
         task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``).
         ``extra``: optional callable, module -> [(library name, tensor)] that ``sync`` sends besides ``named_parameters()`` unless a parameter already has
-        that name (a TIED parameter appears once in ``named_parameters()``; the library wants it under both names: ``kirag_amd.retriever.splade``)."""
+        that name (a TIED parameter appears once in ``named_parameters()``; the library wants it under both names: ``kirag_amd.retriever.splade``).
+        ``decoder_attention``: 1.0 / 0.0 = the causal / bidirectional mask of a decoder handle; ``None`` = bidirectional for ``model_type`` eurobert (HF's
+        EuroBertModel has no causal mask), else ``DECODER_ATTENTION``."""
         lib = _lib.load()
         self.rename = rename
         self.extra = extra
@@ -348,7 +400,12 @@ class HipBertForward:
         self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
         self.is_deberta = getattr(config, "model_type", "bert") in (DEBERTA_TYPE, "deberta")
         self.is_decoder = getattr(config, "model_type", "bert") in DECODER_BASES
+        self.is_jina3 = getattr(config, "model_type", "bert") == JINA3_TYPE
         decoder = check_decoder_config(config) if self.is_decoder else None     # refuses what the kernels do not compute, before a handle exists
+        jina3 = check_jina3_config(config) if self.is_jina3 else None           # likewise
+        if decoder_attention is None:
+            decoder_attention = 0.0 if getattr(config, "model_type", "bert") == EUROBERT_TYPE else self.DECODER_ATTENTION
+        self.decoder_attention = float(decoder_attention) if self.is_decoder else None
         self.heads, self.kv_heads = (decoder["heads"], decoder["kv_heads"]) if decoder else (0, 0)
         deberta = check_deberta_config(config) if self.is_deberta else None     # refuses what the kernels do not compute, before a handle exists
         inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
@@ -372,6 +429,9 @@ class HipBertForward:
         self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
         if self.is_t5:
             cfg = _lib.BertCfg(t5["hidden"], t5["layers"], t5["heads"], self.ff, config.vocab_size, t5["max_pos"], type_vocab, t5["ln_eps"])
+        elif self.is_jina3:      # max_pos capped at the rotary tables' 8192: it only bounds the sequence length
+            cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff, config.vocab_size, jina3["max_pos"],
+                               config.type_vocab_size, float(config.layer_norm_eps))
         elif self.is_decoder:
             cfg = _lib.BertCfg(decoder["hidden"], decoder["layers"], decoder["heads"], self.ff, config.vocab_size, decoder["max_pos"], type_vocab, decoder["ln_eps"])
         else:
@@ -411,8 +471,14 @@ class HipBertForward:
         if decoder is not None:
             f = decoder["inv_freq"]
             _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", f.data_ptr(), f.numel()))
-            v = C.c_float(self.DECODER_ATTENTION)
+            v = C.c_float(self.decoder_attention)
             _lib.check(lib.kr_encoder_load_weight(h, DECODER_SETTING.encode(), C.addressof(v), 1))
+        # a rotary BERT handle (jina-embeddings-v3): HF's own frequencies, then the feed-forward kind that makes it one
+        if jina3 is not None:
+            f = jina3["inv_freq"]
+            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", f.data_ptr(), f.numel()))
+            v = C.c_float(1.0)
+            _lib.check(lib.kr_encoder_load_weight(h, ROTARY_FF_SETTING.encode(), C.addressof(v), 1))
         # a DeBERTa handle: the two numbers of its bucket rule
         if deberta is not None:
             for name, val in zip(DEBERTA_SETTINGS, (deberta["buckets"], deberta["max_rel"])):
@@ -746,7 +812,7 @@ class _HipModuleMixin:
                 "Move the model to a GPU (kirag_amd has no CPU fallback).")
         idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
         if self._hip is None or self._hip.device_index != idx:
-            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename, extra=type(self)._hip_extra)
+            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename, extra=type(self)._hip_extra, decoder_attention=getattr(self, "_decoder_attention", None))
         self._hip.sync(self)
         return self._hip
 
@@ -846,7 +912,8 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _modern_twin = None              # ... and over ModernBertModel
     _t5_twin = None                  # ... and over T5EncoderModel
     _deberta_twin = None             # ... and over DebertaV2Model
-    _decoder_twin = None             # ... and over Qwen2Model / LlamaModel / MistralModel (DecoderE5Encoder / DecoderBGEEncoder pick the base)
+    _decoder_twin = None             # ... and over Qwen2Model / LlamaModel / MistralModel / EuroBertModel (DecoderE5Encoder / DecoderBGEEncoder pick the base)
+    _jina3_twin = None               # ... and over JinaEmbeddingsV3Model
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -879,6 +946,10 @@ class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
             # disentangled attention under projection names of its own; what the kernels do not compute is refused from config.json alone
             check_deberta_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
             return cls._deberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if model_type == JINA3_TYPE:
+            # NomicBert's rotary post-LN stack with biases and BERT's feed-forward; what the kernels do not compute is refused from config.json alone
+            check_jina3_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
+            return cls._jina3_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         if model_type in DECODER_BASES:
             # a causal pre-LN stack under names of its own; what the kernels do not compute is refused from config.json alone
             return cls._decoder_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
@@ -895,6 +966,14 @@ class _HipMPNetSentenceEncoder(_HipSentenceMixin, MPNetModel):
 
 class _HipNomicSentenceEncoder(_HipSentenceMixin, NomicBertModel):
     _hf_base = NomicBertModel
+
+
+class _HipJinaV3SentenceEncoder(_HipSentenceMixin, JinaEmbeddingsV3Model):
+    _hf_base = JinaEmbeddingsV3Model
+
+    def __init__(self, config, add_pooling_layer=True, **kwargs):
+        check_jina3_config(config)                  # refuses what the kernels do not compute when the model is made, not at its first forward
+        super().__init__(config, add_pooling_layer, **kwargs)
 
 
 class _HipModernBertSentenceEncoder(_HipSentenceMixin, ModernBertModel):
@@ -1033,18 +1112,56 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
     """A decoder LLM used as an embedder: HF's own causal forward in ``train()`` mode, the library's in eval mode.  ``self._pool`` is the instance's pooling
     (``POOL_MEAN`` / ``POOL_LAST``): the ``pooling`` kwarg of ``from_pretrained`` ("mean" / "last"), else the checkpoint's ``1_Pooling/config.json``, else the
     class default (E5 -> mean, BGE -> last; the first token sees itself alone under a causal mask and is never chosen).  ``save_pretrained`` writes the pooling
-    back as a sentence-transformers ``1_Pooling/config.json`` + ``modules.json``, so a reload keeps it.  Appending an EOS token is the tokenizer's business."""
+    back as a sentence-transformers ``1_Pooling/config.json`` + ``modules.json``, so a reload keeps it.  Appending an EOS token is the tokenizer's business.
+    ``self._decoder_attention`` is the instance's mask (1.0 causal / 0.0 bidirectional): the ``attention`` kwarg of ``from_pretrained`` ("causal" /
+    "bidirectional"), else the checkpoint's ``1_Pooling/attention.json`` (``save_pretrained`` writes it), else causal — for fine-tunes that were trained without
+    the causal mask.  An EuroBERT twin is bidirectional and takes nothing else.  ``train()`` mode of a bidirectional Qwen2 / Llama / Mistral twin feeds HF the
+    4-D mask that admits every attended key."""
 
     def __init__(self, config, add_pooling_layer=False, **kwargs):
         check_decoder_config(config)                # refuses what the kernels do not compute when the model is made, not at its first forward
         self._hf_base.__init__(self, config)        # these models have no pooling layer to ask for
         self.kwargs = kwargs
         self._hip = None
+        self._decoder_attention = 0.0 if self._hf_base is EuroBertModel else 1.0
 
-    def set_pooling(self, pooling: str) -> None:
+    @classmethod
+    def _check_pooling(cls, pooling) -> None:
+        if pooling == "cls":
+            raise ValueError("pooling='cls': the library refuses KR_POOL_CLS on decoder handles, bidirectional ones included (they take KR_POOL_MEAN and KR_POOL_LAST); "
+                             f"one of {sorted(DECODER_POOLINGS)}")
         if pooling not in DECODER_POOLINGS:
             raise ValueError(f"pooling={pooling!r}: one of {sorted(DECODER_POOLINGS)}")
+
+    def set_pooling(self, pooling: str) -> None:
+        self._check_pooling(pooling)
         self._pool = DECODER_POOLINGS[pooling]
+
+    @classmethod
+    def _check_attention(cls, attention) -> None:
+        if attention not in DECODER_ATTENTIONS:
+            raise ValueError(f"attention={attention!r}: one of {sorted(DECODER_ATTENTIONS)}")
+        if cls._hf_base is EuroBertModel and attention != "bidirectional":
+            raise ValueError(f"attention={attention!r}: an EuroBERT checkpoint is bidirectional (EuroBertModel has no causal mask)")
+
+    def set_attention(self, attention: str) -> None:
+        self._check_attention(attention)
+        if DECODER_ATTENTIONS[attention] != self._decoder_attention:
+            self._decoder_attention = DECODER_ATTENTIONS[attention]
+            self._hip = None                        # the mask of a handle is fixed at its first finalize
+
+    @property
+    def attention(self) -> str:
+        return {v: k for k, v in DECODER_ATTENTIONS.items()}[self._decoder_attention]
+
+    def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
+        if self._decoder_attention != 0.0 or self._hf_base is EuroBertModel:
+            return super()._torch_pooled(input_ids, attention_mask, token_type_ids)
+        # [B, 1, S, S] additive: every attended key column for every query column, in the place of HF's causal mask
+        dtype = next(self.parameters()).dtype
+        mask4d = torch.zeros(attention_mask.shape, dtype=dtype, device=attention_mask.device).masked_fill(attention_mask == 0, torch.finfo(dtype).min)
+        mask4d = mask4d[:, None, None, :].expand(-1, 1, attention_mask.shape[1], -1).contiguous()
+        return self._hf_base.forward(self, input_ids=input_ids, attention_mask=mask4d, return_dict=True).last_hidden_state
 
     @property
     def pooling(self) -> str:
@@ -1052,9 +1169,11 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        pooling = kwargs.pop("pooling", None)
-        if pooling is not None and pooling not in DECODER_POOLINGS:
-            raise ValueError(f"pooling={pooling!r}: one of {sorted(DECODER_POOLINGS)}")
+        pooling, attention = kwargs.pop("pooling", None), kwargs.pop("attention", None)
+        if pooling is not None:
+            cls._check_pooling(pooling)
+        if attention is not None:
+            cls._check_attention(attention)
         config = kwargs.get("config")
         if not isinstance(config, PretrainedConfig):
             where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
@@ -1062,9 +1181,17 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
         check_decoder_config(config)                # from config.json alone, before a weight is read
         if pooling is None:
             pooling = read_st_pooling(pretrained_model_name_or_path, **kwargs)
+        if attention is None:
+            path = _st_file(pretrained_model_name_or_path, f"{ST_POOLING_DIR}/{ST_ATTENTION_FILE}", kwargs)
+            if path is not None:
+                with open(path) as f:
+                    attention = json.load(f).get("attention")
+                cls._check_attention(attention)
         model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         if pooling is not None:
             model.set_pooling(pooling)
+        if attention is not None:
+            model.set_attention(attention)
         return model
 
     def save_pretrained(self, save_directory, *args, **kwargs):
@@ -1075,6 +1202,8 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
                 "pooling_mode_lasttoken": self._pool == POOL_LAST, "include_prompt": True}
         with open(os.path.join(save_directory, ST_POOLING_DIR, "config.json"), "w") as f:
             json.dump(pool, f, indent=2)
+        with open(os.path.join(save_directory, ST_POOLING_DIR, ST_ATTENTION_FILE), "w") as f:
+            json.dump({"attention": self.attention}, f, indent=2)
         modules = [{"idx": 0, "name": "0", "path": "", "type": "sentence_transformers.models.Transformer"},
                    {"idx": 1, "name": "1", "path": ST_POOLING_DIR, "type": "sentence_transformers.models.Pooling"},
                    {"idx": 2, "name": "2", "path": "2_Normalize", "type": "sentence_transformers.models.Normalize"}]
@@ -1083,8 +1212,8 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
         return out
 
 
-def _decoder_twin(base, pool: int, doc: str):
-    name = base.__name__[:-len("Model")] + ("E5Encoder" if pool == POOL_MEAN else "BGEEncoder")
+def _decoder_twin(base, pool: int, doc: str, name: Optional[str] = None):
+    name = name or base.__name__[:-len("Model")] + ("E5Encoder" if pool == POOL_MEAN else "BGEEncoder")
     return type(name, (_HipDecoderSentenceMixin, base), {"_hf_base": base, "_pool": pool, "__doc__": doc, "__module__": __name__})
 
 
@@ -1094,10 +1223,13 @@ LlamaE5Encoder = _decoder_twin(LlamaModel, POOL_MEAN, "LlamaModel (causal) -> ma
 LlamaBGEEncoder = _decoder_twin(LlamaModel, POOL_LAST, "LlamaModel (causal) -> last attended token -> L2 normalise")
 MistralE5Encoder = _decoder_twin(MistralModel, POOL_MEAN, "MistralModel (causal, no sliding window) -> masked mean -> L2 normalise")
 MistralBGEEncoder = _decoder_twin(MistralModel, POOL_LAST, "MistralModel (causal, no sliding window) -> last attended token -> L2 normalise")
+# EuroBERT: no causal reason to prefer the last token, so both registry classes pool the mean unless the kwarg or 1_Pooling says "last"
+EuroBertE5Encoder = _decoder_twin(EuroBertModel, POOL_MEAN, "EuroBertModel (bidirectional) -> masked mean -> L2 normalise (EuroBERT-210m / -610m fine-tunes)", "EuroBertE5Encoder")
+EuroBertBGEEncoder = _decoder_twin(EuroBertModel, POOL_MEAN, "EuroBertModel (bidirectional) -> masked mean -> L2 normalise", "EuroBertBGEEncoder")
 
 
 class _DecoderDispatch:
-    """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral``); anything else is refused by name"""
+    """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral`` / ``eurobert``); anything else is refused by name"""
     _twins: dict = {}
 
     @classmethod
@@ -1116,12 +1248,12 @@ class _DecoderDispatch:
 
 class DecoderE5Encoder(_DecoderDispatch):
     """a decoder LLM (causal) -> masked mean -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``last``"""
-    _twins = {"qwen2": Qwen2E5Encoder, "llama": LlamaE5Encoder, "mistral": MistralE5Encoder}
+    _twins = {"qwen2": Qwen2E5Encoder, "llama": LlamaE5Encoder, "mistral": MistralE5Encoder, "eurobert": EuroBertE5Encoder}
 
 
 class DecoderBGEEncoder(_DecoderDispatch):
     """a decoder LLM (causal) -> last attended token -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``mean``"""
-    _twins = {"qwen2": Qwen2BGEEncoder, "llama": LlamaBGEEncoder, "mistral": MistralBGEEncoder}
+    _twins = {"qwen2": Qwen2BGEEncoder, "llama": LlamaBGEEncoder, "mistral": MistralBGEEncoder, "eurobert": EuroBertBGEEncoder}
 
 
 class E5Encoder(_HipSentenceEncoder):
@@ -1184,6 +1316,16 @@ class T5BGEEncoder(_HipT5SentenceEncoder):
     _pool = POOL_CLS
 
 
+class JinaV3E5Encoder(_HipJinaV3SentenceEncoder):
+    """JinaEmbeddingsV3Model -> masked mean -> L2 normalise (jinaai/jina-embeddings-v3-hf; task adapters are not applied)"""
+    _pool = POOL_MEAN
+
+
+class JinaV3BGEEncoder(_HipJinaV3SentenceEncoder):
+    """JinaEmbeddingsV3Model -> [:, 0] -> L2 normalise"""
+    _pool = POOL_CLS
+
+
 class DebertaV2E5Encoder(_HipDebertaSentenceEncoder):
     """DebertaV2Model -> masked mean -> L2 normalise (fine-tunes of microsoft/deberta-v3-*)"""
     _pool = POOL_MEAN
@@ -1208,6 +1350,8 @@ E5Encoder._deberta_twin = DebertaV2E5Encoder
 BGEEncoder._deberta_twin = DebertaV2BGEEncoder
 E5Encoder._decoder_twin = DecoderE5Encoder
 BGEEncoder._decoder_twin = DecoderBGEEncoder
+E5Encoder._jina3_twin = JinaV3E5Encoder
+BGEEncoder._jina3_twin = JinaV3BGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:
@@ -1217,6 +1361,11 @@ def _register_nomic_checkpoint_format() -> None:
     from transformers.conversion_mapping import get_checkpoint_conversion_mapping, register_checkpoint_conversion_mapping
     for cls in (NomicBertE5Encoder, NomicBertBGEEncoder):
         register_checkpoint_conversion_mapping(cls.__name__, get_checkpoint_conversion_mapping(NOMIC_TYPE), overwrite=True)
+    # jina-embeddings-v3 checkpoints are stored in their original layout as well, and converted through the mapping of their model_type
+    jina3 = get_checkpoint_conversion_mapping(JINA3_TYPE)
+    for cls in (JinaV3E5Encoder, JinaV3BGEEncoder):
+        if jina3 is not None:
+            register_checkpoint_conversion_mapping(cls.__name__, jina3, overwrite=True)
 
 
 _register_nomic_checkpoint_format()

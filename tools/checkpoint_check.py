@@ -14,7 +14,9 @@ sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*, loaded as th
 head where modules.json lists one; reference T5EncoderModel in fp32 + pooling + that head, GPU only; "LN1" / "LN2" are again the pre-LN residual stream, and
 the feed-forward's hidden state is among the 16-bit-stored tensors: HF's own fp16 runs of v1.1 / flan sizes are known to overflow there) or a
 DeBERTa-v2 / v3 one (model_type deberta-v2: fine-tunes of microsoft/deberta-v3-*; reference DebertaV2Model in fp32, GPU only: the disentangled attention is not in
-the torch emulation) or a
+the torch emulation), a jina-embeddings-v3 one (model_type jina_embeddings_v3; reference JinaEmbeddingsV3Model in fp32 with eager attention, GPU only; task
+adapters are not applied), an EuroBERT or Qwen2 / Llama / Mistral one (decoder handles: --pool mean or last; reference the HF base model in fp32 with eager
+attention under its own mask, or under the all-admitting one where the folder's 1_Pooling/attention.json says "bidirectional") or a
 RoBERTa-family one (model_type roberta / xlm-roberta / camembert: multilingual-e5, bge-m3; the reference is then XLMRobertaModel / RobertaModel in fp32 and the
 HIP encoder follows fairseq's position rule; the torch emulation knows BERT's rule only, so such a checkpoint needs the GPU).  No
 checkpoint exists in the build container (no network), so the defaults of this library — f16 MFMA operands + the residual stream's low half — were chosen on
@@ -154,8 +156,9 @@ def reference_and_stats(model, batches, pool, dev):
             continue
         if nomic:
             att, mlp = layer.self_attn, layer.mlp      # q / k before the rotation (a rotation keeps their size); "h" = what the gated projection stores
+            down = mlp.down_proj if hasattr(mlp, "down_proj") else mlp.fc2      # JinaEmbeddingsV3Model: NomicBert's layer with fc1 / fc2 ("h" = gelu(fc1 x + b1))
             for key, mod in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("y1", att.o_proj), ("ln1", layer.post_attention_layernorm),
-                             ("h", mlp.down_proj), ("y2", mlp.down_proj), ("ln2", layer.post_mlp_layernorm)):
+                             ("h", down), ("y2", down), ("ln2", layer.post_mlp_layernorm)):
                 hooks.append((mod.register_forward_pre_hook(lambda _m, inp, f=grab(li, key): f(_m, inp, inp[0])) if key == "h" else
                               mod.register_forward_hook(grab(li, key))))
             continue
@@ -173,7 +176,10 @@ def reference_and_stats(model, batches, pool, dev):
     with torch.no_grad():
         for ids, mask in batches:
             cur["mask"] = torch.from_numpy(mask).bool().to(dev)
-            out = hf_forward(model, input_ids=torch.from_numpy(ids).to(dev), attention_mask=torch.from_numpy(mask).to(dev)).last_hidden_state
+            if getattr(model, "_decoder_attention", 1.0) == 0.0:      # a decoder twin that runs bidirectionally: its own train()-mode forward (HF under the all-admitting mask)
+                out = model._torch_pooled(torch.from_numpy(ids).to(dev), torch.from_numpy(mask).to(dev), None)
+            else:
+                out = hf_forward(model, input_ids=torch.from_numpy(ids).to(dev), attention_mask=torch.from_numpy(mask).to(dev)).last_hidden_state
             if pool == "mean":
                 m = torch.from_numpy(mask).to(dev)[..., None].bool()
                 e = out.masked_fill(~m, 0.0).sum(1) / m.sum(1)
@@ -200,7 +206,7 @@ def reference_and_stats(model, batches, pool, dev):
 
 def run_mode_hip(model, batches, pool, dtype, lo):
     from kirag_amd.retriever.encoders import HipBertForward
-    h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo)
+    h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, decoder_attention=getattr(model, "_decoder_attention", None))
     h.sync(model)
     return [h.forward_np(ids, mask, {"mean": 0, "cls": 1, "last": 5}[pool]) for ids, mask in batches]
 
@@ -404,14 +410,21 @@ def check(hf_dir, args):
     from kirag_amd.retriever.encoders import DECODER_BASES, DecoderBGEEncoder, DecoderE5Encoder
     if getattr(cfg, "model_type", "bert") in DECODER_BASES:
         # a decoder LLM used as an embedder: the twin of the pooling asked for (mean / last; "cls" is never right under a causal mask), reference = its HF base
-        # class in fp32 with eager attention under its own causal mask.  What the kernels do not compute (128-wide heads, ...) is refused from config.json
+        # class in fp32 with eager attention under its own causal mask — EuroBertModel's own bidirectional one for model_type eurobert, the all-admitting
+        # 4-D mask for a folder whose 1_Pooling/attention.json says "bidirectional".  What the kernels do not compute (128-wide heads, ...) is refused from config.json
         if args.pool == "cls":
-            raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} runs under a causal mask: --pool mean or --pool last")
+            raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} runs on a decoder handle, which pools the mean or the last token: --pool mean or --pool last")
         twin = DecoderE5Encoder if args.pool == "mean" else DecoderBGEEncoder
         return check_model(twin.from_pretrained(hf_dir, pooling=args.pool, attn_implementation="eager"), args, hf_dir)
+    from kirag_amd.retriever.encoders import JINA3_TYPE, check_jina3_config
+    if getattr(cfg, "model_type", "bert") == JINA3_TYPE:
+        # NomicBert's rotary post-LN stack with biases and BERT's feed-forward; reference JinaEmbeddingsV3Model in fp32 with eager attention (task adapters
+        # are not applied: a folder whose weights carry a merged adapter is checked like any other)
+        check_jina3_config(cfg)
+        return check_model(AutoModel.from_pretrained(hf_dir, add_pooling_layer=False, attn_implementation="eager"), args, hf_dir)
     if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE, DEBERTA_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3 and T5 encoders")
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3, T5 encoders, jina-embeddings-v3, EuroBERT and Qwen2 / Llama / Mistral embedders")
     if cfg.model_type == MODERN_TYPE:
         model = AutoModel.from_pretrained(hf_dir, attn_implementation="eager")      # ModernBertModel has no pooling layer
     elif cfg.model_type == DEBERTA_TYPE:
@@ -433,14 +446,16 @@ def check_model(model, args, hf_dir="(in-memory model)"):
                          ", which the torch emulation does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == NOMIC_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has rotary positions and a gated MLP, which the torch emulation does not implement: run on the GPU")
+    if getattr(cfg, "model_type", "bert") == "jina_embeddings_v3" and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has rotary positions, which the torch emulation does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == MODERN_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with rotary positions, a gated MLP and sliding-window attention, which the torch "
                          "emulation does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == T5_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms and a relative attention bias, which the torch emulation does not "
                          "implement: run on the GPU")
-    if getattr(cfg, "model_type", "bert") in ("qwen2", "llama", "mistral") and not use_hip:
-        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a causal pre-LN stack with RMS norms, rotary positions and a gated MLP, which the torch emulation "
+    if getattr(cfg, "model_type", "bert") in ("qwen2", "llama", "mistral", "eurobert") and not use_hip:
+        raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms, rotary positions and a gated MLP, which the torch emulation "
                          "does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == DEBERTA_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} has disentangled attention, which the torch emulation does not implement: run on the GPU")

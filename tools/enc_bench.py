@@ -2,11 +2,13 @@
 """Encode-leg micro benchmark: passages/s of the HIP encoder (synthetic weights) at a BERT shape.
 
     python tools/enc_bench.py [n] [S] [ragged] [--shape e5-large|e5-small|minilm-l6|xlmr-base|xlmr-large|bge-m3|xlmr-base-8k|mpnet-base|mpnet-base-nobias|nomic-base|modernbert-base|modernbert-base-global|t5-base|t5-base-gated|deberta-v3-base ...] [--pool mean|cls] [--hf-fp16] [--expanded | --alternate-gqa (decoder shapes)]
-                              [--first-forward]
+                              [--first-forward] [--alternate-shapes] [--digest]
 
 Several --shape values run one after the other in the same process (default: e5-large).  --hf-fp16 also times HF BertModel / XLMRobertaModel in fp16 under
 torch on the same batch: a yardstick, not a product path.  --first-forward times, instead, the first eval forward of the MODULE (E5Encoder or its XLM-R
-twin on the GPU: the weight sync, the word table included) and the first one after a train() / eval() round trip."""
+twin on the GPU: the weight sync, the word table included) and the first one after a train() / eval() round trip.  --alternate-shapes builds one handle
+per --shape and times them in turns in this process (--reps rounds of 3 forwards: median, min, max).  --digest appends the first 16 hex digits of the sha256 of
+the batch's embeddings (to compare two builds of the library, each in its own process under KIRAG_AMD_LIB)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -67,7 +69,18 @@ LLAMA_1B = dict(hidden_size=2048, num_hidden_layers=16, num_attention_heads=32, 
                 max_position_embeddings=131072, rms_norm_eps=1e-5, hidden_act="silu", tie_word_embeddings=True, model_type="llama", type_vocab_size=1, layer_norm_eps=1e-5,
                 rope_parameters={"rope_theta": 500000.0, "rope_type": "llama3", "factor": 32.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
                                  "original_max_position_embeddings": 8192})
-SHAPES = dict(BS.ENCODER_SHAPES, **{"qwen2-0.5b": QWEN2_05B, "llama-1b": LLAMA_1B}, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# EuroBERT-210m: the decoders' stack (12 x 64 over 12 KV heads, no bias) under a bidirectional mask; --alternate times it against its causal twin
+EUROBERT_210M = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, num_key_value_heads=12, intermediate_size=3072, vocab_size=128256,
+                     max_position_embeddings=8192, rms_norm_eps=1e-5, hidden_act="silu", rope_parameters={"rope_theta": 250000.0, "rope_type": "default"},
+                     tie_word_embeddings=False, model_type="eurobert", type_vocab_size=1, layer_norm_eps=1e-5)
+# jina-embeddings-v3: xlmr-large's stack (biases everywhere, erf-GELU, post-LN) without a position table and with rotary q / k (EPI_QKV_ROTB): what the
+# position scheme costs is the difference to xlmr-large
+JINA_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "vocab_size", "max_position_embeddings", "type_vocab_size",
+             "layer_norm_eps", "hidden_act", "rope_parameters")
+JINA_V3 = dict(BS.E5_LARGE, vocab_size=250002, max_position_embeddings=8194, type_vocab_size=1, layer_norm_eps=1e-5, hidden_act="gelu", model_type="jina_embeddings_v3",
+               rope_parameters={"rope_theta": 20000.0, "rope_type": "default"})
+DECODER_TYPES = ("qwen2", "llama", "mistral", "eurobert")
+SHAPES = dict(BS.ENCODER_SHAPES, **{"qwen2-0.5b": QWEN2_05B, "llama-1b": LLAMA_1B, "eurobert-210m": EUROBERT_210M, "jina-v3": JINA_V3}, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -83,6 +96,8 @@ ap.add_argument("--alternate", action="store_true", help="decoder shapes: a caus
 ap.add_argument("--expanded", action="store_true", help="decoder shapes: build the handle from k_proj / v_proj expanded to [H, H] (expand_kv) instead of the grouped tensors")
 ap.add_argument("--alternate-gqa", action="store_true", help="decoder shapes: a native and an expanded handle of the same weights in this process, timed in turns (--reps rounds)")
 ap.add_argument("--first-forward", action="store_true")
+ap.add_argument("--alternate-shapes", action="store_true", help="one handle per --shape, timed in turns in this process (--reps rounds of 3)")
+ap.add_argument("--digest", action="store_true", help="append the sha256 (16 hex digits) of the batch's embeddings")
 args = ap.parse_args() if __name__ == "__main__" else ap.parse_args([])      # imported (tools/one_shape.py): SHAPES and make_encoder only
 n, S, ragged = args.n, args.S, args.ragged == "ragged"
 dev = torch.device("cuda:0")
@@ -128,16 +143,20 @@ def make_encoder(cfg, extra_state=None):
     """the HIP encoder with synthetic weights; an MPNet shape also gets a bias table N(0, 1) (it has to arrive before the handle's first finalize), a NomicBert
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw).  extra_state: tensors and settings that must
     arrive with the first load (a head: tools/rerank_bench.py), by library name"""
-    if cfg.get("model_type") in ("qwen2", "llama", "mistral"):
+    if cfg.get("model_type") in DECODER_TYPES:
         assert extra_state is None
         return make_decoder(cfg, not args.bidirectional, args.expanded)
-    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2"):
+    if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2", "jina_embeddings_v3"):
         assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
     from types import SimpleNamespace
     from kirag_amd.retriever.encoders import HipBertForward
     ns = SimpleNamespace(**cfg)
-    enc = HipBertForward(ns, 0)
+    if cfg["model_type"] == "jina_embeddings_v3":      # HF's own rotary module is built from HF's own config
+        import transformers as T
+        enc = HipBertForward(T.JinaEmbeddingsV3Config(**{k: cfg[k] for k in JINA_KEYS}), 0)
+    else:
+        enc = HipBertForward(ns, 0)
     if cfg["model_type"] == "modernbert":      # synthetic_state reads BERT's field names
         ns = SimpleNamespace(**dict(cfg, type_vocab_size=1, layer_norm_eps=cfg["norm_eps"]))
     if cfg["model_type"] == "deberta-v2":
@@ -192,6 +211,20 @@ def make_encoder(cfg, extra_state=None):
         st["encoder.LayerNorm.weight"] = torch.ones(cfg["hidden_size"], device=dev)
         st["encoder.LayerNorm.bias"] = torch.zeros(cfg["hidden_size"], device=dev)
         state = st
+    elif cfg["model_type"] == "jina_embeddings_v3":
+        # the same draws under JinaEmbeddingsV3Model's names: every bias kept, no position table
+        names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),
+                 ("attention.output.dense.", "self_attn.o_proj."), ("attention.output.LayerNorm.", "post_attention_layernorm."),
+                 ("intermediate.dense.", "mlp.fc1."), ("output.dense.", "mlp.fc2."), ("output.LayerNorm.", "post_mlp_layernorm."))
+        renamed = {}
+        for k, v in state.items():
+            if "position_embeddings" in k:
+                continue
+            k = k.replace("encoder.layer.", "layers.")
+            for a, b in names:
+                k = k.replace(a, b)
+            renamed[k] = v
+        state = renamed
     elif cfg["model_type"] == "nomic_bert":
         names = (("attention.self.query.", "self_attn.q_proj."), ("attention.self.key.", "self_attn.k_proj."), ("attention.self.value.", "self_attn.v_proj."),
                  ("attention.output.dense.", "self_attn.o_proj."), ("attention.output.LayerNorm.", "post_attention_layernorm."),
@@ -222,10 +255,8 @@ def make_decoder(cfg, causal=True, expanded=False):
     import transformers as T
     from kirag_amd.retriever.encoders import HipBertForward, expand_kv
 
-    class Handle(HipBertForward):
-        DECODER_ATTENTION = 1.0 if causal else 0.0
-    conf = {"qwen2": T.Qwen2Config, "llama": T.LlamaConfig, "mistral": T.MistralConfig}[cfg["model_type"]](**{k: cfg[k] for k in DECODER_KEYS})
-    enc = Handle(conf, 0)
+    conf = {"qwen2": T.Qwen2Config, "llama": T.LlamaConfig, "mistral": T.MistralConfig, "eurobert": T.EuroBertConfig}[cfg["model_type"]](**{k: cfg[k] for k in DECODER_KEYS})
+    enc = HipBertForward(conf, 0, decoder_attention=1.0 if causal else 0.0)
     ns = SimpleNamespace(**dict(cfg, max_position_embeddings=8))      # synthetic_state draws a position table of this many rows; it is dropped below
     state = dict(BS.synthetic_state(ns, dev, 0))
     g = torch.Generator(device=dev); g.manual_seed(977)
@@ -276,17 +307,38 @@ def first_forward(shape, cfg, ids, mask):
           flush=True)
 
 
-pool = {"mean": 0, "cls": 1, "last": 5}[args.pool]
-for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
-    cfg = SHAPES[shape]
+def digest(t):
+    import hashlib
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+
+
+def shape_tokens(cfg):
     ids, mask = BS.synthetic_tokens(dev, n, S, seed=1, ragged=ragged)
     if "pad_token_id" in cfg:
         ids = torch.where(mask != 0, ids, torch.full_like(ids, cfg["pad_token_id"]))      # fairseq's rule counts every column that does not hold the pad id
+    return ids, mask
+
+
+pool = {"mean": 0, "cls": 1, "last": 5}[args.pool]
+if __name__ == "__main__" and args.alternate_shapes:
+    # one process, one handle per shape, timed in turns: what separates two shapes is the difference of their medians, the spread is min .. max
+    made = {shape: (make_encoder(SHAPES[shape]),) + shape_tokens(SHAPES[shape]) for shape in args.shape}
+    times = {shape: [] for shape in made}
+    for _ in range(args.reps):
+        for shape, (e, ids, mask) in made.items():
+            times[shape].append(timed(lambda: e.forward(ids, mask, pool), 3) * 1e3)
+    for shape in made:
+        t = sorted(times[shape])
+        print(f"{shape} pool={args.pool} n={n} S={S} ragged={ragged}: median {t[len(t) // 2]:.3f} ms (min {t[0]:.3f}, max {t[-1]:.3f}, {len(t)} rounds of 3 in turns)", flush=True)
+    sys.exit(0)
+for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
+    cfg = SHAPES[shape]
+    ids, mask = shape_tokens(cfg)
     if args.first_forward:
         first_forward(shape, cfg, ids, mask)
         torch.cuda.empty_cache()
         continue
-    if cfg.get("model_type") in ("qwen2", "llama", "mistral") and args.alternate:
+    if cfg.get("model_type") in DECODER_TYPES and args.alternate:
         # one process, two handles of the same weights, timed in turns: what the causal mask saves is the difference
         pair = {"causal": make_decoder(cfg, True), "bidirectional": make_decoder(cfg, False)}
         times = {k: [] for k in pair}
@@ -300,7 +352,7 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
         del pair
         torch.cuda.empty_cache()
         continue
-    if cfg.get("model_type") in ("qwen2", "llama", "mistral") and args.alternate_gqa:
+    if cfg.get("model_type") in DECODER_TYPES and args.alternate_gqa:
         # one process, two handles of the same weights, timed in turns: what the grouped k / v columns save is the difference; the outputs must be the same bits
         pair = {"native": make_decoder(cfg, not args.bidirectional, False), "expanded": make_decoder(cfg, not args.bidirectional, True)}
         outs = {k: e.forward(ids, mask, pool).clone() for k, e in pair.items()}
@@ -318,7 +370,7 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
         continue
     enc = make_encoder(cfg)
     fl = BS.encoder_flops(enc.cfg, mask.sum(1))
-    if cfg.get("model_type") in ("qwen2", "llama", "mistral"):
+    if cfg.get("model_type") in DECODER_TYPES:
         fl = decoder_flops(cfg, mask.sum(1), not args.bidirectional)
     if cfg.get("model_type") == "nomic_bert":      # the third intermediate matrix: + 8 H^2 per token and layer (FF = 4 H)
         fl += float(mask.sum()) * cfg["num_hidden_layers"] * 8.0 * cfg["hidden_size"] ** 2
@@ -331,7 +383,7 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
     print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
           f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
-          f"{fl/dt/PEAK_MFMA_DENSE_16BIT:.3f} of MFMA peak  ({fl/n/1e9:.2f} GFLOP per sequence)", flush=True)
+          f"{fl/dt/PEAK_MFMA_DENSE_16BIT:.3f} of MFMA peak  ({fl/n/1e9:.2f} GFLOP per sequence)" + (f"  sha256 {digest(enc.forward(ids, mask, pool))}" if args.digest else ""), flush=True)
     del enc
     if args.hf_fp16:
         conf_cls, model_cls, _ = hf_classes(cfg)
