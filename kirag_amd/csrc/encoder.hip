@@ -273,7 +273,7 @@ static int& attn_lds_attr(int device) {
     static int attr_lds_dev[64] = {};
     return attr_lds_dev[device & 63];
 }
-
+// (this launch geometry is restated in run_lds of tests/capi/attn_probe.hip, the test-only probe: change both together)
 template <int DH, int HPB, int AM>
 static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W, hipStream_t st) {
     const int H = e->cfg.hidden, heads = e->cfg.heads;
@@ -294,7 +294,7 @@ static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W,
                        e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, e->plan.kv_dim, attn_kv_mul(H / e->plan.kv_dim), ba);
     return 0;
 }
-
+// (this launch geometry is restated in run_dma of tests/capi/attn_probe.hip, the test-only probe: change both together)
 template <int DH, int AM>
 static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
     const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
