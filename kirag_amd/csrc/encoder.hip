@@ -336,6 +336,7 @@ static int with_epilogue(int epi, F&& f) {
 }
 
 static int set_lds_once(const void* kern, int lds, int device);
+// (this launch geometry is restated in run_shape of tests/capi/proj_probe.hip, the test-only probe: change both together)
 template <class Shape, int STAGES, bool NT>
 static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int device, hipStream_t st) {
     constexpr int lds = STAGES * Shape::STAGE_BYTES + Shape::NWAVE * EPI_STAGE_BYTES;   // 160 KiB for the 256x256 tile: the whole LDS of a CU
@@ -378,6 +379,8 @@ static int set_lds_once(const void* kern, int lds, int device) {
 
 // tile shape per launch: when the 256x256 tiling has fewer tiles than ~5/8 of the CUs (small batches: the reference's per_gpu_batch_size 4-8, the KiRAG
 // loop's triple batches, a 1/8 slice of a query batch) the 128x128 tiling gives 4x the parallelism at a quarter of the per-tile latency
+// (the grids, block sizes, LDS bytes, skinny rings and ldx / ldo defaults below are restated in run_epi / run_skinny of tests/capi/proj_probe.hip, the test-only
+// probe: change both together)
 static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const Encoder* e, hipStream_t st) {
     const Knobs& kn = e->kn;
     const int num_cu = e->num_cu, device = e->device;
