@@ -1,81 +1,32 @@
-"""Drop-in for the reference's ``retriever/encoders.py``: ``E5Encoder`` (:61-77, BertModel -> masked mean-pool
--> L2 normalise) and ``BGEEncoder`` (:100-118, BertModel -> [:,0] -> L2 normalise) whose inference forward runs
-in ``libkirag_amd.so`` (hand-written HIP for gfx950: packed tokens, bf16 MFMA projections, fused attention).
+"""Drop-in for the reference's ``retriever/encoders.py``: ``E5Encoder`` (:61-77, BertModel -> masked mean-pool -> L2 normalise) and ``BGEEncoder``
+(:100-118, BertModel -> [:,0] -> L2 normalise) whose inference forward runs in ``libkirag_amd.so`` (hand-written HIP for gfx950).
 
-Both classes still ARE ``transformers.BertModel`` subclasses — ``from_pretrained`` / ``save_pretrained`` /
-``config.hidden_size`` / ``named_parameters()`` / ``.to()`` / ``.eval()`` keep working exactly as the callers
-expect (``retriever/retrievers.py:29,62-69,124-128``).
+Both classes still ARE ``transformers.BertModel`` subclasses — ``from_pretrained`` / ``save_pretrained`` / ``config.hidden_size`` /
+``named_parameters()`` / ``.to()`` / ``.eval()`` keep working exactly as the callers expect (``retriever/retrievers.py:29,62-69,124-128``).
 
 Which path runs:
-  * ``model.eval()`` (every inference caller: ``compute_corpus_embeddings.py:56``, ``retrievers.py:168``,
-    ``e5.py:28``): the HIP path, whether or not ``torch.no_grad()`` is active (``cal_doc_embeddings`` does not
-    use it, ``compute_corpus_embeddings.py:81``).  The output carries no autograd history.  Parameters must be
-    on a GPU; there is NO CPU fallback — a CPU model in eval mode raises.
-  * ``model.train()`` (Aligner fine-tuning, ``trainer/aligner_trainer.py:25-30``): the inherited PyTorch
-    autograd forward, unchanged — backward is outside the hot path.
+  * ``model.eval()`` (every inference caller: ``compute_corpus_embeddings.py:56``, ``retrievers.py:168``, ``e5.py:28``): the HIP path, whether or not
+    ``torch.no_grad()`` is active (``cal_doc_embeddings`` does not use it, ``compute_corpus_embeddings.py:81``).  The output carries no autograd history.
+    Parameters must be on a GPU; there is NO CPU fallback — a CPU model in eval mode raises.
+  * ``model.train()`` (Aligner fine-tuning, ``trainer/aligner_trainer.py:25-30``): the inherited PyTorch autograd forward, unchanged.
 
-RoBERTa-family checkpoints (``model_type`` roberta / xlm-roberta / camembert: multilingual-e5, bge-m3's dense head): the layer stack is BERT's and the
-state-dict names are identical, but the embedding position follows fairseq's rule (``padding_idx + cumsum(ids != padding_idx)``, ``padding_idx`` itself where
-the id is the padding id).  ``XLMRobertaE5Encoder`` / ``XLMRobertaBGEEncoder`` are the twins of the two classes above over ``transformers.XLMRobertaModel``;
-``E5Encoder.from_pretrained`` / ``BGEEncoder.from_pretrained`` read the checkpoint's ``config.json`` first and return the twin for such a checkpoint, so the
-registry names ``E5Retriever`` / ``BGERetriever`` serve both families.
+Other model families run on the same handle.  ``FAMILIES`` (end of this file) has one entry per family, with a sentence on what the family is: its
+``model_type`` strings, its HF base class, whether it has token types, ``describe(config)`` -> what the handle is created with (``HandleSpec``), and the
+E5 / BGE twin pair over that base class.  ``HipBertForward`` creates handles from it, ``E5Encoder.from_pretrained`` / ``BGEEncoder.from_pretrained`` read
+the checkpoint's ``config.json`` first (``checkpoint_model_type``) and return the family's twin, so the registry names ``E5Retriever`` / ``BGERetriever``
+serve every family.  What a family's kernels do not compute is refused from ``config.json`` alone, by field (``check_*_config``).
 
-MPNet checkpoints (``model_type`` mpnet: all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1, paraphrase-mpnet-base-v2): BERT's post-LN stack under other state-dict
-names, no token types, fairseq's position rule with padding index 1, and one learned bias per (head, bucket of the column distance) added to every attention
-score — a table the attention kernels read (``encoder.relative_attention_bias.weight``).  ``MPNetE5Encoder`` / ``MPNetBGEEncoder`` are the twins over
-``transformers.MPNetModel``; ``from_pretrained`` of the two registry classes dispatches to them as well.
-
-NomicBert checkpoints (``model_type`` nomic_bert: nomic-embed-text-v1 / -v1.5 and their fine-tunes): BERT's post-LN stack without a position table — q and k
-of every head are rotated by the token's column (rotary embeddings, NeoX pairing), inside the QKV projection's epilogue — with a gated MLP
-``down(silu(gate(x)) * up(x))`` (gate | up run as one projection whose epilogue writes the product), no linear biases, and state-dict names of its own.  The
-handle learns the frequencies through ``config.rotary_inv_freq`` (HF's ``rotary_emb.inv_freq``, so every static rope variant of HF is covered).
-``NomicBertE5Encoder`` / ``NomicBertBGEEncoder`` are the twins over ``transformers.NomicBertModel``, reached through the same dispatch.
-
-ModernBERT checkpoints (``model_type`` modernbert: gte-modernbert-base, modernbert-embed, granite-embedding-english-r2, ModernBERT fine-tunes): a PRE-LN stack
-— the residual stream is kept apart from the normalised operand — without a position table or token types, rotary q / k with one frequency vector per layer
-type, the gated MLP ``Wo(gelu(input) * gate)`` with input | gate as one projection, and sliding-window attention (``|column distance| <= sliding_window``) in
-the layers ``config.layer_types`` names.  The handle learns all of it through reserved names (``MODERN_SETTINGS``).  An ``intermediate_size`` that is no
-multiple of 128 (ModernBERT-large: 2624) is zero-padded to the next one (``pad_modernbert_ff``: exact).  ``ModernBertE5Encoder`` / ``ModernBertBGEEncoder``
-are the twins over ``transformers.ModernBertModel``.
-
-T5 encoder checkpoints (``model_type`` t5: sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*): ModernBERT's pre-LN schedule with RMS norms
-(``T5LayerNorm``), the embedding row straight into the residual stream, MPNet's bias per (head, bucket of the column distance) — one table, held by block 0,
-added in every layer — on unscaled scores ``q.k + bias``, no linear bias anywhere, and the feed-forward ``wo(relu(wi x))`` (v1.0) or
-``wo(gelu_new(wi_0 x) * wi_1 x)`` (v1.1 / flan).  The handle learns the kind through ``config.t5_feed_forward`` (``T5_SETTING``).  The sentence-transformers
-``Dense`` module of such a checkpoint (a bias-free ``Linear(H -> P)`` between the pooling and the normalisation) is read into ``self.dense`` by
-``from_pretrained`` and runs inside the library (``dense.weight``): the embeddings are then ``[B, P]``.  ``T5E5Encoder`` / ``T5BGEEncoder`` are the twins over
-``transformers.T5EncoderModel``.
-
-bge-m3's token-level heads (``colbert_linear`` / ``sparse_linear`` on BERT / RoBERTa handles): ``POOL_WITH_SPARSE`` / ``POOL_WITH_COLBERT`` ORed onto pool 0 / 1
-make ``HipBertForward.forward`` / ``forward_np`` return ``(dense [B, H], sparse [B, S] or None, colbert [B, S, P] or None)``, three views into the one tensor
-the library wrote (``_layout``); the twins with the heads and the scoring on top of them live in ``kirag_amd.retriever.m3``.
-
-Decoder-LLM embedders (``model_type`` qwen2 / llama / mistral: the Qwen2.5-0.5B family such as KaLM-embedding-multilingual-mini, Llama-3.2-1B, TinyLlama,
-SmolLM2 fine-tunes): T5's schedule (pre-LN, RMS norms, the embedding row straight into the residual stream) with NomicBert's rotary q / k and SwiGLU, optional
-q / k / v biases, CAUSAL attention (``config.decoder_attention`` = 1) and mean or last-token pooling (``POOL_LAST``; ``pooling=`` kwarg, else the checkpoint's
-``1_Pooling/config.json``, else E5 -> mean, BGE -> last).  Grouped-query ``k_proj`` / ``v_proj`` tensors reach the library with their HF shapes
-(``[kv_heads d_h, H]``: the kernels read KV head ``h // group``) whenever ``kv_heads d_h`` is a multiple of 64; any other checkpoint is expanded first
-(``expand_kv``: each KV head's rows repeated ``heads / kv_heads`` times, exact).  ``check_decoder_config`` refuses from ``config.json`` alone what the kernels do not
-compute (128-wide heads among it).
-
-EuroBERT checkpoints (``model_type`` eurobert: EuroBERT-210m / -610m and their fine-tunes): the decoders' stack with a BIDIRECTIONAL mask
-(``config.decoder_attention`` = 0), under the decoders' rules and classes; ``EuroBertE5Encoder`` / ``EuroBertBGEEncoder`` both pool the mean unless told otherwise.
-The Qwen2 / Llama / Mistral twins take the same choice as ``from_pretrained(..., attention="bidirectional")`` (fine-tunes trained without the causal mask).
-
-jina-embeddings-v3 (``model_type`` jina_embeddings_v3, ``transformers.JinaEmbeddingsV3Model``): NomicBert's post-LN rotary stack with linear biases on q / k / v / o
-(q's and k's added before the rotation) and BERT's feed-forward ``fc2(gelu(fc1 x + b1)) + b2`` in place of SwiGLU (``config.rotary_feed_forward`` = 1).
-``check_jina3_config`` refuses from ``config.json`` alone what the kernels do not compute; task LoRA adapters are not applied (merge them into the weights).
-``JinaV3E5Encoder`` / ``JinaV3BGEEncoder`` are the twins.
-
-SPLADE (``POOL_SPLADE`` on a BERT handle that was given ``cls.predictions.*``): the forward returns ``[B, vocab_size]``; the ``BertForMaskedLM`` twin and
-``SpladeModel`` live in ``kirag_amd.retriever.splade``.
+Heads on top of a handle live elsewhere: bge-m3's token-level heads (``POOL_WITH_SPARSE`` / ``POOL_WITH_COLBERT``: the forward returns three views into one
+tensor, ``_layout``) in ``kirag_amd.retriever.m3``, SPLADE (``POOL_SPLADE``) in ``kirag_amd.retriever.splade``, cross-encoders (``POOL_CLASSIFY``) in
+``kirag_amd.retriever.rerankers``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
 import os
-from typing import Optional
+from dataclasses import dataclass
+from typing import Callable, Optional
 
 import torch
 import torch.nn.functional as F
@@ -121,8 +72,6 @@ DEBERTA_TYPE = "deberta-v2"
 DEBERTA_SETTINGS = ("config.deberta_position_buckets", "config.deberta_max_relative_positions")
 DEBERTA_MAX_BUCKETS = 256                    # the library's bound on position_buckets: 512 rows of encoder.rel_embeddings
 DEBERTA_MAX_POS = 8192                       # ... and on max_position_embeddings of such a handle
-# decoder-LLM embedders: model_type -> the HF base model the twins are built over
-DECODER_BASES = {"qwen2": Qwen2Model, "llama": LlamaModel, "mistral": MistralModel, "eurobert": EuroBertModel}
 EUROBERT_TYPE = "eurobert"                       # the decoders' stack whose HF forward is bidirectional: its handles get config.decoder_attention = 0
 DECODER_ATTENTIONS = {"causal": 1.0, "bidirectional": 0.0}       # the ``attention`` kwarg of the decoder twins' from_pretrained -> the setting
 ST_ATTENTION_FILE = "attention.json"             # next to 1_Pooling/config.json (whose keys sentence-transformers' Pooling module takes as arguments): {"attention": ...}
@@ -165,25 +114,87 @@ def pad_modernbert_ff(name: str, w, ff: int, ff_pad: int):
     return out.numpy() if is_np else out
 
 
+# ---- the shape rules of kr_encoder_create and of the rotary tables, written once.  ``refuse(msg)`` raises the family's NotImplementedError ----
+def _refuser(model_type: Optional[str] = None):
+    """``refuse(msg)``: ``NotImplementedError`` beginning ``model_type='<type>':`` (as it is without a type)"""
+    def refuse(msg):
+        raise NotImplementedError(msg if model_type is None else f"model_type={model_type!r}: {msg}")
+    return refuse
+
+
+def check_hidden(refuse, H: int) -> None:
+    if H % 128 or not 0 < H <= 2048:
+        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
+
+
+def check_heads(refuse, H: int, heads: int) -> None:
+    if heads <= 0 or H % heads or H // heads not in (32, 64):
+        refuse(f"num_attention_heads={heads} with hidden_size={H}: the attention kernels are built for heads of width 32 and 64")
+
+
+def check_ff(refuse, ff: int, field: str = "intermediate_size") -> None:
+    if ff <= 0 or ff % 128:
+        refuse(f"{field}={ff}: the projections need a multiple of 128")
+
+
+def check_head_dim(refuse, config, d_h: int) -> None:
+    head_dim = getattr(config, "head_dim", None) or d_h
+    if int(head_dim) != d_h:
+        refuse(f"head_dim={head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+
+
+def check_rotary_shape(refuse, config):
+    """hidden / heads / intermediate of a rotary family (decoders, jina-embeddings-v3), refused in this order: heads that do not divide, ``head_dim``, the
+    head width, ``hidden_size``, ``intermediate_size``.  Returns ``(H, heads, ff, d_h)``."""
+    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
+    if heads <= 0 or H % heads:
+        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
+    d_h = H // heads
+    check_head_dim(refuse, config, d_h)
+    if d_h not in (32, 64):
+        refuse(f"head_dim={d_h} (hidden_size={H} / num_attention_heads={heads}): the attention kernels are built for heads of width 32 and 64")
+    check_hidden(refuse, H)
+    check_ff(refuse, ff)
+    return H, heads, ff, d_h
+
+
+def rope_frequencies(refuse, scaling, inv_freq, label: str, d_h: Optional[int] = None) -> Tensor:
+    """``inv_freq`` of an HF rotary module as the fp32 host tensor the library takes; refused: an ``attention_scaling`` other than 1, and (with ``d_h``) any
+    count of frequencies but ``d_h / 2``.  ``label`` names the rope type inside the message."""
+    if float(scaling) != 1.0:
+        refuse(f"attention_scaling={float(scaling)} ({label}): only rope variants with attention_scaling 1.0 are implemented")
+    inv = inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
+    if d_h is not None and inv.numel() != d_h // 2:
+        refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
+    return inv
+
+
+def _decoder_rope_frequencies(refuse, config, d_h: int) -> Tensor:
+    rope = _decoder_rope(config)
+    return rope_frequencies(refuse, rope.attention_scaling, rope.inv_freq, f"rope_type {getattr(rope, 'rope_type', None)!r}", d_h)
+
+
+def _hf_config(model_type: str, config: dict):
+    """the HF config object of a ``config.json`` dict (HF's defaults fill the rest)"""
+    from transformers import CONFIG_MAPPING
+    return CONFIG_MAPPING[model_type](**{k: v for k, v in config.items() if k not in ("model_type", "transformers_version", "architectures")})
+
+
 def check_deberta_config(config, head: bool = False) -> dict:
     """``NotImplementedError`` beginning ``model_type='deberta-v2':`` and naming the field, for everything of a DeBERTa-v2 / v3 config the kernels do not compute —
     from the config alone: no weight has been read and the library is not loaded.  ``config``: a ``DebertaV2Config`` or the dict of a ``config.json`` (HF's
     defaults fill the rest).  ``head``: also the fields of ``DebertaV2ForSequenceClassification``'s ContextPooler + classifier.  Returns the two settings of the
     handle, ``{"buckets": position_buckets, "max_rel": max_relative_positions}``."""
-    def refuse(msg):
-        raise NotImplementedError(f"model_type={DEBERTA_TYPE!r}: {msg}")
+    refuse = _refuser(DEBERTA_TYPE)
     is_dict = isinstance(config, dict)
     get = (lambda k, d: config.get(k, d)) if is_dict else (lambda k, d: getattr(config, k, d))
     model_type = get("model_type", DEBERTA_TYPE)
     if model_type != DEBERTA_TYPE:
         refuse(f"model_type={model_type!r}: DeBERTa v1 (its own relative-position rule, no shared projections) is not implemented")
     H, heads, ff = int(get("hidden_size", 1536)), int(get("num_attention_heads", 24)), int(get("intermediate_size", 6144))
-    if H % 128 or not 0 < H <= 2048:
-        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
-    if heads <= 0 or H % heads or H // heads not in (32, 64):
-        refuse(f"num_attention_heads={heads} with hidden_size={H}: the attention kernels are built for heads of width 32 and 64")
-    if ff <= 0 or ff % 128:
-        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
+    check_hidden(refuse, H)
+    check_heads(refuse, H, heads)
+    check_ff(refuse, ff)
     max_pos = int(get("max_position_embeddings", 512))
     if not 0 < max_pos <= DEBERTA_MAX_POS:
         refuse(f"max_position_embeddings={max_pos}: a DeBERTa handle takes at most {DEBERTA_MAX_POS}")
@@ -237,33 +248,12 @@ def check_jina3_config(config) -> dict:
     compute — from the config alone: no weight has been read and the library is not loaded.  ``config``: the HF config or the dict of a ``config.json`` (HF's
     defaults fill the rest).  Returns ``max_pos`` = min(max_position_embeddings, 8192) and ``inv_freq`` from HF's own rotary module."""
     if isinstance(config, dict):
-        from transformers import CONFIG_MAPPING
-        config = CONFIG_MAPPING[JINA3_TYPE](**{k: v for k, v in config.items() if k not in ("model_type", "transformers_version", "architectures")})
-
-    def refuse(msg):
-        raise NotImplementedError(f"model_type={JINA3_TYPE!r}: {msg}")
-    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
-    if heads <= 0 or H % heads:
-        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
-    d_h = H // heads
-    head_dim = getattr(config, "head_dim", None) or d_h
-    if int(head_dim) != d_h:
-        refuse(f"head_dim={head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
-    if d_h not in (32, 64):
-        refuse(f"head_dim={d_h} (hidden_size={H} / num_attention_heads={heads}): the attention kernels are built for heads of width 32 and 64")
-    if H % 128 or not 0 < H <= 2048:
-        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
-    if ff <= 0 or ff % 128:
-        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
+        config = _hf_config(JINA3_TYPE, config)
+    refuse = _refuser(JINA3_TYPE)
+    _, _, _, d_h = check_rotary_shape(refuse, config)
     if getattr(config, "hidden_act", "gelu") != "gelu":
         refuse(f"hidden_act={config.hidden_act!r}: the feed-forward of a {JINA3_TYPE} handle implements erf-GELU only")
-    rope = _decoder_rope(config)
-    if float(rope.attention_scaling) != 1.0:
-        refuse(f"attention_scaling={float(rope.attention_scaling)} (rope_type {getattr(rope, 'rope_type', None)!r}): only rope variants with attention_scaling 1.0 are implemented")
-    inv = rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
-    if inv.numel() != d_h // 2:
-        refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
-    return {"max_pos": min(int(config.max_position_embeddings), JINA3_MAX_POS), "inv_freq": inv}
+    return {"max_pos": min(int(config.max_position_embeddings), JINA3_MAX_POS), "inv_freq": _decoder_rope_frequencies(refuse, config, d_h)}
 
 
 def check_decoder_config(config) -> dict:
@@ -272,32 +262,14 @@ def check_decoder_config(config) -> dict:
     defaults fill the rest).  Returns what the handle is created with: hidden, layers, heads, kv_heads, intermediate, ``max_pos`` =
     min(max_position_embeddings, 8192), ``ln_eps`` = rms_norm_eps, and ``inv_freq`` from HF's own rotary module (so static rope variants such as ``llama3`` are
     covered)."""
-    if isinstance(config, dict):
-        from transformers import CONFIG_MAPPING
-        mt = config.get("model_type")
-        if mt not in DECODER_BASES:
-            raise NotImplementedError(f"model_type={mt!r}: the decoder path is built for {sorted(DECODER_BASES)}")
-        config = CONFIG_MAPPING[mt](**{k: v for k, v in config.items() if k not in ("model_type", "transformers_version", "architectures")})
-    mt = config.model_type
-
-    def refuse(msg):
-        raise NotImplementedError(f"model_type={mt!r}: {msg}")
+    mt = config.get("model_type") if isinstance(config, dict) else config.model_type
+    refuse = _refuser(mt)
     if mt not in DECODER_BASES:
         refuse(f"the decoder path is built for {sorted(DECODER_BASES)}")
-    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
+    if isinstance(config, dict):
+        config = _hf_config(mt, config)
+    H, heads, ff, d_h = check_rotary_shape(refuse, config)
     kv = int(getattr(config, "num_key_value_heads", None) or heads)
-    if heads <= 0 or H % heads:
-        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
-    d_h = H // heads
-    head_dim = getattr(config, "head_dim", None) or d_h
-    if int(head_dim) != d_h:
-        refuse(f"head_dim={head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
-    if d_h not in (32, 64):
-        refuse(f"head_dim={d_h} (hidden_size={H} / num_attention_heads={heads}): the attention kernels are built for heads of width 32 and 64")
-    if H % 128 or not 0 < H <= 2048:
-        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of 128 up to 2048")
-    if ff <= 0 or ff % 128:
-        refuse(f"intermediate_size={ff}: the projections need a multiple of 128")
     if getattr(config, "hidden_act", "silu") != "silu":
         refuse(f"hidden_act={config.hidden_act!r}: the gated MLP of a decoder handle implements silu only")
     if kv <= 0 or heads % kv:
@@ -315,14 +287,9 @@ def check_decoder_config(config) -> dict:
     types = list(getattr(config, "layer_types", None) or [])
     if any(t != "full_attention" for t in types):
         refuse(f"layer_types={types!r}: full_attention layers only")
-    rope = _decoder_rope(config)
-    if float(rope.attention_scaling) != 1.0:
-        refuse(f"attention_scaling={float(rope.attention_scaling)} (rope_type {getattr(rope, 'rope_type', None)!r}): only rope variants with attention_scaling 1.0 are implemented")
-    inv = rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
-    if inv.numel() != d_h // 2:
-        refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
     return {"hidden": H, "layers": int(config.num_hidden_layers), "heads": heads, "kv_heads": kv, "intermediate": ff, "max_pos": max_pos,
-            "ln_eps": float(config.rms_norm_eps), "inv_freq": inv}
+            "ln_eps": float(config.rms_norm_eps), "inv_freq": _decoder_rope_frequencies(refuse, config, d_h)}
+
 
 
 def _decoder_rope(config):
@@ -375,10 +342,139 @@ def read_st_pooling(where, **kwargs) -> Optional[str]:
     return known[on[0]]
 
 
+def _setting(value) -> Tensor:
+    """one number as the fp32 host tensor a reserved-name setting travels as"""
+    return torch.tensor([float(value)], dtype=torch.float32)
+
+
+@dataclass(frozen=True)
+class HandleSpec:
+    """What a handle of one config is created with"""
+    cfg: tuple                                   # the eight kr_bert_cfg values: hidden, layers, heads, intermediate, vocab, max_pos, type_vocab, ln_eps
+    ff: int                                      # the checkpoint's intermediate size ...
+    ff_pad: int                                  # ... and the handle's (ModernBERT: the next multiple of 128, ``pad_modernbert_ff``)
+    settings: tuple = ()                         # ((reserved name, fp32 host tensor), ...) in the order they are loaded, before the first finalize
+    heads: int = 0                               # decoders: query heads and KV heads, for ``kv_for_library``
+    kv_heads: int = 0
+    position_padding_idx: Optional[int] = None   # fairseq's position rule with this padding index; None = BERT's (embedding position = column)
+
+
+@dataclass(frozen=True)
+class Family:
+    """One model family: everything the Python side knows about it (``FAMILIES``, end of this file)"""
+    model_types: tuple                           # the ``model_type`` strings it answers to
+    hf_base: type                                # the HF class the twins are built over
+    describe: Callable                           # config -> HandleSpec; refuses, by field, what the kernels do not compute
+    twins: tuple                                 # (the E5 class, the BGE class) over ``hf_base``
+    token_types: bool = False                    # the checkpoint has a token-type table (and HF's forward takes ``token_type_ids``)
+    flag: Optional[str] = None                   # the ``is_*`` attribute of its handles
+    check: Optional[Callable] = None             # config or config.json dict -> refusal from the config alone, run by the dispatch before a weight is read
+    decoder_attention: Optional[float] = None    # decoders: the family's own mask setting (EuroBERT: 0.0), None = the handle's default
+
+    def twin(self, pool: int):
+        """the E5 twin for a mean-pooling registry class, the BGE twin for any other"""
+        return self.twins[0 if pool == POOL_MEAN else 1]
+
+
+def family_of(model_type: str) -> "Family":
+    """the family of a ``model_type``; anything unknown is treated as BERT, as ``BertModel.from_pretrained`` would"""
+    return FAMILIES.get(model_type, FAMILIES["bert"])
+
+
+def _bert_cfg(config, ff: int, type_vocab: int, eps: float, max_pos=None) -> tuple:
+    return (config.hidden_size, config.num_hidden_layers, config.num_attention_heads, ff, config.vocab_size,
+            config.max_position_embeddings if max_pos is None else max_pos, type_vocab, eps)
+
+
+def _check_bert_like(config, gelu: bool = True) -> None:
+    """what every handle checks after its family's own rules"""
+    if gelu and getattr(config, "hidden_act", "gelu") != "gelu":
+        raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
+    if getattr(config, "position_embedding_type", "absolute") != "absolute":
+        raise NotImplementedError("only absolute position embeddings are implemented")
+
+
+def describe_bert(config) -> HandleSpec:
+    _check_bert_like(config)
+    ff = int(config.intermediate_size)
+    return HandleSpec(_bert_cfg(config, ff, config.type_vocab_size, float(config.layer_norm_eps)), ff, ff)
+
+
+def _fairseq_positions(config, P, type_vocab: int) -> HandleSpec:
+    if P is None:
+        raise ValueError(f"model_type={config.model_type!r} needs config.pad_token_id (the padding index of fairseq's position rule)")
+    ff = int(config.intermediate_size)
+    return HandleSpec(_bert_cfg(config, ff, type_vocab, float(config.layer_norm_eps)), ff, ff, (("config.position_padding_idx", _setting(P)),),
+                      position_padding_idx=int(P))
+
+
+def describe_roberta(config) -> HandleSpec:
+    _check_bert_like(config)
+    return _fairseq_positions(config, getattr(config, "pad_token_id", None), config.type_vocab_size)
+
+
+def describe_mpnet(config) -> HandleSpec:
+    _check_bert_like(config)
+    if getattr(config, "relative_attention_num_buckets", MPNET_BUCKETS) != MPNET_BUCKETS:
+        raise ValueError(f"relative_attention_num_buckets={config.relative_attention_num_buckets}: MPNet's bias table has {MPNET_BUCKETS} buckets "
+                         "(the only size HF's MPNetEncoder computes with)")
+    return _fairseq_positions(config, MPNET_PADDING_IDX, 1)
+
+
+def describe_nomic(config) -> HandleSpec:
+    inv_freq = HipBertForward._nomic_inv_freq(config)      # looked up here, not at import: a test replaces it
+    _check_bert_like(config, gelu=False)
+    ff = int(config.intermediate_size)
+    return HandleSpec(_bert_cfg(config, ff, config.type_vocab_size, float(config.layer_norm_eps)), ff, ff, (("config.rotary_inv_freq", inv_freq),))
+
+
+def describe_modern(config) -> HandleSpec:
+    settings = HipBertForward._modern_settings(config)
+    _check_bert_like(config, gelu=False)
+    ff = int(config.intermediate_size)
+    ff_pad = -(-ff // 128) * 128
+    return HandleSpec(_bert_cfg(config, ff_pad, 1, float(config.norm_eps)), ff, ff_pad, tuple(settings.items()))
+
+
+def describe_t5(config) -> HandleSpec:
+    t5 = HipBertForward._t5_settings(config)
+    _check_bert_like(config, gelu=False)
+    ff = t5["intermediate"]
+    return HandleSpec((t5["hidden"], t5["layers"], t5["heads"], ff, config.vocab_size, t5["max_pos"], 1, t5["ln_eps"]), ff, ff,
+                      ((T5_SETTING, _setting(t5["feed_forward"])),))
+
+
+def describe_deberta(config) -> HandleSpec:
+    deberta = check_deberta_config(config)
+    _check_bert_like(config)
+    ff = int(config.intermediate_size)
+    return HandleSpec(_bert_cfg(config, ff, 1, float(config.layer_norm_eps)), ff, ff,
+                      tuple((name, _setting(deberta[k])) for name, k in zip(DEBERTA_SETTINGS, ("buckets", "max_rel"))))
+
+
+def describe_decoder(config) -> HandleSpec:
+    """HF's own frequencies; the handle adds the mask setting behind them (``HipBertForward.__init__``)"""
+    d = check_decoder_config(config)
+    _check_bert_like(config, gelu=False)
+    ff = int(config.intermediate_size)
+    return HandleSpec((d["hidden"], d["layers"], d["heads"], ff, config.vocab_size, d["max_pos"], 1, d["ln_eps"]), ff, ff,
+                      (("config.rotary_inv_freq", d["inv_freq"]),), heads=d["heads"], kv_heads=d["kv_heads"])
+
+
+def describe_jina3(config) -> HandleSpec:
+    """HF's own frequencies, then the feed-forward kind that makes a rotary post-LN handle a jina-embeddings-v3 one"""
+    jina3 = check_jina3_config(config)
+    _check_bert_like(config)
+    ff = int(config.intermediate_size)
+    return HandleSpec(_bert_cfg(config, ff, config.type_vocab_size, float(config.layer_norm_eps), jina3["max_pos"]), ff, ff,
+                      (("config.rotary_inv_freq", jina3["inv_freq"]), (ROTARY_FF_SETTING, _setting(1.0))))
+
+
 class HipBertForward:
     """Owns a ``kr_encoder`` handle and keeps its weight copy in sync with an ``nn.Module``'s parameters."""
 
-    DECODER_ATTENTION = 1.0          # what a decoder handle's "config.decoder_attention" is given unless ``decoder_attention`` says otherwise: causal
+    DECODER_ATTENTION = 1.0          # what a decoder handle's "config.decoder_attention" is given unless ``decoder_attention`` or its family says otherwise: causal
+    FLAGS = ("is_nomic", "is_modern", "is_t5", "is_deberta", "is_decoder", "is_jina3", "is_mpnet")
 
     def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None,
                  decoder_attention: Optional[float] = None):
@@ -388,56 +484,24 @@ class HipBertForward:
         task model's ``bert.`` / ``roberta.`` prefix and BERT's spelling of the classification head: ``kirag_amd.retriever.rerankers``).
         ``extra``: optional callable, module -> [(library name, tensor)] that ``sync`` sends besides ``named_parameters()`` unless a parameter already has
         that name (a TIED parameter appears once in ``named_parameters()``; the library wants it under both names: ``kirag_amd.retriever.splade``).
-        ``decoder_attention``: 1.0 / 0.0 = the causal / bidirectional mask of a decoder handle; ``None`` = bidirectional for ``model_type`` eurobert (HF's
-        EuroBertModel has no causal mask), else ``DECODER_ATTENTION``."""
+        ``decoder_attention``: 1.0 / 0.0 = the causal / bidirectional mask of a decoder handle; ``None`` = the family's (bidirectional for ``model_type``
+        eurobert: HF's EuroBertModel has no causal mask), else ``DECODER_ATTENTION``."""
         lib = _lib.load()
         self.rename = rename
         self.extra = extra
         self.colbert_dim = 0              # rows of "colbert_linear.weight" once the library has accepted it: the width of a token vector
         self.num_labels = 0               # rows of "classifier.out_proj.weight" once the library has accepted it: the width of a POOL_CLASSIFY forward
-        self.is_nomic = getattr(config, "model_type", "bert") == NOMIC_TYPE
-        self.is_modern = getattr(config, "model_type", "bert") == MODERN_TYPE
-        self.is_t5 = getattr(config, "model_type", "bert") == T5_TYPE
-        self.is_deberta = getattr(config, "model_type", "bert") in (DEBERTA_TYPE, "deberta")
-        self.is_decoder = getattr(config, "model_type", "bert") in DECODER_BASES
-        self.is_jina3 = getattr(config, "model_type", "bert") == JINA3_TYPE
-        decoder = check_decoder_config(config) if self.is_decoder else None     # refuses what the kernels do not compute, before a handle exists
-        jina3 = check_jina3_config(config) if self.is_jina3 else None           # likewise
-        if decoder_attention is None:
-            decoder_attention = 0.0 if getattr(config, "model_type", "bert") == EUROBERT_TYPE else self.DECODER_ATTENTION
-        self.decoder_attention = float(decoder_attention) if self.is_decoder else None
-        self.heads, self.kv_heads = (decoder["heads"], decoder["kv_heads"]) if decoder else (0, 0)
-        deberta = check_deberta_config(config) if self.is_deberta else None     # refuses what the kernels do not compute, before a handle exists
-        inv_freq = self._nomic_inv_freq(config) if self.is_nomic else None      # refuses what the kernels do not compute, before a handle exists
-        modern = self._modern_settings(config) if self.is_modern else None      # likewise
-        t5 = self._t5_settings(config) if self.is_t5 else None                  # likewise
-        if not self.is_nomic and not self.is_modern and not self.is_t5 and not self.is_decoder and getattr(config, "hidden_act", "gelu") != "gelu":
-            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the HIP encoder implements erf-GELU only (and silu for model_type {NOMIC_TYPE!r})")
-        if getattr(config, "position_embedding_type", "absolute") != "absolute":
-            raise NotImplementedError("only absolute position embeddings are implemented")
-        self.is_mpnet = getattr(config, "model_type", "bert") == MPNET_TYPE
-        if self.is_mpnet and getattr(config, "relative_attention_num_buckets", MPNET_BUCKETS) != MPNET_BUCKETS:
-            raise ValueError(f"relative_attention_num_buckets={config.relative_attention_num_buckets}: MPNet's bias table has {MPNET_BUCKETS} buckets "
-                             "(the only size HF's MPNetEncoder computes with)")
-        # MPNet has no token types: one row of zeros stands in for the table (sync supplies it)
-        # ... and neither has ModernBERT; its intermediate size is rounded up to the projections' 128 (pad_modernbert_ff)
-        # ... and T5 has neither token types nor positions: kr_bert_cfg comes from T5Config's own fields (_t5_settings)
-        # ... and DeBERTa-v2 / v3 has neither token types nor a position table (both are optional on its handles)
-        # ... and a decoder has neither; kr_bert_cfg comes from check_decoder_config (max_pos capped at the rotary tables' 8192)
-        type_vocab = 1 if self.is_mpnet or self.is_modern or self.is_t5 or self.is_deberta or self.is_decoder else config.type_vocab_size
-        self.ff = int(t5["intermediate"] if self.is_t5 else config.intermediate_size)
-        self.ff_pad = -(-self.ff // 128) * 128 if self.is_modern else self.ff
-        if self.is_t5:
-            cfg = _lib.BertCfg(t5["hidden"], t5["layers"], t5["heads"], self.ff, config.vocab_size, t5["max_pos"], type_vocab, t5["ln_eps"])
-        elif self.is_jina3:      # max_pos capped at the rotary tables' 8192: it only bounds the sequence length
-            cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff, config.vocab_size, jina3["max_pos"],
-                               config.type_vocab_size, float(config.layer_norm_eps))
-        elif self.is_decoder:
-            cfg = _lib.BertCfg(decoder["hidden"], decoder["layers"], decoder["heads"], self.ff, config.vocab_size, decoder["max_pos"], type_vocab, decoder["ln_eps"])
-        else:
-            eps = float(config.norm_eps if self.is_modern else config.layer_norm_eps)
-            cfg = _lib.BertCfg(config.hidden_size, config.num_hidden_layers, config.num_attention_heads, self.ff_pad,
-                               config.vocab_size, config.max_position_embeddings, type_vocab, eps)
+        family = family_of(getattr(config, "model_type", "bert"))
+        spec = family.describe(config)    # refuses what the kernels do not compute, before a handle exists
+        self.__dict__.update({flag: flag == family.flag for flag in self.FLAGS})
+        settings = list(spec.settings)
+        self.decoder_attention = None
+        if self.is_decoder:               # the setting that makes a handle a decoder's, after HF's own frequencies
+            mask = decoder_attention if decoder_attention is not None else family.decoder_attention if family.decoder_attention is not None else self.DECODER_ATTENTION
+            self.decoder_attention = float(mask)
+            settings.append((DECODER_SETTING, _setting(self.decoder_attention)))
+        self.ff, self.ff_pad, self.heads, self.kv_heads = spec.ff, spec.ff_pad, spec.heads, spec.kv_heads
+        cfg = _lib.BertCfg(*spec.cfg)
         h = C.c_void_p()
         dt = -1 if operand_dtype is None else {"bf16": 0, "f16": 1}[operand_dtype]
         lo = -1 if residual_lo is None else int(bool(residual_lo))
@@ -445,71 +509,36 @@ class HipBertForward:
         self._lib, self._h, self.device_index = lib, h, device_index
         self.operand_dtype = ("bf16", "f16")[lib.kr_encoder_operand_dtype(h)]
         self.residual_lo = bool(lib.kr_encoder_residual_lo(h))
-        self.hidden = t5["hidden"] if self.is_t5 else config.hidden_size
-        self.vocab = int(config.vocab_size)      # the width of a POOL_SPLADE forward
+        self.hidden, self.vocab = int(cfg.hidden), int(cfg.vocab)      # vocab: the width of a POOL_SPLADE forward
         self.out_dim = self.hidden        # width of the embeddings: P once a Dense head ("dense.weight" [P, hidden], T5 handles) has been loaded
         self.fingerprint = None
-        # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P.  It travels through the
-        # name-addressed loader under the reserved name "config.position_padding_idx", before the first finalize, and holds for the handle's life
-        self.position_padding_idx = None
-        if self.is_mpnet or getattr(config, "model_type", "bert") in ROBERTA_TYPES:
-            P = MPNET_PADDING_IDX if self.is_mpnet else getattr(config, "pad_token_id", None)
-            if P is None:
-                raise ValueError(f"model_type={config.model_type!r} needs config.pad_token_id (the padding index of fairseq's position rule)")
-            v = C.c_float(float(P))
-            _lib.check(lib.kr_encoder_load_weight(h, b"config.position_padding_idx", C.addressof(v), 1))
-            self.position_padding_idx = int(P)
-        # rotary positions travel the same way ("config.rotary_inv_freq", d_h / 2 values) and make the handle a NomicBert handle for life
-        if inv_freq is not None:
-            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", inv_freq.data_ptr(), inv_freq.numel()))
-        # a ModernBert handle: the global frequencies under the same name, then its own three settings
-        if modern is not None:
-            for name, t in modern.items():
-                _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
-
-        # a decoder handle: HF's own frequencies, then the setting that makes it one (1 = causal)
-        if decoder is not None:
-            f = decoder["inv_freq"]
-            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", f.data_ptr(), f.numel()))
-            v = C.c_float(self.decoder_attention)
-            _lib.check(lib.kr_encoder_load_weight(h, DECODER_SETTING.encode(), C.addressof(v), 1))
-        # a rotary BERT handle (jina-embeddings-v3): HF's own frequencies, then the feed-forward kind that makes it one
-        if jina3 is not None:
-            f = jina3["inv_freq"]
-            _lib.check(lib.kr_encoder_load_weight(h, b"config.rotary_inv_freq", f.data_ptr(), f.numel()))
-            v = C.c_float(1.0)
-            _lib.check(lib.kr_encoder_load_weight(h, ROTARY_FF_SETTING.encode(), C.addressof(v), 1))
-        # a DeBERTa handle: the two numbers of its bucket rule
-        if deberta is not None:
-            for name, val in zip(DEBERTA_SETTINGS, (deberta["buckets"], deberta["max_rel"])):
-                v = C.c_float(float(val))
-                _lib.check(lib.kr_encoder_load_weight(h, name.encode(), C.addressof(v), 1))
-        # a T5 handle: its feed-forward kind
-        if t5 is not None:
-            v = C.c_float(t5["feed_forward"])
-            _lib.check(lib.kr_encoder_load_weight(h, T5_SETTING.encode(), C.addressof(v), 1))
+        # the position rule of the handle: None = BERT's (embedding position = column), P = fairseq's with padding index P
+        self.position_padding_idx = spec.position_padding_idx
+        # settings travel through the name-addressed loader under reserved names, before the first finalize, and hold for the handle's life
+        for name, t in settings:
+            _lib.check(lib.kr_encoder_load_weight(h, name.encode(), t.data_ptr(), t.numel()))
 
     @staticmethod
     def _t5_settings(config) -> dict:
         """``kr_bert_cfg`` and the feed-forward setting of a T5 handle from an HF ``T5Config``; ``NotImplementedError`` naming the field for what the kernels do
         not compute.  ``max_pos`` only bounds the sequence length (no table is sized by it)."""
+        refuse = _refuser()
         d_model, d_kv, heads = int(config.d_model), int(config.d_kv), int(config.num_heads)
         if d_kv * heads != d_model:
-            raise NotImplementedError(f"d_kv={d_kv} x num_heads={heads} != d_model={d_model}: the HIP encoder needs an inner width equal to d_model")
+            refuse(f"d_kv={d_kv} x num_heads={heads} != d_model={d_model}: the HIP encoder needs an inner width equal to d_model")
         if d_kv not in (32, 64):
-            raise NotImplementedError(f"d_kv={d_kv}: the attention kernels are built for heads of width 32 and 64")
+            refuse(f"d_kv={d_kv}: the attention kernels are built for heads of width 32 and 64")
         buckets = getattr(config, "relative_attention_num_buckets", T5_BUCKETS)
         if buckets != T5_BUCKETS:
-            raise NotImplementedError(f"relative_attention_num_buckets={buckets}: the attention kernels compute {T5_BUCKETS} buckets")
+            refuse(f"relative_attention_num_buckets={buckets}: the attention kernels compute {T5_BUCKETS} buckets")
         max_distance = getattr(config, "relative_attention_max_distance", T5_MAX_DISTANCE)
         if max_distance != T5_MAX_DISTANCE:
-            raise NotImplementedError(f"relative_attention_max_distance={max_distance}: the attention kernels compute max_distance {T5_MAX_DISTANCE}")
+            refuse(f"relative_attention_max_distance={max_distance}: the attention kernels compute max_distance {T5_MAX_DISTANCE}")
         kind = (getattr(config, "dense_act_fn", "relu"), bool(getattr(config, "is_gated_act", False)))
         if kind not in T5_FEED_FORWARDS:
-            raise NotImplementedError(f"dense_act_fn={kind[0]!r} with is_gated_act={kind[1]} (feed_forward_proj={getattr(config, 'feed_forward_proj', None)!r}): "
-                                      "relu and gated gelu_new are implemented")
-        if int(config.d_ff) % 128:
-            raise NotImplementedError(f"d_ff={config.d_ff}: the projections need a multiple of 128")
+            refuse(f"dense_act_fn={kind[0]!r} with is_gated_act={kind[1]} (feed_forward_proj={getattr(config, 'feed_forward_proj', None)!r}): "
+                   "relu and gated gelu_new are implemented")
+        check_ff(refuse, int(config.d_ff), "d_ff")
         return {"hidden": d_model, "layers": int(config.num_layers), "heads": heads, "intermediate": int(config.d_ff),
                 "max_pos": int(getattr(config, "n_positions", None) or 512), "ln_eps": float(config.layer_norm_epsilon), "feed_forward": T5_FEED_FORWARDS[kind]}
 
@@ -519,30 +548,24 @@ class HipBertForward:
         ``ModernBertRotaryEmbedding`` built on the CPU, the half-window (``config.sliding_window`` = ``local_attention // 2``, inclusive) and one flag per layer
         (1 = ``sliding_attention``).  ``NotImplementedError`` naming the field for what the kernels do not compute."""
         from transformers.models.modernbert.modeling_modernbert import ModernBertRotaryEmbedding
+        refuse = _refuser()
         if getattr(config, "hidden_activation", "gelu") != "gelu":
-            raise NotImplementedError(f"hidden_activation={config.hidden_activation!r}: the gated MLP of a {MODERN_TYPE} handle implements erf-GELU only")
-        d_h = config.hidden_size // config.num_attention_heads
-        if (getattr(config, "head_dim", None) or d_h) != d_h:
-            raise NotImplementedError(f"head_dim={config.head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+            refuse(f"hidden_activation={config.hidden_activation!r}: the gated MLP of a {MODERN_TYPE} handle implements erf-GELU only")
+        check_head_dim(refuse, config, config.hidden_size // config.num_attention_heads)
         types = list(config.layer_types)
         unknown = sorted(set(types) - set(MODERN_LAYER_TYPES))
         if unknown or len(types) != config.num_hidden_layers:
-            raise NotImplementedError(f"layer_types={types!r}: one of {MODERN_LAYER_TYPES} per layer is implemented")
+            refuse(f"layer_types={types!r}: one of {MODERN_LAYER_TYPES} per layer is implemented")
         rope = ModernBertRotaryEmbedding(config)
-        freq = {}
-        for t in set(types):
-            scaling = float(getattr(rope, f"{t}_attention_scaling"))
-            if scaling != 1.0:
-                raise NotImplementedError(f"attention_scaling={scaling} ({t}, rope_type {rope.rope_type[t]!r}): only rope variants with attention_scaling 1.0 "
-                                          "are implemented")
-            freq[t] = getattr(rope, f"{t}_inv_freq").detach().to(device="cpu", dtype=torch.float32).contiguous()
+        freq = {t: rope_frequencies(refuse, getattr(rope, f"{t}_attention_scaling"), getattr(rope, f"{t}_inv_freq"), f"{t}, rope_type {rope.rope_type[t]!r}")
+                for t in set(types)}
         out = {"config.rotary_inv_freq": freq.get("full_attention", freq.get("sliding_attention"))}
         if "sliding_attention" in freq:
             w = int(config.sliding_window)
             if w < 1:
-                raise NotImplementedError(f"local_attention={config.local_attention}: the half-window local_attention // 2 must be at least 1")
+                refuse(f"local_attention={config.local_attention}: the half-window local_attention // 2 must be at least 1")
             out[MODERN_SETTINGS[0]] = freq["sliding_attention"]
-            out[MODERN_SETTINGS[1]] = torch.tensor([float(w)], dtype=torch.float32)
+            out[MODERN_SETTINGS[1]] = _setting(w)
         out[MODERN_SETTINGS[2]] = torch.tensor([1.0 if t == "sliding_attention" else 0.0 for t in types], dtype=torch.float32)
         return out
 
@@ -551,16 +574,12 @@ class HipBertForward:
         """``rotary_emb.inv_freq`` of a NomicBert config, from HF's own ``NomicBertRotaryEmbedding`` built on the CPU (whatever static rope type the config
         names); ``NotImplementedError`` naming the field for what the kernels do not compute."""
         from transformers.models.nomic_bert.modeling_nomic_bert import NomicBertRotaryEmbedding
+        refuse = _refuser()
         if getattr(config, "hidden_act", "silu") != "silu":
-            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the gated MLP of a {NOMIC_TYPE} handle implements silu only")
-        d_h = config.hidden_size // config.num_attention_heads
-        if (getattr(config, "head_dim", None) or d_h) != d_h:
-            raise NotImplementedError(f"head_dim={config.head_dim}: the HIP encoder needs head_dim == hidden_size / num_attention_heads = {d_h}")
+            refuse(f"hidden_act={config.hidden_act!r}: the gated MLP of a {NOMIC_TYPE} handle implements silu only")
+        check_head_dim(refuse, config, config.hidden_size // config.num_attention_heads)
         rope = NomicBertRotaryEmbedding(config)
-        if float(rope.attention_scaling) != 1.0:
-            raise NotImplementedError(f"attention_scaling={float(rope.attention_scaling)} (rope_type {rope.rope_type!r}): only rope variants with attention_scaling 1.0 "
-                                      "are implemented")
-        return rope.inv_freq.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        return rope_frequencies(refuse, rope.attention_scaling, rope.inv_freq, f"rope_type {rope.rope_type!r}")
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -609,9 +628,7 @@ class HipBertForward:
         if fp == self.fingerprint:
             return
         for name, p in params:
-            t = pad_modernbert_ff(name, p.detach(), self.ff, self.ff_pad)
-            if self.is_decoder:
-                t = kv_for_library(name, t, self.heads, self.kv_heads, self.hidden)
+            t = self._for_library(name, p.detach())
             if t.dtype != torch.float32 or not t.is_contiguous():
                 t = t.float().contiguous()
             _lib.check(self._lib.kr_encoder_load_weight(self._h, name.encode(), t.data_ptr(), t.numel()))
@@ -619,6 +636,11 @@ class HipBertForward:
         self._load_zero_token_types()
         _lib.check(self._lib.kr_encoder_finalize(self._h))
         self.fingerprint = fp
+
+    def _for_library(self, name: str, w):
+        """a checkpoint tensor as the library takes it: ModernBERT's MLP padded to ``ff_pad``, a decoder's k / v projections native or expanded"""
+        w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
+        return kv_for_library(name, w, self.heads, self.kv_heads, self.hidden) if self.is_decoder else w
 
     def _note_dense(self, name: str, numel: int) -> None:
         """``dense.weight`` [P, hidden] was accepted by the library: the forwards now write [B, P]; ``classifier.out_proj.weight`` [L, hidden]: a
@@ -673,7 +695,7 @@ class HipBertForward:
         return dense, sparse, colbert
 
     def _load_zero_token_types(self) -> None:
-        if self.is_mpnet or self.is_modern:
+        if self.is_mpnet or self.is_modern:      # no token types in the checkpoint: one row of zeros stands in for the table
             z = torch.zeros(self.hidden, dtype=torch.float32)
             _lib.check(self._lib.kr_encoder_load_weight(self._h, b"embeddings.token_type_embeddings.weight", z.data_ptr(), z.numel()))
 
@@ -683,9 +705,7 @@ class HipBertForward:
         for name, w in state.items():
             if self.rename is not None:
                 name = self.rename(name)
-            w = pad_modernbert_ff(name, w, self.ff, self.ff_pad)
-            if self.is_decoder:
-                w = kv_for_library(name, w, self.heads, self.kv_heads, self.hidden)
+            w = self._for_library(name, w)
             if isinstance(w, np.ndarray):
                 w = np.ascontiguousarray(w, dtype=np.float32)
                 ptr, n = w.ctypes.data, w.size
@@ -870,7 +890,7 @@ class _HipSentenceMixin(_HipModuleMixin):
         return self._synced_hip().forward_packed(token_ids, seq_lens, max_len, self._pool, total_tokens)
 
     def _torch_pooled(self, input_ids, attention_mask, token_type_ids):
-        kw = {} if self._hf_base in (MPNetModel, ModernBertModel, T5EncoderModel, DebertaV2Model) + tuple(DECODER_BASES.values()) else {"token_type_ids": token_type_ids}     # MPNet, ModernBERT, T5 and DeBERTa-v3 have no token types
+        kw = {"token_type_ids": token_type_ids} if family_of(self.config.model_type).token_types else {}
         out = self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, return_dict=True, **kw)
         return out.last_hidden_state
 
@@ -904,55 +924,34 @@ class _HipSentenceMixin(_HipModuleMixin):
 _CONFIG_KWARGS = ("cache_dir", "force_download", "local_files_only", "token", "revision", "subfolder", "proxies", "trust_remote_code")
 
 
+def checkpoint_model_type(pretrained_model_name_or_path, kwargs: dict, default: Optional[str] = "bert"):
+    """``(model_type, config)`` of the checkpoint a ``from_pretrained(pretrained_model_name_or_path, **kwargs)`` call names, before a weight is read:
+    ``kwargs["config"]`` where that is a ``PretrainedConfig``, else the dict of the ``config.json`` at the path given there or at the checkpoint's.
+    ``default``: the ``model_type`` of a ``config.json`` that names none."""
+    config = kwargs.get("config")
+    if isinstance(config, PretrainedConfig):
+        return config.model_type, config
+    where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
+    cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
+    return cfg_dict.get("model_type", default), cfg_dict
+
+
 class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
     _hf_base = BertModel
-    _roberta_twin = None             # the same encoder over XLMRobertaModel (set below)
-    _mpnet_twin = None               # ... and over MPNetModel
-    _nomic_twin = None               # ... and over NomicBertModel
-    _modern_twin = None              # ... and over ModernBertModel
-    _t5_twin = None                  # ... and over T5EncoderModel
-    _deberta_twin = None             # ... and over DebertaV2Model
-    _decoder_twin = None             # ... and over Qwen2Model / LlamaModel / MistralModel / EuroBertModel (DecoderE5Encoder / DecoderBGEEncoder pick the base)
-    _jina3_twin = None               # ... and over JinaEmbeddingsV3Model
+    _dispatch_by_model_type = True   # from_pretrained returns the twin of the checkpoint's family (a subclass that runs one family only sets it False)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        """A BERT checkpoint loads exactly as ``BertModel.from_pretrained`` always did.  A RoBERTa-family checkpoint (``ROBERTA_TYPES``) has the same state-dict
-        names and would load into this class without an error and then compute with BERT's position ids: it goes to the XLM-R twin instead."""
-        if cls._roberta_twin is None:
-            return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        config = kwargs.get("config")
-        if isinstance(config, PretrainedConfig):
-            model_type = config.model_type
-        else:
-            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-            model_type = cfg_dict.get("model_type", "bert")
-        if model_type in ROBERTA_TYPES:
-            return cls._roberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type == MPNET_TYPE:
-            # MPNet's layer names differ: loaded into this class every layer would stay randomly initialised, with warnings only
-            return cls._mpnet_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type == NOMIC_TYPE:
-            # other layer names, no position table, a gated MLP: nothing of it fits BertModel
-            return cls._nomic_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type == MODERN_TYPE:
-            # a pre-LN stack under names of its own
-            return cls._modern_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type == T5_TYPE:
-            # an encoder-only T5: RMS norms, a relative attention bias, and (sentence-transformers checkpoints) a Dense head behind the pooling
-            return cls._t5_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type in (DEBERTA_TYPE, "deberta"):
-            # disentangled attention under projection names of its own; what the kernels do not compute is refused from config.json alone
-            check_deberta_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
-            return cls._deberta_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type == JINA3_TYPE:
-            # NomicBert's rotary post-LN stack with biases and BERT's feed-forward; what the kernels do not compute is refused from config.json alone
-            check_jina3_config(config if isinstance(config, PretrainedConfig) else cfg_dict)
-            return cls._jina3_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type in DECODER_BASES:
-            # a causal pre-LN stack under names of its own; what the kernels do not compute is refused from config.json alone
-            return cls._decoder_twin.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        """A BERT checkpoint loads exactly as ``BertModel.from_pretrained`` always did.  A checkpoint of another family would load into this class with
+        warnings at most (RoBERTa's state-dict names are BERT's: it would then compute with BERT's position ids) — it goes to that family's twin instead, after
+        what the kernels do not compute has been refused from ``config.json`` alone."""
+        if cls._dispatch_by_model_type:
+            model_type, config = checkpoint_model_type(pretrained_model_name_or_path, kwargs)
+            family = family_of(model_type)
+            if family.hf_base is not BertModel:
+                if family.check is not None:
+                    family.check(config)
+                return family.twin(cls._pool).from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
@@ -1174,11 +1173,7 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
             cls._check_pooling(pooling)
         if attention is not None:
             cls._check_attention(attention)
-        config = kwargs.get("config")
-        if not isinstance(config, PretrainedConfig):
-            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-            config, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-        check_decoder_config(config)                # from config.json alone, before a weight is read
+        check_decoder_config(checkpoint_model_type(pretrained_model_name_or_path, kwargs)[1])     # from config.json alone, before a weight is read
         if pooling is None:
             pooling = read_st_pooling(pretrained_model_name_or_path, **kwargs)
         if attention is None:
@@ -1212,146 +1207,116 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
         return out
 
 
-def _decoder_twin(base, pool: int, doc: str, name: Optional[str] = None):
-    name = name or base.__name__[:-len("Model")] + ("E5Encoder" if pool == POOL_MEAN else "BGEEncoder")
-    return type(name, (_HipDecoderSentenceMixin, base), {"_hf_base": base, "_pool": pool, "__doc__": doc, "__module__": __name__})
+def _twin_pair(stem: str, bases: tuple, e5_doc: str, bge_doc: str, bge_pool: int = POOL_CLS, **attrs):
+    """``(<stem>E5Encoder, <stem>BGEEncoder)``: the mean-pooling and the ``bge_pool``-pooling sentence encoder over ``bases``"""
+    def make(suffix, pool, doc):
+        return type(stem + suffix, bases, {**attrs, "_pool": pool, "__doc__": doc, "__module__": __name__})
+    return make("E5Encoder", POOL_MEAN, e5_doc), make("BGEEncoder", bge_pool, bge_doc)
 
 
-Qwen2E5Encoder = _decoder_twin(Qwen2Model, POOL_MEAN, "Qwen2Model (causal) -> masked mean -> L2 normalise (the Qwen2.5-0.5B embedders: KaLM-embedding-multilingual-mini)")
-Qwen2BGEEncoder = _decoder_twin(Qwen2Model, POOL_LAST, "Qwen2Model (causal) -> last attended token -> L2 normalise")
-LlamaE5Encoder = _decoder_twin(LlamaModel, POOL_MEAN, "LlamaModel (causal) -> masked mean -> L2 normalise (Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes)")
-LlamaBGEEncoder = _decoder_twin(LlamaModel, POOL_LAST, "LlamaModel (causal) -> last attended token -> L2 normalise")
-MistralE5Encoder = _decoder_twin(MistralModel, POOL_MEAN, "MistralModel (causal, no sliding window) -> masked mean -> L2 normalise")
-MistralBGEEncoder = _decoder_twin(MistralModel, POOL_LAST, "MistralModel (causal, no sliding window) -> last attended token -> L2 normalise")
+def _decoder_pair(base, e5_doc: str, bge_doc: str, bge_pool: int = POOL_LAST):
+    return _twin_pair(base.__name__[:-len("Model")], (_HipDecoderSentenceMixin, base), e5_doc, bge_doc, bge_pool, _hf_base=base)
+
+
+E5Encoder, BGEEncoder = _twin_pair("", (_HipSentenceEncoder,), "BertModel -> masked mean -> L2 normalise", "BertModel -> [:, 0] -> L2 normalise")
+XLMRobertaE5Encoder, XLMRobertaBGEEncoder = _twin_pair(
+    "XLMRoberta", (_HipXLMRSentenceEncoder,), "XLMRobertaModel -> masked mean -> L2 normalise (intfloat/multilingual-e5-*)",
+    "XLMRobertaModel -> [:, 0] -> L2 normalise (the dense head of BAAI/bge-m3)")
+MPNetE5Encoder, MPNetBGEEncoder = _twin_pair(
+    "MPNet", (_HipMPNetSentenceEncoder,), "MPNetModel -> masked mean -> L2 normalise (sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1)",
+    "MPNetModel -> [:, 0] -> L2 normalise")
+NomicBertE5Encoder, NomicBertBGEEncoder = _twin_pair(
+    "NomicBert", (_HipNomicSentenceEncoder,), "NomicBertModel -> masked mean -> L2 normalise (nomic-ai/nomic-embed-text-v1, -v1.5)",
+    "NomicBertModel -> [:, 0] -> L2 normalise")
+ModernBertE5Encoder, ModernBertBGEEncoder = _twin_pair(
+    "ModernBert", (_HipModernBertSentenceEncoder,), "ModernBertModel -> masked mean -> L2 normalise (nomic-ai/modernbert-embed-base)",
+    "ModernBertModel -> [:, 0] -> L2 normalise (Alibaba-NLP/gte-modernbert-base, ibm-granite/granite-embedding-english-r2)")
+T5E5Encoder, T5BGEEncoder = _twin_pair(
+    "T5", (_HipT5SentenceEncoder,), "T5EncoderModel -> masked mean -> Dense -> L2 normalise (sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*)",
+    "T5EncoderModel -> [:, 0] -> Dense -> L2 normalise")
+JinaV3E5Encoder, JinaV3BGEEncoder = _twin_pair(
+    "JinaV3", (_HipJinaV3SentenceEncoder,), "JinaEmbeddingsV3Model -> masked mean -> L2 normalise (jinaai/jina-embeddings-v3-hf; task adapters are not applied)",
+    "JinaEmbeddingsV3Model -> [:, 0] -> L2 normalise")
+DebertaV2E5Encoder, DebertaV2BGEEncoder = _twin_pair(
+    "DebertaV2", (_HipDebertaSentenceEncoder,), "DebertaV2Model -> masked mean -> L2 normalise (fine-tunes of microsoft/deberta-v3-*)",
+    "DebertaV2Model -> [:, 0] -> L2 normalise")
+Qwen2E5Encoder, Qwen2BGEEncoder = _decoder_pair(
+    Qwen2Model, "Qwen2Model (causal) -> masked mean -> L2 normalise (the Qwen2.5-0.5B embedders: KaLM-embedding-multilingual-mini)",
+    "Qwen2Model (causal) -> last attended token -> L2 normalise")
+LlamaE5Encoder, LlamaBGEEncoder = _decoder_pair(
+    LlamaModel, "LlamaModel (causal) -> masked mean -> L2 normalise (Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes)",
+    "LlamaModel (causal) -> last attended token -> L2 normalise")
+MistralE5Encoder, MistralBGEEncoder = _decoder_pair(
+    MistralModel, "MistralModel (causal, no sliding window) -> masked mean -> L2 normalise", "MistralModel (causal, no sliding window) -> last attended token -> L2 normalise")
 # EuroBERT: no causal reason to prefer the last token, so both registry classes pool the mean unless the kwarg or 1_Pooling says "last"
-EuroBertE5Encoder = _decoder_twin(EuroBertModel, POOL_MEAN, "EuroBertModel (bidirectional) -> masked mean -> L2 normalise (EuroBERT-210m / -610m fine-tunes)", "EuroBertE5Encoder")
-EuroBertBGEEncoder = _decoder_twin(EuroBertModel, POOL_MEAN, "EuroBertModel (bidirectional) -> masked mean -> L2 normalise", "EuroBertBGEEncoder")
+EuroBertE5Encoder, EuroBertBGEEncoder = _decoder_pair(
+    EuroBertModel, "EuroBertModel (bidirectional) -> masked mean -> L2 normalise (EuroBERT-210m / -610m fine-tunes)",
+    "EuroBertModel (bidirectional) -> masked mean -> L2 normalise", POOL_MEAN)
+
+
+def _decoder_family(model_type: str, twins: tuple, decoder_attention: Optional[float] = None) -> Family:
+    return Family((model_type,), twins[0]._hf_base, describe_decoder, twins, flag="is_decoder", decoder_attention=decoder_attention)
+
+
+# Every family, once.  Adding one: its entry here (with a describe function above), its twin pair above, and a tests/<family>_util.py.
+_FAMILIES = (
+    # BERT: the post-LN stack with a position table and token types the kernels were written for; anything unknown is treated as one
+    Family(("bert",), BertModel, describe_bert, (E5Encoder, BGEEncoder), token_types=True),
+    # RoBERTa family (multilingual-e5, bge-m3's dense head): BERT's stack and state-dict names, fairseq's position rule (padding_idx + cumsum(ids !=
+    # padding_idx)) with config.pad_token_id.  "xlm-roberta-xl" is pre-LN: not one of them
+    Family(ROBERTA_TYPES, XLMRobertaModel, describe_roberta, (XLMRobertaE5Encoder, XLMRobertaBGEEncoder), token_types=True),
+    # MPNet: BERT's stack under other names, no token types (a zero row stands in), fairseq positions with padding index 1, and one learned bias per
+    # (head, bucket of the column distance) that the attention kernels add to every score (encoder.relative_attention_bias.weight)
+    Family((MPNET_TYPE,), MPNetModel, describe_mpnet, (MPNetE5Encoder, MPNetBGEEncoder), flag="is_mpnet"),
+    # NomicBert (nomic-embed-text-v1 / -v1.5): post-LN without a position table — q / k rotated in the QKV epilogue by HF's own inv_freq — a SwiGLU MLP
+    # with gate | up as one projection, no linear biases
+    Family((NOMIC_TYPE,), NomicBertModel, describe_nomic, (NomicBertE5Encoder, NomicBertBGEEncoder), token_types=True, flag="is_nomic"),
+    # ModernBERT: a PRE-LN stack, rotary q / k with one frequency vector per layer type, the GeGLU MLP Wo(gelu(input) * gate), sliding-window attention in
+    # the layers config.layer_types names (MODERN_SETTINGS); an intermediate size that is no multiple of 128 is zero-padded (pad_modernbert_ff: exact)
+    Family((MODERN_TYPE,), ModernBertModel, describe_modern, (ModernBertE5Encoder, ModernBertBGEEncoder), flag="is_modern"),
+    # T5 encoders (gtr-t5, sentence-t5, instructor): ModernBERT's schedule with RMS norms, MPNet's bias table (held by block 0) on unscaled scores, no bias
+    # anywhere, wo(relu(wi x)) or wo(gelu_new(wi_0 x) * wi_1 x) (T5_SETTING); a sentence-transformers Dense head runs inside the library (dense.weight)
+    Family((T5_TYPE,), T5EncoderModel, describe_t5, (T5E5Encoder, T5BGEEncoder), flag="is_t5"),
+    # DeBERTa-v2 / v3: disentangled attention (c2p + p2c over log buckets of the relative position, shared projections), no position table, no token types.
+    # "deberta" (v1) is named here so that check_deberta_config refuses it by name
+    Family((DEBERTA_TYPE, "deberta"), DebertaV2Model, describe_deberta, (DebertaV2E5Encoder, DebertaV2BGEEncoder), flag="is_deberta", check=check_deberta_config),
+    # jina-embeddings-v3: NomicBert's rotary post-LN stack with biases on q / k / v / o (q's and k's added before the rotation) and BERT's feed-forward
+    # (ROTARY_FF_SETTING); task LoRA adapters are not applied (merge them into the weights)
+    Family((JINA3_TYPE,), JinaEmbeddingsV3Model, describe_jina3, (JinaV3E5Encoder, JinaV3BGEEncoder), token_types=True, flag="is_jina3", check=check_jina3_config),
+    # Decoder-LLM embedders: T5's schedule with NomicBert's rotary q / k and SwiGLU, optional q / k / v biases, a CAUSAL mask (DECODER_SETTING = 1), mean or
+    # last-token pooling; grouped-query k / v go to the library with their HF shapes where kv_heads d_h is a multiple of 64 (kv_for_library)
+    _decoder_family("qwen2", (Qwen2E5Encoder, Qwen2BGEEncoder)),
+    _decoder_family("llama", (LlamaE5Encoder, LlamaBGEEncoder)),
+    _decoder_family("mistral", (MistralE5Encoder, MistralBGEEncoder)),
+    # EuroBERT: the decoders' stack under a BIDIRECTIONAL mask (DECODER_SETTING = 0); the other decoder twins take the same choice as attention="bidirectional"
+    _decoder_family(EUROBERT_TYPE, (EuroBertE5Encoder, EuroBertBGEEncoder), decoder_attention=0.0),
+)
+FAMILIES = {t: f for f in _FAMILIES for t in f.model_types}
+# decoder-LLM embedders: model_type -> the HF base model the twins are built over
+DECODER_BASES = {t: f.hf_base for t, f in FAMILIES.items() if f.flag == "is_decoder"}
 
 
 class _DecoderDispatch:
     """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral`` / ``eurobert``); anything else is refused by name"""
-    _twins: dict = {}
+    _pool = POOL_MEAN
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        config = kwargs.get("config")
-        if isinstance(config, PretrainedConfig):
-            model_type = config.model_type
-        else:
-            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-            model_type = cfg_dict.get("model_type")
-        if model_type not in cls._twins:
-            raise NotImplementedError(f"model_type={model_type!r}: the decoder path is built for {sorted(cls._twins)}")
-        return cls._twins[model_type].from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        model_type, _ = checkpoint_model_type(pretrained_model_name_or_path, kwargs, default=None)
+        if model_type not in DECODER_BASES:
+            raise NotImplementedError(f"model_type={model_type!r}: the decoder path is built for {sorted(DECODER_BASES)}")
+        return FAMILIES[model_type].twin(cls._pool).from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
 
 class DecoderE5Encoder(_DecoderDispatch):
     """a decoder LLM (causal) -> masked mean -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``last``"""
-    _twins = {"qwen2": Qwen2E5Encoder, "llama": LlamaE5Encoder, "mistral": MistralE5Encoder, "eurobert": EuroBertE5Encoder}
+    _pool = POOL_MEAN
 
 
 class DecoderBGEEncoder(_DecoderDispatch):
     """a decoder LLM (causal) -> last attended token -> L2 normalise, unless the ``pooling`` kwarg or the checkpoint's ``1_Pooling`` says ``mean``"""
-    _twins = {"qwen2": Qwen2BGEEncoder, "llama": LlamaBGEEncoder, "mistral": MistralBGEEncoder, "eurobert": EuroBertBGEEncoder}
+    _pool = POOL_LAST
 
-
-class E5Encoder(_HipSentenceEncoder):
-    """BertModel -> masked mean -> L2 normalise"""
-    _pool = POOL_MEAN
-
-
-class BGEEncoder(_HipSentenceEncoder):
-    """BertModel -> [:, 0] -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-class XLMRobertaE5Encoder(_HipXLMRSentenceEncoder):
-    """XLMRobertaModel -> masked mean -> L2 normalise (intfloat/multilingual-e5-*)"""
-    _pool = POOL_MEAN
-
-
-class XLMRobertaBGEEncoder(_HipXLMRSentenceEncoder):
-    """XLMRobertaModel -> [:, 0] -> L2 normalise (the dense head of BAAI/bge-m3)"""
-    _pool = POOL_CLS
-
-
-class MPNetE5Encoder(_HipMPNetSentenceEncoder):
-    """MPNetModel -> masked mean -> L2 normalise (sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1)"""
-    _pool = POOL_MEAN
-
-
-class MPNetBGEEncoder(_HipMPNetSentenceEncoder):
-    """MPNetModel -> [:, 0] -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-class NomicBertE5Encoder(_HipNomicSentenceEncoder):
-    """NomicBertModel -> masked mean -> L2 normalise (nomic-ai/nomic-embed-text-v1, -v1.5)"""
-    _pool = POOL_MEAN
-
-
-class NomicBertBGEEncoder(_HipNomicSentenceEncoder):
-    """NomicBertModel -> [:, 0] -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-class ModernBertE5Encoder(_HipModernBertSentenceEncoder):
-    """ModernBertModel -> masked mean -> L2 normalise (nomic-ai/modernbert-embed-base)"""
-    _pool = POOL_MEAN
-
-
-class ModernBertBGEEncoder(_HipModernBertSentenceEncoder):
-    """ModernBertModel -> [:, 0] -> L2 normalise (Alibaba-NLP/gte-modernbert-base, ibm-granite/granite-embedding-english-r2)"""
-    _pool = POOL_CLS
-
-
-class T5E5Encoder(_HipT5SentenceEncoder):
-    """T5EncoderModel -> masked mean -> Dense -> L2 normalise (sentence-transformers/gtr-t5-*, sentence-t5-*, hkunlp/instructor-*)"""
-    _pool = POOL_MEAN
-
-
-class T5BGEEncoder(_HipT5SentenceEncoder):
-    """T5EncoderModel -> [:, 0] -> Dense -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-class JinaV3E5Encoder(_HipJinaV3SentenceEncoder):
-    """JinaEmbeddingsV3Model -> masked mean -> L2 normalise (jinaai/jina-embeddings-v3-hf; task adapters are not applied)"""
-    _pool = POOL_MEAN
-
-
-class JinaV3BGEEncoder(_HipJinaV3SentenceEncoder):
-    """JinaEmbeddingsV3Model -> [:, 0] -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-class DebertaV2E5Encoder(_HipDebertaSentenceEncoder):
-    """DebertaV2Model -> masked mean -> L2 normalise (fine-tunes of microsoft/deberta-v3-*)"""
-    _pool = POOL_MEAN
-
-
-class DebertaV2BGEEncoder(_HipDebertaSentenceEncoder):
-    """DebertaV2Model -> [:, 0] -> L2 normalise"""
-    _pool = POOL_CLS
-
-
-E5Encoder._roberta_twin = XLMRobertaE5Encoder
-BGEEncoder._roberta_twin = XLMRobertaBGEEncoder
-E5Encoder._mpnet_twin = MPNetE5Encoder
-BGEEncoder._mpnet_twin = MPNetBGEEncoder
-E5Encoder._nomic_twin = NomicBertE5Encoder
-BGEEncoder._nomic_twin = NomicBertBGEEncoder
-E5Encoder._modern_twin = ModernBertE5Encoder
-BGEEncoder._modern_twin = ModernBertBGEEncoder
-E5Encoder._t5_twin = T5E5Encoder
-BGEEncoder._t5_twin = T5BGEEncoder
-E5Encoder._deberta_twin = DebertaV2E5Encoder
-BGEEncoder._deberta_twin = DebertaV2BGEEncoder
-E5Encoder._decoder_twin = DecoderE5Encoder
-BGEEncoder._decoder_twin = DecoderBGEEncoder
-E5Encoder._jina3_twin = JinaV3E5Encoder
-BGEEncoder._jina3_twin = JinaV3BGEEncoder
 
 
 def _register_nomic_checkpoint_format() -> None:

@@ -28,20 +28,11 @@ import torch.nn as nn
 from torch import Tensor
 from transformers import PretrainedConfig
 
-from .encoders import (_CONFIG_KWARGS, POOL_CLS, POOL_WITH_COLBERT, POOL_WITH_SPARSE, ROBERTA_TYPES, BGEEncoder, XLMRobertaBGEEncoder, _st_file,
-                       check_colbert_dim)
+from .encoders import (POOL_CLS, POOL_WITH_COLBERT, POOL_WITH_SPARSE, ROBERTA_TYPES, BGEEncoder, XLMRobertaBGEEncoder, _st_file, check_colbert_dim,
+                       checkpoint_model_type)
 
 COLBERT_FILE, SPARSE_FILE = "colbert_linear.pt", "sparse_linear.pt"
 SCORE_KEYS = ("dense", "sparse", "colbert", "sparse+dense", "colbert+sparse+dense")
-
-
-def _model_type(pretrained_model_name_or_path, kwargs) -> str:
-    config = kwargs.get("config")
-    if isinstance(config, PretrainedConfig):
-        return config.model_type
-    where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-    cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-    return cfg_dict.get("model_type", "bert")
 
 
 def check_head_state(name: str, state: Dict[str, Tensor], hidden: int) -> Tuple[Tensor, Tensor]:
@@ -89,21 +80,17 @@ class _M3HeadsMixin:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        model_type = _model_type(pretrained_model_name_or_path, kwargs)
+        model_type, config = checkpoint_model_type(pretrained_model_name_or_path, kwargs)
         if model_type not in cls._model_types:
             raise NotImplementedError(f"model_type={model_type!r}: {cls.__name__} runs {cls._model_types} checkpoints (bge-m3's heads on other families are not "
                                       "implemented)")
         states = {}
-        hidden = None
         for name, fname in (("colbert_linear", COLBERT_FILE), ("sparse_linear", SPARSE_FILE)):
             path = _st_file(pretrained_model_name_or_path, fname, kwargs)
             if path is None:
                 continue
             state = torch.load(path, map_location="cpu", weights_only=True)
-            if hidden is None:
-                config = kwargs.get("config")
-                hidden = int(config.hidden_size) if isinstance(config, PretrainedConfig) else int(PretrainedConfig.get_config_dict(
-                    pretrained_model_name_or_path, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})[0]["hidden_size"])
+            hidden = int(config.hidden_size if isinstance(config, PretrainedConfig) else config["hidden_size"])
             check_head_state(name, state, hidden)         # refused before the backbone is read
             states[name] = state
         model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
@@ -149,7 +136,7 @@ class XLMRobertaM3Encoder(_M3HeadsMixin, XLMRobertaBGEEncoder):
 class BertM3Encoder(_M3HeadsMixin, BGEEncoder):
     """BertModel -> ``[CLS]`` row + the same two heads (an M3-style fine-tune of a BERT backbone)"""
     _model_types = ("bert",)
-    _roberta_twin = None             # no dispatch to another family's class: from_pretrained refuses other model types by name
+    _dispatch_by_model_type = False  # no dispatch to another family's class: from_pretrained refuses other model types by name
 
 
 def build_lexical_weights(token_ids: Sequence[int], weights: Sequence[float], skip_ids) -> Dict[str, float]:
@@ -202,7 +189,7 @@ class BGEM3Model:
         if isinstance(model_name_or_path, nn.Module) or hasattr(model_name_or_path, "forward_m3"):
             self.model = model_name_or_path
         else:
-            mt = _model_type(model_name_or_path, kwargs)
+            mt, _ = checkpoint_model_type(model_name_or_path, kwargs)
             if mt in ROBERTA_TYPES:
                 cls = XLMRobertaM3Encoder
             elif mt == "bert":

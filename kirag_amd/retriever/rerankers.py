@@ -24,12 +24,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
-from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification, PretrainedConfig,
+from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification,
                           XLMRobertaForSequenceClassification)
 from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
-from .encoders import _CONFIG_KWARGS, DEBERTA_TYPE, check_deberta_config, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin
+from .encoders import (DEBERTA_TYPE, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin, _refuser, check_deberta_config,
+                       check_heads, check_hidden, checkpoint_model_type)
 from .m3 import BGEM3Model
 from .splade import SpladeModel
 
@@ -93,7 +94,6 @@ class BertReranker(_HipClassifierMixin, BertForSequenceClassification):
 
 MODERN_POOLINGS = {"cls": 0.0, "mean": 1.0}       # config.classifier_pooling -> the library's setting "config.classifier_pooling"
 MODERN_POOLING_SETTING = "config.classifier_pooling"
-MODERN_HIDDEN_STEP, MODERN_HIDDEN_MAX, MODERN_HEAD_WIDTHS = 128, 2048, (32, 64)      # kr_encoder_create's shape rule
 
 
 def modern_rename(name: str) -> str:
@@ -105,16 +105,13 @@ def modern_rename(name: str) -> str:
 def check_modern_config(config) -> None:
     """``NotImplementedError`` beginning ``model_type='modernbert':`` and naming the field, for everything the kernels do not compute — from the config alone:
     no weight has been read and the library is not loaded.  ``config``: a ``ModernBertConfig`` or the dict of a ``config.json`` (HF's defaults fill the rest)."""
-    def refuse(msg):
-        raise NotImplementedError(f"model_type={MODERN_TYPE!r}: {msg}")
+    refuse = _refuser(MODERN_TYPE)
     is_dict = isinstance(config, dict)
     get = (lambda k, d: config.get(k, d)) if is_dict else (lambda k, d: getattr(config, k, d))
     # the raw fields first: HF's own config class validates some of them with errors of its own
     H, heads = int(get("hidden_size", 768)), int(get("num_attention_heads", 12))
-    if H % MODERN_HIDDEN_STEP or not 0 < H <= MODERN_HIDDEN_MAX:
-        refuse(f"hidden_size={H}: the HIP encoder takes a multiple of {MODERN_HIDDEN_STEP} up to {MODERN_HIDDEN_MAX}")
-    if heads <= 0 or H % heads or H // heads not in MODERN_HEAD_WIDTHS:
-        refuse(f"num_attention_heads={heads} with hidden_size={H}: the attention kernels are built for heads of width {MODERN_HEAD_WIDTHS}")
+    check_hidden(refuse, H)
+    check_heads(refuse, H, heads)
     if get("classifier_activation", "gelu") != "gelu":
         refuse(f"classifier_activation={get('classifier_activation', None)!r}: the classification head implements erf-GELU only")
     if get("classifier_pooling", "cls") not in MODERN_POOLINGS:
@@ -186,13 +183,7 @@ class BGEReranker:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        config = kwargs.get("config")
-        if isinstance(config, PretrainedConfig):
-            model_type, cfg_dict = config.model_type, config
-        else:
-            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-            model_type = cfg_dict.get("model_type", "bert")
+        model_type, cfg_dict = checkpoint_model_type(pretrained_model_name_or_path, kwargs)
         if model_type == "bert":
             return BertReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         if model_type in ROBERTA_TYPES:

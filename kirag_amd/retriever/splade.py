@@ -30,7 +30,7 @@ import torch.nn as nn
 from torch import Tensor
 from transformers import BertForMaskedLM, PretrainedConfig
 
-from .encoders import _CONFIG_KWARGS, POOL_SPLADE, HipBertForward, _HipModuleMixin
+from .encoders import POOL_SPLADE, HipBertForward, _HipModuleMixin, checkpoint_model_type
 
 DECODER_WEIGHT, DECODER_BIAS = "cls.predictions.decoder.weight", "cls.predictions.decoder.bias"
 
@@ -83,13 +83,8 @@ class BertSpladeEncoder(_HipModuleMixin, BertForMaskedLM):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
-        config = kwargs.get("config")
-        if isinstance(config, PretrainedConfig):
-            cfg_dict = config.to_dict()
-        else:
-            where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
-            cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
-        check_splade_config(cfg_dict)          # refused by name before any weight is read
+        _, config = checkpoint_model_type(pretrained_model_name_or_path, kwargs)
+        check_splade_config(config.to_dict() if isinstance(config, PretrainedConfig) else config)          # refused by name before any weight is read
         return super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
 
     @torch.no_grad()

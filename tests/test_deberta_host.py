@@ -227,7 +227,7 @@ def test_config_defaults_and_dispatch(tmp_path):
     assert ENC.check_deberta_config(D.hf_config(D.cfg(H, 1, 2, FF, 256, 512)), head=True) == {"buckets": 256, "max_rel": 512}
     assert issubclass(ENC.DebertaV2E5Encoder, tr.DebertaV2Model) and issubclass(ENC.DebertaV2BGEEncoder, tr.DebertaV2Model)
     assert issubclass(RR.DebertaV2Reranker, tr.DebertaV2ForSequenceClassification)
-    assert ENC.E5Encoder._deberta_twin is ENC.DebertaV2E5Encoder and ENC.BGEEncoder._deberta_twin is ENC.DebertaV2BGEEncoder
+    assert ENC.FAMILIES["deberta-v2"].twin(ENC.E5Encoder._pool) is ENC.DebertaV2E5Encoder and ENC.FAMILIES["deberta-v2"].twin(ENC.BGEEncoder._pool) is ENC.DebertaV2BGEEncoder
     assert (ENC.DebertaV2E5Encoder._pool, ENC.DebertaV2BGEEncoder._pool) == (ENC.POOL_MEAN, ENC.POOL_CLS)
     # the reranker's names: the backbone loses its prefix, pooler.dense / classifier are the library's head; the pooler half travels as `extra`
     cfg = D.hf_config(D.cfg(H, 1, 2, FF, 32, 128, MAX_POS, V, labels=3))
