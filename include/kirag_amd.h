@@ -232,7 +232,8 @@ typedef struct {
 
 #define KR_POOL_MEAN 0 /* E5: average_pool (encoders.py:56-58) then F.normalize */
 #define KR_POOL_CLS 1  /* BGE: last_hidden[:,0] (encoders.py:116) then F.normalize */
-#define KR_POOL_CLASSIFY 2 /* cross-encoder rerankers: last_hidden[:,0] -> the classification head -> raw logits [B, L] (needs "classifier.*", below) */
+#define KR_POOL_CLASSIFY 2 /* cross-encoder rerankers: last_hidden[:,0] -> the classification head -> raw logits [B, L] (needs "classifier.*", below); on a
+                            * decoder handle with "score.weight": the row of the highest attended column -> the score head (below) */
 /* bge-m3's token-level heads: flag bits ORed onto a base pool of KR_POOL_MEAN or KR_POOL_CLS (kr_encoder_forward / kr_encoder_forward_tt only).  `out` then
  * holds, back to back and all fp32: the dense block [B, hidden] (the bits of the unflagged call with the same base pool), with KR_POOL_WITH_SPARSE the sparse
  * block [B, S], with KR_POOL_WITH_COLBERT the colbert block [B, S, P] ("sparse_linear.*" / "colbert_linear.*" under kr_encoder_load_weight below).  Any other
@@ -382,7 +383,8 @@ void kr_encoder_destroy(kr_encoder* enc);
  *       with another A than it had makes its partner count as never loaded (finalize then reports the partner by its weight slot): after correcting a
  *       k / v mismatch, load both matrices of that layer again;
  *       any other name on the handle, a head's tensors included, is KR_EINVAL at finalize, and these names' decoder-only rows on another handle likewise;
- *     - the forwards take KR_POOL_MEAN and KR_POOL_LAST; KR_POOL_CLS / KR_POOL_CLASSIFY / KR_POOL_SPLADE are KR_EINVAL.
+ *     - the forwards take KR_POOL_MEAN and KR_POOL_LAST; KR_POOL_CLS / KR_POOL_SPLADE are KR_EINVAL, and so is KR_POOL_CLASSIFY unless the handle holds
+ *       the score head ("score.weight", below: the one head's tensor a decoder handle takes).
  *   "config.deberta_position_buckets" + "config.deberta_max_relative_positions": data = ONE float each, Bk (even, 2 .. 256) and M (M - 1 > Bk / 2):
  *   DebertaV2Config's position_buckets and max_relative_positions (max_position_embeddings where that is < 1).  The two together, loaded before the first
  *   finalize, make the handle a DeBERTa handle (DebertaV2Model: microsoft/deberta-v3-* and their fine-tunes) for life; the usual rule of the settings holds
@@ -439,6 +441,19 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   L or a head arriving on a handle finalized without one is KR_EINVAL.  KR_POOL_CLASSIFY without the head is KR_ESTATE, naming the four required tensors.
  *   kr_encoder_finalize refuses these six names (KR_EINVAL, naming the tensor) on a handle of any other kind; RobertaClassificationHead's four names stay
  *   refused on ModernBert handles.
+ * Qwen2ForSequenceClassification / LlamaForSequenceClassification / MistralForSequenceClassification (decoder-LLM cross-encoders, and causal-LM "yes / no"
+ * rerankers folded into one label by the Python layer): on decoder handles ("config.decoder_attention" 1 or 0) the head is ONE tensor, fp32, without a bias,
+ *   "score.weight" [L, hidden], 1 <= L <= 64 (any other count is KR_EINVAL at load).  With it, pool = KR_POOL_CLASSIFY is accepted by the three forward
+ *   entry points (kr_encoder_forward_packed included: decoder pairs carry no token types) and writes out [B, L] fp32,
+ *       logits = score.weight . x,     x = the final-norm row of the sequence's HIGHEST ATTENDED COLUMN (KR_POOL_LAST's row, NOT normalised),
+ *   raw logits, fp32 arithmetic, independent of the batch around a sequence and of the entry point.  HF picks the rightmost column whose id is not
+ *   pad_token_id; the two agree whenever attention_mask == (input_ids != pad_token_id), and the library follows the mask.  Only that row is read behind the
+ *   last layer, so its out-projection, norms and feed-forward run on B gathered rows (KIRAG_AMD_CLS_FULL=1 at create: on every row, same bits); after such a
+ *   forward kr_encoder_last_hidden is KR_ESTATE.  KR_POOL_MEAN and KR_POOL_LAST run as on a handle without the head and write [B, hidden].  An all-masked
+ *   sequence gives a NaN row; a non-finite logit of a sequence with attended tokens is KR_ERANGE.  KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT on it stay
+ *   KR_EINVAL.  The rule of "classifier.*" holds: fixed at the first finalize — the same L takes new values, another L, or the tensor arriving on a handle
+ *   finalized without it, is KR_EINVAL — and a decoder handle WITHOUT it keeps refusing KR_POOL_CLASSIFY with KR_EINVAL.  kr_encoder_finalize refuses
+ *   "score.weight" (KR_EINVAL, naming it) on a handle of any other kind.
  * BAAI/bge-m3's sparse and multi-vector heads (an XLM-R backbone; the same two Linear modules on a BERT backbone are accepted too), fp32:
  *   "colbert_linear.weight" [P, hidden], "colbert_linear.bias" [P]: P % 128 == 0 and 128 <= P <= 2048, any other count is KR_EINVAL;
  *   "sparse_linear.weight" [1, hidden], "sparse_linear.bias" [1].

@@ -89,7 +89,7 @@ struct Encoder {
     std::vector<void**> ws_bufs, own_bufs;
     float* stage = nullptr; size_t stage_elems = 0;   // fp32 upload staging for enc_load_weight
     // the tensors of the heads, HEADS[head].t[i] at head_p[head][i]: fp32, or the 16-bit operand where the row says HALF
-    void* head_p[model::HEAD_COUNT][model::HEAD_MAX_TENSORS] = {};
+    void* head_p[model::HEAD_ALL][model::HEAD_MAX_TENSORS] = {};
     float* hf(int head, int i) const { return static_cast<float*>(head_p[head][i]); }
     uint16_t* hh(int head, int i) const { return static_cast<uint16_t*>(head_p[head][i]); }
     // the relative attention bias as loaded (host) and the table the attention kernels read (AttnBiasArgs), built by finalize
@@ -464,8 +464,10 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // (ModernBert's head with config.classifier_pooling = 1 reads the masked mean: everything up to the last LayerNorm sees KR_POOL_MEAN)
     using namespace model;
     const ModelPlan& p = e->plan;
+    // (a decoder handle's score head reads KR_POOL_LAST's row: everything up to the last layer's attention sees KR_POOL_LAST)
     const bool classify = pool == KR_POOL_CLASSIFY;
-    if (classify) pool = p.classify_mean ? KR_POOL_MEAN : KR_POOL_CLS;
+    const bool score = classify && p.classifier == HEAD_SCORE;
+    if (classify) pool = score ? KR_POOL_LAST : p.classify_mean ? KR_POOL_MEAN : KR_POOL_CLS;
     // KR_POOL_SPLADE packs and attends like KR_POOL_MEAN (no query-only rows) and differs behind the last LayerNorm only
     const bool splade = pool == KR_POOL_SPLADE;
     if (splade) pool = KR_POOL_MEAN;
@@ -509,7 +511,9 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
                            e->word, no_pos ? e->zero_row : e->pos, e->type, e->elng, e->elnb, eps, H,
                            e->use_lo ? e->xlo : nullptr, e->xb);
     }
-    const bool shortcut = pool == KR_POOL_CLS && e->cls_shortcut && e->c_ctx != nullptr && !flags;      // the token-level heads read every row of the last layer
+    // (the score head reads one row per sequence too, the last packed one: the same shortcut on those rows.  The embedding pools of a decoder handle keep
+    // every row)
+    const bool shortcut = (pool == KR_POOL_CLS || score) && e->cls_shortcut && e->c_ctx != nullptr && !flags;      // the token-level heads read every row of the last layer
     e->last_shortcut = shortcut;
     const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid,
                           e->rb, e->use_lo ? e->rlo : nullptr};
@@ -590,7 +594,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
         const uint8_t* rin_lo = in_rb ? all_rows.rlo : all_rows.lo;
         if (last && shortcut)
             hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
-                               pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B);
+                               pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, score ? 1 : 0);
         if (pre) {
             if (last && shortcut) KR_TRY(tail_pre(a, l, cls_rows, last, e->c_rb, cls_rows.rlo));
             else KR_TRY(tail_pre(a, l, all_rows, last, rin, rin_lo));
@@ -623,6 +627,11 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
     hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool_select,
                        p.head[HEAD_DENSE] || classify ? e->pooled : e->out, e->d_err);
+    if (score) {                 // a decoder handle's score head: out [B, L] = score.weight . pooled, one launch without LDS
+        const int L = p.head_dim[HEAD_SCORE];
+        const int64_t waves = (int64_t)B * ((L + SH_LABELS - 1) / SH_LABELS);
+        hipLaunchKernelGGL(k_score_head, dim3((unsigned)((waves + SH_WAVES - 1) / SH_WAVES)), dim3(SH_WAVES * 64), 0, st, e->pooled, e->hf(HEAD_SCORE, 0), B, H, L, e->out, r.nk, e->d_err);
+    } else
     if (classify) {              // the classification head: out [B, L] = Wo . tanh(Wd . pooled + bd) + bo
         const int NJ = H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8, head_lds = CH_SEQ * 2 * H * 4;
         auto head_kernel = NJ == 1 ? &k_cls_head<1> : NJ == 2 ? &k_cls_head<2> : NJ == 4 ? &k_cls_head<4> : &k_cls_head<8>;
@@ -751,7 +760,8 @@ static int check_forward_args(const Encoder* e, bool bad_shape, int B, int S, in
     if (pool != KR_POOL_MEAN && pool != KR_POOL_CLS && pool != KR_POOL_CLASSIFY && pool != KR_POOL_SPLADE && pool != KR_POOL_LAST)
         return fail(KR_EINVAL, "pool must be 0 (mean), 1 (cls), 2 (classify) or 4 (splade), 0 and 1 optionally with KR_POOL_WITH_SPARSE (0x10) / KR_POOL_WITH_COLBERT (0x20)");
     if (flags && pool == KR_POOL_LAST) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 5 (last token)");
-    if (decoder && pool != KR_POOL_MEAN && pool != KR_POOL_LAST)
+    // (KR_POOL_CLASSIFY on a decoder handle that holds the score head passes: the flags' refusal and the forward below)
+    if (decoder && pool != KR_POOL_MEAN && pool != KR_POOL_LAST && !(pool == KR_POOL_CLASSIFY && p.classifier >= 0))
         return fail(KR_EINVAL, "pool = %d (%s) on a decoder handle: it takes KR_POOL_MEAN (0) and KR_POOL_LAST (5) — under a causal mask the first token sees itself alone, "
                                "and the handle has no head", pool, pool == KR_POOL_CLS ? "KR_POOL_CLS" : pool == KR_POOL_CLASSIFY ? "KR_POOL_CLASSIFY" : "KR_POOL_SPLADE");
     if (flags && pool == KR_POOL_CLASSIFY) return fail(KR_EINVAL, "KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT go with pool 0 (mean) or 1 (cls), not with 2 (classify)");
@@ -889,7 +899,9 @@ int enc_last_hidden(void* h, float* out, int B, int S) {
     Encoder* e = reinterpret_cast<Encoder*>(h);
     if (B != e->lastB || S != e->lastS || B == 0) return fail(KR_ESTATE, "no forward of shape [%d,%d] to read back", B, S);
     if (e->last_shortcut)
-        return fail(KR_ESTATE, "the last forward pooled the CLS token: its last layer ran on the CLS rows only (create the encoder with KIRAG_AMD_CLS_FULL=1 to keep every row)");
+        return fail(KR_ESTATE, e->plan.family == model::DECODER
+                                   ? "the last forward ran the score head: its last layer ran on the last rows only (create the encoder with KIRAG_AMD_CLS_FULL=1 to keep every row)"
+                                   : "the last forward pooled the CLS token: its last layer ran on the CLS rows only (create the encoder with KIRAG_AMD_CLS_FULL=1 to keep every row)");
     KR_TRY(select_device(e->device));
     KR_HIP(hipStreamSynchronize(e->last_stream));
     const int H = e->cfg.hidden;

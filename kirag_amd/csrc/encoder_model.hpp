@@ -219,7 +219,11 @@ inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& ou
 //   HEAD_CLS: RobertaClassificationHead (KR_POOL_CLASSIFY): out [B, L] = Wo . tanh(Wd . x + bd) + bo of the raw CLS row.  On a DeBERTa handle the same four
 //   names are DebertaV2ForSequenceClassification's ContextPooler + classifier: erf-GELU where the tanh stands (ModelPlan::cls_gelu).
 //   HEAD_MODERN_CLS: ModernBertForSequenceClassification's, Wo . LayerNorm(erf_gelu(Wd . x + bd)) + bo of the raw CLS row or (config.classifier_pooling = 1) mean.
-enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT };
+//   HEAD_SCORE: the score head of Qwen2 / Llama / MistralForSequenceClassification (HF's GenericForSequenceClassification.score, a Linear without a bias;
+//   KR_POOL_CLASSIFY on a decoder handle): out [B, L] = score.weight . x of the raw row of the highest attended column, behind the final norm.
+// HEAD_COUNT counts the heads of the encoder families — the ones the plan line of tests/capi/encoder_model_check.cpp prints, one digit each — and the decoders'
+// head follows them: the tables and per-head arrays are HEAD_ALL long.
+enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT, HEAD_SCORE = HEAD_COUNT, HEAD_ALL };
 enum : uint8_t { REQUIRED = 1, HALF = 2 };       // HALF: stored as the handle's 16-bit operand (a projection of the loops every layer uses), else fp32
 // workspace buffers that exist because of a head: the head's input rows [B, H]; the packed row of every [b, s] column; the sequence of every packed row; the
 // colbert product [T, P]
@@ -237,7 +241,7 @@ struct HeadDesc {
     int excludes[4];             // heads it is never next to, in the order they are reported; -1 ends the list
     unsigned ws;
 };
-static const HeadDesc HEADS[HEAD_COUNT] = {
+static const HeadDesc HEADS[HEAD_ALL] = {
     {nullptr, "an MLM head", "the MLM head of SPLADE is BertForMaskedLM's and is accepted on BERT handles", "the MLM head takes all six cls.predictions.* tensors or none", 6,
      {{"cls.predictions.transform.dense.weight", XH, XH, XH, REQUIRED | HALF}, {"cls.predictions.transform.dense.bias", XH, X1, XH, REQUIRED},
       {"cls.predictions.transform.LayerNorm.weight", XH, X1, XH, REQUIRED}, {"cls.predictions.transform.LayerNorm.bias", XH, X1, XH, REQUIRED},
@@ -262,6 +266,9 @@ static const HeadDesc HEADS[HEAD_COUNT] = {
      {{"head.dense.weight", XH, XH, XH, REQUIRED}, {"head.dense.bias", XH, X1, XH, 0}, {"head.norm.weight", XH, X1, XH, REQUIRED}, {"head.norm.bias", XH, X1, XH, 0},
       {"classifier.weight", XFREE, XH, XFREE, REQUIRED}, {"classifier.bias", XFREE, X1, XFREE, REQUIRED}},
      'L', 1, 64, 1, 1u << MODERN, {-1}, WS_POOLED},
+    {nullptr, "a score head (score.weight)",
+     "the score head score.weight . x of the last attended token is Qwen2 / Llama / MistralForSequenceClassification's and is accepted on decoder handles (config.decoder_attention)",
+     "", 1, {{"score.weight", XFREE, XH, XFREE, REQUIRED}}, 'L', 1, 64, 1, 1u << DECODER, {-1}, WS_POOLED},
 };
 
 struct HeadState { int dim = 0; unsigned got = 0; };      // the free dimension (0: not known yet), one bit per tensor that was loaded
@@ -277,7 +284,7 @@ inline const char* head_first(int head, const HeadState& s) {
     return HEADS[head].t[i].name;
 }
 inline bool find_head_tensor(const char* name, int& head, int& idx) {
-    for (head = 0; head < HEAD_COUNT; ++head)
+    for (head = 0; head < HEAD_ALL; ++head)
         for (idx = 0; idx < HEADS[head].n; ++idx)
             if (strcmp(name, HEADS[head].t[idx].name) == 0) return true;
     return false;
@@ -434,7 +441,7 @@ struct Loaded {
     Family rel_fam = FAM_NONE;
     int rel_rows = 0, rel_rows_seen = 0;   // rows of DeBERTa's position table as loaded (0: never); of the tensor check_tensor saw last (mark_loaded takes it over)
     bool rel_ln[2] = {false, false};       // encoder.LayerNorm.weight / .bias were loaded
-    HeadState heads[HEAD_COUNT];
+    HeadState heads[HEAD_ALL];
     explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0), kv((size_t)layers * 4, 0) {}
 };
 // The k / v projections under the names a decoder handle shares with NomicBert (self_attn.{k,v}_proj.weight) and their biases: which of the four a resolved
@@ -546,9 +553,9 @@ struct ModelPlan {
     FfKind ff = FF_GELU;
     bool ff_gated = false;                 // w1 is [2 FF, H]
     std::vector<int> zero_fill;            // optional slots that were not loaded
-    bool head[HEAD_COUNT] = {};
-    int head_dim[HEAD_COUNT] = {};
-    int classifier = -1;                   // the head KR_POOL_CLASSIFY runs (HEAD_CLS / HEAD_MODERN_CLS), -1: none
+    bool head[HEAD_ALL] = {};
+    int head_dim[HEAD_ALL] = {};
+    int classifier = -1;                   // the head KR_POOL_CLASSIFY runs (HEAD_CLS / HEAD_MODERN_CLS / HEAD_SCORE), -1: none
     bool classify_mean = false;            // ... on the masked mean (config.classifier_pooling = 1)
     int kv_dim = 0;                        // A: columns of k and rows of V^T (hidden, or kv_heads d_h of a grouped-query decoder handle)
     int out_dim = 0, out_width = 0;        // columns of a pooled row; of the widest row `out` must hold, whatever the pool
@@ -699,7 +706,7 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
         return err(KR_EINVAL, t5 ? "a handle with config.t5_feed_forward takes its bias table as encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
                                  : "a relative attention bias under T5's name but config.t5_feed_forward was never loaded: load it before kr_encoder_finalize");
     // the heads, in the table's order (a refusal names the first tensor of the head that was loaded): family, neighbours, whole
-    for (int h = 0; h < HEAD_COUNT; ++h) {
+    for (int h = 0; h < HEAD_ALL; ++h) {
         const HeadDesc& d = HEADS[h];
         const HeadState& s = ld.heads[h];
         if (!s.got) continue;
@@ -769,13 +776,13 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;
     plan.kv_dim = kv_dim;
-    for (int h = 0; h < HEAD_COUNT; ++h) {
+    for (int h = 0; h < HEAD_ALL; ++h) {
         plan.head[h] = ld.heads[h].got != 0;
         plan.head_dim[h] = ld.heads[h].dim;
         if (plan.head[h]) plan.ws |= HEADS[h].ws;
     }
     if (plan.head[HEAD_DENSE]) plan.out_dim = plan.head_dim[HEAD_DENSE];
-    plan.classifier = plan.head[HEAD_CLS] ? (int)HEAD_CLS : plan.head[HEAD_MODERN_CLS] ? (int)HEAD_MODERN_CLS : -1;
+    plan.classifier = plan.head[HEAD_CLS] ? (int)HEAD_CLS : plan.head[HEAD_MODERN_CLS] ? (int)HEAD_MODERN_CLS : plan.head[HEAD_SCORE] ? (int)HEAD_SCORE : -1;
     plan.classify_mean = set.value(SET_CLS_POOLING) == 1;
     plan.out_width = plan.classifier >= 0 && plan.head_dim[plan.classifier] > plan.out_dim ? plan.head_dim[plan.classifier] : plan.out_dim;
     return Error{};

@@ -680,6 +680,46 @@ __global__ __launch_bounds__(CH_WAVES * 64) void k_cls_head(const float* __restr
     });
 }
 
+// The score head of a decoder cross-encoder (KR_POOL_CLASSIFY on a decoder handle with "score.weight"; the Linear without a bias behind the last token in
+// Qwen2 / Llama / MistralForSequenceClassification): logits[b, l] = W[l, :] . x_b, x = k_pool<NJ, true>'s [B, H] rows under KR_POOL_LAST's row rule, W [L, H],
+// fp32 throughout.  One stage — no Wd, no activation, no bias — so there is nothing to keep in LDS: one wave per (sequence, group of SH_LABELS labels) reads its
+// row of x once and SH_LABELS rows of W, a lane owns 4 consecutive columns per 256-column step and adds its products with fp32 FMAs in column order, and a
+// shuffle butterfly folds the 64 lane sums in a fixed order.  A logit is summed by one wave from its own sequence's row alone, so it depends neither on the
+// batch around it nor on the grid; its sum has H / 64 + 6 additions in a chain, inside the a-priori bound gamma_H sum |w_i x_i| (tests/test_gpu_decoder_reranker.py).
+// A non-finite logit of a sequence with attended tokens (seq_nk > 0) sets bit 1 of the error word, as k_cls_head's guarded variants do; the NaN row of an
+// all-masked sequence passes through.
+constexpr int SH_LABELS = 4, SH_WAVES = 4;
+__global__ __launch_bounds__(SH_WAVES * 64) void k_score_head(const float* __restrict__ pooled, const float* __restrict__ W, int B, int H, int L, float* __restrict__ out,
+                                                             const int* __restrict__ seq_nk, int* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int groups = (L + SH_LABELS - 1) / SH_LABELS;
+    const int64_t wv = (int64_t)blockIdx.x * SH_WAVES + (threadIdx.x >> 6);
+    if (wv >= (int64_t)B * groups) return;
+    const int b = (int)(wv / groups), l0 = (int)(wv % groups) * SH_LABELS;
+    const float* x = pooled + (int64_t)b * H;
+    float acc[SH_LABELS];
+#pragma unroll
+    for (int r = 0; r < SH_LABELS; ++r) acc[r] = 0.f;
+    for (int i = lane * 4; i < H; i += 256) {
+        const float4 a = *reinterpret_cast<const float4*>(x + i);
+#pragma unroll
+        for (int r = 0; r < SH_LABELS; ++r)
+            if (l0 + r < L) {
+                const float4 w = *reinterpret_cast<const float4*>(W + (int64_t)(l0 + r) * H + i);
+                acc[r] = fmaf(w.w, a.w, fmaf(w.z, a.z, fmaf(w.y, a.y, fmaf(w.x, a.x, acc[r]))));
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < SH_LABELS; ++r) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) acc[r] += __shfl_xor(acc[r], m, 64);
+        if (lane == 0 && l0 + r < L) {
+            out[(int64_t)b * L + l0 + r] = acc[r];
+            if (!(fabsf(acc[r]) < INFINITY) && seq_nk[b] > 0) atomicOr(err, 2);
+        }
+    }
+}
+
 // bge-m3's token-level heads (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT).  Both blocks are laid out by the columns of the padded [B, S] input, so the kernels
 // run one wave per SLOT (b, s) and find their packed row through slot_row: k_m3_slots writes off[b] + (rank of column s among the attended columns of its
 // row) — the order fill_seq packs them in — or -1 for a masked column.  The query-only row of a masked column 0 (CLS pooling) sits behind the attended ones
@@ -807,13 +847,15 @@ __global__ __launch_bounds__(256) void k_splade_finish(float* __restrict__ w, in
 }
 
 // CLS shortcut: row seq_off[b] + seq_cls[b] of ctx / the residual stream (hi, lo) -> row b of the compact buffers; also the compact "sequence" tables
-// (one token per sequence) and the row count for the B-row kernels that follow
+// (one token per sequence) and the row count for the B-row kernels that follow.  last_row != 0 (the last-row shortcut of a decoder handle's KR_POOL_CLASSIFY):
+// the sequence's last packed row seq_off[b] + seq_nk[b] - 1 in the CLS row's place — k_pool's KR_POOL_LAST row; an all-masked sequence has none and gathers
+// its first row slot (inside the workspace, whatever it holds: c_nk == 0 makes the pooled row NaN)
 __global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__ ctx, const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,
                                                     const int* __restrict__ seq_off, const int* __restrict__ seq_cls, const int* __restrict__ seq_nk, int H, uint16_t* __restrict__ c_ctx,
                                                     uint16_t* __restrict__ c_xb, uint8_t* __restrict__ c_xlo, int* __restrict__ c_off, int* __restrict__ c_nk,
-                                                    int* __restrict__ c_cls, int* __restrict__ d_B) {
+                                                    int* __restrict__ c_cls, int* __restrict__ d_B, int last_row) {
     const int b = blockIdx.x;
-    const int64_t src = (int64_t)seq_off[b] + seq_cls[b];
+    const int64_t src = (int64_t)seq_off[b] + (last_row ? (seq_nk[b] > 0 ? seq_nk[b] - 1 : 0) : seq_cls[b]);
     for (int i = threadIdx.x * 8; i < H; i += 256 * 8) {
         *reinterpret_cast<uint4*>(c_ctx + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(ctx + src * H + i);
         *reinterpret_cast<uint4*>(c_xb + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(xb + src * H + i);

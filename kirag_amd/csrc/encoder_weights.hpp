@@ -384,7 +384,7 @@ int enc_finalize(void* h) {
         size_t n = 0;
         if (float* dst = slot_f32(e, slot, &n)) KR_HIP(hipMemset(dst, 0, n * 4));
     }
-    for (int hd = 0; hd < HEAD_COUNT; ++hd)
+    for (int hd = 0; hd < HEAD_ALL; ++hd)
         for (int i = 0; p.head[hd] && i < HEADS[hd].n; ++i) KR_TRY(zeros(&e->head_p[hd][i], head_tensor_bytes(e, hd, i, p.head_dim[hd])));
     if (p.ff == FF_GEGLU)
         for (auto& l : e->L) KR_TRY(zeros(&l.b1p, (size_t)2 * e->cfg.intermediate * 4));

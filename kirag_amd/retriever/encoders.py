@@ -40,6 +40,7 @@ POOL_MEAN, POOL_CLS = 0, 1
 POOL_CLASSIFY = 2        # KR_POOL_CLASSIFY: the CLS row -> the classification head -> raw logits [B, num_labels] (kirag_amd.retriever.rerankers)
 CLASSIFIER_OUT = "classifier.out_proj.weight"    # [num_labels, hidden]: its rows are the width of a classify forward
 MODERN_CLASSIFIER_OUT = "classifier.weight"      # ... and ModernBertForSequenceClassification's spelling of it, on ModernBert handles
+SCORE_WEIGHT = "score.weight"                    # ... and the score head of Qwen2 / Llama / MistralForSequenceClassification, on decoder handles
 # bge-m3's token-level heads: flag bits ORed onto POOL_MEAN / POOL_CLS (KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT).  A flagged forward returns the three
 # blocks of its one output tensor (HipBertForward._blocks): dense [B, hidden], sparse [B, S] or None, colbert [B, S, P] or None
 POOL_WITH_SPARSE, POOL_WITH_COLBERT = 0x10, 0x20
@@ -647,7 +648,7 @@ class HipBertForward:
         ``POOL_CLASSIFY`` forward writes [B, L] (``classifier.weight`` on a ModernBert handle)"""
         if name == "dense.weight":
             self.out_dim = int(numel) // self.hidden
-        elif name == CLASSIFIER_OUT or (self.is_modern and name == MODERN_CLASSIFIER_OUT):
+        elif name == CLASSIFIER_OUT or (self.is_modern and name == MODERN_CLASSIFIER_OUT) or (self.is_decoder and name == SCORE_WEIGHT):
             self.num_labels = int(numel) // self.hidden
         elif name == COLBERT_WEIGHT:
             self.colbert_dim = int(numel) // self.hidden

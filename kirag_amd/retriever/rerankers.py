@@ -9,7 +9,10 @@ A cross-encoder is the encoder stack plus a head on the ``[CLS]`` / ``<s>`` row,
     ``classifier(tanh(pooler.dense(x)))``, mapped onto those names, with token types for the second segment;
   * ``ModernBertForSequenceClassification`` (Alibaba-NLP/gte-reranker-modernbert-base, ibm-granite/granite-embedding-reranker-english-r2, CrossEncoder
     fine-tunes of answerdotai/ModernBERT-*): another function, ``classifier(LayerNorm(gelu(head.dense(x))))`` on the ``[CLS]`` row or the masked mean
-    (``config.classifier_pooling``), under HF's own names; no token types, up to 8192 tokens.
+    (``config.classifier_pooling``), under HF's own names; no token types, up to 8192 tokens;
+  * ``Qwen2ForSequenceClassification`` / ``LlamaForSequenceClassification`` / ``MistralForSequenceClassification`` (decoder-LLM cross-encoders, what
+    sentence-transformers' ``CrossEncoder`` trains from Qwen2.5-0.5B, Llama-3.2-1B, TinyLlama or SmolLM2): the decoder stack of the embedders, no ``[CLS]``
+    row — ``score.weight . x`` of the LAST token, a Linear without a bias (``DecoderReranker``, below).
 
 ``XLMRobertaReranker`` / ``BertReranker`` / ``ModernBertReranker`` ARE those HF classes (``from_pretrained`` / ``save_pretrained`` / ``.to()`` keep working); in ``eval()`` mode their
 forward runs in ``libkirag_amd.so`` (``KR_POOL_CLASSIFY``) and returns ``SequenceClassifierOutput(logits=[B, num_labels])`` on the GPU without autograd
@@ -20,17 +23,21 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import json
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
-from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, ModernBertConfig, ModernBertForSequenceClassification,
-                          XLMRobertaForSequenceClassification)
+from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, LlamaForSequenceClassification, MistralForSequenceClassification,
+                          ModernBertConfig, ModernBertForSequenceClassification, Qwen2ForSequenceClassification, XLMRobertaForSequenceClassification)
 from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
-from .encoders import (DEBERTA_TYPE, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, HipBertForward, _HipModuleMixin, _refuser, check_deberta_config,
-                       check_heads, check_hidden, checkpoint_model_type)
+from .encoders import (DEBERTA_TYPE, DECODER_ATTENTIONS, EUROBERT_TYPE, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, ST_ATTENTION_FILE,
+                       ST_POOLING_DIR, HipBertForward, _HipModuleMixin, _refuser, _st_file, check_decoder_config, check_deberta_config, check_heads, check_hidden,
+                       checkpoint_model_type)
 from .m3 import BGEM3Model
 from .splade import SpladeModel
 
@@ -178,6 +185,189 @@ class DebertaV2Reranker(_HipClassifierMixin, DebertaV2ForSequenceClassification)
         return [("classifier.dense.weight", module.pooler.dense.weight), ("classifier.dense.bias", module.pooler.dense.bias)]
 
 
+DECODER_RERANKER_TYPES = ("qwen2", "llama", "mistral")
+
+
+def decoder_rename(name: str) -> str:
+    """``Qwen2ForSequenceClassification`` / ``Llama...`` / ``Mistral...`` parameter name -> the library's: the backbone loses its ``model.`` prefix (the names
+    the decoder embedders send), ``score.weight`` is the library's own spelling"""
+    return _strip(name, "model.")
+
+
+def config_num_labels(config) -> int:
+    """``num_labels`` of an HF config or of the dict of a ``config.json`` (where it is the length of ``id2label``; HF's default is 2)"""
+    if isinstance(config, dict):
+        return len(config["id2label"]) if config.get("id2label") is not None else int(config.get("num_labels", 2))
+    return int(config.num_labels)
+
+
+def check_decoder_reranker_config(config) -> dict:
+    """``NotImplementedError`` beginning ``model_type='<type>':`` for a decoder cross-encoder the kernels do not compute — from the config alone: no weight has
+    been read and the library is not loaded.  Everything ``check_decoder_config`` refuses for the embedders, in its order (128-wide heads included), then
+    ``num_labels`` > 64.  EuroBERT is a decoder stack for the embedders, but ``EuroBertForSequenceClassification`` has another head (dense -> activation ->
+    classifier over ``clf_pooling``) and is refused by name.  ``config``: the HF config or the dict of a ``config.json``."""
+    mt = config.get("model_type") if isinstance(config, dict) else config.model_type
+    refuse = _refuser(mt)
+    if mt == EUROBERT_TYPE:
+        refuse("EuroBertForSequenceClassification's head is dense -> activation -> classifier over clf_pooling, not the score head of the decoder "
+               f"rerankers: they run for {DECODER_RERANKER_TYPES}")
+    if mt not in DECODER_RERANKER_TYPES:
+        refuse(f"the decoder rerankers run for {DECODER_RERANKER_TYPES}")
+    d = check_decoder_config(config)
+    labels = config_num_labels(config)
+    if labels > MAX_LABELS:
+        refuse(f"num_labels={labels}: the score head of the HIP encoder holds at most {MAX_LABELS} labels")
+    return d
+
+
+class _HipDecoderClassifierMixin(_HipClassifierMixin):
+    """A decoder LLM used as a cross-encoder: ``logits = score.weight . x`` with x the final-norm row of the LAST token, no bias (HF's
+    ``GenericForSequenceClassification``).  ``train()`` mode is HF's own forward; eval mode sends the backbone under the decoder embedders' names plus
+    ``score.weight`` and runs ``KR_POOL_CLASSIFY`` with the attention mask.
+
+    The last token.  HF picks the rightmost column with ``input_ids != config.pad_token_id``; the library picks the HIGHEST ATTENDED COLUMN of
+    ``attention_mask``.  The two agree whenever ``attention_mask == (input_ids != pad_token_id)`` — what a tokenizer's padding produces, right or left — and
+    where they differ (a pad id inside the text, a mask with its own idea of the end) the library follows the mask.  A config without ``pad_token_id`` is
+    served as HF serves it, from the last column: the eval forward then needs an all-ones mask (or none) or batch 1, like HF's.
+
+    ``attention`` ("causal", the default, / "bidirectional") is the ``from_pretrained`` kwarg of the decoder embedders with the same meaning, else the
+    checkpoint's ``1_Pooling/attention.json``; ``save_pretrained`` writes that file for a bidirectional twin only, so a causal one saves an ordinary
+    ``...ForSequenceClassification`` folder.  ``train()`` mode of a bidirectional twin feeds HF the 4-D mask that admits every attended key."""
+    _hip_rename = staticmethod(decoder_rename)
+
+    def __init__(self, config, **kwargs):
+        check_decoder_reranker_config(config)          # refuses what the kernels do not compute when the model is made, not at its first forward
+        super().__init__(config, **kwargs)
+        self._decoder_attention = 1.0
+
+    @staticmethod
+    def _check_attention(attention) -> None:
+        if attention not in DECODER_ATTENTIONS:
+            raise ValueError(f"attention={attention!r}: one of {sorted(DECODER_ATTENTIONS)}")
+
+    def set_attention(self, attention: str) -> None:
+        self._check_attention(attention)
+        if DECODER_ATTENTIONS[attention] != self._decoder_attention:
+            self._decoder_attention = DECODER_ATTENTIONS[attention]
+            self._hip = None                            # the mask of a handle is fixed at its first finalize
+
+    @property
+    def attention(self) -> str:
+        return {v: k for k, v in DECODER_ATTENTIONS.items()}[self._decoder_attention]
+
+    def last_token_index(self, input_ids: Tensor, attention_mask: Tensor) -> Tensor:
+        """[B] the column the eval forward reads: the highest attended one (0 for a row without any; its logits are NaN)"""
+        cols = torch.arange(attention_mask.shape[1], device=attention_mask.device)
+        return ((attention_mask != 0) * (cols + 1)).argmax(dim=1)
+
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, **kwargs):
+        if not self.training:
+            if attention_mask is None:
+                attention_mask = torch.ones_like(input_ids)
+            if self.config.pad_token_id is None and input_ids.shape[0] != 1 and not bool((attention_mask != 0).all()):
+                raise ValueError("Cannot handle a padded batch if no padding token is defined (config.pad_token_id is None): pass an all-ones mask or batch 1")
+            return SequenceClassifierOutput(logits=self._hip_forward(input_ids, attention_mask, None))      # decoders have no token types
+        if self._decoder_attention == 0.0 and attention_mask is not None:
+            # [B, 1, S, S] additive: every attended key column for every query column, in the place of HF's causal mask
+            dtype = next(self.parameters()).dtype
+            m = torch.zeros(attention_mask.shape, dtype=dtype, device=attention_mask.device).masked_fill(attention_mask == 0, torch.finfo(dtype).min)
+            attention_mask = m[:, None, None, :].expand(-1, 1, attention_mask.shape[1], -1).contiguous()
+        return self._hf_base.forward(self, input_ids=input_ids, attention_mask=attention_mask, **kwargs)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        attention = kwargs.pop("attention", None)
+        if attention is not None:
+            cls._check_attention(attention)
+        check_decoder_reranker_config(checkpoint_model_type(pretrained_model_name_or_path, kwargs)[1])     # from config.json alone, before a weight is read
+        if attention is None:
+            path = _st_file(pretrained_model_name_or_path, f"{ST_POOLING_DIR}/{ST_ATTENTION_FILE}", kwargs)
+            if path is not None:
+                with open(path) as f:
+                    attention = json.load(f).get("attention")
+                cls._check_attention(attention)
+        model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if attention is not None:
+            model.set_attention(attention)
+        return model
+
+    def save_pretrained(self, save_directory, *args, **kwargs):
+        out = super().save_pretrained(save_directory, *args, **kwargs)
+        if self._decoder_attention == 0.0:
+            os.makedirs(os.path.join(save_directory, ST_POOLING_DIR), exist_ok=True)
+            with open(os.path.join(save_directory, ST_POOLING_DIR, ST_ATTENTION_FILE), "w") as f:
+                json.dump({"attention": self.attention}, f, indent=2)
+        return out
+
+
+class Qwen2Reranker(_HipDecoderClassifierMixin, Qwen2ForSequenceClassification):
+    """Qwen2Model (causal) -> last attended token -> score (CrossEncoder fine-tunes of Qwen2 / Qwen2.5-0.5B ... 1.5B)"""
+    _hf_base = Qwen2ForSequenceClassification
+
+
+class LlamaReranker(_HipDecoderClassifierMixin, LlamaForSequenceClassification):
+    """LlamaModel (causal) -> last attended token -> score (CrossEncoder fine-tunes of Llama-3.2-1B, TinyLlama, SmolLM2)"""
+    _hf_base = LlamaForSequenceClassification
+
+
+class MistralReranker(_HipDecoderClassifierMixin, MistralForSequenceClassification):
+    """MistralModel (causal, no sliding window) -> last attended token -> score"""
+    _hf_base = MistralForSequenceClassification
+
+
+_DECODER_RERANKERS = {"qwen2": Qwen2Reranker, "llama": LlamaReranker, "mistral": MistralReranker}
+
+
+class DecoderReranker:
+    """``from_pretrained`` of the decoder rerankers by ``model_type`` (``qwen2`` / ``llama`` / ``mistral``), as ``DecoderE5Encoder`` dispatches the embedders;
+    anything else is refused by name.  ``from_causal_lm`` folds a causal-LM "yes / no" reranker into a one-label one."""
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        model_type, _ = checkpoint_model_type(pretrained_model_name_or_path, kwargs, default=None)
+        if model_type not in _DECODER_RERANKERS:
+            check_decoder_reranker_config({"model_type": model_type})      # refuses by name (EuroBERT with the sentence about its head)
+        return _DECODER_RERANKERS[model_type].from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)      # (checks config.json before a weight is read)
+
+    @classmethod
+    def from_causal_lm(cls, path, positive_token_id: int, negative_token_id: Optional[int] = None, **kwargs):
+        """A one-label reranker from a causal-LM folder (``Qwen2ForCausalLM`` / ``LlamaForCausalLM`` / ``MistralForCausalLM``): a "yes / no" reranker scores a
+        pair by the difference of two LM-head logits at the last token, ``lm_head[pos] . x - lm_head[neg] . x``, which is the one-label score head
+        ``score.weight = lm_head[pos] - lm_head[neg]`` (``lm_head[pos]`` alone when ``negative_token_id`` is None).  The LM-head rows are the
+        ``embed_tokens`` rows when the embeddings are tied and the folder holds no ``lm_head.weight``.  The result is an ordinary twin:
+        ``save_pretrained`` writes a ``...ForSequenceClassification`` folder that ``BGEReranker.from_pretrained`` loads.
+
+        The prompt template, the instruction prefix and the yes / no token ids of a published LLM reranker are the caller's business: the scores mean what
+        its authors say only on inputs built their way.  No such checkpoint was available to check this recipe against."""
+        from transformers import AutoConfig, AutoModelForCausalLM
+        attention = kwargs.pop("attention", None)
+        config = AutoConfig.from_pretrained(path, **{k: v for k, v in kwargs.items() if k != "config"})
+        d = config.to_dict()
+        d["num_labels"] = 1
+        d.pop("id2label", None); d.pop("label2id", None)
+        check_decoder_reranker_config(d)                # from config.json alone, before a weight is read
+        lm = AutoModelForCausalLM.from_pretrained(path, **kwargs)
+        rows = lm.get_output_embeddings().weight.detach()       # lm_head.weight, or the tied embed_tokens.weight
+        V = rows.shape[0]
+        for t in (positive_token_id, negative_token_id):
+            if t is not None and not 0 <= int(t) < V:
+                raise ValueError(f"token id {t} outside the {V} rows of the LM head")
+        score = rows[int(positive_token_id)].float().clone()
+        if negative_token_id is not None:
+            score -= rows[int(negative_token_id)].float()
+        config.num_labels = 1
+        config.architectures = None
+        model = _DECODER_RERANKERS[config.model_type](config)
+        res = model.model.load_state_dict(lm.model.state_dict(), strict=True)
+        assert not res.missing_keys and not res.unexpected_keys, res
+        with torch.no_grad():
+            model.score.weight.copy_(score[None].to(model.score.weight.dtype))
+        model.to(next(lm.parameters()).dtype)
+        if attention is not None:
+            model.set_attention(attention)
+        return model.eval()
+
+
 class BGEReranker:
     """The registry's entry: ``from_pretrained`` reads the checkpoint's ``config.json`` and returns the twin of its ``model_type``."""
 
@@ -194,8 +384,10 @@ class BGEReranker:
         if model_type in (DEBERTA_TYPE, "deberta"):
             check_deberta_config(cfg_dict, head=True)      # from config.json alone: before a weight is read
             return DebertaV2Reranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r}, {DEBERTA_TYPE!r} and {ROBERTA_TYPES} checkpoints "
-                                  "(the classification heads of other families are other functions)")
+        if model_type in DECODER_RERANKER_TYPES or model_type == EUROBERT_TYPE:      # (EuroBERT: refused there, with the sentence that says why)
+            return DecoderReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r}, {DEBERTA_TYPE!r}, {ROBERTA_TYPES} and "
+                                  f"{DECODER_RERANKER_TYPES} checkpoints (the classification heads of other families are other functions)")
 
 
 RERANKER_MAP = {"BGEReranker": BGEReranker}

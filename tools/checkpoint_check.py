@@ -33,7 +33,8 @@ BERT-family checkpoints show).  This tool replaces that assertion by a measureme
 
 A sequence-classification checkpoint (config.json names an ...ForSequenceClassification architecture: BAAI/bge-reranker-*, cross-encoder/ms-marco-MiniLM-*,
 ModernBertForSequenceClassification: gte-reranker-modernbert-base, granite-embedding-reranker-english-r2, against HF fp32 with eager attention, and
-DebertaV2ForSequenceClassification: mxbai-rerank-*-v1, nli-deberta-v3-*)
+DebertaV2ForSequenceClassification: mxbai-rerank-*-v1, nli-deberta-v3-*, and the decoder cross-encoders Qwen2 / Llama / MistralForSequenceClassification:
+the score head at the last attended token, against HF fp32 with eager attention)
 is loaded as its reranker twin (kirag_amd.retriever.rerankers) instead, GPU only, and the report is the worst |logit - HF fp32 logit| over the built-in
 (question, passage) pairs — every question against every passage — for the four precision modes; the f16 range risk is the encoder's, as above.
 
@@ -59,6 +60,7 @@ import numpy as np
 import torch
 
 F16_MAX = 65504.0
+DECODER_RERANKER_TYPES = ("qwen2", "llama", "mistral")      # ...ForSequenceClassification with the score head (kirag_amd.retriever.rerankers)
 MODES = [("f16", True), ("f16", False), ("bf16", True), ("bf16", False)]      # default first; cost order: last is cheapest
 MODE_COST = {("f16", True): "default: 29.5 ms per 1000-query step", ("f16", False): "-3 %", ("bf16", True): "-3.5 %", ("bf16", False): "-7 %"}
 
@@ -244,6 +246,15 @@ def reranker_inputs(args, hf_dir, cfg):
         qs = [q for q in BASE_QUESTIONS for _ in BASE_PASSAGES]
         return RerankerCollator(tok, maxlength=args.max_length).encode_pairs(qs, BASE_PASSAGES * len(BASE_QUESTIONS))
     rng = np.random.default_rng(args.seed)
+    if cfg.model_type in DECODER_RERANKER_TYPES:      # plain right-padded pairs, no special tokens; never the pad id inside the text (mask == ids != pad: HF's last token)
+        S, lo, pad = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000), cfg.pad_token_id
+        ids = np.full((args.n, S), 0 if pad is None else pad, np.int64); mask = np.zeros((args.n, S), np.int64)
+        for r in range(args.n):
+            n = S if pad is None else int(np.clip(rng.normal(0.8 * S, 0.2 * S), 8, S))      # no pad id: HF reads the last column, so every row is full
+            row = rng.integers(lo, cfg.vocab_size, n)
+            ids[r, :n] = np.where(row == pad, lo, row) if pad is not None else row
+            mask[r, :n] = 1
+        return {"input_ids": torch.from_numpy(ids), "attention_mask": torch.from_numpy(mask)}
     if cfg.model_type in ("modernbert", "deberta-v2"):      # [CLS] q [SEP] p [SEP] with the config's special ids (DeBERTa-v3's tokenizer: 1 and 2), no token types
         S, lo = args.max_length, (5 if cfg.vocab_size <= 2000 else 1000)
         cls_id, sep_id = (cfg.cls_token_id, cfg.sep_token_id) if cfg.model_type == "modernbert" else (1, 2)
@@ -277,17 +288,19 @@ def check_reranker(hf_dir, args):
     if not torch.cuda.is_available() or args.emulate:
         raise SystemExit(f"{hf_dir}: a sequence-classification checkpoint is checked on the GPU (the torch emulation has no classification head)")
     from transformers import AutoConfig
-    modern = AutoConfig.from_pretrained(hf_dir).model_type == "modernbert"
-    kw = {"attn_implementation": "eager"} if modern else {}      # ModernBertForSequenceClassification: the reference is HF fp32 with eager attention
+    model_type = AutoConfig.from_pretrained(hf_dir).model_type
+    modern, decoder = model_type == "modernbert", model_type in DECODER_RERANKER_TYPES
+    kw = {"attn_implementation": "eager"} if modern or decoder else {}      # ModernBert / decoder ...ForSequenceClassification: the reference is HF fp32 with eager attention
     model = BGEReranker.from_pretrained(hf_dir, **kw).float().eval().to("cuda:0")
-    a = {k: v.to("cuda:0") for k, v in reranker_inputs(args, hf_dir, model.config).items() if not (modern and k == "token_type_ids")}
+    a = {k: v.to("cuda:0") for k, v in reranker_inputs(args, hf_dir, model.config).items() if not ((modern or decoder) and k == "token_type_ids")}
     with torch.no_grad():
         ref = model._hf_base.forward(model, **a).logits.double().cpu().numpy()
     print(f"# {hf_dir}: {type(model).__name__}, {model.config.num_hidden_layers} layers, hidden {model.config.hidden_size}, {model.config.num_labels} label(s); "
           f"{len(ref)} pairs of up to {a['input_ids'].shape[1]} tokens; HF fp32 logits {ref.min():.3f} .. {ref.max():.3f}")
     results = []
     for dtype, lo in MODES:
-        h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename, extra=type(model)._hip_extra)
+        h = HipBertForward(model.config, 0, operand_dtype=dtype, residual_lo=lo, rename=type(model)._hip_rename, extra=type(model)._hip_extra,
+                           decoder_attention=getattr(model, "_decoder_attention", None))
         h.sync(model)
         tt = a.get("token_type_ids") if getattr(model.config, "type_vocab_size", 1) > 1 else None
         out = h.forward(a["input_ids"], a["attention_mask"], POOL_CLASSIFY, tt).double().cpu().numpy()

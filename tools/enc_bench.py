@@ -144,8 +144,7 @@ def make_encoder(cfg, extra_state=None):
     shape the same draws under NomicBert's names (no position table, no linear biases, up_proj = a second draw).  extra_state: tensors and settings that must
     arrive with the first load (a head: tools/rerank_bench.py), by library name"""
     if cfg.get("model_type") in DECODER_TYPES:
-        assert extra_state is None
-        return make_decoder(cfg, not args.bidirectional, args.expanded)
+        return make_decoder(cfg, not args.bidirectional, args.expanded, extra_state)
     if cfg.get("model_type") not in ("mpnet", "nomic_bert", "modernbert", "t5", "deberta-v2", "jina_embeddings_v3"):
         assert extra_state is None
         return BS.make_hip_encoder(dev, cfg)
@@ -247,10 +246,10 @@ def make_encoder(cfg, extra_state=None):
     return enc
 
 
-def make_decoder(cfg, causal=True, expanded=False):
+def make_decoder(cfg, causal=True, expanded=False, extra_state=None):
     """a decoder handle with synthetic weights under HF's names: the BERT-shaped draws renamed (no position table, no token types, the norms in their pre-LN
     places, up_proj a second draw), k_proj / v_proj cut to the checkpoint's KV heads — loaded as they are, or with `expanded` repeated per query head first
-    (expand_kv) —, q / k / v biases for qwen2"""
+    (expand_kv) —, q / k / v biases for qwen2; extra_state: a head's tensors by library name, loaded with the rest"""
     from types import SimpleNamespace
     import transformers as T
     from kirag_amd.retriever.encoders import HipBertForward, expand_kv
@@ -278,6 +277,7 @@ def make_decoder(cfg, causal=True, expanded=False):
         st[p + "mlp.down_proj.weight"] = state[f"{b}{l}.output.dense.weight"]
     if expanded:
         st = {k: expand_kv(k, v, cfg["num_attention_heads"], cfg["num_key_value_heads"]) for k, v in st.items()}
+    st.update(extra_state or {})      # a head ("score.weight": tools/rerank_bench.py)
     enc.load_state(st)
     enc.cfg = SimpleNamespace(**cfg)
     return enc
