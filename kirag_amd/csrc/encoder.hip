@@ -15,9 +15,11 @@
 // such as "config.t5_feed_forward", a head tensor such as "dense.weight"): the families, heads and settings are described next to the tables that implement
 // them (encoder_model.hpp).
 //
-// Files.  This one: the Encoder handle, the workspace, launch selection, the forward, the entry points.  encoder_model.hpp: what a handle is (host-only).
-// encoder_weights.hpp: creation, the loader, finalize.  Device code per operand type: encoder_rows.hpp (residual-stream codec, embedding, LayerNorm, pooling),
-// encoder_proj.hpp (projections), encoder_attn.hpp (attention), encoder_pos.hpp (DeBERTa's position scores).  encoder_pack.hip: the token-packing front end.
+// Files.  This one: the Encoder handle, the workspace, the forward as a sequence of steps, the entry points.  encoder_model.hpp: what a handle is and what a
+// pool runs on it (host-only).  encoder_weights.hpp: creation, the loader, finalize.  Per operand type, device code and the launchers of its kernels, which know
+// nothing of the handle (the test-only probes under tests/capi launch through the same ones): encoder_rows.hpp (residual-stream codec, embedding, LayerNorm,
+// pooling; set_lds_once), encoder_proj.hpp (projections: launch_proj picks the main loop, launch_proj_loop launches on one), encoder_attn.hpp (attention:
+// launch_attention), encoder_pos.hpp (DeBERTa's position scores).  encoder_pack.hip: the token-packing front end.
 #include "encoder_rows.hpp"
 #include "encoder_proj.hpp"
 #include "encoder_attn.hpp"
@@ -30,7 +32,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <mutex>
 #include <vector>
 
 namespace kr {
@@ -251,189 +252,29 @@ static int ensure_ws(Encoder* e, int B, int S) {
 namespace kr {
 namespace KR_ENC_NS {
 
-static AttnBiasArgs bias_args(const Encoder* e) { return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0}; }
-static AttnWinArgs win_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->plan.half_window, e->plan.half_window, e->bias_gather ? 1 : 0}; }
+// The attention of a layer (model::AttnMode) as a compile-time constant: f(std::integral_constant<int, AM>{}), in the manner of with_epilogue
+template <class F>
+static int with_attn_mode(int am, F&& f) {
+    switch (am) {
+        case AM_PLAIN: return f(std::integral_constant<int, AM_PLAIN>{});
+        case AM_BIAS: return f(std::integral_constant<int, AM_BIAS>{});
+        case AM_WIN: return f(std::integral_constant<int, AM_WIN>{});
+        case AM_DISENT: return f(std::integral_constant<int, AM_DISENT>{});
+        case AM_CAUSAL: return f(std::integral_constant<int, AM_CAUSAL>{});
+        default: return fail(KR_ESTATE, "attention mode %d is not built into this library", am);
+    }
+}
 // causal: the window's kernels with a one-sided window — every column to the left (no column difference reaches max_pos), none to the right
 static AttnWinArgs causal_args(const Encoder* e) { return AttnWinArgs{e->tok_pos, e->cfg.max_pos, 0, e->bias_gather ? 1 : 0}; }
-// the kernel instantiation a layer's attention runs: AM_CAUSAL has none of its own
-constexpr int attn_kernel_mode(int am) { return am == AM_CAUSAL ? (int)AM_WIN : am; }
-// AM: the attention of a layer (model::AttnMode)
-// (p0, W: pos_span of the forward's S — the layout k_pos_scores wrote this layer's scores in)
+// what the attention kernels of mode AM read beside q, k and V^T: the one place that takes it from the handle (p0, W: pos_span of the forward's S — the
+// layout k_pos_scores wrote a DeBERTa layer's scores in)
 template <int AM>
-static AttnBiasArg<AM == AM_BIAS, AM == AM_WIN || AM == AM_CAUSAL, AM == AM_DISENT> attn_mode_args(const Encoder* e, int p0, int W) {
+static auto attn_mode_args(const Encoder* e, int p0, int W) {
     if constexpr (AM == AM_DISENT) return AttnDisentArgs{e->pos_sc, e->tok_pos, e->deb_bucket, e->cfg.max_pos - 1, p0, W, e->cfg.heads};
-    else if constexpr (AM == AM_BIAS) return bias_args(e);
-    else if constexpr (AM == AM_WIN) return win_args(e);
+    else if constexpr (AM == AM_BIAS) return AttnBiasArgs{e->bias_tab, e->tok_pos, e->bias_width, e->bias_gather ? 1 : 0};
+    else if constexpr (AM == AM_WIN) return AttnWinArgs{e->tok_pos, e->plan.half_window, e->plan.half_window, e->bias_gather ? 1 : 0};
     else if constexpr (AM == AM_CAUSAL) return causal_args(e);
     else return AttnNoBiasArgs{};
-}
-
-template <int DH, int HPB, int KM>
-static int& attn_lds_attr(int device) {
-    static int attr_lds_dev[64] = {};
-    return attr_lds_dev[device & 63];
-}
-// (this launch geometry is restated in run_lds of tests/capi/attn_probe.hip, the test-only probe: change both together)
-template <int DH, int HPB, int AM>
-static int launch_attn(const Encoder* e, int B, int cap, int nqt, int p0, int W, hipStream_t st) {
-    const int H = e->cfg.hidden, heads = e->cfg.heads;
-    // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
-    // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
-    const int kchunk = cap < 128 ? cap : 128;
-    const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
-    constexpr bool BIAS = AM == AM_BIAS, WIN = attn_kernel_mode(AM) == AM_WIN, DIS = AM == AM_DISENT;
-    // per device: function attributes belong to the device's code object instance (one per kernel instantiation: AM_CAUSAL shares AM_WIN's)
-    int& attr_lds = attn_lds_attr<DH, HPB, attn_kernel_mode(AM)>(e->device);
-    if (lds > attr_lds) {
-        KR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN, DIS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_lds = lds;
-    }
-    const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
-    const auto ba = attn_mode_args<AM>(e, p0, W);
-    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN, DIS>), dim3((unsigned)((heads + HPB - 1) / HPB), (unsigned)B, (unsigned)qgroups), dim3(256), lds, st, e->q, e->k, e->vT,
-                       e->ldv, e->seq_off, e->seq_nk, e->seq_nq, H, heads, kchunk, e->ctx, e->plan.kv_dim, attn_kv_mul(H / e->plan.kv_dim), ba);
-    return 0;
-}
-// (this launch geometry is restated in run_dma of tests/capi/attn_probe.hip, the test-only probe: change both together)
-template <int DH, int AM>
-static int launch_attn_dma(const Encoder* e, int B, int nqt, hipStream_t st) {
-    const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
-    const int64_t pairs = (int64_t)B * e->cfg.heads;
-    const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
-    const auto ba = attn_mode_args<AM>(e, 0, 0);
-    hipLaunchKernelGGL((k_attn_dma<DH, AM == AM_BIAS, attn_kernel_mode(AM) == AM_WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, e->q, e->k, e->vT, e->ldv,
-                       e->seq_off, e->seq_nk, e->seq_nq, e->cfg.hidden, e->capT, e->ctx, e->cfg.heads, B, qgroups, e->plan.kv_dim, attn_kv_mul(e->cfg.hidden / e->plan.kv_dim), ba);
-    return 0;
-}
-
-// the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
-// (AM_DISENT is built into the register-staged kernel only: a DeBERTa forward never asks for the ring, see enqueue_forward)
-template <int DH, int AM>
-static int launch_attention(const Encoder* e, int B, int cap, int nqt, bool long_seq, int p0, int W, hipStream_t st) {
-    if constexpr (AM != AM_DISENT) { if (long_seq) return launch_attn_dma<DH, AM>(e, B, nqt, st); }
-    if (nqt >= 3) return launch_attn<DH, 1, AM>(e, B, cap, nqt, p0, W, st);
-    if (nqt == 2) return launch_attn<DH, 2, AM>(e, B, cap, nqt, p0, W, st);
-    return launch_attn<DH, 4, AM>(e, B, cap, nqt, p0, W, st);
-}
-
-// The runtime epilogue as a compile-time constant: f(std::integral_constant<int, EPI>{}) for the epilogues of encoder_proj.hpp.  What a launch site does not
-// build for an epilogue, it excludes itself with `if constexpr`.
-template <class F>
-static int with_epilogue(int epi, F&& f) {
-    switch (epi) {
-        case EPI_QKV: return f(std::integral_constant<int, EPI_QKV>{});
-        case EPI_DENSE: return f(std::integral_constant<int, EPI_DENSE>{});
-        case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{});
-        case EPI_QKV_ROT: return f(std::integral_constant<int, EPI_QKV_ROT>{});
-        case EPI_QKV_ROTB: return f(std::integral_constant<int, EPI_QKV_ROTB>{});
-        case EPI_SWIGLU: return f(std::integral_constant<int, EPI_SWIGLU>{});
-        case EPI_GEGLU: return f(std::integral_constant<int, EPI_GEGLU>{});
-        case EPI_RELU: return f(std::integral_constant<int, EPI_RELU>{});
-        case EPI_GEGLU_TANH: return f(std::integral_constant<int, EPI_GEGLU_TANH>{});
-        case EPI_SPLADE: return f(std::integral_constant<int, EPI_SPLADE>{});
-        default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
-    }
-}
-
-static int set_lds_once(const void* kern, int lds, int device);
-// (this launch geometry is restated in run_shape of tests/capi/proj_probe.hip, the test-only probe: change both together)
-template <class Shape, int STAGES, bool NT>
-static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int device, hipStream_t st) {
-    constexpr int lds = STAGES * Shape::STAGE_BYTES + Shape::NWAVE * EPI_STAGE_BYTES;   // 160 KiB for the 256x256 tile: the whole LDS of a CU
-    // function attributes belong to the device's code-object instance: once per (kernel, device)
-    auto go = [&](auto kern) -> int {
-        KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(Shape::NTHREADS), lds, st, a);
-        return 0;
-    };
-    const bool ant = a.ant && Shape::BM == 256;   // the non-temporal activation operand exists for the ping-pong loop only
-    return with_epilogue(epi, [&](auto tag) -> int {
-        constexpr int EPI = decltype(tag)::value;
-        if constexpr (EPI == EPI_QKV_ROTB && Shape::BM == 256)      // not on the 256 x 256 tile (launch_proj): the bias quads next to its 128 accumulators spill
-            return fail(KR_EINVAL, "projection epilogue %d is not built for the 256 x 256 tile", epi);
-        else if constexpr (EPI == EPI_SPLADE && NT)                 // stores no rows: one instantiation per shape (launch_proj clears nt)
-            return fail(KR_EINVAL, "projection epilogue %d has no non-temporal stores", epi);
-        else if constexpr (EPI == EPI_DENSE) return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>);
-        else return go(&k_proj<EPI, Shape, STAGES, NT>);
-    });
-}
-template <class Shape, int STAGES>
-static int launch_proj_shape(int epi, const ProjArgs& a, int blocks, int device, hipStream_t st) {
-    return a.nt ? launch_proj_shape_nt<Shape, STAGES, true>(epi, a, blocks, device, st) : launch_proj_shape_nt<Shape, STAGES, false>(epi, a, blocks, device, st);
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), safe against concurrent first launches from several host threads (a query
-// encoder and a corpus encoder on one device: ADVICE r04) and with the outcome cached, so that a failing attribute is reported by every launch
-static int set_lds_once(const void* kern, int lds, int device) {
-    struct Ent { const void* k; int dev; hipError_t rc; };
-    static std::mutex mu;
-    static std::vector<Ent> done;
-    std::lock_guard<std::mutex> lock(mu);
-    for (const Ent& x : done)
-        if (x.k == kern && x.dev == device) { if (x.rc != hipSuccess) return fail(KR_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(x.rc)); return 0; }
-    const hipError_t rc = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    done.push_back({kern, device, rc});
-    if (rc != hipSuccess) return fail(KR_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(rc));
-    return 0;
-}
-
-// tile shape per launch: when the 256x256 tiling has fewer tiles than ~5/8 of the CUs (small batches: the reference's per_gpu_batch_size 4-8, the KiRAG
-// loop's triple batches, a 1/8 slice of a query batch) the 128x128 tiling gives 4x the parallelism at a quarter of the per-tile latency
-// (the grids, block sizes, LDS bytes, skinny rings and ldx / ldo defaults below are restated in run_epi / run_skinny of tests/capi/proj_probe.hip, the test-only
-// probe: change both together)
-static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const Encoder* e, hipStream_t st) {
-    const Knobs& kn = e->kn;
-    const int num_cu = e->num_cu, device = e->device;
-    ProjArgs a = a_in;
-    if (a.ldx == 0) a.ldx = a.K;
-    if (a.ldo == 0) a.ldo = a.F;
-    a.pw = kn.pw;
-    a.epi_prio = kn.epi_prio;
-    // store policy by output size (see ProjArgs::nt)
-    a.nt = epi != EPI_SPLADE && max_tokens * (int64_t)(epi_gated(epi) ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
-    // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
-    // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
-    // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
-    a.ant = a.K > a.H ? 1 : 0;
-    const int64_t big_tiles = ((max_tokens + 255) / 256) * ((a.F + 255) / 256);
-    const int64_t small_tiles = ((max_tokens + 127) / 128) * ((a.F + 127) / 128);
-    const int force = kn.force_tile;
-    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * 5) || epi == EPI_QKV_ROTB;   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
-    // a handful of token rows: the skinny loop, one tile per block (latency chain: the operand stream of the launch spread over as many CUs as it has
-    // tiles).  32 x 32 tiles while there is at most one per CU, 64 x 64 (four multiplying waves share every staged K-tile: half the L2 -> LDS bytes per
-    // output element) up to four 32 x 32 tiles' worth per CU — the crossover against the 128x128 producer / consumer loop measured in round 1.
-    // KIRAG_AMD_PROJ_TILE = 32 / 64 forces one of the two.
-    const int64_t skinny_tiles = ((max_tokens + 31) / 32) * (a.F / 32);
-    if (force == 32 || force == 64 || (force == 0 && skinny_tiles <= 4 * (int64_t)num_cu && (max_tokens + 31) / 32 <= 65535)) {
-        const bool one = force == 32 || (force == 0 && skinny_tiles <= num_cu);
-        auto launch = [&](auto shape_tag, auto kern) -> int {
-            constexpr int WM = decltype(shape_tag)::value, RING = WM == 1 ? 16 : 8;
-            using G = SkinnyGeom<WM, WM>;
-            constexpr int lds = RING * G::STAGE;
-            const dim3 grid((unsigned)(a.F / (32 * WM)), (unsigned)((max_tokens + 32 * WM - 1) / (32 * WM)));
-            KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
-            hipLaunchKernelGGL(kern, grid, dim3(G::THREADS), lds, st, a);
-            return 0;
-        };
-        auto pick = [&](auto shape_tag) -> int {
-            constexpr int WM = decltype(shape_tag)::value, RING = WM == 1 ? 16 : 8;
-            return with_epilogue(epi, [&](auto tag) -> int { return launch(shape_tag, &k_proj_skinny<decltype(tag)::value, RING, WM, WM>); });
-        };
-        return one ? pick(std::integral_constant<int, 1>{}) : pick(std::integral_constant<int, 2>{});
-    }
-    if (!small) return launch_proj_shape<ShapeBig, 2>(epi, a, num_cu, device, st);
-    // producer/consumer loop (one persistent block per CU): at most one tile per CU, or more than two (measured: 600 tiles -7 % vs the streaming loop
-    // with two blocks per CU; between one and two tiles per CU the two co-resident streaming blocks quantise better).  130 forces it, 128 the streaming loop
-    if (((small_tiles <= num_cu || small_tiles > 2 * num_cu) && force != 128) || force == 130) {
-        constexpr int lds = SPLIT_RING * ShapeSplit::STAGE_BYTES + 4 * EPI_STAGE_BYTES;
-        auto go = [&](auto kern) -> int {
-            KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
-            hipLaunchKernelGGL(kern, dim3(num_cu), dim3(SPLIT_THREADS), lds, st, a);
-            return 0;
-        };
-        return with_epilogue(epi, [&](auto tag) -> int { return go(&k_proj_split<decltype(tag)::value>); });
-    }
-    return launch_proj_shape<ShapeSmall, 2>(epi, a, 2 * num_cu, device, st);
 }
 
 // The input of a forward as it lies in the workspace.  Padded: [B,S] ids / mask in d_ids / d_mask, with has_tt the caller's token types in d_tt (else all
@@ -452,225 +293,274 @@ struct RowSet {
     uint16_t* rb; uint8_t* rlo;  // ModernBert handles: the pre-LN residual stream of these rows (rlo: nullptr without use_lo)
 };
 
-// every kernel of one forward, enqueued on `st` (input already in the workspace, result left in e->out)
+// Row width as a compile-time constant, f(std::integral_constant<int, N>{}) in the manner of with_epilogue: the LayerNorm family of kernels covers a row in
+// NS steps of 512 elements, the pool and head family in NJ steps of 256
+template <int N> using width_c = std::integral_constant<int, N>;
+template <class F> static auto with_ln_width(int H, F&& f) { return H <= 512 ? f(width_c<1>{}) : H <= 1024 ? f(width_c<2>{}) : f(width_c<4>{}); }
+template <class F> static auto with_pool_width(int H, F&& f) { return H <= 256 ? f(width_c<1>{}) : H <= 512 ? f(width_c<2>{}) : H <= 1024 ? f(width_c<4>{}) : f(width_c<8>{}); }
+
+// What the steps of one forward share (enqueue_forward fills it in)
+struct Forward {
+    Encoder* e; hipStream_t st;
+    int B, S, H, FF; float eps;
+    model::ForwardPool pool;     // what the requested pool packs like, selects and runs behind the last layer
+    int flags; float* tok_out;   // enqueue_forward
+    bool disent;                 // a DeBERTa handle: every sequence through k_attn_lds (the mode is not built into k_attn_dma)
+    bool long_seq;               // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
+    bool shortcut;               // the last layer finishes on one gathered row per sequence (cls_rows)
+    int align;                   // sequence offsets: multiple of 8 tokens under long_seq so that V^T chunks start 16-B aligned, else of 4
+    int nqt_max;                 // q-tiles of the longest possible sequence
+    int span_p0, span_W;         // pos_span of S (DeBERTa handles)
+    int64_t maxT;                // upper bound of the packed token count (each sequence is padded to `align`)
+    unsigned row_grid, ln_grid;  // one wave per row; k_ln is grid-stride (its parameters stay in registers across rows)
+    ProjLaunch pl;
+    AttnOperands attn;
+    RowSet all_rows, cls_rows;
+};
+
+// T5 and decoder handles: the embedding row is the residual stream itself, xb = block 0's attention norm of it
+static bool embed_is_residual(const model::ModelPlan& p) { return p.pos == model::POS_BIAS_ONLY || p.family == model::DECODER; }
+
+// the fields every projection site assigns (ldx / ldo = 0: K / F)
+static void proj(ProjArgs& a, const uint16_t* W, const uint16_t* X, int F, int K, const float* bias, uint16_t* out0, int64_t ldx = 0, int64_t ldo = 0) {
+    a.W = W; a.X = X; a.F = F; a.K = K; a.bias = bias; a.out0 = out0; a.ldx = ldx; a.ldo = ldo;
+}
+
+static void enqueue_embed(const Forward& f) {
+    using namespace model;
+    Encoder* e = f.e;
+    const ModelPlan& p = e->plan;
+    const int H = f.H;
+    if (p.rotary) hipLaunchKernelGGL(k_rot_pos, dim3(f.B), dim3(64), 0, f.st, e->seq_off, e->seq_nq, f.align, e->tok_pos, e->tok_rpos);
+    if (embed_is_residual(p)) {
+        const auto embed_kernel = with_ln_width(H, [](auto ns) { return &k_embed_rms<decltype(ns)::value>; });
+        hipLaunchKernelGGL(embed_kernel, dim3(f.row_grid), dim3(256), 0, f.st, e->tok_id, e->d_T, e->word, e->elng, f.eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
+    } else {
+        const bool no_pos = p.pos == POS_ROTARY || f.disent;      // a zero row in place of a position row
+        hipLaunchKernelGGL(k_embed_ln, dim3(f.row_grid), dim3(256), 0, f.st, e->tok_id, no_pos ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T,
+                           e->word, no_pos ? e->zero_row : e->pos, e->type, e->elng, e->elnb, f.eps, H,
+                           e->use_lo ? e->xlo : nullptr, e->xb);
+    }
+}
+
+// The norm behind a residual projection of a layer's tail, on the rows of r.  Post-LN: xb = LayerNorm(y + bias + xb), the low half read at r.lo and written to
+// lo_out.  Pre-LN (k_ln16_pre; RMS on T5 handles): (rin, rin_lo) + y + bias is the residual stream, stored to (rb_out, r.rlo) unless rb_out is nullptr; xb =
+// the NEXT norm of it, its low half to lo_out unless that is nullptr.
+// LayerNorm streams: y (dead after the kernel) and the low half (next read by the next LayerNorm, ~600 MiB of traffic later) are loaded / stored
+// non-temporally — they do not displace the 16-bit stream the next GEMM reads: -1.3 % forward at 1024 x 128 tokens, -0.1...0.5 % at 1000 x 32; 8 blocks
+// per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
+static void launch_norm(const Forward& f, const RowSet& r, const float* bias, const float* g, const float* b, const uint16_t* rin, const uint8_t* rin_lo, uint16_t* rb_out,
+                        uint8_t* lo_out) {
+    const model::ModelPlan& p = f.e->plan;
+    if (p.pre_ln) {
+        const auto ln_tail_kernel = p.rms ? with_ln_width(f.H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1, true>; })
+                                          : with_ln_width(f.H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1>; });
+        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, f.st, r.y, bias, r.rows, g, b, f.eps, f.H, rin, rin_lo, rb_out, r.rlo, lo_out, r.xb);
+    } else {
+        const auto ln_kernel = with_ln_width(f.H, [](auto ns) { return &k_ln16<decltype(ns)::value, 7>; });
+        hipLaunchKernelGGL(ln_kernel, dim3(r.ln_grid), dim3(256), 0, f.st, r.y, bias, r.rows, g, b, f.eps, f.H, (const uint8_t*)r.lo, lo_out, r.xb);
+    }
+}
+// The tail of a layer on the rows of r: Wo + residual -> norm, W1 + activation, W2 + residual -> norm.  Post-LN: the norms are LayerNorms of the sum.  Pre-LN
+// (ModernBert, T5 and decoder handles) on the same five launches: r += y + b, xb = the next norm of r.  (rin, rin_lo): the residual stream as a pre-LN layer
+// finds it — r.rb / r.rlo, or for layer 0 on all rows the embedding LayerNorm's output itself (xb / xlo: attn_norm of layer 0 is the identity)
+static int enqueue_tail(const Forward& f, ProjArgs a, const LayerW& l, const RowSet& r, bool last, const uint16_t* rin, const uint8_t* rin_lo) {
+    static constexpr int FF_EPI[] = {EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH};   // by FfKind
+    const model::ModelPlan& p = f.e->plan;
+    const int H = f.H, FF = f.FF;
+    const bool pre = p.pre_ln;
+    a.Tp = r.rows;
+    // attention.output.dense / attn.Wo, then the norm: xb = LayerNorm(y + b + xb), or r += y + b; xb = mlp_norm(r)
+    proj(a, l.wo, r.ctx, H, H, l.bo_eff, r.y);
+    KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, f.pl, f.st));
+    launch_norm(f, r, l.bo_eff, l.ln1g, l.ln1b, rin, rin_lo, r.rb, pre ? nullptr : r.lo);
+    // intermediate.dense + GELU, or gate_proj | up_proj / mlp.Wi (input | gate) as one GEMM of 2 FF columns + SwiGLU / GEGLU: h [rows, FF] either way.  A T5
+    // handle: wi + relu, or wi_0 | wi_1 the same way + gelu_new, no bias
+    proj(a, l.w1, r.xb, p.ff_gated ? 2 * FF : FF, H, pre ? l.b1p : l.b1, r.h, 0, FF);
+    KR_TRY(launch_proj(FF_EPI[p.ff], a, r.max_rows, f.pl, f.st));
+    // output.dense / mlp.Wo, then the norm.  The LAST one always writes the low half: pooling and kr_encoder_last_hidden read the final hidden state with 16
+    // mantissa bits.  Pre-LN: xb = the next layer's attn_norm(r), or final_norm(r), behind which nothing reads r
+    proj(a, l.w2, r.h, H, FF, l.b2, r.y, FF, 0);
+    KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, f.pl, f.st));
+    launch_norm(f, r, l.b2, l.ln2g, l.ln2b, r.rb, r.rlo, last ? nullptr : r.rb, last ? r.lo_last : pre ? nullptr : r.lo);
+    return 0;
+}
+
+// one layer: q | k | v^T, attention, for the last layer of a shortcut forward the gather, the tail
+static int enqueue_layer(const Forward& f, size_t li) {
+    using namespace model;
+    static constexpr int QKV_EPI[] = {EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB};   // by QkvKind
+    Encoder* e = f.e;
+    const ModelPlan& p = e->plan;
+    const LayerW& l = e->L[li];
+    const LayerPlan& lp = p.layers[li];
+    const bool first = li == 0, last = li + 1 == e->L.size(), pre = p.pre_ln;
+    const int H = f.H;
+    const bool local = lp.attn == AM_WIN;      // a ModernBert handle's sliding-window layer: its own rotary table, windowed attention
+    ProjArgs a{};
+    a.Tp = e->d_T; a.H = H;
+    a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
+    // q | k | v^T in one GEMM (F = H + 2A: 3H unless k and v are a grouped-query decoder's)
+    a.A = p.kv_dim;
+    proj(a, l.wqkv, e->xb, H + 2 * p.kv_dim, H, l.bqkv, e->q);
+    a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv;
+    KR_TRY(launch_proj(QKV_EPI[lp.qkv], a, f.maxT, f.pl, f.st));
+    auto attend = [&](auto dh) -> int {
+        constexpr int DH = decltype(dh)::value;
+        if (lp.attn == AM_DISENT) {      // q . PK and k . PQ of every packed row, for the bias tiles of this layer's attention
+            // (k_pos_scores reads k with q's pitch H and head h of both: a DeBERTa handle has one KV head per query head, describe() refuses any other)
+            if (p.kv_dim != H) return fail(KR_ESTATE, "a DeBERTa handle with k / v width %d != hidden", p.kv_dim);
+            const dim3 grid((unsigned)((f.maxT + POS_ROWS - 1) / POS_ROWS), (unsigned)e->cfg.heads);
+            hipLaunchKernelGGL(k_pos_scores<DH>, grid, dim3(256), 0, f.st, e->q, e->k, e->d_T, H, e->cfg.heads, l.pk16, l.pq16, (int)round_up(2 * p.deb_buckets, 32), f.span_p0, f.span_W,
+                               e->pos_sc);
+        }
+        return with_attn_mode(lp.attn, [&](auto am) -> int {
+            return launch_attention<DH>(f.attn, (int)round_up(f.S, 32), f.nqt_max, f.long_seq, attn_mode_args<decltype(am)::value>(e, f.span_p0, f.span_W), e->device, f.st);
+        });
+    };
+    if (H == 32 * e->cfg.heads) KR_TRY(attend(std::integral_constant<int, 32>{})); else KR_TRY(attend(std::integral_constant<int, 64>{}));
+    // CLS shortcut: only the CLS row of every sequence is read after the last layer: gather those rows and finish the layer on B rows (same kernels, same
+    // arithmetic per row: the projection loops are bit-identical for every tiling and LayerNorm is per row, so the embedding does not change by one bit)
+    // (a pre-LN handle: the residual stream travels in the place of xb — the operand is rewritten by the first norm of the tail)
+    // (a T5 or decoder handle: the embedding launch has stored the residual stream itself, layer 0 finds it like every layer)
+    const bool in_rb = pre && (!first || embed_is_residual(p));
+    const uint16_t* rin = in_rb ? e->rb : e->xb;
+    const uint8_t* rin_lo = in_rb ? f.all_rows.rlo : f.all_rows.lo;
+    if (!(last && f.shortcut)) return enqueue_tail(f, a, l, f.all_rows, last, rin, rin_lo);
+    hipLaunchKernelGGL(k_gather_cls, dim3(f.B), dim3(256), 0, f.st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
+                       pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, f.pool.score ? 1 : 0);
+    return enqueue_tail(f, a, l, f.cls_rows, last, e->c_rb, f.cls_rows.rlo);
+}
+// KR_POOL_SPLADE behind the last layer: the MLM head on every packed row, max over each sequence's rows, log1p — into f.tok_out [B, vocab]
+static int enqueue_splade_head(const Forward& f) {
+    using namespace model;
+    Encoder* e = f.e;
+    const int H = f.H, V = e->cfg.vocab;
+    // t = LayerNorm(gelu(Wt x + bt)) of the packed rows: y <- EPI_GELU, q <- k_ln16_head (both buffers are free behind the last layer; xb / xlo keep the
+    // final hidden state for kr_encoder_last_hidden)
+    ProjArgs a{};
+    a.Tp = e->d_T; a.H = H;
+    proj(a, e->hh(HEAD_MLM, 0), e->xb, H, H, e->hf(HEAD_MLM, 1), e->y);
+    KR_TRY(launch_proj(EPI_GELU, a, f.maxT, f.pl, f.st));
+    KR_HIP(hipMemsetAsync(e->row_seq, 0xff, (size_t)e->capT * 4, f.st));
+    hipLaunchKernelGGL(k_splade_rowseq, dim3(f.B), dim3(64), 0, f.st, e->seq_off, e->seq_nk, e->row_seq);
+    const auto head_ln = with_ln_width(H, [](auto ns) { return &k_ln16_head<decltype(ns)::value>; });
+    hipLaunchKernelGGL(head_ln, dim3(f.ln_grid), dim3(256), 0, f.st, e->y, e->zero_row, e->d_T, e->hf(HEAD_MLM, 2), e->hf(HEAD_MLM, 3), f.eps, H, e->row_seq, e->q, e->d_err);
+    // the decoder: [rows] x [Vpad, H]^T reduced over each sequence's rows inside the launch (EPI_SPLADE), then log1p in place
+    KR_HIP(hipMemsetAsync(f.tok_out, 0, (size_t)f.B * V * 4, f.st));
+    proj(a, e->hh(HEAD_MLM, 4), e->q, (int)extent(e->cfg, XVPAD), H, e->hf(HEAD_MLM, 5), nullptr);
+    a.row_seq = e->row_seq; a.smax = reinterpret_cast<unsigned int*>(f.tok_out); a.V = V;
+    KR_TRY(launch_proj(EPI_SPLADE, a, f.maxT, f.pl, f.st));
+    const int64_t n = (int64_t)f.B * V;
+    hipLaunchKernelGGL(k_splade_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, f.st, f.tok_out, n, e->d_err);
+    return 0;
+}
+
+// pooling (masked mean, CLS or last row, L2-normalised; raw rows for a classifier) and the head behind it, into e->out
+static int enqueue_pool_and_head(const Forward& f) {
+    using namespace model;
+    Encoder* e = f.e;
+    const ModelPlan& p = e->plan;
+    const int B = f.B, H = f.H;
+    const RowSet& r = f.shortcut ? f.cls_rows : f.all_rows;
+    const int NJ = with_pool_width(H, [](auto nj) { return (int)decltype(nj)::value; });
+    const auto pool_kernel = f.pool.classify ? with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value, true>; })
+                                             : with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value>; });
+    const int pool_lds = POOL_WAVES * NJ * 256 * 4 + POOL_WAVES * 4;
+    KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
+    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, f.st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, f.pool.select,
+                       p.head[HEAD_DENSE] || f.pool.classify ? e->pooled : e->out, e->d_err);
+    if (f.pool.score) {          // a decoder handle's score head: out [B, L] = score.weight . pooled, one launch without LDS
+        const int L = p.head_dim[HEAD_SCORE];
+        const int64_t waves = (int64_t)B * ((L + SH_LABELS - 1) / SH_LABELS);
+        hipLaunchKernelGGL(k_score_head, dim3((unsigned)((waves + SH_WAVES - 1) / SH_WAVES)), dim3(SH_WAVES * 64), 0, f.st, e->pooled, e->hf(HEAD_SCORE, 0), B, H, L, e->out, r.nk, e->d_err);
+    } else if (f.pool.classify) {
+        // the classification head: out [B, L] = Wo . act(Wd . pooled + bd) + bo, one kernel per (width, act).  HEAD_CLS {Wd, bd, Wo, bo}: tanh, or DeBERTa's
+        // erf-GELU (cls_gelu).  HEAD_MODERN_CLS {Wd, bd, norm g, norm b, Wo, bo}: Wo . LayerNorm(erf_gelu(Wd . pooled + bd)) + bo.  The GELU variants guard
+        // their result (r.nk, the error word); the tanh head takes neither
+        const int hd = p.classifier;
+        const bool gln = hd == HEAD_MODERN_CLS, gelu = gln || p.cls_gelu;
+        const auto head_kernel = with_pool_width(H, [&](auto nj) {
+            constexpr int N = decltype(nj)::value;
+            return gln ? &k_cls_head<N, true> : gelu ? &k_cls_head<N, false, true> : &k_cls_head<N>;
+        });
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(head_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));      // the widest H of the instantiation (64 KiB at 2048)
+        hipLaunchKernelGGL(head_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), CH_SEQ * 2 * H * 4, f.st, e->pooled, e->hf(hd, 0), e->hf(hd, 1), e->hf(hd, gln ? 4 : 2),
+                           e->hf(hd, gln ? 5 : 3), B, H, p.head_dim[hd], e->out, gln ? e->hf(hd, 2) : nullptr, gln ? e->hf(hd, 3) : nullptr, gln ? f.eps : 0.f,
+                           gelu ? r.nk : nullptr, gelu ? e->d_err : nullptr);
+    } else if (p.head[HEAD_DENSE]) {     // the Dense head: out [B, P] = normalize(W . pooled)
+        const int P = p.head_dim[HEAD_DENSE], dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
+        // one kernel, an LDS size per handle: the attribute is set once per device (set_lds_once) to what the largest handle needs, H = P = 2048 (64 KiB + 16 B)
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(&k_pool_dense), PD_SEQ * (2048 + 2048) * 4 + PD_SEQ * 4, e->device));
+        hipLaunchKernelGGL(k_pool_dense, dim3((B + PD_SEQ - 1) / PD_SEQ), dim3(256), dense_lds, f.st, e->pooled, e->hf(HEAD_DENSE, 0), B, H, P, e->out);
+    }
+    return 0;
+}
+
+// bge-m3's token-level blocks, straight into f.tok_out: sparse [B, S], then colbert [B, S, P]
+static int enqueue_m3_blocks(const Forward& f) {
+    using namespace model;
+    Encoder* e = f.e;
+    const int H = f.H, P = e->plan.head_dim[HEAD_COLBERT];
+    const int64_t slots = (int64_t)f.B * f.S;
+    const unsigned slot_grid = (unsigned)((slots + 3) / 4);
+    hipLaunchKernelGGL(k_m3_slots, dim3(f.B), dim3(64), 0, f.st, e->d_mask, e->seq_off, f.S, e->slot_row);
+    float* o = f.tok_out;
+    if (f.flags & KR_POOL_WITH_SPARSE) {
+        hipLaunchKernelGGL(k_m3_sparse, dim3(slot_grid), dim3(256), 0, f.st, e->xb, e->xlo, e->hf(HEAD_SPARSE, 0), e->hf(HEAD_SPARSE, 1), e->slot_row, slots, H, o, e->d_err);
+        o += slots;
+    }
+    if (f.flags & KR_POOL_WITH_COLBERT) {      // one more projection of the packed rows on the loops every layer uses, then bias + norm + scatter
+        ProjArgs a{};
+        a.Tp = e->d_T; a.H = H;
+        proj(a, e->hh(HEAD_COLBERT, 0), e->xb, P, H, e->hf(HEAD_COLBERT, 1), e->cy);
+        KR_TRY(launch_proj(EPI_DENSE, a, f.maxT, f.pl, f.st));
+        hipLaunchKernelGGL(k_m3_rows, dim3(slot_grid), dim3(256), 0, f.st, e->cy, e->hf(HEAD_COLBERT, 1), e->slot_row, slots, P, o, e->d_err);
+    }
+    return 0;
+}
+
+// every kernel of one forward, enqueued on `st` (input already in the workspace, result left in e->out): resolve the pool, pack, embed, the layers, the head
 // flags: KR_POOL_WITH_SPARSE / KR_POOL_WITH_COLBERT (pool is the base pool); tok_out: device memory for the token-level blocks, [B, S] then [B, S, P]
 // pool = KR_POOL_SPLADE: tok_out is the [B, vocab] result, used as the reduction buffer of the decoder launch; nothing is left in e->out
 static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, const Input& in, int flags = 0, float* tok_out = nullptr) {
-    const int H = e->cfg.hidden, FF = e->cfg.intermediate;
-    const float eps = e->cfg.ln_eps;
-    e->kn.read();
-    // KR_POOL_CLASSIFY reads the CLS row like KR_POOL_CLS — the query row of a masked column 0, the packed token count, the CLS shortcut — and differs behind
-    // the last LayerNorm only (k_pool's raw rows, then k_cls_head): everything up to there sees KR_POOL_CLS
-    // (ModernBert's head with config.classifier_pooling = 1 reads the masked mean: everything up to the last LayerNorm sees KR_POOL_MEAN)
     using namespace model;
     const ModelPlan& p = e->plan;
-    // (a decoder handle's score head reads KR_POOL_LAST's row: everything up to the last layer's attention sees KR_POOL_LAST)
-    const bool classify = pool == KR_POOL_CLASSIFY;
-    const bool score = classify && p.classifier == HEAD_SCORE;
-    if (classify) pool = score ? KR_POOL_LAST : p.classify_mean ? KR_POOL_MEAN : KR_POOL_CLS;
-    // KR_POOL_SPLADE packs and attends like KR_POOL_MEAN (no query-only rows) and differs behind the last LayerNorm only
-    const bool splade = pool == KR_POOL_SPLADE;
-    if (splade) pool = KR_POOL_MEAN;
-    // KR_POOL_LAST packs and attends like KR_POOL_MEAN too (no query-only row, the last layer on every row); k_pool alone sees the difference
-    const int pool_select = pool;
-    if (pool == KR_POOL_LAST) pool = KR_POOL_MEAN;
-    const int nqt_max = (S + (pool == KR_POOL_CLS ? 1 : 0) + 31) / 32;             // q-tiles of the longest possible sequence
-    const bool disent = p.pos == POS_DISENT;                                       // a DeBERTa handle: every sequence through k_attn_lds (the mode is not built into k_attn_dma)
-    const bool long_seq = nqt_max > 4 && !e->kn.attn_lds && !disent;               // > 128 tokens: the LDS-DMA attention kernel (KIRAG_AMD_ATTN_LDS=1: never)
-    int span_p0 = 0, span_W = 0;
-    if (disent) pos_span(e, S, span_p0, span_W);
-    const int align = long_seq ? 8 : 4;                                            // sequence offsets: multiple of 8 tokens so that V^T chunks start 16-B aligned
-    const PackRules rules{e->cfg.vocab, e->cfg.type_vocab, pool, align, p.pad_idx};
+    e->kn.read();
+    Forward f{};
+    f.e = e; f.st = st; f.B = B; f.S = S; f.H = e->cfg.hidden; f.FF = e->cfg.intermediate; f.eps = e->cfg.ln_eps; f.flags = flags; f.tok_out = tok_out;
+    f.pool = resolve_pool(p, pool);
+    f.pl = ProjLaunch{e->num_cu, e->device, e->kn.pw, e->kn.epi_prio, e->kn.force_tile};
+    const int cls_row = f.pool.pack == KR_POOL_CLS ? 1 : 0;      // the query-only row of a masked column 0
+    f.nqt_max = (S + cls_row + 31) / 32;
+    f.disent = p.pos == POS_DISENT;
+    f.long_seq = f.nqt_max > 4 && !e->kn.attn_lds && !f.disent;
+    if (f.disent) pos_span(e, S, f.span_p0, f.span_W);
+    f.align = f.long_seq ? 8 : 4;
+    const PackRules rules{e->cfg.vocab, e->cfg.type_vocab, f.pool.pack, f.align, p.pad_idx};
     const SeqTables seq{e->seq_nk, e->seq_has0, e->seq_nq, e->seq_off, e->seq_cls, e->d_T};
     const TokTables tok{e->tok_id, e->tok_pos, e->tok_type, e->tok_epos, e->d_err};
     if (in.ragged) pack_ragged(e->rag_ids(), e->rag_lens(), e->rag_in_off(), B, S, in.total, rules, seq, tok, st);
     else pack_padded(e->d_ids, e->d_mask, in.has_tt ? e->d_tt : nullptr, B, S, rules, seq, tok, st);
-    const int64_t maxT = (int64_t)B * (((S + (pool == KR_POOL_CLS ? 1 : 0)) + align - 1) & ~(align - 1));   // upper bound of the packed token count (each sequence is padded to `align`)
-    const unsigned row_grid = (unsigned)((maxT + 3) / 4);
-    // LayerNorm streams: y (dead after the kernel) and the low half (next read by the next LayerNorm, ~600 MiB of traffic later) are loaded / stored
-    // non-temporally — they do not displace the 16-bit stream the next GEMM reads: -1.3 % forward at 1024 x 128 tokens, -0.1...0.5 % at 1000 x 32; 8 blocks
-    // per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
-    auto ln_kernel = H <= 512 ? &k_ln16<1, 7> : H <= 1024 ? &k_ln16<2, 7> : &k_ln16<4, 7>;
-    auto ln_pre_kernel = H <= 512 ? &k_ln16_pre<1, 1> : H <= 1024 ? &k_ln16_pre<2, 1> : &k_ln16_pre<4, 1>;      // ModernBert handles (y non-temporal as above)
-    const bool pre = p.pre_ln;
-    auto ln_rms_kernel = H <= 512 ? &k_ln16_pre<1, 1, true> : H <= 1024 ? &k_ln16_pre<2, 1, true> : &k_ln16_pre<4, 1, true>;    // T5 handles
-    const auto ln_tail_kernel = p.rms ? ln_rms_kernel : ln_pre_kernel;
-    auto pool_kernel = classify ? (H <= 256 ? &k_pool<1, true> : H <= 512 ? &k_pool<2, true> : H <= 1024 ? &k_pool<4, true> : &k_pool<8, true>)
-                                : (H <= 256 ? &k_pool<1> : H <= 512 ? &k_pool<2> : H <= 1024 ? &k_pool<4> : &k_pool<8>);
-    const int pool_lds = POOL_WAVES * (H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8) * 256 * 4 + POOL_WAVES * 4;
-    unsigned ln_mult = 8u;
-    const unsigned ln_grid = std::min(row_grid, (unsigned)e->num_cu_all * ln_mult);   // k_ln is grid-stride (its parameters stay in registers across rows)
-    if (p.rotary) hipLaunchKernelGGL(k_rot_pos, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nq, align, e->tok_pos, e->tok_rpos);
-    const bool embed_rms = p.pos == POS_BIAS_ONLY || p.family == DECODER;
-    if (embed_rms) {     // the embedding row is the residual stream; xb = block 0's attention norm of it (T5 and decoder handles)
-        auto embed_kernel = H <= 512 ? &k_embed_rms<1> : H <= 1024 ? &k_embed_rms<2> : &k_embed_rms<4>;
-        hipLaunchKernelGGL(embed_kernel, dim3(row_grid), dim3(256), 0, st, e->tok_id, e->d_T, e->word, e->elng, eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
-    } else {
-        const bool no_pos = p.pos == POS_ROTARY || disent;      // a zero row in place of a position row
-        hipLaunchKernelGGL(k_embed_ln, dim3(row_grid), dim3(256), 0, st, e->tok_id, no_pos ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T,
-                           e->word, no_pos ? e->zero_row : e->pos, e->type, e->elng, e->elnb, eps, H,
-                           e->use_lo ? e->xlo : nullptr, e->xb);
-    }
-    // (the score head reads one row per sequence too, the last packed one: the same shortcut on those rows.  The embedding pools of a decoder handle keep
-    // every row)
-    const bool shortcut = (pool == KR_POOL_CLS || score) && e->cls_shortcut && e->c_ctx != nullptr && !flags;      // the token-level heads read every row of the last layer
-    e->last_shortcut = shortcut;
-    const RowSet all_rows{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, maxT, ln_grid,
-                          e->rb, e->use_lo ? e->rlo : nullptr};
-    const RowSet cls_rows{e->c_ctx, e->c_xb, e->c_y, e->c_h, e->use_lo ? e->c_xlo : nullptr, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, B,
-                          std::min((unsigned)((B + 3) / 4), (unsigned)e->num_cu_all * ln_mult), e->c_rb, e->use_lo ? e->c_rlo : nullptr};
-    static constexpr int QKV_EPI[] = {EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB}, FF_EPI[] = {EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH};   // by QkvKind, FfKind
-    const int ff_epi = FF_EPI[p.ff], ff_cols = p.ff_gated ? 2 * FF : FF;
-    // the pre-LN tail of a ModernBert layer on the same five launches.  (rin, rin_lo): the residual stream as this layer finds it — r.rb / r.rlo, or for layer
-    // 0 on all rows the embedding LayerNorm's output itself (xb / xlo: attn_norm of layer 0 is the identity)
-    auto tail_pre = [&](ProjArgs a, const LayerW& l, const RowSet& r, bool last, const uint16_t* rin, const uint8_t* rin_lo) {
-        a.Tp = r.rows;
-        // attn.Wo; r += y + b; xb = mlp_norm(r)
-        a.W = l.wo; a.X = r.ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = r.y; a.ldx = 0; a.ldo = 0;
-        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, rin, rin_lo, r.rb, r.rlo, (uint8_t*)nullptr, r.xb);
-        // mlp.Wi (input | gate as one GEMM of 2 FF columns) + GEGLU: h [rows, FF].  A T5 handle: wi + relu, or wi_0 | wi_1 the same way + gelu_new, no bias
-        a.W = l.w1; a.X = r.xb; a.F = ff_cols; a.K = H; a.bias = l.b1p; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
-        KR_TRY(launch_proj(ff_epi, a, r.max_rows, e, st));
-        // mlp.Wo; r += y + b; xb = the next layer's attn_norm(r), or final_norm(r) with its low half for the readers of the final hidden state
-        a.W = l.w2; a.X = r.h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = r.y; a.ldx = FF; a.ldo = 0;
-        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.b2, r.rows, l.ln2g, l.ln2b, eps, H, (const uint16_t*)r.rb, (const uint8_t*)r.rlo,
-                           last ? (uint16_t*)nullptr : r.rb, r.rlo, last ? r.lo_last : (uint8_t*)nullptr, r.xb);
-        return 0;
-    };
-    auto tail = [&](ProjArgs a, const LayerW& l, const RowSet& r, bool last) {
-        a.Tp = r.rows;
-        // attention.output.dense + residual -> LayerNorm
-        a.W = l.wo; a.X = r.ctx; a.F = H; a.K = H; a.bias = l.bo_eff; a.out0 = r.y; a.ldx = 0; a.ldo = 0;
-        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        hipLaunchKernelGGL(ln_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.bo_eff, r.rows, l.ln1g, l.ln1b, eps, H, r.lo, r.lo, r.xb);
-        // intermediate.dense + GELU, or gate_proj | up_proj (one GEMM of 2 FF columns) + SwiGLU: h [rows, FF] either way
-        a.W = l.w1; a.X = r.xb; a.F = ff_cols; a.K = H; a.bias = l.b1; a.out0 = r.h; a.ldx = 0; a.ldo = FF;
-        KR_TRY(launch_proj(ff_epi, a, r.max_rows, e, st));
-        // output.dense + residual -> LayerNorm
-        a.W = l.w2; a.X = r.h; a.F = H; a.K = FF; a.bias = l.b2; a.out0 = r.y; a.ldx = FF; a.ldo = 0;
-        KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, e, st));
-        // the LAST LayerNorm always writes the low half: pooling and kr_encoder_last_hidden read the final hidden state with 16 mantissa bits
-        hipLaunchKernelGGL(ln_kernel, dim3(r.ln_grid), dim3(256), 0, st, r.y, l.b2, r.rows, l.ln2g, l.ln2b, eps, H, r.lo, last ? r.lo_last : r.lo, r.xb);
-        return 0;
-    };
-    for (const LayerW& l : e->L) {
-        const bool last = (&l == &e->L.back());
-        const bool first = (&l == &e->L.front());
-        const LayerPlan& lp = p.layers[&l - &e->L.front()];
-        const bool local = lp.attn == AM_WIN;      // a ModernBert handle's sliding-window layer: its own rotary table, windowed attention
-        ProjArgs a{};
-        a.Tp = e->d_T; a.H = H;
-        a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
-        // q | k | v^T in one GEMM (F = H + 2A: 3H unless k and v are a grouped-query decoder's)
-        a.A = p.kv_dim;
-        a.W = l.wqkv; a.X = e->xb; a.F = H + 2 * p.kv_dim; a.K = H; a.bias = l.bqkv; a.out0 = e->q; a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv; a.ldx = 0; a.ldo = 0;
-        KR_TRY(launch_proj(QKV_EPI[lp.qkv], a, maxT, e, st));
-        {
-            const int cap = (int)round_up(S, 32);
-            const int am = lp.attn;
-            auto go = [&](auto dh) -> int {
-                constexpr int DH = decltype(dh)::value;
-                if (am == AM_DISENT) {      // q . PK and k . PQ of every packed row, for the bias tiles of this layer's attention
-                    // (k_pos_scores reads k with q's pitch H and head h of both: a DeBERTa handle has one KV head per query head, describe() refuses any other)
-                    if (p.kv_dim != H) return fail(KR_ESTATE, "a DeBERTa handle with k / v width %d != hidden", p.kv_dim);
-                    const dim3 grid((unsigned)((maxT + POS_ROWS - 1) / POS_ROWS), (unsigned)e->cfg.heads);
-                    hipLaunchKernelGGL(k_pos_scores<DH>, grid, dim3(256), 0, st, e->q, e->k, e->d_T, H, e->cfg.heads, l.pk16, l.pq16, (int)round_up(2 * p.deb_buckets, 32), span_p0, span_W, e->pos_sc);
-                    return launch_attention<DH, AM_DISENT>(e, B, cap, nqt_max, long_seq, span_p0, span_W, st);
-                }
-                return am == AM_BIAS ? launch_attention<DH, AM_BIAS>(e, B, cap, nqt_max, long_seq, 0, 0, st)
-                     : am == AM_WIN ? launch_attention<DH, AM_WIN>(e, B, cap, nqt_max, long_seq, 0, 0, st)
-                     : am == AM_CAUSAL ? launch_attention<DH, AM_CAUSAL>(e, B, cap, nqt_max, long_seq, 0, 0, st) : launch_attention<DH, AM_PLAIN>(e, B, cap, nqt_max, long_seq, 0, 0, st);
-            };
-            if (H == 32 * e->cfg.heads) KR_TRY(go(std::integral_constant<int, 32>{})); else KR_TRY(go(std::integral_constant<int, 64>{}));
-        }
-        // CLS shortcut: only the CLS row of every sequence is read after the last layer: gather those rows and finish the layer on B rows (same kernels, same
-        // arithmetic per row: the projection loops are bit-identical for every tiling and LayerNorm is per row, so the embedding does not change by one bit)
-        // (a ModernBert handle: the residual stream travels in the place of xb — the operand is rewritten by the first LayerNorm of the tail)
-        // (a T5 handle: the embedding launch has stored the residual stream itself, layer 0 finds it like every layer)
-        const bool in_rb = pre && (!first || embed_rms);
-        const uint16_t* rin = in_rb ? e->rb : e->xb;
-        const uint8_t* rin_lo = in_rb ? all_rows.rlo : all_rows.lo;
-        if (last && shortcut)
-            hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
-                               pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, score ? 1 : 0);
-        if (pre) {
-            if (last && shortcut) KR_TRY(tail_pre(a, l, cls_rows, last, e->c_rb, cls_rows.rlo));
-            else KR_TRY(tail_pre(a, l, all_rows, last, rin, rin_lo));
-        } else {
-            KR_TRY(tail(a, l, last && shortcut ? cls_rows : all_rows, last));
-        }
-    }
-    if (splade) {
-        // t = LayerNorm(gelu(Wt x + bt)) of the packed rows: y <- EPI_GELU, q <- k_ln16_head (both buffers are free behind the last layer; xb / xlo keep the
-        // final hidden state for kr_encoder_last_hidden)
-        ProjArgs a{};
-        a.Tp = e->d_T; a.H = H; a.W = e->hh(HEAD_MLM, 0); a.X = e->xb; a.F = H; a.K = H; a.bias = e->hf(HEAD_MLM, 1); a.out0 = e->y;
-        KR_TRY(launch_proj(EPI_GELU, a, maxT, e, st));
-        KR_HIP(hipMemsetAsync(e->row_seq, 0xff, (size_t)e->capT * 4, st));
-        hipLaunchKernelGGL(k_splade_rowseq, dim3(B), dim3(64), 0, st, e->seq_off, e->seq_nk, e->row_seq);
-        auto head_ln = H <= 512 ? &k_ln16_head<1> : H <= 1024 ? &k_ln16_head<2> : &k_ln16_head<4>;
-        hipLaunchKernelGGL(head_ln, dim3(ln_grid), dim3(256), 0, st, e->y, e->zero_row, e->d_T, e->hf(HEAD_MLM, 2), e->hf(HEAD_MLM, 3), eps, H, e->row_seq, e->q, e->d_err);
-        // the decoder: [rows] x [Vpad, H]^T reduced over each sequence's rows inside the launch (EPI_SPLADE), then log1p in place
-        const int V = e->cfg.vocab;
-        KR_HIP(hipMemsetAsync(tok_out, 0, (size_t)B * V * 4, st));
-        a.W = e->hh(HEAD_MLM, 4); a.X = e->q; a.F = (int)extent(e->cfg, XVPAD); a.bias = e->hf(HEAD_MLM, 5); a.out0 = nullptr;
-        a.row_seq = e->row_seq; a.smax = reinterpret_cast<unsigned int*>(tok_out); a.V = V;
-        KR_TRY(launch_proj(EPI_SPLADE, a, maxT, e, st));
-        const int64_t n = (int64_t)B * V;
-        hipLaunchKernelGGL(k_splade_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tok_out, n, e->d_err);
-        KR_HIP(hipGetLastError());
-        return 0;
-    }
-    const RowSet& r = shortcut ? cls_rows : all_rows;
-    KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
-    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, pool_select,
-                       p.head[HEAD_DENSE] || classify ? e->pooled : e->out, e->d_err);
-    if (score) {                 // a decoder handle's score head: out [B, L] = score.weight . pooled, one launch without LDS
-        const int L = p.head_dim[HEAD_SCORE];
-        const int64_t waves = (int64_t)B * ((L + SH_LABELS - 1) / SH_LABELS);
-        hipLaunchKernelGGL(k_score_head, dim3((unsigned)((waves + SH_WAVES - 1) / SH_WAVES)), dim3(SH_WAVES * 64), 0, st, e->pooled, e->hf(HEAD_SCORE, 0), B, H, L, e->out, r.nk, e->d_err);
-    } else
-    if (classify) {              // the classification head: out [B, L] = Wo . tanh(Wd . pooled + bd) + bo
-        const int NJ = H <= 256 ? 1 : H <= 512 ? 2 : H <= 1024 ? 4 : 8, head_lds = CH_SEQ * 2 * H * 4;
-        auto head_kernel = NJ == 1 ? &k_cls_head<1> : NJ == 2 ? &k_cls_head<2> : NJ == 4 ? &k_cls_head<4> : &k_cls_head<8>;
-        KR_TRY(set_lds_once(reinterpret_cast<const void*>(head_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));      // the widest H of the instantiation (64 KiB at 2048)
-        if (p.classifier == HEAD_MODERN_CLS) {       // ModernBert's: Wo . LayerNorm(erf_gelu(Wd . pooled + bd)) + bo, same LDS
-            auto gln_kernel = NJ == 1 ? &k_cls_head<1, true> : NJ == 2 ? &k_cls_head<2, true> : NJ == 4 ? &k_cls_head<4, true> : &k_cls_head<8, true>;
-            KR_TRY(set_lds_once(reinterpret_cast<const void*>(gln_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));
-            hipLaunchKernelGGL(gln_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_MODERN_CLS, 0), e->hf(HEAD_MODERN_CLS, 1),
-                               e->hf(HEAD_MODERN_CLS, 4), e->hf(HEAD_MODERN_CLS, 5), B, H, p.head_dim[HEAD_MODERN_CLS], e->out, e->hf(HEAD_MODERN_CLS, 2), e->hf(HEAD_MODERN_CLS, 3), eps, r.nk, e->d_err);
-        } else if (p.cls_gelu) {                     // DeBERTa's: Wo . erf_gelu(Wd . pooled + bd) + bo, same LDS
-            auto gelu_kernel = NJ == 1 ? &k_cls_head<1, false, true> : NJ == 2 ? &k_cls_head<2, false, true> : NJ == 4 ? &k_cls_head<4, false, true> : &k_cls_head<8, false, true>;
-            KR_TRY(set_lds_once(reinterpret_cast<const void*>(gelu_kernel), CH_SEQ * 2 * NJ * 256 * 4, e->device));
-            hipLaunchKernelGGL(gelu_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_CLS, 0), e->hf(HEAD_CLS, 1), e->hf(HEAD_CLS, 2),
-                               e->hf(HEAD_CLS, 3), B, H, p.head_dim[HEAD_CLS], e->out, nullptr, nullptr, 0.f, r.nk, e->d_err);
-        } else
-        hipLaunchKernelGGL(head_kernel, dim3((B + CH_SEQ - 1) / CH_SEQ), dim3(CH_WAVES * 64), head_lds, st, e->pooled, e->hf(HEAD_CLS, 0), e->hf(HEAD_CLS, 1), e->hf(HEAD_CLS, 2), e->hf(HEAD_CLS, 3), B, H,
-                           p.head_dim[HEAD_CLS], e->out, nullptr, nullptr, 0.f, nullptr, nullptr);
-    } else
-    if (p.head[HEAD_DENSE]) {     // the Dense head: out [B, P] = normalize(W . pooled)
-        const int P = p.head_dim[HEAD_DENSE], dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
-        // one kernel, an LDS size per handle: the attribute is set once per device (set_lds_once) to what the largest handle needs, H = P = 2048 (64 KiB + 16 B)
-        KR_TRY(set_lds_once(reinterpret_cast<const void*>(&k_pool_dense), PD_SEQ * (2048 + 2048) * 4 + PD_SEQ * 4, e->device));
-        hipLaunchKernelGGL(k_pool_dense, dim3((B + PD_SEQ - 1) / PD_SEQ), dim3(256), dense_lds, st, e->pooled, e->hf(HEAD_DENSE, 0), B, H, P, e->out);
-    }
-    if (flags) {                 // bge-m3's token-level blocks, straight into tok_out: sparse [B, S], then colbert [B, S, P]
-        const int64_t slots = (int64_t)B * S;
-        const unsigned slot_grid = (unsigned)((slots + 3) / 4);
-        hipLaunchKernelGGL(k_m3_slots, dim3(B), dim3(64), 0, st, e->d_mask, e->seq_off, S, e->slot_row);
-        float* o = tok_out;
-        if (flags & KR_POOL_WITH_SPARSE) {
-            hipLaunchKernelGGL(k_m3_sparse, dim3(slot_grid), dim3(256), 0, st, e->xb, e->xlo, e->hf(HEAD_SPARSE, 0), e->hf(HEAD_SPARSE, 1), e->slot_row, slots, H, o, e->d_err);
-            o += slots;
-        }
-        if (flags & KR_POOL_WITH_COLBERT) {      // one more projection of the packed rows on the loops every layer uses, then bias + norm + scatter
-            ProjArgs a{};
-            a.Tp = e->d_T; a.H = H; a.W = e->hh(HEAD_COLBERT, 0); a.X = e->xb; a.F = p.head_dim[HEAD_COLBERT]; a.K = H; a.bias = e->hf(HEAD_COLBERT, 1); a.out0 = e->cy;
-            KR_TRY(launch_proj(EPI_DENSE, a, maxT, e, st));
-            hipLaunchKernelGGL(k_m3_rows, dim3(slot_grid), dim3(256), 0, st, e->cy, e->hf(HEAD_COLBERT, 1), e->slot_row, slots, p.head_dim[HEAD_COLBERT], o, e->d_err);
-        }
+    f.maxT = (int64_t)B * ((S + cls_row + f.align - 1) & ~(f.align - 1));
+    f.row_grid = (unsigned)((f.maxT + 3) / 4);
+    const unsigned ln_cap = (unsigned)e->num_cu_all * 8u;      // 8 LayerNorm blocks per CU (launch_norm)
+    f.ln_grid = std::min(f.row_grid, ln_cap);
+    // one row per sequence behind the last layer (the CLS row; the score head's last packed row — the embedding pools of a decoder handle keep every row): the
+    // last layer finishes on the gathered rows.  The token-level heads read every row of the last layer
+    f.shortcut = f.pool.one_row && e->cls_shortcut && e->c_ctx != nullptr && !flags;
+    e->last_shortcut = f.shortcut;
+    f.attn = AttnOperands{e->q, e->k, e->vT, e->ldv, e->seq_off, e->seq_nk, e->seq_nq, e->ctx, f.H, e->cfg.heads, p.kv_dim, e->capT, B};
+    f.all_rows = RowSet{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, f.maxT, f.ln_grid,
+                        e->rb, e->use_lo ? e->rlo : nullptr};
+    f.cls_rows = RowSet{e->c_ctx, e->c_xb, e->c_y, e->c_h, e->use_lo ? e->c_xlo : nullptr, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, B,
+                        std::min((unsigned)((B + 3) / 4), ln_cap), e->c_rb, e->use_lo ? e->c_rlo : nullptr};
+    enqueue_embed(f);
+    for (size_t li = 0; li < e->L.size(); ++li) KR_TRY(enqueue_layer(f, li));
+    if (f.pool.splade) KR_TRY(enqueue_splade_head(f));
+    else {
+        KR_TRY(enqueue_pool_and_head(f));
+        if (flags) KR_TRY(enqueue_m3_blocks(f));
     }
     KR_HIP(hipGetLastError());
     return 0;
@@ -801,7 +691,8 @@ static int begin_forward(Encoder* e, int B, int S, hipStream_t st) {
 // (tok_elems > 0: the token-level blocks of a flagged forward with a host `out` wait in e->tok_stage and follow the dense block)
 static int finish_forward(Encoder* e, int B, int S, int pool, float* out, hipStream_t st, size_t tok_elems = 0) {
     // (KR_POOL_SPLADE has no dense block: its [B, vocab] result is written to a device `out` by the kernels, or waits in e->tok_stage like a token-level block)
-    const size_t dense_elems = pool == KR_POOL_SPLADE ? 0 : (size_t)B * (pool == KR_POOL_CLASSIFY ? e->plan.head_dim[e->plan.classifier] : e->plan.out_dim);
+    const model::ForwardPool fp = model::resolve_pool(e->plan, pool);
+    const size_t dense_elems = fp.splade ? 0 : (size_t)B * (fp.classify ? e->plan.head_dim[e->plan.classifier] : e->plan.out_dim);
     if (dense_elems) KR_HIP(hipMemcpyAsync(out, e->out, dense_elems * 4, hipMemcpyDefault, st));
     if (tok_elems) KR_HIP(hipMemcpyAsync(out + dense_elems, e->tok_stage, tok_elems * 4, hipMemcpyDefault, st));
     e->lastB = B; e->lastS = S; e->last_stream = st;
@@ -828,12 +719,19 @@ static int grow_tok_stage(Encoder* e, size_t elems) {
     e->tok_stage_elems = elems;
     return 0;
 }
-// where a KR_POOL_SPLADE forward reduces into: a device `out` is the reduction buffer itself (the kernels hold the caller's pointer: never replayed from a
-// captured graph), a host `out` is staged
-static int splade_target(Encoder* e, int B, float* out, float** red) {
-    if (is_device_pointer(out)) { *red = out; return 0; }
-    KR_TRY(grow_tok_stage(e, (size_t)B * e->cfg.vocab));
-    *red = e->tok_stage;
+// Where the kernels write what a forward returns beside the dense block — bge-m3's token-level blocks (flags), the [B, vocab] result of KR_POOL_SPLADE (also
+// the reduction buffer of its decoder launch) — and how many floats of it wait in e->tok_stage for finish_forward.  A device `out` takes them straight from the
+// kernels (0.5 GB at 1024 x 128 x 1024: no second trip through the workspace), a host `out` is staged.  The kernels hold the caller's pointer, so such a forward
+// is never replayed from a captured graph.  *target = nullptr: the forward has no such block
+static int token_target(Encoder* e, int B, int S, int pool, int flags, float* out, float** target, size_t* staged) {
+    const size_t slots = (size_t)B * S;
+    const size_t elems = pool == KR_POOL_SPLADE ? (size_t)B * e->cfg.vocab
+                                                : ((flags & KR_POOL_WITH_SPARSE) ? slots : 0) + ((flags & KR_POOL_WITH_COLBERT) ? slots * e->plan.head_dim[model::HEAD_COLBERT] : 0);
+    *target = nullptr; *staged = 0;
+    if (!elems) return 0;
+    if (is_device_pointer(out)) { *target = pool == KR_POOL_SPLADE ? out : out + (size_t)B * e->plan.out_dim; return 0; }
+    KR_TRY(grow_tok_stage(e, elems));
+    *target = e->tok_stage; *staged = elems;
     return 0;
 }
 
@@ -847,25 +745,12 @@ int enc_forward(void* h, const int64_t* input_ids, const int64_t* attention_mask
     KR_HIP(hipMemcpyAsync(e->d_mask, attention_mask, (size_t)B * S * 8, hipMemcpyDefault, st));
     if (token_type_ids) KR_HIP(hipMemcpyAsync(e->d_tt, token_type_ids, (size_t)B * S * 8, hipMemcpyDefault, st));
     const int flags = pool & M3_FLAGS;
-    if (pool == KR_POOL_SPLADE) {
-        float* red = nullptr;
-        KR_TRY(splade_target(e, B, out, &red));
-        KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, 0, red));
-        return finish_forward(e, B, S, pool, out, st, red == out ? 0 : (size_t)B * e->cfg.vocab);
-    }
-    if (!flags) {
-        KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
-        return finish_forward(e, B, S, pool, out, st);
-    }
-    // bge-m3's token-level blocks: a device `out` takes them straight from the kernels (0.5 GB at 1024 x 128 x 1024: no second trip through the workspace), a
-    // host `out` is staged.  The kernels hold the caller's pointer, so a flagged forward is never replayed from a captured graph.
     pool &= ~M3_FLAGS;
-    const size_t slots = (size_t)B * S;
-    const size_t tok_elems = ((flags & KR_POOL_WITH_SPARSE) ? slots : 0) + ((flags & KR_POOL_WITH_COLBERT) ? slots * e->plan.head_dim[model::HEAD_COLBERT] : 0);
-    const bool direct = is_device_pointer(out);
-    if (!direct) KR_TRY(grow_tok_stage(e, tok_elems));
-    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, flags, direct ? out + (size_t)B * e->plan.out_dim : e->tok_stage));
-    return finish_forward(e, B, S, pool, out, st, direct ? 0 : tok_elems);
+    float* target = nullptr; size_t staged = 0;
+    KR_TRY(token_target(e, B, S, pool, flags, out, &target, &staged));
+    if (target) KR_TRY(enqueue_forward(e, B, S, pool, st, Input{false, token_type_ids != nullptr, 0}, flags, target));
+    else KR_TRY(run_forward(e, B, S, pool, st, token_type_ids != nullptr));
+    return finish_forward(e, B, S, pool, out, st, staged);
 }
 
 // kr_encoder_forward_packed: the same forward from the ragged token list (int32 ids of the attended positions + int32 length per sequence)
@@ -877,10 +762,10 @@ int enc_forward_packed(void* h, const int32_t* token_ids, const int32_t* seq_len
     KR_TRY(begin_forward(e, B, S, st));
     if (total_tokens > 0) KR_HIP(hipMemcpyAsync(e->rag_ids(), token_ids, (size_t)total_tokens * 4, hipMemcpyDefault, st));
     KR_HIP(hipMemcpyAsync(e->rag_lens(), seq_lens, (size_t)B * 4, hipMemcpyDefault, st));
-    float* red = nullptr;
-    if (pool == KR_POOL_SPLADE) KR_TRY(splade_target(e, B, out, &red));
-    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{true, false, (int)total_tokens}, 0, red));
-    return finish_forward(e, B, S, pool, out, st, red && red != out ? (size_t)B * e->cfg.vocab : 0);
+    float* target = nullptr; size_t staged = 0;      // (check_forward_args: a ragged forward takes no flags)
+    KR_TRY(token_target(e, B, S, pool, 0, out, &target, &staged));
+    KR_TRY(enqueue_forward(e, B, S, pool, st, Input{true, false, (int)total_tokens}, 0, target));
+    return finish_forward(e, B, S, pool, out, st, staged);
 }
 
 int enc_check(void* h) {

@@ -1,4 +1,5 @@
-// Sentence encoder, device code of the attention (AttnState ... k_attn_lds, k_attn_dma).  Part of encoder.hip (see its header).
+// Sentence encoder, the attention: device code (AttnState ... k_attn_lds, k_attn_dma) and, behind it, the host code that launches it (launch_attn_lds,
+// launch_attn_dma, launch_attention).  Part of encoder.hip (see its header).
 #pragma once
 #include "encoder_rows.hpp"
 
@@ -439,7 +440,7 @@ __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os
 // not the head width).
 // __launch_bounds__(256, 3) at DH = 64: at most 168 registers per lane, which makes hipcc keep the MFMA accumulators in VGPRs; with the default bound it
 // put them in AGPRs and spent 112 of the 276 VALU instructions of a key tile on v_accvgpr_read / _write around the softmax rescale.  A 32-wide head
-// stages half the bytes (<= 25 KiB per block for any HPB, see launch_attn) and keeps half the Q fragments and accumulators: four blocks per CU (<= 128
+// stages half the bytes (<= 25 KiB per block for any HPB, see launch_attn_lds) and keeps half the Q fragments and accumulators: four blocks per CU (<= 128
 // registers).
 // Grouped-query attention: query head h reads KV head h / group, group = heads / kv_heads.  The kernels take the group as kv_mul = 65536 / group + 1
 // (attn_kv_mul, host): (h * kv_mul) >> 16 == h / group for every h < 1024 and group <= 64 (h (kv_mul group - 65536) < 65536) — a multiply and a shift where a
@@ -821,6 +822,57 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
     } else {
         attn_dma_body<DH, 0>(q, k, vT, ldv, seq_off[b], seq_nk[b], nq, H, head, qg, capT, ctx, smem, ldk, kv_mul, ba);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// host side: the launchers (the library's forward and tests/capi/attn_probe.hip launch through them)
+// ---------------------------------------------------------------------------------------------------------
+// The operands of one layer's attention as they lie in the workspace: q / ctx [capT, H], k [capT + 64, kv_dim], vT [kv_dim, ldv], the sequence tables of the
+// nseq sequences (offsets: multiples of 4 tokens for k_attn_lds, of 8 for k_attn_dma)
+struct AttnOperands {
+    const uint16_t *q, *k, *vT; int64_t ldv;
+    const int *seq_off, *seq_nk, *seq_nq;
+    uint16_t* ctx;
+    int H, heads, kv_dim;
+    int64_t capT; int nseq;
+};
+// The mode of a launch is the type of its arguments (AttnNoBiasArgs, AttnBiasArgs, AttnWinArgs — a causal layer's too —, AttnDisentArgs)
+template <class BA> constexpr bool attn_is_bias = std::is_same_v<BA, AttnBiasArgs>;
+template <class BA> constexpr bool attn_is_win = std::is_same_v<BA, AttnWinArgs>;
+template <class BA> constexpr bool attn_is_disent = std::is_same_v<BA, AttnDisentArgs>;
+
+// the register-staged kernel, HPB heads per block.  cap: the batch width rounded up to 32; nqt: q-tiles of the longest sequence
+template <int DH, int HPB, class BA>
+static int launch_attn_lds(const AttnOperands& o, int cap, int nqt, const BA& ba, int device, hipStream_t st) {
+    // keys staged at a time: K kchunk x 2 DH B + V^T DH x (2 kchunk + 8) B per head, plus 4 O tiles of 32 x 2 DH B.  DH = 64: 49-50 KiB per block for any
+    // (S, HPB), 3 blocks per CU; DH = 32: 24-25 KiB, 4 blocks per CU (attn_lds_blocks: the registers, not the LDS, bound it)
+    const int kchunk = cap < 128 ? cap : 128;
+    const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
+    const auto kern = &k_attn_lds<DH, HPB, attn_is_bias<BA>, attn_is_win<BA>, attn_is_disent<BA>>;
+    KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
+    const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);   // blocks per (sequence, head group): 4 / HPB q-tiles each
+    hipLaunchKernelGGL(kern, dim3((unsigned)((o.heads + HPB - 1) / HPB), (unsigned)o.nseq, (unsigned)qgroups), dim3(256), lds, st, o.q, o.k, o.vT, o.ldv, o.seq_off, o.seq_nk,
+                       o.seq_nq, o.H, o.heads, kchunk, o.ctx, o.kv_dim, attn_kv_mul(o.H / o.kv_dim), ba);
+    return 0;
+}
+// the LDS-DMA ring (not built with the disentangled terms)
+template <int DH, class BA>
+static int launch_attn_dma(const AttnOperands& o, int nqt, const BA& ba, hipStream_t st) {
+    const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;       // blocks per (sequence, head): 8 q-tiles each
+    const int64_t pairs = (int64_t)o.nseq * o.heads;
+    const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;    // whole groups of 8 pairs (see k_attn_dma)
+    hipLaunchKernelGGL((k_attn_dma<DH, attn_is_bias<BA>, attn_is_win<BA>>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, st, o.q, o.k, o.vT, o.ldv, o.seq_off,
+                       o.seq_nk, o.seq_nq, o.H, o.capT, o.ctx, o.heads, o.nseq, qgroups, o.kv_dim, attn_kv_mul(o.H / o.kv_dim), ba);
+    return 0;
+}
+// the attention of one layer: the LDS-DMA ring for long sequences, else the register-staged kernel with 1 / 2 / 4 heads per block by q-tiles per sequence
+// (the disentangled terms are built into the register-staged kernel only: a DeBERTa forward never asks for the ring)
+template <int DH, class BA>
+static int launch_attention(const AttnOperands& o, int cap, int nqt, bool long_seq, const BA& ba, int device, hipStream_t st) {
+    if constexpr (!attn_is_disent<BA>) { if (long_seq) return launch_attn_dma<DH>(o, nqt, ba, st); }
+    if (nqt >= 3) return launch_attn_lds<DH, 1>(o, cap, nqt, ba, device, st);
+    if (nqt == 2) return launch_attn_lds<DH, 2>(o, cap, nqt, ba, device, st);
+    return launch_attn_lds<DH, 4>(o, cap, nqt, ba, device, st);
 }
 
 }  // namespace KR_ENC_NS

@@ -788,5 +788,24 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     return Error{};
 }
 
+// What a forward with `pool` (KR_POOL_*, the token-level flags taken off) runs on a finalized handle.  KR_POOL_CLASSIFY, KR_POOL_SPLADE and KR_POOL_LAST pack
+// and attend like another pool and differ behind the last layer only:
+//   pack      what the packing front end and the attention see: KR_POOL_CLS (a query-only row for a masked column 0, the packed token count) or KR_POOL_MEAN
+//   select    the row k_pool reads: KR_POOL_MEAN, KR_POOL_CLS or KR_POOL_LAST (a splade forward does not pool)
+//   classify  k_pool leaves the raw row to the classifier (ModelPlan::classifier); score: that head is a decoder's HEAD_SCORE, on the last row;
+//             ModernBert's with config.classifier_pooling = 1 reads the masked mean
+//   splade    the MLM head on every row in place of pooling
+//   one_row   behind the last layer's attention one row per sequence is read, the CLS row or the score head's last row: the layer may finish on those rows alone
+struct ForwardPool { int pack, select; bool classify, score, splade, one_row; };
+inline ForwardPool resolve_pool(const ModelPlan& p, int pool) {
+    ForwardPool f{pool, pool, pool == KR_POOL_CLASSIFY, false, pool == KR_POOL_SPLADE, false};
+    f.score = f.classify && p.classifier == HEAD_SCORE;
+    if (f.classify) f.select = f.score ? KR_POOL_LAST : p.classify_mean ? KR_POOL_MEAN : KR_POOL_CLS;
+    if (f.splade) f.select = KR_POOL_MEAN;
+    f.pack = f.select == KR_POOL_LAST ? KR_POOL_MEAN : f.select;
+    f.one_row = f.pack == KR_POOL_CLS || f.score;
+    return f;
+}
+
 }  // namespace model
 }  // namespace kr

@@ -1,6 +1,9 @@
-// Sentence encoder, device code of the projections (ProjArgs, the epilogues, k_proj*).  Part of encoder.hip (see its header).
+// Sentence encoder, the projections: device code (ProjArgs, the epilogues, k_proj*) and, behind it, the host code that launches it (launch_proj_loop: one
+// launch on a given main loop; launch_proj: which loop a launch of a forward takes).  Part of encoder.hip (see its header).
 #pragma once
 #include "encoder_rows.hpp"
+
+#include <type_traits>
 
 namespace kr {
 namespace KR_ENC_NS {
@@ -546,6 +549,120 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
             }
         }
     });
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// host side: the launchers (the library's forward and tests/capi/proj_probe.hip launch through them)
+// ---------------------------------------------------------------------------------------------------------
+// The runtime epilogue as a compile-time constant: f(std::integral_constant<int, EPI>{}) for the epilogues above.  What a launch site does not build for an
+// epilogue, it excludes itself with `if constexpr`.
+template <class F>
+static int with_epilogue(int epi, F&& f) {
+    switch (epi) {
+        case EPI_QKV: return f(std::integral_constant<int, EPI_QKV>{});
+        case EPI_DENSE: return f(std::integral_constant<int, EPI_DENSE>{});
+        case EPI_GELU: return f(std::integral_constant<int, EPI_GELU>{});
+        case EPI_QKV_ROT: return f(std::integral_constant<int, EPI_QKV_ROT>{});
+        case EPI_QKV_ROTB: return f(std::integral_constant<int, EPI_QKV_ROTB>{});
+        case EPI_SWIGLU: return f(std::integral_constant<int, EPI_SWIGLU>{});
+        case EPI_GEGLU: return f(std::integral_constant<int, EPI_GEGLU>{});
+        case EPI_RELU: return f(std::integral_constant<int, EPI_RELU>{});
+        case EPI_GEGLU_TANH: return f(std::integral_constant<int, EPI_GEGLU_TANH>{});
+        case EPI_SPLADE: return f(std::integral_constant<int, EPI_SPLADE>{});
+        default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
+    }
+}
+
+// one launch: the LDS attribute once per (kernel, device), then the kernel
+template <class Kern>
+static int launch_proj_kernel(Kern kern, dim3 grid, int threads, int lds, const ProjArgs& a, int device, hipStream_t st) {
+    KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, a);
+    return 0;
+}
+
+// the persistent loops over whole tiles (k_proj): `blocks` blocks walk the tiles
+template <class Shape, int STAGES, bool NT>
+static int launch_proj_shape_nt(int epi, const ProjArgs& a, int blocks, int device, hipStream_t st) {
+    constexpr int lds = STAGES * Shape::STAGE_BYTES + Shape::NWAVE * EPI_STAGE_BYTES;   // 160 KiB for the 256x256 tile: the whole LDS of a CU
+    auto go = [&](auto kern) -> int { return launch_proj_kernel(kern, dim3(blocks), Shape::NTHREADS, lds, a, device, st); };
+    const bool ant = a.ant && Shape::BM == 256;   // the non-temporal activation operand exists for the ping-pong loop only
+    return with_epilogue(epi, [&](auto tag) -> int {
+        constexpr int EPI = decltype(tag)::value;
+        if constexpr (EPI == EPI_QKV_ROTB && Shape::BM == 256)      // not on the 256 x 256 tile (launch_proj): the bias quads next to its 128 accumulators spill
+            return fail(KR_EINVAL, "projection epilogue %d is not built for the 256 x 256 tile", epi);
+        else if constexpr (EPI == EPI_SPLADE && NT)                 // stores no rows: one instantiation per shape (launch_proj clears nt)
+            return fail(KR_EINVAL, "projection epilogue %d has no non-temporal stores", epi);
+        else if constexpr (EPI == EPI_DENSE) return ant ? go(&k_proj<EPI_DENSE, Shape, STAGES, NT, true>) : go(&k_proj<EPI_DENSE, Shape, STAGES, NT>);
+        else return go(&k_proj<EPI, Shape, STAGES, NT>);
+    });
+}
+// the skinny loop: one (32 WM)^2 tile per block, a ring of 16 / 8 K-tiles
+template <int WM>
+static int launch_proj_skinny(int epi, const ProjArgs& a, int64_t max_tokens, int device, hipStream_t st) {
+    constexpr int RING = WM == 1 ? 16 : 8;
+    using G = SkinnyGeom<WM, WM>;
+    const dim3 grid((unsigned)(a.F / (32 * WM)), (unsigned)((max_tokens + 32 * WM - 1) / (32 * WM)));
+    return with_epilogue(epi, [&](auto tag) -> int {
+        return launch_proj_kernel(&k_proj_skinny<decltype(tag)::value, RING, WM, WM>, grid, G::THREADS, RING * G::STAGE, a, device, st);
+    });
+}
+
+// Mechanism.  One projection launch on the main loop `loop` (the values of KIRAG_AMD_PROJ_TILE: 256 ping-pong, 128 streaming, 130 producer / consumer, 64 / 32
+// skinny) with `a` as given (nt, ant, pw, epi_prio, ldx, ldo): grid, block size, LDS bytes, the LDS attribute, the instantiation, the launch.  blocks: the
+// persistent grid of 256 / 128 / 130; max_tokens: the token rows the skinny grid covers.  What a loop is not built for is refused: EPI_QKV_ROTB on the 256 tile,
+// EPI_SPLADE with non-temporal stores; ant is honoured by EPI_DENSE on the ping-pong loop only.
+static int launch_proj_loop(int epi, const ProjArgs& a, int loop, int blocks, int64_t max_tokens, int device, hipStream_t st) {
+    switch (loop) {
+        case 256: return a.nt ? launch_proj_shape_nt<ShapeBig, 2, true>(epi, a, blocks, device, st) : launch_proj_shape_nt<ShapeBig, 2, false>(epi, a, blocks, device, st);
+        case 128: return a.nt ? launch_proj_shape_nt<ShapeSmall, 2, true>(epi, a, blocks, device, st) : launch_proj_shape_nt<ShapeSmall, 2, false>(epi, a, blocks, device, st);
+        case 130: {
+            constexpr int lds = SPLIT_RING * ShapeSplit::STAGE_BYTES + 4 * EPI_STAGE_BYTES;
+            return with_epilogue(epi, [&](auto tag) -> int { return launch_proj_kernel(&k_proj_split<decltype(tag)::value>, dim3(blocks), SPLIT_THREADS, lds, a, device, st); });
+        }
+        case 64: return launch_proj_skinny<2>(epi, a, max_tokens, device, st);
+        case 32: return launch_proj_skinny<1>(epi, a, max_tokens, device, st);
+        default: return fail(KR_EINVAL, "projection loop %d: 256, 128, 130, 64 or 32", loop);
+    }
+}
+
+// Policy.  What a forward's projection launches with: the CUs the persistent grids are sized for, the device, and the A/B switches read once per forward
+// (KIRAG_AMD_PATCH_W, KIRAG_AMD_EPI_PRIO, KIRAG_AMD_PROJ_TILE)
+struct ProjLaunch { int num_cu, device, pw, epi_prio, force_tile; };
+
+// tile shape per launch: when the 256x256 tiling has fewer tiles than ~5/8 of the CUs (small batches: the reference's per_gpu_batch_size 4-8, the KiRAG
+// loop's triple batches, a 1/8 slice of a query batch) the 128x128 tiling gives 4x the parallelism at a quarter of the per-tile latency
+static int launch_proj(int epi, const ProjArgs& a_in, int64_t max_tokens, const ProjLaunch& ctx, hipStream_t st) {
+    const int num_cu = ctx.num_cu, device = ctx.device;
+    ProjArgs a = a_in;
+    if (a.ldx == 0) a.ldx = a.K;
+    if (a.ldo == 0) a.ldo = a.F;
+    a.pw = ctx.pw;
+    a.epi_prio = ctx.epi_prio;
+    // store policy by output size (see ProjArgs::nt)
+    a.nt = epi != EPI_SPLADE && max_tokens * (int64_t)(epi_gated(epi) ? a.F / 2 : a.F) * 2 > ((int64_t)96 << 20) ? 1 : 0;
+    // FF2 (K = FF > H): its activation operand h is a once-through stream four times the size of every other activation (256 MiB at 32 k tokens); loaded
+    // non-temporally it leaves the L2 / Infinity Cache to the weights and to the residual stream the LayerNorm behind it reads: -0.7 % forward time at
+    // 1000 x 32 tokens, neutral elsewhere (profiles/r04/tried_nt_activations.txt; outputs bit-identical).
+    a.ant = a.K > a.H ? 1 : 0;
+    const int64_t big_tiles = ((max_tokens + 255) / 256) * ((a.F + 255) / 256);
+    const int64_t small_tiles = ((max_tokens + 127) / 128) * ((a.F + 127) / 128);
+    const int force = ctx.force_tile;
+    const bool small = force == 128 || (force != 256 && big_tiles * 8 < (int64_t)num_cu * 5) || epi == EPI_QKV_ROTB;   // measured crossover: ~5/8 of the CUs busy with 256x256 tiles
+    // a handful of token rows: the skinny loop, one tile per block (latency chain: the operand stream of the launch spread over as many CUs as it has
+    // tiles).  32 x 32 tiles while there is at most one per CU, 64 x 64 (four multiplying waves share every staged K-tile: half the L2 -> LDS bytes per
+    // output element) up to four 32 x 32 tiles' worth per CU — the crossover against the 128x128 producer / consumer loop measured in round 1.
+    // KIRAG_AMD_PROJ_TILE = 32 / 64 forces one of the two.
+    const int64_t skinny_tiles = ((max_tokens + 31) / 32) * (a.F / 32);
+    if (force == 32 || force == 64 || (force == 0 && skinny_tiles <= 4 * (int64_t)num_cu && (max_tokens + 31) / 32 <= 65535)) {
+        const bool one = force == 32 || (force == 0 && skinny_tiles <= num_cu);
+        return launch_proj_loop(epi, a, one ? 32 : 64, 0, max_tokens, device, st);
+    }
+    if (!small) return launch_proj_loop(epi, a, 256, num_cu, max_tokens, device, st);
+    // producer/consumer loop (one persistent block per CU): at most one tile per CU, or more than two (measured: 600 tiles -7 % vs the streaming loop
+    // with two blocks per CU; between one and two tiles per CU the two co-resident streaming blocks quantise better).  130 forces it, 128 the streaming loop
+    if (((small_tiles <= num_cu || small_tiles > 2 * num_cu) && force != 128) || force == 130) return launch_proj_loop(epi, a, 130, num_cu, max_tokens, device, st);
+    return launch_proj_loop(epi, a, 128, 2 * num_cu, max_tokens, device, st);
 }
 
 }  // namespace KR_ENC_NS

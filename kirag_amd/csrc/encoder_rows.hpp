@@ -3,6 +3,9 @@
 #pragma once
 #include "gemm_nt.hpp"
 
+#include <mutex>
+#include <vector>
+
 // This file is compiled TWICE (kirag_amd/csrc/Makefile): once per 16-bit operand type of the MFMAs and of every stored activation —
 //   bf16 (8 significand bits, fp32 range)  and  f16 (11 significand bits, |x| <= 65504; -DKR_ENC_F16)
 // — into the namespaces kr::enc_bf16 / kr::enc_f16; encoder_api.hip holds the C entry points and picks one per handle (kr_encoder_create_ex).
@@ -865,6 +868,29 @@ __global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__
         c_off[b] = b; c_nk[b] = seq_nk[b] > 0 ? 1 : 0; c_cls[b] = 0;   // c_nk == 0: an all-masked sequence (its NaN is the reference's own, not an overflow: k_pool)
         if (b == 0) *d_B = (int)gridDim.x;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize), the one place that sets it: function attributes belong to the device's code-object instance, so the
+// largest `lds` set so far is remembered per (kernel, device) and the attribute is raised only by a launch that needs more.  Safe against concurrent first
+// launches from several host threads (a query encoder and a corpus encoder on one device: ADVICE r04) and with the outcome cached, so that a failing
+// attribute is reported by every launch
+static int set_lds_once(const void* kern, int lds, int device) {
+    struct Ent { const void* k; int dev; int lds; hipError_t rc; };
+    static std::mutex mu;
+    static std::vector<Ent> done;
+    std::lock_guard<std::mutex> lock(mu);
+    Ent* ent = nullptr;
+    for (Ent& x : done)
+        if (x.k == kern && x.dev == device) { ent = &x; break; }
+    if (ent && ent->rc != hipSuccess) return fail(KR_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(ent->rc));
+    if (ent && lds <= ent->lds) return 0;
+    const hipError_t rc = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (ent) { ent->lds = lds; ent->rc = rc; } else done.push_back({kern, device, lds, rc});
+    if (rc != hipSuccess) return fail(KR_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(rc));
+    return 0;
 }
 
 }  // namespace KR_ENC_NS

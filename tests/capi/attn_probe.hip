@@ -8,8 +8,8 @@
 // the caller fills slack, alignment rows and ctx (a sentinel) as it likes.  The entry point refuses every argument set under which a kernel could read or write
 // outside these arrays (return value < 0, message through kr_attn_probe_error), so a wrong test cannot fault the GPU.
 //
-// LAUNCH GEOMETRY: copied from launch_attn / launch_attn_dma in kirag_amd/csrc/encoder.hip (grid, kchunk, LDS bytes, attn_kv_mul, sequence offsets aligned to 4
-// tokens for k_attn_lds and to 8 for k_attn_dma).  Change both places together; the model-level tests remain the check that the library launches with it.
+// The launch itself (grid, kchunk, LDS bytes and attribute, attn_kv_mul) is the library's: launch_attn_lds / launch_attn_dma of encoder_attn.hpp, the ones the
+// forward goes through, called with the caller's `kernel` and `cap`.  Sequence offsets are aligned to 4 tokens for k_attn_lds and to 8 for k_attn_dma.
 #include "../../kirag_amd/csrc/encoder_attn.hpp"
 
 #include <cstring>
@@ -90,49 +90,26 @@ static int check_args(const AttnProbeArgs& a) {
     return 0;
 }
 
-template <int DH, int HPB, bool BIAS, bool WIN, class BA>
-static hipError_t run_lds(const AttnProbeArgs& a, const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* off, const int* nk, const int* nq, uint16_t* ctx,
-                          int nqt, const BA& ba) {
-    // launch_attn (encoder.hip)
-    const int kchunk = a.cap < 128 ? a.cap : 128;
-    const int lds = HPB * (kchunk * 2 * DH + DH * (kchunk * 2 + 8)) + 4 * 32 * 2 * DH;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_lds<DH, HPB, BIAS, WIN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);
-    hipLaunchKernelGGL((k_attn_lds<DH, HPB, BIAS, WIN, false>), dim3((unsigned)((a.heads + HPB - 1) / HPB), (unsigned)a.nseq, (unsigned)qgroups), dim3(256), lds, 0, q, k, vT, ldv, off, nk, nq,
-                       a.H, a.heads, kchunk, ctx, a.ldk, attn_kv_mul(a.heads / a.kv_heads), ba);
-    return hipGetLastError();
-}
-
-template <int DH, bool BIAS, bool WIN, class BA>
-static hipError_t run_dma(const AttnProbeArgs& a, const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* off, const int* nk, const int* nq, uint16_t* ctx,
-                          int nqt, const BA& ba) {
-    // launch_attn_dma (encoder.hip)
-    const int qgroups = (nqt + ADMA_QT - 1) / ADMA_QT;
-    const int64_t pairs = (int64_t)a.nseq * a.heads;
-    const int64_t blocks = (pairs + 7) / 8 * 8 * qgroups;
-    hipLaunchKernelGGL((k_attn_dma<DH, BIAS, WIN>), dim3((unsigned)blocks), dim3(ADMA_THREADS), AdmaGeom<DH>::LDS, 0, q, k, vT, ldv, off, nk, nq, a.H, a.capT, ctx, a.heads, a.nseq, qgroups,
-                       a.ldk, attn_kv_mul(a.heads / a.kv_heads), ba);
-    return hipGetLastError();
-}
-
-template <int DH, bool BIAS, bool WIN, class BA>
-static hipError_t run_kernel(const AttnProbeArgs& a, const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* off, const int* nk, const int* nq, uint16_t* ctx,
-                             int nqt, const BA& ba) {
+// the library's launchers (encoder_attn.hpp) with the caller's kernel, heads per block and cap.  A launcher that fails without a HIP error has refused its
+// arguments
+template <int DH, class BA>
+static hipError_t run_kernel(const AttnProbeArgs& a, const AttnOperands& ops, int nqt, int device, const BA& ba) {
+    int rc = 0;
     switch (a.kernel) {
-        case 0: return run_dma<DH, BIAS, WIN>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, ba);
-        case 1: return run_lds<DH, 1, BIAS, WIN>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, ba);
-        case 2: return run_lds<DH, 2, BIAS, WIN>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, ba);
-        default: return run_lds<DH, 4, BIAS, WIN>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, ba);
+        case 0: rc = launch_attn_dma<DH>(ops, nqt, ba, 0); break;
+        case 1: rc = launch_attn_lds<DH, 1>(ops, a.cap, nqt, ba, device, 0); break;
+        case 2: rc = launch_attn_lds<DH, 2>(ops, a.cap, nqt, ba, device, 0); break;
+        default: rc = launch_attn_lds<DH, 4>(ops, a.cap, nqt, ba, device, 0); break;
     }
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess || rc == 0 ? e : hipErrorInvalidValue;
 }
 
 template <int DH>
-static hipError_t run_mode(const AttnProbeArgs& a, const uint16_t* q, const uint16_t* k, const uint16_t* vT, int64_t ldv, const int* off, const int* nk, const int* nq, uint16_t* ctx,
-                           int nqt, const int* col, const float* tab) {
-    if (a.mode == 0) return run_kernel<DH, false, false>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, AttnNoBiasArgs{});
-    if (a.mode == 1) return run_kernel<DH, true, false>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, AttnBiasArgs{tab, col, a.width, a.gather ? 1 : 0});
-    return run_kernel<DH, false, true>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, AttnWinArgs{col, a.wl, a.wr, a.gather ? 1 : 0});
+static hipError_t run_mode(const AttnProbeArgs& a, const AttnOperands& ops, int nqt, int device, const int* col, const float* tab) {
+    if (a.mode == 0) return run_kernel<DH>(a, ops, nqt, device, AttnNoBiasArgs{});
+    if (a.mode == 1) return run_kernel<DH>(a, ops, nqt, device, AttnBiasArgs{tab, col, a.width, a.gather ? 1 : 0});
+    return run_kernel<DH>(a, ops, nqt, device, AttnWinArgs{col, a.wl, a.wr, a.gather ? 1 : 0});
 }
 
 #ifdef KR_ENC_BUILD_F16
@@ -162,8 +139,11 @@ extern "C" __attribute__((visibility("default"))) int KR_ATTN_PROBE(const AttnPr
     if (a.mode != 0) PR_HIP(upload(bufs, &col, a.col, (size_t)(capT + 64)));
     if (a.mode == 1) PR_HIP(upload(bufs, &tab, a.tab, (size_t)a.heads * a.width));
     if (nqt > 0) {
-        if (a.dh == 64) PR_HIP(run_mode<64>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, col, tab));
-        else PR_HIP(run_mode<32>(a, q, k, vT, ldv, off, nk, nq, ctx, nqt, col, tab));
+        int device = 0;
+        PR_HIP(hipGetDevice(&device));
+        const AttnOperands ops{q, k, vT, ldv, off, nk, nq, ctx, a.H, a.heads, a.ldk, capT, a.nseq};
+        if (a.dh == 64) PR_HIP(run_mode<64>(a, ops, nqt, device, col, tab));
+        else PR_HIP(run_mode<32>(a, ops, nqt, device, col, tab));
     }
     PR_HIP(hipDeviceSynchronize());
     PR_HIP(hipMemcpy(a.ctx, ctx, (size_t)capT * a.H * 2, hipMemcpyDeviceToHost));

@@ -1,7 +1,8 @@
 // Drives kirag_amd/csrc/encoder_model.hpp without a device (tests/test_encoder_model_host.py).  stdin:
 //   config HIDDEN LAYERS HEADS FF VOCAB MAX_POS TYPE_VOCAB      (first line)
-//   setting NAME v0 v1 ...      tensor NAME NUMEL      finalize
-// stdout, one line per command: "setting NAME rc=R msg", "tensor NAME slot=S family=F layer=L expect=N rc=R msg", "finalize rc=R msg" or "finalize rc=0 plan ...".
+//   setting NAME v0 v1 ...      tensor NAME NUMEL      finalize      pools
+// stdout, one line per command: "setting NAME rc=R msg", "tensor NAME slot=S family=F layer=L expect=N rc=R msg", "finalize rc=R msg" or "finalize rc=0 plan ...",
+// "pools rc=0 plan pool0=... pool5=..." (resolve_pool on the last finalized plan).
 // The loader's bookkeeping of the library (encoder_weights.hpp: enc_load_weight, enc_finalize) is repeated here in its host-only part.
 #include "../../kirag_amd/csrc/encoder_model.hpp"
 
@@ -35,15 +36,27 @@ int main() {
     Settings set;
     Loaded ld(cfg.layers);
     bool finalized_once = false;
+    ModelPlan plan;      // of the last finalize that succeeded
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
         if (!(in >> cmd)) continue;
         if (cmd == "finalize") {
-            ModelPlan plan;
-            const Error e = describe(cfg, set, ld, plan);
+            ModelPlan p;
+            const Error e = describe(cfg, set, ld, p);
             if (e.code) std::cout << "finalize rc=" << e.code << " " << e.msg << "\n";
-            else std::cout << "finalize rc=0 plan " << plan_line(plan) << "\n";
+            else std::cout << "finalize rc=0 plan " << plan_line(p) << "\n";
+            if (!e.code) plan = p;
             finalized_once = finalized_once || e.code == 0;
+            continue;
+        }
+        if (cmd == "pools") {      // resolve_pool of the finalized plan: poolN=pack,select,classify,score,splade,one_row for every KR_POOL_*
+            if (!finalized_once) { std::cout << "pools rc=" << KR_ESTATE << " no finalized plan\n"; continue; }
+            std::cout << "pools rc=0 plan";
+            for (int pool : {KR_POOL_MEAN, KR_POOL_CLS, KR_POOL_CLASSIFY, KR_POOL_SPLADE, KR_POOL_LAST}) {
+                const ForwardPool f = resolve_pool(plan, pool);
+                std::cout << " pool" << pool << "=" << f.pack << "," << f.select << "," << f.classify << "," << f.score << "," << f.splade << "," << f.one_row;
+            }
+            std::cout << "\n";
             continue;
         }
         if (!(in >> name)) return 2;

@@ -13,9 +13,9 @@
 // The entry point refuses every argument set under which a kernel could read or write outside these arrays (return value -1, message through
 // kr_proj_probe_error), so a wrong test cannot fault the GPU.  A HIP error returns -2.
 //
-// LAUNCH GEOMETRY: copied from launch_proj / launch_proj_shape_nt in kirag_amd/csrc/encoder.hip (grid, block size, LDS bytes, the LDS attribute, the skinny
-// rings of 16 / 8 K-tiles, ldx = K, ldo = F or F / 2, the epilogues each loop is not built for).  Change both places together; the model-level tests remain the
-// check that the library launches with it.  `loop` means what KIRAG_AMD_PROJ_TILE means: 256 ping-pong, 128 streaming, 130 producer / consumer, 64 / 32 skinny.
+// The launch itself (grid, block size, LDS bytes and attribute, the skinny rings, the instantiation an epilogue has on a loop) is the library's:
+// launch_proj_loop of encoder_proj.hpp, the one every projection of a forward goes through, called with the caller's `loop`, `blocks`, `nt` and `ant`, ldx = K
+// and ldo = F or F / 2.  `loop` means what KIRAG_AMD_PROJ_TILE means: 256 ping-pong, 128 streaming, 130 producer / consumer, 64 / 32 skinny.
 #include "../../kirag_amd/csrc/encoder_proj.hpp"
 
 #include <cstring>
@@ -122,70 +122,6 @@ static int check_args(const ProjProbeArgs& a) {
     return 0;
 }
 
-template <int EPI, class Shape, bool NT>
-static hipError_t run_shape(const ProjArgs& p, int blocks, bool ant) {
-    // launch_proj_shape_nt (encoder.hip)
-    constexpr int lds = 2 * Shape::STAGE_BYTES + Shape::NWAVE * EPI_STAGE_BYTES;
-    auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(Shape::NTHREADS), lds, 0, p);
-        return hipGetLastError();
-    };
-    if constexpr (EPI == EPI_QKV_ROTB && Shape::BM == 256) return hipErrorInvalidValue;      // refused by check_args
-    else if constexpr (EPI == EPI_SPLADE && NT) return hipErrorInvalidValue;
-    else if constexpr (EPI == EPI_DENSE && Shape::BM == 256) return ant ? go(&k_proj<EPI_DENSE, Shape, 2, NT, true>) : go(&k_proj<EPI_DENSE, Shape, 2, NT>);
-    else return go(&k_proj<EPI, Shape, 2, NT>);
-}
-
-template <int EPI, int WM>
-static hipError_t run_skinny(const ProjArgs& p, int T) {
-    // the skinny branch of launch_proj (encoder.hip)
-    constexpr int RING = WM == 1 ? 16 : 8;
-    using G = SkinnyGeom<WM, WM>;
-    constexpr int lds = RING * G::STAGE;
-    auto kern = &k_proj_skinny<EPI, RING, WM, WM>;
-    const dim3 grid((unsigned)(p.F / (32 * WM)), (unsigned)((T + 32 * WM - 1) / (32 * WM)));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(G::THREADS), lds, 0, p);
-    return hipGetLastError();
-}
-
-template <int EPI>
-static hipError_t run_epi(const ProjProbeArgs& a, const ProjArgs& p, int num_cu) {
-    switch (a.loop) {
-        case 256: return a.nt ? run_shape<EPI, ShapeBig, true>(p, a.blocks ? a.blocks : num_cu, a.ant != 0) : run_shape<EPI, ShapeBig, false>(p, a.blocks ? a.blocks : num_cu, a.ant != 0);
-        case 128: return a.nt ? run_shape<EPI, ShapeSmall, true>(p, a.blocks ? a.blocks : 2 * num_cu, false) : run_shape<EPI, ShapeSmall, false>(p, a.blocks ? a.blocks : 2 * num_cu, false);
-        case 130: {
-            // the producer / consumer branch of launch_proj (encoder.hip)
-            constexpr int lds = SPLIT_RING * ShapeSplit::STAGE_BYTES + 4 * EPI_STAGE_BYTES;
-            auto kern = &k_proj_split<EPI>;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(a.blocks ? a.blocks : num_cu), dim3(SPLIT_THREADS), lds, 0, p);
-            return hipGetLastError();
-        }
-        case 64: return run_skinny<EPI, 2>(p, a.T);
-        default: return run_skinny<EPI, 1>(p, a.T);
-    }
-}
-
-static hipError_t run(const ProjProbeArgs& a, const ProjArgs& p, int num_cu) {
-    switch (a.epi) {
-        case EPI_QKV: return run_epi<EPI_QKV>(a, p, num_cu);
-        case EPI_DENSE: return run_epi<EPI_DENSE>(a, p, num_cu);
-        case EPI_GELU: return run_epi<EPI_GELU>(a, p, num_cu);
-        case EPI_QKV_ROT: return run_epi<EPI_QKV_ROT>(a, p, num_cu);
-        case EPI_QKV_ROTB: return run_epi<EPI_QKV_ROTB>(a, p, num_cu);
-        case EPI_SWIGLU: return run_epi<EPI_SWIGLU>(a, p, num_cu);
-        case EPI_GEGLU: return run_epi<EPI_GEGLU>(a, p, num_cu);
-        case EPI_RELU: return run_epi<EPI_RELU>(a, p, num_cu);
-        case EPI_GEGLU_TANH: return run_epi<EPI_GEGLU_TANH>(a, p, num_cu);
-        default: return run_epi<EPI_SPLADE>(a, p, num_cu);
-    }
-}
-
 #ifdef KR_ENC_BUILD_F16
 #define KR_PROJ_PROBE kr_proj_probe_f16
 #else
@@ -232,7 +168,7 @@ extern "C" __attribute__((visibility("default"))) int KR_PROJ_PROBE(const ProjPr
         PR_HIP(upload(bufs, &smax, init.data(), init.size()));
         PR_HIP(upload(bufs, &row_seq, a.row_seq, capT));
     }
-    // ProjArgs as launch_proj completes them (encoder.hip): ldx = K, ldo = the width of out0
+    // ProjArgs as launch_proj completes them (encoder_proj.hpp): ldx = K, ldo = the width of out0
     p.W = W; p.X = X; p.Tp = Tp; p.F = a.F; p.K = a.K; p.H = a.H; p.A = a.A; p.bias = bias;
     p.out0 = splade ? nullptr : out0 + GUARD_ROWS * w0;
     p.out1 = qkv ? out1 + (size_t)GUARD_ROWS * a.A : nullptr;
@@ -241,7 +177,13 @@ extern "C" __attribute__((visibility("default"))) int KR_PROJ_PROBE(const ProjPr
     p.pw = a.pw; p.epi_prio = a.epi_prio; p.ant = a.ant; p.nt = a.nt;
     p.rot_cos = rc_; p.rot_sin = rs_; p.tpos = tpos; p.max_pos = a.max_pos; p.dh = a.dh;
     p.row_seq = row_seq; p.smax = splade ? smax + a.V : nullptr; p.V = a.V;
-    PR_HIP(run(a, p, num_cu));
+    {   // the library's launcher on the caller's loop.  blocks = 0: the persistent grid of a forward, one block per CU, two on the streaming loop.  A launcher
+        // that fails without a HIP error has refused its arguments (check_args refuses them first)
+        const int blocks = a.blocks ? a.blocks : a.loop == 128 ? 2 * num_cu : num_cu;
+        const int lrc = launch_proj_loop(a.epi, p, a.loop, blocks, a.T, dev, 0);
+        const hipError_t le = hipGetLastError();
+        PR_HIP(le != hipSuccess || lrc == 0 ? le : hipErrorInvalidValue);
+    }
     PR_HIP(hipDeviceSynchronize());
     if (!splade) PR_HIP(hipMemcpy(a.out0, out0, rows * w0 * 2, hipMemcpyDeviceToHost));
     if (qkv) {

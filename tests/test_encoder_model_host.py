@@ -389,3 +389,43 @@ def test_heads_after_the_first_finalize(check):
     # an optional tensor of ModernBert's head may arrive after a finalize without it
     late = modern + [ln for ln in MCLS if ln[1] in MR.HEAD_REQUIRED] + FIN + [ln for ln in MCLS if ln[1] not in MR.HEAD_REQUIRED] + FIN
     assert all(d["rc"] == 0 for d in check(late, **mkw))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# what a pool runs on a plan (resolve_pool): the forward and the result copy read this one table
+# ---------------------------------------------------------------------------------------------------------
+POOL_MEAN, POOL_CLS, POOL_CLASSIFY, POOL_SPLADE, POOL_LAST = 0, 1, 2, 4, 5
+# pool -> (pack, select, classify, score, splade, one_row); select None: a splade forward does not pool
+POOLS_COMMON = {POOL_MEAN: (POOL_MEAN, POOL_MEAN, 0, 0, 0, 0), POOL_CLS: (POOL_CLS, POOL_CLS, 0, 0, 0, 1), POOL_SPLADE: (POOL_MEAN, None, 0, 0, 1, 0),
+                POOL_LAST: (POOL_MEAN, POOL_LAST, 0, 0, 0, 0)}
+CLASSIFY_CLS_ROW, CLASSIFY_MEAN, CLASSIFY_SCORE = (POOL_CLS, POOL_CLS, 1, 0, 0, 1), (POOL_MEAN, POOL_MEAN, 1, 0, 0, 0), (POOL_MEAN, POOL_LAST, 1, 1, 0, 1)
+
+
+def decoder_with_score_head(heads=4):
+    """a decoder handle (config.decoder_attention, the Qwen2 / Llama names) with score.weight [3, H]"""
+    t = [("embed_tokens.weight", V * H), ("norm.weight", H)]
+    for l in range(L):
+        p = "layers.%d." % l
+        t += [(p + "input_layernorm.weight", H), (p + "post_attention_layernorm.weight", H)] + [(p + "mlp.%s_proj.weight" % x, FF * H) for x in ("gate", "up", "down")]
+        t += [(p + "self_attn.%s_proj.weight" % x, H * H) for x in "qkvo"]
+    lines = [("setting", "config.rotary_inv_freq", [0.5] * (H // heads // 2)), ("setting", "config.decoder_attention", [1.0])]
+    return lines + [("tensor", n, k) for n, k in t] + [("tensor", "score.weight", 3 * H)], dict(heads=heads, type_vocab=1)
+
+
+@pytest.mark.parametrize("plan,classify", [("bert+cls", CLASSIFY_CLS_ROW), ("modernbert+head", CLASSIFY_CLS_ROW), ("modernbert+head+mean", CLASSIFY_MEAN),
+                                           ("decoder+score", CLASSIFY_SCORE)])
+def test_resolve_pool_table(check, plan, classify):
+    if plan == "bert+cls":
+        lines, kw = script("bert", extra=CLS)
+    elif plan.startswith("modernbert"):
+        lines, kw = script("modernbert", extra=MCLS + ([("setting", MR.POOLING_NAME, [1])] if plan.endswith("+mean") else []))
+    else:
+        lines, kw = decoder_with_score_head()
+    out = check(lines + FIN + [("pools",)], **kw)
+    assert all(d["rc"] == 0 for d in out), [d for d in out if d["rc"]]
+    want = dict(POOLS_COMMON)
+    want[POOL_CLASSIFY] = classify
+    for pool, row in want.items():
+        got = tuple(int(x) for x in out[-1]["pool%d" % pool].split(","))
+        assert len(got) == 6 and all(g == w for g, w in zip(got, row) if w is not None), (plan, pool, got, row)
+    assert check([("pools",)])[-1]["rc"] == KR_ESTATE      # nothing finalized: no plan to resolve

@@ -2,7 +2,7 @@
 """What bge-m3's token-level heads cost: flagged (KR_POOL_WITH_SPARSE | KR_POOL_WITH_COLBERT) against unflagged CLS forwards on ONE handle with the heads
 (synthetic weights), alternated in one process, device output.
 
-    python tools/m3_bench.py [--shape xlmr-large] [--batches 1x64,100x256,1000x128] [--P 1024] [--rounds 6] [--once]
+    python tools/m3_bench.py [--shape xlmr-large] [--batches 1x64,100x256,1000x128] [--P 1024] [--rounds 6] [--once [--digest]]
     KIRAG_AMD_LIB=<another build> KIRAG_AMD_LIB_OLDER=1 python tools/m3_bench.py --plain [--shape e5-large] [--batches 1024x128] [--dump out.npy]
 
 A flagged forward differs from the unflagged one in three things: its last layer runs on every row instead of the CLS rows, one more [T, H] x [H, P] product,
@@ -25,6 +25,7 @@ ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--once", action="store_true")
 ap.add_argument("--plain", action="store_true")
 ap.add_argument("--dump", default=None)
+ap.add_argument("--digest", action="store_true", help="with --once: append the sha256 (16 hex digits) of the flagged forward's three blocks")
 args = ap.parse_args()
 sys.argv = sys.argv[:1]
 import enc_bench as EB  # noqa: E402  (its shape table)
@@ -48,8 +49,9 @@ for B, S in (tuple(int(v) for v in t.split("x")) for t in args.batches.split(","
     if "pad_token_id" in cfg:
         ids = torch.where(mask != 0, ids, torch.full_like(ids, cfg["pad_token_id"]))
     if args.once:
-        enc.forward(ids, mask, FLAGGED); torch.cuda.synchronize()
-        print(f"{args.shape} {B} x {S} P={args.P}: one flagged forward", flush=True)
+        blocks = enc.forward(ids, mask, FLAGGED); torch.cuda.synchronize()
+        print(f"{args.shape} {B} x {S} P={args.P}: one flagged forward" + (f"  sha256 dense {EB.digest(blocks[0])} sparse {EB.digest(blocks[1])} colbert {EB.digest(blocks[2])}"
+                                                                         if args.digest else ""), flush=True)
         continue
     pools = (POOL_MEAN,) if args.plain else (FLAGGED, POOL_CLS)
     res = {p: [] for p in pools}

@@ -2,7 +2,7 @@
 """What the SPLADE head costs: KR_POOL_SPLADE against mean-pool forwards on ONE handle with the MLM head (synthetic weights, bert-base shape: 12 layers,
 H 768, V 30522), alternated in one process, device output.
 
-    python tools/splade_bench.py [--batches 1x32,100x256,1024x128] [--rounds 6] [--once]
+    python tools/splade_bench.py [--batches 1x32,100x256,1024x128] [--rounds 6] [--once [--digest]]
     python tools/splade_bench.py --trace <directory of a rocprofv3 --kernel-trace run of --once>
 
 A SPLADE forward differs from the mean-pool one in: its last layer is the same (mean pooling runs it on every row too), no k_pool, one H -> H EPI_GELU
@@ -10,7 +10,7 @@ projection, the transform LayerNorm, and the decoder launch [T] x [Vpad, H]^T wi
 [B, V] zero-fill and k_splade_finish.  --once runs one SPLADE forward per batch shape and nothing else: the run to put under a kernel trace; --trace prints,
 from that trace, the decoder launch's time per FLOP next to the FF1 + GELU launches of the same forward.
 The unflagged A/B against the parent commit's library is tools/m3_bench.py --plain (KIRAG_AMD_LIB, --dump for the bit-for-bit comparison)."""
-import argparse, csv, glob, os, sys, time
+import argparse, csv, glob, hashlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
@@ -22,6 +22,7 @@ ap.add_argument("--batches", default="1x32,100x256,1024x128")
 ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--once", action="store_true")
 ap.add_argument("--trace", default=None)
+ap.add_argument("--digest", action="store_true", help="with --once: append the sha256 (16 hex digits) of the [B, V] result")
 args = ap.parse_args()
 
 
@@ -70,7 +71,8 @@ for B, S in (tuple(int(v) for v in t.split("x")) for t in args.batches.split(","
     ids, mask = BS.synthetic_tokens(dev, B, S, seed=1)
     if args.once:
         out = enc.forward(ids, mask, POOL_SPLADE); torch.cuda.synchronize()
-        print(f"bert-base {B} x {S}: one SPLADE forward, zero share {float((out == 0).float().mean()):.3f}", flush=True)
+        print(f"bert-base {B} x {S}: one SPLADE forward, zero share {float((out == 0).float().mean()):.3f}"
+              + (f"  sha256 {hashlib.sha256(out.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]}" if args.digest else ""), flush=True)
         continue
     pools = (POOL_SPLADE, POOL_MEAN)
     res = {p: [] for p in pools}
