@@ -385,6 +385,19 @@ void kr_encoder_destroy(kr_encoder* enc);
  *       any other name on the handle, a head's tensors included, is KR_EINVAL at finalize, and these names' decoder-only rows on another handle likewise;
  *     - the forwards take KR_POOL_MEAN and KR_POOL_LAST; KR_POOL_CLS / KR_POOL_SPLADE are KR_EINVAL, and so is KR_POOL_CLASSIFY unless the handle holds
  *       the score head ("score.weight", below: the one head's tensor a decoder handle takes).
+ *   "config.head_dim": data = ONE float, 32, 64 or 128: the head width d_h of a decoder handle where it is a config field of its own (transformers Qwen3Model:
+ *   Qwen3-Embedding-0.6B, Qwen3-Reranker-0.6B); anything else is KR_EINVAL, and so is the setting on a handle without "config.decoder_attention" (at finalize).
+ *   Send it before "config.rotary_inv_freq" — which then takes d_h / 2 values — and before the weights (behind a layer's attention tensors it is KR_EINVAL);
+ *   the usual rule of the settings holds.  Never loaded: d_h = hidden / heads and the handle is what it always was.  With it
+ *     - q and the context are Dq = heads * d_h wide, a multiple of 128 up to 4096 (else KR_EINVAL at finalize): "layers.N.self_attn.q_proj.weight" is
+ *       [Dq, hidden], "o_proj.weight" [hidden, Dq], "k_proj.weight" / "v_proj.weight" [A, hidden] with A = kv_heads * d_h <= Dq, kv_heads a divisor of heads and
+ *       A % 64 == 0; any other element count is KR_EINVAL at load, naming the tensor.  kr_bert_cfg is unchanged: hidden / heads must still be 32 or 64 at
+ *       kr_encoder_create, so Qwen3-0.6B (1024 / 16 = 64, d_h = 128) loads and Qwen3-1.7B (2048 / 16) does not;
+ *     - "layers.N.self_attn.q_norm.weight" and "layers.N.self_attn.k_norm.weight", fp32 [d_h] each, are the RMS norms Qwen3 applies to every head of q and of
+ *       k behind the projection and in front of the rotation: x * rsqrt(mean(x^2) + ln_eps) * weight over the head's d_h features.  Decoder handles only
+ *       (with or without "config.head_dim"), every layer's two or none (a partial set is KR_ESTATE at finalize, naming the missing tensor), never next to a
+ *       q_proj / k_proj bias, fixed at the first finalize like a head.  The value 128 needs them (KR_EINVAL at finalize without).  Such a handle runs one more
+ *       kernel per layer, in place on q and k; 128-wide heads run a kernel of their own (k_attn_wide) at every sequence length.
  *   "config.deberta_position_buckets" + "config.deberta_max_relative_positions": data = ONE float each, Bk (even, 2 .. 256) and M (M - 1 > Bk / 2):
  *   DebertaV2Config's position_buckets and max_relative_positions (max_position_embeddings where that is < 1).  The two together, loaded before the first
  *   finalize, make the handle a DeBERTa handle (DebertaV2Model: microsoft/deberta-v3-* and their fine-tunes) for life; the usual rule of the settings holds

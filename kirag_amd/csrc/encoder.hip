@@ -48,6 +48,9 @@ struct LayerW {
     // DeBERTa handles: query_proj / key_proj as loaded (fp32 [H, H]); PQ / PK = their projections of the position table, [heads][TP][d_h] 16-bit (build_disent_tables)
     float *wq32 = nullptr, *wk32 = nullptr;
     uint16_t *pq16 = nullptr, *pk16 = nullptr;
+    // handles with q / k norms (Qwen3): the norm weights [d_h] fp32, q's with the score scale log2(e) / sqrt(d_h); the scale the loader folded into W_q (k_qk_norm_rope)
+    float *qng = nullptr, *kng = nullptr;
+    float qfold = 1.f;
 };
 
 // A/B switches of the projection / attention launches, read from the environment ONCE per forward (enqueue_forward), not per launch: a forward is 96
@@ -183,6 +186,7 @@ static void pos_span(const Encoder* e, int S, int& p0, int& W) {
 static int ensure_ws(Encoder* e, int B, int S) {
     const int64_t maxT = (int64_t)B * (S + 8);
     const int H = e->cfg.hidden, FF = e->cfg.intermediate;
+    const int64_t Dq = e->plan.q_dim;     // q and ctx rows: heads d_h wide, H unless the handle has a head width of its own
     int span_p0 = 0, span_W = 0;
     if (e->plan.family == model::DEBERTA) pos_span(e, S, span_p0, span_W);
     if (!e->d_T) {
@@ -217,27 +221,27 @@ static int ensure_ws(Encoder* e, int B, int S) {
     if (p.ws & model::WS_SLOT_ROW) KR_TRY(dmalloc(e->ws_bufs, &e->slot_row, capBS * 4));
     if (p.ws & model::WS_ROW_SEQ) KR_TRY(dmalloc(e->ws_bufs, &e->row_seq, capT * 4));
     if (p.ws & model::WS_CY) KR_TRY(dmalloc(e->ws_bufs, &e->cy, capT * p.head_dim[model::HEAD_COLBERT] * 2));      // capT rows: the projection's tiles are whole (see k_proj)
-    KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * H * 2));
+    KR_TRY(dmalloc(e->ws_bufs, &e->xb, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->q, capT * Dq * 2));
     const int64_t A = p.kv_dim;   // k [T, A] and V^T [A, ldv] exist once per KV head: A = H unless the handle is a grouped-query decoder's
     KR_TRY(dmalloc(e->ws_bufs, &e->k, (capT + 64) * A * 2));    // 64 rows of slack: k_attn_dma reads whole 64-key chunks (the rows past a sequence are masked)
     KR_HIP(hipMemset(e->k, 0, (size_t)(capT + 64) * A * 2));
     e->ldv = capT + 64;   // slack: the last key tile of the last sequence may read up to 43 columns past T
     KR_TRY(dmalloc(e->ws_bufs, &e->vT, (size_t)A * e->ldv * 2));
     KR_HIP(hipMemset(e->vT, 0, (size_t)A * e->ldv * 2));
-    KR_TRY(dmalloc(e->ws_bufs, &e->ctx, capT * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->h, capT * FF * 2));
+    KR_TRY(dmalloc(e->ws_bufs, &e->ctx, capT * Dq * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->h, capT * FF * 2));
     if (p.pre_ln) {
         KR_TRY(dmalloc(e->ws_bufs, &e->rb, capT * H * 2));
         if (e->use_lo) KR_TRY(dmalloc(e->ws_bufs, &e->rlo, capT * H));
     }
     if (e->cls_shortcut) {
         const int64_t capC = round_up(capB, 256);                 // token-indexed buffers come in multiples of the 256-row tile (see k_proj)
-        KR_TRY(dmalloc(e->ws_bufs, &e->c_ctx, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xb, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_y, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xlo, capC * H));
+        KR_TRY(dmalloc(e->ws_bufs, &e->c_ctx, capC * Dq * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xb, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_y, capC * H * 2)); KR_TRY(dmalloc(e->ws_bufs, &e->c_xlo, capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_h, capC * FF * 2));
         if (p.pre_ln) {
             KR_TRY(dmalloc(e->ws_bufs, &e->c_rb, capC * H * 2)); KR_HIP(hipMemset(e->c_rb, 0, (size_t)capC * H * 2));
             if (e->use_lo) { KR_TRY(dmalloc(e->ws_bufs, &e->c_rlo, capC * H)); KR_HIP(hipMemset(e->c_rlo, 0x80, (size_t)capC * H)); }
         }
-        KR_HIP(hipMemset(e->c_ctx, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xb, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xlo, 0x80, (size_t)capC * H));
+        KR_HIP(hipMemset(e->c_ctx, 0, (size_t)capC * Dq * 2)); KR_HIP(hipMemset(e->c_xb, 0, (size_t)capC * H * 2)); KR_HIP(hipMemset(e->c_xlo, 0x80, (size_t)capC * H));
         KR_TRY(dmalloc(e->ws_bufs, &e->c_off, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_nk, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->c_cls, capB * 4)); KR_TRY(dmalloc(e->ws_bufs, &e->d_B, sizeof(int)));
     }
     e->capT = capT; e->capB = (int)capB; e->capBS = capBS; e->capW = span_W;
@@ -369,9 +373,9 @@ static int enqueue_tail(const Forward& f, ProjArgs a, const LayerW& l, const Row
     const model::ModelPlan& p = f.e->plan;
     const int H = f.H, FF = f.FF;
     const bool pre = p.pre_ln;
-    a.Tp = r.rows;
-    // attention.output.dense / attn.Wo, then the norm: xb = LayerNorm(y + b + xb), or r += y + b; xb = mlp_norm(r)
-    proj(a, l.wo, r.ctx, H, H, l.bo_eff, r.y);
+    a.Tp = r.rows; a.H = H;
+    // attention.output.dense / attn.Wo (K = the width of the context), then the norm: xb = LayerNorm(y + b + xb), or r += y + b; xb = mlp_norm(r)
+    proj(a, l.wo, r.ctx, H, p.q_dim, l.bo_eff, r.y);
     KR_TRY(launch_proj(EPI_DENSE, a, r.max_rows, f.pl, f.st));
     launch_norm(f, r, l.bo_eff, l.ln1g, l.ln1b, rin, rin_lo, r.rb, pre ? nullptr : r.lo);
     // intermediate.dense + GELU, or gate_proj | up_proj / mlp.Wi (input | gate) as one GEMM of 2 FF columns + SwiGLU / GEGLU: h [rows, FF] either way.  A T5
@@ -389,22 +393,30 @@ static int enqueue_tail(const Forward& f, ProjArgs a, const LayerW& l, const Row
 // one layer: q | k | v^T, attention, for the last layer of a shortcut forward the gather, the tail
 static int enqueue_layer(const Forward& f, size_t li) {
     using namespace model;
-    static constexpr int QKV_EPI[] = {EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB};   // by QkvKind
+    static constexpr int QKV_EPI[] = {EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB, EPI_QKV_SPLIT};   // by QkvKind
     Encoder* e = f.e;
     const ModelPlan& p = e->plan;
     const LayerW& l = e->L[li];
     const LayerPlan& lp = p.layers[li];
     const bool first = li == 0, last = li + 1 == e->L.size(), pre = p.pre_ln;
-    const int H = f.H;
+    const int H = f.H, Dq = p.q_dim;           // Dq = heads d_h: the width of q and ctx (H unless the handle has a head width of its own)
     const bool local = lp.attn == AM_WIN;      // a ModernBert handle's sliding-window layer: its own rotary table, windowed attention
     ProjArgs a{};
-    a.Tp = e->d_T; a.H = H;
-    a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = H / e->cfg.heads;
-    // q | k | v^T in one GEMM (F = H + 2A: 3H unless k and v are a grouped-query decoder's)
+    a.Tp = e->d_T; a.H = Dq;
+    a.rot_cos = local ? e->rot_cos_l : e->rot_cos; a.rot_sin = local ? e->rot_sin_l : e->rot_sin; a.tpos = e->tok_rpos; a.max_pos = e->cfg.max_pos; a.dh = p.head_w;
+    // q | k | v^T in one GEMM (F = Dq + 2A: 3H unless k and v are a grouped-query decoder's or the head width is the handle's own)
     a.A = p.kv_dim;
-    proj(a, l.wqkv, e->xb, H + 2 * p.kv_dim, H, l.bqkv, e->q);
+    proj(a, l.wqkv, e->xb, Dq + 2 * p.kv_dim, H, l.bqkv, e->q);
     a.out1 = e->k; a.outT = e->vT; a.ldT = e->ldv;
     KR_TRY(launch_proj(QKV_EPI[lp.qkv], a, f.maxT, f.pl, f.st));
+    if (lp.qkv == QKV_SPLIT) {
+        // the q / k norms of the layer and the rotation behind them, in place on q and k: one more read and write of both
+        const int nh = e->cfg.heads + p.kv_dim / p.head_w, lph = p.head_w / 8;
+        const auto norm_kernel = p.head_w == 128 ? &k_qk_norm_rope<128> : p.head_w == 64 ? &k_qk_norm_rope<64> : &k_qk_norm_rope<32>;
+        const int64_t units = f.maxT * nh, per_block = 4 * (64 / lph);
+        hipLaunchKernelGGL(norm_kernel, dim3((unsigned)((units + per_block - 1) / per_block)), dim3(256), 0, f.st, e->q, e->k, e->d_T, e->cfg.heads, p.kv_dim / p.head_w, l.qng, l.kng,
+                           f.eps * l.qfold * l.qfold, f.eps, a.rot_cos, a.rot_sin, e->tok_rpos, e->cfg.max_pos);
+    }
     auto attend = [&](auto dh) -> int {
         constexpr int DH = decltype(dh)::value;
         if (lp.attn == AM_DISENT) {      // q . PK and k . PQ of every packed row, for the bias tiles of this layer's attention
@@ -418,7 +430,12 @@ static int enqueue_layer(const Forward& f, size_t li) {
             return launch_attention<DH>(f.attn, (int)round_up(f.S, 32), f.nqt_max, f.long_seq, attn_mode_args<decltype(am)::value>(e, f.span_p0, f.span_W), e->device, f.st);
         });
     };
-    if (H == 32 * e->cfg.heads) KR_TRY(attend(std::integral_constant<int, 32>{})); else KR_TRY(attend(std::integral_constant<int, 64>{}));
+    if (p.head_w == 128) {
+        // (its own lambda: the 128-wide kernels are built for the plain and the window / causal modes, and no k_pos_scores<128> exists)
+        if (lp.attn == AM_CAUSAL) KR_TRY(launch_attention<128>(f.attn, (int)round_up(f.S, 32), f.nqt_max, false, causal_args(e), e->device, f.st));
+        else if (lp.attn == AM_PLAIN) KR_TRY(launch_attention<128>(f.attn, (int)round_up(f.S, 32), f.nqt_max, false, AttnNoBiasArgs{}, e->device, f.st));
+        else return fail(KR_ESTATE, "attention mode %d is not built for 128-wide heads", (int)lp.attn);
+    } else if (p.head_w == 32) KR_TRY(attend(std::integral_constant<int, 32>{})); else KR_TRY(attend(std::integral_constant<int, 64>{}));
     // CLS shortcut: only the CLS row of every sequence is read after the last layer: gather those rows and finish the layer on B rows (same kernels, same
     // arithmetic per row: the projection loops are bit-identical for every tiling and LayerNorm is per row, so the embedding does not change by one bit)
     // (a pre-LN handle: the residual stream travels in the place of xb — the operand is rewritten by the first norm of the tail)
@@ -428,7 +445,7 @@ static int enqueue_layer(const Forward& f, size_t li) {
     const uint8_t* rin_lo = in_rb ? f.all_rows.rlo : f.all_rows.lo;
     if (!(last && f.shortcut)) return enqueue_tail(f, a, l, f.all_rows, last, rin, rin_lo);
     hipLaunchKernelGGL(k_gather_cls, dim3(f.B), dim3(256), 0, f.st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
-                       pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, f.pool.score ? 1 : 0);
+                       pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, f.pool.score ? 1 : 0, Dq);
     return enqueue_tail(f, a, l, f.cls_rows, last, e->c_rb, f.cls_rows.rlo);
 }
 // KR_POOL_SPLADE behind the last layer: the MLM head on every packed row, max over each sequence's rows, log1p — into f.tok_out [B, vocab]
@@ -534,7 +551,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     const int cls_row = f.pool.pack == KR_POOL_CLS ? 1 : 0;      // the query-only row of a masked column 0
     f.nqt_max = (S + cls_row + 31) / 32;
     f.disent = p.pos == POS_DISENT;
-    f.long_seq = f.nqt_max > 4 && !e->kn.attn_lds && !f.disent;
+    f.long_seq = f.nqt_max > 4 && !e->kn.attn_lds && !f.disent && p.head_w != 128;      // (128-wide heads: k_attn_wide at every length)
     if (f.disent) pos_span(e, S, f.span_p0, f.span_W);
     f.align = f.long_seq ? 8 : 4;
     const PackRules rules{e->cfg.vocab, e->cfg.type_vocab, f.pool.pack, f.align, p.pad_idx};
@@ -550,7 +567,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     // last layer finishes on the gathered rows.  The token-level heads read every row of the last layer
     f.shortcut = f.pool.one_row && e->cls_shortcut && e->c_ctx != nullptr && !flags;
     e->last_shortcut = f.shortcut;
-    f.attn = AttnOperands{e->q, e->k, e->vT, e->ldv, e->seq_off, e->seq_nk, e->seq_nq, e->ctx, f.H, e->cfg.heads, p.kv_dim, e->capT, B};
+    f.attn = AttnOperands{e->q, e->k, e->vT, e->ldv, e->seq_off, e->seq_nk, e->seq_nq, e->ctx, p.q_dim, e->cfg.heads, p.kv_dim, e->capT, B};
     f.all_rows = RowSet{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, f.maxT, f.ln_grid,
                         e->rb, e->use_lo ? e->rlo : nullptr};
     f.cls_rows = RowSet{e->c_ctx, e->c_xb, e->c_y, e->c_h, e->use_lo ? e->c_xlo : nullptr, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, B,

@@ -20,10 +20,13 @@ namespace KR_ENC_NS {
 // perm(i) = i with bits 2 and 3 exchanged: a lane's registers 8a .. 8a+7 then hold 8 CONSECUTIVE keys (16 a + 8 hf .. + 7), i.e. the P^T fragment of a
 // k-step matches one contiguous 16-byte run of a V^T row (without the permutation a lane owns keys {0..3, 8..11} + 4 hf: two 8-byte reads per fragment).
 // The permutation maps each ds_read_b128 lane group onto itself, so the K reads stay bank-conflict free.
-// Everything is a template on the head width DH (32 or 64): S^T takes DH / 16 k-steps of the 32x32x16 MFMA, O^T is DH / 32 accumulators of 32 d rows.
+// Everything is a template on the head width DH (32, 64 or 128): S^T takes DH / 16 k-steps of the 32x32x16 MFMA, O^T is DH / 32 accumulators of 32 d rows.
+// (DH = 128 — Qwen3 handles — is built into the register-staged body only and launched as k_attn_wide, at every sequence length; it has no bias-table and no
+// disentangled mode.)
 //   K image   rows of 2 DH bytes (DH / 8 16-B chunks), chunk index XOR attn_kswz<DH>(key): DH = 64 128-B rows, XOR ((key >> 1) & 7) (same image as the
-//             GEMM ring); DH = 32 64-B rows, XOR ((key >> 2) & 3).  Either way the 16 lanes of a ds_read_b128 group (keys {0..3, 12..15, 20..27} or
-//             {4..11, 16..19, 28..31} of a 32-key tile) land on 16 different 16-B slots of a 256-B bank window
+//             GEMM ring); DH = 32 64-B rows, XOR ((key >> 2) & 3); DH = 128 256-B rows (every row starts on bank 0), XOR (key & 15).  Either way the 16 lanes
+//             of a ds_read_b128 group (keys {0..3, 12..15, 20..27} or {4..11, 16..19, 28..31} of a 32-key tile: key & 15 takes 16 different values in both)
+//             land on 16 different 16-B slots of a 256-B bank window
 //   V^T image k_attn_lds: DH rows, row pitch 2 * cap + 8 bytes (pitch / 8 odd: conflict-free ds_read_b64), keys >= nk stored as zero;
 //             k_attn_dma: [DH d][128 B] per chunk, chunk index XOR ((d >> 1) & 7) like the 64-wide K image (one ds_read_b128 per fragment), columns >= nk
 //             of the last chunk zeroed in LDS after they landed (no 0 * NaN from rows of other sequences).
@@ -31,7 +34,7 @@ namespace KR_ENC_NS {
 // ---------------------------------------------------------------------------------------------------------
 template <int DH>
 struct AttnState {
-    static_assert(DH == 32 || DH == 64, "head width 32 or 64");
+    static_assert(DH == 32 || DH == 64 || DH == 128, "head width 32, 64 or 128");
     f32x16 o[DH / 32];  // O^T of the tile: d rows 32 j .. 32 j + 31 in o[j]
     float mref, l;      // reference maximum (log2 units) the accumulated o / l are scaled by; running denominator
 };
@@ -47,9 +50,9 @@ __device__ __forceinline__ void attn_init(AttnState<DH>& s) {
 
 __device__ __forceinline__ int attn_perm(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
-// 16-B chunk swizzle of row `key` of a K image with 2 DH-byte rows (128 / DH rows per 256-B bank window)
+// 16-B chunk swizzle of row `key` of a K image with 2 DH-byte rows (128 / DH rows per 256-B bank window; DH = 128: one)
 template <int DH>
-__device__ __forceinline__ int attn_kswz(int key) { return (key >> (DH == 64 ? 1 : 2)) & (DH / 8 - 1); }
+__device__ __forceinline__ int attn_kswz(int key) { return (key >> (DH == 128 ? 0 : DH == 64 ? 1 : 2)) & (DH / 8 - 1); }
 
 // One 64-key step of a wave's 32-query tile.  Kst: K image (128-B rows, swizzled), k0 = row of the step's first key in it; nvalid = keys of the
 // step that exist (MASKED instantiation: < 64; <= 32: the second 32-key tile is skipped — it would only add exact zeros); vfrag(dh, ks) returns the
@@ -403,6 +406,7 @@ __device__ __forceinline__ void attn_step64(AttnState<DH>& s, const uint4 (&qf)[
     else attn_step64m<3>(s, qf, Kst, k0, nvalid, c, hf, vfrag, bl, kb);
 }
 
+// (H: the row pitch of ctx, heads * DH)
 // normalise a finished 32-query tile and store it as whole 2 DH-byte rows of ctx (columns head * DH ..) through the wave-private LDS block Os of
 // 32 x 2 DH bytes (8-byte chunk index XOR the row)
 // ZERO_EMPTY (window instantiations): a query whose window holds no attended key (the CLS row of a masked column 0 whose sequence starts beyond column w)
@@ -429,7 +433,7 @@ __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os
     }
 #pragma unroll
     for (int p4 = 0; p4 < 32 * LR / 64; ++p4) {
-        const int rq = p4 * (64 / LR) + (lane >> (DH == 64 ? 3 : 2)), ch = lane & (LR - 1);
+        const int rq = p4 * (64 / LR) + (lane >> (DH == 128 ? 4 : DH == 64 ? 3 : 2)), ch = lane & (LR - 1);
         const uint2 lo = *reinterpret_cast<const uint2*>(Os + rq * RB + (((2 * ch) ^ (rq & (C8 - 1))) << 3));
         const uint2 hi = *reinterpret_cast<const uint2*>(Os + rq * RB + (((2 * ch + 1) ^ (rq & (C8 - 1))) << 3));
         if (q0 + rq < nq) *reinterpret_cast<uint4*>(ctx + (off + q0 + rq) * H + head * DH + ch * 8) = make_uint4(lo.x, lo.y, hi.x, hi.y);
@@ -447,7 +451,7 @@ __device__ __forceinline__ void attn_store_tile(const AttnState<DH>& s, char* Os
 // division by a kernel argument is a reciprocal sequence in every block of the short-sequence launches.  group = 1: kv_mul = 65537, the head itself.
 __host__ __device__ inline int attn_kv_mul(int group) { return 65536 / group + 1; }
 __device__ __forceinline__ int attn_kv_head(int head, int kv_mul) { return (int)(((unsigned)head * (unsigned)kv_mul) >> 16); }
-template <int DH> constexpr int attn_lds_blocks() { return DH == 64 ? 3 : 4; }
+template <int DH> constexpr int attn_lds_blocks() { return DH == 128 ? 1 : DH == 64 ? 3 : 4; }
 template <int DH, int HPB, int BM>
 __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
                                               const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
@@ -462,11 +466,13 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
     if ((int)blockIdx.z * QT * 32 >= nq) return;          // block-uniform: no q-tile of this block exists (nq == 0 included)
     const int nk = seq_nk[b];
     const int64_t off = seq_off[b];
-    constexpr int KR = 2 * DH, NC = DH / 8, NCS = DH == 64 ? 3 : 2;   // K row bytes, 16-B chunks per K row (1 << NCS)
+    constexpr int KR = 2 * DH, NC = DH / 8, NCS = DH == 128 ? 4 : DH == 64 ? 3 : 2;   // K row bytes, 16-B chunks per K row (1 << NCS)
     const int vpitch = kchunk * 2 + 8;
     char* Ks = smem;                                      // [HPB][kchunk][KR]
     char* Vs = smem + (size_t)HPB * kchunk * KR;          // [HPB][DH][vpitch]
-    char* Os = Vs + (size_t)HPB * DH * vpitch + wave * (32 * KR);
+    // the O staging: behind V^T, or at DH = 128 (4 x 8 KiB) over the K / V^T area once every wave is done with it (the barrier behind the key loop): 65 KiB per
+    // block at kchunk = 128 instead of 97 (launch_attn_wide)
+    char* Os = (DH == 128 ? smem : Vs + (size_t)HPB * DH * vpitch) + wave * (32 * KR);
     const int hs = wave % HPB;
     const int head = hb * HPB + hs;
     const bool active = head < heads && q0 < nq;          // inactive waves still stage and meet every barrier
@@ -598,6 +604,7 @@ __device__ __forceinline__ void attn_lds_body(const uint16_t* __restrict__ q, co
             attn_step64<true>(st, qf, Kh, kfull, nkc - kfull, c, hf, vfrag, bl, kc0 + kfull);
         }
     }
+    if constexpr (DH == 128) __syncthreads();             // block-uniform: every wave of a block that got here meets it, active or not
     if (!active) return;
     attn_store_tile<DH, WIN>(st, Os, ctx, off, q0, nq, H, head, lane);
 }
@@ -620,6 +627,26 @@ __global__ __launch_bounds__(256, attn_lds_blocks<DH>()) void k_attn_lds(const u
         else attn_lds_body<DH, HPB, 1>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     } else {
         attn_lds_body<DH, HPB, 0>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
+    }
+}
+
+// 128-wide heads (Qwen3 handles): the register-staged body under a name of its own — four O^T accumulators and eight Q fragments per lane do not fit the 168
+// registers k_attn_lds is held to.  ONE block per CU by registers: held to 256 VGPRs + AGPRs (__launch_bounds__(256, 2)) hipcc spills 10 vector registers
+// in the plain and 31 - 37 in the window / causal instantiations (44 - 88 B of scratch per lane: reloads are VMEM operations inside the key loop), so the bound
+// is (256, 1) and the compiler takes 256 VGPRs + 152 - 156 AGPRs.  The LDS side is ready for two (<= 68 KiB per block, launch_attn_wide); getting the
+// registers under 256 without spills is the follow-up.  Plain and window / causal modes; every sequence length (the chunked key loop
+// serves any S, as for DeBERTa handles).
+template <int HPB, bool WIN = false>
+__global__ __launch_bounds__(256, attn_lds_blocks<128>()) void k_attn_wide(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ vT, int64_t ldv,
+                                                   const int* __restrict__ seq_off, const int* __restrict__ seq_nk, const int* __restrict__ seq_nq,
+                                                   int H, int heads, int kchunk, uint16_t* __restrict__ ctx, int ldk, int kv_mul, AttnBiasArg<false, WIN> ba) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if constexpr (WIN) {
+        const int b = blockIdx.y;
+        if (attn_bias_gathers(ba, seq_off[b], seq_nk[b])) attn_lds_body<128, HPB, 5>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
+        else attn_lds_body<128, HPB, 3>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
+    } else {
+        attn_lds_body<128, HPB, 0>(q, k, vT, ldv, seq_off, seq_nk, seq_nq, H, heads, kchunk, ctx, ldk, kv_mul, ba, smem);
     }
 }
 
@@ -828,7 +855,8 @@ __global__ __launch_bounds__(ADMA_THREADS, 512 / ADMA_THREADS) void k_attn_dma(c
 // host side: the launchers (the library's forward and tests/capi/attn_probe.hip launch through them)
 // ---------------------------------------------------------------------------------------------------------
 // The operands of one layer's attention as they lie in the workspace: q / ctx [capT, H], k [capT + 64, kv_dim], vT [kv_dim, ldv], the sequence tables of the
-// nseq sequences (offsets: multiples of 4 tokens for k_attn_lds, of 8 for k_attn_dma)
+// nseq sequences (offsets: multiples of 4 tokens for k_attn_lds, of 8 for k_attn_dma).  H is the row pitch of q and ctx, heads * DH: the hidden size unless the
+// handle has a head width of its own (config.head_dim)
 struct AttnOperands {
     const uint16_t *q, *k, *vT; int64_t ldv;
     const int *seq_off, *seq_nk, *seq_nq;
@@ -855,6 +883,24 @@ static int launch_attn_lds(const AttnOperands& o, int cap, int nqt, const BA& ba
                        o.seq_nq, o.H, o.heads, kchunk, o.ctx, o.kv_dim, attn_kv_mul(o.H / o.kv_dim), ba);
     return 0;
 }
+// the register-staged kernel at DH = 128.  K kchunk x 256 B + V^T 128 x (2 kchunk + 8) B per head; the O staging (32 KiB) re-uses that area: 65 KiB at
+// kchunk = 128 (HPB = 1), 67 KiB at 64 (HPB = 2), 68 KiB at 32 (HPB = 4)
+constexpr int attn_wide_lds(int hpb, int kchunk) {
+    const int kv = hpb * (kchunk * 256 + 128 * (kchunk * 2 + 8)), os = 4 * 32 * 256;
+    return kv > os ? kv : os;
+}
+template <int HPB, class BA>
+static int launch_attn_wide(const AttnOperands& o, int cap, int nqt, const BA& ba, int device, hipStream_t st) {
+    static_assert(!attn_is_bias<BA> && !attn_is_disent<BA>, "128-wide heads: plain and window / causal attention only");
+    const int kchunk = cap < 128 ? cap : 128;
+    const int lds = attn_wide_lds(HPB, kchunk);
+    const auto kern = &k_attn_wide<HPB, attn_is_win<BA>>;
+    KR_TRY(set_lds_once(reinterpret_cast<const void*>(kern), lds, device));
+    const int qgroups = (nqt + (4 / HPB) - 1) / (4 / HPB);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((o.heads + HPB - 1) / HPB), (unsigned)o.nseq, (unsigned)qgroups), dim3(256), lds, st, o.q, o.k, o.vT, o.ldv, o.seq_off, o.seq_nk,
+                       o.seq_nq, o.H, o.heads, kchunk, o.ctx, o.kv_dim, attn_kv_mul(o.H / o.kv_dim), ba);
+    return 0;
+}
 // the LDS-DMA ring (not built with the disentangled terms)
 template <int DH, class BA>
 static int launch_attn_dma(const AttnOperands& o, int nqt, const BA& ba, hipStream_t st) {
@@ -869,10 +915,16 @@ static int launch_attn_dma(const AttnOperands& o, int nqt, const BA& ba, hipStre
 // (the disentangled terms are built into the register-staged kernel only: a DeBERTa forward never asks for the ring)
 template <int DH, class BA>
 static int launch_attention(const AttnOperands& o, int cap, int nqt, bool long_seq, const BA& ba, int device, hipStream_t st) {
+    if constexpr (DH == 128) {
+        // every length through k_attn_wide (long_seq is never set for such a handle); the bias-table and disentangled modes stay 32 / 64 only
+        if constexpr (attn_is_bias<BA> || attn_is_disent<BA>) return fail(KR_ESTATE, "128-wide heads run plain and window / causal attention only");
+        else return nqt >= 3 ? launch_attn_wide<1>(o, cap, nqt, ba, device, st) : nqt == 2 ? launch_attn_wide<2>(o, cap, nqt, ba, device, st) : launch_attn_wide<4>(o, cap, nqt, ba, device, st);
+    } else {
     if constexpr (!attn_is_disent<BA>) { if (long_seq) return launch_attn_dma<DH>(o, nqt, ba, st); }
     if (nqt >= 3) return launch_attn_lds<DH, 1>(o, cap, nqt, ba, device, st);
     if (nqt == 2) return launch_attn_lds<DH, 2>(o, cap, nqt, ba, device, st);
     return launch_attn_lds<DH, 4>(o, cap, nqt, ba, device, st);
+    }
 }
 
 }  // namespace KR_ENC_NS

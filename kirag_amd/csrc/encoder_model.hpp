@@ -46,6 +46,10 @@ inline Error err(int code, const char* fmt, ...) {
 //   (Qwen2), and with the setting's value 1 a causal mask: key column <= query column (AM_CAUSAL).  Grouped-query attention is native: k_proj / v_proj (and their biases) come as
 //   [A, H] (/ [A]), A = kv_heads d_h with kv_heads dividing heads and A % 64 == 0 (kv_dim_ok), or expanded to [H, H]; A is read off the element count, k and v
 //   of every layer must agree (describe()), and query head h reads KV head h / (heads / kv_heads).
+//   Qwen3 (config.head_dim + layers.N.self_attn.{q,k}_norm.weight): the head width d_h is a setting of its own, 32 / 64 / 128, and need not be hidden / heads:
+//   q and the context are Dq = heads d_h wide (q_proj [Dq, H], o_proj [H, Dq]), k / V^T A = kv_heads d_h <= Dq.  With the two norm vectors [d_h] of every
+//   layer, q and k leave the projection unrotated (QKV_SPLIT) and k_qk_norm_rope applies the RMS norm over each head and then the rotation (encoder_rows.hpp);
+//   d_h = 128 exists with the norms only and runs k_attn_wide at every length.
 //   ROTARY_BERT (config.rotary_feed_forward = 1, needs config.rotary_inv_freq; JinaEmbeddingsV3Model): NOMIC's post-LN stack and rotary q / k under NOMIC's
 //   projection names, with BERT's feed-forward fc2(gelu(fc1 x + b1)) + b2 in place of SwiGLU (mlp.fc1 in PLAIN row order) and optional biases on q / k / v
 //   (the decoders' rows: q's and k's in the packed rows' order, added before the rotation) and o.
@@ -57,6 +61,7 @@ inline const char* family_name(Family f) { static const char* const n[] = {"unkn
 // tensor slots: 0..4 embeddings, then L_COUNT per layer (L_UW: the second half of a gated intermediate projection); below zero what is no slot of `got`
 enum { T_WORD = 0, T_POS, T_TYPE, T_ELNG, T_ELNB, T_LAYER0 };
 enum { T_IGNORED = -1, T_RELBIAS = -2, T_WQKV = -3, T_WI = -4, T_WIB = -5, T_WQKVB = -6 };   // ModernBert's fused tensors of one layer: attn.Wqkv.{weight,bias}, mlp.Wi.{weight,bias}
+enum { T_QNORM = -10, T_KNORM = -11 };                      // a Qwen3 layer's self_attn.q_norm.weight / k_norm.weight [d_h] (no slot of `got`: Loaded::qk_norm)
 enum { T_RELEMB = -7, T_RELLNG = -8, T_RELLNB = -9 };      // DeBERTa's position table encoder.rel_embeddings.weight [2 Bk, H] and the norm over its rows, encoder.LayerNorm.{weight,bias}
 constexpr int DEB_MAX_BUCKETS = 256;   // position_buckets of every v3 checkpoint, and the most a handle takes: 512 table rows
 enum { L_QW = 0, L_QB, L_KW, L_KB, L_VW, L_VB, L_OW, L_OB, L_LN1G, L_LN1B, L_IW, L_IB, L_FW, L_FB, L_LN2G, L_LN2B, L_UW, L_COUNT };
@@ -109,6 +114,7 @@ static const NameRow NAME_ROWS[] = {
     {"model.embed_tokens.weight", WHOLE, DECODER, T_WORD, XV, XH, 0}, {"norm.weight", WHOLE, DECODER, L_LN2G, XH, X1, LAST_LAYER}, {"model.norm.weight", WHOLE, DECODER, L_LN2G, XH, X1, LAST_LAYER},
     {"input_layernorm.weight", LAYER, DECODER, L_LN2G, XH, X1, NORM_BEFORE}, {"self_attn.q_proj.bias", LAYER, DECODER, L_QB, XH, X1, 0},
     {"self_attn.k_proj.bias", LAYER, DECODER, L_KB, XH, X1, 0}, {"self_attn.v_proj.bias", LAYER, DECODER, L_VB, XH, X1, 0},
+    {"self_attn.q_norm.weight", LAYER, DECODER, T_QNORM, XHALF_DH, X1, 0}, {"self_attn.k_norm.weight", LAYER, DECODER, T_KNORM, XHALF_DH, X1, 0},      // (d_h elements: check_tensor)
     {"final_norm.weight", TAIL, MODERN, L_LN2G, XH, X1, LAST_LAYER}, {"final_norm.bias", TAIL, MODERN, L_LN2B, XH, X1, LAST_LAYER},
     {"encoder.relative_attention_bias.weight", ENDS, MPNET, T_RELBIAS, XBUCKETS, XHEADS, 0},
     // DebertaV2Model: the position table (its row count is 2 Bk: check_tensor) and its norm; the attention projections into BERT's slots, every other tensor
@@ -331,9 +337,12 @@ inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_
 //   config.deberta_position_buckets = Bk (even, 2 .. 256) and config.deberta_max_relative_positions = M (M - 1 > Bk / 2): DebertaV2Config's position_buckets and
 //   max_relative_positions (max_position_embeddings where that is < 1); the two together make the handle a DeBERTa handle.
 //   config.decoder_attention: the handle is a decoder-LLM stack (needs config.rotary_inv_freq); 1 = causal attention, 0 = bidirectional on the same stack.
+//   config.head_dim: the head width d_h of a decoder handle, 32 / 64 / 128, where it is not hidden / heads (Qwen3Config.head_dim).  Sent before
+//   config.rotary_inv_freq (which then takes d_h / 2 values) and before the weights: q_proj is [heads d_h, hidden], o_proj [hidden, heads d_h], k_proj / v_proj
+//   [kv_heads d_h, hidden].  128 needs the q / k norms of every layer.  Never set: hidden / heads, and the handle is what it was without the setting.
 //   config.rotary_feed_forward: the feed-forward of a rotary post-LN handle (config.rotary_inv_freq), 0 = NomicBert's SwiGLU (also when never set),
 //   1 = fc2(gelu(fc1 x + b1)) + b2 with linear biases: a rotary BERT handle (jina-embeddings-v3).
-enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_ROTARY_FF, SET_DECODER_ATTN, SET_COUNT };
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_ROTARY_FF, SET_HEAD_DIM, SET_DECODER_ATTN, SET_COUNT };
 enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
 struct SettingRow {
     const char* name;
@@ -358,6 +367,7 @@ static const SettingRow SETTINGS[SET_COUNT] = {
     {"config.deberta_position_buckets", X1, V_INT, 2, DEB_MAX_BUCKETS, "an even integer", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 2},
     {"config.deberta_max_relative_positions", X1, V_INT, 2, 65536, "an integer M with M - 1 > position_buckets / 2", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 0},
     {"config.rotary_feed_forward", X1, V_INT, 0, 1, "0 (SwiGLU) or 1 (gelu with biases)", "NomicBert's SwiGLU", 0, 0, -1, 0},
+    {"config.head_dim", X1, V_INT, 32, 128, "32, 64 or 128", "heads of hidden / heads features", 0, -1, -1, 32},
     {"config.decoder_attention", X1, V_INT, 0, 1, "0 (bidirectional) or 1 (causal)", "not a decoder handle", 0, -1, -1, 0},
 };
 constexpr int64_t SETTING_MAX_VALUES = 4096;
@@ -380,8 +390,10 @@ inline Error set_setting(const kr_bert_cfg& cfg, Settings& set, const HeadState*
         return err(KR_EINVAL, "unknown setting '%s' (known: %s)", name, known.c_str());
     }
     const SettingRow& r = SETTINGS[si];
-    if (r.count == XANY ? (numel < 1 || numel > SETTING_MAX_VALUES) : numel != extent(cfg, r.count))
-        return r.count == XHALF_DH ? err(KR_EINVAL, "%s takes d_h / 2 = %lld values, got %lld", name, (long long)extent(cfg, r.count), (long long)numel)
+    // (the rotary frequencies of a handle with config.head_dim: half of THAT width)
+    const int64_t count = r.count == XHALF_DH && set.has(SET_HEAD_DIM) ? set.value(SET_HEAD_DIM) / 2 : extent(cfg, r.count);
+    if (r.count == XANY ? (numel < 1 || numel > SETTING_MAX_VALUES) : numel != count)
+        return r.count == XHALF_DH ? err(KR_EINVAL, "%s takes d_h / 2 = %lld values, got %lld", name, (long long)count, (long long)numel)
              : r.count == X1 ? err(KR_EINVAL, "'%s' takes one value, got %lld", name, (long long)numel) : err(KR_EINVAL, "'%s': %lld values", name, (long long)numel);
     if (r.max_pos_limit && cfg.max_pos > r.max_pos_limit)
         return err(KR_EINVAL, "%s: max_position_embeddings = %d, rotary tables are built for at most %d", name, cfg.max_pos, r.max_pos_limit);
@@ -389,6 +401,7 @@ inline Error set_setting(const kr_bert_cfg& cfg, Settings& set, const HeadState*
     for (int64_t i = 0; i < numel; ++i) {
         const float x = vals[i];
         if (r.rule != V_INT && !std::isfinite(x)) return err(KR_EINVAL, "'%s' holds a non-finite value", name);
+        if (si == SET_HEAD_DIM && x == 96.f) return err(KR_EINVAL, "%s = 96: expected %s", name, r.expects);
         if (r.rule == V_INT && (!(x >= (float)r.lo && x <= (float)hi) || x != (float)(int)x || (r.step > 1 && (int)x % r.step != 0))) return err(KR_EINVAL, "%s = %g: expected %s (%d .. %d)", name, (double)x, r.expects, r.lo, hi);
     }
     const std::vector<float> v(vals, vals + numel);
@@ -442,8 +455,18 @@ struct Loaded {
     int rel_rows = 0, rel_rows_seen = 0;   // rows of DeBERTa's position table as loaded (0: never); of the tensor check_tensor saw last (mark_loaded takes it over)
     bool rel_ln[2] = {false, false};       // encoder.LayerNorm.weight / .bias were loaded
     HeadState heads[HEAD_ALL];
-    explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0), kv((size_t)layers * 4, 0) {}
+    std::vector<uint8_t> qk_norm;          // per layer: self_attn.q_norm.weight, self_attn.k_norm.weight were loaded
+    int q_rows = 0, o_cols = 0;            // rows of the last q_proj.weight / columns of the last o_proj.weight loaded under the shared names (0: never), with
+    int q_rows_seen = 0, o_cols_seen = 0;  // ... those of the tensor check_tensor saw last (mark_loaded takes them over)
+    explicit Loaded(int layers = 0) : got(T_LAYER0 + (size_t)layers * L_COUNT, 0), kv((size_t)layers * 4, 0), qk_norm((size_t)layers * 2, 0) {}
+    bool any_qk_norm() const { for (uint8_t x : qk_norm) if (x) return true; return false; }
 };
+// the q / o projections under the names a decoder handle shares with NomicBert: 0 = q_proj.weight, 1 = o_proj.weight, 2 = q_proj.bias (-1: none).  Their
+// width is Dq = heads d_h, hidden unless the handle has config.head_dim
+inline int qo_index(const Resolved& r) {
+    if (r.slot < T_LAYER0 || (r.fam != NOMIC && r.fam != DECODER)) return -1;
+    switch ((r.slot - T_LAYER0) % L_COUNT) { case L_QW: return 0; case L_OW: return 1; case L_QB: return 2; default: return -1; }
+}
 // The k / v projections under the names a decoder handle shares with NomicBert (self_attn.{k,v}_proj.weight) and their biases: which of the four a resolved
 // tensor is (-1: none).  They alone come in a grouped-query form.
 inline int kv_index(const Resolved& r) {
@@ -452,16 +475,34 @@ inline int kv_index(const Resolved& r) {
 }
 // A = kv_heads d_h rows: whole KV heads, their number a divisor of the query heads, and whole 64-column wave slices of the QKV epilogue (no wave straddles
 // q | k | v); A = H is the plain (or expanded) form
-inline bool kv_dim_ok(const kr_bert_cfg& c, int64_t A) {
-    const int64_t dh = c.hidden / c.heads;
-    return A > 0 && A <= c.hidden && A % dh == 0 && c.heads % (A / dh) == 0 && A % 64 == 0;
+// (head_dim: the value of config.head_dim, 0 = never set: d_h = hidden / heads; A <= Dq = heads d_h)
+inline bool kv_dim_ok(const kr_bert_cfg& c, int64_t A, int head_dim = 0) {
+    const int64_t dh = head_dim ? head_dim : c.hidden / c.heads;
+    return A > 0 && A <= c.heads * dh && A % dh == 0 && c.heads % (A / dh) == 0 && A % 64 == 0;
 }
 // A resolved tensor arriving with `numel` elements: its count.  The bias table [32, heads] (MPNet's name or T5's) has the rule of the heads: before the first
 // finalize it makes the handle an MPNet handle (a T5 handle needs it); afterwards a handle that has it takes new values (the weight sync reloads every
 // parameter) and a handle finalized without it refuses it.
 // DeBERTa's position table [2 Bk, H] and its norm have the same rule; the table's row count is fixed with it (describe() holds it against the setting).
-inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolved& r, int64_t numel, Loaded& ld, bool finalized_once) {
+// head_dim: the value of config.head_dim (0: never set).  With it the q / o projections are held against Dq = heads d_h, k / v against whole heads of d_h.
+inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolved& r, int64_t numel, Loaded& ld, bool finalized_once, int head_dim = 0) {
     if (r.slot == T_IGNORED) return Error{};
+    const int64_t dh = head_dim ? head_dim : cfg.hidden / cfg.heads, Dq = cfg.heads * dh;
+    if (r.slot == T_QNORM || r.slot == T_KNORM) {
+        if (numel != dh) return err(KR_EINVAL, "tensor '%s' has %lld elements, expected head_dim = %lld", name, (long long)numel, (long long)dh);
+        if (finalized_once && !ld.any_qk_norm())
+            return err(KR_EINVAL, "'%s' after kr_encoder_finalize: the handle was finalized without q / k norms and stays what it is", name);
+        return Error{};
+    }
+    if (const int qi = qo_index(r); qi >= 0 && head_dim) {
+        const int64_t want = qi == 2 ? Dq : Dq * cfg.hidden;
+        if (numel != want)
+            return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld (config.head_dim = %d: %d heads x %d = %lld %s)", name, (long long)numel, (long long)want, head_dim,
+                       cfg.heads, head_dim, (long long)Dq, qi == 1 ? "columns" : "rows");
+        if (qi == 0) ld.q_rows_seen = (int)Dq; else if (qi == 1) ld.o_cols_seen = (int)Dq;
+        return Error{};
+    }
+    if (const int qi = qo_index(r); qi == 0) ld.q_rows_seen = cfg.hidden; else if (qi == 1) ld.o_cols_seen = cfg.hidden;
     if (r.slot == T_RELEMB) {
         const int64_t rows = numel / cfg.hidden;
         if (numel <= 0 || numel % cfg.hidden != 0 || rows % 2 != 0 || rows < 4 || rows > 2 * DEB_MAX_BUCKETS)
@@ -486,9 +527,9 @@ inline Error check_tensor(const kr_bert_cfg& cfg, const char* name, const Resolv
         // [A, H] / [A]: every valid A is taken here; whether the handle is one that takes A < H, and whether its tensors agree, is describe()'s business.
         // After the first finalize A is what the handle has (all four kinds and all layers agree by then)
         const int64_t cols = kvi < 2 ? cfg.hidden : 1, A = numel / cols;
-        if (numel % cols != 0 || !kv_dim_ok(cfg, A))
+        if (numel % cols != 0 || !kv_dim_ok(cfg, A, head_dim))
             return err(KR_EINVAL, "tensor '%s' has %lld elements, expected %lld, or the grouped-query form %s with A = kv_heads * %d, kv_heads a divisor of %d and A %% 64 == 0", name,
-                       (long long)numel, (long long)r.numel, kvi < 2 ? "[A, hidden]" : "[A]", cfg.hidden / cfg.heads, cfg.heads);
+                       (long long)numel, (long long)(head_dim ? Dq * cols : r.numel), kvi < 2 ? "[A, hidden]" : "[A]", (int)dh, cfg.heads);
         if (finalized_once && ld.kv[0] && A != ld.kv[0])
             return err(KR_EINVAL, "'%s' with A = %lld rows after kr_encoder_finalize: the k / v width of the handle is fixed (it has A = %d)", name, (long long)A, ld.kv[0]);
         ld.kv_seen = (int)A;
@@ -504,6 +545,7 @@ inline void mark_loaded(Loaded& ld, const Resolved& r) {
     const uint8_t tag = (uint8_t)(r.fam | (r.gated ? GATED_NAME : 0));
     uint8_t* g = r.layer >= 0 ? &ld.got[T_LAYER0 + (size_t)r.layer * L_COUNT] : nullptr;
     if (r.slot == T_RELBIAS) ld.rel_fam = r.fam;
+    else if (r.slot == T_QNORM || r.slot == T_KNORM) ld.qk_norm[(size_t)r.layer * 2 + (r.slot == T_KNORM)] = 1;
     else if (r.slot == T_RELEMB) ld.rel_rows = ld.rel_rows_seen;
     else if (r.slot == T_RELLNG || r.slot == T_RELLNB) ld.rel_ln[r.slot == T_RELLNB] = true;
     else if (r.slot == T_WQKV) g[L_QW] = g[L_KW] = g[L_VW] = tag;
@@ -511,6 +553,7 @@ inline void mark_loaded(Loaded& ld, const Resolved& r) {
     else if (r.slot == T_WI) g[L_IW] = g[L_UW] = tag;
     else if (r.slot == T_WIB) g[L_IB] = tag;
     else if (r.slot >= 0) ld.got[r.slot] = tag;
+    if (const int qi = qo_index(r); qi == 0) ld.q_rows = ld.q_rows_seen; else if (qi == 1) ld.o_cols = ld.o_cols_seen;
     if (const int kvi = kv_index(r); kvi >= 0) {
         // k's rows start at H and v's behind k's A rows of the packed matrix: a matrix that comes back with another A has overwritten, or moved away from,
         // its partner, which therefore counts as never loaded
@@ -537,7 +580,7 @@ static const FamilyRow FAMILIES[] = {
 };
 
 enum PosSource : uint8_t { POS_COLUMN, POS_FAIRSEQ, POS_ROTARY, POS_BIAS_ONLY, POS_DISENT };   // the embedding's position row: by column, by fairseq's rule, none (a zero row; q / k rotated), none (T5: no table), none (DeBERTa: a zero row)
-enum QkvKind : uint8_t { QKV_PLAIN, QKV_ROT, QKV_ROT_BIAS };                       // EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB (a ModernBert layer with attn.Wqkv.bias)
+enum QkvKind : uint8_t { QKV_PLAIN, QKV_ROT, QKV_ROT_BIAS, QKV_SPLIT };            // EPI_QKV, EPI_QKV_ROT, EPI_QKV_ROTB (a ModernBert layer with attn.Wqkv.bias), EPI_QKV_SPLIT (q / k norms: rotated behind them)
 enum AttnMode : uint8_t { AM_PLAIN = 0, AM_BIAS = 1, AM_WIN = 2, AM_DISENT = 3, AM_CAUSAL = 4 };  // plain, with the relative attention bias, under the sliding window (and the local rotary table), DeBERTa's disentangled position terms, key column <= query column (the window's kernels with a one-sided window)
 enum FfKind : uint8_t { FF_GELU, FF_SWIGLU, FF_GEGLU, FF_RELU, FF_GEGLU_TANH };    // EPI_GELU, EPI_SWIGLU, EPI_GEGLU, EPI_RELU, EPI_GEGLU_TANH
 struct LayerPlan { QkvKind qkv; AttnMode attn; };
@@ -558,6 +601,8 @@ struct ModelPlan {
     int classifier = -1;                   // the head KR_POOL_CLASSIFY runs (HEAD_CLS / HEAD_MODERN_CLS / HEAD_SCORE), -1: none
     bool classify_mean = false;            // ... on the masked mean (config.classifier_pooling = 1)
     int kv_dim = 0;                        // A: columns of k and rows of V^T (hidden, or kv_heads d_h of a grouped-query decoder handle)
+    int head_w = 0, q_dim = 0;             // d_h and Dq = heads d_h, the width of q and of the context: hidden / heads and hidden unless config.head_dim says otherwise
+    bool qk_norm = false;                  // every layer has self_attn.{q,k}_norm.weight: QKV_SPLIT, then k_qk_norm_rope
     int out_dim = 0, out_width = 0;        // columns of a pooled row; of the widest row `out` must hold, whatever the pool
     unsigned ws = 0;                       // WS_*
 };
@@ -580,6 +625,34 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     const bool deb = set.has(SET_DEB_BUCKETS) || set.has(SET_DEB_MAX_REL), dec = set.has(SET_DECODER_ATTN);
     const int pad_idx = set.value(SET_PAD_IDX), t5_ff = set.value(SET_T5_FF), Bk = set.value(SET_DEB_BUCKETS, 0), max_rel = set.value(SET_DEB_MAX_REL, 0);
     const bool rbert = set.value(SET_ROTARY_FF, 0) == 1;
+    const int head_w = set.value(SET_HEAD_DIM, cfg.hidden / cfg.heads), q_dim = cfg.heads * head_w;
+    const bool qk_norm = ld.any_qk_norm();
+    if (set.has(SET_HEAD_DIM) && !dec)
+        return err(KR_EINVAL, "config.head_dim on a handle without config.decoder_attention: a head width of its own is accepted on decoder handles only");
+    if (qk_norm && !dec)
+        return err(KR_EINVAL, "'layers.N.self_attn.{q,k}_norm.weight' on a handle without config.decoder_attention: the q / k norms are accepted on decoder handles only");
+    if (set.has(SET_HEAD_DIM)) {
+        if (q_dim % 128 != 0 || q_dim > 4096)
+            return err(KR_EINVAL, "config.head_dim = %d with %d heads: heads * head_dim = %d must be a multiple of 128 up to 4096", head_w, cfg.heads, q_dim);
+        if (rot && (int)set.v[SET_ROTARY].size() != head_w / 2)
+            return err(KR_EINVAL, "config.rotary_inv_freq holds %zu values, config.head_dim = %d needs %d: load config.head_dim first", set.v[SET_ROTARY].size(), head_w, head_w / 2);
+        if (ld.q_rows && ld.q_rows != q_dim)
+            return err(KR_EINVAL, "'layers.N.self_attn.q_proj.weight' has %d rows, config.head_dim = %d needs %d: load config.head_dim before the weights", ld.q_rows, head_w, q_dim);
+        if (ld.o_cols && ld.o_cols != q_dim)
+            return err(KR_EINVAL, "'layers.N.self_attn.o_proj.weight' has %d columns, config.head_dim = %d needs %d: load config.head_dim before the weights", ld.o_cols, head_w, q_dim);
+    }
+    if (qk_norm)
+        for (int li = 0; li < cfg.layers; ++li) {
+            for (int x = 0; x < 2; ++x)
+                if (!ld.qk_norm[(size_t)li * 2 + x])
+                    return err(KR_ESTATE, "'layers.%d.self_attn.%s_norm.weight' was never loaded: a handle takes the q / k norms of every layer or none", li, x ? "k" : "q");
+            for (const int id : {L_QB, L_KB})
+                if (ld.got[T_LAYER0 + (size_t)li * L_COUNT + id])
+                    return err(KR_EINVAL, "'%s' next to the q / k norms: a handle with self_attn.{q,k}_norm.weight has no q / k bias",
+                               slot_tensor_name(T_LAYER0 + (size_t)li * L_COUNT + id, DECODER).c_str());
+        }
+    if (head_w == 128 && !qk_norm)
+        return err(KR_EINVAL, "config.head_dim = 128 without layers.N.self_attn.{q,k}_norm.weight: 128-wide heads run with the q / k norms only (Qwen3)");
     const Family fam = dec ? DECODER : deb ? DEBERTA : t5 ? T5 : modern ? MODERN : rbert ? ROTARY_BERT : rot ? NOMIC : rel ? MPNET : BERT;
     const std::vector<float>& flags = set.v[SET_LOCAL_LAYERS];
     if (rbert) {
@@ -625,7 +698,7 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
                        slot_tensor_name(i, ROTARY_BERT).c_str());
     // the k / v width A: one per handle — k and v of a layer agree, the layers agree, the biases agree with the matrices; A < H on decoder handles only (the
     // attention kernels of every other family read K / V^T of head h, not of head h / group)
-    int kv_dim = cfg.hidden;
+    int kv_dim = q_dim;
     {
         static const int ids[4] = {L_KW, L_VW, L_KB, L_VB};
         int first_l = -1, first_k = 0;
@@ -635,6 +708,8 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
                 const int A = ld.kv[(size_t)li * 4 + x];
                 if (!ld.got[slot] || !A) continue;
                 const std::string nm = slot_tensor_name(slot, fam_of(ld.got[slot]));
+                if (dec && !kv_dim_ok(cfg, A, set.value(SET_HEAD_DIM, 0)))
+                    return err(KR_EINVAL, "'%s' with A = %d rows: expected A = kv_heads * %d, kv_heads a divisor of %d, A %% 64 == 0 and A <= %d", nm.c_str(), A, head_w, cfg.heads, q_dim);
                 if (!dec && A != cfg.hidden)
                     return err(KR_EINVAL, "'%s' with A = %d rows on a handle without config.decoder_attention: grouped-query k / v projections are accepted on decoder handles only "
                                           "(load the setting before kr_encoder_finalize, or expand the tensor to %d rows)", nm.c_str(), A, cfg.hidden);
@@ -769,13 +844,13 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
     plan.deb_buckets = Bk; plan.deb_max_rel = max_rel; plan.deb_norm = deb && ld.rel_ln[0]; plan.cls_gelu = deb;
     plan.pad_idx = pad_idx; plan.half_window = set.value(SET_HALF_WINDOW, 0);
     for (int li = 0; li < cfg.layers; ++li)
-        plan.layers.push_back({!rot ? QKV_PLAIN : (modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB]) ||
+        plan.layers.push_back({!rot ? QKV_PLAIN : qk_norm ? QKV_SPLIT : (modern && ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB]) ||
                                                     ((dec || rbert) && (ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_QB] || ld.got[T_LAYER0 + (size_t)li * L_COUNT + L_KB])) ? QKV_ROT_BIAS : QKV_ROT,
                                dec ? (set.value(SET_DECODER_ATTN) == 1 ? AM_CAUSAL : AM_PLAIN) : deb ? AM_DISENT : rel ? AM_BIAS : modern && flags[li] != 0.f ? AM_WIN : AM_PLAIN});
     plan.ff = t5 ? (t5_ff ? FF_GEGLU_TANH : FF_RELU) : modern ? FF_GEGLU : rot && !rbert ? FF_SWIGLU : FF_GELU;
     plan.ff_gated = plan.ff == FF_GEGLU_TANH || plan.ff == FF_GEGLU || plan.ff == FF_SWIGLU;
     plan.out_dim = cfg.hidden;
-    plan.kv_dim = kv_dim;
+    plan.kv_dim = kv_dim; plan.head_w = head_w; plan.q_dim = q_dim; plan.qk_norm = qk_norm;
     for (int h = 0; h < HEAD_ALL; ++h) {
         plan.head[h] = ld.heads[h].got != 0;
         plan.head_dim[h] = ld.heads[h].dim;

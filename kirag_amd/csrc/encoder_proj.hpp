@@ -29,8 +29,8 @@ __device__ __forceinline__ void gemm_main(const uint16_t* __restrict__ A, int64_
 // projections: C[token, feature] = X[token, :] . W[feature, :]   (rows = tokens, cols = output features)
 // ---------------------------------------------------------------------------------------------------------
 struct ProjArgs {
-    const uint16_t* W; const uint16_t* X; const int* Tp; int F; int K; int H;
-    int A;   // the rotating QKV epilogues: columns of k and rows of V^T (F = H + 2A; A = H unless k / v are a grouped-query decoder's, A % 64 == 0)
+    const uint16_t* W; const uint16_t* X; const int* Tp; int F; int K; int H;   // H: the QKV epilogues' width of q (hidden unless the handle has a head width of its own)
+    int A;   // the rotating QKV epilogues and EPI_QKV_SPLIT: columns of k and rows of V^T (F = H + 2A; A = H unless k / v are a grouped-query decoder's, A % 64 == 0)
     const float* bias;
     uint16_t* out0; uint16_t* out1; uint16_t* outT; int64_t ldT;   // QKV: q [T,H], k [T,A] row-major; vT [A, ldT].  Others: out0 [T, F]
     int64_t ldx, ldo;   // row pitch (elements) of X and of out0 (EPI_DENSE / EPI_GELU); 0 = K / F
@@ -45,8 +45,9 @@ struct ProjArgs {
     const int* row_seq; unsigned int* smax; int V;
 };
 
-enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6, EPI_RELU = 7, EPI_GEGLU_TANH = 8, EPI_SPLADE = 9 };
+enum { EPI_QKV = 0, EPI_DENSE = 1, EPI_GELU = 2, EPI_QKV_ROT = 3, EPI_SWIGLU = 4, EPI_GEGLU = 5, EPI_QKV_ROTB = 6, EPI_RELU = 7, EPI_GEGLU_TANH = 8, EPI_SPLADE = 9, EPI_QKV_SPLIT = 10 };
 constexpr bool epi_rotates(int epi) { return epi == EPI_QKV_ROT || epi == EPI_QKV_ROTB; }
+constexpr bool epi_splits(int epi) { return epi_rotates(epi) || epi == EPI_QKV_SPLIT; }   // F = H + 2A: q | k [T, A] | V^T [A, ldT]
 constexpr bool epi_gated(int epi) { return epi == EPI_SWIGLU || epi == EPI_GEGLU || epi == EPI_GEGLU_TANH; }   // F = 2 FF GEMM columns -> FF stored
 
 // The two epilogues of NomicBert handles combine feature pairs: a rotary pair (j, j + d_h / 2) of q or k, or gate and up of one intermediate feature.  The
@@ -339,6 +340,8 @@ __device__ __forceinline__ void splade_reduce(const ProjArgs& a, AccTile<Shape>&
 //              Wqkv x + b (ModernBert handles that were given attn.Wqkv.bias)
 //   EPI_QKV_ROT: EPI_QKV without a bias, q and k rotated by the token's column before they are rounded (NomicBert handles; V^T as in EPI_QKV).  Both rotating
 //              epilogues take F = H + 2A: [0,H) -> q, [H,H+A) -> k [T,A], [H+A,F) -> V^T [A,ldT] (A < H: a grouped-query decoder handle, one k / V^T per KV head)
+//   EPI_QKV_SPLIT: the same three regions of F = H + 2A with nothing done to them: no bias, no rotation (handles with q / k norms: k_qk_norm_rope normalises and
+//              rotates q and k in place behind this launch)
 //   EPI_SWIGLU:  F = 2 FF, gate | up interleaved per tile: out0[T, F / 2] = silu(gate) * up, no bias (NomicBert handles)
 //   EPI_GEGLU:   F = 2 FF, input | gate interleaved the same way: out0[T, F / 2] = erf_gelu(input + b) * (gate + b') (ModernBert handles; bias in the rows' order)
 //   EPI_RELU:    out0[T,F] = max(acc, 0), no bias (T5 v1.0 handles: DenseReluDense.wi)
@@ -368,6 +371,10 @@ __device__ __forceinline__ void proj_epilogue(const ProjArgs& a, AccTile<ShapeE>
             store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, a.H, t0, f0 - region * a.H,
                                     [&](f32x4 v, int mi, int ni, int g) { return v + b[ni][g]; });
         }
+    } else if constexpr (EPI == EPI_QKV_SPLIT) {
+        const int region = f0 < a.H ? 0 : f0 < a.H + a.A ? 1 : 2;
+        if (region == 2) store_transposed_bf16<ShapeE, NT>(acc, stage, a.outT, a.ldT, t0, f0 - a.H - a.A);
+        else store_rows_bf16<ShapeE, NT>(acc, stage, region ? a.out1 : a.out0, region ? a.A : a.H, t0, f0 - region * a.H, [&](f32x4 v, int, int, int) { return v; });
     } else if constexpr (epi_rotates(EPI)) {
         // F = H + 2A: q below H, k below H + A (stored with pitch A), V^T behind; H % 64 == 0 and A % 64 == 0, so a wave's columns never straddle them
         const int region = f0 < a.H ? 0 : f0 < a.H + a.A ? 1 : 2;
@@ -525,9 +532,9 @@ __global__ __launch_bounds__((WM * WN + 4) * 64) void k_proj_skinny(ProjArgs a) 
         for (int g = 0; g < 4; ++g) {
             f32x4 v = {acc.v[0][0][4 * g], acc.v[0][0][4 * g + 1], acc.v[0][0][4 * g + 2], acc.v[0][0][4 * g + 3]};
             const int f = (int)f0 + 8 * g + 4 * h;        // first of the lane's 4 consecutive features
-            if constexpr (EPI == EPI_QKV || epi_rotates(EPI)) {
-                // EPI_QKV: thirds of 3H.  The rotating epilogues: q below H, k below H + A with pitch A, V^T behind (proj_epilogue)
-                const int kv = epi_rotates(EPI) ? a.A : a.H;
+            if constexpr (EPI == EPI_QKV || epi_splits(EPI)) {
+                // EPI_QKV: thirds of 3H.  The rotating epilogues and EPI_QKV_SPLIT: q below H, k below H + A with pitch A, V^T behind (proj_epilogue)
+                const int kv = epi_splits(EPI) ? a.A : a.H;
                 const int region = (int)f0 < a.H ? 0 : (int)f0 < a.H + kv ? 1 : 2;
                 if (region == 2) {                        // V^T [feature, token]; its bias lives in bo_eff
 #pragma unroll
@@ -569,6 +576,7 @@ static int with_epilogue(int epi, F&& f) {
         case EPI_RELU: return f(std::integral_constant<int, EPI_RELU>{});
         case EPI_GEGLU_TANH: return f(std::integral_constant<int, EPI_GEGLU_TANH>{});
         case EPI_SPLADE: return f(std::integral_constant<int, EPI_SPLADE>{});
+        case EPI_QKV_SPLIT: return f(std::integral_constant<int, EPI_QKV_SPLIT>{});
         default: return fail(KR_EINVAL, "projection epilogue %d is not built into this library", epi);
     }
 }

@@ -54,11 +54,12 @@ __global__ void k_scale_copy(const float* __restrict__ src, float* __restrict__ 
 }
 
 // b_o' = b_o + W_o . b_v : softmax rows sum to 1, so P (X W_v^T + b_v) = P X W_v^T + b_v and the value bias moves into the output projection
-__global__ void k_fold_vbias(const uint16_t* __restrict__ wo, const float* __restrict__ bo, const float* __restrict__ bv, float* __restrict__ out, int H) {
+// (wo [H, K], bv [K]: K = the width of the context, H unless the handle has a head width of its own)
+__global__ void k_fold_vbias(const uint16_t* __restrict__ wo, const float* __restrict__ bo, const float* __restrict__ bv, float* __restrict__ out, int H, int K) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H) return;
     float s = 0.f;
-    for (int j = 0; j < H; ++j) s += ET::to_f32(wo[(int64_t)i * H + j]) * bv[j];
+    for (int j = 0; j < K; ++j) s += ET::to_f32(wo[(int64_t)i * K + j]) * bv[j];
     out[i] = bo[i] + s;
 }
 
@@ -200,6 +201,56 @@ __global__ __launch_bounds__(64) void k_rot_pos(const int* __restrict__ seq_off,
     const int first = min(tok_pos[o], tok_pos[o + n - 1]);
     const int padded = (n + align - 1) & ~(align - 1);
     for (int i = threadIdx.x; i < padded; i += 64) rpos[o + i] = i < n ? tok_pos[o + i] - first : 0;
+}
+
+// Handles with q / k norms (Qwen3): behind the EPI_QKV_SPLIT projection, in place on q [T, heads DH] and k [T, kv_heads DH], per (token, head) in fp32
+//   x <- x * rsqrt(mean(x^2) + eps) * g, then the NeoX rotation by the token's position (x'[j] = x[j] cos - x[j + DH/2] sin, x'[j + DH/2] = x[j + DH/2] cos +
+//   x[j] sin) — HF's order, norm before rope.  gq carries the score scale log2(e) / sqrt(DH): a scale folded in FRONT of an RMS norm is undone by it.  (W_q does
+//   carry the loader's fold s all the same — the loader cannot know that norms will follow: eps_q = s^2 eps makes the norm of s x the norm of x.)
+// DH / 8 lanes per head, a lane owns features 4 i .. 4 i + 3 and their rotary partners (+ DH / 2): two 8-byte accesses, a rotary pair never leaves its lane,
+// the sum of squares is log2(DH / 8) shuffles.  A 64-wide head lies in tile-pair order (ROWS_HEAD64: its 16-feature blocks as 0, 2, 1, 3), as the rotating
+// epilogues store it, and stays so; 32- and 128-wide heads in plain order.  The rows past the packed total are not touched.
+template <int DH>
+__global__ __launch_bounds__(256) void k_qk_norm_rope(uint16_t* __restrict__ q, uint16_t* __restrict__ k, const int* __restrict__ Tp, int heads, int kv_heads,
+                                                      const float* __restrict__ gq, const float* __restrict__ gk, float eps_q, float eps_k,
+                                                      const float* __restrict__ rot_cos, const float* __restrict__ rot_sin, const int* __restrict__ tpos, int max_pos) {
+    static_assert(DH == 32 || DH == 64 || DH == 128, "head width 32, 64 or 128");
+    constexpr int LPH = DH / 8, HPW = 64 / LPH;           // lanes per head, heads per wave
+    const int lane = threadIdx.x & 63, i = lane % LPH;
+    const int nh = heads + kv_heads;
+    const int64_t u = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * HPW + lane / LPH;
+    const bool live = u < (int64_t)*Tp * nh;              // whole LPH-lane groups are live or not; the others ride along for the shuffles
+    const int64_t t = live ? u / nh : 0;
+    const int hd = live ? (int)(u % nh) : 0;
+    const bool isq = hd < heads;
+    uint16_t* row = isq ? q + (t * heads + hd) * DH : k + (t * kv_heads + (hd - heads)) * DH;
+    const int f = 4 * i;                                  // the lane's first feature; where it and its partner lie in the row
+    const int pa = DH == 64 ? (f < 16 ? f : f + 16) : f, pb = DH == 64 ? (f < 16 ? f + 16 : f + 32) : f + DH / 2;
+    const uint2 wa = *reinterpret_cast<const uint2*>(row + pa), wb = *reinterpret_cast<const uint2*>(row + pb);
+    float x[4] = {unpack_lo16(wa.x), unpack_hi16(wa.x), unpack_lo16(wa.y), unpack_hi16(wa.y)};
+    float y[4] = {unpack_lo16(wb.x), unpack_hi16(wb.x), unpack_lo16(wb.y), unpack_hi16(wb.y)};
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss += x[j] * x[j] + y[j] * y[j];
+#pragma unroll
+    for (int m = LPH / 2; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    const float rs = rsqrtf(ss * (1.0f / DH) + (isq ? eps_q : eps_k));
+    const float* g = isq ? gq : gk;
+    const float4 ga = *reinterpret_cast<const float4*>(g + f), gb = *reinterpret_cast<const float4*>(g + f + DH / 2);
+    const int p = tpos[t];
+    const int64_t ro = (int64_t)((unsigned)p < (unsigned)max_pos ? p : 0) * (DH / 2) + f;
+    const float4 cs = *reinterpret_cast<const float4*>(rot_cos + ro), sn = *reinterpret_cast<const float4*>(rot_sin + ro);
+    const float gav[4] = {ga.x, ga.y, ga.z, ga.w}, gbv[4] = {gb.x, gb.y, gb.z, gb.w}, c[4] = {cs.x, cs.y, cs.z, cs.w}, s[4] = {sn.x, sn.y, sn.z, sn.w};
+    float oa[4], ob[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = x[j] * rs * gav[j], b = y[j] * rs * gbv[j];
+        oa[j] = a * c[j] - b * s[j];
+        ob[j] = b * c[j] + a * s[j];
+    }
+    if (!live) return;
+    *reinterpret_cast<uint2*>(row + pa) = make_uint2(pack_bf16x2(oa[0], oa[1]), pack_bf16x2(oa[2], oa[3]));
+    *reinterpret_cast<uint2*>(row + pb) = make_uint2(pack_bf16x2(ob[0], ob[1]), pack_bf16x2(ob[2], ob[3]));
 }
 
 // LayerNorm(y + bias + residual) with 16-byte accesses: a lane owns 8 consecutive elements per 512-element step (one global_load_dwordx4 per tensor and step:
@@ -856,11 +907,12 @@ __global__ __launch_bounds__(256) void k_splade_finish(float* __restrict__ w, in
 __global__ __launch_bounds__(256) void k_gather_cls(const uint16_t* __restrict__ ctx, const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,
                                                     const int* __restrict__ seq_off, const int* __restrict__ seq_cls, const int* __restrict__ seq_nk, int H, uint16_t* __restrict__ c_ctx,
                                                     uint16_t* __restrict__ c_xb, uint8_t* __restrict__ c_xlo, int* __restrict__ c_off, int* __restrict__ c_nk,
-                                                    int* __restrict__ c_cls, int* __restrict__ d_B, int last_row) {
+                                                    int* __restrict__ c_cls, int* __restrict__ d_B, int last_row, int Dq) {
     const int b = blockIdx.x;
     const int64_t src = (int64_t)seq_off[b] + (last_row ? (seq_nk[b] > 0 ? seq_nk[b] - 1 : 0) : seq_cls[b]);
+    // the context rows are Dq = heads d_h wide (H unless the handle has a head width of its own), the residual stream H
+    for (int i = threadIdx.x * 8; i < Dq; i += 256 * 8) *reinterpret_cast<uint4*>(c_ctx + (int64_t)b * Dq + i) = *reinterpret_cast<const uint4*>(ctx + src * Dq + i);
     for (int i = threadIdx.x * 8; i < H; i += 256 * 8) {
-        *reinterpret_cast<uint4*>(c_ctx + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(ctx + src * H + i);
         *reinterpret_cast<uint4*>(c_xb + (int64_t)b * H + i) = *reinterpret_cast<const uint4*>(xb + src * H + i);
         if (xlo) *reinterpret_cast<uint2*>(c_xlo + (int64_t)b * H + i) = *reinterpret_cast<const uint2*>(xlo + src * H + i);
     }

@@ -7,6 +7,10 @@ namespace KR_ENC_NS {
 
 static int refuse(const model::Error& er) { return er.code ? fail(er.code, "%s", er.msg.c_str()) : 0; }
 
+// the head width d_h and Dq = heads d_h, the width of q and of the context: hidden / heads and hidden unless the handle was given config.head_dim
+static int head_width(const Encoder* e) { return e->set.value(model::SET_HEAD_DIM, e->cfg.hidden / e->cfg.heads); }
+static int64_t q_width(const Encoder* e) { return (int64_t)e->cfg.heads * head_width(e); }
+
 void enc_destroy(void* h);
 
 int enc_create(const kr_bert_cfg* cfg, int device, int residual_lo, void** out) {
@@ -67,9 +71,25 @@ static int set_config(Encoder* e, const char* name, const float* data, int64_t n
         v.resize((size_t)numel);
         KR_HIP(hipMemcpy(v.data(), data, (size_t)numel * 4, hipMemcpyDefault));
     }
+    const bool head_dim = model::find_setting(name) == model::SET_HEAD_DIM;
+    if (head_dim && !e->finalized_once)      // the packed QKV matrix, o_proj and the bias rows are laid out by it
+        for (size_t i = model::T_LAYER0; i < e->ld.got.size(); ++i) {
+            const int id = (int)((i - model::T_LAYER0) % model::L_COUNT);
+            if (e->ld.got[i] && id >= model::L_QW && id <= model::L_OW) return fail(KR_EINVAL, "config.head_dim behind a layer's attention tensors: load it before the weights");
+        }
     bool stored = false;
     KR_TRY(refuse(model::set_setting(e->cfg, e->set, e->ld.heads, e->finalized_once, name, v.data(), numel, stored)));
     if (stored) e->ready = false;
+    if (stored && head_dim) {
+        // [Dq + 2A, H] with A <= Dq, [H, Dq] and the q | k | v bias rows at the handle's own width (enc_create allocated them for Dq = H)
+        const size_t H = e->cfg.hidden, Dq = (size_t)q_width(e);
+        free_ws(e);
+        for (auto& l : e->L) {
+            (void)hipFree(l.wqkv); l.wqkv = nullptr; (void)hipFree(l.wo); l.wo = nullptr; (void)hipFree(l.bqkv); l.bqkv = nullptr;      // (own_bufs keeps pointing at the members)
+            KR_HIP(hipMalloc(reinterpret_cast<void**>(&l.wqkv), 3 * Dq * H * 2)); KR_HIP(hipMalloc(reinterpret_cast<void**>(&l.wo), H * Dq * 2));
+            KR_HIP(hipMalloc(reinterpret_cast<void**>(&l.bqkv), 3 * Dq * 4));
+        }
+    }
     return 0;
 }
 
@@ -215,10 +235,11 @@ static float* slot_f32(Encoder* e, int slot, size_t* count = nullptr) {
         if (slot == T_TYPE) n = (size_t)e->cfg.type_vocab * H;
     } else {
         LayerW& l = e->L[(slot - T_LAYER0) / L_COUNT];
+        const size_t Dq = (size_t)q_width(e);      // the q | k | v bias rows: Dq floats each (v's per query head)
         switch ((slot - T_LAYER0) % L_COUNT) {
-            case L_QB: p = l.bqkv; break;
-            case L_KB: p = l.bqkv + H; break;
-            case L_VB: p = l.bqkv + 2 * H; break;
+            case L_QB: p = l.bqkv; n = Dq; break;
+            case L_KB: p = l.bqkv + Dq; n = Dq; break;
+            case L_VB: p = l.bqkv + 2 * Dq; n = Dq; break;
             case L_OB: p = l.bo; break;
             case L_LN1G: p = l.ln1g; break;
             case L_LN1B: p = l.ln1b; break;
@@ -244,8 +265,21 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     const int slot = r.slot, layer = r.layer;
     // NomicBert's and ModernBert's names: q / k (rotary partners) and the gated projection's rows go into tile-pair order; T5's: wi_0 | wi_1 only
     const bool paired = r.fam == NOMIC || r.fam == MODERN, gated = paired || r.gated;
-    KR_TRY(refuse(check_tensor(e->cfg, hf_name, r, numel, e->ld, e->finalized_once)));
+    KR_TRY(refuse(check_tensor(e->cfg, hf_name, r, numel, e->ld, e->finalized_once, e->set.value(SET_HEAD_DIM, 0))));
     if (slot == T_IGNORED) return 0;   // pooler.* / position_ids: not used by the encoders (encoders.py:74,115 take last_hidden_state)
+    const int64_t dh = head_width(e), Dq = q_width(e);
+    if (slot == T_QNORM || slot == T_KNORM) {
+        // the weight of a layer's q / k norm, fp32 [d_h]; q's carries the score scale log2(e) / sqrt(d_h) (k_qk_norm_rope)
+        float*& dst = slot == T_QNORM ? e->L[layer].qng : e->L[layer].kng;
+        if (!dst) KR_TRY(dmalloc(e->own_bufs, &dst, (size_t)dh * 4));
+        std::vector<float> g((size_t)numel);
+        KR_HIP(hipMemcpy(g.data(), data, (size_t)numel * 4, hipMemcpyDefault));
+        if (slot == T_QNORM) for (float& x : g) x *= (float)(1.4426950408889634 / std::sqrt((double)dh));
+        KR_HIP(hipMemcpy(dst, g.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
+        mark_loaded(e->ld, r);
+        e->ready = false;
+        return 0;
+    }
     if (slot <= T_RELEMB) {            // DeBERTa's position table and its norm, kept as loaded on the host: finalize builds every layer's PQ / PK from them (build_disent_tables)
         std::vector<float>& dst = slot == T_RELEMB ? e->rel_emb : slot == T_RELLNG ? e->rel_lng : e->rel_lnb;
         dst.resize((size_t)numel);
@@ -274,14 +308,14 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
     // no 1 / sqrt(d_h): under T5's names log2(e) alone is folded in
     // DeBERTa's scores are (q.k + q.PK + k.PQ) / sqrt(3 d_h): under DeBERTa's names that factor
     const float qscale = r.fam == T5 ? (float)1.4426950408889634
-                       : r.fam == DEBERTA ? (float)(1.4426950408889634 / std::sqrt(3.0 * (double)(H / e->cfg.heads))) : (float)(1.4426950408889634 / std::sqrt((double)(H / e->cfg.heads)));
+                       : r.fam == DEBERTA ? (float)(1.4426950408889634 / std::sqrt(3.0 * (double)(H / e->cfg.heads))) : (float)(1.4426950408889634 / std::sqrt((double)dh));
     // rows [n / H, H] from element `first` of the staged copy; mode >= 0: into tile-pair order (k_f32_to_bf16_rows)
     auto to_bf16 = [&](uint16_t* dst, int64_t first, int64_t n, float scale, int mode) {
         const unsigned g = (unsigned)((n + 255) / 256);
         if (mode < 0) hipLaunchKernelGGL(k_f32_to_bf16, dim3(g), dim3(256), 0, 0, e->stage + first, dst, n, scale);
         else hipLaunchKernelGGL(k_f32_to_bf16_rows, dim3(g), dim3(256), 0, 0, e->stage + first, dst, n, (int)H, scale, mode);
     };
-    const int head64 = paired && H == 64 * e->cfg.heads ? (int)ROWS_HEAD64 : -1;
+    const int head64 = paired && dh == 64 ? (int)ROWS_HEAD64 : -1;
     // the tensors that fill w1 allocate it: [FF, H], or gated [2 FF, H]; a layer holds one kind
     auto claim_w1 = [&](LayerW& l, int li) -> int {
         if (l.w1 && l.gated != gated)
@@ -323,17 +357,17 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
             std::vector<float> b((size_t)numel), pb((size_t)numel);
             KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
             // (k's comes with its own A = numel entries: whole 64-wide heads, so the row order applies per head as in the matrix)
-            const bool h64 = H == 64 * e->cfg.heads;
+            const bool h64 = dh == 64;
             for (int64_t i = 0; i < numel; ++i) pb[(size_t)(h64 ? tile_pair_row(i, ROWS_HEAD64) : i)] = b[(size_t)i] * (id == L_QB ? qscale : 1.f);
             KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)numel * 4, hipMemcpyHostToDevice));
-        } else if (r.fam == DECODER && id == L_VB && numel != H) {
+        } else if (r.fam == DECODER && id == L_VB && numel != Dq) {
             // a grouped-query value bias [A]: kept per QUERY head, [H], where the plain one lives — the QKV epilogue never reads it, k_fold_vbias folds
             // Wo . bv into bo_eff over the context's H columns, and column c of the context is head c / d_h, which reads KV head (c / d_h) / group
-            const int64_t dh = H / e->cfg.heads, group = H / numel;
-            std::vector<float> b((size_t)numel), pb((size_t)H);
+            const int64_t group = Dq / numel;
+            std::vector<float> b((size_t)numel), pb((size_t)Dq);
             KR_HIP(hipMemcpy(b.data(), e->stage, (size_t)numel * 4, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < H; ++i) pb[(size_t)i] = b[(size_t)((i / dh / group) * dh + i % dh)];
-            KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)H * 4, hipMemcpyHostToDevice));
+            for (int64_t i = 0; i < Dq; ++i) pb[(size_t)i] = b[(size_t)((i / dh / group) * dh + i % dh)];
+            KR_HIP(hipMemcpy(slot_f32(e, slot), pb.data(), (size_t)Dq * 4, hipMemcpyHostToDevice));
         } else if (float* dst = slot == T_WORD ? e->word : slot_f32(e, slot))
             hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, e->stage, dst, numel, id == L_QB ? qscale : 1.f);
         else {
@@ -344,11 +378,12 @@ int enc_load_weight(void* h, const char* hf_name, const float* data, int64_t num
                 KR_HIP(hipMemcpy(keep, e->stage, (size_t)numel * 4, hipMemcpyDeviceToDevice));
             }
             switch (id) {
-                case L_QW: to_bf16(l.wqkv, 0, numel, qscale, head64); break;
+                case L_QW: to_bf16(l.wqkv, 0, numel, qscale, head64); l.qfold = qscale; break;
                 // the packed matrix is [H + 2A, H]: q's rows, k's from row H, v's from row H + A, A = numel / H the tensor's own row count (H unless it is a
                 // grouped-query decoder's: describe() holds k's against v's) — so the load order stays free
-                case L_KW: to_bf16(l.wqkv + H * H, 0, numel, 1.f, head64); break;
-                case L_VW: to_bf16(l.wqkv + H * H + numel, 0, numel, 1.f, -1); break;
+                // (Dq rows of q: H unless the handle has config.head_dim)
+                case L_KW: to_bf16(l.wqkv + Dq * H, 0, numel, 1.f, head64); break;
+                case L_VW: to_bf16(l.wqkv + Dq * H + numel, 0, numel, 1.f, -1); break;
                 case L_OW: to_bf16(l.wo, 0, numel, 1.f, -1); break;
                 case L_IW: to_bf16(l.w1, 0, numel, 1.f, gated ? (int)ROWS_GATE : -1); break;
                 case L_UW: to_bf16(l.w1, 0, numel, 1.f, ROWS_UP); break;
@@ -391,7 +426,7 @@ int enc_finalize(void* h) {
     if (p.rotary || p.head[HEAD_MLM] || p.pos == POS_DISENT) KR_TRY(zeros(&e->zero_row, (size_t)H * 4));
     if (p.rotary) KR_TRY(build_rotary_table(e, e->set.v[SET_ROTARY], &e->rot_cos, &e->rot_sin));
     if (p.rotary_local) KR_TRY(build_rotary_table(e, e->set.v[SET_ROTARY_LOCAL], &e->rot_cos_l, &e->rot_sin_l));
-    for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * H, l.bo_eff, H);
+    for (auto& l : e->L) hipLaunchKernelGGL(k_fold_vbias, dim3((H + 127) / 128), dim3(128), 0, 0, l.wo, l.bo, l.bqkv + 2 * p.q_dim, l.bo_eff, H, p.q_dim);
     if (p.rel_bias) KR_TRY(build_bias_table(e));
     KR_HIP(hipGetLastError());
     if (p.family == DEBERTA) KR_TRY(build_disent_tables(e));

@@ -32,7 +32,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 from transformers import (BertModel, DebertaV2Model, EuroBertModel, JinaEmbeddingsV3Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel,
-                          PretrainedConfig, Qwen2Model, T5EncoderModel, XLMRobertaModel)
+                          PretrainedConfig, Qwen2Model, Qwen3Model, T5EncoderModel, XLMRobertaModel)
 
 from .. import _lib
 
@@ -81,6 +81,10 @@ ROTARY_FF_SETTING = "config.rotary_feed_forward"     # reserved name (include/ki
 JINA3_MAX_POS = 8192                             # the rotary tables' limit: it only bounds the sequence length (the checkpoint says 8194)
 DECODER_SETTING = "config.decoder_attention"     # reserved name (include/kirag_amd.h): one float, 1 = causal, 0 = bidirectional on the same stack
 DECODER_MAX_POS = 8192                           # the rotary tables' limit: it only bounds the sequence length
+QWEN3_TYPE = "qwen3"                             # the decoders' stack with a head width of its own and RMS norms over every head of q and k
+HEAD_DIM_SETTING = "config.head_dim"             # reserved name (include/kirag_amd.h): one float, 32 / 64 / 128, sent before the frequencies and the weights
+QWEN3_HEAD_DIMS = (32, 64, 128)
+QWEN3_MAX_Q_WIDTH = 4096                         # heads * head_dim: the width of q and of the attention output
 DECODER_POOLINGS = {"mean": POOL_MEAN, "last": _lib.POOL_LAST}
 ST_POOLING_DIR = "1_Pooling"
 ST_DENSE_TYPE = "sentence_transformers.models.Dense"
@@ -168,6 +172,25 @@ def rope_frequencies(refuse, scaling, inv_freq, label: str, d_h: Optional[int] =
     if d_h is not None and inv.numel() != d_h // 2:
         refuse(f"the rotary module has {inv.numel()} frequencies, head_dim / 2 = {d_h // 2} are implemented (no partial rotation)")
     return inv
+
+
+def check_qwen3_shape(refuse, config):
+    """hidden / heads / head_dim / intermediate of a Qwen3 config.  ``head_dim`` is a field of its own there (Qwen3-0.6B: 16 heads of 128 on hidden 1024) and
+    travels as ``HEAD_DIM_SETTING``; the handle is still created from ``hidden_size / num_attention_heads``, which must be 32 or 64.  Returns ``(H, heads, ff, d_h)``."""
+    H, heads, ff = int(config.hidden_size), int(config.num_attention_heads), int(config.intermediate_size)
+    if heads <= 0 or H % heads:
+        refuse(f"num_attention_heads={heads} does not divide hidden_size={H}")
+    d_h = int(getattr(config, "head_dim", None) or H // heads)
+    if d_h not in QWEN3_HEAD_DIMS:
+        refuse(f"head_dim={d_h}: the attention kernels are built for heads of width 32, 64 and 128")
+    if H // heads not in (32, 64):
+        refuse(f"hidden_size={H} / num_attention_heads={heads} = {H // heads}: a handle is created from hidden_size / num_attention_heads, which must be 32 or 64 "
+               f"whatever head_dim says (Qwen3-0.6B: 1024 / 16 = 64 runs; Qwen3-1.7B and up: 2048 / 16 = 128 do not yet)")
+    check_hidden(refuse, H)
+    check_ff(refuse, ff)
+    if (heads * d_h) % 128 or heads * d_h > QWEN3_MAX_Q_WIDTH:
+        refuse(f"num_attention_heads={heads} x head_dim={d_h} = {heads * d_h}: the width of q must be a multiple of 128 up to {QWEN3_MAX_Q_WIDTH}")
+    return H, heads, ff, d_h
 
 
 def _decoder_rope_frequencies(refuse, config, d_h: int) -> Tensor:
@@ -258,7 +281,7 @@ def check_jina3_config(config) -> dict:
 
 
 def check_decoder_config(config) -> dict:
-    """``NotImplementedError`` beginning ``model_type='<type>':`` and naming the field, for everything of a Qwen2 / Llama / Mistral / EuroBERT config the kernels do not
+    """``NotImplementedError`` beginning ``model_type='<type>':`` and naming the field, for everything of a Qwen2 / Llama / Mistral / Qwen3 / EuroBERT config the kernels do not
     compute — from the config alone: no weight has been read and the library is not loaded.  ``config``: the HF config or the dict of a ``config.json`` (HF's
     defaults fill the rest).  Returns what the handle is created with: hidden, layers, heads, kv_heads, intermediate, ``max_pos`` =
     min(max_position_embeddings, 8192), ``ln_eps`` = rms_norm_eps, and ``inv_freq`` from HF's own rotary module (so static rope variants such as ``llama3`` are
@@ -269,12 +292,17 @@ def check_decoder_config(config) -> dict:
         refuse(f"the decoder path is built for {sorted(DECODER_BASES)}")
     if isinstance(config, dict):
         config = _hf_config(mt, config)
-    H, heads, ff, d_h = check_rotary_shape(refuse, config)
+    qwen3 = mt == QWEN3_TYPE
+    H, heads, ff, d_h = check_qwen3_shape(refuse, config) if qwen3 else check_rotary_shape(refuse, config)
     kv = int(getattr(config, "num_key_value_heads", None) or heads)
     if getattr(config, "hidden_act", "silu") != "silu":
         refuse(f"hidden_act={config.hidden_act!r}: the gated MLP of a decoder handle implements silu only")
     if kv <= 0 or heads % kv:
         refuse(f"num_key_value_heads={kv} does not divide num_attention_heads={heads}")
+    if qwen3 and (kv * d_h) % KV_NATIVE_MULTIPLE:
+        refuse(f"num_key_value_heads={kv} x head_dim={d_h} = {kv * d_h}: the width of k / v must be a multiple of {KV_NATIVE_MULTIPLE}")
+    if qwen3 and getattr(config, "attention_bias", False):
+        refuse("attention_bias=True: the q / k norms of a Qwen3 handle run on projections without a bias")
     if getattr(config, "attention_bias", False):
         refuse("attention_bias=True: a bias on o_proj is not implemented (the q / k / v biases of Qwen2 are)")
     if getattr(config, "mlp_bias", False):
@@ -289,7 +317,7 @@ def check_decoder_config(config) -> dict:
     if any(t != "full_attention" for t in types):
         refuse(f"layer_types={types!r}: full_attention layers only")
     return {"hidden": H, "layers": int(config.num_hidden_layers), "heads": heads, "kv_heads": kv, "intermediate": ff, "max_pos": max_pos,
-            "ln_eps": float(config.rms_norm_eps), "inv_freq": _decoder_rope_frequencies(refuse, config, d_h)}
+            "ln_eps": float(config.rms_norm_eps), "inv_freq": _decoder_rope_frequencies(refuse, config, d_h), "head_dim": d_h if qwen3 else None}
 
 
 
@@ -322,7 +350,7 @@ def kv_for_library(name: str, w, heads: int, kv_heads: int, hidden: int):
     """A decoder checkpoint's tensor as the weight sync sends it: unchanged — grouped-query ``k_proj`` / ``v_proj`` tensors included — when the library
     takes ``A = kv_heads d_h`` natively (``A % 64 == 0``), else with the KV heads expanded (``expand_kv``; e.g. 4 heads of 32 over 1 KV head: A = 32).  A tensor
     that already has ``hidden`` rows (a caller who expanded it) passes as it is."""
-    A = kv_heads * (hidden // heads)
+    A = kv_heads * (hidden // heads)      # (a Qwen3 handle's k / v have kv_heads * head_dim rows, a multiple of 64 by check_decoder_config: they pass as they are)
     if A % KV_NATIVE_MULTIPLE == 0 or w.shape[0] != A:
         return w
     return expand_kv(name, w, heads, kv_heads)
@@ -458,8 +486,10 @@ def describe_decoder(config) -> HandleSpec:
     d = check_decoder_config(config)
     _check_bert_like(config, gelu=False)
     ff = int(config.intermediate_size)
+    # (a Qwen3 handle: the head width first — the frequencies are counted against it, and the weights are laid out by it)
+    width = ((HEAD_DIM_SETTING, _setting(d["head_dim"])),) if d["head_dim"] is not None else ()
     return HandleSpec((d["hidden"], d["layers"], d["heads"], ff, config.vocab_size, d["max_pos"], 1, d["ln_eps"]), ff, ff,
-                      (("config.rotary_inv_freq", d["inv_freq"]),), heads=d["heads"], kv_heads=d["kv_heads"])
+                      width + (("config.rotary_inv_freq", d["inv_freq"]),), heads=d["heads"], kv_heads=d["kv_heads"])
 
 
 def describe_jina3(config) -> HandleSpec:
@@ -1244,6 +1274,8 @@ DebertaV2E5Encoder, DebertaV2BGEEncoder = _twin_pair(
 Qwen2E5Encoder, Qwen2BGEEncoder = _decoder_pair(
     Qwen2Model, "Qwen2Model (causal) -> masked mean -> L2 normalise (the Qwen2.5-0.5B embedders: KaLM-embedding-multilingual-mini)",
     "Qwen2Model (causal) -> last attended token -> L2 normalise")
+Qwen3E5Encoder, Qwen3BGEEncoder = _decoder_pair(
+    Qwen3Model, "Qwen3Model (causal) -> masked mean -> L2 normalise", "Qwen3Model (causal) -> last attended token -> L2 normalise (Qwen/Qwen3-Embedding-0.6B)")
 LlamaE5Encoder, LlamaBGEEncoder = _decoder_pair(
     LlamaModel, "LlamaModel (causal) -> masked mean -> L2 normalise (Llama-3.2-1B, TinyLlama, SmolLM2 fine-tunes)",
     "LlamaModel (causal) -> last attended token -> L2 normalise")
@@ -1289,6 +1321,9 @@ _FAMILIES = (
     _decoder_family("qwen2", (Qwen2E5Encoder, Qwen2BGEEncoder)),
     _decoder_family("llama", (LlamaE5Encoder, LlamaBGEEncoder)),
     _decoder_family("mistral", (MistralE5Encoder, MistralBGEEncoder)),
+    # Qwen3: the same stack with head_dim as a config field of its own (HEAD_DIM_SETTING: q_proj [heads head_dim, hidden], 128-wide heads included), an RMS norm
+    # over every head of q and of k in front of the rotation (layers.N.self_attn.{q,k}_norm.weight) and no q / k / v bias
+    _decoder_family(QWEN3_TYPE, (Qwen3E5Encoder, Qwen3BGEEncoder)),
     # EuroBERT: the decoders' stack under a BIDIRECTIONAL mask (DECODER_SETTING = 0); the other decoder twins take the same choice as attention="bidirectional"
     _decoder_family(EUROBERT_TYPE, (EuroBertE5Encoder, EuroBertBGEEncoder), decoder_attention=0.0),
 )
@@ -1298,7 +1333,7 @@ DECODER_BASES = {t: f.hf_base for t, f in FAMILIES.items() if f.flag == "is_deco
 
 
 class _DecoderDispatch:
-    """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral`` / ``eurobert``); anything else is refused by name"""
+    """``from_pretrained`` of the decoder twins by ``model_type`` (``qwen2`` / ``llama`` / ``mistral`` / ``qwen3`` / ``eurobert``); anything else is refused by name"""
     _pool = POOL_MEAN
 
     @classmethod

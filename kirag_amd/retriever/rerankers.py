@@ -31,11 +31,12 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 from transformers import (BertForSequenceClassification, DebertaV2ForSequenceClassification, LlamaForSequenceClassification, MistralForSequenceClassification,
-                          ModernBertConfig, ModernBertForSequenceClassification, Qwen2ForSequenceClassification, XLMRobertaForSequenceClassification)
+                          ModernBertConfig, ModernBertForSequenceClassification, Qwen2ForSequenceClassification, Qwen3ForSequenceClassification,
+                          XLMRobertaForSequenceClassification)
 from transformers.modeling_outputs import SequenceClassifierOutput
 
 from ..collators import RerankerCollator
-from .encoders import (DEBERTA_TYPE, DECODER_ATTENTIONS, EUROBERT_TYPE, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, ST_ATTENTION_FILE,
+from .encoders import (DEBERTA_TYPE, DECODER_ATTENTIONS, EUROBERT_TYPE, QWEN3_TYPE, MODERN_LAYER_TYPES, MODERN_TYPE, POOL_CLASSIFY, ROBERTA_TYPES, ST_ATTENTION_FILE,
                        ST_POOLING_DIR, HipBertForward, _HipModuleMixin, _refuser, _st_file, check_decoder_config, check_deberta_config, check_heads, check_hidden,
                        checkpoint_model_type)
 from .m3 import BGEM3Model
@@ -186,6 +187,7 @@ class DebertaV2Reranker(_HipClassifierMixin, DebertaV2ForSequenceClassification)
 
 
 DECODER_RERANKER_TYPES = ("qwen2", "llama", "mistral")
+QWEN3_RERANKER_TYPES = (QWEN3_TYPE,)     # Qwen3ForSequenceClassification, and Qwen3ForCausalLM "yes / no" rerankers through ``DecoderReranker.from_causal_lm``
 
 
 def decoder_rename(name: str) -> str:
@@ -211,8 +213,8 @@ def check_decoder_reranker_config(config) -> dict:
     if mt == EUROBERT_TYPE:
         refuse("EuroBertForSequenceClassification's head is dense -> activation -> classifier over clf_pooling, not the score head of the decoder "
                f"rerankers: they run for {DECODER_RERANKER_TYPES}")
-    if mt not in DECODER_RERANKER_TYPES:
-        refuse(f"the decoder rerankers run for {DECODER_RERANKER_TYPES}")
+    if mt not in DECODER_RERANKER_TYPES + QWEN3_RERANKER_TYPES:
+        refuse(f"the decoder rerankers run for {DECODER_RERANKER_TYPES + QWEN3_RERANKER_TYPES}")
     d = check_decoder_config(config)
     labels = config_num_labels(config)
     if labels > MAX_LABELS:
@@ -305,6 +307,11 @@ class Qwen2Reranker(_HipDecoderClassifierMixin, Qwen2ForSequenceClassification):
     _hf_base = Qwen2ForSequenceClassification
 
 
+class Qwen3Reranker(_HipDecoderClassifierMixin, Qwen3ForSequenceClassification):
+    """Qwen3Model (causal, q / k norms, head_dim of its own) -> last attended token -> score (Qwen3-Reranker-0.6B folded by ``DecoderReranker.from_causal_lm``)"""
+    _hf_base = Qwen3ForSequenceClassification
+
+
 class LlamaReranker(_HipDecoderClassifierMixin, LlamaForSequenceClassification):
     """LlamaModel (causal) -> last attended token -> score (CrossEncoder fine-tunes of Llama-3.2-1B, TinyLlama, SmolLM2)"""
     _hf_base = LlamaForSequenceClassification
@@ -315,7 +322,7 @@ class MistralReranker(_HipDecoderClassifierMixin, MistralForSequenceClassificati
     _hf_base = MistralForSequenceClassification
 
 
-_DECODER_RERANKERS = {"qwen2": Qwen2Reranker, "llama": LlamaReranker, "mistral": MistralReranker}
+_DECODER_RERANKERS = {"qwen2": Qwen2Reranker, "llama": LlamaReranker, "mistral": MistralReranker, QWEN3_TYPE: Qwen3Reranker}
 
 
 class DecoderReranker:
@@ -331,7 +338,7 @@ class DecoderReranker:
 
     @classmethod
     def from_causal_lm(cls, path, positive_token_id: int, negative_token_id: Optional[int] = None, **kwargs):
-        """A one-label reranker from a causal-LM folder (``Qwen2ForCausalLM`` / ``LlamaForCausalLM`` / ``MistralForCausalLM``): a "yes / no" reranker scores a
+        """A one-label reranker from a causal-LM folder (``Qwen2ForCausalLM`` / ``LlamaForCausalLM`` / ``MistralForCausalLM`` / ``Qwen3ForCausalLM``): a "yes / no" reranker scores a
         pair by the difference of two LM-head logits at the last token, ``lm_head[pos] . x - lm_head[neg] . x``, which is the one-label score head
         ``score.weight = lm_head[pos] - lm_head[neg]`` (``lm_head[pos]`` alone when ``negative_token_id`` is None).  The LM-head rows are the
         ``embed_tokens`` rows when the embeddings are tied and the folder holds no ``lm_head.weight``.  The result is an ordinary twin:
@@ -384,7 +391,7 @@ class BGEReranker:
         if model_type in (DEBERTA_TYPE, "deberta"):
             check_deberta_config(cfg_dict, head=True)      # from config.json alone: before a weight is read
             return DebertaV2Reranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
-        if model_type in DECODER_RERANKER_TYPES or model_type == EUROBERT_TYPE:      # (EuroBERT: refused there, with the sentence that says why)
+        if model_type in DECODER_RERANKER_TYPES + QWEN3_RERANKER_TYPES or model_type == EUROBERT_TYPE:      # (EuroBERT: refused there, with the sentence that says why)
             return DecoderReranker.from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         raise NotImplementedError(f"model_type={model_type!r}: cross-encoder rerankers run for 'bert', {MODERN_TYPE!r}, {DEBERTA_TYPE!r}, {ROBERTA_TYPES} and "
                                   f"{DECODER_RERANKER_TYPES} checkpoints (the classification heads of other families are other functions)")

@@ -60,7 +60,7 @@ import numpy as np
 import torch
 
 F16_MAX = 65504.0
-DECODER_RERANKER_TYPES = ("qwen2", "llama", "mistral")      # ...ForSequenceClassification with the score head (kirag_amd.retriever.rerankers)
+DECODER_RERANKER_TYPES = ("qwen2", "llama", "mistral", "qwen3")      # ...ForSequenceClassification with the score head (kirag_amd.retriever.rerankers)
 MODES = [("f16", True), ("f16", False), ("bf16", True), ("bf16", False)]      # default first; cost order: last is cheapest
 MODE_COST = {("f16", True): "default: 29.5 ms per 1000-query step", ("f16", False): "-3 %", ("bf16", True): "-3.5 %", ("bf16", False): "-7 %"}
 
@@ -437,7 +437,7 @@ def check(hf_dir, args):
         return check_model(AutoModel.from_pretrained(hf_dir, add_pooling_layer=False, attn_implementation="eager"), args, hf_dir)
     if getattr(cfg, "model_type", "bert") not in ("bert", MPNET_TYPE, NOMIC_TYPE, MODERN_TYPE, DEBERTA_TYPE) + ROBERTA_TYPES:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r}; the HIP encoder implements the BERT architecture (e5 / bge), the RoBERTa family "
-                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3, T5 encoders, jina-embeddings-v3, EuroBERT and Qwen2 / Llama / Mistral embedders")
+                         f"{ROBERTA_TYPES} (multilingual-e5, bge-m3), MPNet (all-mpnet-base-v2), NomicBert (nomic-embed-text-v1 / -v1.5), ModernBERT, DeBERTa-v2 / v3, T5 encoders, jina-embeddings-v3, EuroBERT and Qwen2 / Llama / Mistral / Qwen3 embedders")
     if cfg.model_type == MODERN_TYPE:
         model = AutoModel.from_pretrained(hf_dir, attn_implementation="eager")      # ModernBertModel has no pooling layer
     elif cfg.model_type == DEBERTA_TYPE:
@@ -467,7 +467,7 @@ def check_model(model, args, hf_dir="(in-memory model)"):
     if getattr(cfg, "model_type", "bert") == T5_TYPE and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms and a relative attention bias, which the torch emulation does not "
                          "implement: run on the GPU")
-    if getattr(cfg, "model_type", "bert") in ("qwen2", "llama", "mistral", "eurobert") and not use_hip:
+    if getattr(cfg, "model_type", "bert") in ("qwen2", "llama", "mistral", "eurobert", "qwen3") and not use_hip:
         raise SystemExit(f"{hf_dir}: model_type {cfg.model_type!r} is a pre-LN stack with RMS norms, rotary positions and a gated MLP, which the torch emulation "
                          "does not implement: run on the GPU")
     if getattr(cfg, "model_type", "bert") == DEBERTA_TYPE and not use_hip:

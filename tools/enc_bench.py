@@ -79,8 +79,13 @@ JINA_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "interme
              "layer_norm_eps", "hidden_act", "rope_parameters")
 JINA_V3 = dict(BS.E5_LARGE, vocab_size=250002, max_position_embeddings=8194, type_vocab_size=1, layer_norm_eps=1e-5, hidden_act="gelu", model_type="jina_embeddings_v3",
                rope_parameters={"rope_theta": 20000.0, "rope_type": "default"})
-DECODER_TYPES = ("qwen2", "llama", "mistral", "eurobert")
-SHAPES = dict(BS.ENCODER_SHAPES, **{"qwen2-0.5b": QWEN2_05B, "llama-1b": LLAMA_1B, "eurobert-210m": EUROBERT_210M, "jina-v3": JINA_V3}, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
+# Qwen3-Embedding-0.6B / Qwen3-Reranker-0.6B: head_dim is a config field of its own — 16 heads of 128 over 8 KV heads on hidden 1024 (q and the attention output
+# are 2048 wide), an RMS norm over every head of q and k in front of the rotation, no bias
+QWEN3_06B = dict(hidden_size=1024, num_hidden_layers=28, num_attention_heads=16, num_key_value_heads=8, head_dim=128, intermediate_size=3072, vocab_size=151936,
+                 max_position_embeddings=32768, rms_norm_eps=1e-6, hidden_act="silu", tie_word_embeddings=True, model_type="qwen3", type_vocab_size=1, layer_norm_eps=1e-6,
+                 rope_parameters={"rope_theta": 1000000.0, "rope_type": "default"})
+DECODER_TYPES = ("qwen2", "llama", "mistral", "eurobert", "qwen3")
+SHAPES = dict(BS.ENCODER_SHAPES, **{"qwen2-0.5b": QWEN2_05B, "qwen3-0.6b": QWEN3_06B, "llama-1b": LLAMA_1B, "eurobert-210m": EUROBERT_210M, "jina-v3": JINA_V3}, **{"deberta-v3-base": DEBERTA_V3_BASE, "t5-base": T5_BASE, "t5-base-gated": T5_BASE_GATED, "modernbert-base": MODERNBERT_BASE, "modernbert-base-global": MODERNBERT_BASE_GLOBAL, "xlmr-base": XLMR_BASE, "xlmr-large": XLMR_LARGE, "bge-m3": BGE_M3, "mpnet-base": MPNET_BASE,
                                     "mpnet-base-nobias": MPNET_BASE_NOBIAS, "nomic-base": NOMIC_BASE, "xlmr-base-8k": XLMR_BASE_8K})
 
 ap = argparse.ArgumentParser()
@@ -254,23 +259,31 @@ def make_decoder(cfg, causal=True, expanded=False, extra_state=None):
     import transformers as T
     from kirag_amd.retriever.encoders import HipBertForward, expand_kv
 
-    conf = {"qwen2": T.Qwen2Config, "llama": T.LlamaConfig, "mistral": T.MistralConfig, "eurobert": T.EuroBertConfig}[cfg["model_type"]](**{k: cfg[k] for k in DECODER_KEYS})
+    qwen3 = cfg["model_type"] == "qwen3"
+    conf = {"qwen2": T.Qwen2Config, "llama": T.LlamaConfig, "mistral": T.MistralConfig, "eurobert": T.EuroBertConfig, "qwen3": T.Qwen3Config}[cfg["model_type"]](
+        **{k: cfg[k] for k in DECODER_KEYS + (("head_dim",) if qwen3 else ())})
     enc = HipBertForward(conf, 0, decoder_attention=1.0 if causal else 0.0)
     ns = SimpleNamespace(**dict(cfg, max_position_embeddings=8))      # synthetic_state draws a position table of this many rows; it is dropped below
     state = dict(BS.synthetic_state(ns, dev, 0))
     g = torch.Generator(device=dev); g.manual_seed(977)
     L, b, H = cfg["num_hidden_layers"], "encoder.layer.", cfg["hidden_size"]
-    kv_rows = H // cfg["num_attention_heads"] * cfg["num_key_value_heads"]
+    d_h = cfg.get("head_dim") or H // cfg["num_attention_heads"]
+    kv_rows, q_rows = d_h * cfg["num_key_value_heads"], d_h * cfg["num_attention_heads"]
+    # (a Qwen3 shape: q_proj [q_rows, H] and o_proj [H, q_rows] with q_rows != H — drawn here like the BERT-shaped ones, 0.02 N(0, 1))
+    wide = lambda r, c: 0.02 * torch.randn((r, c), generator=g, device=dev)
     st = {"embed_tokens.weight": state["embeddings.word_embeddings.weight"], "norm.weight": state[f"{b}{L - 1}.output.LayerNorm.weight"]}
     for l in range(L):
         p = f"layers.{l}."
         st[p + "input_layernorm.weight"] = state[f"{b}{l - 1}.output.LayerNorm.weight"] if l else state["embeddings.LayerNorm.weight"]
         st[p + "post_attention_layernorm.weight"] = state[f"{b}{l}.attention.output.LayerNorm.weight"]
-        for nm, t, rows in (("query", "q", H), ("key", "k", kv_rows), ("value", "v", kv_rows)):
-            st[p + f"self_attn.{t}_proj.weight"] = state[f"{b}{l}.attention.self.{nm}.weight"][:rows].contiguous()
+        for nm, t, rows in (("query", "q", q_rows), ("key", "k", kv_rows), ("value", "v", kv_rows)):
+            st[p + f"self_attn.{t}_proj.weight"] = state[f"{b}{l}.attention.self.{nm}.weight"][:rows].contiguous() if rows <= H else wide(rows, H)
             if cfg["model_type"] == "qwen2":
                 st[p + f"self_attn.{t}_proj.bias"] = state[f"{b}{l}.attention.self.{nm}.bias"][:rows].contiguous()
-        st[p + "self_attn.o_proj.weight"] = state[f"{b}{l}.attention.output.dense.weight"]
+        st[p + "self_attn.o_proj.weight"] = state[f"{b}{l}.attention.output.dense.weight"] if q_rows == H else wide(H, q_rows)
+        if qwen3:
+            st[p + "self_attn.q_norm.weight"] = 1.0 + 0.1 * torch.randn(d_h, generator=g, device=dev)
+            st[p + "self_attn.k_norm.weight"] = 1.0 + 0.1 * torch.randn(d_h, generator=g, device=dev)
         wi = state[f"{b}{l}.intermediate.dense.weight"]
         st[p + "mlp.gate_proj.weight"] = wi
         st[p + "mlp.up_proj.weight"] = 0.02 * torch.randn(wi.shape, generator=g, device=dev)
@@ -284,10 +297,11 @@ def make_decoder(cfg, causal=True, expanded=False, extra_state=None):
 
 
 def decoder_flops(cfg, lens, causal):
-    """8 H^2 (q, k, v, o with k / v expanded) + 6 H FF per token and layer, 4 s H of attention per token — half of it under the causal mask"""
+    """8 H Dq (q, k, v, o with k / v expanded; Dq = H unless head_dim is the shape's own) + 6 H FF per token and layer, 4 s Dq of attention per token — half of it under the causal mask"""
     lens = lens.double()
     H, FF = cfg["hidden_size"], cfg["intermediate_size"]
-    return float((cfg["num_hidden_layers"] * lens * (8.0 * H * H + 6.0 * H * FF + (2.0 if causal else 4.0) * lens * H)).sum())
+    Dq = cfg["num_attention_heads"] * cfg["head_dim"] if cfg.get("head_dim") else H      # the width of q and of the attention output (a Qwen3 shape: not H)
+    return float((cfg["num_hidden_layers"] * lens * (8.0 * H * Dq + 6.0 * H * FF + (2.0 if causal else 4.0) * lens * Dq)).sum())
 
 
 def first_forward(shape, cfg, ids, mask):
@@ -381,7 +395,7 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
         lens = mask.sum(1).double()
         fl = float((cfg["num_layers"] * lens * (8.0 * cfg["hidden_size"] ** 2 + 6.0 * cfg["hidden_size"] * cfg["d_ff"] + 4.0 * lens * cfg["hidden_size"])).sum())
     dt = timed(lambda: enc.forward(ids, mask, pool), args.reps)
-    print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
+    print(f"{shape} (H {cfg['hidden_size']}, {cfg['num_attention_heads']} heads of {cfg.get('head_dim') or cfg['hidden_size'] // cfg['num_attention_heads']}, L {cfg['num_hidden_layers']}) "
           f"tile={os.environ.get('KIRAG_AMD_PROJ_TILE','auto')} pool={args.pool} n={n} S={S} ragged={ragged}: {dt*1e3:.2f} ms  {n/dt:.0f} seq/s  {fl/dt/1e12:.0f} TFLOP/s  "
           f"{fl/dt/PEAK_MFMA_DENSE_16BIT:.3f} of MFMA peak  ({fl/n/1e9:.2f} GFLOP per sequence)" + (f"  sha256 {digest(enc.forward(ids, mask, pool))}" if args.digest else ""), flush=True)
     del enc
