@@ -467,6 +467,27 @@ void kr_encoder_destroy(kr_encoder* enc);
  *   KR_EINVAL.  The rule of "classifier.*" holds: fixed at the first finalize — the same L takes new values, another L, or the tensor arriving on a handle
  *   finalized without it, is KR_EINVAL — and a decoder handle WITHOUT it keeps refusing KR_POOL_CLASSIFY with KR_EINVAL.  kr_encoder_finalize refuses
  *   "score.weight" (KR_EINVAL, naming it) on a handle of any other kind.
+ * The tail of a sentence-transformers pipeline (what a checkpoint folder's modules.json states behind the transformer: Pooling, an optional Dense, Normalize or
+ * not), on handles of EVERY family and through all three forward entry points.  Three settings, under the usual rule (accepted before the first finalize;
+ * later the same value is a no-op and another is KR_EINVAL), ONE float each:
+ *   "config.normalize_output": 1 (also when never loaded) = the row of KR_POOL_MEAN / KR_POOL_CLS / KR_POOL_LAST — and the output of the Dense head below — is
+ *       divided by its norm; 0 = it is written as pooled (checkpoints trained for the dot product: facebook/contriever, msmarco-distilbert-base-tas-b,
+ *       multi-qa-mpnet-base-dot-v1).  The norm is formed either way: a non-finite row of a sequence with attended tokens stays KR_ERANGE.
+ *   "config.pool_tokens": what a KR_POOL_MEAN forward makes of the attended tokens: 0 (also when never loaded) = their mean, 1 = the element-wise max,
+ *       2 = sum / sqrt(n) (sentence-transformers' mean_sqrt_len_tokens).  KR_POOL_CLS and KR_POOL_LAST keep their row.  A sequence without attended tokens
+ *       gives a NaN row under all three and raises no error.
+ *   "config.st_dense_activation": 0 (also when never loaded) = identity, 1 = tanh: the activation of the head below; KR_EINVAL at finalize on a handle without
+ *       it, and after the first finalize it is known to handles with the head only.
+ *   Any other number, or more than one, is KR_EINVAL at load.
+ *   "st_dense.weight" [P, hidden], P % 4 == 0 and 4 <= P <= 2048 (any other count is KR_EINVAL at load), and "st_dense.bias" [P], optional, zero unless loaded
+ *   (alone it fails kr_encoder_finalize as "'st_dense.weight' was never loaded"): sentence-transformers' Dense module.  With it the three pools above write
+ *   out [B, P] fp32,
+ *       out = act(st_dense.weight . x + st_dense.bias),     x = the pooled row, NOT normalised,
+ *   then divided by its norm (F.normalize's 1e-12 floor) unless "config.normalize_output" is 0; fp32 arithmetic in an order that does not depend on the batch
+ *   around a sequence; a NaN pooled row stays NaN, a non-finite output of a sequence with attended tokens is KR_ERANGE.  The rule of every head holds: fixed at
+ *   the first finalize — the same P takes new values, another P, or the head arriving on a handle finalized without it, is KR_EINVAL.
+ *   kr_encoder_finalize refuses the three settings and the head (KR_EINVAL, naming both sides) on a handle that holds ANY other head: the MLM head, bge-m3's two,
+ *   "dense.weight", the three classification heads.  (A T5 checkpoint whose Dense has no bias and no activation keeps "dense.weight".)
  * BAAI/bge-m3's sparse and multi-vector heads (an XLM-R backbone; the same two Linear modules on a BERT backbone are accepted too), fp32:
  *   "colbert_linear.weight" [P, hidden], "colbert_linear.bias" [P]: P % 128 == 0 and 128 <= P <= 2048, any other count is KR_EINVAL;
  *   "sparse_linear.weight" [1, hidden], "sparse_linear.bias" [1].

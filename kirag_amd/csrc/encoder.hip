@@ -481,12 +481,33 @@ static int enqueue_pool_and_head(const Forward& f) {
     const int B = f.B, H = f.H;
     const RowSet& r = f.shortcut ? f.cls_rows : f.all_rows;
     const int NJ = with_pool_width(H, [](auto nj) { return (int)decltype(nj)::value; });
-    const auto pool_kernel = f.pool.classify ? with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value, true>; })
-                                             : with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value>; });
+    // the rows stay as pooled (RAW) for a classifier, for the sentence-transformers Dense head (which normalises its own output) and under
+    // config.normalize_output = 0; config.pool_tokens selects what a KR_POOL_MEAN forward pools (k_pool_tok: the max, sum / sqrt(n))
+    const bool st_dense = p.head[HEAD_ST_DENSE] && !f.pool.classify;
+    const bool raw = f.pool.classify || st_dense || !p.normalize;
+    const int tok = f.pool.select == KR_POOL_MEAN && !f.pool.classify ? p.pool_tokens : POOL_TOK_MEAN;
+    float* pool_out = p.head[HEAD_DENSE] || f.pool.classify || st_dense ? e->pooled : e->out;
     const int pool_lds = POOL_WAVES * NJ * 256 * 4 + POOL_WAVES * 4;
-    KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
-    hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, f.st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, f.pool.select,
-                       p.head[HEAD_DENSE] || f.pool.classify ? e->pooled : e->out, e->d_err);
+    if (tok != POOL_TOK_MEAN) {
+        const auto tok_kernel = with_pool_width(H, [&](auto nj) {
+            constexpr int N = decltype(nj)::value;
+            return tok == POOL_TOK_MAX ? (raw ? &k_pool_tok<N, true, 1> : &k_pool_tok<N, false, 1>) : (raw ? &k_pool_tok<N, true, 2> : &k_pool_tok<N, false, 2>);
+        });
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(tok_kernel), pool_lds, e->device));
+        hipLaunchKernelGGL(tok_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, f.st, r.xb, r.lo_last, r.off, r.nk, H, pool_out, e->d_err);
+    } else {
+        const auto pool_kernel = raw ? with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value, true>; })
+                                     : with_pool_width(H, [](auto nj) { return &k_pool<decltype(nj)::value>; });
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(pool_kernel), pool_lds, e->device));
+        hipLaunchKernelGGL(pool_kernel, dim3(B), dim3(POOL_WAVES * 64), pool_lds, f.st, r.xb, r.lo_last, r.off, r.nk, r.cls, H, f.pool.select, pool_out, e->d_err);
+    }
+    if (st_dense) {              // out [B, P] = act(st_dense.weight . pooled + st_dense.bias), normalised unless config.normalize_output = 0
+        const int P = p.head_dim[HEAD_ST_DENSE], dense_lds = PD_SEQ * (H + P) * 4 + PD_SEQ * 4;
+        KR_TRY(set_lds_once(reinterpret_cast<const void*>(&k_st_dense), PD_SEQ * (2048 + 2048) * 4 + PD_SEQ * 4, e->device));
+        hipLaunchKernelGGL(k_st_dense, dim3((B + PD_SEQ - 1) / PD_SEQ), dim3(256), dense_lds, f.st, e->pooled, e->hf(HEAD_ST_DENSE, 0), e->hf(HEAD_ST_DENSE, 1), B, H, P,
+                           p.st_tanh ? 1 : 0, p.normalize ? 1 : 0, r.nk, e->out, e->d_err);
+        return 0;
+    }
     if (f.pool.score) {          // a decoder handle's score head: out [B, L] = score.weight . pooled, one launch without LDS
         const int L = p.head_dim[HEAD_SCORE];
         const int64_t waves = (int64_t)B * ((L + SH_LABELS - 1) / SH_LABELS);

@@ -227,14 +227,17 @@ inline Error resolve_name(const kr_bert_cfg& cfg, const char* name, Resolved& ou
 //   HEAD_MODERN_CLS: ModernBertForSequenceClassification's, Wo . LayerNorm(erf_gelu(Wd . x + bd)) + bo of the raw CLS row or (config.classifier_pooling = 1) mean.
 //   HEAD_SCORE: the score head of Qwen2 / Llama / MistralForSequenceClassification (HF's GenericForSequenceClassification.score, a Linear without a bias;
 //   KR_POOL_CLASSIFY on a decoder handle): out [B, L] = score.weight . x of the raw row of the highest attended column, behind the final norm.
+//   HEAD_ST_DENSE: sentence-transformers' Dense module behind the pooling of ANY family (k_st_dense): out [B, P] = act(st_dense.weight . x + st_dense.bias) of the
+//   RAW pooled row x, act = config.st_dense_activation (identity / tanh), then divided by its norm unless config.normalize_output = 0.  Never next to another head.
 // HEAD_COUNT counts the heads of the encoder families — the ones the plan line of tests/capi/encoder_model_check.cpp prints, one digit each — and the decoders'
 // head follows them: the tables and per-head arrays are HEAD_ALL long.
-enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT, HEAD_SCORE = HEAD_COUNT, HEAD_ALL };
+enum Head { HEAD_MLM = 0, HEAD_COLBERT, HEAD_SPARSE, HEAD_DENSE, HEAD_CLS, HEAD_MODERN_CLS, HEAD_COUNT, HEAD_SCORE = HEAD_COUNT, HEAD_ST_DENSE, HEAD_ALL };
 enum : uint8_t { REQUIRED = 1, HALF = 2 };       // HALF: stored as the handle's 16-bit operand (a projection of the loops every layer uses), else fp32
 // workspace buffers that exist because of a head: the head's input rows [B, H]; the packed row of every [b, s] column; the sequence of every packed row; the
 // colbert product [T, P]
 enum : unsigned { WS_POOLED = 1, WS_SLOT_ROW = 2, WS_ROW_SEQ = 4, WS_CY = 8 };
 constexpr int HEAD_MAX_TENSORS = 6;
+enum { POOL_TOK_MEAN = 0, POOL_TOK_MAX = 1, POOL_TOK_SQRT_LEN = 2 };      // config.pool_tokens
 struct HeadTensor { const char* name; Ext r, c, store_r; uint8_t flags; };     // store_r: the rows it is stored with (zero rows behind r)
 struct HeadDesc {
     const char* subject;         // what a refusal calls the head's tensors (nullptr: the first one that was loaded)
@@ -275,6 +278,9 @@ static const HeadDesc HEADS[HEAD_ALL] = {
     {nullptr, "a score head (score.weight)",
      "the score head score.weight . x of the last attended token is Qwen2 / Llama / MistralForSequenceClassification's and is accepted on decoder handles (config.decoder_attention)",
      "", 1, {{"score.weight", XFREE, XH, XFREE, REQUIRED}}, 'L', 1, 64, 1, 1u << DECODER, {-1}, WS_POOLED},
+    {"st_dense.*", "a sentence-transformers Dense head (st_dense.weight)", "the sentence-transformers Dense head is accepted on every family",
+     "the sentence-transformers Dense head takes st_dense.weight, with or without st_dense.bias", 2,
+     {{"st_dense.weight", XFREE, XH, XFREE, REQUIRED}, {"st_dense.bias", XFREE, X1, XFREE, 0}}, 'P', 4, 2048, 4, ~0u, {-1}, WS_POOLED},
 };
 
 struct HeadState { int dim = 0; unsigned got = 0; };      // the free dimension (0: not known yet), one bit per tensor that was loaded
@@ -342,7 +348,14 @@ inline Error check_head_tensor(const kr_bert_cfg& cfg, int head, int idx, int64_
 //   [kv_heads d_h, hidden].  128 needs the q / k norms of every layer.  Never set: hidden / heads, and the handle is what it was without the setting.
 //   config.rotary_feed_forward: the feed-forward of a rotary post-LN handle (config.rotary_inv_freq), 0 = NomicBert's SwiGLU (also when never set),
 //   1 = fc2(gelu(fc1 x + b1)) + b2 with linear biases: a rotary BERT handle (jina-embeddings-v3).
-enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_ROTARY_FF, SET_HEAD_DIM, SET_DECODER_ATTN, SET_COUNT };
+//   The tail of a sentence-transformers pipeline (modules.json: Pooling, Dense, Normalize), on every family and never next to a head other than HEAD_ST_DENSE:
+//   config.normalize_output: 1 (also when never set) = the KR_POOL_MEAN / KR_POOL_CLS / KR_POOL_LAST row, or the Dense head's, is divided by its norm; 0 = it is
+//   written as it is (checkpoints trained for the dot product).  The norm is formed either way: a non-finite row stays KR_ERANGE.
+//   config.pool_tokens: what a KR_POOL_MEAN forward pools over the attended tokens, 0 = their mean (also when never set), 1 = the element-wise max,
+//   2 = sum / sqrt(n) (mean_sqrt_len_tokens).  A sequence without attended tokens gives NaN under all three.
+//   config.st_dense_activation: the activation of HEAD_ST_DENSE, 0 = identity (also when never set), 1 = tanh; after the first finalize it is known to handles
+//   with that head only.
+enum Setting { SET_PAD_IDX = 0, SET_ROTARY, SET_ROTARY_LOCAL, SET_HALF_WINDOW, SET_LOCAL_LAYERS, SET_T5_FF, SET_CLS_POOLING, SET_DEB_BUCKETS, SET_DEB_MAX_REL, SET_ROTARY_FF, SET_HEAD_DIM, SET_NORMALIZE_OUT, SET_POOL_TOKENS, SET_ST_ACT, SET_DECODER_ATTN, SET_COUNT };
 enum ValueRule : uint8_t { V_FINITE, V_FLAGS, V_INT };
 struct SettingRow {
     const char* name;
@@ -368,6 +381,9 @@ static const SettingRow SETTINGS[SET_COUNT] = {
     {"config.deberta_max_relative_positions", X1, V_INT, 2, 65536, "an integer M with M - 1 > position_buckets / 2", "no disentangled attention: not a DeBERTa handle", 0, -1, -1, 0},
     {"config.rotary_feed_forward", X1, V_INT, 0, 1, "0 (SwiGLU) or 1 (gelu with biases)", "NomicBert's SwiGLU", 0, 0, -1, 0},
     {"config.head_dim", X1, V_INT, 32, 128, "32, 64 or 128", "heads of hidden / heads features", 0, -1, -1, 32},
+    {"config.normalize_output", X1, V_INT, 0, 1, "0 (rows as pooled) or 1 (divided by their norm)", "normalised rows", 0, 1, -1, 0},
+    {"config.pool_tokens", X1, V_INT, 0, 2, "0 (mean), 1 (max) or 2 (sum / sqrt(n))", "the masked mean", 0, 0, -1, 0},
+    {"config.st_dense_activation", X1, V_INT, 0, 1, "0 (identity) or 1 (tanh)", "the identity", 0, 0, HEAD_ST_DENSE, 0},
     {"config.decoder_attention", X1, V_INT, 0, 1, "0 (bidirectional) or 1 (causal)", "not a decoder handle", 0, -1, -1, 0},
 };
 constexpr int64_t SETTING_MAX_VALUES = 4096;
@@ -604,6 +620,9 @@ struct ModelPlan {
     int head_w = 0, q_dim = 0;             // d_h and Dq = heads d_h, the width of q and of the context: hidden / heads and hidden unless config.head_dim says otherwise
     bool qk_norm = false;                  // every layer has self_attn.{q,k}_norm.weight: QKV_SPLIT, then k_qk_norm_rope
     int out_dim = 0, out_width = 0;        // columns of a pooled row; of the widest row `out` must hold, whatever the pool
+    bool normalize = true;                 // config.normalize_output
+    int pool_tokens = 0;                   // config.pool_tokens: POOL_TOK_*
+    bool st_tanh = false;                  // config.st_dense_activation = 1
     unsigned ws = 0;                       // WS_*
 };
 
@@ -792,6 +811,18 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
         for (int i = 0; i < d.n; ++i)
             if ((d.t[i].flags & REQUIRED) && !(s.got & (1u << i))) return err(KR_ESTATE, "'%s' was never loaded: %s", d.t[i].name, d.whole);
     }
+    // the sentence-transformers tail (its three settings, its Dense head) stands alone: never next to another head
+    for (int h = 0; h < HEAD_ALL; ++h) {
+        if (h == HEAD_ST_DENSE || !ld.heads[h].got) continue;
+        const char* other = HEADS[h].subject ? HEADS[h].subject : HEADS[h].t[0].name;
+        if (ld.heads[HEAD_ST_DENSE].got)
+            return err(KR_EINVAL, "'%s' next to '%s': a handle has %s or %s, not both", head_first(HEAD_ST_DENSE, ld.heads[HEAD_ST_DENSE]), other, HEADS[HEAD_ST_DENSE].noun, HEADS[h].noun);
+        for (const Setting st : {SET_NORMALIZE_OUT, SET_POOL_TOKENS, SET_ST_ACT})
+            if (set.has(st))
+                return err(KR_EINVAL, "%s next to '%s': the settings of a sentence-transformers pipeline are accepted on handles without %s", SETTINGS[st].name, other, HEADS[h].noun);
+    }
+    if (set.has(SET_ST_ACT) && !ld.heads[HEAD_ST_DENSE].got)
+        return err(KR_EINVAL, "config.st_dense_activation on a handle without st_dense.weight: it selects the activation of the sentence-transformers Dense head");
     if (set.has(SET_CLS_POOLING) && !(modern && ld.heads[HEAD_MODERN_CLS].got))
         return err(KR_EINVAL, "config.classifier_pooling on a %s: it selects the row ModernBert's classification head reads",
                    modern ? "ModernBert handle without head.dense / head.norm / classifier" : "handle that is no ModernBert handle");
@@ -857,6 +888,8 @@ inline Error describe(const kr_bert_cfg& cfg, const Settings& set, const Loaded&
         if (plan.head[h]) plan.ws |= HEADS[h].ws;
     }
     if (plan.head[HEAD_DENSE]) plan.out_dim = plan.head_dim[HEAD_DENSE];
+    if (plan.head[HEAD_ST_DENSE]) plan.out_dim = plan.head_dim[HEAD_ST_DENSE];
+    plan.normalize = set.value(SET_NORMALIZE_OUT, 1) != 0; plan.pool_tokens = set.value(SET_POOL_TOKENS, 0); plan.st_tanh = set.value(SET_ST_ACT, 0) == 1;
     plan.classifier = plan.head[HEAD_CLS] ? (int)HEAD_CLS : plan.head[HEAD_MODERN_CLS] ? (int)HEAD_MODERN_CLS : plan.head[HEAD_SCORE] ? (int)HEAD_SCORE : -1;
     plan.classify_mean = set.value(SET_CLS_POOLING) == 1;
     plan.out_width = plan.classifier >= 0 && plan.head_dim[plan.classifier] > plan.out_dim ? plan.head_dim[plan.classifier] : plan.out_dim;

@@ -536,6 +536,91 @@ __global__ __launch_bounds__(POOL_WAVES * 64) void k_pool(const uint16_t* __rest
     }
 }
 
+// config.pool_tokens (k_pool_tok): what a KR_POOL_MEAN forward makes of the attended tokens where it is not their mean.  k_pool's walk over all tokens, without its
+// one-row pools (KR_POOL_CLS / KR_POOL_LAST keep k_pool under every setting):  TOK = 1 the element-wise MAX — the accumulators start at -inf, wave w folds tokens
+// w, w + 16, ..., the 16 partial rows are folded in wave order; a maximum does not depend on the order, and a NaN element is kept (pool_max);  TOK = 2
+// sum / sqrt(n), the mean's sums in the mean's order, divided once.  A sequence without attended tokens is NaN under both, without an error bit, like the mean
+// of nothing.  RAW, the norm and the error word: k_pool's.
+__device__ __forceinline__ float pool_max(float acc, float v) { return (v > acc || v != v) ? v : acc; }      // a NaN arrives and stays (fmaxf would drop it)
+template <int NJ, bool RAW, int TOK>     // 256-element steps that cover a row: H <= 256 NJ
+__global__ __launch_bounds__(POOL_WAVES * 64) void k_pool_tok(const uint16_t* __restrict__ xb, const uint8_t* __restrict__ xlo, const int* __restrict__ seq_off,
+                                                             const int* __restrict__ seq_nk, int H, float* __restrict__ out, int* __restrict__ err) {
+    static_assert(TOK == 1 || TOK == 2, "the max or sum / sqrt(n); the mean is k_pool");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* part = reinterpret_cast<float*>(smem);                     // [POOL_WAVES][NJ * 256]
+    float* red = part + POOL_WAVES * NJ * 256;                        // [POOL_WAVES]
+    constexpr int HP = NJ * 256;
+    constexpr float ACC0 = TOK == 1 ? -INFINITY : 0.f;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t off = seq_off[b];
+    const int nk = seq_nk[b];
+    auto fold = [](float a, float v) { if constexpr (TOK == 1) return pool_max(a, v); else return a + v; };
+    float4 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = make_float4(ACC0, ACC0, ACC0, ACC0);
+    constexpr int PU = NJ <= 4 ? 4 : 2;       // tokens of the wave per step, all their loads issued before the first fold (k_pool)
+    for (int t = wave; t < nk; t += POOL_WAVES * PU) {
+        ushort4 hi[PU][NJ]; unsigned int lo[PU][NJ];
+#pragma unroll
+        for (int u = 0; u < PU; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int i = lane * 4 + j * 256;
+                if (i < H && t + POOL_WAVES * u < nk) {
+                    hi[u][j] = *reinterpret_cast<const ushort4*>(xb + (off + t + POOL_WAVES * u) * H + i);
+                    lo[u][j] = xlo ? *reinterpret_cast<const unsigned int*>(xlo + (off + t + POOL_WAVES * u) * H + i) : 0x80808080u;
+                }
+            }
+#pragma unroll
+        for (int u = 0; u < PU; ++u)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int i = lane * 4 + j * 256;
+                if (i < H && t + POOL_WAVES * u < nk) {
+                    acc[j].x = fold(acc[j].x, lo_decode_final(lo[u][j] & 0xffu, ET::to_f32(hi[u][j].x))); acc[j].y = fold(acc[j].y, lo_decode_final((lo[u][j] >> 8) & 0xffu, ET::to_f32(hi[u][j].y)));
+                    acc[j].z = fold(acc[j].z, lo_decode_final((lo[u][j] >> 16) & 0xffu, ET::to_f32(hi[u][j].z))); acc[j].w = fold(acc[j].w, lo_decode_final(lo[u][j] >> 24, ET::to_f32(hi[u][j].w)));
+                }
+            }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int i = lane * 4 + j * 256;
+        if (i < H) *reinterpret_cast<float4*>(&part[wave * HP + i]) = acc[j];
+    }
+    __syncthreads();
+    constexpr int VJ = (NJ * 256 + POOL_WAVES * 64 - 1) / (POOL_WAVES * 64);      // elements per thread of the pooled row
+    float v[VJ];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) {
+        const int i = tid + j * POOL_WAVES * 64;
+        v[j] = 0.f;
+        if (i < H) {
+            float s = part[i];
+#pragma unroll
+            for (int w = 1; w < POOL_WAVES; ++w) s = fold(s, part[w * HP + i]);
+            v[j] = nk <= 0 ? NAN : TOK == 1 ? s : s / sqrtf((float)nk);
+            ss += v[j] * v[j];
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    float n2 = red[0];
+#pragma unroll
+    for (int w = 1; w < POOL_WAVES; ++w) n2 += red[w];
+    const float nrm = sqrtf(n2);
+    if (tid == 0 && nk > 0 && !(nrm < INFINITY)) atomicOr(err, 2);      // a non-finite row of a sequence with attended tokens: KR_ERANGE (k_pool)
+    const float den = fmaxf(nrm, 1e-12f);   // F.normalize eps; NaN norm stays NaN (fmaxf would drop it)
+#pragma unroll
+    for (int j = 0; j < VJ; ++j) {
+        const int i = tid + j * POOL_WAVES * 64;
+        if constexpr (RAW) { if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] : NAN; }
+        else if (i < H) out[(int64_t)b * H + i] = (nrm == nrm) ? v[j] / den : NAN;
+    }
+}
+
 // T5 handles: the embedding row IS the residual stream (no embedding norm, no positions, no token types): r = shared[id] -> rb / rlo, and
 // xb = RMS(block 0's attention norm)(r).  One wave per token, the row arithmetic and the residual codec of k_ln16_pre.
 template <int NS>
@@ -617,6 +702,67 @@ __global__ __launch_bounds__(256) void k_pool_dense(const float* __restrict__ po
         const float nrm = sqrtf(red[s]);
         const float den = fmaxf(nrm, 1e-12f);           // NaN norm stays NaN (fmaxf would drop it)
         out[(int64_t)(b0 + s) * P + (i - s * P)] = (nrm == nrm) ? y[i] / den : NAN;
+    }
+}
+
+// sentence-transformers' Dense module behind the pooling of any family (HEAD_ST_DENSE: "st_dense.weight" [P, H], "st_dense.bias" [P], zero unless loaded):
+// out[b, :] = act(W . x_b + bias) of k_pool's RAW rows x [B, H] (k_pool<NJ, true> / k_pool_tok<NJ, true, TOK>), act = tanhf or the identity, then divided by its
+// norm (F.normalize's 1e-12 floor) unless the handle has config.normalize_output = 0; fp32 throughout.  k_pool_dense's layout and summation order: PD_SEQ
+// sequences per block with their rows in LDS, wave w computes features w, w + 4, ... from ONE read of the W row, a lane's partial sums are added in column
+// order and folded by a shuffle butterfly — a row does not depend on its batch.  A NaN pooled row stays NaN; a non-finite output of a sequence WITH attended
+// tokens sets bit 1 of the error word (the norm is formed either way).
+__global__ __launch_bounds__(256) void k_st_dense(const float* __restrict__ pooled, const float* __restrict__ W, const float* __restrict__ bias, int B, int H, int P, int act_tanh,
+                                                  int normalize, const int* __restrict__ seq_nk, float* __restrict__ out, int* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* p = reinterpret_cast<float*>(smem);          // [PD_SEQ][H]
+    float* y = p + PD_SEQ * H;                          // [PD_SEQ][P]
+    float* red = y + PD_SEQ * P;                        // [PD_SEQ]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * PD_SEQ;
+    for (int i = tid; i < PD_SEQ * H; i += 256) {
+        const int s = i / H;
+        p[i] = b0 + s < B ? pooled[(int64_t)(b0 + s) * H + (i - s * H)] : 0.f;
+    }
+    __syncthreads();
+    for (int f = wave; f < P; f += 4) {
+        float acc[PD_SEQ];
+#pragma unroll
+        for (int s = 0; s < PD_SEQ; ++s) acc[s] = 0.f;
+        for (int i = lane * 4; i < H; i += 256) {
+            const float4 w = *reinterpret_cast<const float4*>(W + (int64_t)f * H + i);
+#pragma unroll
+            for (int s = 0; s < PD_SEQ; ++s) {
+                const float4 x = *reinterpret_cast<const float4*>(p + s * H + i);
+                acc[s] += (w.x * x.x + w.y * x.y) + (w.z * x.z + w.w * x.w);
+            }
+        }
+        const float bf = bias[f];
+#pragma unroll
+        for (int s = 0; s < PD_SEQ; ++s) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) acc[s] += __shfl_xor(acc[s], m, 64);
+            if (lane == 0) y[s * P + f] = act_tanh ? tanhf(acc[s] + bf) : acc[s] + bf;
+        }
+    }
+    __syncthreads();
+    // |y_s|^2: wave w sums sequence w's features (lane-strided, then across the wave): one fixed order per row
+    {
+        float ss = 0.f;
+        for (int f = lane; f < P; f += 64) ss += y[wave * P + f] * y[wave * P + f];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+        if (lane == 0) {
+            red[wave] = ss;
+            if (b0 + wave < B && seq_nk[b0 + wave] > 0 && !(sqrtf(ss) < INFINITY)) atomicOr(err, 2);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < PD_SEQ * P; i += 256) {
+        const int s = i / P;
+        if (b0 + s >= B) continue;
+        const float nrm = sqrtf(red[s]);
+        const float den = fmaxf(nrm, 1e-12f);           // NaN norm stays NaN (fmaxf would drop it)
+        out[(int64_t)(b0 + s) * P + (i - s * P)] = !normalize ? y[i] : (nrm == nrm) ? y[i] / den : NAN;
     }
 }
 

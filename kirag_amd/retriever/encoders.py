@@ -31,7 +31,7 @@ from typing import Callable, Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor
-from transformers import (BertModel, DebertaV2Model, EuroBertModel, JinaEmbeddingsV3Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel,
+from transformers import (BertModel, DebertaV2Model, DistilBertModel, EuroBertModel, JinaEmbeddingsV3Model, LlamaModel, MistralModel, ModernBertModel, MPNetModel, NomicBertModel,
                           PretrainedConfig, Qwen2Model, Qwen3Model, T5EncoderModel, XLMRobertaModel)
 
 from .. import _lib
@@ -89,6 +89,19 @@ DECODER_POOLINGS = {"mean": POOL_MEAN, "last": _lib.POOL_LAST}
 ST_POOLING_DIR = "1_Pooling"
 ST_DENSE_TYPE = "sentence_transformers.models.Dense"
 ST_IDENTITY = "torch.nn.modules.linear.Identity"
+ST_MODULE = "sentence_transformers.models."      # modules.json: the prefix of every module type
+ST_TANH = "torch.nn.modules.activation.Tanh"
+ST_ACTIVATIONS = {ST_IDENTITY: "identity", ST_TANH: "tanh"}
+# the tail of a sentence-transformers pipeline on a handle (include/kirag_amd.h): three reserved settings and the Dense head's two tensors
+ST_NORMALIZE_SETTING, ST_POOL_TOKENS_SETTING, ST_DENSE_ACT_SETTING = "config.normalize_output", "config.pool_tokens", "config.st_dense_activation"
+ST_DENSE_WEIGHT, ST_DENSE_BIAS = "st_dense.weight", "st_dense.bias"
+ST_DENSE_MIN, ST_DENSE_MAX, ST_DENSE_STEP = 4, 2048, 4       # the library's rule for out_features
+# 1_Pooling/config.json: key -> the pooling; what a KR_POOL_MEAN forward pools under each (config.pool_tokens)
+ST_POOLING_KEYS = {"pooling_mode_cls_token": "cls", "pooling_mode_mean_tokens": "mean", "pooling_mode_max_tokens": "max",
+                   "pooling_mode_mean_sqrt_len_tokens": "mean_sqrt_len", "pooling_mode_lasttoken": "last"}
+ST_POOL_TOKENS = {"mean": 0, "max": 1, "mean_sqrt_len": 2}
+DISTILBERT_TYPE = "distilbert"
+DISTILBERT_EPS = 1e-12   # every LayerNorm of HF's DistilBertModel is built with eps=1e-12; the config has no field for it
 MPNET_BUCKETS = 32       # MPNetEncoder.relative_position_bucket is always called with its defaults (32 buckets, max_distance 128)
 
 
@@ -371,6 +384,25 @@ def read_st_pooling(where, **kwargs) -> Optional[str]:
     return known[on[0]]
 
 
+def st_pool(last_hidden_states: Tensor, attention_mask: Tensor, pooling: str) -> Tensor:
+    """sentence-transformers' ``Pooling`` in torch, one mode: "cls" = column 0, "last" = the highest attended column, "mean" = the masked mean (``average_pool``),
+    "max" = the element-wise max over the attended tokens, "mean_sqrt_len" = their sum / sqrt(n)"""
+    if pooling == "cls":
+        return last_hidden_states[:, 0]
+    if pooling == "last":
+        cols = torch.arange(attention_mask.shape[1], device=attention_mask.device)
+        last = ((attention_mask != 0) * (cols + 1)).argmax(dim=1)
+        return last_hidden_states[torch.arange(last_hidden_states.shape[0], device=last.device), last]
+    if pooling == "mean":
+        return average_pool(last_hidden_states, attention_mask)
+    keep = attention_mask[..., None].bool()
+    if pooling == "max":
+        return last_hidden_states.masked_fill(~keep, float("-inf")).max(dim=1).values
+    if pooling == "mean_sqrt_len":
+        return last_hidden_states.masked_fill(~keep, 0.0).sum(dim=1) / attention_mask.sum(dim=1)[..., None].to(last_hidden_states.dtype).sqrt()
+    raise ValueError(f"pooling={pooling!r}: one of {sorted(ST_POOLING_KEYS.values())}")
+
+
 def _setting(value) -> Tensor:
     """one number as the fp32 host tensor a reserved-name setting travels as"""
     return torch.tensor([float(value)], dtype=torch.float32)
@@ -399,6 +431,7 @@ class Family:
     flag: Optional[str] = None                   # the ``is_*`` attribute of its handles
     check: Optional[Callable] = None             # config or config.json dict -> refusal from the config alone, run by the dispatch before a weight is read
     decoder_attention: Optional[float] = None    # decoders: the family's own mask setting (EuroBERT: 0.0), None = the handle's default
+    zero_type_row: bool = False                  # a family without a flag of its own whose handle needs a zero token-type row (DistilBERT on a BERT handle)
 
     def twin(self, pool: int):
         """the E5 twin for a mean-pooling registry class, the BGE twin for any other"""
@@ -508,7 +541,7 @@ class HipBertForward:
     FLAGS = ("is_nomic", "is_modern", "is_t5", "is_deberta", "is_decoder", "is_jina3", "is_mpnet")
 
     def __init__(self, config, device_index: int, operand_dtype: Optional[str] = None, residual_lo: Optional[bool] = None, rename=None, extra=None,
-                 decoder_attention: Optional[float] = None):
+                 decoder_attention: Optional[float] = None, pipeline_settings: tuple = ()):
         """``operand_dtype``: "f16" / "bf16" = 16-bit type of the MFMA operands and stored activations, ``residual_lo``: keep the residual stream's
         low half; ``None`` = the library default (f16 + low half; environment ``KIRAG_AMD_ENCODER_DTYPE`` / ``KIRAG_AMD_RESIDUAL_LO`` override it).
         ``rename``: optional callable, parameter name of the module -> the name the library knows (``sync`` / ``load_state`` apply it to every name; a
@@ -516,7 +549,8 @@ class HipBertForward:
         ``extra``: optional callable, module -> [(library name, tensor)] that ``sync`` sends besides ``named_parameters()`` unless a parameter already has
         that name (a TIED parameter appears once in ``named_parameters()``; the library wants it under both names: ``kirag_amd.retriever.splade``).
         ``decoder_attention``: 1.0 / 0.0 = the causal / bidirectional mask of a decoder handle; ``None`` = the family's (bidirectional for ``model_type``
-        eurobert: HF's EuroBertModel has no causal mask), else ``DECODER_ATTENTION``."""
+        eurobert: HF's EuroBertModel has no causal mask), else ``DECODER_ATTENTION``.
+        ``pipeline_settings``: ((reserved name, fp32 host tensor), ...) of a sentence-transformers tail (``StPipeline.settings``), sent with the family's own."""
         lib = _lib.load()
         self.rename = rename
         self.extra = extra
@@ -525,7 +559,8 @@ class HipBertForward:
         family = family_of(getattr(config, "model_type", "bert"))
         spec = family.describe(config)    # refuses what the kernels do not compute, before a handle exists
         self.__dict__.update({flag: flag == family.flag for flag in self.FLAGS})
-        settings = list(spec.settings)
+        self._zero_type_row = family.zero_type_row      # a BERT handle of a checkpoint without token types (DistilBERT): one row of zeros stands in for the table
+        settings = list(spec.settings) + list(pipeline_settings)
         self.decoder_attention = None
         if self.is_decoder:               # the setting that makes a handle a decoder's, after HF's own frequencies
             mask = decoder_attention if decoder_attention is not None else family.decoder_attention if family.decoder_attention is not None else self.DECODER_ATTENTION
@@ -676,7 +711,7 @@ class HipBertForward:
     def _note_dense(self, name: str, numel: int) -> None:
         """``dense.weight`` [P, hidden] was accepted by the library: the forwards now write [B, P]; ``classifier.out_proj.weight`` [L, hidden]: a
         ``POOL_CLASSIFY`` forward writes [B, L] (``classifier.weight`` on a ModernBert handle)"""
-        if name == "dense.weight":
+        if name == "dense.weight" or name == ST_DENSE_WEIGHT:
             self.out_dim = int(numel) // self.hidden
         elif name == CLASSIFIER_OUT or (self.is_modern and name == MODERN_CLASSIFIER_OUT) or (self.is_decoder and name == SCORE_WEIGHT):
             self.num_labels = int(numel) // self.hidden
@@ -726,7 +761,7 @@ class HipBertForward:
         return dense, sparse, colbert
 
     def _load_zero_token_types(self) -> None:
-        if self.is_mpnet or self.is_modern:      # no token types in the checkpoint: one row of zeros stands in for the table
+        if self.is_mpnet or self.is_modern or getattr(self, "_zero_type_row", False):      # no token types in the checkpoint: one row of zeros stands in for the table
             z = torch.zeros(self.hidden, dtype=torch.float32)
             _lib.check(self._lib.kr_encoder_load_weight(self._h, b"embeddings.token_type_embeddings.weight", z.data_ptr(), z.numel()))
 
@@ -862,8 +897,10 @@ class _HipModuleMixin:
                 f"{type(self).__name__} in eval mode runs on the MI355X HIP path only; its parameters are on {p.device}. "
                 "Move the model to a GPU (kirag_amd has no CPU fallback).")
         idx = p.device.index if p.device.index is not None else torch.cuda.current_device()
-        if self._hip is None or self._hip.device_index != idx:
-            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename, extra=type(self)._hip_extra, decoder_attention=getattr(self, "_decoder_attention", None))
+        if self._hip is None or self._hip.device_index != idx:      # (set_pipeline / set_pooling drop the handle: its settings are fixed at the first finalize)
+            st = getattr(self, "_st", None)
+            self._hip = HipBertForward(self.config, idx, rename=type(self)._hip_rename, extra=type(self)._hip_extra, decoder_attention=getattr(self, "_decoder_attention", None),
+                                       pipeline_settings=st.settings() if st is not None else ())
         self._hip.sync(self)
         return self._hip
 
@@ -906,11 +943,81 @@ class _HipSentenceMixin(_HipModuleMixin):
     """Everything the sentence encoders add to their HF base class (``_hf_base``: ``BertModel``, ``XLMRobertaModel`` or ``MPNetModel``, the next class in the MRO): the HIP
     eval forward, weight sync, ``forward_packed``, the train / eval switch and the pooled autograd forward of ``train()`` mode."""
     _hf_base = None
+    _st = None                               # (an StPipeline) the tail a checkpoint's modules.json states (``pipeline="checkpoint"``); None = the class's own: its pool, then L2 normalise
+    ST_DENSE_DIR = "2_Dense"
 
     def __init__(self, config, add_pooling_layer=True, **kwargs):
         super().__init__(config, add_pooling_layer)
         self.kwargs = kwargs
         self._hip: Optional[HipBertForward] = None
+
+    # ---- the tail of a sentence-transformers pipeline (``StPipeline``): pooling, an optional Dense, Normalize or not ----
+    def set_pipeline(self, pipe: Optional["StPipeline"]) -> None:
+        """Install (or, with ``None``, remove) the tail ``pipe``: the instance's pool, its Dense head as the submodule ``st_dense`` — a parameter like any other: the
+        weight sync sends it as ``st_dense.weight`` / ``st_dense.bias``, ``train()`` mode applies it in torch — and whether rows are normalised.  The handle is
+        rebuilt at the next eval forward: settings and the output width are fixed at a handle's first finalize."""
+        if getattr(self, "st_dense", None) is not None:
+            del self.st_dense
+        if pipe is None:
+            self.__dict__.pop("_st", None)
+            self.__dict__.pop("_pool", None)
+        else:
+            if pipe.pooling == "last" and not family_of(self.config.model_type).flag == "is_decoder":
+                raise NotImplementedError(f"pooling 'last' on model_type={self.config.model_type!r}: last-token pooling runs on decoder handles only")
+            if pipe.dense_weight is not None:
+                P, H = pipe.dense_weight.shape
+                p = next(self.parameters())
+                self.st_dense = torch.nn.Linear(H, P, bias=pipe.dense_bias is not None, device=p.device, dtype=p.dtype)
+                with torch.no_grad():
+                    self.st_dense.weight.copy_(pipe.dense_weight)
+                    if pipe.dense_bias is not None:
+                        self.st_dense.bias.copy_(pipe.dense_bias)
+            self._st = StPipeline(pipe.pooling, None, None, pipe.activation, pipe.normalize)      # the weights live in st_dense from here on
+            self._pool = POOL_CLS if pipe.pooling == "cls" else POOL_LAST if pipe.pooling == "last" else POOL_MEAN
+        self._hip = None
+
+    def _st_tail(self, last_hidden_states: Tensor, attention_mask: Tensor) -> Tensor:
+        """``self._st`` in torch on HF's last_hidden_state (``train()`` mode): what the library computes behind the last layer"""
+        emb = st_pool(last_hidden_states, attention_mask, self._st.pooling)
+        dense = getattr(self, "st_dense", None)
+        if dense is not None:
+            emb = dense(emb)
+            if self._st.activation == "tanh":
+                emb = torch.tanh(emb)
+        return F.normalize(emb, p=2, dim=1) if self._st.normalize else emb
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        """``pipeline="checkpoint"``: the registry class only selects the family twin; pooling, Dense and normalisation are what the folder's ``modules.json``
+        states (``read_st_pipeline``; a folder without one behaves as if the kwarg were absent).  Absent: the class's own tail, as ever."""
+        pipeline = kwargs.pop("pipeline", None)
+        if not (pipeline in (None, "checkpoint") or isinstance(pipeline, StPipeline)):
+            raise ValueError(f"pipeline={pipeline!r}: 'checkpoint' (the folder's modules.json decides the tail) or None")
+        pipe = pipeline if isinstance(pipeline, StPipeline) else None      # (an StPipeline: a twin that has parsed the folder already hands it on)
+        if pipeline == "checkpoint":
+            model_type, config = checkpoint_model_type(pretrained_model_name_or_path, kwargs)
+            pipe = read_st_pipeline(pretrained_model_name_or_path, _config_hidden(config), model_type=model_type, **kwargs)      # refuses before a weight of the model is read
+        model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
+        if pipe is not None:
+            model.set_pipeline(pipe)
+        return model
+
+    def save_pretrained(self, save_directory, *args, **kwargs):
+        """With a tail from a checkpoint (``set_pipeline``): the HF files hold the base model's state dict and nothing else; ``modules.json``,
+        ``1_Pooling/config.json``, ``2_Dense/`` and the Normalize entry (or not) are written back so that a reload with ``pipeline="checkpoint"`` gives the same
+        embeddings."""
+        if "_st" not in self.__dict__:
+            return super().save_pretrained(save_directory, *args, **kwargs)
+        dense = getattr(self, "st_dense", None)
+        if dense is not None:
+            del self.st_dense
+        try:
+            out = super().save_pretrained(save_directory, *args, **kwargs)
+        finally:
+            if dense is not None:
+                self.st_dense = dense
+        write_st_pipeline(save_directory, self._st, int(self.config.hidden_size), dense, self.ST_DENSE_DIR)
+        return out
 
     def forward_packed(self, token_ids: Tensor, seq_lens: Tensor, max_len: int, total_tokens: Optional[int] = None) -> Tensor:
         """Sentence embeddings [B, hidden] from the ragged token list of a right-padded batch (int32 attended ids back to back + int32 lengths; see
@@ -929,10 +1036,10 @@ class _HipSentenceMixin(_HipModuleMixin):
         if not self.training:
             return self._hip_forward(input_ids, attention_mask, token_type_ids)
         last_hidden_states = self._torch_pooled(input_ids, attention_mask, token_type_ids)
+        if self._st is not None:
+            return self._st_tail(last_hidden_states, attention_mask)
         if self._pool == POOL_LAST:      # the row of the highest attended column
-            cols = torch.arange(attention_mask.shape[1], device=attention_mask.device)
-            last = ((attention_mask != 0) * (cols + 1)).argmax(dim=1)
-            embeddings = last_hidden_states[torch.arange(last_hidden_states.shape[0], device=last.device), last]
+            embeddings = st_pool(last_hidden_states, attention_mask, "last")
         else:
             embeddings = average_pool(last_hidden_states, attention_mask) if self._pool == POOL_MEAN else last_hidden_states[:, 0]
         if getattr(self, "dense", None) is not None:         # the sentence-transformers Dense head of a T5 checkpoint
@@ -944,6 +1051,8 @@ class _HipSentenceMixin(_HipModuleMixin):
     def embedding_size(self) -> int:
         """width of the embeddings ``forward`` returns: ``out_features`` of the Dense head where the checkpoint has one, else ``config.hidden_size``"""
         dense = getattr(self, "dense", None)
+        if dense is None:
+            dense = getattr(self, "st_dense", None)
         return int(dense.out_features) if dense is not None else int(self.config.hidden_size)
 
     def hip_last_hidden_state(self, B: int, S: int) -> Tensor:
@@ -965,6 +1074,12 @@ def checkpoint_model_type(pretrained_model_name_or_path, kwargs: dict, default: 
     where = config if isinstance(config, (str, bytes)) or hasattr(config, "__fspath__") else pretrained_model_name_or_path
     cfg_dict, _ = PretrainedConfig.get_config_dict(where, **{k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs})
     return cfg_dict.get("model_type", default), cfg_dict
+
+
+def _config_hidden(config) -> int:
+    """the width of last_hidden_state from a config object or the dict of a ``config.json``, under whichever name the family spells it"""
+    get = (lambda k: config.get(k)) if isinstance(config, dict) else (lambda k: getattr(config, k, None))
+    return int(get("hidden_size") or get("d_model") or get("dim"))
 
 
 class _HipSentenceEncoder(_HipSentenceMixin, BertModel):
@@ -1025,12 +1140,76 @@ class _HipDebertaSentenceEncoder(_HipSentenceMixin, DebertaV2Model):
         self._hip = None
 
 
+# DistilBertModel's state-dict names -> BERT's, the names the handle knows (the mapping lives here, not in the library's name table: a DistilBERT handle IS a
+# BERT handle, created without token types)
+_DISTILBERT_BLOCKS = (("attention.q_lin.", "attention.self.query."), ("attention.k_lin.", "attention.self.key."), ("attention.v_lin.", "attention.self.value."),
+                      ("attention.out_lin.", "attention.output.dense."), ("sa_layer_norm.", "attention.output.LayerNorm."), ("ffn.lin1.", "intermediate.dense."),
+                      ("ffn.lin2.", "output.dense."), ("output_layer_norm.", "output.LayerNorm."))
+
+
+def distilbert_rename(name: str) -> str:
+    """a ``DistilBertModel`` parameter name as the library knows it: ``transformer.layer.N.<block>`` -> ``encoder.layer.N.<BERT's block>``; ``embeddings.*`` and
+    the tail's ``st_dense.*`` pass as they are.  Anything else is a ``KeyError``: nothing is dropped silently."""
+    if name.startswith("embeddings.") or name.startswith("st_dense."):
+        return name
+    if name.startswith("transformer.layer."):
+        n, _, rest = name[len("transformer.layer."):].partition(".")
+        for theirs, ours in _DISTILBERT_BLOCKS:
+            if rest.startswith(theirs):
+                return f"encoder.layer.{n}.{ours}{rest[len(theirs):]}"
+    raise KeyError(f"{name!r} is no parameter of a DistilBertModel")
+
+
+def check_distilbert_config(config) -> None:
+    """``NotImplementedError`` beginning ``model_type='distilbert':`` and naming the field, for what the kernels do not compute — from the config alone: no weight
+    has been read and the library is not loaded.  ``config``: a ``DistilBertConfig`` or the dict of a ``config.json`` (HF's defaults fill the rest)."""
+    refuse = _refuser(DISTILBERT_TYPE)
+    get = (lambda k, d: config.get(k, d)) if isinstance(config, dict) else (lambda k, d: getattr(config, k, d))
+    if get("activation", "gelu") != "gelu":
+        refuse(f"activation={get('activation', None)!r}: the HIP encoder implements erf-GELU only")
+    H, heads, ff = int(get("dim", 768)), int(get("n_heads", 12)), int(get("hidden_dim", 3072))
+    if H % 128 or not 0 < H <= 2048:
+        refuse(f"dim={H}: the HIP encoder takes a multiple of 128 up to 2048")
+    if heads <= 0 or H % heads or H // heads not in (32, 64):
+        refuse(f"n_heads={heads} with dim={H}: the attention kernels are built for heads of width 32 and 64")
+    check_ff(refuse, ff, "hidden_dim")
+
+
+def describe_distilbert(config) -> HandleSpec:
+    check_distilbert_config(config)
+    ff = int(config.hidden_dim)
+    return HandleSpec((int(config.dim), int(config.n_layers), int(config.n_heads), ff, int(config.vocab_size), int(config.max_position_embeddings), 1, DISTILBERT_EPS), ff, ff)
+
+
+class _HipDistilBertSentenceEncoder(_HipSentenceMixin, DistilBertModel):
+    _hf_base = DistilBertModel
+    _hip_rename = staticmethod(distilbert_rename)
+
+    def __init__(self, config, add_pooling_layer=False, **kwargs):
+        check_distilbert_config(config)             # refuses what the kernels do not compute when the model is made, not at its first forward
+        DistilBertModel.__init__(self, config)      # DistilBertModel has no pooling layer to ask for
+        self.kwargs = kwargs
+        self._hip = None
+
+
 def _st_file(where, name: str, kwargs: dict) -> Optional[str]:
     """path of file ``name`` of the checkpoint ``where`` (a folder, or a hub id through transformers' cache), ``None`` when it has none"""
     from transformers.utils import cached_file
     loc = {k: kwargs[k] for k in _CONFIG_KWARGS if k in kwargs and k != "trust_remote_code"}
     return cached_file(where, name, _raise_exceptions_for_missing_entries=False, _raise_exceptions_for_gated_repo=False,
                        _raise_exceptions_for_connection_errors=False, **loc)
+
+
+def _read_dense_state(where, sub: str, kwargs: dict) -> dict:
+    """the state dict of the Dense module in sub-folder ``sub`` (``linear.weight``, with a bias ``linear.bias``): ``model.safetensors``, else ``pytorch_model.bin``"""
+    st = _st_file(where, f"{sub}/model.safetensors", kwargs)
+    if st is not None:
+        from safetensors.torch import load_file
+        return load_file(st)
+    pt = _st_file(where, f"{sub}/pytorch_model.bin", kwargs)
+    if pt is None:
+        raise FileNotFoundError(f"the Dense module {sub!r} has neither model.safetensors nor pytorch_model.bin")
+    return torch.load(pt, map_location="cpu", weights_only=True)
 
 
 def read_st_dense(where, d_model: int, **kwargs) -> Optional[Tensor]:
@@ -1058,19 +1237,137 @@ def read_st_dense(where, d_model: int, **kwargs) -> Optional[Tensor]:
         raise NotImplementedError("Dense bias=True: a head without a bias is implemented")
     if dc.get("activation_function", ST_IDENTITY) != ST_IDENTITY:
         raise NotImplementedError(f"Dense activation_function={dc.get('activation_function')!r}: the identity is implemented")
-    st = _st_file(where, f"{sub}/model.safetensors", kwargs)
-    if st is not None:
-        from safetensors.torch import load_file
-        state = load_file(st)
-    else:
-        pt = _st_file(where, f"{sub}/pytorch_model.bin", kwargs)
-        if pt is None:
-            raise FileNotFoundError(f"the Dense module {sub!r} has neither model.safetensors nor pytorch_model.bin")
-        state = torch.load(pt, map_location="cpu", weights_only=True)
-    w = state["linear.weight"].float()
+    w = _read_dense_state(where, sub, kwargs)["linear.weight"].float()
     if w.dim() != 2 or w.shape[1] != d_model or w.shape[0] != dc.get("out_features", w.shape[0]):
         raise ValueError(f"Dense linear.weight has shape {tuple(w.shape)}, its config says [{dc.get('out_features')}, {d_model}]")
     return w
+
+
+@dataclass(frozen=True)
+class StPipeline:
+    """The tail of a sentence-transformers pipeline: what follows the transformer in ``modules.json``"""
+    pooling: str                                 # "cls" / "mean" / "max" / "mean_sqrt_len" / "last"
+    dense_weight: Optional[Tensor] = None        # [P, hidden] of the Dense module, None without one
+    dense_bias: Optional[Tensor] = None          # [P], None for a Dense without a bias
+    activation: str = "identity"                 # "identity" / "tanh"
+    normalize: bool = True                       # a Normalize module closes the pipeline
+
+    def settings(self) -> tuple:
+        """((reserved name, fp32 host tensor), ...): what differs from a handle's defaults, in the library's order"""
+        out = []
+        if not self.normalize:
+            out.append((ST_NORMALIZE_SETTING, _setting(0)))
+        if ST_POOL_TOKENS.get(self.pooling, 0):
+            out.append((ST_POOL_TOKENS_SETTING, _setting(ST_POOL_TOKENS[self.pooling])))
+        if self.activation == "tanh":
+            out.append((ST_DENSE_ACT_SETTING, _setting(1)))
+        return tuple(out)
+
+
+def _st_json(where, name: str, kwargs: dict, what: str) -> dict:
+    path = _st_file(where, name, kwargs)
+    if path is None:
+        raise FileNotFoundError(f"modules.json lists {what}, which has no {name}")
+    with open(path) as f:
+        return json.load(f)
+
+
+def read_st_pipeline(where, hidden: int, **kwargs) -> Optional[StPipeline]:
+    """The tail the checkpoint's ``modules.json`` states — which pooling (``1_Pooling/config.json``), whether a ``Dense`` follows and with what bias and
+    activation (its ``config.json`` + ``linear.weight`` / ``linear.bias`` from ``model.safetensors`` or ``pytorch_model.bin``), whether a ``Normalize`` closes it —
+    or ``None`` for a folder without ``modules.json``.  What the library does not compute is a ``NotImplementedError`` naming the field, raised before a weight
+    is read.  ``model_type`` (kwarg; else the checkpoint's ``config.json``) decides whether ``last`` is available.  Needs no ``sentence_transformers``: the files are
+    read as they are, and what their keys mean is recalled from that package, not checked against it."""
+    model_type = kwargs.pop("model_type", None)
+    listing = _st_file(where, "modules.json", kwargs)
+    if listing is None:
+        return None
+    if model_type is None:
+        model_type = checkpoint_model_type(where, kwargs)[0]
+    with open(listing) as f:
+        modules = sorted(json.load(f), key=lambda m: m.get("idx", 0))
+    kinds = [str(m.get("type", "")) for m in modules]
+    short = [k[len(ST_MODULE):] if k.startswith(ST_MODULE) else k for k in kinds]
+    for k in short:
+        if k not in ("Transformer", "Pooling", "Dense", "Normalize"):
+            raise NotImplementedError(f"modules.json lists a module of type {k!r}: Transformer, Pooling, Dense and Normalize are implemented")
+    if short[:1] != ["Transformer"] or short.count("Transformer") != 1:
+        raise NotImplementedError(f"modules.json lists the modules {short!r}: one Transformer, in front, is implemented")
+    if short.count("Pooling") != 1 or short[1] != "Pooling":
+        raise NotImplementedError(f"modules.json lists the modules {short!r}: exactly one Pooling module, behind the Transformer, is implemented")
+    if short.count("Dense") > 1:
+        raise NotImplementedError(f"modules.json lists {short.count('Dense')} Dense modules: a second Dense is not implemented")
+    if short.count("Normalize") > 1:
+        raise NotImplementedError(f"modules.json lists {short.count('Normalize')} Normalize modules: one is implemented")
+    if "Normalize" in short and "Dense" in short and short.index("Normalize") < short.index("Dense"):
+        raise NotImplementedError("modules.json lists Normalize in front of the Dense module: the Dense head reads the pooled row as it is")
+    pc = _st_json(where, f"{modules[1].get('path', ST_POOLING_DIR)}/config.json", kwargs, "a Pooling module")
+    on = sorted(k for k, v in pc.items() if k.startswith("pooling_mode_") and v is True)
+    if "pooling_mode_weightedmean_tokens" in on:
+        raise NotImplementedError("pooling_mode_weightedmean_tokens=true: the position-weighted mean is not implemented")
+    if len(on) != 1:
+        raise NotImplementedError(f"the Pooling module switches on {on!r}: exactly one pooling mode is implemented (sentence-transformers would concatenate them)")
+    if on[0] not in ST_POOLING_KEYS:
+        raise NotImplementedError(f"{on[0]}=true: one of {sorted(ST_POOLING_KEYS)} is implemented")
+    if pc.get("include_prompt", True) is False:
+        raise NotImplementedError("include_prompt=false: leaving the prompt's tokens out of the pooling is not implemented")
+    pooling = ST_POOLING_KEYS[on[0]]
+    if pooling == "last" and family_of(model_type).flag != "is_decoder":
+        raise NotImplementedError(f"pooling_mode_lasttoken=true on model_type={model_type!r}: last-token pooling runs on decoder handles only")
+    normalize = "Normalize" in short
+    if "Dense" not in short:
+        return StPipeline(pooling, normalize=normalize)
+    sub = modules[short.index("Dense")]["path"]
+    dc = _st_json(where, f"{sub}/config.json", kwargs, f"the Dense module {sub!r}")
+    if dc.get("in_features") != hidden:
+        raise NotImplementedError(f"Dense in_features={dc.get('in_features')}: the head must read the pooled hidden size {hidden}")
+    P = dc.get("out_features")
+    if not isinstance(P, int) or P % ST_DENSE_STEP or not ST_DENSE_MIN <= P <= ST_DENSE_MAX:
+        raise NotImplementedError(f"Dense out_features={P}: the library takes a multiple of {ST_DENSE_STEP} with {ST_DENSE_MIN} <= out_features <= {ST_DENSE_MAX}")
+    act = dc.get("activation_function", ST_TANH)      # (the module's own default is Tanh)
+    if act not in ST_ACTIVATIONS:
+        raise NotImplementedError(f"Dense activation_function={act!r}: {sorted(ST_ACTIVATIONS)} are implemented")
+    has_bias = bool(dc.get("bias", True))
+    state = _read_dense_state(where, sub, kwargs)
+    w = state["linear.weight"].float()
+    if tuple(w.shape) != (P, hidden):
+        raise ValueError(f"Dense linear.weight has shape {tuple(w.shape)}, its config says [{P}, {hidden}]")
+    b = None
+    if has_bias:
+        if "linear.bias" not in state:
+            raise ValueError(f"the Dense module {sub!r} says bias=true and holds no linear.bias")
+        b = state["linear.bias"].float()
+        if tuple(b.shape) != (P,):
+            raise ValueError(f"Dense linear.bias has shape {tuple(b.shape)}, its config says [{P}]")
+    return StPipeline(pooling, w, b, ST_ACTIVATIONS[act], normalize)
+
+
+def write_st_pipeline(save_directory, pipe: StPipeline, hidden: int, dense=None, dense_dir: str = "2_Dense") -> None:
+    """``modules.json``, ``1_Pooling/config.json``, with ``dense`` (a ``torch.nn.Linear``) ``<dense_dir>/config.json`` + ``model.safetensors``, and the Normalize
+    entry where ``pipe.normalize``: the files ``read_st_pipeline`` reads back"""
+    os.makedirs(os.path.join(save_directory, ST_POOLING_DIR), exist_ok=True)
+    pool = {"word_embedding_dimension": hidden, **{k: v == pipe.pooling for k, v in ST_POOLING_KEYS.items()}, "pooling_mode_weightedmean_tokens": False,
+            "include_prompt": True}
+    with open(os.path.join(save_directory, ST_POOLING_DIR, "config.json"), "w") as f:
+        json.dump(pool, f, indent=2)
+    modules = [{"idx": 0, "name": "0", "path": "", "type": ST_MODULE + "Transformer"}, {"idx": 1, "name": "1", "path": ST_POOLING_DIR, "type": ST_MODULE + "Pooling"}]
+    if dense is not None:
+        from safetensors.torch import save_file
+        os.makedirs(os.path.join(save_directory, dense_dir), exist_ok=True)
+        P, H = dense.weight.shape
+        act = {v: k for k, v in ST_ACTIVATIONS.items()}[pipe.activation]
+        with open(os.path.join(save_directory, dense_dir, "config.json"), "w") as f:
+            json.dump({"in_features": H, "out_features": P, "bias": dense.bias is not None, "activation_function": act}, f, indent=2)
+        state = {"linear.weight": dense.weight.detach().float().cpu().contiguous()}
+        if dense.bias is not None:
+            state["linear.bias"] = dense.bias.detach().float().cpu().contiguous()
+        save_file(state, os.path.join(save_directory, dense_dir, "model.safetensors"))
+        modules.append({"idx": len(modules), "name": str(len(modules)), "path": dense_dir, "type": ST_DENSE_TYPE})
+    if pipe.normalize:
+        n = len(modules)
+        modules.append({"idx": n, "name": str(n), "path": f"{n}_Normalize", "type": ST_MODULE + "Normalize"})
+    with open(os.path.join(save_directory, "modules.json"), "w") as f:
+        json.dump(modules, f, indent=2)
 
 
 class _HipT5SentenceEncoder(_HipSentenceMixin, T5EncoderModel):
@@ -1103,6 +1400,14 @@ class _HipT5SentenceEncoder(_HipSentenceMixin, T5EncoderModel):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
+        if kwargs.get("pipeline") == "checkpoint":
+            # a tail the class's own path computes (its pool -> a bias-free identity Dense -> Normalize) keeps that path, dense.weight, bit for bit
+            loc = {k: v for k, v in kwargs.items() if k in _CONFIG_KWARGS}
+            pipe = read_st_pipeline(pretrained_model_name_or_path, _config_hidden(checkpoint_model_type(pretrained_model_name_or_path, kwargs)[1]), model_type=T5_TYPE, **loc)
+            own = pipe is not None and pipe.normalize and pipe.dense_bias is None and pipe.activation == "identity" and pipe.pooling == ("mean" if cls._pool == POOL_MEAN else "cls")
+            kwargs.pop("pipeline")
+            if pipe is not None and not own:
+                return super().from_pretrained(pretrained_model_name_or_path, *model_args, pipeline=pipe, **kwargs)
         model = super().from_pretrained(pretrained_model_name_or_path, *model_args, **kwargs)
         w = read_st_dense(pretrained_model_name_or_path, int(model.config.d_model), **kwargs)
         if w is not None:
@@ -1166,6 +1471,9 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
     def set_pooling(self, pooling: str) -> None:
         self._check_pooling(pooling)
         self._pool = DECODER_POOLINGS[pooling]
+        if self._st is not None:         # an explicit pooling overrides the folder's
+            self._st = StPipeline(pooling, None, None, self._st.activation, self._st.normalize)
+            self._hip = None
 
     @classmethod
     def _check_attention(cls, attention) -> None:
@@ -1195,7 +1503,7 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
 
     @property
     def pooling(self) -> str:
-        return {v: k for k, v in DECODER_POOLINGS.items()}[self._pool]
+        return self._st.pooling if self._st is not None else {v: k for k, v in DECODER_POOLINGS.items()}[self._pool]
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, **kwargs):
@@ -1205,7 +1513,9 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
         if attention is not None:
             cls._check_attention(attention)
         check_decoder_config(checkpoint_model_type(pretrained_model_name_or_path, kwargs)[1])     # from config.json alone, before a weight is read
-        if pooling is None:
+        # (pipeline="checkpoint": the folder's modules.json decides the pooling, max and mean_sqrt_len included — _HipSentenceMixin.from_pretrained)
+        by_folder = kwargs.get("pipeline") == "checkpoint" and _st_file(pretrained_model_name_or_path, "modules.json", kwargs) is not None
+        if pooling is None and not by_folder:
             pooling = read_st_pooling(pretrained_model_name_or_path, **kwargs)
         if attention is None:
             path = _st_file(pretrained_model_name_or_path, f"{ST_POOLING_DIR}/{ST_ATTENTION_FILE}", kwargs)
@@ -1223,6 +1533,10 @@ class _HipDecoderSentenceMixin(_HipSentenceMixin):
     def save_pretrained(self, save_directory, *args, **kwargs):
         out = super().save_pretrained(save_directory, *args, **kwargs)
         os.makedirs(os.path.join(save_directory, ST_POOLING_DIR), exist_ok=True)
+        if "_st" in self.__dict__:       # the tail came from a folder and has been written back as it was (_HipSentenceMixin.save_pretrained): the mask alone is added
+            with open(os.path.join(save_directory, ST_POOLING_DIR, ST_ATTENTION_FILE), "w") as f:
+                json.dump({"attention": self.attention}, f, indent=2)
+            return out
         pool = {"word_embedding_dimension": int(self.config.hidden_size), "pooling_mode_cls_token": False, "pooling_mode_mean_tokens": self._pool == POOL_MEAN,
                 "pooling_mode_max_tokens": False, "pooling_mode_mean_sqrt_len_tokens": False, "pooling_mode_weightedmean_tokens": False,
                 "pooling_mode_lasttoken": self._pool == POOL_LAST, "include_prompt": True}
@@ -1256,6 +1570,9 @@ XLMRobertaE5Encoder, XLMRobertaBGEEncoder = _twin_pair(
 MPNetE5Encoder, MPNetBGEEncoder = _twin_pair(
     "MPNet", (_HipMPNetSentenceEncoder,), "MPNetModel -> masked mean -> L2 normalise (sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-cos-v1)",
     "MPNetModel -> [:, 0] -> L2 normalise")
+DistilBertE5Encoder, DistilBertBGEEncoder = _twin_pair(
+    "DistilBert", (_HipDistilBertSentenceEncoder,), "DistilBertModel -> masked mean -> L2 normalise (msmarco-distilbert-*, multi-qa-distilbert-cos-v1)",
+    "DistilBertModel -> [:, 0] -> L2 normalise")
 NomicBertE5Encoder, NomicBertBGEEncoder = _twin_pair(
     "NomicBert", (_HipNomicSentenceEncoder,), "NomicBertModel -> masked mean -> L2 normalise (nomic-ai/nomic-embed-text-v1, -v1.5)",
     "NomicBertModel -> [:, 0] -> L2 normalise")
@@ -1287,6 +1604,14 @@ EuroBertE5Encoder, EuroBertBGEEncoder = _decoder_pair(
     "EuroBertModel (bidirectional) -> masked mean -> L2 normalise", POOL_MEAN)
 
 
+class ContrieverEncoder(_HipSentenceEncoder):
+    """retriever/encoders.py:80-97 of the reference: BertModel -> masked mean, NOT normalised (facebook/contriever, contriever-msmarco: trained for the dot
+    product).  Eval mode runs the HIP path with ``config.normalize_output = 0``; ``train()`` mode the reference's arithmetic on HF's forward."""
+    _pool = POOL_MEAN
+    _dispatch_by_model_type = False
+    _st = StPipeline("mean", normalize=False)
+
+
 def _decoder_family(model_type: str, twins: tuple, decoder_attention: Optional[float] = None) -> Family:
     return Family((model_type,), twins[0]._hf_base, describe_decoder, twins, flag="is_decoder", decoder_attention=decoder_attention)
 
@@ -1301,6 +1626,9 @@ _FAMILIES = (
     # MPNet: BERT's stack under other names, no token types (a zero row stands in), fairseq positions with padding index 1, and one learned bias per
     # (head, bucket of the column distance) that the attention kernels add to every score (encoder.relative_attention_bias.weight)
     Family((MPNET_TYPE,), MPNetModel, describe_mpnet, (MPNetE5Encoder, MPNetBGEEncoder), flag="is_mpnet"),
+    # DistilBERT (the backbone of msmarco-distilbert-base-tas-b, multi-qa-distilbert-*, distiluse): BERT's layer stack without token types (a zero row stands in)
+    # under other state-dict names (distilbert_rename); the position table is sent as it stands in the state dict, sinusoidal or learned
+    Family((DISTILBERT_TYPE,), DistilBertModel, describe_distilbert, (DistilBertE5Encoder, DistilBertBGEEncoder), check=check_distilbert_config, zero_type_row=True),
     # NomicBert (nomic-embed-text-v1 / -v1.5): post-LN without a position table — q / k rotated in the QKV epilogue by HF's own inv_freq — a SwiGLU MLP
     # with gate | up as one projection, no linear biases
     Family((NOMIC_TYPE,), NomicBertModel, describe_nomic, (NomicBertE5Encoder, NomicBertBGEEncoder), token_types=True, flag="is_nomic"),

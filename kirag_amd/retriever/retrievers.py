@@ -61,7 +61,8 @@ class BaseRetriever(nn.Module):
 
     @property
     def hidden_size(self):
-        return self.encoder.config.hidden_size
+        dense = getattr(self.encoder, "st_dense", None)      # a checkpoint's own Dense head (pipeline="checkpoint"): the embeddings are out_features wide
+        return int(dense.out_features) if dense is not None else self.encoder.config.hidden_size
 
     def compute_logits(self, query_embeddings, doc_embeddings, **kwargs):
         nq, nd = query_embeddings.dim(), doc_embeddings.dim()

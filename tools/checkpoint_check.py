@@ -407,8 +407,54 @@ def check_m3(hf_dir, args):
     return out
 
 
+def check_pipeline(hf_dir, args):
+    """--pipeline checkpoint: the tail the folder's modules.json states (pooling, Dense, Normalize or not) on the family's twin.  Reference: the twin's HF base
+    class in fp32 followed by that tail in torch (``_st_tail``); tested: its eval forward, the HIP path.  Besides the score error and 1 - cos the worst
+    ELEMENT-WISE deviation is reported: 1 - cos says nothing about the length of a row that is not normalised."""
+    from transformers import AutoConfig
+    from kirag_amd.retriever.encoders import DECODER_BASES, MPNET_PADDING_IDX, MPNET_TYPE, ROBERTA_TYPES, BGEEncoder, DecoderBGEEncoder, DecoderE5Encoder, E5Encoder
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{hf_dir}: --pipeline checkpoint compares the HIP path with HF: run on the GPU")
+    cfg = AutoConfig.from_pretrained(hf_dir)
+    mt = getattr(cfg, "model_type", "bert")
+    decoder = mt in DECODER_BASES
+    cls = (DecoderE5Encoder if args.pool == "mean" else DecoderBGEEncoder) if decoder else (E5Encoder if args.pool == "mean" else BGEEncoder)
+    model = cls.from_pretrained(hf_dir, pipeline="checkpoint", **({"attn_implementation": "eager"} if decoder else {})).float().eval().to("cuda:0")
+    if model._st is None:
+        raise SystemExit(f"{hf_dir}: no modules.json: the folder states no pipeline (run without --pipeline)")
+    mpnet = mt == MPNET_TYPE
+    roberta = mpnet or mt in ROBERTA_TYPES
+    batches = load_inputs(args, hf_dir, cfg.vocab_size, (MPNET_PADDING_IDX if mpnet else cfg.pad_token_id) if roberta else None)
+    ref, out = [], []
+    with torch.no_grad():
+        for ids, mask in batches:
+            ti, tm = torch.from_numpy(ids).to("cuda:0"), torch.from_numpy(mask).to("cuda:0")
+            ref.append(model._st_tail(model._torch_pooled(ti, tm, None), tm).double().cpu().numpy())
+            out.append(model(ti, tm).double().cpu().numpy())
+    finite = all(np.isfinite(o).all() for o in out)
+    dev = float(max(np.abs(o - r).max() for o, r in zip(out, ref)))
+    scale = float(max(np.abs(r).max() for r in ref))
+    err = float(np.abs(out[0] @ out[1].T - ref[0] @ ref[1].T).max())
+    cos = float(max((1 - (o * r).sum(1) / np.linalg.norm(o, axis=1) / np.linalg.norm(r, axis=1)).max() for o, r in zip(out, ref)))
+    st = model._st
+    dense = getattr(model, "st_dense", None)
+    print(f"# {hf_dir}: model_type {mt}, pipeline from modules.json: pooling {st.pooling}, "
+          f"{'Dense ' + str(tuple(dense.weight.shape)) + (' + bias' if dense.bias is not None else '') + ' ' + st.activation if dense is not None else 'no Dense'}, "
+          f"{'Normalize' if st.normalize else 'NOT normalised'}; {sum(len(b[0]) for b in batches)} sequences")
+    print(f"  worst |out - ref| element-wise = {dev:.2e} (largest |ref| element {scale:.2e})   worst |q.d - ref| = {err:.2e}   worst 1 - cos = {cos:.2e}" + ("" if finite else "   NON-FINITE OUTPUT"))
+    res = {"checkpoint": hf_dir, "tested_path": "hip", "pipeline": {"pooling": st.pooling, "dense": None if dense is None else list(dense.weight.shape), "bias": dense is not None and dense.bias is not None,
+                                                                  "activation": st.activation, "normalize": st.normalize},
+           "worst_elementwise_deviation": dev, "largest_reference_element": scale, "worst_score_error": err, "worst_1_minus_cos": cos, "finite": finite}
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    return res
+
+
 def check(hf_dir, args):
     from transformers import AutoConfig, AutoModel
+    if getattr(args, "pipeline", None) == "checkpoint":
+        return check_pipeline(hf_dir, args)
     cfg = AutoConfig.from_pretrained(hf_dir)
     if os.path.isdir(hf_dir) and (os.path.exists(os.path.join(hf_dir, "colbert_linear.pt")) or os.path.exists(os.path.join(hf_dir, "sparse_linear.pt"))):
         return check_m3(hf_dir, args)
@@ -524,6 +570,8 @@ def parse(argv=None):
     ap.add_argument("--n", type=int, default=32, help="sequences per side (queries / passages)")
     ap.add_argument("--max-length", type=int, default=128)
     ap.add_argument("--pool", default="mean", choices=["mean", "cls", "last"], help="mean = E5Encoder, cls = BGEEncoder, last = the last attended token (decoder checkpoints)")
+    ap.add_argument("--pipeline", default=None, choices=["checkpoint"], help="checkpoint = pooling, Dense and normalisation as the folder's modules.json states them "
+                    "(--pool then only selects the registry class); reports the worst element-wise deviation as well")
     ap.add_argument("--emulate", action="store_true", help="torch emulation of the rounding points even when a GPU is present")
     ap.add_argument("--random-tokens", action="store_true")
     ap.add_argument("--seed", type=int, default=0)

@@ -100,6 +100,8 @@ ap.add_argument("--bidirectional", action="store_true", help="decoder shapes: co
 ap.add_argument("--alternate", action="store_true", help="decoder shapes: a causal and a bidirectional handle in this process, timed in turns (--reps rounds)")
 ap.add_argument("--expanded", action="store_true", help="decoder shapes: build the handle from k_proj / v_proj expanded to [H, H] (expand_kv) instead of the grouped tensors")
 ap.add_argument("--alternate-gqa", action="store_true", help="decoder shapes: a native and an expanded handle of the same weights in this process, timed in turns (--reps rounds)")
+ap.add_argument("--alternate-tail", action="store_true", help="BERT shapes: three handles of the same weights — the plain masked mean, config.normalize_output = 0 and "
+                "config.pool_tokens = 1 (max) — timed in turns in this process (--reps rounds of 3)")
 ap.add_argument("--first-forward", action="store_true")
 ap.add_argument("--alternate-shapes", action="store_true", help="one handle per --shape, timed in turns in this process (--reps rounds of 3)")
 ap.add_argument("--digest", action="store_true", help="append the sha256 (16 hex digits) of the batch's embeddings")
@@ -350,6 +352,27 @@ for shape in (args.shape or ["e5-large"]) if __name__ == "__main__" else ():
     ids, mask = shape_tokens(cfg)
     if args.first_forward:
         first_forward(shape, cfg, ids, mask)
+        torch.cuda.empty_cache()
+        continue
+    if args.alternate_tail:
+        # one process, three handles of the same weights, timed in turns: what a tail costs over the plain mean is the difference of the medians
+        from types import SimpleNamespace
+        from kirag_amd.retriever.encoders import HipBertForward, StPipeline
+        assert cfg.get("model_type", "bert") == "bert", "--alternate-tail builds BERT handles"
+        ns = SimpleNamespace(**cfg)
+        state = dict(BS.synthetic_state(ns, dev, 0))
+        trio = {}
+        for k, pipe in (("mean", None), ("unnormalised", StPipeline("mean", normalize=False)), ("max", StPipeline("max"))):
+            trio[k] = HipBertForward(ns, 0, pipeline_settings=pipe.settings() if pipe else ())
+            trio[k].load_state(state)
+        times = {k: [] for k in trio}
+        for _ in range(args.reps):
+            for k, e in trio.items():
+                times[k].append(timed(lambda: e.forward(ids, mask, 0), 3) * 1e3)
+        for k in trio:
+            t = sorted(times[k])
+            print(f"{shape} tail={k} n={n} S={S} ragged={ragged}: median {t[len(t) // 2]:.3f} ms (min {t[0]:.3f}, max {t[-1]:.3f}, {len(t)} rounds of 3 in turns)", flush=True)
+        del trio, state
         torch.cuda.empty_cache()
         continue
     if cfg.get("model_type") in DECODER_TYPES and args.alternate:
