@@ -297,10 +297,7 @@ struct RowSet {
     uint16_t* rb; uint8_t* rlo;  // ModernBert handles: the pre-LN residual stream of these rows (rlo: nullptr without use_lo)
 };
 
-// Row width as a compile-time constant, f(std::integral_constant<int, N>{}) in the manner of with_epilogue: the LayerNorm family of kernels covers a row in
-// NS steps of 512 elements, the pool and head family in NJ steps of 256
-template <int N> using width_c = std::integral_constant<int, N>;
-template <class F> static auto with_ln_width(int H, F&& f) { return H <= 512 ? f(width_c<1>{}) : H <= 1024 ? f(width_c<2>{}) : f(width_c<4>{}); }
+// Row width as a compile-time constant (width_c, with_ln_width: encoder_rows.hpp): the pool and head family of kernels covers a row in NJ steps of 256
 template <class F> static auto with_pool_width(int H, F&& f) { return H <= 256 ? f(width_c<1>{}) : H <= 512 ? f(width_c<2>{}) : H <= 1024 ? f(width_c<4>{}) : f(width_c<8>{}); }
 
 // What the steps of one forward share (enqueue_forward fills it in)
@@ -335,35 +332,24 @@ static void enqueue_embed(const Forward& f) {
     Encoder* e = f.e;
     const ModelPlan& p = e->plan;
     const int H = f.H;
-    if (p.rotary) hipLaunchKernelGGL(k_rot_pos, dim3(f.B), dim3(64), 0, f.st, e->seq_off, e->seq_nq, f.align, e->tok_pos, e->tok_rpos);
+    if (p.rotary) launch_rot_pos(e->seq_off, e->seq_nq, f.align, e->tok_pos, e->tok_rpos, (unsigned)f.B, f.st);
     if (embed_is_residual(p)) {
-        const auto embed_kernel = with_ln_width(H, [](auto ns) { return &k_embed_rms<decltype(ns)::value>; });
-        hipLaunchKernelGGL(embed_kernel, dim3(f.row_grid), dim3(256), 0, f.st, e->tok_id, e->d_T, e->word, e->elng, f.eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb);
+        launch_embed_rms(e->tok_id, e->d_T, e->word, e->elng, f.eps, H, e->rb, e->use_lo ? e->rlo : nullptr, e->xb, f.row_grid, f.st);
     } else {
         const bool no_pos = p.pos == POS_ROTARY || f.disent;      // a zero row in place of a position row
-        hipLaunchKernelGGL(k_embed_ln, dim3(f.row_grid), dim3(256), 0, f.st, e->tok_id, no_pos ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T,
-                           e->word, no_pos ? e->zero_row : e->pos, e->type, e->elng, e->elnb, f.eps, H,
-                           e->use_lo ? e->xlo : nullptr, e->xb);
+        launch_embed_ln(e->tok_id, no_pos ? e->tok_zero : p.pos == POS_FAIRSEQ ? e->tok_epos : e->tok_pos, e->tok_type, e->d_T, e->word, no_pos ? e->zero_row : e->pos, e->type,
+                        e->elng, e->elnb, f.eps, H, e->use_lo ? e->xlo : nullptr, e->xb, f.row_grid, f.st);
     }
 }
 
 // The norm behind a residual projection of a layer's tail, on the rows of r.  Post-LN: xb = LayerNorm(y + bias + xb), the low half read at r.lo and written to
 // lo_out.  Pre-LN (k_ln16_pre; RMS on T5 handles): (rin, rin_lo) + y + bias is the residual stream, stored to (rb_out, r.rlo) unless rb_out is nullptr; xb =
-// the NEXT norm of it, its low half to lo_out unless that is nullptr.
-// LayerNorm streams: y (dead after the kernel) and the low half (next read by the next LayerNorm, ~600 MiB of traffic later) are loaded / stored
-// non-temporally — they do not displace the 16-bit stream the next GEMM reads: -1.3 % forward at 1024 x 128 tokens, -0.1...0.5 % at 1000 x 32; 8 blocks
-// per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
+// the NEXT norm of it, its low half to lo_out unless that is nullptr.  (The kernels and their cache policies: launch_ln_pre / launch_ln_post, encoder_rows.hpp)
 static void launch_norm(const Forward& f, const RowSet& r, const float* bias, const float* g, const float* b, const uint16_t* rin, const uint8_t* rin_lo, uint16_t* rb_out,
                         uint8_t* lo_out) {
     const model::ModelPlan& p = f.e->plan;
-    if (p.pre_ln) {
-        const auto ln_tail_kernel = p.rms ? with_ln_width(f.H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1, true>; })
-                                          : with_ln_width(f.H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1>; });
-        hipLaunchKernelGGL(ln_tail_kernel, dim3(r.ln_grid), dim3(256), 0, f.st, r.y, bias, r.rows, g, b, f.eps, f.H, rin, rin_lo, rb_out, r.rlo, lo_out, r.xb);
-    } else {
-        const auto ln_kernel = with_ln_width(f.H, [](auto ns) { return &k_ln16<decltype(ns)::value, 7>; });
-        hipLaunchKernelGGL(ln_kernel, dim3(r.ln_grid), dim3(256), 0, f.st, r.y, bias, r.rows, g, b, f.eps, f.H, (const uint8_t*)r.lo, lo_out, r.xb);
-    }
+    if (p.pre_ln) launch_ln_pre(p.rms, r.y, bias, r.rows, g, b, f.eps, f.H, rin, rin_lo, rb_out, r.rlo, lo_out, r.xb, r.ln_grid, f.st);
+    else launch_ln_post(r.y, bias, r.rows, g, b, f.eps, f.H, r.lo, lo_out, r.xb, r.ln_grid, f.st);
 }
 // The tail of a layer on the rows of r: Wo + residual -> norm, W1 + activation, W2 + residual -> norm.  Post-LN: the norms are LayerNorms of the sum.  Pre-LN
 // (ModernBert, T5 and decoder handles) on the same five launches: r += y + b, xb = the next norm of r.  (rin, rin_lo): the residual stream as a pre-LN layer
@@ -411,11 +397,9 @@ static int enqueue_layer(const Forward& f, size_t li) {
     KR_TRY(launch_proj(QKV_EPI[lp.qkv], a, f.maxT, f.pl, f.st));
     if (lp.qkv == QKV_SPLIT) {
         // the q / k norms of the layer and the rotation behind them, in place on q and k: one more read and write of both
-        const int nh = e->cfg.heads + p.kv_dim / p.head_w, lph = p.head_w / 8;
-        const auto norm_kernel = p.head_w == 128 ? &k_qk_norm_rope<128> : p.head_w == 64 ? &k_qk_norm_rope<64> : &k_qk_norm_rope<32>;
-        const int64_t units = f.maxT * nh, per_block = 4 * (64 / lph);
-        hipLaunchKernelGGL(norm_kernel, dim3((unsigned)((units + per_block - 1) / per_block)), dim3(256), 0, f.st, e->q, e->k, e->d_T, e->cfg.heads, p.kv_dim / p.head_w, l.qng, l.kng,
-                           f.eps * l.qfold * l.qfold, f.eps, a.rot_cos, a.rot_sin, e->tok_rpos, e->cfg.max_pos);
+        const int kv_heads = p.kv_dim / p.head_w;
+        launch_qk_norm_rope(p.head_w, e->q, e->k, e->d_T, e->cfg.heads, kv_heads, l.qng, l.kng, f.eps * l.qfold * l.qfold, f.eps, a.rot_cos, a.rot_sin, e->tok_rpos, e->cfg.max_pos,
+                            qk_norm_grid(f.maxT, e->cfg.heads, kv_heads, p.head_w), f.st);
     }
     auto attend = [&](auto dh) -> int {
         constexpr int DH = decltype(dh)::value;
@@ -444,8 +428,8 @@ static int enqueue_layer(const Forward& f, size_t li) {
     const uint16_t* rin = in_rb ? e->rb : e->xb;
     const uint8_t* rin_lo = in_rb ? f.all_rows.rlo : f.all_rows.lo;
     if (!(last && f.shortcut)) return enqueue_tail(f, a, l, f.all_rows, last, rin, rin_lo);
-    hipLaunchKernelGGL(k_gather_cls, dim3(f.B), dim3(256), 0, f.st, e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb,
-                       pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, f.pool.score ? 1 : 0, Dq);
+    launch_gather_cls(e->ctx, rin, rin_lo, e->seq_off, e->seq_cls, e->seq_nk, H, e->c_ctx, pre ? e->c_rb : e->c_xb, pre ? e->c_rlo : e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B,
+                      f.pool.score ? 1 : 0, Dq, (unsigned)f.B, f.st);
     return enqueue_tail(f, a, l, f.cls_rows, last, e->c_rb, f.cls_rows.rlo);
 }
 // KR_POOL_SPLADE behind the last layer: the MLM head on every packed row, max over each sequence's rows, log1p — into f.tok_out [B, vocab]
@@ -461,8 +445,7 @@ static int enqueue_splade_head(const Forward& f) {
     KR_TRY(launch_proj(EPI_GELU, a, f.maxT, f.pl, f.st));
     KR_HIP(hipMemsetAsync(e->row_seq, 0xff, (size_t)e->capT * 4, f.st));
     hipLaunchKernelGGL(k_splade_rowseq, dim3(f.B), dim3(64), 0, f.st, e->seq_off, e->seq_nk, e->row_seq);
-    const auto head_ln = with_ln_width(H, [](auto ns) { return &k_ln16_head<decltype(ns)::value>; });
-    hipLaunchKernelGGL(head_ln, dim3(f.ln_grid), dim3(256), 0, f.st, e->y, e->zero_row, e->d_T, e->hf(HEAD_MLM, 2), e->hf(HEAD_MLM, 3), f.eps, H, e->row_seq, e->q, e->d_err);
+    launch_ln_head(e->y, e->zero_row, e->d_T, e->hf(HEAD_MLM, 2), e->hf(HEAD_MLM, 3), f.eps, H, e->row_seq, e->q, e->d_err, f.ln_grid, f.st);
     // the decoder: [rows] x [Vpad, H]^T reduced over each sequence's rows inside the launch (EPI_SPLADE), then log1p in place
     KR_HIP(hipMemsetAsync(f.tok_out, 0, (size_t)f.B * V * 4, f.st));
     proj(a, e->hh(HEAD_MLM, 4), e->q, (int)extent(e->cfg, XVPAD), H, e->hf(HEAD_MLM, 5), nullptr);
@@ -581,9 +564,8 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     if (in.ragged) pack_ragged(e->rag_ids(), e->rag_lens(), e->rag_in_off(), B, S, in.total, rules, seq, tok, st);
     else pack_padded(e->d_ids, e->d_mask, in.has_tt ? e->d_tt : nullptr, B, S, rules, seq, tok, st);
     f.maxT = (int64_t)B * ((S + cls_row + f.align - 1) & ~(f.align - 1));
-    f.row_grid = (unsigned)((f.maxT + 3) / 4);
-    const unsigned ln_cap = (unsigned)e->num_cu_all * 8u;      // 8 LayerNorm blocks per CU (launch_norm)
-    f.ln_grid = std::min(f.row_grid, ln_cap);
+    f.row_grid = row_grid(f.maxT);
+    f.ln_grid = ln_grid(f.maxT, e->num_cu_all);      // 8 LayerNorm blocks per CU (encoder_rows.hpp)
     // one row per sequence behind the last layer (the CLS row; the score head's last packed row — the embedding pools of a decoder handle keep every row): the
     // last layer finishes on the gathered rows.  The token-level heads read every row of the last layer
     f.shortcut = f.pool.one_row && e->cls_shortcut && e->c_ctx != nullptr && !flags;
@@ -592,7 +574,7 @@ static int enqueue_forward(Encoder* e, int B, int S, int pool, hipStream_t st, c
     f.all_rows = RowSet{e->ctx, e->xb, e->y, e->h, e->use_lo ? e->xlo : nullptr, e->xlo, e->seq_off, e->seq_nk, e->seq_cls, e->d_T, f.maxT, f.ln_grid,
                         e->rb, e->use_lo ? e->rlo : nullptr};
     f.cls_rows = RowSet{e->c_ctx, e->c_xb, e->c_y, e->c_h, e->use_lo ? e->c_xlo : nullptr, e->c_xlo, e->c_off, e->c_nk, e->c_cls, e->d_B, B,
-                        std::min((unsigned)((B + 3) / 4), ln_cap), e->c_rb, e->use_lo ? e->c_rlo : nullptr};
+                        ln_grid(B, e->num_cu_all), e->c_rb, e->use_lo ? e->c_rlo : nullptr};
     enqueue_embed(f);
     for (size_t li = 0; li < e->L.size(); ++li) KR_TRY(enqueue_layer(f, li));
     if (f.pool.splade) KR_TRY(enqueue_splade_head(f));

@@ -3,7 +3,9 @@
 #pragma once
 #include "gemm_nt.hpp"
 
+#include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 // This file is compiled TWICE (kirag_amd/csrc/Makefile): once per 16-bit operand type of the MFMAs and of every stored activation —
@@ -1089,6 +1091,62 @@ static int set_lds_once(const void* kern, int lds, int device) {
     if (ent) { ent->lds = lds; ent->rc = rc; } else done.push_back({kern, device, lds, rc});
     if (rc != hipSuccess) return fail(KR_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(rc));
     return 0;
+}
+
+// Row width as a compile-time constant, f(std::integral_constant<int, N>{}) in the manner of with_epilogue: the LayerNorm family of kernels covers a row in
+// NS steps of 512 elements (the pool and head family in NJ steps of 256: with_pool_width, encoder.hip)
+template <int N> using width_c = std::integral_constant<int, N>;
+template <class F> static auto with_ln_width(int H, F&& f) { return H <= 512 ? f(width_c<1>{}) : H <= 1024 ? f(width_c<2>{}) : f(width_c<4>{}); }
+
+// The launches of the row kernels above: which instantiation a width or a head width gets, its cache policy and its block size, as plain functions of
+// pointers, sizes, a grid and a stream — a forward (encoder.hip) and the kernels' own tests (tests/capi/rows_probe.hip) go through the same lines.  The grids
+// of a forward: one wave per row (row_grid) for the embedding kernels; the grid-stride LayerNorms at most 8 blocks per CU (ln_grid; profiles/r04/
+// tried_ln_policies.txt); the q / k norm one DH / 8-lane group per (row, head) unit (qk_norm_grid).
+static unsigned row_grid(int64_t rows) { return (unsigned)((rows + 3) / 4); }
+static unsigned ln_grid(int64_t rows, int num_cu) { return std::min(row_grid(rows), (unsigned)num_cu * 8u); }
+static unsigned qk_norm_grid(int64_t rows, int heads, int kv_heads, int head_w) {
+    const int64_t units = rows * (heads + kv_heads), per_block = 4 * (64 / (head_w / 8));
+    return (unsigned)((units + per_block - 1) / per_block);
+}
+static void launch_rot_pos(const int* seq_off, const int* seq_nq, int align, const int* tok_pos, int* rpos, unsigned B, hipStream_t st) {
+    hipLaunchKernelGGL(k_rot_pos, dim3(B), dim3(64), 0, st, seq_off, seq_nq, align, tok_pos, rpos);
+}
+static void launch_embed_rms(const int* tok_id, const int* Tp, const float* word, const float* g, float eps, int H, uint16_t* rb, uint8_t* rlo, uint16_t* xb, unsigned grid,
+                             hipStream_t st) {
+    const auto embed_kernel = with_ln_width(H, [](auto ns) { return &k_embed_rms<decltype(ns)::value>; });
+    hipLaunchKernelGGL(embed_kernel, dim3(grid), dim3(256), 0, st, tok_id, Tp, word, g, eps, H, rb, rlo, xb);
+}
+static void launch_embed_ln(const int* tok_id, const int* tok_pos, const int* tok_type, const int* Tp, const float* word, const float* pos, const float* type, const float* g,
+                            const float* bta, float eps, int H, uint8_t* xlo, uint16_t* xb, unsigned grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_embed_ln, dim3(grid), dim3(256), 0, st, tok_id, tok_pos, tok_type, Tp, word, pos, type, g, bta, eps, H, xlo, xb);
+}
+// LayerNorm streams: y (dead after the kernel) and the low half (next read by the next LayerNorm, ~600 MiB of traffic later) are loaded / stored
+// non-temporally — they do not displace the 16-bit stream the next GEMM reads: -1.3 % forward at 1024 x 128 tokens, -0.1...0.5 % at 1000 x 32; 8 blocks
+// per CU instead of 4: -0.25 % (profiles/r04/tried_ln_policies.txt; outputs bit-identical)
+static void launch_ln_post(const uint16_t* y, const float* bias, const int* Tp, const float* g, const float* b, float eps, int H, const uint8_t* xlo_in, uint8_t* xlo,
+                           uint16_t* xb, unsigned grid, hipStream_t st) {
+    const auto ln_kernel = with_ln_width(H, [](auto ns) { return &k_ln16<decltype(ns)::value, 7>; });
+    hipLaunchKernelGGL(ln_kernel, dim3(grid), dim3(256), 0, st, y, bias, Tp, g, b, eps, H, xlo_in, xlo, xb);
+}
+static void launch_ln_pre(bool rms, const uint16_t* y, const float* bias, const int* Tp, const float* g, const float* b, float eps, int H, const uint16_t* rb_in,
+                          const uint8_t* rlo_in, uint16_t* rb_out, uint8_t* rlo_out, uint8_t* xlo, uint16_t* xb, unsigned grid, hipStream_t st) {
+    const auto ln_tail_kernel = rms ? with_ln_width(H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1, true>; })
+                                    : with_ln_width(H, [](auto ns) { return &k_ln16_pre<decltype(ns)::value, 1>; });
+    hipLaunchKernelGGL(ln_tail_kernel, dim3(grid), dim3(256), 0, st, y, bias, Tp, g, b, eps, H, rb_in, rlo_in, rb_out, rlo_out, xlo, xb);
+}
+static void launch_ln_head(const uint16_t* y, const float* zero, const int* Tp, const float* g, const float* b, float eps, int H, const int* row_seq, uint16_t* out, int* err,
+                           unsigned grid, hipStream_t st) {
+    const auto head_ln = with_ln_width(H, [](auto ns) { return &k_ln16_head<decltype(ns)::value>; });
+    hipLaunchKernelGGL(head_ln, dim3(grid), dim3(256), 0, st, y, zero, Tp, g, b, eps, H, row_seq, out, err);
+}
+static void launch_qk_norm_rope(int head_w, uint16_t* q, uint16_t* k, const int* Tp, int heads, int kv_heads, const float* gq, const float* gk, float eps_q, float eps_k,
+                                const float* rot_cos, const float* rot_sin, const int* tpos, int max_pos, unsigned grid, hipStream_t st) {
+    const auto norm_kernel = head_w == 128 ? &k_qk_norm_rope<128> : head_w == 64 ? &k_qk_norm_rope<64> : &k_qk_norm_rope<32>;
+    hipLaunchKernelGGL(norm_kernel, dim3(grid), dim3(256), 0, st, q, k, Tp, heads, kv_heads, gq, gk, eps_q, eps_k, rot_cos, rot_sin, tpos, max_pos);
+}
+static void launch_gather_cls(const uint16_t* ctx, const uint16_t* xb, const uint8_t* xlo, const int* seq_off, const int* seq_cls, const int* seq_nk, int H, uint16_t* c_ctx,
+                              uint16_t* c_xb, uint8_t* c_xlo, int* c_off, int* c_nk, int* c_cls, int* d_B, int last_row, int Dq, unsigned B, hipStream_t st) {
+    hipLaunchKernelGGL(k_gather_cls, dim3(B), dim3(256), 0, st, ctx, xb, xlo, seq_off, seq_cls, seq_nk, H, c_ctx, c_xb, c_xlo, c_off, c_nk, c_cls, d_B, last_row, Dq);
 }
 
 }  // namespace KR_ENC_NS

@@ -1,29 +1,17 @@
 """The residual stream's low byte (kirag_amd/csrc/encoder_rows.hpp: lo_encode / lo_decode) as a numpy specification: x is kept as hi = the 16-bit operand
 (round to nearest) plus ONE byte = the distance bits(x) - bits(hi) on the fp32 bit patterns in units of 2^LO_SH fp32 ulps (= ulp(hi) / 256), biased by 128
 and clamped BEFORE the shift (the shift-then-clamp form is selected to v_ashr_pk_u8_i32, which writes only 16 bits on gfx950: tests/test_build_quality.py).
-The properties below are what the kernels rely on; the device functions are exercised by tools/lo_codec_check.hip and, end to end, by the encoder goldens."""
+The properties below are what the kernels rely on.  The specification itself (to_hi, encode, decode) lives in tests/rows_probe_util.py; the device functions
+are held to it bit for bit by tests/test_gpu_rows_probe.py, which launches the norm kernels alone (tests/capi/rows_probe.hip) on rows whose correct output is
+any fp32 vector the test chooses: binade edges, the clamped tie, |x| < 2^-25, the f16 subnormal range, values beyond 65504 and every byte on both signs."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-
-def to_hi(x, kind):
-    if kind == "f16":
-        return x.astype(np.float16).astype(np.float32)
-    b = x.view(np.uint32).astype(np.uint64)
-    b = (b + 0x7fff + ((b >> 16) & 1)) >> 16 << 16          # bf16: round to nearest even on the bit pattern
-    return b.astype(np.uint32).view(np.float32)
-
-
-def encode(x, hi, sh):
-    d = (x.view(np.uint32).astype(np.int64) - hi.view(np.uint32).astype(np.int64) + 2**31) % 2**32 - 2**31      # int32 wrap
-    return (np.clip(d + (1 << (sh - 1)) + (128 << sh), 0, (256 << sh) - 1) >> sh).astype(np.uint8)
-
-
-def decode(byte, hi, sh):
-    """lo_decode_final: what the readers of the final hidden state use (a non-finite hi decodes to itself, round 5); for finite hi identical to the
-    3-instruction lo_decode of the LayerNorm's residual path"""
-    x = ((hi.view(np.uint32).astype(np.int64) + (byte.astype(np.int64) << sh) - (128 << sh)) % 2**32).astype(np.uint32).view(np.float32)
-    return np.where((hi.view(np.uint32) & 0x7f800000) == 0x7f800000, hi, x)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rows_probe_util import decode, encode, to_hi  # noqa: E402
 
 
 @pytest.mark.parametrize("kind,sh,mant", [("f16", 5, 10), ("bf16", 8, 7)])
