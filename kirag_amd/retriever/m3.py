@@ -4,7 +4,7 @@ ReLU) and a normalised vector per token (``colbert_linear``, H -> P, scored by M
 ``XLMRobertaM3Encoder`` / ``BertM3Encoder`` ARE the sentence encoders of ``kirag_amd.retriever.encoders`` (CLS pooling) with the two ``nn.Linear`` heads as
 sub-modules: ``named_parameters()`` carries ``colbert_linear.{weight,bias}`` / ``sparse_linear.{weight,bias}`` through the ordinary weight sync, and
 ``forward_m3`` asks the library for the extra blocks (``KR_POOL_WITH_SPARSE`` / ``KR_POOL_WITH_COLBERT``, ``include/kirag_amd.h``).  ``BGEM3Model`` is the
-user-facing object: ``encode``, ``compute_score``, ``rerank``.
+user-facing object: ``encode``, ``compute_score``, ``rerank``, and — over an ``Indexer`` and a ``late.MultiVectorStore`` — ``index_passages`` / ``retrieve``.
 
 UNVERIFIED OFFLINE.  FlagEmbedding is not a dependency of this project and was not at hand when this was written: the arithmetic below is THIS PROJECT'S
 definition, recalled from ``FlagEmbedding.BGEM3FlagModel``, not checked against it.  The recalled points:
@@ -290,3 +290,51 @@ class BGEM3Model:
         if top_k is not None:
             order = order[:top_k]
         return order, torch.from_numpy(s.astype(np.float32))[order]
+
+    # ---- dense top-n from the index, MaxSim over the stored token vectors of those n (kirag_amd.retriever.late) ----
+    @torch.no_grad()
+    def index_passages(self, ids, passages: Sequence[str], indexer, store, batch_size: int = 64, max_length: int = 512) -> None:
+        """ONE flagged forward per batch: the dense block goes to ``indexer.index_data`` (an ``Indexer``), the colbert block to ``store.add_block`` (a
+        ``MultiVectorStore`` on the encoder's GPU) — the token vectors of columns 1 .. len - 1, converted to float16 and packed on the device.  Neither block
+        visits the host.  Sparse weights are not stored: lexical scoring of stored passages is out of scope.
+
+        The two containers are kept in step: every id of the call is checked before the first forward (not a decimal number, twice in the call, already in
+        the store: ``ValueError``, nothing indexed); a batch the store refuses (a non-finite vector) never reaches the index; a batch the index refuses after
+        the store took it is taken out of the store again before the error is passed on.  Batches before the failing one stay in both."""
+        ids = list(ids)
+        if len(ids) != len(passages):
+            raise ValueError(f"{len(ids)} ids for {len(passages)} passages")
+        store.check_new_ids(ids)
+        tok = self._tokenizer()
+        for s in range(0, len(passages), batch_size):
+            enc = tok(list(passages[s:s + batch_size]), padding=True, truncation=True, max_length=max_length, return_tensors="pt")
+            dense, _, colbert = self.model.forward_m3(enc["input_ids"], enc["attention_mask"], return_sparse=False, return_colbert=True)
+            batch_ids = ids[s:s + batch_size]
+            store.add_block(batch_ids, colbert, enc["attention_mask"], skip_first=True)
+            try:
+                indexer.index_data(batch_ids, dense)
+            except BaseException:
+                store._drop_last(len(batch_ids))
+                raise
+
+    def retrieve(self, queries, indexer, store, top_k: int = 10, n_candidates: int = 100, weights=(1.0, 1.0),
+                 max_length: int = 512) -> List[Tuple[List[str], np.ndarray]]:
+        """Per query: ``indexer.search_knn`` gives ``n_candidates`` ids (at most the index's size) with their exact dense scores, ``store.maxsim`` scores
+        those passages' stored token vectors against the query's (all queries in one launch), and the best ``top_k`` by (combined descending, dense rank
+        ascending) come back as ``(ids, float32 scores)``; combined = ``(w_d dense + w_c colbert) / (w_d + w_c)``, ``weights = (w_d, w_c)``.  An empty
+        index, or ``n_candidates <= 0``, gives every query an empty result.  The sparse head takes no part: its weights are not stored."""
+        if isinstance(queries, str):
+            queries = [queries]
+        wd, wc = (float(w) for w in weights)
+        n = min(int(n_candidates), int(indexer.index.ntotal))
+        if n <= 0:
+            return [([], np.empty(0, np.float32)) for _ in queries]
+        q = self.encode(list(queries), max_length=max_length, return_dense=True, return_sparse=False, return_colbert_vecs=True)
+        hits = indexer.search_knn(q["dense_vecs"], n, verbose=False)
+        colbert = store.maxsim(q["colbert_vecs"], [h[0] for h in hits], reduce="mean")
+        out = []
+        for (cand, dense), col in zip(hits, colbert):
+            s = (wd * np.asarray(dense, np.float64) + wc * col.astype(np.float64)) / (wd + wc)
+            order = np.lexsort((np.arange(len(s)), -s))[:top_k]
+            out.append(([str(cand[i]) for i in order], s[order].astype(np.float32)))
+        return out
