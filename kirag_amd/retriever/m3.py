@@ -4,7 +4,8 @@ ReLU) and a normalised vector per token (``colbert_linear``, H -> P, scored by M
 ``XLMRobertaM3Encoder`` / ``BertM3Encoder`` ARE the sentence encoders of ``kirag_amd.retriever.encoders`` (CLS pooling) with the two ``nn.Linear`` heads as
 sub-modules: ``named_parameters()`` carries ``colbert_linear.{weight,bias}`` / ``sparse_linear.{weight,bias}`` through the ordinary weight sync, and
 ``forward_m3`` asks the library for the extra blocks (``KR_POOL_WITH_SPARSE`` / ``KR_POOL_WITH_COLBERT``, ``include/kirag_amd.h``).  ``BGEM3Model`` is the
-user-facing object: ``encode``, ``compute_score``, ``rerank``, and — over an ``Indexer`` and a ``late.MultiVectorStore`` — ``index_passages`` / ``retrieve``.
+user-facing object: ``encode``, ``compute_score``, ``rerank``, and — over an ``Indexer`` and a ``late.MultiVectorStore`` — ``index_passages`` / ``retrieve``;
+over a ``sparse_index.SparseIndexer``, ``retrieve_sparse``.
 
 UNVERIFIED OFFLINE.  FlagEmbedding is not a dependency of this project and was not at hand when this was written: the arithmetic below is THIS PROJECT'S
 definition, recalled from ``FlagEmbedding.BGEM3FlagModel``, not checked against it.  The recalled points:
@@ -293,28 +294,44 @@ class BGEM3Model:
 
     # ---- dense top-n from the index, MaxSim over the stored token vectors of those n (kirag_amd.retriever.late) ----
     @torch.no_grad()
-    def index_passages(self, ids, passages: Sequence[str], indexer, store, batch_size: int = 64, max_length: int = 512) -> None:
+    def index_passages(self, ids, passages: Sequence[str], indexer, store, batch_size: int = 64, max_length: int = 512, sparse_index=None) -> None:
         """ONE flagged forward per batch: the dense block goes to ``indexer.index_data`` (an ``Indexer``), the colbert block to ``store.add_block`` (a
         ``MultiVectorStore`` on the encoder's GPU) — the token vectors of columns 1 .. len - 1, converted to float16 and packed on the device.  Neither block
-        visits the host.  Sparse weights are not stored: lexical scoring of stored passages is out of scope.
+        visits the host.  With a ``sparse_index`` (a ``sparse_index.SparseIndexer``) the same forward also asks for the sparse block and the passages'
+        ``lexical_weights`` (``build_lexical_weights``, as ``encode`` builds them) go to ``sparse_index.index_data``; without one, sparse weights are not stored.
 
         The two containers are kept in step: every id of the call is checked before the first forward (not a decimal number, twice in the call, already in
         the store: ``ValueError``, nothing indexed); a batch the store refuses (a non-finite vector) never reaches the index; a batch the index refuses after
-        the store took it is taken out of the store again before the error is passed on.  Batches before the failing one stay in both."""
+        the store took it is taken out of the store again before the error is passed on.  Batches before the failing one stay in both.  The sparse index is
+        the container in the middle: its ids are checked before the first forward too, a batch it refuses is taken out of the store, a batch the index refuses
+        is taken out of both."""
         ids = list(ids)
         if len(ids) != len(passages):
             raise ValueError(f"{len(ids)} ids for {len(passages)} passages")
         store.check_new_ids(ids)
+        if sparse_index is not None:
+            sparse_index.check_new_ids(ids)
         tok = self._tokenizer()
+        skip = self._skip_ids() if sparse_index is not None else ()
         for s in range(0, len(passages), batch_size):
             enc = tok(list(passages[s:s + batch_size]), padding=True, truncation=True, max_length=max_length, return_tensors="pt")
-            dense, _, colbert = self.model.forward_m3(enc["input_ids"], enc["attention_mask"], return_sparse=False, return_colbert=True)
+            dense, sparse, colbert = self.model.forward_m3(enc["input_ids"], enc["attention_mask"], return_sparse=sparse_index is not None, return_colbert=True)
             batch_ids = ids[s:s + batch_size]
+            if sparse_index is not None:
+                w, ids_np, lens = sparse.float().cpu().numpy(), enc["input_ids"].numpy(), enc["attention_mask"].sum(dim=1).tolist()
+                lex = [build_lexical_weights(ids_np[b, :n], w[b, :n], skip) for b, n in enumerate(lens)]
+                if colbert.data_ptr() % 16:       # behind the [B, S] sparse block the colbert view starts where B * S left it; add_block's kernel reads 16-byte pieces
+                    colbert = colbert.clone()
             store.add_block(batch_ids, colbert, enc["attention_mask"], skip_first=True)
+            taken = [store]
             try:
+                if sparse_index is not None:
+                    sparse_index.index_data(batch_ids, lex)
+                    taken.append(sparse_index)
                 indexer.index_data(batch_ids, dense)
             except BaseException:
-                store._drop_last(len(batch_ids))
+                for c in taken:
+                    c._drop_last(len(batch_ids))
                 raise
 
     def retrieve(self, queries, indexer, store, top_k: int = 10, n_candidates: int = 100, weights=(1.0, 1.0),
@@ -338,3 +355,11 @@ class BGEM3Model:
             order = np.lexsort((np.arange(len(s)), -s))[:top_k]
             out.append(([str(cand[i]) for i in order], s[order].astype(np.float32)))
         return out
+
+    def retrieve_sparse(self, queries, sparse_index, top_k: int = 10, max_length: int = 512) -> List[Tuple[List[str], List[float]]]:
+        """Per query the best ``top_k`` stored passages by lexical matching score, exact, over the whole ``sparse_index`` (``SparseIndexer.search_knn``): the
+        query's ``lexical_weights`` against the stored ones (rounded to float16).  A passage that shares no token with the query is no result."""
+        if isinstance(queries, str):
+            queries = [queries]
+        q = self.encode(list(queries), max_length=max_length, return_dense=False, return_sparse=True, return_colbert_vecs=False)
+        return sparse_index.search_knn(q["lexical_weights"], top_k)

@@ -10,15 +10,17 @@ reduces them over each sequence's rows.
 
 ``BertSpladeEncoder`` IS ``transformers.BertForMaskedLM`` (``from_pretrained`` / ``save_pretrained`` / ``.to()`` keep working, ``forward`` stays HF's own and
 returns token logits — that is what ``train()`` mode uses); ``forward_splade`` is the inference path, eval mode and GPU only, no CPU fallback.  ``SpladeModel`` is
-the user-facing object in the shape of ``BGEM3Model``: ``encode``, ``encode_dense``, ``compute_score``, ``rerank``.
+the user-facing object in the shape of ``BGEM3Model``: ``encode``, ``encode_dense``, ``compute_score``, ``rerank``, ``index_passages``, ``retrieve``.
 
 UNVERIFIED OFFLINE.  Neither naver's ``splade`` package nor ``sentence_transformers`` is a dependency of this project, and neither was at hand when this was
 written: the formula above is recalled from naver's ``Splade`` module and from sentence-transformers' ``SpladePooling("max")``, not checked against them.  The
 arithmetic under test is ``transformers.BertForMaskedLM(...).logits`` followed by that formula.  No SPLADE weights were available either: real-checkpoint numerics
 are unmeasured (``tools/checkpoint_check.py <dir>`` measures them).
 
-Not covered: DistilBERT- / RoBERTa-based MLM heads (refused by ``model_type``), SPLADE's sum pooling, an inverted index or any corpus pipeline over sparse
-vectors, FLOPS-regularised training.
+``index_passages`` / ``retrieve`` fill and search a ``sparse_index.SparseIndexer``: the ``[B, vocab]`` rows of a forward are compacted on the GPU and stored
+as float16 postings, a query is scored against every stored passage by ``libkirag_sparse.so``.
+
+Not covered: DistilBERT- / RoBERTa-based MLM heads (refused by ``model_type``), SPLADE's sum pooling, FLOPS-regularised training.
 """
 from __future__ import annotations
 
@@ -187,3 +189,35 @@ class SpladeModel:
         if top_k is not None:
             order = order[:top_k]
         return order, torch.from_numpy(s.astype(np.float32))[order]
+
+    # ---- exact retrieval over a resident sparse index (kirag_amd.retriever.sparse_index) ----
+    @torch.no_grad()
+    def index_passages(self, ids, passages: Sequence[str], sparse_index, batch_size: int = 64, max_length: int = 512) -> None:
+        """ONE forward per batch; its ``[B, vocab]`` block goes to ``sparse_index.index_block`` with the tokenizer's pad id skipped, as ``encode`` skips it: the
+        rows are compacted on the GPU and only the kept (term, float16 weight) entries visit the host.  Every id of the call is checked before the first
+        forward (not a decimal number, twice in the call, already stored: ``ValueError``, nothing indexed)."""
+        ids = list(ids)
+        if len(ids) != len(passages):
+            raise ValueError(f"{len(ids)} ids for {len(passages)} passages")
+        sparse_index.check_new_ids(ids)
+        tok = self._tokenizer()
+        for s in range(0, len(passages), batch_size):
+            enc = tok(list(passages[s:s + batch_size]), padding=True, truncation=True, max_length=max_length, return_tensors="pt")
+            block = self.model.forward_splade(enc["input_ids"], enc["attention_mask"], enc.get("token_type_ids"))
+            sparse_index.index_block(ids[s:s + batch_size], block, (tok.pad_token_id,))
+
+    def retrieve(self, queries, sparse_index, top_k: int = 10, max_length: int = 512) -> List[Tuple[List[str], List[float]]]:
+        """Per query the best ``top_k`` stored passages by the dot product of the two sparse vectors, exact, over the whole index
+        (``SparseIndexer.search_knn``'s shape): the query's fp32 weights (pad id skipped) against the stored float16 ones.  A passage that shares no term with
+        the query is no result."""
+        if isinstance(queries, str):
+            queries = [queries]
+        pad = self._tokenizer().pad_token_id
+        vecs = self.encode_dense(list(queries), max_length=max_length).float().cpu().numpy()
+        sparse = []
+        for v in vecs:
+            idx = np.flatnonzero(v > 0)
+            if pad is not None:
+                idx = idx[idx != pad]
+            sparse.append((idx.astype(np.int32), v[idx]))
+        return sparse_index.search_knn(sparse, top_k)
