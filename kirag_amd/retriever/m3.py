@@ -5,7 +5,8 @@ ReLU) and a normalised vector per token (``colbert_linear``, H -> P, scored by M
 sub-modules: ``named_parameters()`` carries ``colbert_linear.{weight,bias}`` / ``sparse_linear.{weight,bias}`` through the ordinary weight sync, and
 ``forward_m3`` asks the library for the extra blocks (``KR_POOL_WITH_SPARSE`` / ``KR_POOL_WITH_COLBERT``, ``include/kirag_amd.h``).  ``BGEM3Model`` is the
 user-facing object: ``encode``, ``compute_score``, ``rerank``, and — over an ``Indexer`` and a ``late.MultiVectorStore`` — ``index_passages`` / ``retrieve``;
-over a ``sparse_index.SparseIndexer``, ``retrieve_sparse``.
+over a ``sparse_index.SparseIndexer``, ``retrieve_sparse``; over all three, ``retrieve_hybrid`` (the weighted ``colbert+sparse+dense`` of the dense top-n, from the
+stored forms) and ``retrieve_rrf`` (rank fusion of the dense and the sparse ranking, ``fusion.rrf``).
 
 UNVERIFIED OFFLINE.  FlagEmbedding is not a dependency of this project and was not at hand when this was written: the arithmetic below is THIS PROJECT'S
 definition, recalled from ``FlagEmbedding.BGEM3FlagModel``, not checked against it.  The recalled points:
@@ -363,3 +364,66 @@ class BGEM3Model:
             queries = [queries]
         q = self.encode(list(queries), max_length=max_length, return_dense=False, return_sparse=True, return_colbert_vecs=False)
         return sparse_index.search_knn(q["lexical_weights"], top_k)
+
+    # ---- all three stored forms: dense top-n, then the exact sparse score and MaxSim of those n (sparse_index.score_pairs, store.maxsim) ----
+    def retrieve_hybrid(self, queries, indexer, store, sparse_index, top_k: int = 10, n_candidates: int = 100, weights=(1.0, 1.0, 1.0),
+                        max_length: int = 512) -> List[Tuple[List[str], np.ndarray]]:
+        """``compute_score``'s ``colbert+sparse+dense`` over the stored forms.  ONE flagged forward encodes the queries (dense, sparse and colbert together);
+        per query ``indexer.search_knn`` gives ``n_candidates`` ids (at most the index's size) with their exact dense scores, ``sparse_index.score_pairs``
+        gives those passages' lexical matching scores against the stored (float16) weights and ``store.maxsim`` their MaxSim, each in one launch for all
+        queries.  The best ``top_k`` by (combined descending, dense rank ascending) come back as ``(ids, float32 scores)``; combined =
+        ``(w_d dense + w_s sparse + w_c colbert) / (w_d + w_s + w_c)`` in float64, ``weights = (w_d, w_s, w_c)``.  ``store=None`` gives ``sparse+dense``:
+        ``(w_d dense + w_s sparse) / (w_d + w_s)``, ``w_c`` is ignored and the colbert head is not asked for.  An empty index, or ``n_candidates <= 0``, gives
+        every query an empty result.  A candidate that one container lacks raises that container's ``KeyError`` before any scoring launch."""
+        if isinstance(queries, str):
+            queries = [queries]
+        wd, ws, wc = (float(w) for w in weights)
+        n = min(int(n_candidates), int(indexer.index.ntotal))
+        if n <= 0:
+            return [([], np.empty(0, np.float32)) for _ in queries]
+        q = self.encode(list(queries), max_length=max_length, return_dense=True, return_sparse=True, return_colbert_vecs=store is not None)
+        hits = indexer.search_knn(q["dense_vecs"], n, verbose=False)
+        cands = [h[0] for h in hits]
+        for c in cands:                           # both containers know every candidate before either scores
+            sparse_index.rows_of(c)
+            if store is not None:
+                store._rows(c)
+        sparse = sparse_index.score_pairs(q["lexical_weights"], cands)
+        colbert = store.maxsim(q["colbert_vecs"], cands, reduce="mean") if store is not None else [None] * len(cands)
+        out = []
+        for (cand, dense), sp, col in zip(hits, sparse, colbert):
+            if col is None:
+                s = (wd * np.asarray(dense, np.float64) + ws * sp.astype(np.float64)) / (wd + ws)
+            else:
+                s = (wd * np.asarray(dense, np.float64) + ws * sp.astype(np.float64) + wc * col.astype(np.float64)) / (wd + ws + wc)
+            order = np.lexsort((np.arange(len(s)), -s))[:top_k]
+            out.append(([str(cand[i]) for i in order], s[order].astype(np.float32)))
+        return out
+
+    def retrieve_rrf(self, queries, indexer, sparse_index, top_k: int = 10, n_candidates: int = 100, k: float = 60.0,
+                     store=None) -> List[Tuple[List[str], np.ndarray]]:
+        """Reciprocal rank fusion (``fusion.rrf``, constant ``k``) of the dense top-``n_candidates`` ranking (``indexer.search_knn``) and the sparse
+        top-``n_candidates`` ranking (``sparse_index.search_knn``; at most 1024).  With a ``store`` a third ranking enters: MaxSim (``reduce="mean"``) over
+        the union of the two lists — the dense list, then the sparse ids it lacks — ordered by (colbert descending, position in the union ascending), so a
+        candidate only the sparse search found reaches the multi-vector head without a dense score.  Per query ``(ids, float64 scores)`` as ``rrf`` gives
+        them, the best ``top_k``.  ``n_candidates <= 0`` gives every query an empty result."""
+        from .fusion import rrf
+        if isinstance(queries, str):
+            queries = [queries]
+        n = int(n_candidates)
+        if n <= 0:
+            return [([], np.empty(0, np.float64)) for _ in queries]
+        q = self.encode(list(queries), max_length=512, return_dense=True, return_sparse=True, return_colbert_vecs=store is not None)
+        nd = min(n, int(indexer.index.ntotal))
+        dense = [h[0] for h in indexer.search_knn(q["dense_vecs"], nd, verbose=False)] if nd > 0 else [[] for _ in queries]
+        sparse = [h[0] for h in sparse_index.search_knn(q["lexical_weights"], n)]
+        rankings = [[[str(i) for i in d], [str(i) for i in s]] for d, s in zip(dense, sparse)]
+        if store is not None:
+            unions = []
+            for d, s in rankings:
+                have = set(d)
+                unions.append(d + [i for i in s if i not in have])
+            for r, u, col in zip(rankings, unions, store.maxsim(q["colbert_vecs"], unions, reduce="mean")):
+                order = np.lexsort((np.arange(len(col)), -col.astype(np.float64)))
+                r.append([u[i] for i in order])
+        return [rrf(r, k=k, top_k=top_k) for r in rankings]

@@ -11,6 +11,12 @@
     of a ``[blocks, V + 1]`` tensor.  The inversion runs on the host in numpy and is incremental: a block is inverted once, when its R-th row arrives, and
     uploaded; only the open tail block is inverted again, lazily at the next search after an add.
 
+  * lazily, a device mirror of the forward form (``terms`` int32 and ``weights`` float16, grown by doubling; ``row_off`` stays on the host): nothing is
+    uploaded until the first ``score_pairs`` call, and then only the suffix added since the last one.  An index that is only searched never holds it.
+
+``score_pairs`` / ``rerank`` score given (query, id) pairs against the stored rows without scanning the index (``kp_sparse_dot``, ``libkirag_pairs.so``,
+``include/kirag_pairs.h``): the same definition, so wherever ``search_knn`` returns an id, ``score_pairs`` gives it the same score bits.
+
 ``search_knn`` scores on the GPU and only there (``ks_search``: exact, in the summation order the header defines).  An index on ``"cpu"`` stores, returns,
 saves and loads but refuses to search: there is no torch scoring path.
 
@@ -42,7 +48,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .. import _sparse_lib
+from .. import _pairs_lib, _sparse_lib
 
 INDEX_FILE = "sparse_index.ksparse"
 MAGIC = b"KSPARSE1"
@@ -104,6 +110,8 @@ class SparseIndexer:
         self._post_off = [0]          # per closed block, plus the tail's end once the tail is inverted
         self._closed = 0              # blocks inverted for good
         self._tail_rows = 0           # rows of the open tail block that _post / _ptr reflect
+        self._d_terms = self._d_weights = None      # the device mirror of the forward form, made by the first score_pairs
+        self._synced = 0              # entries of _terms / _weights the mirror reflects
 
     # ---- the host truth ----
     @property
@@ -294,6 +302,7 @@ class SparseIndexer:
             self._closed = keep // R
         del self._post_off[self._closed + 1:]
         self._tail_rows = 0
+        self._synced = min(self._synced, self.nnz)      # the entries behind are overwritten by the next add
 
     # ---- the inverted form ----
     def _invert_into(self, b: int, r0: int, r1: int) -> None:
@@ -368,6 +377,90 @@ class SparseIndexer:
             n = int((r >= 0).sum())
             out.append(([str(i) for i in self._ids[r[:n]].tolist()], s[:n].tolist()))
         return out
+
+    # ---- scoring given (query, id) pairs (GPU only) ----
+    def _sync_mirror(self) -> None:
+        """bring the device mirror of the forward form up to date: upload the entries added since the last call"""
+        nnz = self.nnz
+        if self._d_terms is None or nnz > self._d_terms.shape[0]:
+            cap = max(int(self._d_terms.shape[0]) if self._d_terms is not None else 0, 1 << 16)
+            while cap < nnz:
+                cap *= 2
+            terms = torch.empty(cap, dtype=torch.int32, device=self.device)
+            weights = torch.empty(cap, dtype=torch.float16, device=self.device)
+            if self._synced:
+                terms[:self._synced] = self._d_terms[:self._synced]
+                weights[:self._synced] = self._d_weights[:self._synced]
+            self._d_terms, self._d_weights = terms, weights
+        if nnz > self._synced:
+            a = self._synced
+            self._d_terms[a:nnz] = torch.from_numpy(self._terms[a:nnz]).to(self.device)
+            self._d_weights[a:nnz] = torch.from_numpy(self._weights[a:nnz]).to(self.device)
+            self._synced = nnz
+
+    def rows_of(self, ids) -> np.ndarray:
+        """the rows of stored ids as int64; an unknown id raises ``KeyError``"""
+        ids = list(ids)
+        try:
+            return np.fromiter((self._row_of[int(i)] for i in ids), dtype=np.int64, count=len(ids))
+        except KeyError as e:
+            raise KeyError(f"id {e.args[0]} is not in the index") from None
+        except ValueError:
+            bad = next(i for i in ids if not str(i).strip().lstrip("+-").isdigit())
+            raise KeyError(f"id {bad} is not in the index") from None
+
+    def score_pairs(self, queries, candidates) -> List[np.ndarray]:
+        """``queries``: as ``search_knn`` takes them; ``candidates``: per query a list of ids.  One fp32 array of scores per query, in the order of its ids:
+        the score ``search_knn`` would give that passage (same bits), ``+0.0`` when it shares no term with the query.  A length mismatch raises ``ValueError``
+        and an unknown id ``KeyError`` before anything is launched; an index on the CPU raises ``RuntimeError``."""
+        queries, candidates = list(queries), list(candidates)
+        if len(queries) != len(candidates):
+            raise ValueError(f"{len(queries)} queries, {len(candidates)} candidate lists")
+        return self.score_rows(queries, [self.rows_of(c) for c in candidates])
+
+    def score_rows(self, queries, rows) -> List[np.ndarray]:
+        """``score_pairs`` for a caller that holds row numbers (insertion order, as ``search_arrays`` returns them) instead of ids: per query an int64 array of
+        rows.  A row outside ``[0, ntotal)`` is refused by the library by name."""
+        queries, rows = list(queries), [np.ascontiguousarray(r, np.int64).reshape(-1) for r in rows]
+        if len(queries) != len(rows):
+            raise ValueError(f"{len(queries)} queries, {len(rows)} row lists")
+        if self.device.type != "cuda":
+            raise RuntimeError("SparseIndexer.score_pairs runs on the GPU (libkirag_pairs.so): this index is on the CPU and there is no torch scoring path")
+        q_off, q_term, q_w = self._queries_csr(queries)
+        sizes = [len(r) for r in rows]
+        npairs = int(sum(sizes))
+        if npairs == 0:
+            return [np.empty(0, np.float32) for _ in rows]
+        pair_q = np.repeat(np.arange(len(rows), dtype=np.int64), sizes)
+        pair_row = np.ascontiguousarray(np.concatenate(rows))
+        first = np.zeros(len(rows) + 1, np.int64)           # the first pair of each query
+        np.cumsum(sizes, out=first[1:])
+        lib = _pairs_lib.load()
+        self._sync_mirror()
+        with torch.cuda.device(self.device):
+            out = torch.empty(npairs, dtype=torch.float32, device=self.device)
+            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+            for s in range(0, len(rows), _pairs_lib.MAX_QUERIES):              # the library's bounds per call: queries, then pairs
+                e = min(len(rows), s + _pairs_lib.MAX_QUERIES)
+                off = np.ascontiguousarray(q_off[s:e + 1] - q_off[s])
+                a = int(q_off[s])
+                for p0 in range(int(first[s]), int(first[e]), _pairs_lib.MAX_PAIRS):
+                    p1 = min(int(first[e]), p0 + _pairs_lib.MAX_PAIRS)
+                    pq = np.ascontiguousarray(pair_q[p0:p1] - s)
+                    _pairs_lib.check(lib.kp_sparse_dot(self._d_terms.data_ptr(), self._d_weights.data_ptr(), self.nnz, self._row_off.ctypes.data, self._n,
+                                                       self.vocab_size, off.ctypes.data, e - s, q_term[a:].ctypes.data, q_w[a:].ctypes.data, pq.ctypes.data,
+                                                       pair_row[p0:].ctypes.data, p1 - p0, out[p0:].data_ptr(), self.device.index, stream))
+            flat = out.cpu().numpy()
+        return np.split(flat, first[1:-1])
+
+    def rerank(self, query, candidate_ids, top_k: Optional[int] = None) -> Tuple[List[str], np.ndarray]:
+        """``(ids, scores)`` of the best ``top_k`` candidates (all when ``None``) by (score descending, position in ``candidate_ids`` ascending)"""
+        cand = list(candidate_ids)
+        s = self.score_pairs([query], [cand])[0]
+        order = np.lexsort((np.arange(len(s)), -s.astype(np.float64)))
+        if top_k is not None:
+            order = order[:top_k]
+        return [str(int(cand[i])) for i in order], s[order]
 
     # ---- files ----
     def serialize(self, dir_path) -> None:
